@@ -7,14 +7,18 @@ cuda/LNW/LinearNeedlemanWunschV12.cu:487-491) on a 10k-pair 1024x1024 LinearSmit
 the int32 scores to rank 0 per step).  A "step" = one DP fill of the whole resident batch, int16 score matrix
 written to HBM, + that gather.  Inputs are resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]            # N=1
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]            # N=1
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
-  "roofline":     algorithmic HBM bytes per fill / mean fill-kernel time (HIP events on the launch stream)
-  "cpu_baseline": the reference's own CPU classes (oracle/_ref, built from /root/reference in the build
-                  container) or, if that binary is absent, the C oracle port -- timed on this host's cores on a
-                  bounded sample of the same batch.  Reported beside the GPU number, never measured as it.
+Prints ONE JSON line on rank 0: metric / value / unit / higher_is_better / dtype / ms_per_step (wall time of the K
+timed steps / K) and the workload's config.  A plain run does only what that headline needs; --full adds
+  "roofline":     algorithmic HBM bytes per fill / mean fill-kernel time (HIP events around every timed fill)
+  "ranks":        every rank's fill-kernel ms, matrix-pool record and score checksum (rank 0 checks the gather)
+  "cpu_baseline": the reference's own CPU classes (oracle/_ref, built by oracle/Makefile `make ref` where the
+                  reference sources are present) or, if that binary is absent, the C oracle port -- timed on this
+                  host's cores on a bounded sample of the same batch.  Reported beside the GPU number, never measured as it.
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy: scores and end cells of every pair
+(float64) and the score matrices of a seeded sample of pairs (float32).  Inputs are seeded, so equal arguments give equal inputs.
 """
 from __future__ import annotations
 
@@ -46,6 +50,9 @@ WORKLOADS = {
     "anw_100k_short": ("ANW", 100000, 0, 0, 3, -1, -3, -1, 6),
 }
 BAND = 128
+DUMP_PAIRS = 4  # --dump-outputs: score matrices of this many pairs (seeded choice)
+DUMP_MAX_CELLS = 1_100_000  # a matrix with more cells (banded 4096 x 4096) is dumped as a seeded sample of this many cells
+DUMP_MAX_BYTES = 64 << 20
 
 
 def kernel_source_hash() -> str:
@@ -77,6 +84,35 @@ def pool_record(desc: dict) -> dict:
     return {"mode": desc["pool"], "bytes": nbytes, "chunk_mb": int(desc.get("pool_chunk_mb", 0)), "candidates_memset_ms": ms,
             "candidates_fill_ms": fills, "candidates_kind": kinds, "kept": kept,
             "memset_tbps": round(nbytes / (ms[kept] * 1e-3) / 1e12, 3) if len(ms) > kept and ms[kept] > 0 else None}
+
+
+def dump_outputs(out_dir, batch, algo_name, gathered=None):
+    """What the last fill computed, as a caller receives it: score and end cell of every pair (dpx_batch_results) and the int16
+    score matrices (dpx_batch_matrix; H, and I / D of the affine algorithm) of DUMP_PAIRS seeded pairs, every value exact in the
+    float type it is stored in.  `gathered`: the score vector rank 0 received from the gather (N > 1)."""
+    import numpy as np
+
+    import dpx_gpu_genomics_project_amd as dpx
+
+    scores, end_row, end_col = batch.results()
+    arrays = {"scores": scores, "end_row": end_row, "end_col": end_col}
+    if gathered is not None:
+        arrays["gathered_scores"] = gathered
+    arrays = {k: np.asarray(v, np.float64) for k, v in arrays.items()}
+    pairs = np.sort(np.random.default_rng(0).choice(batch.num_pairs, min(DUMP_PAIRS, batch.num_pairs), replace=False))
+    arrays["matrix_pairs"] = pairs.astype(np.float64)
+    kinds = [("H", dpx.MAT_H)] + ([("I", dpx.MAT_I), ("D", dpx.MAT_D)] if algo_name == "ANW" else [])
+    for p in pairs:
+        for tag, which in kinds:
+            mat = batch.matrix(int(p), which).astype(np.float32)
+            if mat.size > DUMP_MAX_CELLS:  # flat indices of the sample, ascending, seeded by the pair
+                mat = mat.ravel()[np.sort(np.random.default_rng(int(p)).choice(mat.size, DUMP_MAX_CELLS, replace=False))]
+            arrays[f"matrix_{tag}_pair{p}"] = mat
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def cpu_baseline(sb, algo_name, match, mismatch, gap_open, gap_extend, budget_pairs, shape):
@@ -161,7 +197,13 @@ def main():
     ap.add_argument("--share-gpu", action="store_true", help="all ranks use cuda:0 (rehearsal only; RCCL refuses this)")
     ap.add_argument("--dump-scores", default="", help="tests: every rank saves its local scores to PREFIX.rank<r>.npy, rank 0 "
                     "the gathered vector to PREFIX.gathered.npy (after the timed region)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps rank 0 writes what the last step "
+                    "computed as DIR/<name>.npy (float64 / float32, at most 64 MB)")
+    ap.add_argument("--full", action="store_true", help="also the roofline and per-rank figures (HIP events around every timed "
+                    "fill), the result checks and the CPU baseline; a plain run measures the headline only")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -250,53 +292,66 @@ def main():
     for _ in range(args.warmup):
         step()
     fence()
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+    # --full: HIP events around every timed fill for the per-kernel / roofline figures; a plain run launches the steps alone
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)] if args.full else None
+    last = None
     t0 = time.perf_counter()
     for k in range(args.steps):
-        ev[k][0].record()
+        if ev:
+            ev[k][0].record()
         batch.fill(stream)
-        ev[k][1].record()
+        if ev:
+            ev[k][1].record()
         if world > 1:
             last = exchange()
     fence()
     elapsed = time.perf_counter() - t0
-    kernel_ms = sum(a.elapsed_time(b) for a, b in ev) / max(args.steps, 1)
-    local_kernel_ms = kernel_ms
 
     red_dev = scores_t.device if args.backend == "nccl" else torch.device("cpu")
     t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
-    kt = torch.tensor([kernel_ms], dtype=torch.float64, device=red_dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dist.all_reduce(kt, op=dist.ReduceOp.MAX)
-    elapsed, kernel_ms = float(t.item()), float(kt.item())
+    elapsed = float(t.item())
 
-    # sanity on results (outside the timed region): a few pairs against the closed-form identical-pair score
-    scores, er, ec = batch.results()
-    ident = [p for p in range(npairs) if (rank * npairs + p) % 101 == 100][:4]
-    for p in ident if m else []:
-        assert scores[p] == match * min(m, n), "identical pair must score match*len"
-    # Every rank reports its own fill time, pool record and a checksum of its LOCAL scores; rank 0 checks the gathered vector
-    # against every rank's checksum (not only its own slice), so the first run on N real GPUs verifies the collective itself.
-    def checksum(vec) -> int:
-        v = np.asarray(vec, dtype=np.int64)
-        return int((v * (np.arange(v.size, dtype=np.int64) % 1021 + 1)).sum() & 0x7FFFFFFFFFFF)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, batch, algo_name, last.cpu().numpy() if last is not None else None)
 
-    mine = {"rank": rank, "device": local_rank, "pairs": int(npairs), "kernel_ms": round(local_kernel_ms, 4),
-            "pool": pool_record(batch.describe()), "scores_checksum": checksum(scores)}
-    ranks = [mine]
-    if world > 1:
-        ranks = [None] * world
-        dist.all_gather_object(ranks, mine)
-    if world > 1 and rank == 0:  # the gathered vector must carry every rank's scores in rank order
-        assert last is not None and last.numel() == sum(r["pairs"] for r in ranks)
-        g = last.cpu().numpy()
-        off = 0
-        for r in ranks:
-            r["gathered_ok"] = checksum(g[off:off + r["pairs"]]) == r["scores_checksum"]
-            off += r["pairs"]
-        assert torch.equal(last[:npairs].cpu(), torch.from_numpy(scores))
-        assert all(r["gathered_ok"] for r in ranks), [r for r in ranks if not r["gathered_ok"]]
+    if args.full:
+        kernel_ms = sum(a.elapsed_time(b) for a, b in ev) / args.steps
+        local_kernel_ms = kernel_ms
+        kt = torch.tensor([kernel_ms], dtype=torch.float64, device=red_dev)
+        if world > 1:
+            dist.all_reduce(kt, op=dist.ReduceOp.MAX)
+        kernel_ms = float(kt.item())
+
+    if args.full or args.dump_scores:
+        scores, er, ec = batch.results()
+    if args.full:
+        # sanity on results (outside the timed region): a few pairs against the closed-form identical-pair score
+        ident = [p for p in range(npairs) if (rank * npairs + p) % 101 == 100][:4]
+        for p in ident if m else []:
+            assert scores[p] == match * min(m, n), "identical pair must score match*len"
+        # Every rank reports its own fill time, pool record and a checksum of its LOCAL scores; rank 0 checks the gathered vector
+        # against every rank's checksum (not only its own slice), so the first run on N real GPUs verifies the collective itself.
+        def checksum(vec) -> int:
+            v = np.asarray(vec, dtype=np.int64)
+            return int((v * (np.arange(v.size, dtype=np.int64) % 1021 + 1)).sum() & 0x7FFFFFFFFFFF)
+
+        mine = {"rank": rank, "device": local_rank, "pairs": int(npairs), "kernel_ms": round(local_kernel_ms, 4),
+                "pool": pool_record(batch.describe()), "scores_checksum": checksum(scores)}
+        ranks = [mine]
+        if world > 1:
+            ranks = [None] * world
+            dist.all_gather_object(ranks, mine)
+        if world > 1 and rank == 0:  # the gathered vector must carry every rank's scores in rank order
+            assert last is not None and last.numel() == sum(r["pairs"] for r in ranks)
+            g = last.cpu().numpy()
+            off = 0
+            for r in ranks:
+                r["gathered_ok"] = checksum(g[off:off + r["pairs"]]) == r["scores_checksum"]
+                off += r["pairs"]
+            assert torch.equal(last[:npairs].cpu(), torch.from_numpy(scores))
+            assert all(r["gathered_ok"] for r in ranks), [r for r in ranks if not r["gathered_ok"]]
 
     if args.dump_scores:
         np.save(f"{args.dump_scores}.rank{rank}.npy", scores)
@@ -311,18 +366,6 @@ def main():
         dtype = desc["dtype"]
         total_cells = info["cells"] * world
         value = total_cells * args.steps / elapsed / 1e9
-        achieved = info["algorithmic_bytes"] / (kernel_ms * 1e-3) / 1e9
-        # HBM bytes per fill from the PMC passes of tools/profile_all.sh (rocprofv3 --pmc WRITE_SIZE / FETCH_SIZE, separate runs),
-        # recorded together with a hash of the kernel sources: a figure measured on other kernels is reported as stale
-        traffic, traffic_stale = None, None
-        prof = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(prof):
-            try:
-                rec = json.load(open(prof))
-                traffic = rec.get("workloads", {}).get(args.workload)
-                traffic_stale = rec.get("kernel_source_sha256") != kernel_source_hash()
-            except Exception:
-                traffic = None
         out = {
             "metric": "GCUPS", "value": round(value, 2), "unit": "GCUPS", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
@@ -336,27 +379,40 @@ def main():
                        "cells_per_gpu": info["cells"], "matrix_bytes_per_gpu": info["matrix_bytes"],
                        "precondition_fills": precondition_fills, "kernel": desc["kernel"],
                        "rows_per_lane": desc["rows_per_lane"]},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_stale": traffic_stale,
-                         "kernel_ms": round(kernel_ms, 4), "algorithmic_bytes_per_launch": info["algorithmic_bytes"],
-                         "kernel_gcups": round(info["cells"] / (kernel_ms * 1e-3) / 1e9, 1),
-                         "pool": pool_record(desc)},
         }
-        # what a caller WITHOUT DPX_TUNE_PLACEMENT gets: the first pool the engine built (candidate 0 of the shopping), timed by the
-        # engine with the same fill (3 launches) before the other candidates existed -- the product-representative figure beside the shopped one
-        pool = out["roofline"]["pool"] or {}
-        if pool.get("candidates_fill_ms"):
-            first_ms = pool["candidates_fill_ms"][0]
-            out["roofline"]["kernel_ms_first_pool"] = first_ms
-            out["roofline"]["frac_first_pool"] = round(info["algorithmic_bytes"] / (first_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if first_ms > 0 else None
-        if algo_name == "BSW":  # GCUPS counts refLen x queryLen as the reference does; also give the in-band rate
-            inband = (info["algorithmic_bytes"] - npairs * (m + n + 28)) // 2
-            out["roofline"]["in_band_cells_per_launch"] = inband
-            out["roofline"]["in_band_kernel_gcups"] = round(inband / (kernel_ms * 1e-3) / 1e9, 1)
-        out["ranks"] = ranks  # per rank: fill-kernel ms, matrix-pool record, checksum of its scores (+ gathered_ok on rank 0's check)
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(sb, algo_name, match, mismatch, gap_open, gap_extend,
-                                               args.cpu_pairs if m else npairs, shape)
+        if args.full:
+            achieved = info["algorithmic_bytes"] / (kernel_ms * 1e-3) / 1e9
+            # HBM bytes per fill from the PMC passes of tools/profile_all.sh (rocprofv3 --pmc WRITE_SIZE / FETCH_SIZE, separate runs),
+            # recorded together with a hash of the kernel sources: a figure measured on other kernels is reported as stale
+            traffic, traffic_stale = None, None
+            prof = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(prof):
+                try:
+                    rec = json.load(open(prof))
+                    traffic = rec.get("workloads", {}).get(args.workload)
+                    traffic_stale = rec.get("kernel_source_sha256") != kernel_source_hash()
+                except Exception:
+                    traffic = None
+            out["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_stale": traffic_stale,
+                               "kernel_ms": round(kernel_ms, 4), "algorithmic_bytes_per_launch": info["algorithmic_bytes"],
+                               "kernel_gcups": round(info["cells"] / (kernel_ms * 1e-3) / 1e9, 1),
+                               "pool": pool_record(desc)}
+            # what a caller WITHOUT DPX_TUNE_PLACEMENT gets: the first pool the engine built (candidate 0 of the shopping), timed by the
+            # engine with the same fill (3 launches) before the other candidates existed -- the product-representative figure beside the shopped one
+            pool = out["roofline"]["pool"] or {}
+            if pool.get("candidates_fill_ms"):
+                first_ms = pool["candidates_fill_ms"][0]
+                out["roofline"]["kernel_ms_first_pool"] = first_ms
+                out["roofline"]["frac_first_pool"] = round(info["algorithmic_bytes"] / (first_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if first_ms > 0 else None
+            if algo_name == "BSW":  # GCUPS counts refLen x queryLen as the reference does; also give the in-band rate
+                inband = (info["algorithmic_bytes"] - npairs * (m + n + 28)) // 2
+                out["roofline"]["in_band_cells_per_launch"] = inband
+                out["roofline"]["in_band_kernel_gcups"] = round(inband / (kernel_ms * 1e-3) / 1e9, 1)
+            out["ranks"] = ranks  # per rank: fill-kernel ms, matrix-pool record, checksum of its scores (+ gathered_ok on rank 0's check)
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(sb, algo_name, match, mismatch, gap_open, gap_extend,
+                                                   args.cpu_pairs if m else npairs, shape)
         print(json.dumps(out), flush=True)
     batch.close()
     if world > 1:

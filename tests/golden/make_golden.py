@@ -14,6 +14,8 @@ Outputs are data only (inputs + expected outputs):
                                 python/LinearBandedSmithWaterman.py (its C++/CUDA twins are broken upstream)
   fakedpx_kat.json              the known answers asserted by the reference's c++/testFakeDPX.cpp:10-113,
                                 re-evaluated through the compiled FakeDPX class (op, a, b, c, result, pred)
+  oracle_vs_ref.json            what the reference classes compute for the inputs of tests/test_oracle_vs_ref.py
+                                (test_oracle_vs_ref.record(); alone: python tests/golden/make_golden.py oracle_vs_ref)
 """
 import gzip
 import json
@@ -150,7 +152,16 @@ def main():
         kat.append({"op": op, "a": a & 0xFFFFFFFF, "b": b & 0xFFFFFFFF, "c": c & 0xFFFFFFFF, "result": int(r), "pred": int(p)})
     json.dump(kat, open(os.path.join(HERE, "fakedpx_kat.json"), "w"), indent=0)
     print("wrote", len(cases), "matrix cases,", len(banded), "banded cases,", len(kat), "FakeDPX known answers")
+    oracle_vs_ref()
+
+
+def oracle_vs_ref():
+    assert O.have_ref(), "build oracle/_ref first (make -C oracle ref)"
+    import test_oracle_vs_ref as V
+
+    json.dump(V.record(), open(V.GOLDEN, "w"), separators=(",", ":"))
+    print("wrote", V.GOLDEN)
 
 
 if __name__ == "__main__":
-    main()
+    oracle_vs_ref() if sys.argv[1:] == ["oracle_vs_ref"] else main()

@@ -31,7 +31,7 @@ def _torchrun_bench(tmp_path, world, extra):
     prefix = str(tmp_path / "scores")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--backend", "gloo", "--share-gpu",
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--dump-scores", prefix] + extra
+           "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--dump-scores", prefix] + extra
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:] + r.stdout[-1000:]

@@ -1,14 +1,18 @@
-"""Pin the oracle: the C restatement (oracle/dpx_oracle.c) against the REAL reference classes compiled from
-/root/reference into oracle/_ref/ (oracle/Makefile `make ref`).  Runs only where oracle/_ref exists (the build
-container, or the GPU box when the prebuilt _ref travelled with the repo); the committed fixtures in
-tests/golden/ carry the same evidence everywhere else (tests/test_oracle_golden.py)."""
+"""Pin the oracle: the C restatement (oracle/dpx_oracle.c) against the REAL reference classes.  Everywhere, against what those
+classes computed for exactly these inputs, recorded in tests/golden/oracle_vs_ref.json (score, CRC32 of every matrix and of the
+printed lines, the DPX primitives' answers; tests/golden/make_golden.py).  Where oracle/_ref was built (oracle/Makefile
+`make ref`), also against the live reference classes, matrix by matrix, and the record against them."""
+import json
+import os
+import zlib
+
 import numpy as np
 import pytest
 
 import oracle_py as O
 from dpx_gpu_genomics_project_amd.synth import make_batch, make_ragged_batch
 
-pytestmark = pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built (no /root/reference here)")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oracle_vs_ref.json")
 
 
 def _cases():
@@ -26,48 +30,10 @@ def _cases():
 
 
 WEIGHTS = [(3, -1, -2), (5, -2, -3), (1, -1, -1), (2, -3, -1)]
+ANW_WEIGHTS = [(3, -1, -3, -1), (5, -2, -4, -1), (1, -1, -2, -2), (2, -2, 0, -1)]
 
 
-@pytest.mark.parametrize("w", WEIGHTS)
-def test_lsw_matches_reference(w):
-    for refs, qry in _cases():
-        o = O.lsw(refs, qry, *w)
-        r = O.ref_lsw(refs, qry, *w)
-        assert np.array_equal(o.H, r.H)
-        assert o.score == r.score
-        # directions only matter where H > 0 (the reference never reads them elsewhere)
-        mask = o.H > 0
-        assert np.array_equal(o.dir[mask], r.dir[mask])
-        a, b, c = O.lsw_traceback(refs, qry, o)
-        expect = f"0 | {o.score}\n" + ("\n\n\n" if o.score == 0 else f"{a}\n{b}\n{c}\n")
-        assert r.text == expect
-
-
-@pytest.mark.parametrize("w", WEIGHTS)
-def test_lnw_matches_reference(w):
-    for refs, qry in _cases():
-        o = O.lnw(refs, qry, *w)
-        r = O.ref_lnw(refs, qry, *w)
-        assert np.array_equal(o.H, r.H)
-        assert np.array_equal(o.dir, r.dir)
-        assert o.score == r.score
-        a, b, c = O.lnw_traceback(refs, qry, o)
-        assert r.text == f"0 | {o.score}\n{a}\n{b}\n{c}\n"
-
-
-@pytest.mark.parametrize("w", [(3, -1, -3, -1), (5, -2, -4, -1), (1, -1, -2, -2), (2, -2, 0, -1)])
-def test_anw_matches_reference(w):
-    for refs, qry in _cases():
-        o = O.anw(refs, qry, *w)
-        r = O.ref_anw(refs, qry, *w)
-        for name in ("H", "I", "D", "dirH", "dirI", "dirD"):
-            assert np.array_equal(getattr(o, name), getattr(r, name)), name
-        assert o.score == r.score
-        a, b, c = O.anw_traceback(refs, qry, o)
-        assert r.text == f"0 | {o.score}\n{a}\n{b}\n{c}\n"
-
-
-def test_dpx_primitives_match_reference_model():
+def _dpx_inputs():
     rng = np.random.default_rng(11)
     vals = [0, 1, 2, 3, 0xFFFFFFFF, 0x7FFFFFFF, 0x80000000, 0x00FF00FF, 0xFF00FF00, 0xFFFF00FF, 0xFFFFFF00,
             0xFFFD00FF, 0xFFFE00FF, 0xFFFE01FF, 0xFFFF0001, 0x7FFF8000, 0x80007FFF]
@@ -75,12 +41,122 @@ def test_dpx_primitives_match_reference_model():
     for op in range(36):
         for _ in range(200):
             a, b, c = (vals[int(i)] for i in rng.integers(0, len(vals), 3))
-            want = O.ref_dpx(op, a, b, c)
-            got = O.dpx(op, a, b, c)
-            s16 = lambda v: (v & 0xFFFF) - 0x10000 if v & 0x8000 else v & 0xFFFF
-            if op == 1 and max(s16(a), s16(b), s16(c)) < 0:
-                # reference bug: __vimax3_s16x2 sign-extends a negative low half over the high half
-                # (c++/FakeDPX.cpp:28).  The oracle returns the mathematically correct halves.
-                assert got[0] & 0xFFFF == want[0] & 0xFFFF
-                continue
-            assert got == want, (op, hex(a), hex(b), hex(c))
+            yield op, a, b, c
+
+
+def _crc(a):
+    return zlib.crc32(np.ascontiguousarray(a, dtype="<i4").tobytes()) & 0xFFFFFFFF
+
+
+def _text_crc(text):
+    return zlib.crc32(text.encode("latin-1")) & 0xFFFFFFFF
+
+
+def _cases_crc():
+    return zlib.crc32(b"".join(len(r).to_bytes(4, "little") + r + len(q).to_bytes(4, "little") + q for r, q in _cases())) & 0xFFFFFFFF
+
+
+def _key(w):
+    return ",".join(map(str, w))
+
+
+# One digest per case, computed the same way from the oracle's and the reference's results.  LSW directions only matter where
+# H > 0 (the reference never reads them elsewhere).
+def _lsw_digest(r, text):
+    return [int(r.score), _crc(r.H), _crc(np.where(r.H > 0, r.dir, 0)), _text_crc(text)]
+
+
+def _lnw_digest(r, text):
+    return [int(r.score), _crc(r.H), _crc(r.dir), _text_crc(text)]
+
+
+def _anw_digest(r, text):
+    return [int(r.score)] + [_crc(getattr(r, name)) for name in ("H", "I", "D", "dirH", "dirI", "dirD")] + [_text_crc(text)]
+
+
+def record():
+    """What the reference classes (oracle/_ref/libref_shim.so) compute for every case and primitive: tests/golden/oracle_vs_ref.json."""
+    cases = _cases()
+    out = {"cases_crc": _cases_crc(), "lsw": {}, "lnw": {}, "anw": {}}
+    for w in WEIGHTS:
+        out["lsw"][_key(w)] = [_lsw_digest(r, r.text) for r in (O.ref_lsw(a, b, *w) for a, b in cases)]
+        out["lnw"][_key(w)] = [_lnw_digest(r, r.text) for r in (O.ref_lnw(a, b, *w) for a, b in cases)]
+    for w in ANW_WEIGHTS:
+        out["anw"][_key(w)] = [_anw_digest(r, r.text) for r in (O.ref_anw(a, b, *w) for a, b in cases)]
+    out["dpx"] = [[int(v) for v in O.ref_dpx(op, a, b, c)] for op, a, b, c in _dpx_inputs()]
+    return out
+
+
+@pytest.fixture(scope="module")
+def golden():
+    g = json.load(open(GOLDEN))
+    assert g["cases_crc"] == _cases_crc(), "the inputs differ from those recorded: regenerate with tests/golden/make_golden.py"
+    return g
+
+
+@pytest.mark.parametrize("w", WEIGHTS)
+def test_lsw_matches_reference(golden, w):
+    want = golden["lsw"][_key(w)]
+    for k, (refs, qry) in enumerate(_cases()):
+        o = O.lsw(refs, qry, *w)
+        a, b, c = O.lsw_traceback(refs, qry, o)
+        expect = f"0 | {o.score}\n" + ("\n\n\n" if o.score == 0 else f"{a}\n{b}\n{c}\n")
+        assert _lsw_digest(o, expect) == want[k], k
+        if O.have_ref():
+            r = O.ref_lsw(refs, qry, *w)
+            assert np.array_equal(o.H, r.H)
+            assert o.score == r.score
+            mask = o.H > 0
+            assert np.array_equal(o.dir[mask], r.dir[mask])
+            assert r.text == expect
+            assert _lsw_digest(r, r.text) == want[k], k
+
+
+@pytest.mark.parametrize("w", WEIGHTS)
+def test_lnw_matches_reference(golden, w):
+    want = golden["lnw"][_key(w)]
+    for k, (refs, qry) in enumerate(_cases()):
+        o = O.lnw(refs, qry, *w)
+        a, b, c = O.lnw_traceback(refs, qry, o)
+        expect = f"0 | {o.score}\n{a}\n{b}\n{c}\n"
+        assert _lnw_digest(o, expect) == want[k], k
+        if O.have_ref():
+            r = O.ref_lnw(refs, qry, *w)
+            assert np.array_equal(o.H, r.H)
+            assert np.array_equal(o.dir, r.dir)
+            assert o.score == r.score
+            assert r.text == expect
+            assert _lnw_digest(r, r.text) == want[k], k
+
+
+@pytest.mark.parametrize("w", ANW_WEIGHTS)
+def test_anw_matches_reference(golden, w):
+    want = golden["anw"][_key(w)]
+    for k, (refs, qry) in enumerate(_cases()):
+        o = O.anw(refs, qry, *w)
+        a, b, c = O.anw_traceback(refs, qry, o)
+        expect = f"0 | {o.score}\n{a}\n{b}\n{c}\n"
+        assert _anw_digest(o, expect) == want[k], k
+        if O.have_ref():
+            r = O.ref_anw(refs, qry, *w)
+            for name in ("H", "I", "D", "dirH", "dirI", "dirD"):
+                assert np.array_equal(getattr(o, name), getattr(r, name)), name
+            assert o.score == r.score
+            assert r.text == expect
+            assert _anw_digest(r, r.text) == want[k], k
+
+
+def test_dpx_primitives_match_reference_model(golden):
+    recorded = golden["dpx"]
+    for k, (op, a, b, c) in enumerate(_dpx_inputs()):
+        want = tuple(recorded[k])
+        if O.have_ref():
+            assert O.ref_dpx(op, a, b, c) == want, (op, hex(a), hex(b), hex(c))
+        got = O.dpx(op, a, b, c)
+        s16 = lambda v: (v & 0xFFFF) - 0x10000 if v & 0x8000 else v & 0xFFFF
+        if op == 1 and max(s16(a), s16(b), s16(c)) < 0:
+            # reference bug: __vimax3_s16x2 sign-extends a negative low half over the high half
+            # (c++/FakeDPX.cpp:28).  The oracle returns the mathematically correct halves.
+            assert got[0] & 0xFFFF == want[0] & 0xFFFF
+            continue
+        assert got == want, (op, hex(a), hex(b), hex(c))

@@ -5,6 +5,6 @@ A=$(realpath $1); B=$(realpath $2)
 for i in 1 2 3; do
   for L in $A $B; do
     printf "%s " $(basename $L)
-    DPX_LIB=$L python bench.py --no-cpu-baseline --steps 30 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['roofline']['kernel_ms'])"
+    DPX_LIB=$L python bench.py --full --no-cpu-baseline --steps 30 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['roofline']['kernel_ms'])"
   done
 done

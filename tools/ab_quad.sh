@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."
 for rep in 1 2; do
   for v in "" tools/bin/quad_exp1.so tools/bin/quad_exp2.so tools/bin/quad_nocompute.so; do
     for wl in ${WLS:-lnw_100k_short}; do
-      DPX_LIB=$v python3 bench.py --workload $wl --no-cpu-baseline --steps 100 2>/dev/null | python3 -c "
+      DPX_LIB=$v python3 bench.py --full --workload $wl --no-cpu-baseline --steps 100 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read()); print('${v:-shipped}', '$wl', d['value'], 'GCUPS', d['roofline']['kernel_ms'], 'ms')"
     done

@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."
 OUT=${1:-gpurun_out/all_workloads.jsonl}; : > $OUT
 for wl in lsw_10k_1024 lnw_10k_1024 lsw_1k_512 anw_1k_1024 bsw_10k_4096_b128 lnw_100k_short lsw_100k_short anw_100k_short; do
-  python3 bench.py --workload $wl --no-cpu-baseline 2>/dev/null >> $OUT
+  python3 bench.py --full --workload $wl --no-cpu-baseline 2>/dev/null >> $OUT
 done
 python3 - $OUT <<'PY'
 import sys, json

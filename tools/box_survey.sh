@@ -8,7 +8,7 @@ OUT=gpurun_out/box_survey_$(date +%s).txt
 ID=$(rocm-smi --showuniqueid 2>/dev/null | grep -i "unique id" | head -1 | awk '{print $NF}')
 [ -x tools/bin/clkprobe ] || hipcc --offload-arch=gfx950 -O2 tools/clkprobe.hip -o tools/bin/clkprobe 2>/dev/null
 CLK=$(tools/bin/clkprobe 2>/dev/null | tail -1 | sed 's/clkprobe rep 2: //')
-line() { python3 bench.py --workload $1 --no-cpu-baseline --steps 30 2>/dev/null | python3 -c "
+line() { python3 bench.py --full --workload $1 --no-cpu-baseline --steps 30 2>/dev/null | python3 -c "
 import sys,json
 d=json.loads(sys.stdin.read()); r=d['roofline']; p=r.get('pool') or {}
 print('$1', d['value'], 'GCUPS', r['kernel_ms'], 'ms frac', r['frac'], 'pool_fill_ms', p.get('candidates_fill_ms'), 'memset_ms', p.get('candidates_memset_ms'))"; }
@@ -16,7 +16,7 @@ print('$1', d['value'], 'GCUPS', r['kernel_ms'], 'ms frac', r['frac'], 'pool_fil
   echo "box $(hostname) gpu ${ID:-?} | $CLK"
   rocm-smi --showmaxpower --showperflevel 2>/dev/null | grep -E "Max Graphics Package Power|Performance Level" | head -2
   echo "-- idle:"; rocm-smi --showclocks --showpower --showtemp 2>/dev/null | grep -E "sclk|mclk|Graphics Package Power|junction" | head -4
-  python3 bench.py --workload lsw_10k_1024 --no-cpu-baseline --steps 2500 > /tmp/bs_long.json 2>/dev/null &
+  python3 bench.py --full --workload lsw_10k_1024 --no-cpu-baseline --steps 2500 > /tmp/bs_long.json 2>/dev/null &
   BP=$!
   sleep 5
   for k in 1 2 3; do echo "-- under the headline fill (sample $k):"; rocm-smi --showclocks --showpower --showtemp 2>/dev/null | grep -E "sclk|mclk|Graphics Package Power|junction" | head -4; sleep 1; done

@@ -3,7 +3,7 @@
 # one block of chunks) on THIS box (development aid): do the boxes on which the default is slow prefer another write pattern?
 mkdir -p gpurun_out
 OUT=gpurun_out/group_sweep_$(date +%s).txt
-run() { printf "%-40s " "[$1]"; env $1 python3 bench.py --workload ${2:-lsw_10k_1024} --no-cpu-baseline --steps 30 2>/dev/null | python3 -c "
+run() { printf "%-40s " "[$1]"; env $1 python3 bench.py --full --workload ${2:-lsw_10k_1024} --no-cpu-baseline --steps 30 2>/dev/null | python3 -c "
 import sys,json
 d=json.loads(sys.stdin.read()); r=d['roofline']; p=r.get('pool') or {}
 print(d['value'], r['kernel_ms'], 'frac', r['frac'], p.get('candidates_fill_ms'), p.get('candidates_memset_ms'))"; }

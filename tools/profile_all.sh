@@ -16,7 +16,7 @@ cd /tmp && export TMPDIR=/tmp && cd $REPO
 [ -x tools/bin/clkprobe ] && tools/bin/clkprobe > $OUT/clkprobe.txt 2>&1
 for WL in $WLS; do
   EXTRA="--no-cpu-baseline"; [ $WL = lsw_10k_1024 ] && EXTRA=""
-  python3 bench.py --workload $WL $EXTRA > $OUT/${WL}_bench.json 2> $OUT/${WL}_bench.err || { echo "bench $WL failed"; continue; }
+  python3 bench.py --full --workload $WL $EXTRA > $OUT/${WL}_bench.json 2> $OUT/${WL}_bench.err || { echo "bench $WL failed"; continue; }
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${WL}_stats -o st -- python3 bench.py --workload $WL --no-cpu-baseline \
       > $OUT/${WL}_bench_under_rocprof.json 2> $OUT/${WL}_stats.err || { echo "stats $WL failed"; continue; }
   cp $(find $OUT/${WL}_stats -name '*kernel_stats.csv' | head -1) $OUT/${WL}_kernel_stats.csv

@@ -9,7 +9,7 @@ set -u
 TAG=$1; WL=${2:-lsw_10k_1024}
 REPO=$(pwd); OUT=$REPO/gpurun_out/profile; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $REPO
-python3 bench.py --workload $WL > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || exit 1
+python3 bench.py --full --workload $WL > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || exit 1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_stats -o st -- python3 bench.py --workload $WL --no-cpu-baseline \
     > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/${TAG}_stats.err || exit 1
 cp $(find $OUT/${TAG}_stats -name '*kernel_stats.csv' | head -1) $OUT/${TAG}_kernel_stats.csv

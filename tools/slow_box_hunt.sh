@@ -3,7 +3,7 @@
 # candidate, 256-MiB chunks, fills in >= 3.6 ms) also the headline on other pool constructions, one fresh process each.
 mkdir -p gpurun_out
 OUT=gpurun_out/slow_box_hunt_$(date +%s).txt
-run() { printf "%-34s " "[$1]"; env $1 python3 bench.py --no-cpu-baseline --steps 30 2>/dev/null | python3 -c "
+run() { printf "%-34s " "[$1]"; env $1 python3 bench.py --full --no-cpu-baseline --steps 30 2>/dev/null | python3 -c "
 import sys,json
 d=json.loads(sys.stdin.read()); r=d['roofline']; p=r.get('pool') or {}
 print(d['value'], r['kernel_ms'], 'frac', r['frac'], p.get('candidates_kind'), p.get('candidates_fill_ms'), 'kept', p.get('kept'))"; }
