@@ -13,7 +13,7 @@ import numpy as np
 
 ALGO_LNW, ALGO_LSW, ALGO_ANW, ALGO_BSW = 0, 1, 2, 3
 ALGO_NAMES = {ALGO_LNW: "LNW", ALGO_LSW: "LSW", ALGO_ANW: "ANW", ALGO_BSW: "BSW"}
-KEEP_MATRICES, SCORE_ONLY, TIME_FILLS, TUNE_PLACEMENT = 0x0, 0x1, 0x2, 0x4
+KEEP_MATRICES, SCORE_ONLY, TIME_FILLS, TUNE_PLACEMENT, KEEP_DIRECTIONS = 0x0, 0x1, 0x2, 0x4, 0x8
 MAT_H, MAT_I, MAT_D = 0, 1, 2
 
 # every symbol include/dpx_align.h declares (tests check the .so exports all of them)
@@ -24,8 +24,10 @@ ABI_SYMBOLS = (
     "dpx_abi_version", "dpx_batch_create", "dpx_batch_create_on", "dpx_pack2", "dpx_batch_create_packed2", "dpx_batch_fill", "dpx_batch_fill_timed", "dpx_batch_last_fill_usec", "dpx_batch_last_output_usec", "dpx_batch_sync",
     "dpx_batch_device_results", "dpx_batch_results", "dpx_batch_matrix", "dpx_batch_traceback",
     "dpx_batch_output_begin", "dpx_batch_output_end", "dpx_batch_output_take", "dpx_text_free",
-    "dpx_batch_info", "dpx_batch_describe", "dpx_batch_destroy", "dpx_align_batch", "dpx_prim_eval",
+    "dpx_batch_info", "dpx_batch_describe", "dpx_batch_destroy", "dpx_align_batch", "dpx_prim_eval", "dpx_batch_directions",
 )
+# declared entry points a library may lack and still load (an older build): checked when they are called
+OPTIONAL_SYMBOLS = ("dpx_batch_directions",)
 
 
 class DpxError(RuntimeError):
@@ -99,8 +101,11 @@ def load() -> C.CDLL:
     lib.dpx_batch_destroy.argtypes = [vp]
     lib.dpx_align_batch.argtypes = [C.POINTER(Params), vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
     lib.dpx_prim_eval.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp]
-    for name in ABI_SYMBOLS:  # every declared entry point must be exported
-        getattr(lib, name)
+    if hasattr(lib, "dpx_batch_directions"):
+        lib.dpx_batch_directions.argtypes = [vp, C.c_size_t, C.c_int, vp]
+    for name in ABI_SYMBOLS:  # every declared entry point must be exported (the optional ones by libraries that have them)
+        if name not in OPTIONAL_SYMBOLS:
+            getattr(lib, name)
     if lib.dpx_abi_version() < ABI_VERSION_NEEDED:
         raise DpxError(-8, f"{path} has ABI version {lib.dpx_abi_version()}, this binding needs >= {ABI_VERSION_NEEDED} -- rebuild it")
     _lib = lib
@@ -201,6 +206,16 @@ class Batch:
         m, n = int(self.pairs["querySize"][pair]), int(self.pairs["referenceSize"][pair])
         out = np.empty((m + 1, n + 1), np.int16)
         _check(self._lib.dpx_batch_matrix(self._h, pair, which, out.ctypes.data), "dpx_batch_matrix")
+        return out
+
+    def directions(self, pair: int, which: int = MAT_H) -> np.ndarray:
+        """The reference's direction matrix of a KEEP_DIRECTIONS batch: uint8 (m+1, n+1), c++/backtrack.h enums (directionMain for
+        MAT_H, directionIndel for ANW's MAT_I / MAT_D)."""
+        if not hasattr(self._lib, "dpx_batch_directions"):
+            raise DpxError(-8, f"{lib_path()} has no dpx_batch_directions -- rebuild it")
+        m, n = int(self.pairs["querySize"][pair]), int(self.pairs["referenceSize"][pair])
+        out = np.empty((m + 1, n + 1), np.uint8)
+        _check(self._lib.dpx_batch_directions(self._h, pair, which, out.ctypes.data), "dpx_batch_directions")
         return out
 
     def traceback(self, pair: int) -> Tuple[str, str, str]:

@@ -20,6 +20,7 @@
 #include <utility>
 #include <vector>
 
+#include "dpx_dir.h"
 #include "dpx_kernels.h"
 #include "dpx_layout.h"
 
@@ -542,6 +543,11 @@ struct dpx_batch {
     size_t nSingles = 0, nCouples = 0, nLanePairs = 0, nWaves = 0; /* launch-list sizes (dpx_batch_describe) */
     PoolRecord poolRec;    /* how the matrix pool behind dMat was built / timed */
     bool tunePool = false, tuneShop = false; /* DPX_TUNE_PLACEMENT: the pool is timed / shopped for at the end of dpx_batch_create */
+    /* DPX_KEEP_DIRECTIONS: 4-bit codes in the pool behind dMat (matElems counts them in int16 units, dpx_dir.h), filled by
+     * k_linear_dir / k_affine_dir; references too long for LDS get a per-wave area of edge rows + staged reference behind the codes */
+    bool dirs = false;
+    dpx_dir_args dirArgs{};
+    size_t dirScratch = 0; /* bytes of that area (0: LDS) */
 };
 
 extern "C" {
@@ -732,6 +738,19 @@ static bool fits_int16(const dpx_params &p, long long m, long long n) {
     return lo >= -lim && hi <= lim;
 }
 
+/* The same rigorous bounds for a DPX_KEEP_DIRECTIONS batch: int32 arithmetic, checked against 2^28 so that every value stays clear
+ * of the affine kernels' -2^29 virtual borders; no column limit (no 16-bit column keys). */
+static bool fits_dir(const dpx_params &p, long long m, long long n) {
+    auto pos = [](long long v) { return v > 0 ? v : 0; };
+    auto neg = [](long long v) { return v < 0 ? v : 0; };
+    const long long lim = 1ll << 28, diag = pos(std::max<long long>(p.match, p.mismatch)) * std::min(m, n);
+    if (p.algo == DPX_ALGO_LSW) return diag + pos(p.gapOpen) * (m + n) <= lim;
+    if (p.algo == DPX_ALGO_LNW) return neg(p.gapOpen) * (m + n) >= -lim && diag + pos(p.gapOpen) * (m + n) <= lim;
+    const long long o = p.gapOpen, e = p.gapExtend;
+    const long long loH = 2 * neg(o) + neg(e) * (m + n), hiH = diag + (pos(o) + pos(e)) * (m + n);
+    return loH + neg(o + e) >= -lim && hiH + pos(o) + pos(e) * std::max(m, n) <= lim;
+}
+
 /* The "+Opt" packed kernel (k_linear_fill_pk) does EVERY add in wrapping 16-bit halves (v_pk_add_i16 / v_pk_mad_i16), so
  * not only the stored H values but the weights themselves and the intermediates `diag + s` and `max(up, left) + gap`
  * must stay inside int16: H lies in [lo, hi] (fits_int16's bounds), an intermediate is one weight away from an H value
@@ -876,7 +895,13 @@ static void shop_pool_by_fill(dpx_batch *b, PoolRecord &rec, PhaseTrace &trace) 
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (hipEventCreate(&e0) != hipSuccess) { (void)hipGetLastError(); return; }
     if (hipEventCreate(&e1) != hipSuccess) { (void)hipGetLastError(); (void)hipEventDestroy(e0); return; }
-    auto set_pool = [&](void *p) { b->dMat = (int16_t *)p; b->args.mat = b->dMat; b->pkArgs.mat = b->dMat; };
+    auto set_pool = [&](void *p) {
+        b->dMat = (int16_t *)p; b->args.mat = b->dMat; b->pkArgs.mat = b->dMat;
+        if (b->dirs) { /* the codes and the long-reference area live in the pool as well */
+            b->dirArgs.codes = reinterpret_cast<uint8_t *>(p);
+            b->dirArgs.scratch = b->dirScratch ? reinterpret_cast<unsigned char *>(p) + b->matElems * sizeof(int16_t) : nullptr;
+        }
+    };
     auto time_fill = [&]() -> float {
         float ms = -1.f;
         hipError_t e = launch_all(b, b->stream);
@@ -1026,6 +1051,9 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
         if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); return DPX_ERR_NO_DEVICE; }
         if (device >= n) return DPX_ERR_INVALID;
     } else if (device != -1) return DPX_ERR_INVALID;
+    const bool dirs = (flags & DPX_KEEP_DIRECTIONS) != 0;
+    if (dirs && (flags & DPX_SCORE_ONLY)) return DPX_ERR_INVALID;
+    if (dirs && params->algo == DPX_ALGO_BSW) return DPX_ERR_UNSUPPORTED; /* banded directions: not implemented */
     rc = bind_device(device);
     if (rc != DPX_OK) return rc;
 
@@ -1040,6 +1068,7 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
     b->numPairs = numPairs;
     b->store = !(flags & DPX_SCORE_ONLY);
     b->planes = params->algo == DPX_ALGO_ANW ? 3 : 1;
+    b->dirs = dirs;
     b->pairs.resize(numPairs);
 
     /* geometry, validation */
@@ -1052,7 +1081,7 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
             delete b;
             return DPX_ERR_INVALID;
         }
-        if (!fits_int16(*params, sp.querySize, sp.referenceSize)) { delete b; return DPX_ERR_RANGE; }
+        if (!(dirs ? fits_dir(*params, sp.querySize, sp.referenceSize) : fits_int16(*params, sp.querySize, sp.referenceSize))) { delete b; return DPX_ERR_RANGE; }
         dpx_pair_dev &pd = b->pairs[i];
         pd.refIdx = sp.referenceIdx; pd.n = sp.referenceSize;
         pd.qryIdx = sp.queryIdx;     pd.m = sp.querySize;
@@ -1070,6 +1099,11 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
     if (kn.rowsPerLane) {
         const int v = kn.rowsPerLane;
         if (v == 2 || v == 4 || v == 8 || (v == 16 && params->algo != DPX_ALGO_ANW)) R = v;
+    }
+    if (dirs) { /* direction kernels: LSW keeps per-row best cells and stays at <= 8 rows per lane (VGPRs), ANW at <= 8 as always */
+        R = b->maxM <= 128 ? 2 : b->maxM <= 256 ? 4 : (b->maxM <= 512 || params->algo != DPX_ALGO_LNW) ? 8 : 16;
+        const int v = kn.rowsPerLane;
+        if (v == 2 || v == 4 || v == 8 || (v == 16 && params->algo == DPX_ALGO_LNW)) R = v;
     }
     b->R = R;
     int kernelAlgo = params->algo;
@@ -1094,7 +1128,9 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
         pd.lanes = 64;
         pd.rows = 0;
         b->algBytes += (uint64_t)pd.m + (uint64_t)pd.n + 16u + 12u;
-        if (b->store) {
+        if (dirs) {
+            b->algBytes += ((uint64_t)(pd.m + 1) * (uint64_t)(pd.n + 1) + 1) / 2; /* half a byte per cell */
+        } else if (b->store) {
             if (banded) { /* 2 B per in-band cell */
                 const uint64_t inband = band_cells(pd.m, pd.n, params->band);
                 b->bandCells += inband;
@@ -1116,7 +1152,13 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
     b->ldsBytes = perWave * (DPX_FILL_THREADS / 64);
     /* Store-bound fills run ~2 % faster with 3-4 waves per SIMD than with 6-7 (fewer write streams in flight,
      * profiles/README.md): cap residency at 4 workgroups per CU through the LDS request. */
-    if (b->store && !banded && b->ldsBytes < kLdsFloor) b->ldsBytes = kLdsFloor;
+    if (b->store && !banded && !dirs && b->ldsBytes < kLdsFloor) b->ldsBytes = kLdsFloor;
+    /* direction kernels: int32 edge row(s) [n+2] + staged reference [n+192]; per wave in LDS, or -- when even a one-wave workgroup
+     * could not hold that -- in the batch's allocation */
+    const size_t dirEdgeBytes = align_up((size_t)(b->maxN + 2) * 4, 16);
+    const size_t dirPerWave = dirEdgeBytes * nEdges + align_up((size_t)b->maxN + 192, 16);
+    const bool dirGlobal = dirs && dirPerWave > 64u * 1024u;
+    if (dirs) b->ldsBytes = 0;
     if (b->ldsBytes > 160u * 1024u) { delete b; return DPX_ERR_UNSUPPORTED; }
 
 #define CREATE_TRY(call)                                                      \
@@ -1142,7 +1184,7 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
      * (the low half's column 0), and for SW: score * 8 + 7 in 16 bits (row tags) and gap <= 0, mismatch <= 0 (rows past the query's
      * end are not masked: with such weights they never exceed the real rows above them).  DPX_LANES_PK=0 keeps the int32 kernels. */
     bool lanesPk = false;
-    if (linearAlgo && b->store && b->maxM > 0 && b->maxM <= 1024) {
+    if (linearAlgo && b->store && !dirs && b->maxM > 0 && b->maxM <= 1024) {
         dpx_params kp = *params;
         kp.algo = kernelAlgo;
         auto pos = [](long long v) { return v > 0 ? v : 0; };
@@ -1163,6 +1205,7 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
     bool useLanes = lanesShape && b->maxM <= 256 && numPairs >= 2048;
     bool lanesForced = false;
     if (kn.lanes >= 0) { useLanes = kn.lanes != 0 && lanesShape; lanesForced = true; }
+    if (dirs) useLanes = false; /* every pair on k_linear_dir / k_affine_dir */
     std::vector<dpx_wave_desc> waves;
     size_t lanesRefArea = 0, lanesPairs = 0;
     if (useLanes) {
@@ -1218,6 +1261,7 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
     if (b->lanePacked) usePacked = false;
     else
     if (kn.packed >= 0) usePacked = kn.packed != 0 && b->store && (linearAlgo || banded);
+    if (dirs) usePacked = false;
     /* 16-bit wrapping arithmetic: only when weights and every intermediate provably fit (also under DPX_PACKED=1) */
     if (usePacked) {
         dpx_params kp = *params;
@@ -1268,7 +1312,7 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
         const int sW = dpx_tiled_stripes(b->maxM, sR);
         const size_t edgeStride = align_up((size_t)b->maxN + 2, 8); /* int16 elements */
         const size_t lds = 512 + align_up((size_t)b->maxN + 128 + 16, 16) + (size_t)std::max(sW - 1, 0) * edgeStride * 2;
-        const bool shape = linearAlgo && b->store && !b->lanePacked && !b->packed && !anyEmpty && numPairs > 0 && sW >= 2 && sW <= 16 && lds <= 160u * 1024u;
+        const bool shape = linearAlgo && b->store && !dirs && !b->lanePacked && !b->packed && !anyEmpty && numPairs > 0 && sW >= 2 && sW <= 16 && lds <= 160u * 1024u;
         /* measured (bench.py --pairs N, DPX_SPLIT=0/1, HIP events around every fill; GCUPS split vs one wave per pair):
          *   1024 x 1024 (4 stripes of 4 rows per lane against ONE 16-rows-per-lane wave): 600 pairs 1864 vs 1768, 1200: 2229 vs 1765,
          *   2500: 2483 vs 2315, 3500: 2592 vs 2393, 4096: 2603 vs 2671 (and the packed kernel takes over);
@@ -1385,8 +1429,9 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
     if (b->store) {
         int group = 64;
         if (kn.group >= 1 && kn.group <= 1000000) group = kn.group;
-        const uint32_t chunkElems = (banded || b->split) ? 512u : dpx_tiled_chunk_elems(b->R, b->planes);
+        const uint32_t chunkElems = (banded || b->split || dirs) ? 512u : dpx_tiled_chunk_elems(b->R, b->planes); /* (dirs: 1-KiB code chunks) */
         auto chunksOf = [&](const dpx_pair_dev &pd) -> uint64_t {
+            if (dirs) return dpx_dir_chunks(pd.m, pd.n, b->R);
             if (pd.lanes == 32) return dpx_split_chunks(pd.m, pd.n, b->R);
             return banded ? dpx_band_chunks(pd.m, pd.n, params->band) : dpx_tiled_chunks(pd.m, pd.n, b->R);
         };
@@ -1442,17 +1487,19 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
         CREATE_TRY(hipMemcpyAsync(b->arena, b->hStage, stageBytes, hipMemcpyHostToDevice, b->stream));
         b->uploadPending = true;
     }
-    if (b->store && b->matElems) {
+    if (dirGlobal) b->dirScratch = align_up(std::min<size_t>(std::max<size_t>(numSingles, 1), DPX_DIR_SCRATCH_SLOTS) * dirPerWave, 256);
+    if (b->store && (b->matElems || b->dirScratch)) {
         void *pool = nullptr;
         bool fresh = false;
         /* DPX_POOL_GUARD=1 (tests): 4 MiB behind the matrices are filled with a pattern here and checked by dpx_batch_sync() -- a kernel that
          * writes past the end of the batch's matrices fails the test instead of hitting whatever is mapped behind the pool */
         const bool guardOn = kn.poolGuard != 0;
         b->guardBytes = guardOn ? (size_t)4 << 20 : 0;
-        CREATE_TRY(g_matCache.take(&pool, b->matElems * sizeof(int16_t) + b->guardBytes, &b->matPoolBytes, &fresh));
-        if (b->guardBytes) CREATE_TRY(hipMemset((char *)pool + b->matElems * sizeof(int16_t), 0xA5, b->guardBytes));
+        const size_t guardAt = b->matElems * sizeof(int16_t) + b->dirScratch;
+        CREATE_TRY(g_matCache.take(&pool, guardAt + b->guardBytes, &b->matPoolBytes, &fresh));
+        if (b->guardBytes) CREATE_TRY(hipMemset((char *)pool + guardAt, 0xA5, b->guardBytes));
         if (b->guardBytes && kn.poolGuard == 2) { /* (the checker's own test: one byte of the band is already wrong) */
-            CREATE_TRY(hipMemset((char *)pool + b->matElems * sizeof(int16_t) + 12345, 0, 1));
+            CREATE_TRY(hipMemset((char *)pool + guardAt + 12345, 0, 1));
             b->guardSelfTest = true;
         }
         /* DPX_TUNE_PLACEMENT (callers that fill the batch many times): the pool is timed with hipMemset and, if it is a fresh one,
@@ -1557,6 +1604,23 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
         if (b->sideStream && (hipEventCreateWithFlags(&b->evFork, hipEventDisableTiming) != hipSuccess ||
                               hipEventCreateWithFlags(&b->evJoin, hipEventDisableTiming) != hipSuccess)) (void)hipGetLastError();
     }
+    if (dirs) {
+        dpx_dir_args &d = b->dirArgs;
+        d.seq = b->dSeq;
+        d.pairs = b->dPairs;
+        d.order = b->dOrder;
+        d.numPairs = (int32_t)numSingles;
+        d.match = params->match; d.mismatch = params->mismatch;
+        d.gapOpen = params->gapOpen; d.gapExtend = params->gapExtend;
+        d.codes = reinterpret_cast<uint8_t *>(b->dMat);
+        d.score = b->dScore; d.endRow = b->dEndRow; d.endCol = b->dEndCol;
+        d.ldsPerWave = (uint32_t)dirPerWave;
+        d.ldsEdge2Off = (uint32_t)dirEdgeBytes;
+        d.ldsRefOff = (uint32_t)(dirEdgeBytes * nEdges);
+        d.scratch = b->dirScratch ? reinterpret_cast<unsigned char *>(b->dMat) + b->matElems * sizeof(int16_t) : nullptr;
+        /* four waves per workgroup when their LDS fits, one otherwise */
+        d.wavesPerBlock = (d.scratch || dirPerWave * 4 > 160u * 1024u) ? 1u : fill_waves_per_block(numSingles);
+    }
     b->nSingles = numSingles;
     b->nCouples = b->packed ? numCouples : 0;
     b->nLanePairs = b->lanePacked ? lanesPairs : 0;
@@ -1577,6 +1641,7 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
  * The secondary kernels therefore go to the batch's side stream between a fork and a join event; on `s` the fill still
  * looks like one operation (events recorded on `s` around it time all of it). */
 static hipError_t launch_all(dpx_batch *b, hipStream_t s) {
+    if (b->dirs) return dpx_launch_fill_dir(b->dirArgs, b->kernelAlgo, b->R, s);
     const bool hasMain = b->args.numPairs > 0;
     int kernels = 0;
     if (b->packed) kernels++;
@@ -1691,7 +1756,7 @@ int dpx_batch_fill_timed(dpx_batch *b, int repeats, double *usecPerFill) {
 static int check_guard(dpx_batch *b) {
     if (!b->guardBytes || !b->dMat) return DPX_OK;
     std::vector<unsigned char> h(b->guardBytes);
-    HIP_TRY(hipMemcpy(h.data(), (const char *)b->dMat + b->matElems * sizeof(int16_t), b->guardBytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h.data(), (const char *)b->dMat + b->matElems * sizeof(int16_t) + b->dirScratch, b->guardBytes, hipMemcpyDeviceToHost));
     for (size_t k = 0; k < h.size(); k++)
         if (h[k] != 0xA5) { t_err = "DPX_POOL_GUARD: byte " + std::to_string(k) + " behind the matrices was overwritten"; return DPX_ERR_HIP; }
     return DPX_OK;
@@ -1746,9 +1811,29 @@ int dpx_batch_results(dpx_batch *b, int32_t *scores, int32_t *endRow, int32_t *e
     return check_guard(b);
 }
 
+int dpx_batch_directions(dpx_batch *b, size_t pair, int which, uint8_t *out) {
+    if (!b || !out || pair >= b->numPairs || which < 0 || which >= b->planes) return DPX_ERR_INVALID;
+    if (!b->dirs) return DPX_ERR_NO_MATRIX;
+    if (!b->filled) return DPX_ERR_NOT_FILLED;
+    int rc = bind_device(b->device);
+    if (rc != DPX_OK) return rc;
+    const dpx_pair_dev &pd = b->pairs[pair];
+    const size_t total = (size_t)(pd.m + 1) * (size_t)(pd.n + 1);
+    uint8_t *dOut = nullptr;
+    size_t dOutCap = 0;
+    if (b->lastStream && b->lastStream != b->stream) HIP_TRY(hipStreamSynchronize(b->lastStream));
+    HIP_TRY(g_tbDevCache.take((void **)&dOut, std::max<size_t>(total, 16), &dOutCap)); /* row-major scratch */
+    hipError_t e = dpx_launch_export_dir(reinterpret_cast<const uint8_t *>(b->dMat), pd, b->dSeq, b->kernelAlgo, b->R, which, dOut, b->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    if (e == hipSuccess) e = hipMemcpy(out, dOut, total, hipMemcpyDeviceToHost);
+    g_tbDevCache.park(dOut, dOutCap);
+    if (e != hipSuccess) return hip_fail(e, "dpx_batch_directions");
+    return DPX_OK;
+}
+
 int dpx_batch_matrix(dpx_batch *b, size_t pair, int which, int16_t *out) {
     if (!b || !out || pair >= b->numPairs || which < 0 || which >= b->planes) return DPX_ERR_INVALID;
-    if (!b->store) return DPX_ERR_NO_MATRIX;
+    if (!b->store || b->dirs) return DPX_ERR_NO_MATRIX;
     if (!b->filled) return DPX_ERR_NOT_FILLED;
     int rc = bind_device(b->device);
     if (rc != DPX_OK) return rc;
@@ -1813,7 +1898,8 @@ static int output_begin(dpx_batch *b, uint64_t firstNumber) {
         if (b->kernelAlgo == DPX_ALGO_LSW || b->kernelAlgo == DPX_ALGO_LNW || b->kernelAlgo == DPX_ALGO_BSW) walk = 2;
         else if (b->kernelAlgo == DPX_ALGO_ANW && b->numPairs <= 20000) walk = 2;
         { const int w = knobs().tbWalk; if (w >= 0) walk = std::min(2, w); }
-        HIP_TRY(dpx_launch_traceback(b->args, (int)np, b->kernelAlgo, b->R, b->planes, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream));
+        if (b->dirs) HIP_TRY(dpx_launch_traceback_dir(b->dirArgs, (int)np, b->kernelAlgo, b->R, b->dTbOff, b->dTb, b->dTbLen, b->stream));
+        else HIP_TRY(dpx_launch_traceback(b->args, (int)np, b->kernelAlgo, b->R, b->planes, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream));
         b->tbLinesValid = true;
     }
     HIP_TRY(dpx_launch_output(b->dPairs, b->dScore, b->dTbLen, b->dTbOff, b->dTb, (int)np, (unsigned long long)firstNumber,
@@ -1971,11 +2057,14 @@ int dpx_batch_describe(dpx_batch *b, char *buf, size_t cap) {
     static const char *names[] = {"LNW", "LSW", "ANW", "BSW"};
     const char *kernel = b->kernelAlgo == DPX_ALGO_BSW ? (b->packed ? "k_banded_fill_pk" : "k_banded_fill") : b->kernelAlgo == DPX_ALGO_ANW ? (b->lanePacked ? "k_affine_lanes" : "k_affine_fill")
                          : b->packed ? "k_linear_fill_pk" : b->lanesPk ? "k_linear_lanes_pk" : b->lanePacked ? "k_linear_lanes" : b->split ? "k_linear_split" : "k_linear_fill";
+    if (b->dirs) kernel = b->kernelAlgo == DPX_ALGO_ANW ? "k_affine_dir" : "k_linear_dir";
     /* dtype = the arithmetic type of the kernel that fills (most of) the batch */
     int len = snprintf(buf, cap, "algo=%s kernel_algo=%s kernel=%s dtype=%s rows_per_lane=%d store=%d couples=%zu lane_pairs=%zu waves=%zu singles=%zu row_tags=%d seq_input=%s waves_per_workgroup=%u",
                        names[b->prm.algo], names[b->kernelAlgo], kernel, (b->packed || b->lanesPk) ? "int16" : "int32", b->R, b->store ? 1 : 0, b->nCouples, b->nLanePairs,
                        b->nWaves, b->nSingles, (int)b->pkArgs.rowTags, b->packed2 ? "packed2" : "bytes",
-                       (b->packed || b->lanePacked) ? b->pkArgs.wavesPerBlock : b->split ? (unsigned)b->splitWaves : b->args.wavesPerBlock);
+                       b->dirs ? b->dirArgs.wavesPerBlock : (b->packed || b->lanePacked) ? b->pkArgs.wavesPerBlock : b->split ? (unsigned)b->splitWaves : b->args.wavesPerBlock);
+    if (b->dirs && len > 0 && (size_t)len < cap) /* the code layout, and where the edge rows live */
+        len += snprintf(buf + len, cap - (size_t)len, " matrix=dir4 dir_edges=%s dir_scratch_bytes=%zu", b->dirScratch ? "global" : "lds", b->dirScratch);
     if (b->dMat && len > 0 && (size_t)len < cap) { /* the matrix pool: how it was built, and the memset time of every candidate that was timed */
         const PoolRecord &r = b->poolRec;
         len += snprintf(buf + len, cap - (size_t)len, " pool=%s pool_bytes=%zu pool_chunk_mb=%zu pool_kept=%d pool_memset_ms=", r.mode.c_str(), b->matPoolBytes,

@@ -8,7 +8,7 @@
 // stdout keeps the reference's lines so logs stay diff-able.
 //
 //   dpx_main -pairs <file> [-match 3] [-mismatch -1] [-open -2 | -gap -2] [-extend -1]
-//            [-algo LSW|LNW|ANW|BSW] [-band 128] [-batch N | -pool-gb 4] [-inflight K] [-tune 0|1] [-device 0] [-noprint] [-pack2] [-producer P] [-rank r -world w]
+//            [-algo LSW|LNW|ANW|BSW] [-band 128] [-batch N | -pool-gb 4] [-inflight K] [-tune 0|1] [-device 0] [-noprint] [-pack2] [-directions] [-producer P] [-rank r -world w]
 //
 // Batch size: by default from a matrix-pool BUDGET (-pool-gb, 4 GiB): as many pairs as fit the budget, at most 20000 (the
 // reference sizes its buffers once for BATCH_SIZE = 10000 reads of 150 bases, cuda/LNW/LinearNeedlemanWunschV9.cu:26-46,
@@ -65,6 +65,7 @@ int main(int argc, char *argv[]) {
     double poolGb = 4.0;
     bool print = true, pack2 = false;
     int producerFlag = -1; // producer threads; -1: by batch size (2 for batches of many short pairs, none for few long ones)
+    bool directions = false; // -directions: batches keep 4-bit direction codes (DPX_KEEP_DIRECTIONS): int32 scores, a quarter of the pool per pair
     int inflight = 3;      // batches on the device at a time (= matrix pools reserved)
     int tuneFlag = -1;     // -1: by the length of the job
     std::string algoName = "LSW";
@@ -85,6 +86,7 @@ int main(int argc, char *argv[]) {
         else if (!strcmp(argv[i], "-device")) device = atoi(next("-device"));
         else if (!strcmp(argv[i], "-noprint")) print = false;
         else if (!strcmp(argv[i], "-pack2")) pack2 = true;
+        else if (!strcmp(argv[i], "-directions")) directions = true;
         else if (!strcmp(argv[i], "-producer")) producerFlag = atoi(next("-producer"));
         else if (!strcmp(argv[i], "-inflight")) inflight = atoi(next("-inflight"));
         else if (!strcmp(argv[i], "-tune")) tuneFlag = atoi(next("-tune"));
@@ -115,7 +117,8 @@ int main(int argc, char *argv[]) {
     // the two matrix pools of the pipeline are built while the file is parsed (nothing else needs the device yet)
     // (the budget is per score plane: the three planes of the affine algorithm get three times the bytes, so that a batch holds
     // as many pairs -- and fills the chip as well -- as a linear-gap batch of the same shapes)
-    const size_t poolBudget = (size_t)(poolGb * (double)(1ull << 30)) * (algo == DPX_ALGO_ANW ? 3 : 1);
+    // (-directions: one 4-bit code per cell whatever the algorithm, so the budget stays per batch and holds 4x -- ANW 12x -- the pairs)
+    const size_t poolBudget = (size_t)(poolGb * (double)(1ull << 30)) * (algo == DPX_ALGO_ANW && !directions ? 3 : 1);
     std::thread reserve;
     // (and pinned text buffers: one being printed, one per batch in flight, two spare)
     const bool budgetedBatches = batchSize == 0;
@@ -135,7 +138,13 @@ int main(int argc, char *argv[]) {
 
     if (batchSize == 0) { // pairs per batch from the pool budget: 2 bytes per cell and plane, rows / columns padded as the layouts pad them
         const double cols = (algo == DPX_ALGO_BSW && 2.0 * band < (double)fileInfo.maxReferenceLength) ? 2.0 * band + 8 : (double)fileInfo.maxReferenceLength + 128;
-        const double perPair = 2.0 * (algo == DPX_ALGO_ANW ? 3 : 1) * ((double)fileInfo.maxQueryLength + 64) * cols;
+        // (-directions: half a byte per cell; rows rounded up to whole stripes of 64 * R, every stripe n + 63 steps rounded up to 32 / R --
+        // the code layout of csrc/dpx_dir.h, R picked from the longest query as dpx_batch_create picks it)
+        const long long mq = fileInfo.maxQueryLength, dR = mq <= 128 ? 2 : mq <= 256 ? 4 : (mq <= 512 || algo != DPX_ALGO_LNW) ? 8 : 16;
+        const double dirRows = (double)((mq + 64 * dR - 1) / (64 * dR) * 64 * dR);
+        const double dirCols = (double)(((long long)fileInfo.maxReferenceLength + 63 + 32 / dR - 1) / (32 / dR) * (32 / dR));
+        const double perPair = directions ? 0.5 * dirRows * dirCols + 1024.0
+                                          : 2.0 * (algo == DPX_ALGO_ANW ? 3 : 1) * ((double)fileInfo.maxQueryLength + 64) * cols;
         const double fit = (double)poolBudget / (perPair > 0 ? perPair : 1);
         batchSize = (size_t)std::min(20000.0, std::max(64.0, fit));
         batchSize &= ~(size_t)1; // even: the packed kernels fill COUPLES of equal-shaped pairs, an odd batch leaves one pair to a second kernel
@@ -216,7 +225,7 @@ int main(int argc, char *argv[]) {
         next.first = first;
         next.count = std::min(batchSize, shardHi - first);
         const uint64_t t0 = get_time();
-        const unsigned flags = DPX_KEEP_MATRICES | DPX_TIME_FILLS | ((tunePools && tuned.fetch_add(1) < inflight) ? DPX_TUNE_PLACEMENT : 0u);
+        const unsigned flags = (directions ? DPX_KEEP_DIRECTIONS : DPX_KEEP_MATRICES) | DPX_TIME_FILLS | ((tunePools && tuned.fetch_add(1) < inflight) ? DPX_TUNE_PLACEMENT : 0u);
         int prc = pack2 ? dpx_batch_create_packed2(-1, &prm, packed.data(), fileInfo.numBytes, alphabet, reinterpret_cast<const dpx_seq_pair *>(sequenceIdxs),
                                                    first, next.count, flags, &next.b)
                         : dpx_batch_create(&prm, sequences, fileInfo.numBytes, reinterpret_cast<const dpx_seq_pair *>(sequenceIdxs), first, next.count,

@@ -24,7 +24,7 @@ extern "C" {
 
 /* 1: round 1.  2: + dpx_batch_create_on, dpx_batch_fill_timed, dpx_batch_last_fill_usec, dpx_batch_output_begin/_end/_take,
  * dpx_text_free, DPX_TUNE_PLACEMENT (round 2).  3: + dpx_pool_reserve, dpx_text_reserve, dpx_batch_last_output_usec, dpx_pack2, dpx_batch_create_packed2; dpx_batch_describe reports the
- * matrix pool (round 3).  Additions only: a caller built against an older version keeps working; dpx_abi_version() >= the version
+ * matrix pool (round 3); + DPX_KEEP_DIRECTIONS, dpx_batch_directions (detect them by the exported symbol: the number stays 3).  Additions only: a caller built against an older version keeps working; dpx_abi_version() >= the version
  * a caller needs is the check. */
 #define DPX_ABI_VERSION 3
 
@@ -76,8 +76,15 @@ typedef struct dpx_params {
 #define DPX_TUNE_PLACEMENT 0x4u /* the batch will be filled many times: time its matrix pool (>= 1 GiB) with hipMemset and shop for a better
                                    one with the batch's OWN FILL on four more candidate pools (the same fill runs 2 - 27 % apart on
                                    two pools of the same construction); every candidate's times go into dpx_batch_describe's pool_* fields */
+#define DPX_KEEP_DIRECTIONS 0x8u /* LNW / LSW / ANW: keep one 4-bit direction code per cell instead of the int16 score matrices, compute in
+                                    int32 (the reference's evolved kernels keep directions only, cuda/LNW/LinearNeedlemanWunschV6.cu:167).  Same
+                                    scores, end cells, text and tracebacks as a DPX_KEEP_MATRICES batch; half a byte per cell plus ~32 B of stripe
+                                    padding per query row (about a quarter of an int16 H batch's bytes, a twelfth of ANW's H/I/D, from
+                                    a few hundred rows on; short reads keep a larger fraction); scores may exceed int16 (bounds checked against 2^28) and references 65 000 columns.
+                                    dpx_batch_matrix() returns DPX_ERR_NO_MATRIX, dpx_batch_directions() exports the codes.  With
+                                    DPX_SCORE_ONLY: DPX_ERR_INVALID; with BSW: DPX_ERR_UNSUPPORTED (banded directions are not implemented). */
 
-/* matrix selectors for dpx_batch_matrix */
+/* matrix selectors for dpx_batch_matrix / dpx_batch_directions */
 #define DPX_MAT_H 0 /* scoring matrix   (reference: memo / scoringMemo)            */
 #define DPX_MAT_I 1 /* ANW horizontal-gap matrix (queryInsertionMemo)               */
 #define DPX_MAT_D 2 /* ANW vertical-gap matrix   (queryDeletionMemo)                */
@@ -173,6 +180,13 @@ int dpx_batch_results(dpx_batch *b, int32_t *scores, int32_t *endRow, int32_t *e
  * memory of (m+1)*(n+1) int16.  On the device the matrix lives in the engine's wavefront-tiled layout
  * (DESIGN.md); this call un-tiles it with a device kernel and copies it back. */
 int dpx_batch_matrix(dpx_batch *b, size_t pair, int which, int16_t *out);
+
+/* Export one pair's direction matrix of a DPX_KEEP_DIRECTIONS batch as the reference's back-trackers read it: row-major (m+1) x (n+1)
+ * uint8 including the border row / column, values of c++/backtrack.h -- `which` DPX_MAT_H: enum directionMain (NONE_MAIN 0, MATCH 1,
+ * MISMATCH 2, QUERY_INSERTION 3, QUERY_DELETION 4; LNW / ANW borders: QUERY_DELETION down column 0, QUERY_INSERTION along row 0;
+ * LSW: NONE_MAIN where the best candidate is negative, c++/LinearSmithWaterman.cpp:106-109); DPX_MAT_I / DPX_MAT_D (ANW only):
+ * enum directionIndel (GAP_OPEN 1, GAP_EXTEND 2; 0 on the borders).  DPX_ERR_NO_MATRIX on a batch without the flag. */
+int dpx_batch_directions(dpx_batch *b, size_t pair, int which, uint8_t *out);
 
 /* Device traceback of one pair from the stored matrices, with the reference's tie rules.
  * Produces the three lines the reference prints (reference / relation / query; c++/backtrack.cpp:21-356).
