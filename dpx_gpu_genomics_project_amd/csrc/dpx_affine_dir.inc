@@ -1,0 +1,136 @@
+/* dpx_affine_dir.inc -- body of the affine-gap direction fills, included by dpx_dir_kernels.hip inside k_affine_dir (ANW, LOCAL = false)
+ * and k_asw_dir (ASW, LOCAL = true), for the reason given in dpx_affine_fill.inc.  In scope: `a`, R, GLOBAL and LOCAL. */
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int G = 32 / R;
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int slot = blockIdx.x * (int)a.wavesPerBlock + wv; /* in this launch (the scratch area's index) */
+    if (a.firstSlot + slot >= a.numPairs) return;
+    const int p = a.order ? a.order[a.firstSlot + slot] : a.firstSlot + slot;
+    const dpx_pair_dev pr = a.pairs[p];
+    const int n = pr.n, m = pr.m;
+    const int match = a.match, mismatch = a.mismatch;
+    const int o = a.gapOpen, e = a.gapExtend, oe = o + e;
+
+    if (m <= 0 || n <= 0) {
+        if (lane == 0) { /* H[m][n] on the border: 0 at the origin, else o + len*e (AffineNeedlemanWunsch.cpp:43-53); ASW: 0 at (0, 0) */
+            const int len = m <= 0 ? max(n, 0) : m;
+            a.score[p] = (LOCAL || len <= 0) ? 0 : o + len * e;
+            a.endRow[p] = LOCAL ? 0 : max(m, 0);
+            a.endCol[p] = LOCAL ? 0 : max(n, 0);
+        }
+        return;
+    }
+    const unsigned char *ref = reinterpret_cast<const unsigned char *>(a.seq + pr.refIdx);
+    const unsigned char *qry = reinterpret_cast<const unsigned char *>(a.seq + pr.qryIdx);
+    unsigned char *my;
+    if constexpr (GLOBAL) my = a.scratch + (size_t)slot * a.ldsPerWave;
+    else my = smem + (size_t)wv * a.ldsPerWave;
+    int32_t *edgeH = reinterpret_cast<int32_t *>(my);
+    int32_t *edgeD = reinterpret_cast<int32_t *>(my + a.ldsEdge2Off);
+    const unsigned char *refl = dir_stage(my + a.ldsRefOff + 64, ref, n, lane) - 64;
+    for (int x = lane; x <= n + 1; x += 64) { edgeH[x] = LOCAL ? 0 : o + x * e; edgeD[x] = DPX_NEG; } /* H[0][j] (:50-53; ASW 0), virtual D[0][j] */
+    if constexpr (GLOBAL) __threadfence_block();
+
+    const int S = dpx_tiled_stripes(m, R);
+    const int Wp = (int)dpx_dir_stripe_steps(n, R);
+    const size_t cs = (size_t)pr.chunkStride * 2u;
+    unsigned char *cbase = a.codes + (size_t)pr.matOff * 2u + (size_t)lane * 16u;
+
+    int Hl[R], Il[R], qc[R];
+    [[maybe_unused]] int bestv = 0, bestrow = 0, bestcol = 0; /* ASW: the lane's first strict maximum */
+    [[maybe_unused]] int bv[R], bc[R];                         /* ASW: per row, best H and its first column (int32: no 16-bit keys) */
+    for (int k = 0; k < S; k++) {
+        const int row0 = k * 64 * R + lane * R;
+        const int nrows = min(max(m - row0, 0), R);
+        const bool hasRows = nrows > 0, hasNext = k + 1 < S;
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            qc[r] = r < nrows ? (int)qry[row0 + r] : 0x100;
+            Hl[r] = LOCAL ? 0 : o + (row0 + 1 + r) * e; /* H[i][0] = o + i*e (:43-46); ASW: 0 */
+            Il[r] = DPX_NEG;                /* virtual I[i][0] */
+            if constexpr (LOCAL) { bv[r] = 0; bc[r] = 0; }
+        }
+        int dBot = DPX_NEG;                 /* D of the lane's bottom row, for the lane below */
+        int dtop = (LOCAL || row0 == 0) ? 0 : o + row0 * e;
+        const unsigned char *rp = refl + 64 - lane;
+        int rcN = rp[0];
+        int eHN = edgeH[1], eDN = edgeD[1];
+        unsigned char *dst = cbase + (size_t)k * (size_t)(Wp / G) * cs;
+        for (int t0 = 0; t0 < Wp; t0 += G) {
+            uint32_t acc[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int q = 0; q < G; q++) {
+                const int t = t0 + q;
+                const int rc = rcN, eH = eHN, eD = eDN;
+                rcN = rp[t + 1];
+                eHN = edgeH[min(t + 2, n + 1)];
+                eDN = edgeD[min(t + 2, n + 1)];
+                const int upH = wave_shr1(Hl[R - 1], eH);
+                const int upD = wave_shr1(dBot, eD);
+                const int j = t - lane + 1;
+                uint32_t w[2] = {0u, 0u};
+                if (hasRows && j >= 1 && j <= n) {
+                    int uH = upH, uD = upD, d = dtop;
+#pragma unroll
+                    for (int r = 0; r < R; r++) {
+                        const int lH = Hl[r];
+                        const int s = (qc[r] == rc) ? match : mismatch;
+                        const int dOpen = uH + oe, dExt = uD + e; /* :185-197 */
+                        const int Dn = max(dOpen, dExt);
+                        const int iOpen = lH + oe, iExt = Il[r] + e; /* :201-213 */
+                        const int In = max(iOpen, iExt);
+                        const int mm = d + s; /* :216-236 */
+                        const int v = max(Dn, mm);
+                        int h = max(In, v);
+                        uint32_t code = In >= v ? 3u : (Dn >= mm ? 2u : 1u);
+                        if constexpr (LOCAL) { /* ASW: H = max(0, best); move 0 where H == 0 (the walk stops there) */
+                            h = max(h, 0);
+                            if (h == 0) code = 0u;
+                            if (h > bv[r]) { bv[r] = h; bc[r] = j; } /* first strict maximum of the row */
+                        }
+                        code |= (iOpen >= iExt ? 0u : 4u) | (dOpen >= dExt ? 0u : 8u);
+                        w[(r * 4) >> 5] |= code << ((r * 4) & 31);
+                        d = lH;
+                        uH = h;
+                        uD = Dn;
+                        Hl[r] = h;
+                        Il[r] = In;
+                    }
+                    dBot = uD;
+                    dtop = upH;
+                    if (hasNext && lane == 63) { edgeH[j] = Hl[R - 1]; edgeD[j] = dBot; }
+                }
+                dir_put<R>(acc, q, w[0], w[1]);
+            }
+            dir_store(dst + (size_t)(t0 / G) * cs, acc);
+        }
+        if constexpr (GLOBAL) __threadfence_block();
+        if constexpr (LOCAL) {
+#pragma unroll
+            for (int r = 0; r < R; r++)
+                if (r < nrows && bv[r] > bestv) { bestv = bv[r]; bestrow = row0 + 1 + r; bestcol = bc[r]; }
+        }
+    }
+    if constexpr (LOCAL) { /* first strict maximum in row-major order (k_linear_dir) */
+        const unsigned long long mine = ((unsigned long long)(unsigned)bestv << 32) | (unsigned)(0x7FFFFFFF - bestrow);
+        const unsigned long long top = dir_wave_max_u64(mine);
+        if ((int)(top >> 32) == 0) {
+            if (lane == 0) { a.score[p] = 0; a.endRow[p] = 0; a.endCol[p] = 0; }
+        } else if (mine == top) {
+            a.score[p] = bestv;
+            a.endRow[p] = bestrow;
+            a.endCol[p] = bestcol;
+        }
+        return;
+    }
+    const int lastBase = (S - 1) * 64 * R;
+    const int lm = (m - 1 - lastBase) / R, rm = (m - 1 - lastBase) % R;
+    if (lane == lm) {
+        int v = Hl[0];
+#pragma unroll
+        for (int r = 1; r < R; r++) v = (r == rm) ? Hl[r] : v;
+        a.score[p] = v; /* scoringMemo[m][n] (:365) */
+        a.endRow[p] = m;
+        a.endCol[p] = n;
+    }

@@ -703,15 +703,18 @@ int dpx_shutdown(void) {
 
 /* ------------------------------------------------------------------------------------------ batch */
 
+/* the three-plane Gotoh algorithms: ANW (global) and ASW (local) */
+static bool is_affine(int algo) { return algo == DPX_ALGO_ANW || algo == DPX_ALGO_ASW; }
+
 static int validate_params(const dpx_params *p) {
     if (!p) return DPX_ERR_INVALID;
-    if (p->algo < DPX_ALGO_LNW || p->algo > DPX_ALGO_BSW) return DPX_ERR_INVALID;
+    if (p->algo < DPX_ALGO_LNW || p->algo > DPX_ALGO_ASW) return DPX_ERR_INVALID;
     if (p->algo == DPX_ALGO_BSW && p->band < 1) return DPX_ERR_INVALID;
     /* the int32 kernels add a weight to a cell value (|H| <= 32767 after fits_int16) and to the affine kernels' virtual
      * -2^29 borders: weights beyond +-2^20 could wrap those sums (and no int16 matrix could hold what they produce) */
     const long long lim = 1ll << 20;
     for (long long w : {(long long)p->match, (long long)p->mismatch, (long long)p->gapOpen,
-                        p->algo == DPX_ALGO_ANW ? (long long)p->gapExtend : 0ll})
+                        is_affine(p->algo) ? (long long)p->gapExtend : 0ll})
         if (w > lim || w < -lim) return DPX_ERR_RANGE;
     return DPX_OK;
 }
@@ -727,6 +730,13 @@ static bool fits_int16(const dpx_params &p, long long m, long long n) {
         /* 0 <= H <= best diagonal run (+ positive gaps); the kernels also pack a column / step index into 16 bits */
         const long long top = diag + pos(p.gapOpen) * (m + n);
         return top <= lim && n <= 65000 && (m + n) <= 65000;
+    }
+    if (p.algo == DPX_ALGO_ASW) {
+        /* 0 <= H <= hiH as for ANW; I, D >= o + e (an open from H >= 0, then extensions never below it: D = max(H + o + e, ...));
+         * I, D <= hiH + o + e * max(m, n); the 16-bit column keys as for LSW */
+        const long long o = p.gapOpen, e = p.gapExtend;
+        const long long hiH = diag + (pos(o) + pos(e)) * (m + n);
+        return neg(o + e) >= -lim && hiH + pos(o) + pos(e) * std::max(m, n) <= lim && n <= 65000 && (m + n) <= 65000;
     }
     if (p.algo == DPX_ALGO_LNW) {
         const long long lo = neg(p.gapOpen) * (m + n), hi = diag + pos(p.gapOpen) * (m + n);
@@ -745,6 +755,11 @@ static bool fits_dir(const dpx_params &p, long long m, long long n) {
     auto neg = [](long long v) { return v < 0 ? v : 0; };
     const long long lim = 1ll << 28, diag = pos(std::max<long long>(p.match, p.mismatch)) * std::min(m, n);
     if (p.algo == DPX_ALGO_LSW) return diag + pos(p.gapOpen) * (m + n) <= lim;
+    if (p.algo == DPX_ALGO_ASW) { /* fits_int16's ASW bounds without the column keys (the direction fill keeps an int32 column per row) */
+        const long long o = p.gapOpen, e = p.gapExtend;
+        const long long hiH = diag + (pos(o) + pos(e)) * (m + n);
+        return neg(o + e) >= -lim && hiH + pos(o) + pos(e) * std::max(m, n) <= lim;
+    }
     if (p.algo == DPX_ALGO_LNW) return neg(p.gapOpen) * (m + n) >= -lim && diag + pos(p.gapOpen) * (m + n) <= lim;
     const long long o = p.gapOpen, e = p.gapExtend;
     const long long loH = 2 * neg(o) + neg(e) * (m + n), hiH = diag + (pos(o) + pos(e)) * (m + n);
@@ -769,7 +784,7 @@ static bool packed_safe(const dpx_params &p, long long m, long long n) {
 
 /* rows per lane of the lane-packed kernels: a pair of m rows takes ceil(m / 8) lanes (m <= 512); 16 rows per lane (two row
  * blocks) for the linear-gap kernels up to 1024 rows */
-static int lanes_rows(int maxM, int algo) { return (maxM <= 512 || algo == DPX_ALGO_ANW) ? 8 : 16; }
+static int lanes_rows(int maxM, int algo) { return (maxM <= 512 || is_affine(algo)) ? 8 : 16; }
 
 /* Pack pairs (`idx`, sorted by reference length, longest first) into waves of 64 lanes for the lane-packed kernels:
  * a pair takes ceil(m / R) consecutive lanes, a wave up to DPX_WAVE_SLOTS pairs whose staged references fit the wave's
@@ -1067,7 +1082,7 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
     b->flags = flags;
     b->numPairs = numPairs;
     b->store = !(flags & DPX_SCORE_ONLY);
-    b->planes = params->algo == DPX_ALGO_ANW ? 3 : 1;
+    b->planes = is_affine(params->algo) ? 3 : 1;
     b->dirs = dirs;
     b->pairs.resize(numPairs);
 
@@ -1095,10 +1110,10 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
     /* rows per lane: smallest tile that keeps short queries in one stripe, 8 (or DPX_R) otherwise */
     /* linear gaps: 16 rows per lane once a query is longer than 512 (one stripe up to 1024 rows, two 1-KiB sub-tiles per
      * step: measured 4 % faster than 8 rows x 2 rolling stripes); the affine kernel carries three chains and stays at 8 */
-    int R = b->maxM <= 128 ? 2 : b->maxM <= 256 ? 4 : (b->maxM <= 512 || params->algo == DPX_ALGO_ANW) ? 8 : 16;
+    int R = b->maxM <= 128 ? 2 : b->maxM <= 256 ? 4 : (b->maxM <= 512 || is_affine(params->algo)) ? 8 : 16;
     if (kn.rowsPerLane) {
         const int v = kn.rowsPerLane;
-        if (v == 2 || v == 4 || v == 8 || (v == 16 && params->algo != DPX_ALGO_ANW)) R = v;
+        if (v == 2 || v == 4 || v == 8 || (v == 16 && !is_affine(params->algo))) R = v;
     }
     if (dirs) { /* direction kernels: LSW keeps per-row best cells and stays at <= 8 rows per lane (VGPRs), ANW at <= 8 as always */
         R = b->maxM <= 128 ? 2 : b->maxM <= 256 ? 4 : (b->maxM <= 512 || params->algo != DPX_ALGO_LNW) ? 8 : 16;
@@ -1143,7 +1158,7 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
 
     /* LDS per wave: edge row(s) of int16 [n+2] + staged reference [n+128] */
     const size_t edgeBytes = align_up((size_t)(b->maxN + 2) * 2, 16);
-    const size_t nEdges = params->algo == DPX_ALGO_ANW ? 2 : 1;
+    const size_t nEdges = is_affine(params->algo) ? 2 : 1; /* H and D */
     /* (+16 everywhere: a staged string starts up to 15 bytes into its buffer, at its own address mod 16 -- stage_bytes) */
     const size_t refBytes = align_up((size_t)b->maxN + 128 + 16, 16);
     const size_t qBytes = align_up((size_t)b->maxM + 64 + 32, 16); /* banded kernel: staged query + 64 B of index slack */
@@ -1177,7 +1192,7 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
      * fill the chip with a fraction of the waves run several pairs per wave, ceil(m/8) lanes each (k_linear_lanes /
      * k_affine_lanes, tile layout); DPX_LANES=0/1 overrides. */
     const bool linearAlgo = kernelAlgo == DPX_ALGO_LNW || kernelAlgo == DPX_ALGO_LSW;
-    const bool lanesAlgo = linearAlgo || kernelAlgo == DPX_ALGO_ANW;
+    const bool lanesAlgo = linearAlgo || is_affine(kernelAlgo); /* (ANW: k_affine_lanes, ASW: k_asw_lanes) */
     /* (the staged references of a wave's pairs share its LDS: keep the path to references that leave the request small) */
     /* Packed lane kernel (round 3, k_linear_lanes_pk): 16 rows per lane as two 8-row blocks of the SAME pair in the two halves of every
      * register.  Needs the 16-bit wrapping adds to be safe (packed_safe), room below the smallest border for its "minus infinity"
@@ -1594,7 +1609,7 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
         k.ldsPerWave = (uint32_t)(dpx_lanes_stage_bytes(kernelAlgo, kLanesR, b->store) + lanesRefArea);
         /* (the lane-packed kernels keep their four-wave workgroups at every size: 20 000 short reads 131-148 us against 150-153 with one-wave
          * workgroups, 100 000 the same; DPX_WPB=1 forces the latter) */
-        k.wavesPerBlock = kernelAlgo == DPX_ALGO_ANW ? 1u : (kn.wavesPerBlock == 1 ? 1u : (uint32_t)dpx_lanes_waves_per_block(kernelAlgo));
+        k.wavesPerBlock = is_affine(kernelAlgo) ? 1u : (kn.wavesPerBlock == 1 ? 1u : (uint32_t)dpx_lanes_waves_per_block(kernelAlgo));
         b->pkLdsBytes = (size_t)k.ldsPerWave * (size_t)k.wavesPerBlock;
         if (b->pkLdsBytes > 160u * 1024u) { dpx_batch_destroy(b); return DPX_ERR_UNSUPPORTED; }
     }
@@ -1896,7 +1911,7 @@ static int output_begin(dpx_batch *b, uint64_t firstNumber) {
          * DPX_TB_WALK=0/1/2 forces one (tests). */
         int walk = b->numPairs >= 65536 ? 1 : 0;
         if (b->kernelAlgo == DPX_ALGO_LSW || b->kernelAlgo == DPX_ALGO_LNW || b->kernelAlgo == DPX_ALGO_BSW) walk = 2;
-        else if (b->kernelAlgo == DPX_ALGO_ANW && b->numPairs <= 20000) walk = 2;
+        else if (is_affine(b->kernelAlgo) && b->numPairs <= 20000) walk = 2; /* (ASW: as ANW; its walk 1 is walk 0) */
         { const int w = knobs().tbWalk; if (w >= 0) walk = std::min(2, w); }
         if (b->dirs) HIP_TRY(dpx_launch_traceback_dir(b->dirArgs, (int)np, b->kernelAlgo, b->R, b->dTbOff, b->dTb, b->dTbLen, b->stream));
         else HIP_TRY(dpx_launch_traceback(b->args, (int)np, b->kernelAlgo, b->R, b->planes, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream));
@@ -2054,10 +2069,11 @@ int dpx_batch_traceback(dpx_batch *b, size_t pair, char *refLine, char *relLine,
 
 int dpx_batch_describe(dpx_batch *b, char *buf, size_t cap) {
     if (!b || !buf || !cap) return DPX_ERR_INVALID;
-    static const char *names[] = {"LNW", "LSW", "ANW", "BSW"};
+    static const char *names[] = {"LNW", "LSW", "ANW", "BSW", "ASW"};
     const char *kernel = b->kernelAlgo == DPX_ALGO_BSW ? (b->packed ? "k_banded_fill_pk" : "k_banded_fill") : b->kernelAlgo == DPX_ALGO_ANW ? (b->lanePacked ? "k_affine_lanes" : "k_affine_fill")
+                         : b->kernelAlgo == DPX_ALGO_ASW ? (b->lanePacked ? "k_asw_lanes" : "k_asw_fill")
                          : b->packed ? "k_linear_fill_pk" : b->lanesPk ? "k_linear_lanes_pk" : b->lanePacked ? "k_linear_lanes" : b->split ? "k_linear_split" : "k_linear_fill";
-    if (b->dirs) kernel = b->kernelAlgo == DPX_ALGO_ANW ? "k_affine_dir" : "k_linear_dir";
+    if (b->dirs) kernel = b->kernelAlgo == DPX_ALGO_ANW ? "k_affine_dir" : b->kernelAlgo == DPX_ALGO_ASW ? "k_asw_dir" : "k_linear_dir";
     /* dtype = the arithmetic type of the kernel that fills (most of) the batch */
     int len = snprintf(buf, cap, "algo=%s kernel_algo=%s kernel=%s dtype=%s rows_per_lane=%d store=%d couples=%zu lane_pairs=%zu waves=%zu singles=%zu row_tags=%d seq_input=%s waves_per_workgroup=%u",
                        names[b->prm.algo], names[b->kernelAlgo], kernel, (b->packed || b->lanesPk) ? "int16" : "int32", b->R, b->store ? 1 : 0, b->nCouples, b->nLanePairs,

@@ -207,115 +207,15 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_linear_dir(const dpx_dir_a
  * ===================================================================================================== */
 template <int R, bool GLOBAL>
 __global__ void __launch_bounds__(DPX_FILL_THREADS) k_affine_dir(const dpx_dir_args a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int G = 32 / R;
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int slot = blockIdx.x * (int)a.wavesPerBlock + wv; /* in this launch (the scratch area's index) */
-    if (a.firstSlot + slot >= a.numPairs) return;
-    const int p = a.order ? a.order[a.firstSlot + slot] : a.firstSlot + slot;
-    const dpx_pair_dev pr = a.pairs[p];
-    const int n = pr.n, m = pr.m;
-    const int match = a.match, mismatch = a.mismatch;
-    const int o = a.gapOpen, e = a.gapExtend, oe = o + e;
+    constexpr bool LOCAL = false;
+#include "dpx_affine_dir.inc"
+}
 
-    if (m <= 0 || n <= 0) {
-        if (lane == 0) { /* H[m][n] on the border: 0 at the origin, else o + len*e (AffineNeedlemanWunsch.cpp:43-53) */
-            const int len = m <= 0 ? max(n, 0) : m;
-            a.score[p] = len <= 0 ? 0 : o + len * e;
-            a.endRow[p] = max(m, 0);
-            a.endCol[p] = max(n, 0);
-        }
-        return;
-    }
-    const unsigned char *ref = reinterpret_cast<const unsigned char *>(a.seq + pr.refIdx);
-    const unsigned char *qry = reinterpret_cast<const unsigned char *>(a.seq + pr.qryIdx);
-    unsigned char *my;
-    if constexpr (GLOBAL) my = a.scratch + (size_t)slot * a.ldsPerWave;
-    else my = smem + (size_t)wv * a.ldsPerWave;
-    int32_t *edgeH = reinterpret_cast<int32_t *>(my);
-    int32_t *edgeD = reinterpret_cast<int32_t *>(my + a.ldsEdge2Off);
-    const unsigned char *refl = dir_stage(my + a.ldsRefOff + 64, ref, n, lane) - 64;
-    for (int x = lane; x <= n + 1; x += 64) { edgeH[x] = o + x * e; edgeD[x] = DPX_NEG; } /* H[0][j] (:50-53), virtual D[0][j] */
-    if constexpr (GLOBAL) __threadfence_block();
-
-    const int S = dpx_tiled_stripes(m, R);
-    const int Wp = (int)dpx_dir_stripe_steps(n, R);
-    const size_t cs = (size_t)pr.chunkStride * 2u;
-    unsigned char *cbase = a.codes + (size_t)pr.matOff * 2u + (size_t)lane * 16u;
-
-    int Hl[R], Il[R], qc[R];
-    for (int k = 0; k < S; k++) {
-        const int row0 = k * 64 * R + lane * R;
-        const int nrows = min(max(m - row0, 0), R);
-        const bool hasRows = nrows > 0, hasNext = k + 1 < S;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            qc[r] = r < nrows ? (int)qry[row0 + r] : 0x100;
-            Hl[r] = o + (row0 + 1 + r) * e; /* H[i][0] = o + i*e (:43-46) */
-            Il[r] = DPX_NEG;                /* virtual I[i][0] */
-        }
-        int dBot = DPX_NEG;                 /* D of the lane's bottom row, for the lane below */
-        int dtop = row0 == 0 ? 0 : o + row0 * e;
-        const unsigned char *rp = refl + 64 - lane;
-        int rcN = rp[0];
-        int eHN = edgeH[1], eDN = edgeD[1];
-        unsigned char *dst = cbase + (size_t)k * (size_t)(Wp / G) * cs;
-        for (int t0 = 0; t0 < Wp; t0 += G) {
-            uint32_t acc[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-            for (int q = 0; q < G; q++) {
-                const int t = t0 + q;
-                const int rc = rcN, eH = eHN, eD = eDN;
-                rcN = rp[t + 1];
-                eHN = edgeH[min(t + 2, n + 1)];
-                eDN = edgeD[min(t + 2, n + 1)];
-                const int upH = wave_shr1(Hl[R - 1], eH);
-                const int upD = wave_shr1(dBot, eD);
-                const int j = t - lane + 1;
-                uint32_t w[2] = {0u, 0u};
-                if (hasRows && j >= 1 && j <= n) {
-                    int uH = upH, uD = upD, d = dtop;
-#pragma unroll
-                    for (int r = 0; r < R; r++) {
-                        const int lH = Hl[r];
-                        const int s = (qc[r] == rc) ? match : mismatch;
-                        const int dOpen = uH + oe, dExt = uD + e; /* :185-197 */
-                        const int Dn = max(dOpen, dExt);
-                        const int iOpen = lH + oe, iExt = Il[r] + e; /* :201-213 */
-                        const int In = max(iOpen, iExt);
-                        const int mm = d + s; /* :216-236 */
-                        const int v = max(Dn, mm);
-                        const int h = max(In, v);
-                        uint32_t code = In >= v ? 3u : (Dn >= mm ? 2u : 1u);
-                        code |= (iOpen >= iExt ? 0u : 4u) | (dOpen >= dExt ? 0u : 8u);
-                        w[(r * 4) >> 5] |= code << ((r * 4) & 31);
-                        d = lH;
-                        uH = h;
-                        uD = Dn;
-                        Hl[r] = h;
-                        Il[r] = In;
-                    }
-                    dBot = uD;
-                    dtop = upH;
-                    if (hasNext && lane == 63) { edgeH[j] = Hl[R - 1]; edgeD[j] = dBot; }
-                }
-                dir_put<R>(acc, q, w[0], w[1]);
-            }
-            dir_store(dst + (size_t)(t0 / G) * cs, acc);
-        }
-        if constexpr (GLOBAL) __threadfence_block();
-    }
-    const int lastBase = (S - 1) * 64 * R;
-    const int lm = (m - 1 - lastBase) / R, rm = (m - 1 - lastBase) % R;
-    if (lane == lm) {
-        int v = Hl[0];
-#pragma unroll
-        for (int r = 1; r < R; r++) v = (r == rm) ? Hl[r] : v;
-        a.score[p] = v; /* scoringMemo[m][n] (:365) */
-        a.endRow[p] = m;
-        a.endCol[p] = n;
-    }
+/* ASW (affine-gap Smith-Waterman, include/dpx_align.h): the same fill with the zero floor; code move 0 where H == 0, bits 2 / 3 as ANW */
+template <int R, bool GLOBAL>
+__global__ void __launch_bounds__(DPX_FILL_THREADS) k_asw_dir(const dpx_dir_args a) {
+    constexpr bool LOCAL = true;
+#include "dpx_affine_dir.inc"
 }
 
 /* ---- the walk over the codes: one WAVE per pair, runs of path steps decided by all 64 lanes at once ----
@@ -360,7 +260,8 @@ __global__ void __launch_bounds__(64) k_traceback_dir(const dpx_dir_args a, int 
         pos -= cnt; j -= cnt;
     };
     int cur = 0; /* ANW: 0 SCORING, 1 INSERTION, 2 DELETION */
-    bool done = algo == DPX_K_LSW ? !(a.score[p] > 0 && i > 0 && j > 0) : false; /* LSW score 0: no path (LinearSmithWaterman.cpp:253-257) */
+    const bool affine = algo == DPX_K_ANW || algo == DPX_K_ASW; /* three states; ASW also stops where H == 0 (move 0) */
+    bool done = (algo == DPX_K_LSW || algo == DPX_K_ASW) ? !(a.score[p] > 0 && i > 0 && j > 0) : false; /* score 0: no path (LinearSmithWaterman.cpp:253-257) */
     while (!done) {
         if (algo == DPX_K_LNW && (i == 0 || j == 0)) { /* borders: row 0 is QUERY_INSERTION, column 0 QUERY_DELETION */
             tail_left(j);
@@ -377,9 +278,9 @@ __global__ void __launch_bounds__(64) k_traceback_dir(const dpx_dir_args a, int 
         if (algo == DPX_K_LSW && (c0 & 4)) break; /* arrived on H == 0 (:222) -- the start cell has H > 0 */
         const int mv = c0 & 3;
         int kind = mv == 3 ? 3 : mv == 2 ? 2 : 1; /* LNW / ANW: anything but up / left is the diagonal */
-        if (algo == DPX_K_LSW && mv == 0) break;
-        if (algo == DPX_K_ANW && cur != 0) kind = cur == 1 ? 3 : 2;
-        if (algo == DPX_K_ANW && kind != 1) { /* a gap: step l is taken while the cells before it extend (bit 2 for I, bit 3 for D) */
+        if ((algo == DPX_K_LSW || (algo == DPX_K_ASW && cur == 0)) && mv == 0) break;
+        if (affine && cur != 0) kind = cur == 1 ? 3 : 2;
+        if (affine && kind != 1) { /* a gap: step l is taken while the cells before it extend (bit 2 for I, bit 3 for D) */
             const int c = kind == 3 ? cL : cU, bit = kind == 3 ? 4 : 8;
             const int k = dir_run(c >= 0 && (c & bit));
             const int steps = k == 64 ? 64 : k + 1; /* (an extension never reaches row / column 0: the virtual borders open) */
@@ -396,6 +297,7 @@ __global__ void __launch_bounds__(64) k_traceback_dir(const dpx_dir_args a, int 
         const int c = kind == 1 ? cD : kind == 2 ? cU : cL;
         bool ok = c >= 0;
         if (algo == DPX_K_LSW) ok = ok && (c & 3) == kind && (lane == 0 || !(c & 4));
+        else if (algo == DPX_K_ASW) ok = ok && (c & 3) == 1; /* (a cell with H == 0 ends the run: move 0) */
         else if (kind == 1) ok = ok && (c & 3) != 2 && (c & 3) != 3;
         else ok = ok && (c & 3) == kind;
         const int steps = dir_run(ok); /* >= 1: lane 0 is the walker's cell */
@@ -426,7 +328,7 @@ __global__ void __launch_bounds__(256) k_export_dir(const unsigned char *codes, 
     const int i = (int)(idx / (uint64_t)(n + 1)), j = (int)(idx % (uint64_t)(n + 1));
     uint8_t v;
     if (i == 0 || j == 0) {
-        if (which != 0 || algo == DPX_K_LSW || (i == 0 && j == 0)) v = 0;
+        if (which != 0 || algo == DPX_K_LSW || algo == DPX_K_ASW || (i == 0 && j == 0)) v = 0; /* (SW borders hold H = 0: NONE) */
         else v = (j == 0) ? 4 : 3; /* column 0: QUERY_DELETION, row 0: QUERY_INSERTION */
     } else {
         int sh;
@@ -476,6 +378,11 @@ hipError_t launch_affine_dir_R(const dpx_dir_args &a, hipStream_t s) {
     return a.scratch ? dir_launch(k_affine_dir<R, true>, a, s) : dir_launch(k_affine_dir<R, false>, a, s);
 }
 
+template <int R>
+hipError_t launch_asw_dir_R(const dpx_dir_args &a, hipStream_t s) {
+    return a.scratch ? dir_launch(k_asw_dir<R, true>, a, s) : dir_launch(k_asw_dir<R, false>, a, s);
+}
+
 } // namespace
 
 hipError_t dpx_launch_fill_dir(const dpx_dir_args &a, int algo, int R, hipStream_t stream) {
@@ -485,6 +392,14 @@ hipError_t dpx_launch_fill_dir(const dpx_dir_args &a, int algo, int R, hipStream
         case 2: return launch_affine_dir_R<2>(a, stream);
         case 4: return launch_affine_dir_R<4>(a, stream);
         case 8: return launch_affine_dir_R<8>(a, stream);
+        default: return hipErrorInvalidValue;
+        }
+    }
+    if (algo == DPX_K_ASW) {
+        switch (R) {
+        case 2: return launch_asw_dir_R<2>(a, stream);
+        case 4: return launch_asw_dir_R<4>(a, stream);
+        case 8: return launch_asw_dir_R<8>(a, stream);
         default: return hipErrorInvalidValue;
         }
     }

@@ -12,6 +12,7 @@
 #define DPX_K_LSW 1
 #define DPX_K_ANW 2
 #define DPX_K_BSW 3
+#define DPX_K_ASW 4 /* affine-gap Smith-Waterman: the ANW kernels' Gotoh recurrence with LSW's zero floor and start cell */
 
 /* one wave per pair; DPX_FILL_THREADS/64 independent waves share a workgroup (no barriers between them) */
 #ifndef DPX_FILL_THREADS

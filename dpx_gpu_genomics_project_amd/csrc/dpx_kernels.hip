@@ -1439,18 +1439,21 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_linear_lanes_pk(const dpx_
  *   H[i][j] = max(I, max(D, H[i-1][j-1]+s))                                                (:229-236)
  * The i==1 / j==1 special cases are expressed by virtual borders D[0][j] = I[i][0] = DPX_NEG, which gives the
  * identical values for every stored cell.  Three int16 planes (H, I, D) are written per step.
+ * Affine-gap Smith-Waterman (ASW, LOCAL = true) shares the body: H = max(0, ...) with zero borders, and the start cell is tracked
+ * as in k_linear_fill (per-row (H << 16 | 0xFFFF - j) keys folded per stripe, one wave reduction at the end).
  * ===================================================================================================== */
 template <int R>
 struct AffState {
     int Hl[R], Il[R]; /* H[row][j-1], I[row][j-1] */
     int Dl[R];        /* D[row][j] just computed (needed only for the store and the lane hand-off) */
     int qc[R];
+    unsigned key[R];  /* ASW: per-row running max of (H << 16 | 0xFFFF - j) */
     int dtop;
 };
 
-template <int R>
+template <int R, bool LOCAL>
 __device__ __forceinline__ void aff_cells(AffState<R> &st, const int upH, const int upD, const int rc, const int match,
-                                          const int mismatch, const int oe, const int e) {
+                                          const int mismatch, const int oe, const int e, const unsigned negj) {
     int uH = upH, uD = upD, d = st.dtop;
 #pragma unroll
     for (int r = 0; r < R; r++) {
@@ -1458,7 +1461,11 @@ __device__ __forceinline__ void aff_cells(AffState<R> &st, const int upH, const 
         const int s = (st.qc[r] == rc) ? match : mismatch;
         const int Dn = max(uH + oe, uD + e);
         const int In = max(lH + oe, st.Il[r] + e);
-        const int h = max(max(Dn, d + s), In); /* v_max3_i32 */
+        int h = max(max(Dn, d + s), In); /* v_max3_i32 */
+        if constexpr (LOCAL) {
+            h = max(h, 0);
+            st.key[r] = max(st.key[r], ((unsigned)h << 16) | negj);
+        }
         d = lH;
         uH = h;
         uD = Dn;
@@ -1469,7 +1476,7 @@ __device__ __forceinline__ void aff_cells(AffState<R> &st, const int upH, const 
     st.dtop = upH;
 }
 
-template <int R, bool STORE, bool MASKED, bool WHOLE>
+template <int R, bool LOCAL, bool STORE, bool MASKED, bool WHOLE>
 __device__ __forceinline__ void aff_step(AffState<R> &st, const int t, const int lane, const int n, const bool laneHasRows,
                                          const int match, const int mismatch, const int oe, const int e, const int e0H,
                                          const int e0D, const int rc, int16_t *edgeH, int16_t *edgeD,
@@ -1480,7 +1487,7 @@ __device__ __forceinline__ void aff_step(AffState<R> &st, const int t, const int
     bool active = true;
     if constexpr (MASKED) active = laneHasRows && (j >= 1) && (j <= n);
     if (active) {
-        aff_cells<R>(st, upH, upD, rc, match, mismatch, oe, e);
+        aff_cells<R, LOCAL>(st, upH, upD, rc, match, mismatch, oe, e, 0xFFFFu - (unsigned)j);
         if (writeEdge && lane == 63) {
             edgeH[j] = (int16_t)st.Hl[R - 1];
             edgeD[j] = (int16_t)st.Dl[R - 1];
@@ -1502,175 +1509,58 @@ __device__ __forceinline__ void aff_step(AffState<R> &st, const int t, const int
     }
 }
 
+/* ASW: fold per-row (H << 16 | 0xFFFF - j) keys into the lane's best (lin_fold_keys) */
+template <int R>
+__device__ __forceinline__ void fold_row_keys(const unsigned (&key)[R], const int row0, const int nrows, int &bestv, int &bestrow, int &bestcol) {
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const int hv = (int)(key[r] >> 16), col = 0xFFFF - (int)(key[r] & 0xFFFFu);
+        if (r < nrows && hv > bestv) {
+            bestv = hv;
+            bestrow = row0 + 1 + r;
+            bestcol = col;
+        }
+    }
+}
+
+/* ASW: fold a finished stripe's per-row keys into the lane's best (lin_fold_keys) */
+template <int R>
+__device__ __forceinline__ void aff_fold_keys(const AffState<R> &st, const int row0, const int nrows, int &bestv, int &bestrow, int &bestcol) {
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const int hv = (int)(st.key[r] >> 16), col = 0xFFFF - (int)(st.key[r] & 0xFFFFu);
+        if (r < nrows && hv > bestv) {
+            bestv = hv;
+            bestrow = row0 + 1 + r;
+            bestcol = col;
+        }
+    }
+}
+
+/* first strict maximum in row-major order over the lanes' bests (k_linear_fill, c++/LinearSmithWaterman.cpp:145-157) */
+__device__ __forceinline__ void sw_publish(const dpx_fill_args &a, const int p, const int lane, const int bestv, const int bestrow, const int bestcol) {
+    const unsigned long long mine = ((unsigned long long)(unsigned)bestv << 32) | (unsigned)(0x7FFFFFFF - bestrow);
+    const unsigned long long top = wave_max_u64(mine);
+    if ((int)(top >> 32) == 0) {
+        if (lane == 0) { a.score[p] = 0; a.endRow[p] = 0; a.endCol[p] = 0; }
+    } else if (mine == top) { /* rows are unique per lane: exactly one lane matches, and it holds the row's first column */
+        a.score[p] = bestv;
+        a.endRow[p] = bestrow;
+        a.endCol[p] = bestcol;
+    }
+}
+
+/* one wave per pair: k_affine_fill (ANW) and k_asw_fill (ASW) share their body, dpx_affine_fill.inc */
 template <int R, bool STORE>
 __global__ void __launch_bounds__(DPX_FILL_THREADS) k_affine_fill(const dpx_fill_args a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int p = blockIdx.x * (int)a.wavesPerBlock + wv;
-    if (p >= a.numPairs) return;
-    if (a.order) p = a.order[p];
-    const dpx_pair_dev pr = a.pairs[p];
-    const int n = pr.n, m = pr.m;
-    const int match = a.match, mismatch = a.mismatch;
-    const int o = a.gapOpen, e = a.gapExtend, oe = o + e;
-
-    if (m <= 0 || n <= 0) {
-        if (lane == 0) { /* H[m][n] on the border: 0 at the origin, else o + len*e (AffineNeedlemanWunsch.cpp:43-53) */
-            const int len = m <= 0 ? max(n, 0) : m;
-            a.score[p] = len <= 0 ? 0 : o + len * e;
-            a.endRow[p] = max(m, 0);
-            a.endCol[p] = max(n, 0);
-        }
-        return;
-    }
-    const unsigned char *ref = reinterpret_cast<const unsigned char *>(a.seq + pr.refIdx);
-    const unsigned char *qry = reinterpret_cast<const unsigned char *>(a.seq + pr.qryIdx);
-    unsigned char *my = smem + (size_t)wv * a.ldsPerWave;
-    int16_t *edgeH = reinterpret_cast<int16_t *>(my);
-    int16_t *edgeD = reinterpret_cast<int16_t *>(my + a.ldsEdge2Off);
-    const unsigned char *refl = stage_bytes(my + a.ldsRefOff + 64, ref, n, lane, 64) - 64;
-    /* row-0 border H[0][j] = o + j*e (AffineNeedlemanWunsch.cpp:50-53); D[0][j] is the virtual DPX_NEG (k == 0 below) */
-    for (int x = lane; x <= n + 1; x += 64) { edgeH[x] = (int16_t)(o + x * e); edgeD[x] = 0; }
-
-    int16_t *Mp = a.mat + pr.matOff;
-    const int W = n + 63;
-    const int S = dpx_tiled_stripes(m, R);
-    AffState<R> st;
-
-    if (STORE && S >= 2 && n >= 128) {
-        /* ---------- rolling schedule (see k_linear_fill): lanes run straight on into the next stripe ---------- */
-        const unsigned char *ql = stage_bytes(my + a.ldsQryOff, qry, m, lane, 64);
-        int row0 = lane * R;
-        int nrows = min(max(m - row0, 0), R);
-        int jl = 1 - lane, kl = 0;
-        load_query_rows<R>(st.qc, qry, row0, nrows);
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            st.Hl[r] = o + (row0 + 1 + r) * e;
-            st.Il[r] = DPX_NEG;
-            st.Dl[r] = DPX_NEG;
-        }
-        st.dtop = row0 == 0 ? 0 : o + row0 * e;
-        int j0 = 1;
-        bool sw = false;
-        int rcN = refl[63 + jl];
-        int eHN = edgeH[1];
-        int eDN = DPX_NEG; /* lane 0 is in stripe 0 first: virtual D[0][j] */
-        const size_t cs = pr.chunkStride;
-        int16_t *tile = Mp + (size_t)lane * R;
-        const int total = S * n + 63;
-        auto roll_step = [&](const int T) {
-            const int rc = rcN, eH = eHN, eD = eDN;
-            const int jn = (jl >= n) ? 1 : jl + 1;
-            rcN = refl[63 + jn];
-            j0 = (j0 >= n) ? 1 : j0 + 1;
-            eHN = edgeH[j0];
-            eDN = (T + 1 < n) ? DPX_NEG : (int)edgeD[j0]; /* lane 0 leaves stripe 0 after n steps */
-            const int upH = wave_shr1(st.Hl[R - 1], eH);
-            const int upD = wave_shr1(st.Dl[R - 1], eD);
-            if (sw) {
-                row0 += 64 * R;
-                nrows = min(max(m - row0, 0), R);
-#pragma unroll
-                for (int r = 0; r < R; r++) {
-                    st.qc[r] = (r < nrows) ? (int)ql[row0 + r] : 0x100;
-                    st.Hl[r] = o + (row0 + 1 + r) * e;
-                    st.Il[r] = DPX_NEG;
-                    st.Dl[r] = DPX_NEG;
-                }
-                st.dtop = o + row0 * e;
-            }
-            if (jl >= 1 && kl < S && nrows > 0) {
-                aff_cells<R>(st, upH, upD, rc, match, mismatch, oe, e);
-                if (lane == 63 && kl + 1 < S) {
-                    edgeH[jl] = (int16_t)st.Hl[R - 1];
-                    edgeD[jl] = (int16_t)st.Dl[R - 1];
-                }
-            }
-            if constexpr (STORE) {
-                if (ramp_stores<R>(lane, T, S * n, a.rampLines)) { /* on the pair's two ramps only the lines with cells */
-                    int16_t *dst = tile + (size_t)T * cs;
-                    store_tile<R>(dst, st.Hl);
-                    store_tile<R>(dst + 64 * R, st.Il);
-                    store_tile<R>(dst + 128 * R, st.Dl);
-                }
-            }
-            sw = false;
-            if (jl >= n) { jl = 1; kl++; sw = kl < S; }
-            else jl++;
-        };
-        int T = 0;
-        for (; T + 1 < total; T += 2) {
-            roll_step(T);
-            roll_step(T + 1);
-        }
-        if (T < total) roll_step(T);
-    } else {
-    for (int k = 0; k < S; k++) {
-            const int base = k * 64 * R;
-            const int row0 = base + lane * R;
-            const int nrows = min(max(m - row0, 0), R);
-            const bool laneHasRows = nrows > 0;
-            const bool hasNext = (k + 1 < S);
-            load_query_rows<R>(st.qc, qry, row0, nrows);
-    #pragma unroll
-            for (int r = 0; r < R; r++) {
-                st.Hl[r] = o + (row0 + 1 + r) * e; /* H[i][0] = o + i*e (:43-46) */
-                st.Il[r] = DPX_NEG;                /* virtual I[i][0] */
-                st.Dl[r] = DPX_NEG;
-            }
-            st.dtop = row0 == 0 ? 0 : o + row0 * e; /* H[0][0] = 0 */
-            const size_t cs = pr.chunkStride;
-            int16_t *tile = Mp + (size_t)k * (size_t)n * cs + (size_t)lane * R;
-    
-            const unsigned char *rp = refl + 64 - lane;
-            int rcN = rp[0];
-            int eHN = edgeH[1];
-            int eDN = k == 0 ? DPX_NEG : (int)edgeD[1];
-    #define DPX_AFF_STEP(MASKED_, WHOLE_, HASROWS_)                                                                               \
-            {                                                                                                             \
-                const int rc = rcN, eH = eHN, eD = eDN;                                                                   \
-                rcN = rp[t + 1];                                                                                          \
-                eHN = edgeH[min(t + 2, n + 1)];                                                                           \
-                eDN = k == 0 ? DPX_NEG : (int)edgeD[min(t + 2, n + 1)];                                                   \
-                aff_step<R, STORE, MASKED_, WHOLE_>(st, t, lane, n, HASROWS_, match, mismatch, oe, e, eH, eD, rc, edgeH, edgeD, \
-                                            hasNext, tile + (size_t)t * cs, storeLanes, a.rampLines);                     \
-            }
-            const bool fast = (base + 64 * R <= m) && (n >= 64);
-            const int storeLanes = (S == 1) ? store_lanes<R>(m) : 64;
-            if (S == 1) {
-                if (fast) {
-                    int t = 0;
-                    for (; t < 63; t++) DPX_AFF_STEP(true, true, true)
-                    for (; t + 1 < n;) { DPX_AFF_STEP(false, true, true) t++; DPX_AFF_STEP(false, true, true) t++; } /* two steps per trip */
-                    for (; t < n; t++) DPX_AFF_STEP(false, true, true)
-                    for (; t < W; t++) DPX_AFF_STEP(true, true, true)
-                } else {
-                    for (int t = 0; t < W; t++) DPX_AFF_STEP(true, true, laneHasRows)
-                }
-            } else if (fast) { /* stripes share their ramp chunks: masked stores on the ramps */
-                int t = 0;
-                for (; t < 63; t++) DPX_AFF_STEP(true, false, true)
-                for (; t + 1 < n;) { DPX_AFF_STEP(false, false, true) t++; DPX_AFF_STEP(false, false, true) t++; }
-                for (; t < n; t++) DPX_AFF_STEP(false, false, true)
-                for (; t < W; t++) DPX_AFF_STEP(true, false, true)
-            } else {
-                for (int t = 0; t < W; t++) DPX_AFF_STEP(true, false, laneHasRows)
-            }
-    #undef DPX_AFF_STEP
-        }
+    constexpr bool LOCAL = false;
+#include "dpx_affine_fill.inc"
 }
-    const int lastBase = (S - 1) * 64 * R;
-    const int lm = (m - 1 - lastBase) / R, rm = (m - 1 - lastBase) % R;
-    if (lane == lm) {
-        int v = st.Hl[0];
-#pragma unroll
-        for (int r = 1; r < R; r++) v = (r == rm) ? st.Hl[r] : v;
-        a.score[p] = v; /* scoringMemo[m][n] (:365) */
-        a.endRow[p] = m;
-        a.endCol[p] = n;
-    }
+
+template <int R, bool STORE>
+__global__ void __launch_bounds__(DPX_FILL_THREADS) k_asw_fill(const dpx_fill_args a) {
+    constexpr bool LOCAL = true;
+#include "dpx_affine_fill.inc"
 }
 
 /* Affine lane-packed kernel: the Gotoh recurrence of k_affine_fill on the several-pairs-per-wave schedule of
@@ -1690,12 +1580,13 @@ struct AffStateG {
     int qc[R];
     int dtopOe;        /* H[row0][j-1] + (o+e) */
     int DeLast;        /* D[row0+R][j] + e of the column just computed (the next lane's "D above") */
+    unsigned key[R];   /* ASW: per-row running max of (H << 16 | 0xFFFF - j) */
 };
 
 /* D = max(H_up + oe, D_up + e);  I = max(H_left + oe, I_left + e);  H = max3(D, H_diag + s, I)   (c++/AffineNeedlemanWunsch.cpp:185-236) */
-template <int R>
+template <int R, bool LOCAL>
 __device__ __forceinline__ void aff_cells_g(AffStateG<R> &st, const int upHoe, const int upDe, const int rc, const int matchG, const int mismatchG,
-                                            const int oe, const int e, int (&Hv)[R], int (&Iv)[R], int (&Dv)[R]) {
+                                            const int oe, const int e, int (&Hv)[R], int (&Iv)[R], int (&Dv)[R], const unsigned negj) {
     int dterm[R];
 #pragma unroll
     for (int r = 0; r < R; r++) dterm[r] = ((r == 0) ? st.dtopOe : st.Hoe[r - 1]) + ((st.qc[r] == rc) ? matchG : mismatchG); /* (s - oe) */
@@ -1704,7 +1595,11 @@ __device__ __forceinline__ void aff_cells_g(AffStateG<R> &st, const int upHoe, c
     for (int r = 0; r < R; r++) {
         const int Dn = max(ug, ud);
         const int In = max(st.Hoe[r], st.Ie[r]);
-        const int h = max(max(Dn, dterm[r]), In); /* v_max3_i32 */
+        int h = max(max(Dn, dterm[r]), In); /* v_max3_i32 */
+        if constexpr (LOCAL) { /* ASW: the zero floor, and the row's start-cell key */
+            h = max(h, 0);
+            st.key[r] = max(st.key[r], ((unsigned)h << 16) | negj);
+        }
         Hv[r] = h; Iv[r] = In; Dv[r] = Dn;
         ug = h + oe;
         ud = Dn + e;
@@ -1717,136 +1612,14 @@ __device__ __forceinline__ void aff_cells_g(AffStateG<R> &st, const int upHoe, c
 
 template <int R, bool STORE>
 __global__ void __launch_bounds__(DPX_ALANES_THREADS) k_affine_lanes(const dpx_fill_args a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    static_assert(R == 8, "one 8-row block per lane");
-    constexpr int kPlane = 64 * kStageLine; /* bytes of one plane's lines */
-    constexpr int kStageBytes = 3 * kPlane;
-    constexpr int kStepElems = 3 * 512;     /* int16 elements of one chunk of the wave's stream (dpx_layout.h) */
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int w = blockIdx.x * (DPX_ALANES_THREADS / 64) + wv;
-    if (w >= a.numPairs) return; /* wave-uniform; numPairs = number of wave descriptors */
-    const LaneSlot sl = find_slot(a.waves + w, lane);
-    const bool has = sl.has;
-    const int p = sl.p, l = sl.l;
-    const dpx_pair_dev pr = a.pairs[p];
-    const int n = has ? pr.n : 0, m = has ? pr.m : 0;
-    const int o = a.gapOpen, e = a.gapExtend, oe = o + e;
-    const int matchG = a.match - oe, mismatchG = a.mismatch - oe;
-    const unsigned char *ref = reinterpret_cast<const unsigned char *>(a.seq + pr.refIdx);
-    const unsigned char *qry = reinterpret_cast<const unsigned char *>(a.seq + pr.qryIdx);
+    constexpr bool LOCAL = false;
+#include "dpx_affine_lanes.inc"
+}
 
-    unsigned char *tileL = smem + (size_t)wv * a.ldsPerWave;
-    unsigned char *refl = tileL + (STORE ? kStageBytes : kLaneScratch) + sl.refOff;
-    const unsigned char *refs = stage_bytes(refl, ref, n, l, max(sl.num, 1));
-
-    const int row0 = l * R;
-    const int nrows = min(max(m - row0, 0), R);
-    AffStateG<R> st;
-    load_query_rows<R>(st.qc, qry, row0, nrows);
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        st.Hoe[r] = o + (row0 + 1 + r) * e + oe; /* H[i][0] = o + i*e (AffineNeedlemanWunsch.cpp:43-46) */
-        st.Ie[r] = DPX_NEG + e;                  /* virtual I[i][0] */
-    }
-    st.dtopOe = (row0 == 0 ? 0 : o + row0 * e) + oe; /* H[0][0] = 0 */
-    st.DeLast = DPX_NEG + e;
-
-    const int skew = l + sl.d; /* this lane runs column j = t - skew + 1 in step t; skew = lane (mod 8) */
-    const int n8 = (n + 7) & ~7;
-    const int LB = (int)dpx_tile8_row_blocks(m);
-    /* routing, once: a lane's lines are complete in the steps skew + 7, skew + 15, ... <= n8 + skew - 1 (first | last << 16); every lane
-     * keeps the words of the eight lanes of its group in registers */
-    uint32_t rt[8];
-    if constexpr (STORE) {
-        const bool rowsHere = has && (LB - l) > 0;
-        uint32_t *mine = reinterpret_cast<uint32_t *>(tileL + lane * kStageLine + 128);
-        mine[0] = rowsHere ? ((uint32_t)(skew + 7) | ((uint32_t)(n8 + skew - 1) << 16)) : 0x00007FFFu; /* (never valid: first > last) */
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-        for (int k = 0; k < 8; k++) rt[k] = *reinterpret_cast<const uint32_t *>(tileL + ((lane & ~7) | k) * kStageLine + 128);
-    }
-    int16_t *waveBase = a.mat + (size_t)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(pr.matOff >> 32)) << 32) |
-                                         (unsigned)__builtin_amdgcn_readfirstlane((int)(pr.matOff & 0xFFFFFFFFull)));
-    const int steps = __builtin_amdgcn_readfirstlane(wave_max_i32(has ? (STORE ? n8 : n) + skew : 0));
-    const unsigned char *rp = refs - skew;
-    const unsigned nEff = nrows > 0 ? (unsigned)n : 0u;
-    const int rpLast = n + skew; /* rp[rpLast] = refs[n]: inside the slack of stage_bytes */
-    unsigned char *putPtr = tileL + lane * kStageLine; /* + plane * kPlane + (t & 7) * 16 */
-    const unsigned char *fetchPtr[8]; /* piece lane % 8 of the line of lane k of this lane's group, rotated by its owner (see k_linear_lanes) */
-#pragma unroll
-    for (int k = 0; k < 8; k++) fetchPtr[k] = tileL + ((lane & ~7) | k) * kStageLine + (((lane + k) & 7) << 4);
-    u32x4 pend[3];
-    bool pendOk = false;
-    int16_t *pendDst = nullptr;
-    int bordOe = o + (1 - skew) * e + oe; /* first lane of a slot: H[0][j] + (o+e), j = t - skew + 1 */
-    int rcN = rp[0];
-    auto flush = [&]() __attribute__((always_inline)) {
-        if (pendOk) {
-#pragma unroll
-            for (int pl = 0; pl < 3; pl++) stream_store(reinterpret_cast<u32x4 *>(pendDst + (pl << 9)), pend[pl]);
-        }
-    };
-    auto pack8 = [](const int (&v)[R]) __attribute__((always_inline)) -> u32x4 {
-        u32x4 x = {pack_lo16(v[0], v[1]), pack_lo16(v[2], v[3]), pack_lo16(v[4], v[5]), pack_lo16(v[6], v[7])};
-        return x;
-    };
-    auto lane_step = [&](const int t, auto kTag) __attribute__((always_inline)) {
-        constexpr int K = decltype(kTag)::value; /* t & 7 */
-        const int tms = t - skew;
-        const int rc = rcN;
-        rcN = rp[min(t + 1, rpLast)];
-        const int shH = wave_shr1(st.Hoe[R - 1], 0), shD = wave_shr1(st.DeLast, 0);
-        const int upHoe = (l == 0) ? bordOe : shH;          /* row-0 border H[0][j] = o + j*e (:50-53) */
-        const int upDe = (l == 0) ? (DPX_NEG + e) : shD;    /* virtual D[0][j] */
-        bordOe += e;
-        if ((unsigned)tms < nEff) {
-            int Hv[R], Iv[R], Dv[R];
-            aff_cells_g<R>(st, upHoe, upDe, rc, matchG, mismatchG, oe, e, Hv, Iv, Dv);
-            if constexpr (STORE) {
-                *reinterpret_cast<u32x4 *>(putPtr + 0 * kPlane + (K << 4)) = pack8(Hv);
-                *reinterpret_cast<u32x4 *>(putPtr + 1 * kPlane + (K << 4)) = pack8(Iv);
-                *reinterpret_cast<u32x4 *>(putPtr + 2 * kPlane + (K << 4)) = pack8(Dv);
-            }
-        }
-        if constexpr (STORE) {
-            flush();
-            constexpr int O = (K + 1) & 7; /* the owners of the lines that are complete now */
-            const uint32_t r = rt[O];
-            pendOk = (uint32_t)t >= (r & 0xFFFFu) && (uint32_t)t <= (r >> 16);
-            pendDst = waveBase + (size_t)t * kStepElems + (lane << 3);
-#pragma unroll
-            for (int pl = 0; pl < 3; pl++) pend[pl] = *reinterpret_cast<const u32x4 *>(fetchPtr[O] + pl * kPlane);
-        }
-    };
-    {
-        int t = 0;
-        for (; t + 8 <= steps; t += 8) {
-            lane_step(t + 0, std::integral_constant<int, 0>{}); lane_step(t + 1, std::integral_constant<int, 1>{});
-            lane_step(t + 2, std::integral_constant<int, 2>{}); lane_step(t + 3, std::integral_constant<int, 3>{});
-            lane_step(t + 4, std::integral_constant<int, 4>{}); lane_step(t + 5, std::integral_constant<int, 5>{});
-            lane_step(t + 6, std::integral_constant<int, 6>{}); lane_step(t + 7, std::integral_constant<int, 7>{});
-        }
-        if (t + 0 < steps) lane_step(t + 0, std::integral_constant<int, 0>{});
-        if (t + 1 < steps) lane_step(t + 1, std::integral_constant<int, 1>{});
-        if (t + 2 < steps) lane_step(t + 2, std::integral_constant<int, 2>{});
-        if (t + 3 < steps) lane_step(t + 3, std::integral_constant<int, 3>{});
-        if (t + 4 < steps) lane_step(t + 4, std::integral_constant<int, 4>{});
-        if (t + 5 < steps) lane_step(t + 5, std::integral_constant<int, 5>{});
-        if (t + 6 < steps) lane_step(t + 6, std::integral_constant<int, 6>{});
-    }
-    if constexpr (STORE) flush();
-    const int lm = (m - 1) / R, rm = (m - 1) % R;
-    if (has && l == lm) {
-        int v = st.Hoe[0];
-#pragma unroll
-        for (int r = 1; r < R; r++) v = (r == rm) ? st.Hoe[r] : v;
-        a.score[p] = v - oe; /* scoringMemo[m][n] (:365); the state is H + (o+e) */
-        a.endRow[p] = m;
-        a.endCol[p] = n;
-    }
+template <int R, bool STORE>
+__global__ void __launch_bounds__(DPX_ALANES_THREADS) k_asw_lanes(const dpx_fill_args a) {
+    constexpr bool LOCAL = true;
+#include "dpx_affine_lanes.inc"
 }
 
 /* =====================================================================================================
@@ -2226,7 +1999,7 @@ __global__ void k_export_matrix(const int16_t *mat, dpx_pair_dev pr, int algo, i
             if (plane != 0) v = 0;                                   /* I / D are zero-initialised (ANW.cpp:24-27) */
             else if (algo == DPX_K_LNW) v = len * gapOpen;           /* LNW.cpp:31-41 */
             else if (algo == DPX_K_ANW) v = len == 0 ? 0 : gapOpen + len * gapExtend; /* ANW.cpp:43-53 */
-            else v = 0;                                              /* LSW / BSW */
+            else v = 0;                                              /* LSW / BSW / ASW */
         } else if (algo == DPX_K_BSW) {
             const int dlt = i - j;
             v = (dlt <= band - 1 && -dlt <= band - 1) ? mat[pr.matOff + dpx_band_index(i, j, band, pr.chunkStride)] : 0;
@@ -2350,7 +2123,8 @@ struct TileWalker {
     }
 };
 
-/* one lane walks one pair */
+/* one lane walks one pair (ASW = true: k_asw_traceback, algo DPX_K_ASW, the ANW walk's local form) */
+template <bool ASW>
 __device__ void tb_walk_lane(const dpx_fill_args &a, const int p, int algo, int R, int planes, int cachedWalk, const int32_t *endRow,
                              const int32_t *endCol, const uint64_t *tbOff, char *tb, int32_t *tbLen) {
     const dpx_pair_dev pr = a.pairs[p];
@@ -2438,11 +2212,14 @@ __device__ void tb_walk_lane(const dpx_fill_args &a, const int p, int algo, int 
             else if (del >= mm) { EMIT('_', ' ', qc); i--; }
             else { EMIT(rc, eq ? '*' : '|', qc); i--; j--; }
         }
-    } else { /* ANW */
+    } else { /* ANW; ASW (k_asw_traceback): the same walk, which stops where H = 0 and has no end gaps */
         const int o = a.gapOpen, e = a.gapExtend;
         int cur = 0; /* 0 SCORING, 1 INSERTION, 2 DELETION */
         while (i != 0 && j != 0) {
             if (cur == 0) {
+                if constexpr (ASW) {
+                    if (v.get(i, j, 0) <= 0) break;
+                }
                 const bool eq = qw.get(i - 1) == rw.get(j - 1);
                 const int mm = v.get(i - 1, j - 1, 0) + (eq ? match : mismatch);
                 const int D = v.get(i, j, 2), I = v.get(i, j, 1);
@@ -2460,8 +2237,10 @@ __device__ void tb_walk_lane(const dpx_fill_args &a, const int p, int algo, int 
                 EMIT('_', ' ', qw.get(i - 1)); i--;
             }
         }
-        while (i > 0) { EMIT('_', ' ', qw.get(i - 1)); i--; }
-        while (j > 0) { EMIT(rw.get(j - 1), ' ', '_'); j--; }
+        if constexpr (!ASW) {
+            while (i > 0) { EMIT('_', ' ', qw.get(i - 1)); i--; }
+            while (j > 0) { EMIT(rw.get(j - 1), ' ', '_'); j--; }
+        }
     }
 #undef EMIT
     if (pos & 3) { /* the 1-3 newest characters have not filled a dword: the newest sits in the lowest byte, at `pos` */
@@ -2477,7 +2256,14 @@ __global__ void k_traceback(const dpx_fill_args a, int numPairs, int algo, int R
                             const int32_t *endCol, const uint64_t *tbOff, char *tb, int32_t *tbLen) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= numPairs) return;
-    tb_walk_lane(a, p, algo, R, planes, cachedWalk, endRow, endCol, tbOff, tb, tbLen);
+    tb_walk_lane<false>(a, p, algo, R, planes, cachedWalk, endRow, endCol, tbOff, tb, tbLen);
+}
+
+__global__ void k_asw_traceback(const dpx_fill_args a, int numPairs, int R, int planes, const int32_t *endRow, const int32_t *endCol,
+                                const uint64_t *tbOff, char *tb, int32_t *tbLen) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= numPairs) return;
+    tb_walk_lane<true>(a, p, DPX_K_ASW, R, planes, 0, endRow, endCol, tbOff, tb, tbLen);
 }
 
 /* -----------------------------------------------------------------------------------------------------
@@ -2550,7 +2336,7 @@ __global__ void __launch_bounds__(64) k_traceback_wave(const dpx_fill_args a, in
     const dpx_pair_dev pr = a.pairs[p];
     const int n = pr.n, m = pr.m;
     const int Rr = pr.rows ? (int)pr.rows : R;
-    /* (the host launches this kernel for LSW / LNW / banded SW with one plane and ANW with three; rows per lane are
+    /* (the host launches this kernel for LSW / LNW / banded SW with one plane and ANW / ASW with three; rows per lane are
      * 2, 4, 8 or 16 in every full-matrix layout; empty sequences walk along a border or not at all) */
     const unsigned char *ref = reinterpret_cast<const unsigned char *>(a.seq + pr.refIdx);
     const unsigned char *qry = reinterpret_cast<const unsigned char *>(a.seq + pr.qryIdx);
@@ -2559,7 +2345,7 @@ __global__ void __launch_bounds__(64) k_traceback_wave(const dpx_fill_args a, in
     char *lr = tb + tbOff[p], *lx = lr + cap, *lq = lx + cap;
     int pos = cap;
     const int match = a.match, mismatch = a.mismatch, g = a.gapOpen, ext = a.gapExtend;
-    /* H on row 0 / column 0, `len` cells from the corner (TbView::get): LNW len * gap, ANW open + len * extend (0 in the corner), LSW 0 */
+    /* H on row 0 / column 0, `len` cells from the corner (TbView::get): LNW len * gap, ANW open + len * extend (0 in the corner), LSW / ASW 0 */
     auto bval = [&](const int len) -> int { return algo == DPX_K_LNW ? len * g : (algo == DPX_K_ANW ? (len ? g + len * ext : 0) : 0); };
     /* where the 16-byte piece (8 rows of a row group, one column) lies: shifts only for the two layouts whose lanes own >= 8 rows */
     const int Q = Rr >> 3, lgQ = Q == 2 ? 1 : 0;
@@ -2673,7 +2459,7 @@ __global__ void __launch_bounds__(64) k_traceback_wave(const dpx_fill_args a, in
         }
         { const int qi = r0 + lane; chQ = (lane < WR && qi >= 0 && qi < m) ? rawQ : 0u; } /* query character of row r0 + 1 + lane */
         chR = (jc >= 1 && jc <= n) ? rawR : 0u;
-        if (algo != DPX_K_LSW) { /* the borders of H as cells: column 0 and row 0 (LSW: zeros, as loaded) */
+        if (algo != DPX_K_LSW && algo != DPX_K_ASW) { /* the borders of H as cells: column 0 and row 0 (LSW / ASW: zeros, as loaded) */
 #pragma unroll
             for (int gi = 0; gi < CNT; gi++) {
                 const int grp = gBase + gFirst + gi;
@@ -2773,6 +2559,7 @@ __global__ void __launch_bounds__(64) k_traceback_wave(const dpx_fill_args a, in
             const int dg = cell(0, cq - 1, rq - 1), I = cell(1, cq, rq), D = cell(2, cq, rq);
             const int mm = dg + ((uint32_t)qc == rc ? match : mismatch);
             d = I >= max(D, mm) ? 1u : (D >= mm ? 2u : 0u);
+            if (algo == DPX_K_ASW && cell(0, cq, rq) <= 0) d = 3u; /* ASW: H = 0, the local alignment starts here */
             if (ii <= 0 || jc <= 0) d = 3u;
         }
         return d;
@@ -2823,7 +2610,7 @@ __global__ void __launch_bounds__(64) k_traceback_wave(const dpx_fill_args a, in
     };
     int cur = 0; /* ANW: 0 SCORING, 1 INSERTION, 2 DELETION */
     for (;;) {
-        if (algo == DPX_K_LSW ? !(i > 0 && j > 0) : !(i != 0 || j != 0)) break;
+        if ((algo == DPX_K_LSW || algo == DPX_K_ASW) ? !(i > 0 && j > 0) : !(i != 0 || j != 0)) break;
         if (need_window()) { load_window(max(i, 1), max(j, 1)); wantFull = false; } /* (a window anchored on row 1 / column 1 also serves row 0 / column 0) */
         const int r = i - R0 - 1, c = j - cLo;
         if constexpr (PLANES == 1) {
@@ -2866,10 +2653,15 @@ __global__ void __launch_bounds__(64) k_traceback_wave(const dpx_fill_args a, in
                 if (run) {
                     emit_diag(c, run, qc); i -= run; j -= run;
                     const int cx = c - run, rx = r - run; /* the cell that ends the run has been decided with it */
-                    if (cx >= 1 && rx >= 1 && i > 0 && j > 0) { const int dx = __builtin_amdgcn_readlane((int)d, cx); if (dx == 1 || dx == 2) cur = dx; }
+                    if (cx >= 1 && rx >= 1 && i > 0 && j > 0) {
+                        const int dx = __builtin_amdgcn_readlane((int)d, cx);
+                        if (dx == 1 || dx == 2) cur = dx;
+                        else if (algo == DPX_K_ASW) break; /* H = 0 */
+                    }
                     continue;
                 }
                 cur = __builtin_amdgcn_readlane((int)d, c); /* 1: to INSERTION, 2: to DELETION */
+                if (algo == DPX_K_ASW && cur == 3) break;    /* (ASW: 3 = H is 0 here) */
             } else if (cur == 1) {
                 /* INSERTION: steps to the left along row r until (and including) the cell where the gap was opened; lane l decides the cell in column l */
                 const int cq = max(lane, 1), jc = cLo + cq;
@@ -3156,6 +2948,12 @@ hipError_t launch_affine_R(const dpx_fill_args &a, bool store, dim3 grid, size_t
                  : launch_fill_kernel(k_affine_fill<R, false>, a, grid, lds, s);
 }
 
+template <int R>
+hipError_t launch_asw_R(const dpx_fill_args &a, bool store, dim3 grid, size_t lds, hipStream_t s) {
+    return store ? launch_fill_kernel(k_asw_fill<R, true>, a, grid, lds, s)
+                 : launch_fill_kernel(k_asw_fill<R, false>, a, grid, lds, s);
+}
+
 } // namespace
 
 /* ---- host-callable launchers (used by dpx_capi.cpp) ---- */
@@ -3191,6 +2989,14 @@ hipError_t dpx_launch_fill(const dpx_fill_args &a, int algo, int R, bool store, 
         default: return hipErrorInvalidValue;
         }
     }
+    if (algo == DPX_K_ASW) {
+        switch (R) {
+        case 2: return launch_asw_R<2>(a, store, grid, ldsBytes, stream);
+        case 4: return launch_asw_R<4>(a, store, grid, ldsBytes, stream);
+        case 8: return launch_asw_R<8>(a, store, grid, ldsBytes, stream);
+        default: return hipErrorInvalidValue;
+        }
+    }
     return hipErrorInvalidValue;
 }
 
@@ -3199,9 +3005,9 @@ hipError_t dpx_launch_fill(const dpx_fill_args &a, int algo, int R, bool store, 
  * 1 for the affine one). */
 size_t dpx_lanes_stage_bytes(int algo, int R, bool store) {
     if (!store) return (size_t)kLaneScratch;
-    return (size_t)(algo == DPX_K_ANW ? 3 : 1) * (size_t)(R / 8) * 64u * (size_t)kStageLine;
+    return (size_t)((algo == DPX_K_ANW || algo == DPX_K_ASW) ? 3 : 1) * (size_t)(R / 8) * 64u * (size_t)kStageLine;
 }
-int dpx_lanes_waves_per_block(int algo) { return algo == DPX_K_ANW ? DPX_ALANES_THREADS / 64 : DPX_FILL_THREADS / 64; } /* (the most: small launches of the linear kernels use 1) */
+int dpx_lanes_waves_per_block(int algo) { return (algo == DPX_K_ANW || algo == DPX_K_ASW) ? DPX_ALANES_THREADS / 64 : DPX_FILL_THREADS / 64; } /* (the most: small launches of the linear kernels use 1) */
 
 template <class K>
 static hipError_t launch_lanes_kernel(K kernel, const dpx_fill_args &a, dim3 grid, int threads, size_t lds, hipStream_t s) {
@@ -3215,12 +3021,18 @@ static hipError_t launch_lanes_kernel(K kernel, const dpx_fill_args &a, dim3 gri
 
 hipError_t dpx_launch_fill_lanes(const dpx_fill_args &a, int algo, int R, bool store, size_t ldsBytes, hipStream_t stream) {
     if (a.numPairs <= 0) return hipSuccess;
-    const int wpb = algo == DPX_K_ANW ? DPX_ALANES_THREADS / 64 : (int)a.wavesPerBlock; /* (ldsBytes = per wave x this) */
+    const int wpb = (algo == DPX_K_ANW || algo == DPX_K_ASW) ? DPX_ALANES_THREADS / 64 : (int)a.wavesPerBlock; /* (ldsBytes = per wave x this) */
     dim3 grid((unsigned)((a.numPairs + wpb - 1) / wpb));
     if (algo == DPX_K_ANW) {
         const int th = DPX_ALANES_THREADS;
         if (R == 8) return store ? launch_lanes_kernel(k_affine_lanes<8, true>, a, grid, th, ldsBytes, stream)
                                  : launch_lanes_kernel(k_affine_lanes<8, false>, a, grid, th, ldsBytes, stream);
+        return hipErrorInvalidValue;
+    }
+    if (algo == DPX_K_ASW) {
+        const int th = DPX_ALANES_THREADS;
+        if (R == 8) return store ? launch_lanes_kernel(k_asw_lanes<8, true>, a, grid, th, ldsBytes, stream)
+                                 : launch_lanes_kernel(k_asw_lanes<8, false>, a, grid, th, ldsBytes, stream);
         return hipErrorInvalidValue;
     }
     const bool local = algo == DPX_K_LSW;
@@ -3315,9 +3127,11 @@ hipError_t dpx_launch_traceback(const dpx_fill_args &a, int numPairs, int algo, 
     if (numPairs <= 0) return hipSuccess;
     const bool cachedWalk = walk == 1;
     if (walk == 2) { /* one wave per pair with an LDS window (k_traceback_wave) */
-        const size_t lds = dpx_traceback_wave_lds(algo == DPX_K_ANW ? 3 : 1);
+        const size_t lds = dpx_traceback_wave_lds((algo == DPX_K_ANW || algo == DPX_K_ASW) ? 3 : 1);
         if (algo == DPX_K_ANW)
             hipLaunchKernelGGL((k_traceback_wave<3, false, DPX_K_ANW>), dim3((unsigned)numPairs), dim3(64), lds, stream, a, numPairs, R, a.endRow, a.endCol, tbOff, tb, tbLen);
+        else if (algo == DPX_K_ASW)
+            hipLaunchKernelGGL((k_traceback_wave<3, false, DPX_K_ASW>), dim3((unsigned)numPairs), dim3(64), lds, stream, a, numPairs, R, a.endRow, a.endCol, tbOff, tb, tbLen);
         else if (algo == DPX_K_BSW)
             hipLaunchKernelGGL((k_traceback_wave<1, true, DPX_K_LSW>), dim3((unsigned)numPairs), dim3(64), lds, stream, a, numPairs, R, a.endRow, a.endCol, tbOff, tb, tbLen);
         else if (algo == DPX_K_LNW)
@@ -3326,8 +3140,12 @@ hipError_t dpx_launch_traceback(const dpx_fill_args &a, int numPairs, int algo, 
             hipLaunchKernelGGL((k_traceback_wave<1, false, DPX_K_LSW>), dim3((unsigned)numPairs), dim3(64), lds, stream, a, numPairs, R, a.endRow, a.endCol, tbOff, tb, tbLen);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(k_traceback, dim3((unsigned)((numPairs + 63) / 64)), dim3(64), 0, stream, a, numPairs, algo, R, planes,
-                       cachedWalk ? 1 : 0, a.endRow, a.endCol, tbOff, tb, tbLen);
+    if (algo == DPX_K_ASW) /* (walk 1 caches linear-gap columns only: the ASW walk is walk 0's) */
+        hipLaunchKernelGGL(k_asw_traceback, dim3((unsigned)((numPairs + 63) / 64)), dim3(64), 0, stream, a, numPairs, R, planes, a.endRow,
+                           a.endCol, tbOff, tb, tbLen);
+    else
+        hipLaunchKernelGGL(k_traceback, dim3((unsigned)((numPairs + 63) / 64)), dim3(64), 0, stream, a, numPairs, algo, R, planes,
+                           cachedWalk ? 1 : 0, a.endRow, a.endCol, tbOff, tb, tbLen);
     return hipGetLastError();
 }
 

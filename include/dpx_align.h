@@ -24,7 +24,8 @@ extern "C" {
 
 /* 1: round 1.  2: + dpx_batch_create_on, dpx_batch_fill_timed, dpx_batch_last_fill_usec, dpx_batch_output_begin/_end/_take,
  * dpx_text_free, DPX_TUNE_PLACEMENT (round 2).  3: + dpx_pool_reserve, dpx_text_reserve, dpx_batch_last_output_usec, dpx_pack2, dpx_batch_create_packed2; dpx_batch_describe reports the
- * matrix pool (round 3); + DPX_KEEP_DIRECTIONS, dpx_batch_directions (detect them by the exported symbol: the number stays 3).  Additions only: a caller built against an older version keeps working; dpx_abi_version() >= the version
+ * matrix pool (round 3); + DPX_KEEP_DIRECTIONS, dpx_batch_directions (detect them by the exported symbol: the number stays 3); + DPX_ALGO_ASW
+ * (detect it by creating a batch: an older library returns DPX_ERR_INVALID for algo 4).  Additions only: a caller built against an older version keeps working; dpx_abi_version() >= the version
  * a caller needs is the check. */
 #define DPX_ABI_VERSION 3
 
@@ -46,7 +47,12 @@ typedef enum dpx_algo {
     DPX_ALGO_LNW = 0, /* LinearNeedlemanWunsch   c++/LinearNeedlemanWunsch.cpp:89-135, cuda/LNW/ *.cu      */
     DPX_ALGO_LSW = 1, /* LinearSmithWaterman     c++/LinearSmithWaterman.cpp:70-114,  cuda/LinearSmithWaterman.cu */
     DPX_ALGO_ANW = 2, /* AffineNeedlemanWunsch   c++/AffineNeedlemanWunsch.cpp:167-240, cuda/AffineNeedlemanWunsch.cu */
-    DPX_ALGO_BSW = 3  /* BandedSmithWaterman     python/LinearBandedSmithWaterman.py:62-104 (C++/CUDA twins are broken) */
+    DPX_ALGO_BSW = 3, /* BandedSmithWaterman     python/LinearBandedSmithWaterman.py:62-104 (C++/CUDA twins are broken) */
+    DPX_ALGO_ASW = 4  /* affine-gap (Gotoh) Smith-Waterman, no reference counterpart: ANW's D / I / H recurrence and tie order with
+                         H = max(0, best) and zero borders; score = max H, end cell = its first cell in row-major order (LSW's rule);
+                         the walk follows ANW's three states from there and stops where H = 0 (no end gaps); LSW's text block.  Same
+                         dpx_params fields as ANW (band ignored).  Every flag ANW takes: matrices, DPX_SCORE_ONLY, DPX_KEEP_DIRECTIONS.
+                         Added without an ABI bump: a library that predates it returns DPX_ERR_INVALID for algo 4. */
 } dpx_algo;
 
 /* Identical in layout to the reference's `struct seqPair` (c++/parseInput.h:22-29): byte offsets into the
@@ -76,7 +82,7 @@ typedef struct dpx_params {
 #define DPX_TUNE_PLACEMENT 0x4u /* the batch will be filled many times: time its matrix pool (>= 1 GiB) with hipMemset and shop for a better
                                    one with the batch's OWN FILL on four more candidate pools (the same fill runs 2 - 27 % apart on
                                    two pools of the same construction); every candidate's times go into dpx_batch_describe's pool_* fields */
-#define DPX_KEEP_DIRECTIONS 0x8u /* LNW / LSW / ANW: keep one 4-bit direction code per cell instead of the int16 score matrices, compute in
+#define DPX_KEEP_DIRECTIONS 0x8u /* LNW / LSW / ANW / ASW: keep one 4-bit direction code per cell instead of the int16 score matrices, compute in
                                     int32 (the reference's evolved kernels keep directions only, cuda/LNW/LinearNeedlemanWunschV6.cu:167).  Same
                                     scores, end cells, text and tracebacks as a DPX_KEEP_MATRICES batch; half a byte per cell plus ~32 B of stripe
                                     padding per query row (about a quarter of an int16 H batch's bytes, a twelfth of ANW's H/I/D, from
@@ -86,8 +92,8 @@ typedef struct dpx_params {
 
 /* matrix selectors for dpx_batch_matrix / dpx_batch_directions */
 #define DPX_MAT_H 0 /* scoring matrix   (reference: memo / scoringMemo)            */
-#define DPX_MAT_I 1 /* ANW horizontal-gap matrix (queryInsertionMemo)               */
-#define DPX_MAT_D 2 /* ANW vertical-gap matrix   (queryDeletionMemo)                */
+#define DPX_MAT_I 1 /* ANW / ASW horizontal-gap matrix (queryInsertionMemo)         */
+#define DPX_MAT_D 2 /* ANW / ASW vertical-gap matrix   (queryDeletionMemo)          */
 
 typedef struct dpx_batch dpx_batch; /* opaque, device-resident batch of pairs */
 
@@ -184,7 +190,8 @@ int dpx_batch_matrix(dpx_batch *b, size_t pair, int which, int16_t *out);
 /* Export one pair's direction matrix of a DPX_KEEP_DIRECTIONS batch as the reference's back-trackers read it: row-major (m+1) x (n+1)
  * uint8 including the border row / column, values of c++/backtrack.h -- `which` DPX_MAT_H: enum directionMain (NONE_MAIN 0, MATCH 1,
  * MISMATCH 2, QUERY_INSERTION 3, QUERY_DELETION 4; LNW / ANW borders: QUERY_DELETION down column 0, QUERY_INSERTION along row 0;
- * LSW: NONE_MAIN where the best candidate is negative, c++/LinearSmithWaterman.cpp:106-109); DPX_MAT_I / DPX_MAT_D (ANW only):
+ * LSW: NONE_MAIN where the best candidate is negative, c++/LinearSmithWaterman.cpp:106-109; ASW: NONE_MAIN wherever H == 0, borders
+ * included); DPX_MAT_I / DPX_MAT_D (ANW / ASW):
  * enum directionIndel (GAP_OPEN 1, GAP_EXTEND 2; 0 on the borders).  DPX_ERR_NO_MATRIX on a batch without the flag. */
 int dpx_batch_directions(dpx_batch *b, size_t pair, int which, uint8_t *out);
 
