@@ -703,13 +703,15 @@ int dpx_shutdown(void) {
 
 /* ------------------------------------------------------------------------------------------ batch */
 
-/* the three-plane Gotoh algorithms: ANW (global) and ASW (local) */
-static bool is_affine(int algo) { return algo == DPX_ALGO_ANW || algo == DPX_ALGO_ASW; }
+/* the three-plane Gotoh algorithms: ANW (global), ASW (local) and BASW (local, banded) */
+static bool is_affine(int algo) { return algo == DPX_ALGO_ANW || algo == DPX_ALGO_ASW || algo == DPX_ALGO_BASW; }
+/* the algorithms with a band parameter (and, unless the band covers the matrix, the anti-diagonal band kernels and layout) */
+static bool is_banded(int algo) { return algo == DPX_ALGO_BSW || algo == DPX_ALGO_BASW; }
 
 static int validate_params(const dpx_params *p) {
     if (!p) return DPX_ERR_INVALID;
-    if (p->algo < DPX_ALGO_LNW || p->algo > DPX_ALGO_ASW) return DPX_ERR_INVALID;
-    if (p->algo == DPX_ALGO_BSW && p->band < 1) return DPX_ERR_INVALID;
+    if (p->algo < DPX_ALGO_LNW || p->algo > DPX_ALGO_BASW) return DPX_ERR_INVALID;
+    if (is_banded(p->algo) && p->band < 1) return DPX_ERR_INVALID;
     /* the int32 kernels add a weight to a cell value (|H| <= 32767 after fits_int16) and to the affine kernels' virtual
      * -2^29 borders: weights beyond +-2^20 could wrap those sums (and no int16 matrix could hold what they produce) */
     const long long lim = 1ll << 20;
@@ -731,7 +733,7 @@ static bool fits_int16(const dpx_params &p, long long m, long long n) {
         const long long top = diag + pos(p.gapOpen) * (m + n);
         return top <= lim && n <= 65000 && (m + n) <= 65000;
     }
-    if (p.algo == DPX_ALGO_ASW) {
+    if (p.algo == DPX_ALGO_ASW || p.algo == DPX_ALGO_BASW) { /* (BASW: a band only removes paths, and its kernel packs the step index m + n into 16 bits as BSW's does) */
         /* 0 <= H <= hiH as for ANW; I, D >= o + e (an open from H >= 0, then extensions never below it: D = max(H + o + e, ...));
          * I, D <= hiH + o + e * max(m, n); the 16-bit column keys as for LSW */
         const long long o = p.gapOpen, e = p.gapExtend;
@@ -1068,7 +1070,7 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
     } else if (device != -1) return DPX_ERR_INVALID;
     const bool dirs = (flags & DPX_KEEP_DIRECTIONS) != 0;
     if (dirs && (flags & DPX_SCORE_ONLY)) return DPX_ERR_INVALID;
-    if (dirs && params->algo == DPX_ALGO_BSW) return DPX_ERR_UNSUPPORTED; /* banded directions: not implemented */
+    if (dirs && is_banded(params->algo)) return DPX_ERR_UNSUPPORTED; /* banded directions: not implemented */
     rc = bind_device(device);
     if (rc != DPX_OK) return rc;
 
@@ -1122,9 +1124,9 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
     }
     b->R = R;
     int kernelAlgo = params->algo;
-    if (params->algo == DPX_ALGO_BSW) {
+    if (is_banded(params->algo)) {
         if (params->band >= std::max(b->maxM, b->maxN)) {
-            kernelAlgo = DPX_ALGO_LSW; /* the band covers every cell: identical to the unbanded recurrence */
+            kernelAlgo = params->algo == DPX_ALGO_BSW ? DPX_ALGO_LSW : DPX_ALGO_ASW; /* the band covers every cell: identical to the unbanded recurrence */
         } else if (params->band > 512) {
             delete b;
             return DPX_ERR_UNSUPPORTED; /* band kernel holds <= 8 cells per lane (band <= 512) */
@@ -1133,7 +1135,9 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
         }
     }
     b->kernelAlgo = kernelAlgo;
-    const bool banded = kernelAlgo == DPX_ALGO_BSW;
+    const bool banded = is_banded(kernelAlgo);
+    const bool bandedLinear = kernelAlgo == DPX_ALGO_BSW; /* (the packed-int16 band kernel exists for linear gaps only) */
+    const int bandPlanes = kernelAlgo == DPX_ALGO_BASW ? 3 : 1;
 
     /* matrix placement + algorithmic bytes: int16 cells incl. borders, sequences, 16 B pair record, 12 B result */
     for (size_t i = 0; i < numPairs; i++) {
@@ -1146,10 +1150,10 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
         if (dirs) {
             b->algBytes += ((uint64_t)(pd.m + 1) * (uint64_t)(pd.n + 1) + 1) / 2; /* half a byte per cell */
         } else if (b->store) {
-            if (banded) { /* 2 B per in-band cell */
+            if (banded) { /* 2 B per in-band cell and plane */
                 const uint64_t inband = band_cells(pd.m, pd.n, params->band);
                 b->bandCells += inband;
-                b->algBytes += 2ull * inband;
+                b->algBytes += 2ull * (uint64_t)bandPlanes * inband;
             } else {
                 b->algBytes += 2ull * (uint64_t)b->planes * (uint64_t)(pd.m + 1) * (uint64_t)(pd.n + 1);
             }
@@ -1192,7 +1196,7 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
      * fill the chip with a fraction of the waves run several pairs per wave, ceil(m/8) lanes each (k_linear_lanes /
      * k_affine_lanes, tile layout); DPX_LANES=0/1 overrides. */
     const bool linearAlgo = kernelAlgo == DPX_ALGO_LNW || kernelAlgo == DPX_ALGO_LSW;
-    const bool lanesAlgo = linearAlgo || is_affine(kernelAlgo); /* (ANW: k_affine_lanes, ASW: k_asw_lanes) */
+    const bool lanesAlgo = linearAlgo || (is_affine(kernelAlgo) && !banded); /* (ANW: k_affine_lanes, ASW: k_asw_lanes) */
     /* (the staged references of a wave's pairs share its LDS: keep the path to references that leave the request small) */
     /* Packed lane kernel (round 3, k_linear_lanes_pk): 16 rows per lane as two 8-row blocks of the SAME pair in the two halves of every
      * register.  Needs the 16-bit wrapping adds to be safe (packed_safe), room below the smallest border for its "minus infinity"
@@ -1271,11 +1275,11 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
      * the 16-rows-per-lane packed kernel wins from ~700 couples on; 512 x 512 (8 rows per lane) at 1500: 2235 / 2060 / 1987, 2000: 2432 /
      * 2495 / 2211, 3000: 2334 / 2744 / 2446, 4000: 2877 / 2811 / 2478 -- there only from ~2000 couples on */
     const size_t pkMinPairs = (linearAlgo && b->R == 16) ? 1400 : 4096;
-    bool usePacked = !b->lanePacked && b->store && ((linearAlgo && dpx_tiled_stripes(b->maxM, b->R) == 1) || banded) &&
+    bool usePacked = !b->lanePacked && b->store && ((linearAlgo && dpx_tiled_stripes(b->maxM, b->R) == 1) || bandedLinear) &&
                      numPairs >= pkMinPairs;
     if (b->lanePacked) usePacked = false;
     else
-    if (kn.packed >= 0) usePacked = kn.packed != 0 && b->store && (linearAlgo || banded);
+    if (kn.packed >= 0) usePacked = kn.packed != 0 && b->store && (linearAlgo || bandedLinear);
     if (dirs) usePacked = false;
     /* 16-bit wrapping arithmetic: only when weights and every intermediate provably fit (also under DPX_PACKED=1) */
     if (usePacked) {
@@ -1444,7 +1448,7 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
     if (b->store) {
         int group = 64;
         if (kn.group >= 1 && kn.group <= 1000000) group = kn.group;
-        const uint32_t chunkElems = (banded || b->split || dirs) ? 512u : dpx_tiled_chunk_elems(b->R, b->planes); /* (dirs: 1-KiB code chunks) */
+        const uint32_t chunkElems = banded ? dpx_band_chunk_elems(bandPlanes) : (b->split || dirs) ? 512u : dpx_tiled_chunk_elems(b->R, b->planes); /* (dirs: 1-KiB code chunks) */
         auto chunksOf = [&](const dpx_pair_dev &pd) -> uint64_t {
             if (dirs) return dpx_dir_chunks(pd.m, pd.n, b->R);
             if (pd.lanes == 32) return dpx_split_chunks(pd.m, pd.n, b->R);
@@ -1655,6 +1659,11 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
  * 1024 SIMDs) then costs a latency-bound tail of its own.
  * The secondary kernels therefore go to the batch's side stream between a fork and a join event; on `s` the fill still
  * looks like one operation (events recorded on `s` around it time all of it). */
+static hipError_t launch_main(dpx_batch *b, hipStream_t s) { /* the one-wave-per-pair kernel of the batch's algorithm */
+    if (b->kernelAlgo == DPX_ALGO_BASW) return dpx_launch_basw_fill(b->args, b->R, b->store, b->ldsBytes, s);
+    return dpx_launch_fill(b->args, b->kernelAlgo, b->R, b->store, b->ldsBytes, s);
+}
+
 static hipError_t launch_all(dpx_batch *b, hipStream_t s) {
     if (b->dirs) return dpx_launch_fill_dir(b->dirArgs, b->kernelAlgo, b->R, s);
     const bool hasMain = b->args.numPairs > 0;
@@ -1674,17 +1683,17 @@ static hipError_t launch_all(dpx_batch *b, hipStream_t s) {
     hipError_t e = hipSuccess;
     /* secondary kernel first (it is the short one; the main kernel then fills the chip around it) */
     if (b->lanePacked) {
-        if (e == hipSuccess && hasMain) e = dpx_launch_fill(b->args, b->kernelAlgo, b->R, b->store, b->ldsBytes, side); /* empty pairs */
+        if (e == hipSuccess && hasMain) e = launch_main(b, side); /* empty pairs */
         if (e == hipSuccess) e = b->lanesPk ? dpx_launch_fill_lanes_packed(b->pkArgs, b->kernelAlgo, b->pkLdsBytes, s)
                                             : dpx_launch_fill_lanes(b->pkArgs, b->kernelAlgo, b->R, b->store, b->pkLdsBytes, s);
     } else if (b->packed) {
-        if (e == hipSuccess && hasMain) e = dpx_launch_fill(b->args, b->kernelAlgo, b->R, b->store, b->ldsBytes, side);
+        if (e == hipSuccess && hasMain) e = launch_main(b, side);
         if (e == hipSuccess) e = b->kernelAlgo == DPX_ALGO_BSW ? dpx_launch_banded_packed(b->pkArgs, b->R, b->pkLdsBytes, s)
                                                                : dpx_launch_fill_packed(b->pkArgs, b->kernelAlgo, b->R, b->pkLdsBytes, s);
     } else if (b->split) {
         e = dpx_launch_fill_split(b->args, b->kernelAlgo, b->R, b->splitWaves, b->splitLds, s);
     } else {
-        e = dpx_launch_fill(b->args, b->kernelAlgo, b->R, b->store, b->ldsBytes, s);
+        e = launch_main(b, s);
     }
     if (forked) {
         hipError_t j = hipEventRecord(b->evJoin, side);
@@ -1858,8 +1867,10 @@ int dpx_batch_matrix(dpx_batch *b, size_t pair, int which, int16_t *out) {
     size_t dOutCap = 0;
     if (b->lastStream && b->lastStream != b->stream) HIP_TRY(hipStreamSynchronize(b->lastStream));
     HIP_TRY(g_tbDevCache.take((void **)&dOut, total * sizeof(int16_t), &dOutCap)); /* row-major scratch */
-    hipError_t e = dpx_launch_export(b->dMat, pd, b->kernelAlgo, b->R, b->planes, which, b->prm.gapOpen, b->prm.gapExtend,
-                                     b->prm.band, dOut, b->stream);
+    hipError_t e = b->kernelAlgo == DPX_ALGO_BASW
+                       ? dpx_launch_basw_export(b->dMat, pd, which, b->prm.band, dOut, b->stream)
+                       : dpx_launch_export(b->dMat, pd, b->kernelAlgo, b->R, b->planes, which, b->prm.gapOpen, b->prm.gapExtend,
+                                           b->prm.band, dOut, b->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
     if (e == hipSuccess) e = hipMemcpy(out, dOut, total * sizeof(int16_t), hipMemcpyDeviceToHost);
     g_tbDevCache.park(dOut, dOutCap);
@@ -1913,7 +1924,10 @@ static int output_begin(dpx_batch *b, uint64_t firstNumber) {
         if (b->kernelAlgo == DPX_ALGO_LSW || b->kernelAlgo == DPX_ALGO_LNW || b->kernelAlgo == DPX_ALGO_BSW) walk = 2;
         else if (is_affine(b->kernelAlgo) && b->numPairs <= 20000) walk = 2; /* (ASW: as ANW; its walk 1 is walk 0) */
         { const int w = knobs().tbWalk; if (w >= 0) walk = std::min(2, w); }
-        if (b->dirs) HIP_TRY(dpx_launch_traceback_dir(b->dirArgs, (int)np, b->kernelAlgo, b->R, b->dTbOff, b->dTb, b->dTbLen, b->stream));
+        /* banded affine SW: as ASW -- one wave per pair up to 20 000 pairs (k_basw_traceback_wave, band-layout window loads for the three
+         * planes), one lane per pair beyond that or under DPX_TB_WALK=0 / 1 (k_basw_traceback) */
+        if (b->kernelAlgo == DPX_ALGO_BASW) HIP_TRY(dpx_launch_basw_traceback(b->args, (int)np, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream));
+        else if (b->dirs) HIP_TRY(dpx_launch_traceback_dir(b->dirArgs, (int)np, b->kernelAlgo, b->R, b->dTbOff, b->dTb, b->dTbLen, b->stream));
         else HIP_TRY(dpx_launch_traceback(b->args, (int)np, b->kernelAlgo, b->R, b->planes, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream));
         b->tbLinesValid = true;
     }
@@ -2069,8 +2083,8 @@ int dpx_batch_traceback(dpx_batch *b, size_t pair, char *refLine, char *relLine,
 
 int dpx_batch_describe(dpx_batch *b, char *buf, size_t cap) {
     if (!b || !buf || !cap) return DPX_ERR_INVALID;
-    static const char *names[] = {"LNW", "LSW", "ANW", "BSW", "ASW"};
-    const char *kernel = b->kernelAlgo == DPX_ALGO_BSW ? (b->packed ? "k_banded_fill_pk" : "k_banded_fill") : b->kernelAlgo == DPX_ALGO_ANW ? (b->lanePacked ? "k_affine_lanes" : "k_affine_fill")
+    static const char *names[] = {"LNW", "LSW", "ANW", "BSW", "ASW", "BASW"};
+    const char *kernel = b->kernelAlgo == DPX_ALGO_BASW ? "k_basw_fill" : b->kernelAlgo == DPX_ALGO_BSW ? (b->packed ? "k_banded_fill_pk" : "k_banded_fill") : b->kernelAlgo == DPX_ALGO_ANW ? (b->lanePacked ? "k_affine_lanes" : "k_affine_fill")
                          : b->kernelAlgo == DPX_ALGO_ASW ? (b->lanePacked ? "k_asw_lanes" : "k_asw_fill")
                          : b->packed ? "k_linear_fill_pk" : b->lanesPk ? "k_linear_lanes_pk" : b->lanePacked ? "k_linear_lanes" : b->split ? "k_linear_split" : "k_linear_fill";
     if (b->dirs) kernel = b->kernelAlgo == DPX_ALGO_ANW ? "k_affine_dir" : b->kernelAlgo == DPX_ALGO_ASW ? "k_asw_dir" : "k_linear_dir";
@@ -2079,6 +2093,9 @@ int dpx_batch_describe(dpx_batch *b, char *buf, size_t cap) {
                        names[b->prm.algo], names[b->kernelAlgo], kernel, (b->packed || b->lanesPk) ? "int16" : "int32", b->R, b->store ? 1 : 0, b->nCouples, b->nLanePairs,
                        b->nWaves, b->nSingles, (int)b->pkArgs.rowTags, b->packed2 ? "packed2" : "bytes",
                        b->dirs ? b->dirArgs.wavesPerBlock : (b->packed || b->lanePacked) ? b->pkArgs.wavesPerBlock : b->split ? (unsigned)b->splitWaves : b->args.wavesPerBlock);
+    if (b->kernelAlgo == DPX_ALGO_BASW && len > 0 && (size_t)len < cap) /* which walk the batch's traceback takes */
+        len += snprintf(buf + len, cap - (size_t)len, " traceback=%s",
+                        (knobs().tbWalk >= 0 ? knobs().tbWalk >= 2 : b->numPairs <= 20000) ? "k_basw_traceback_wave" : "k_basw_traceback");
     if (b->dirs && len > 0 && (size_t)len < cap) /* the code layout, and where the edge rows live */
         len += snprintf(buf + len, cap - (size_t)len, " matrix=dir4 dir_edges=%s dir_scratch_bytes=%zu", b->dirScratch ? "global" : "lds", b->dirScratch);
     if (b->dMat && len > 0 && (size_t)len < cap) { /* the matrix pool: how it was built, and the memset time of every candidate that was timed */

@@ -13,6 +13,7 @@
 #define DPX_K_ANW 2
 #define DPX_K_BSW 3
 #define DPX_K_ASW 4 /* affine-gap Smith-Waterman: the ANW kernels' Gotoh recurrence with LSW's zero floor and start cell */
+#define DPX_K_BASW 5 /* banded affine-gap Smith-Waterman: ASW's recurrence on BSW's band and anti-diagonal schedule (dpx_basw_kernels.hip) */
 
 /* one wave per pair; DPX_FILL_THREADS/64 independent waves share a workgroup (no barriers between them) */
 #ifndef DPX_FILL_THREADS
@@ -61,6 +62,12 @@ size_t dpx_out_scan_tiles(size_t numPairs);
 hipError_t dpx_launch_output(const dpx_pair_dev *pairs, const int32_t *score, const int32_t *tbLen, const uint64_t *tbOff, const char *tb,
                              int numPairs, unsigned long long firstNumber, unsigned long long *tileSums, unsigned long long *outOff, char *out,
                              bool scanOnly, bool compactOnly, hipStream_t stream);
+/* banded affine SW (dpx_basw_kernels.hip): the fill (C = dpx_band_cpl(band) cells per lane), one plane of one pair as a row-major matrix,
+ * and the traceback (walk 2: one wave per pair with an LDS window of the three planes; otherwise one lane per pair) */
+hipError_t dpx_launch_basw_fill(const dpx_fill_args &a, int C, bool store, size_t ldsBytes, hipStream_t stream);
+hipError_t dpx_launch_basw_export(const int16_t *mat, const dpx_pair_dev &pr, int plane, int band, int16_t *out, hipStream_t stream);
+hipError_t dpx_launch_basw_traceback(const dpx_fill_args &a, int numPairs, int walk, const uint64_t *tbOff, char *tb, int32_t *tbLen,
+                                     hipStream_t stream);
 hipError_t dpx_launch_unpack2(const uint32_t *packed, uint32_t alphabet, char *out, size_t numDwords, hipStream_t stream);
 hipError_t dpx_launch_prim_eval(const int32_t *op, const uint32_t *a, const uint32_t *b, const uint32_t *c, size_t count,
                                 uint32_t *res, uint32_t *pred, hipStream_t stream);

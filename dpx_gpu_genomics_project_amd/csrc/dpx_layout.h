@@ -25,7 +25,7 @@
  *   window instead of G streams 2 MB apart -- measured +12 % write bandwidth (tools/wbench.hip: 5.45 -> 6.12 TB/s),
  *   the difference between ~7000 and ~200 DRAM pages / TLB entries open at a time.
  *
- * Banded SW: anti-diagonal-major band layout, see dpx_band_index().
+ * Banded SW: anti-diagonal-major band layout, see dpx_band_index(); banded affine SW: the same per plane, dpx_band_plane_index().
  */
 #ifndef DPX_LAYOUT_H
 #define DPX_LAYOUT_H
@@ -168,6 +168,21 @@ DPX_HD uint64_t dpx_band_index(int i, int j, int band, uint32_t chunkStride) {
     const int sc = dpx_log2(C), sg = dpx_log2(G);
     const int l = s >> sc, c = s & (C - 1);
     return (uint64_t)(A >> sg) * (uint64_t)chunkStride + (uint64_t)((l << (sg + sc)) + ((A & (G - 1)) << sc) + c);
+}
+/*
+ * Banded affine SW (three planes H, I, D): every plane has the band layout above, and the three 512-element pieces of one step group
+ * lie side by side -- chunk = [plane][lane][G*C] int16, 3 KiB:
+ *
+ *       element(i, j, plane) = dpx_band_index(i, j, band, chunkStride) + plane * 512
+ *       (chunkStride = 3 * 512 elements when a pair stands alone, GROUP * 3 * 512 when GROUP pairs are interleaved)
+ *
+ * A pair takes dpx_band_chunks(m, n, band) chunks PER PLANE, so a batch's matrix is exactly three times a linear-gap banded batch's
+ * for the same pairs, band and grouping.  This is the one index function of the layout: fill, export and traceback all use it.
+ */
+#define DPX_BAND_PLANE_ELEMS 512
+DPX_HD uint32_t dpx_band_chunk_elems(int planes) { return (uint32_t)(planes * DPX_BAND_PLANE_ELEMS); }
+DPX_HD uint64_t dpx_band_plane_index(int i, int j, int band, int plane, uint32_t chunkStride) {
+    return dpx_band_index(i, j, band, chunkStride) + (uint64_t)(plane * DPX_BAND_PLANE_ELEMS);
 }
 
 #endif

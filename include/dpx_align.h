@@ -25,7 +25,7 @@ extern "C" {
 /* 1: round 1.  2: + dpx_batch_create_on, dpx_batch_fill_timed, dpx_batch_last_fill_usec, dpx_batch_output_begin/_end/_take,
  * dpx_text_free, DPX_TUNE_PLACEMENT (round 2).  3: + dpx_pool_reserve, dpx_text_reserve, dpx_batch_last_output_usec, dpx_pack2, dpx_batch_create_packed2; dpx_batch_describe reports the
  * matrix pool (round 3); + DPX_KEEP_DIRECTIONS, dpx_batch_directions (detect them by the exported symbol: the number stays 3); + DPX_ALGO_ASW
- * (detect it by creating a batch: an older library returns DPX_ERR_INVALID for algo 4).  Additions only: a caller built against an older version keeps working; dpx_abi_version() >= the version
+ * (detect it by creating a batch: an older library returns DPX_ERR_INVALID for algo 4); + DPX_ALGO_BASW (likewise: DPX_ERR_INVALID for algo 5).  Additions only: a caller built against an older version keeps working; dpx_abi_version() >= the version
  * a caller needs is the check. */
 #define DPX_ABI_VERSION 3
 
@@ -48,11 +48,24 @@ typedef enum dpx_algo {
     DPX_ALGO_LSW = 1, /* LinearSmithWaterman     c++/LinearSmithWaterman.cpp:70-114,  cuda/LinearSmithWaterman.cu */
     DPX_ALGO_ANW = 2, /* AffineNeedlemanWunsch   c++/AffineNeedlemanWunsch.cpp:167-240, cuda/AffineNeedlemanWunsch.cu */
     DPX_ALGO_BSW = 3, /* BandedSmithWaterman     python/LinearBandedSmithWaterman.py:62-104 (C++/CUDA twins are broken) */
-    DPX_ALGO_ASW = 4  /* affine-gap (Gotoh) Smith-Waterman, no reference counterpart: ANW's D / I / H recurrence and tie order with
+    DPX_ALGO_ASW = 4, /* affine-gap (Gotoh) Smith-Waterman, no reference counterpart: ANW's D / I / H recurrence and tie order with
                          H = max(0, best) and zero borders; score = max H, end cell = its first cell in row-major order (LSW's rule);
                          the walk follows ANW's three states from there and stops where H = 0 (no end gaps); LSW's text block.  Same
                          dpx_params fields as ANW (band ignored).  Every flag ANW takes: matrices, DPX_SCORE_ONLY, DPX_KEEP_DIRECTIONS.
                          Added without an ABI bump: a library that predates it returns DPX_ERR_INVALID for algo 4. */
+    DPX_ALGO_BASW = 5 /* banded affine-gap Smith-Waterman, no reference counterpart: ASW's parameters plus BSW's band B >= 1.  A cell
+                         (i, j), 1 <= i <= m, 1 <= j <= n, is in the band when |i - j| <= B - 1 (BSW's rule).  In-band cells follow ASW's
+                         recurrence and tie order: D = max(H_up + o + e, D_up + e), I = max(H_left + o + e, I_left + e), GAP_OPEN wins a
+                         tie; best = H_diag + s, D >= best takes it, then I >= best takes it; H = max(0, best), move NONE where H == 0.
+                         Every neighbour that is a border cell or lies outside the band reads H = 0, I = D = -infinity, so the first
+                         in-band cell of a row or column always opens.  Cells outside the band: H = 0, and dpx_batch_matrix exports
+                         H = I = D = 0 there, as on the borders.  Score = max H, end cell = its first cell in row-major order ((0, 0)
+                         and 0 when every H is 0).  The walk is ASW's three-state walk from the end cell and stops where H == 0; it
+                         cannot leave the band (an extension out of a cell outside the band costs -infinity + e, so GAP_OPEN wins there).
+                         LSW's / ASW's text block.  B >= max(m, n) of the batch runs as ASW (same results); otherwise B <= 512, a wider
+                         band that does not cover the matrix is DPX_ERR_UNSUPPORTED.  gapOpen = 0 gives BSW's H matrix with linear gap
+                         gapExtend.  Matrices and DPX_SCORE_ONLY; DPX_KEEP_DIRECTIONS is DPX_ERR_UNSUPPORTED, as for BSW.
+                         Added without an ABI bump or a new symbol: a library that predates it returns DPX_ERR_INVALID for algo 5. */
 } dpx_algo;
 
 /* Identical in layout to the reference's `struct seqPair` (c++/parseInput.h:22-29): byte offsets into the
@@ -72,7 +85,7 @@ typedef struct dpx_params {
     int32_t mismatch;
     int32_t gapOpen;   /* linear gap for LNW/LSW/BSW; gap-open for ANW */
     int32_t gapExtend; /* ANW only */
-    int32_t band;      /* BSW only: cells with |i-j| <= band-1 are computed */
+    int32_t band;      /* BSW / BASW: cells with |i-j| <= band-1 are computed */
 } dpx_params;
 
 /* dpx_batch_create flags */
@@ -88,12 +101,12 @@ typedef struct dpx_params {
                                     padding per query row (about a quarter of an int16 H batch's bytes, a twelfth of ANW's H/I/D, from
                                     a few hundred rows on; short reads keep a larger fraction); scores may exceed int16 (bounds checked against 2^28) and references 65 000 columns.
                                     dpx_batch_matrix() returns DPX_ERR_NO_MATRIX, dpx_batch_directions() exports the codes.  With
-                                    DPX_SCORE_ONLY: DPX_ERR_INVALID; with BSW: DPX_ERR_UNSUPPORTED (banded directions are not implemented). */
+                                    DPX_SCORE_ONLY: DPX_ERR_INVALID; with BSW / BASW: DPX_ERR_UNSUPPORTED (banded directions are not implemented). */
 
 /* matrix selectors for dpx_batch_matrix / dpx_batch_directions */
 #define DPX_MAT_H 0 /* scoring matrix   (reference: memo / scoringMemo)            */
-#define DPX_MAT_I 1 /* ANW / ASW horizontal-gap matrix (queryInsertionMemo)         */
-#define DPX_MAT_D 2 /* ANW / ASW vertical-gap matrix   (queryDeletionMemo)          */
+#define DPX_MAT_I 1 /* ANW / ASW / BASW horizontal-gap matrix (queryInsertionMemo)  */
+#define DPX_MAT_D 2 /* ANW / ASW / BASW vertical-gap matrix   (queryDeletionMemo)   */
 
 typedef struct dpx_batch dpx_batch; /* opaque, device-resident batch of pairs */
 
