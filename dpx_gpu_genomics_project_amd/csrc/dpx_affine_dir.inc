@@ -1,5 +1,6 @@
 /* dpx_affine_dir.inc -- body of the affine-gap direction fills, included by dpx_dir_kernels.hip inside k_affine_dir (ANW, LOCAL = false)
- * and k_asw_dir (ASW, LOCAL = true), for the reason given in dpx_affine_fill.inc.  In scope: `a`, R, GLOBAL and LOCAL. */
+ * k_asw_dir (ASW, LOCAL = true) and k_asg_dir (ASG, SEMI = true), for the reason given in dpx_affine_fill.inc.  In scope: `a`, R, GLOBAL,
+ * LOCAL and SEMI. */
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int G = 32 / R;
     const int lane = threadIdx.x & 63;
@@ -13,11 +14,12 @@
     const int o = a.gapOpen, e = a.gapExtend, oe = o + e;
 
     if (m <= 0 || n <= 0) {
-        if (lane == 0) { /* H[m][n] on the border: 0 at the origin, else o + len*e (AffineNeedlemanWunsch.cpp:43-53); ASW: 0 at (0, 0) */
+        if (lane == 0) { /* H[m][n] on the border: 0 at the origin, else o + len*e (AffineNeedlemanWunsch.cpp:43-53); ASW: 0 at (0, 0);
+                          * ASG: 0 at (0, 0) for an empty query, else o + m*e at (m, 0) */
             const int len = m <= 0 ? max(n, 0) : m;
-            a.score[p] = (LOCAL || len <= 0) ? 0 : o + len * e;
+            a.score[p] = (LOCAL || len <= 0 || (SEMI && m <= 0)) ? 0 : o + len * e;
             a.endRow[p] = LOCAL ? 0 : max(m, 0);
-            a.endCol[p] = LOCAL ? 0 : max(n, 0);
+            a.endCol[p] = (LOCAL || SEMI) ? 0 : max(n, 0);
         }
         return;
     }
@@ -29,7 +31,7 @@
     int32_t *edgeH = reinterpret_cast<int32_t *>(my);
     int32_t *edgeD = reinterpret_cast<int32_t *>(my + a.ldsEdge2Off);
     const unsigned char *refl = dir_stage(my + a.ldsRefOff + 64, ref, n, lane) - 64;
-    for (int x = lane; x <= n + 1; x += 64) { edgeH[x] = LOCAL ? 0 : o + x * e; edgeD[x] = DPX_NEG; } /* H[0][j] (:50-53; ASW 0), virtual D[0][j] */
+    for (int x = lane; x <= n + 1; x += 64) { edgeH[x] = (LOCAL || SEMI) ? 0 : o + x * e; edgeD[x] = DPX_NEG; } /* H[0][j] (:50-53; ASW / ASG 0), virtual D[0][j] */
     if constexpr (GLOBAL) __threadfence_block();
 
     const int S = dpx_tiled_stripes(m, R);
@@ -39,7 +41,8 @@
 
     int Hl[R], Il[R], qc[R];
     [[maybe_unused]] int bestv = 0, bestrow = 0, bestcol = 0; /* ASW: the lane's first strict maximum */
-    [[maybe_unused]] int bv[R], bc[R];                         /* ASW: per row, best H and its first column (int32: no 16-bit keys) */
+    [[maybe_unused]] int bv[R], bc[R];                         /* ASW: per row, best H and its first column (int32: no 16-bit keys); ASG: bv[0] / bc[0], of register rsel */
+    [[maybe_unused]] const int rsel = (m - 1) % R;             /* ASG: the register of row m in the lane that owns it */
     for (int k = 0; k < S; k++) {
         const int row0 = k * 64 * R + lane * R;
         const int nrows = min(max(m - row0, 0), R);
@@ -51,6 +54,7 @@
             Il[r] = DPX_NEG;                /* virtual I[i][0] */
             if constexpr (LOCAL) { bv[r] = 0; bc[r] = 0; }
         }
+        if constexpr (SEMI) { bv[0] = o + m * e; bc[0] = 0; } /* ASG: row m's column-0 border takes part, and wins a tie (read from the lane that owns row m) */
         int dBot = DPX_NEG;                 /* D of the lane's bottom row, for the lane below */
         int dtop = (LOCAL || row0 == 0) ? 0 : o + row0 * e;
         const unsigned char *rp = refl + 64 - lane;
@@ -99,6 +103,12 @@
                     }
                     dBot = uD;
                     dtop = upH;
+                    if constexpr (SEMI) { /* the first maximum of ONE row: register rsel (a select chain on the wave-uniform rsel) */
+                        int hm = Hl[0];
+#pragma unroll
+                        for (int r = 1; r < R; r++) hm = (r == rsel) ? Hl[r] : hm;
+                        if (hm > bv[0]) { bv[0] = hm; bc[0] = j; }
+                    }
                     if (hasNext && lane == 63) { edgeH[j] = Hl[R - 1]; edgeD[j] = dBot; }
                 }
                 dir_put<R>(acc, q, w[0], w[1]);
@@ -126,6 +136,14 @@
     }
     const int lastBase = (S - 1) * 64 * R;
     const int lm = (m - 1 - lastBase) / R, rm = (m - 1 - lastBase) % R;
+    if constexpr (SEMI) { /* row m: register rm of lane lm of the last stripe */
+        if (lane == lm) {
+            a.score[p] = bv[0];
+            a.endRow[p] = m;
+            a.endCol[p] = bc[0];
+        }
+        return;
+    }
     if (lane == lm) {
         int v = Hl[0];
 #pragma unroll

@@ -1,8 +1,10 @@
 /* dpx_affine_fill.inc -- body of the one-wave-per-pair affine-gap fill kernels, included by dpx_kernels.hip inside k_affine_fill (ANW,
- * LOCAL = false) and k_asw_fill (ASW, LOCAL = true).  The body sits in each kernel itself rather than in a shared __device__ function:
+ * LOCAL = false), k_asw_fill (ASW, LOCAL = true) and k_asg_fill (ASG, SEMI = true: ANW's cells under a zero row-0 border, the end cell is
+ * the first maximum of row m, column 0 included).  The body sits in each kernel itself rather than in a shared __device__ function:
  * passing the kernel argument block to a function changed the scheduling of the ANW kernel (its gfx950 code differed, and 4000 x 512^2
  * filled 3-8 % slower); included this way the ANW kernels compile to the code they compiled to before ASW existed.
- * In scope: `a` (the kernel's dpx_fill_args), R, STORE and LOCAL. */
+ * In scope: `a` (the kernel's dpx_fill_args), R, STORE, LOCAL and SEMI. */
+    constexpr int MODE = LOCAL ? 1 : (SEMI ? 2 : 0); /* aff_cells: ANW, ASW, ASG */
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -15,11 +17,12 @@
     const int o = a.gapOpen, e = a.gapExtend, oe = o + e;
 
     if (m <= 0 || n <= 0) {
-        if (lane == 0) { /* H[m][n] on the border: 0 at the origin, else o + len*e (AffineNeedlemanWunsch.cpp:43-53); ASW: score 0 at (0, 0) */
+        if (lane == 0) { /* H[m][n] on the border: 0 at the origin, else o + len*e (AffineNeedlemanWunsch.cpp:43-53); ASW: score 0 at (0, 0);
+                          * ASG: row 0 is free (0 at (0, 0)), an empty reference leaves the query as one gap (o + m*e at (m, 0)) */
             const int len = m <= 0 ? max(n, 0) : m;
-            a.score[p] = (LOCAL || len <= 0) ? 0 : o + len * e;
+            a.score[p] = (LOCAL || len <= 0 || (SEMI && m <= 0)) ? 0 : o + len * e;
             a.endRow[p] = LOCAL ? 0 : max(m, 0);
-            a.endCol[p] = LOCAL ? 0 : max(n, 0);
+            a.endCol[p] = (LOCAL || SEMI) ? 0 : max(n, 0);
         }
         return;
     }
@@ -30,13 +33,14 @@
     int16_t *edgeD = reinterpret_cast<int16_t *>(my + a.ldsEdge2Off);
     const unsigned char *refl = stage_bytes(my + a.ldsRefOff + 64, ref, n, lane, 64) - 64;
     /* row-0 border H[0][j] = o + j*e (AffineNeedlemanWunsch.cpp:50-53); D[0][j] is the virtual DPX_NEG (k == 0 below) */
-    for (int x = lane; x <= n + 1; x += 64) { edgeH[x] = (int16_t)(LOCAL ? 0 : o + x * e); edgeD[x] = 0; } /* (ASW: H[0][j] = 0) */
+    for (int x = lane; x <= n + 1; x += 64) { edgeH[x] = (int16_t)((LOCAL || SEMI) ? 0 : o + x * e); edgeD[x] = 0; } /* (ASW / ASG: H[0][j] = 0) */
 
     int16_t *Mp = a.mat + pr.matOff;
     const int W = n + 63;
     const int S = dpx_tiled_stripes(m, R);
     AffState<R> st;
     [[maybe_unused]] int bestv = 0, bestrow = 0, bestcol = 0; /* ASW */
+    [[maybe_unused]] const int rsel = (m - 1) % R;            /* ASG: the register of row m in the lane that owns it (a stripe is 64 * R rows) */
 
     if (STORE && S >= 2 && n >= 128) {
         /* ---------- rolling schedule (see k_linear_fill): lanes run straight on into the next stripe ---------- */
@@ -85,7 +89,7 @@
                 st.dtop = LOCAL ? 0 : o + row0 * e;
             }
             if (jl >= 1 && kl < S && nrows > 0) {
-                aff_cells<R, LOCAL>(st, upH, upD, rc, match, mismatch, oe, e, 0xFFFFu - (unsigned)jl);
+                aff_cells<R, MODE>(st, upH, upD, rc, match, mismatch, oe, e, 0xFFFFu - (unsigned)jl, rsel);
                 if (lane == 63 && kl + 1 < S) {
                     edgeH[jl] = (int16_t)st.Hl[R - 1];
                     edgeD[jl] = (int16_t)st.Dl[R - 1];
@@ -139,8 +143,8 @@
                 rcN = rp[t + 1];                                                                                          \
                 eHN = edgeH[min(t + 2, n + 1)];                                                                           \
                 eDN = k == 0 ? DPX_NEG : (int)edgeD[min(t + 2, n + 1)];                                                   \
-                aff_step<R, LOCAL, STORE, MASKED_, WHOLE_>(st, t, lane, n, HASROWS_, match, mismatch, oe, e, eH, eD, rc, edgeH, edgeD, \
-                                            hasNext, tile + (size_t)t * cs, storeLanes, a.rampLines);                     \
+                aff_step<R, MODE, STORE, MASKED_, WHOLE_>(st, t, lane, n, HASROWS_, match, mismatch, oe, e, eH, eD, rc, edgeH, edgeD, \
+                                            hasNext, tile + (size_t)t * cs, storeLanes, a.rampLines, rsel);               \
             }
             const bool fast = (base + 64 * R <= m) && (n >= 64);
             const int storeLanes = (S == 1) ? store_lanes<R>(m) : 64;
@@ -173,6 +177,11 @@
     }
     const int lastBase = (S - 1) * 64 * R;
     const int lm = (m - 1 - lastBase) / R, rm = (m - 1 - lastBase) % R;
+    if constexpr (SEMI) { /* row m's key is that of lane lm in the last stripe (on the rolling schedule too: a lane stops switching there, and
+                           * its key starts again with every stripe) */
+        if (lane == lm) asg_publish(a, p, m, st.key[0], o + m * e);
+        return;
+    }
     if (lane == lm) {
         int v = st.Hl[0];
 #pragma unroll

@@ -1,5 +1,7 @@
 /* dpx_affine_lanes.inc -- body of the lane-packed affine-gap kernels, included by dpx_kernels.hip inside k_affine_lanes (ANW, LOCAL = false)
- * and k_asw_lanes (ASW, LOCAL = true), for the reason given in dpx_affine_fill.inc.  In scope: `a`, R, STORE and LOCAL. */
+ * k_asw_lanes (ASW, LOCAL = true) and k_asg_lanes (ASG, SEMI = true), for the reason given in dpx_affine_fill.inc.  In scope: `a`, R, STORE,
+ * LOCAL and SEMI. */
+    constexpr int MODE = LOCAL ? 1 : (SEMI ? 2 : 0); /* aff_cells_g: ANW, ASW, ASG */
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     static_assert(R == 8, "one 8-row block per lane");
     constexpr int kPlane = 64 * kStageLine; /* bytes of one plane's lines */
@@ -36,6 +38,7 @@
     st.dtopOe = ((LOCAL || row0 == 0) ? 0 : o + row0 * e) + oe; /* H[0][0] = 0 */
     st.DeLast = DPX_NEG + e;
 
+    [[maybe_unused]] const int rsel = (m - 1) & (R - 1); /* ASG: the register of row m in the slot's lane (m-1)/8 */
     const int skew = l + sl.d; /* this lane runs column j = t - skew + 1 in step t; skew = lane (mod 8) */
     const int n8 = (n + 7) & ~7;
     const int LB = (int)dpx_tile8_row_blocks(m);
@@ -65,7 +68,7 @@
     u32x4 pend[3];
     bool pendOk = false;
     int16_t *pendDst = nullptr;
-    int bordOe = (LOCAL ? 0 : o + (1 - skew) * e) + oe; /* first lane of a slot: H[0][j] + (o+e), j = t - skew + 1 (ASW: H[0][j] = 0) */
+    int bordOe = ((LOCAL || SEMI) ? 0 : o + (1 - skew) * e) + oe; /* first lane of a slot: H[0][j] + (o+e), j = t - skew + 1 (ASW / ASG: H[0][j] = 0) */
     int rcN = rp[0];
     auto flush = [&]() __attribute__((always_inline)) {
         if (pendOk) {
@@ -85,10 +88,10 @@
         const int shH = wave_shr1(st.Hoe[R - 1], 0), shD = wave_shr1(st.DeLast, 0);
         const int upHoe = (l == 0) ? bordOe : shH;          /* row-0 border H[0][j] = o + j*e (:50-53) */
         const int upDe = (l == 0) ? (DPX_NEG + e) : shD;    /* virtual D[0][j] */
-        if constexpr (!LOCAL) bordOe += e;
+        if constexpr (!LOCAL && !SEMI) bordOe += e;
         if ((unsigned)tms < nEff) {
             int Hv[R], Iv[R], Dv[R];
-            aff_cells_g<R, LOCAL>(st, upHoe, upDe, rc, matchG, mismatchG, oe, e, Hv, Iv, Dv, 0xFFFEu - (unsigned)tms);
+            aff_cells_g<R, MODE>(st, upHoe, upDe, rc, matchG, mismatchG, oe, e, Hv, Iv, Dv, 0xFFFEu - (unsigned)tms, rsel);
             if constexpr (STORE) {
                 *reinterpret_cast<u32x4 *>(putPtr + 0 * kPlane + (K << 4)) = pack8(Hv);
                 *reinterpret_cast<u32x4 *>(putPtr + 1 * kPlane + (K << 4)) = pack8(Iv);
@@ -144,6 +147,10 @@
         return;
     }
     const int lm = (m - 1) / R, rm = (m - 1) % R;
+    if constexpr (SEMI) { /* row m's key: register rm of the slot's lane (m-1)/8 (the host keeps pairs without cells off this kernel) */
+        if (has && l == lm) asg_publish(a, p, m, st.key[0], o + m * e);
+        return;
+    }
     if (has && l == lm) {
         int v = st.Hoe[0];
 #pragma unroll

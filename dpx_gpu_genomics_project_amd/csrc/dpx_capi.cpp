@@ -703,14 +703,14 @@ int dpx_shutdown(void) {
 
 /* ------------------------------------------------------------------------------------------ batch */
 
-/* the three-plane Gotoh algorithms: ANW (global), ASW (local) and BASW (local, banded) */
-static bool is_affine(int algo) { return algo == DPX_ALGO_ANW || algo == DPX_ALGO_ASW || algo == DPX_ALGO_BASW; }
+/* the three-plane Gotoh algorithms: ANW (global), ASW (local), BASW (local, banded) and ASG (semi-global) */
+static bool is_affine(int algo) { return algo == DPX_ALGO_ANW || algo == DPX_ALGO_ASW || algo == DPX_ALGO_BASW || algo == DPX_ALGO_ASG; }
 /* the algorithms with a band parameter (and, unless the band covers the matrix, the anti-diagonal band kernels and layout) */
 static bool is_banded(int algo) { return algo == DPX_ALGO_BSW || algo == DPX_ALGO_BASW; }
 
 static int validate_params(const dpx_params *p) {
     if (!p) return DPX_ERR_INVALID;
-    if (p->algo < DPX_ALGO_LNW || p->algo > DPX_ALGO_BASW) return DPX_ERR_INVALID;
+    if (p->algo < DPX_ALGO_LNW || p->algo > DPX_ALGO_ASG) return DPX_ERR_INVALID;
     if (is_banded(p->algo) && p->band < 1) return DPX_ERR_INVALID;
     /* the int32 kernels add a weight to a cell value (|H| <= 32767 after fits_int16) and to the affine kernels' virtual
      * -2^29 borders: weights beyond +-2^20 could wrap those sums (and no int16 matrix could hold what they produce) */
@@ -744,9 +744,16 @@ static bool fits_int16(const dpx_params &p, long long m, long long n) {
         const long long lo = neg(p.gapOpen) * (m + n), hi = diag + pos(p.gapOpen) * (m + n);
         return lo >= -lim && hi <= lim;
     }
+    /* ANW, and ASG: every ASG cell H[i][j] is the best score of an alignment path between a reference substring ref[a:j] and the query
+     * prefix qry[0:i] (the free row 0 chooses a), or the column-0 border, an all-gap path.  Such a path has at most m + n steps and at
+     * most min(m, n) diagonal ones, so ANW's bounds hold for it: hiH sums the positive contributions a path can collect, loH is below
+     * the all-gap path every cell can fall back on (o + i*e after a free row 0, or ANW's own).  I and D are one open / extension away
+     * as for ANW.  ASG's fills also keep ((H + 32768) << 16 | 65535 - j) keys for row m: H inside int16 is this check, and the column
+     * must fit 16 bits (the same 65000 as LSW's and ASW's keys). */
     const long long o = p.gapOpen, e = p.gapExtend;
     const long long loH = 2 * neg(o) + neg(e) * (m + n), hiH = diag + (pos(o) + pos(e)) * (m + n);
     const long long lo = loH + neg(o + e), hi = hiH + pos(o) + pos(e) * std::max(m, n);
+    if (p.algo == DPX_ALGO_ASG && n > 65000) return false;
     return lo >= -lim && hi <= lim;
 }
 
@@ -763,6 +770,7 @@ static bool fits_dir(const dpx_params &p, long long m, long long n) {
         return neg(o + e) >= -lim && hiH + pos(o) + pos(e) * std::max(m, n) <= lim;
     }
     if (p.algo == DPX_ALGO_LNW) return neg(p.gapOpen) * (m + n) >= -lim && diag + pos(p.gapOpen) * (m + n) <= lim;
+    /* ANW, and ASG by the argument in fits_int16 (its direction fill keeps row m's first maximum as an int32 value and column: no key, no column limit) */
     const long long o = p.gapOpen, e = p.gapExtend;
     const long long loH = 2 * neg(o) + neg(e) * (m + n), hiH = diag + (pos(o) + pos(e)) * (m + n);
     return loH + neg(o + e) >= -lim && hiH + pos(o) + pos(e) * std::max(m, n) <= lim;
@@ -1196,7 +1204,7 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
      * fill the chip with a fraction of the waves run several pairs per wave, ceil(m/8) lanes each (k_linear_lanes /
      * k_affine_lanes, tile layout); DPX_LANES=0/1 overrides. */
     const bool linearAlgo = kernelAlgo == DPX_ALGO_LNW || kernelAlgo == DPX_ALGO_LSW;
-    const bool lanesAlgo = linearAlgo || (is_affine(kernelAlgo) && !banded); /* (ANW: k_affine_lanes, ASW: k_asw_lanes) */
+    const bool lanesAlgo = linearAlgo || (is_affine(kernelAlgo) && !banded); /* (ANW: k_affine_lanes, ASW: k_asw_lanes, ASG: k_asg_lanes) */
     /* (the staged references of a wave's pairs share its LDS: keep the path to references that leave the request small) */
     /* Packed lane kernel (round 3, k_linear_lanes_pk): 16 rows per lane as two 8-row blocks of the SAME pair in the two halves of every
      * register.  Needs the 16-bit wrapping adds to be safe (packed_safe), room below the smallest border for its "minus infinity"
@@ -2083,11 +2091,12 @@ int dpx_batch_traceback(dpx_batch *b, size_t pair, char *refLine, char *relLine,
 
 int dpx_batch_describe(dpx_batch *b, char *buf, size_t cap) {
     if (!b || !buf || !cap) return DPX_ERR_INVALID;
-    static const char *names[] = {"LNW", "LSW", "ANW", "BSW", "ASW", "BASW"};
+    static const char *names[] = {"LNW", "LSW", "ANW", "BSW", "ASW", "BASW", "ASG"};
     const char *kernel = b->kernelAlgo == DPX_ALGO_BASW ? "k_basw_fill" : b->kernelAlgo == DPX_ALGO_BSW ? (b->packed ? "k_banded_fill_pk" : "k_banded_fill") : b->kernelAlgo == DPX_ALGO_ANW ? (b->lanePacked ? "k_affine_lanes" : "k_affine_fill")
                          : b->kernelAlgo == DPX_ALGO_ASW ? (b->lanePacked ? "k_asw_lanes" : "k_asw_fill")
+                         : b->kernelAlgo == DPX_ALGO_ASG ? (b->lanePacked ? "k_asg_lanes" : "k_asg_fill")
                          : b->packed ? "k_linear_fill_pk" : b->lanesPk ? "k_linear_lanes_pk" : b->lanePacked ? "k_linear_lanes" : b->split ? "k_linear_split" : "k_linear_fill";
-    if (b->dirs) kernel = b->kernelAlgo == DPX_ALGO_ANW ? "k_affine_dir" : b->kernelAlgo == DPX_ALGO_ASW ? "k_asw_dir" : "k_linear_dir";
+    if (b->dirs) kernel = b->kernelAlgo == DPX_ALGO_ANW ? "k_affine_dir" : b->kernelAlgo == DPX_ALGO_ASW ? "k_asw_dir" : b->kernelAlgo == DPX_ALGO_ASG ? "k_asg_dir" : "k_linear_dir";
     /* dtype = the arithmetic type of the kernel that fills (most of) the batch */
     int len = snprintf(buf, cap, "algo=%s kernel_algo=%s kernel=%s dtype=%s rows_per_lane=%d store=%d couples=%zu lane_pairs=%zu waves=%zu singles=%zu row_tags=%d seq_input=%s waves_per_workgroup=%u",
                        names[b->prm.algo], names[b->kernelAlgo], kernel, (b->packed || b->lanesPk) ? "int16" : "int32", b->R, b->store ? 1 : 0, b->nCouples, b->nLanePairs,

@@ -207,14 +207,22 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_linear_dir(const dpx_dir_a
  * ===================================================================================================== */
 template <int R, bool GLOBAL>
 __global__ void __launch_bounds__(DPX_FILL_THREADS) k_affine_dir(const dpx_dir_args a) {
-    constexpr bool LOCAL = false;
+    constexpr bool LOCAL = false, SEMI = false;
 #include "dpx_affine_dir.inc"
 }
 
 /* ASW (affine-gap Smith-Waterman, include/dpx_align.h): the same fill with the zero floor; code move 0 where H == 0, bits 2 / 3 as ANW */
 template <int R, bool GLOBAL>
 __global__ void __launch_bounds__(DPX_FILL_THREADS) k_asw_dir(const dpx_dir_args a) {
-    constexpr bool LOCAL = true;
+    constexpr bool LOCAL = true, SEMI = false;
+#include "dpx_affine_dir.inc"
+}
+
+/* ASG (affine-gap semi-global alignment, include/dpx_align.h): ANW's fill and codes under a zero row-0 border; the end cell is the first
+ * maximum of row m, its column-0 border included */
+template <int R, bool GLOBAL>
+__global__ void __launch_bounds__(DPX_FILL_THREADS) k_asg_dir(const dpx_dir_args a) {
+    constexpr bool LOCAL = false, SEMI = true;
 #include "dpx_affine_dir.inc"
 }
 
@@ -260,7 +268,7 @@ __global__ void __launch_bounds__(64) k_traceback_dir(const dpx_dir_args a, int 
         pos -= cnt; j -= cnt;
     };
     int cur = 0; /* ANW: 0 SCORING, 1 INSERTION, 2 DELETION */
-    const bool affine = algo == DPX_K_ANW || algo == DPX_K_ASW; /* three states; ASW also stops where H == 0 (move 0) */
+    const bool affine = algo == DPX_K_ANW || algo == DPX_K_ASW || algo == DPX_K_ASG; /* three states; ASW also stops where H == 0 (move 0) */
     bool done = (algo == DPX_K_LSW || algo == DPX_K_ASW) ? !(a.score[p] > 0 && i > 0 && j > 0) : false; /* score 0: no path (LinearSmithWaterman.cpp:253-257) */
     while (!done) {
         if (algo == DPX_K_LNW && (i == 0 || j == 0)) { /* borders: row 0 is QUERY_INSERTION, column 0 QUERY_DELETION */
@@ -310,9 +318,9 @@ __global__ void __launch_bounds__(64) k_traceback_dir(const dpx_dir_args a, int 
         if (kind != 3) i -= steps;
         if (kind != 2) j -= steps;
     }
-    if (algo == DPX_K_ANW) { /* :348-360 */
+    if (algo == DPX_K_ANW || algo == DPX_K_ASG) { /* :348-360; ASG: column 0 drains the query, the reference before the alignment is free */
         tail_up(i);
-        tail_left(j);
+        if (algo == DPX_K_ANW) tail_left(j);
     }
     if (lane == 0) tbLen[p] = cap - pos;
 }
@@ -328,7 +336,7 @@ __global__ void __launch_bounds__(256) k_export_dir(const unsigned char *codes, 
     const int i = (int)(idx / (uint64_t)(n + 1)), j = (int)(idx % (uint64_t)(n + 1));
     uint8_t v;
     if (i == 0 || j == 0) {
-        if (which != 0 || algo == DPX_K_LSW || algo == DPX_K_ASW || (i == 0 && j == 0)) v = 0; /* (SW borders hold H = 0: NONE) */
+        if (which != 0 || algo == DPX_K_LSW || algo == DPX_K_ASW || (i == 0 && (j == 0 || algo == DPX_K_ASG))) v = 0; /* (SW borders, ASG's row 0: H = 0, NONE) */
         else v = (j == 0) ? 4 : 3; /* column 0: QUERY_DELETION, row 0: QUERY_INSERTION */
     } else {
         int sh;
@@ -383,6 +391,11 @@ hipError_t launch_asw_dir_R(const dpx_dir_args &a, hipStream_t s) {
     return a.scratch ? dir_launch(k_asw_dir<R, true>, a, s) : dir_launch(k_asw_dir<R, false>, a, s);
 }
 
+template <int R>
+hipError_t launch_asg_dir_R(const dpx_dir_args &a, hipStream_t s) {
+    return a.scratch ? dir_launch(k_asg_dir<R, true>, a, s) : dir_launch(k_asg_dir<R, false>, a, s);
+}
+
 } // namespace
 
 hipError_t dpx_launch_fill_dir(const dpx_dir_args &a, int algo, int R, hipStream_t stream) {
@@ -400,6 +413,14 @@ hipError_t dpx_launch_fill_dir(const dpx_dir_args &a, int algo, int R, hipStream
         case 2: return launch_asw_dir_R<2>(a, stream);
         case 4: return launch_asw_dir_R<4>(a, stream);
         case 8: return launch_asw_dir_R<8>(a, stream);
+        default: return hipErrorInvalidValue;
+        }
+    }
+    if (algo == DPX_K_ASG) {
+        switch (R) {
+        case 2: return launch_asg_dir_R<2>(a, stream);
+        case 4: return launch_asg_dir_R<4>(a, stream);
+        case 8: return launch_asg_dir_R<8>(a, stream);
         default: return hipErrorInvalidValue;
         }
     }

@@ -14,6 +14,7 @@
 #define DPX_K_BSW 3
 #define DPX_K_ASW 4 /* affine-gap Smith-Waterman: the ANW kernels' Gotoh recurrence with LSW's zero floor and start cell */
 #define DPX_K_BASW 5 /* banded affine-gap Smith-Waterman: ASW's recurrence on BSW's band and anti-diagonal schedule (dpx_basw_kernels.hip) */
+#define DPX_K_ASG 6 /* affine-gap semi-global alignment: the ANW kernels under a zero row-0 border, ending on the first maximum of row m */
 
 /* one wave per pair; DPX_FILL_THREADS/64 independent waves share a workgroup (no barriers between them) */
 #ifndef DPX_FILL_THREADS

@@ -1447,13 +1447,13 @@ struct AffState {
     int Hl[R], Il[R]; /* H[row][j-1], I[row][j-1] */
     int Dl[R];        /* D[row][j] just computed (needed only for the store and the lane hand-off) */
     int qc[R];
-    unsigned key[R];  /* ASW: per-row running max of (H << 16 | 0xFFFF - j) */
+    unsigned key[R];  /* ASW: per-row running max of (H << 16 | 0xFFFF - j); ASG: key[0] alone, of ((H + 0x8000) << 16 | 0xFFFF - j) in register rsel */
     int dtop;
 };
 
-template <int R, bool LOCAL>
+template <int R, int MODE> /* 0 ANW, 1 ASW, 2 ASG */
 __device__ __forceinline__ void aff_cells(AffState<R> &st, const int upH, const int upD, const int rc, const int match,
-                                          const int mismatch, const int oe, const int e, const unsigned negj) {
+                                          const int mismatch, const int oe, const int e, const unsigned negj, [[maybe_unused]] const int rsel = 0) {
     int uH = upH, uD = upD, d = st.dtop;
 #pragma unroll
     for (int r = 0; r < R; r++) {
@@ -1462,7 +1462,7 @@ __device__ __forceinline__ void aff_cells(AffState<R> &st, const int upH, const 
         const int Dn = max(uH + oe, uD + e);
         const int In = max(lH + oe, st.Il[r] + e);
         int h = max(max(Dn, d + s), In); /* v_max3_i32 */
-        if constexpr (LOCAL) {
+        if constexpr (MODE == 1) {
             h = max(h, 0);
             st.key[r] = max(st.key[r], ((unsigned)h << 16) | negj);
         }
@@ -1474,20 +1474,29 @@ __device__ __forceinline__ void aff_cells(AffState<R> &st, const int upH, const 
         st.Dl[r] = Dn;
     }
     st.dtop = upH;
+    if constexpr (MODE == 2) { /* ASG: no floor; the running (max, first column) of ONE row, register rsel = (m-1) % R of every lane (the lane
+                                * that owns row m reads it).  H may be negative: biased into 0 .. 65535.  A select chain on the wave-uniform
+                                * rsel, not an indexed read: the registers stay registers. */
+        int hm = st.Hl[0];
+#pragma unroll
+        for (int r = 1; r < R; r++) hm = (r == rsel) ? st.Hl[r] : hm;
+        st.key[0] = max(st.key[0], ((unsigned)(hm + 0x8000) << 16) | negj);
+    }
 }
 
-template <int R, bool LOCAL, bool STORE, bool MASKED, bool WHOLE>
+template <int R, int MODE, bool STORE, bool MASKED, bool WHOLE>
 __device__ __forceinline__ void aff_step(AffState<R> &st, const int t, const int lane, const int n, const bool laneHasRows,
                                          const int match, const int mismatch, const int oe, const int e, const int e0H,
                                          const int e0D, const int rc, int16_t *edgeH, int16_t *edgeD,
-                                         const bool writeEdge, int16_t *tileDst, const int storeLanes, const int rampLines) {
+                                         const bool writeEdge, int16_t *tileDst, const int storeLanes, const int rampLines,
+                                         [[maybe_unused]] const int rsel = 0) {
     const int j = t - lane + 1;
     const int upH = wave_shr1(st.Hl[R - 1], e0H);
     const int upD = wave_shr1(st.Dl[R - 1], e0D);
     bool active = true;
     if constexpr (MASKED) active = laneHasRows && (j >= 1) && (j <= n);
     if (active) {
-        aff_cells<R, LOCAL>(st, upH, upD, rc, match, mismatch, oe, e, 0xFFFFu - (unsigned)j);
+        aff_cells<R, MODE>(st, upH, upD, rc, match, mismatch, oe, e, 0xFFFFu - (unsigned)j, rsel);
         if (writeEdge && lane == 63) {
             edgeH[j] = (int16_t)st.Hl[R - 1];
             edgeD[j] = (int16_t)st.Dl[R - 1];
@@ -1550,16 +1559,32 @@ __device__ __forceinline__ void sw_publish(const dpx_fill_args &a, const int p, 
     }
 }
 
-/* one wave per pair: k_affine_fill (ANW) and k_asw_fill (ASW) share their body, dpx_affine_fill.inc */
+/* ASG: score and end cell of row m from that row's biased key (the lane that owns row m calls this with its own key): the first
+ * maximum over columns 0 .. n, column 0 being the border H[m][0] = o + m*e, which wins a tie as the smallest column */
+__device__ __forceinline__ void asg_publish(const dpx_fill_args &a, const int p, const int m, const unsigned key, const int colZero) {
+    const int hv = (int)(key >> 16) - 0x8000, col = 0xFFFF - (int)(key & 0xFFFFu);
+    const bool zero = colZero >= hv;
+    a.score[p] = zero ? colZero : hv;
+    a.endRow[p] = m;
+    a.endCol[p] = zero ? 0 : col;
+}
+
+/* one wave per pair: k_affine_fill (ANW), k_asw_fill (ASW) and k_asg_fill (ASG) share their body, dpx_affine_fill.inc */
 template <int R, bool STORE>
 __global__ void __launch_bounds__(DPX_FILL_THREADS) k_affine_fill(const dpx_fill_args a) {
-    constexpr bool LOCAL = false;
+    constexpr bool LOCAL = false, SEMI = false;
 #include "dpx_affine_fill.inc"
 }
 
 template <int R, bool STORE>
 __global__ void __launch_bounds__(DPX_FILL_THREADS) k_asw_fill(const dpx_fill_args a) {
-    constexpr bool LOCAL = true;
+    constexpr bool LOCAL = true, SEMI = false;
+#include "dpx_affine_fill.inc"
+}
+
+template <int R, bool STORE>
+__global__ void __launch_bounds__(DPX_FILL_THREADS) k_asg_fill(const dpx_fill_args a) {
+    constexpr bool LOCAL = false, SEMI = true;
 #include "dpx_affine_fill.inc"
 }
 
@@ -1580,13 +1605,14 @@ struct AffStateG {
     int qc[R];
     int dtopOe;        /* H[row0][j-1] + (o+e) */
     int DeLast;        /* D[row0+R][j] + e of the column just computed (the next lane's "D above") */
-    unsigned key[R];   /* ASW: per-row running max of (H << 16 | 0xFFFF - j) */
+    unsigned key[R];   /* ASW: per-row running max of (H << 16 | 0xFFFF - j); ASG: key[0] alone, of ((H + 0x8000) << 16 | 0xFFFF - j) in register rsel */
 };
 
 /* D = max(H_up + oe, D_up + e);  I = max(H_left + oe, I_left + e);  H = max3(D, H_diag + s, I)   (c++/AffineNeedlemanWunsch.cpp:185-236) */
-template <int R, bool LOCAL>
+template <int R, int MODE> /* 0 ANW, 1 ASW, 2 ASG */
 __device__ __forceinline__ void aff_cells_g(AffStateG<R> &st, const int upHoe, const int upDe, const int rc, const int matchG, const int mismatchG,
-                                            const int oe, const int e, int (&Hv)[R], int (&Iv)[R], int (&Dv)[R], const unsigned negj) {
+                                            const int oe, const int e, int (&Hv)[R], int (&Iv)[R], int (&Dv)[R], const unsigned negj,
+                                            [[maybe_unused]] const int rsel = 0) {
     int dterm[R];
 #pragma unroll
     for (int r = 0; r < R; r++) dterm[r] = ((r == 0) ? st.dtopOe : st.Hoe[r - 1]) + ((st.qc[r] == rc) ? matchG : mismatchG); /* (s - oe) */
@@ -1596,7 +1622,7 @@ __device__ __forceinline__ void aff_cells_g(AffStateG<R> &st, const int upHoe, c
         const int Dn = max(ug, ud);
         const int In = max(st.Hoe[r], st.Ie[r]);
         int h = max(max(Dn, dterm[r]), In); /* v_max3_i32 */
-        if constexpr (LOCAL) { /* ASW: the zero floor, and the row's start-cell key */
+        if constexpr (MODE == 1) { /* ASW: the zero floor, and the row's start-cell key */
             h = max(h, 0);
             st.key[r] = max(st.key[r], ((unsigned)h << 16) | negj);
         }
@@ -1608,17 +1634,29 @@ __device__ __forceinline__ void aff_cells_g(AffStateG<R> &st, const int upHoe, c
     }
     st.DeLast = ud;
     st.dtopOe = upHoe;
+    if constexpr (MODE == 2) { /* ASG: the biased key of one row, register rsel = (m-1) % 8 of the slot's lanes (aff_cells) */
+        int hm = Hv[0];
+#pragma unroll
+        for (int r = 1; r < R; r++) hm = (r == rsel) ? Hv[r] : hm;
+        st.key[0] = max(st.key[0], ((unsigned)(hm + 0x8000) << 16) | negj);
+    }
 }
 
 template <int R, bool STORE>
 __global__ void __launch_bounds__(DPX_ALANES_THREADS) k_affine_lanes(const dpx_fill_args a) {
-    constexpr bool LOCAL = false;
+    constexpr bool LOCAL = false, SEMI = false;
 #include "dpx_affine_lanes.inc"
 }
 
 template <int R, bool STORE>
 __global__ void __launch_bounds__(DPX_ALANES_THREADS) k_asw_lanes(const dpx_fill_args a) {
-    constexpr bool LOCAL = true;
+    constexpr bool LOCAL = true, SEMI = false;
+#include "dpx_affine_lanes.inc"
+}
+
+template <int R, bool STORE>
+__global__ void __launch_bounds__(DPX_ALANES_THREADS) k_asg_lanes(const dpx_fill_args a) {
+    constexpr bool LOCAL = false, SEMI = true;
 #include "dpx_affine_lanes.inc"
 }
 
@@ -1999,6 +2037,7 @@ __global__ void k_export_matrix(const int16_t *mat, dpx_pair_dev pr, int algo, i
             if (plane != 0) v = 0;                                   /* I / D are zero-initialised (ANW.cpp:24-27) */
             else if (algo == DPX_K_LNW) v = len * gapOpen;           /* LNW.cpp:31-41 */
             else if (algo == DPX_K_ANW) v = len == 0 ? 0 : gapOpen + len * gapExtend; /* ANW.cpp:43-53 */
+            else if (algo == DPX_K_ASG) v = i == 0 ? 0 : gapOpen + i * gapExtend; /* ASG: free row 0, ANW's column 0 */
             else v = 0;                                              /* LSW / BSW / ASW */
         } else if (algo == DPX_K_BSW) {
             const int dlt = i - j;
@@ -2123,8 +2162,9 @@ struct TileWalker {
     }
 };
 
-/* one lane walks one pair (ASW = true: k_asw_traceback, algo DPX_K_ASW, the ANW walk's local form) */
-template <bool ASW>
+/* one lane walks one pair (MODE 1: k_asw_traceback, algo DPX_K_ASW, the ANW walk's local form; MODE 2: k_asg_traceback, algo DPX_K_ASG, the ANW
+ * walk under ASG's borders, which stops on row 0) */
+template <int MODE>
 __device__ void tb_walk_lane(const dpx_fill_args &a, const int p, int algo, int R, int planes, int cachedWalk, const int32_t *endRow,
                              const int32_t *endCol, const uint64_t *tbOff, char *tb, int32_t *tbLen) {
     const dpx_pair_dev pr = a.pairs[p];
@@ -2212,16 +2252,19 @@ __device__ void tb_walk_lane(const dpx_fill_args &a, const int p, int algo, int 
             else if (del >= mm) { EMIT('_', ' ', qc); i--; }
             else { EMIT(rc, eq ? '*' : '|', qc); i--; j--; }
         }
-    } else { /* ANW; ASW (k_asw_traceback): the same walk, which stops where H = 0 and has no end gaps */
+    } else { /* ANW; ASW (k_asw_traceback): the same walk, which stops where H = 0 and has no end gaps; ASG (k_asg_traceback): no row-0 tail */
         const int o = a.gapOpen, e = a.gapExtend;
         int cur = 0; /* 0 SCORING, 1 INSERTION, 2 DELETION */
         while (i != 0 && j != 0) {
             if (cur == 0) {
-                if constexpr (ASW) {
+                if constexpr (MODE == 1) {
                     if (v.get(i, j, 0) <= 0) break;
                 }
                 const bool eq = qw.get(i - 1) == rw.get(j - 1);
-                const int mm = v.get(i - 1, j - 1, 0) + (eq ? match : mismatch);
+                int dg;
+                if constexpr (MODE == 2) dg = i == 1 ? 0 : (j == 1 ? o + (i - 1) * e : v.get(i - 1, j - 1, 0)); /* ASG's borders (the only border cell this walk reads) */
+                else dg = v.get(i - 1, j - 1, 0);
+                const int mm = dg + (eq ? match : mismatch);
                 const int D = v.get(i, j, 2), I = v.get(i, j, 1);
                 const int vmax = max(D, mm);
                 if (I >= vmax) cur = 1;
@@ -2237,9 +2280,11 @@ __device__ void tb_walk_lane(const dpx_fill_args &a, const int p, int algo, int 
                 EMIT('_', ' ', qw.get(i - 1)); i--;
             }
         }
-        if constexpr (!ASW) {
+        if constexpr (MODE != 1) {
             while (i > 0) { EMIT('_', ' ', qw.get(i - 1)); i--; }
-            while (j > 0) { EMIT(rw.get(j - 1), ' ', '_'); j--; }
+            if constexpr (MODE == 0) {
+                while (j > 0) { EMIT(rw.get(j - 1), ' ', '_'); j--; }
+            }
         }
     }
 #undef EMIT
@@ -2256,14 +2301,21 @@ __global__ void k_traceback(const dpx_fill_args a, int numPairs, int algo, int R
                             const int32_t *endCol, const uint64_t *tbOff, char *tb, int32_t *tbLen) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= numPairs) return;
-    tb_walk_lane<false>(a, p, algo, R, planes, cachedWalk, endRow, endCol, tbOff, tb, tbLen);
+    tb_walk_lane<0>(a, p, algo, R, planes, cachedWalk, endRow, endCol, tbOff, tb, tbLen);
 }
 
 __global__ void k_asw_traceback(const dpx_fill_args a, int numPairs, int R, int planes, const int32_t *endRow, const int32_t *endCol,
                                 const uint64_t *tbOff, char *tb, int32_t *tbLen) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= numPairs) return;
-    tb_walk_lane<true>(a, p, DPX_K_ASW, R, planes, 0, endRow, endCol, tbOff, tb, tbLen);
+    tb_walk_lane<1>(a, p, DPX_K_ASW, R, planes, 0, endRow, endCol, tbOff, tb, tbLen);
+}
+
+__global__ void k_asg_traceback(const dpx_fill_args a, int numPairs, int R, int planes, const int32_t *endRow, const int32_t *endCol,
+                                const uint64_t *tbOff, char *tb, int32_t *tbLen) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= numPairs) return;
+    tb_walk_lane<2>(a, p, DPX_K_ASG, R, planes, 0, endRow, endCol, tbOff, tb, tbLen);
 }
 
 /* -----------------------------------------------------------------------------------------------------
@@ -2336,7 +2388,7 @@ __global__ void __launch_bounds__(64) k_traceback_wave(const dpx_fill_args a, in
     const dpx_pair_dev pr = a.pairs[p];
     const int n = pr.n, m = pr.m;
     const int Rr = pr.rows ? (int)pr.rows : R;
-    /* (the host launches this kernel for LSW / LNW / banded SW with one plane and ANW / ASW with three; rows per lane are
+    /* (the host launches this kernel for LSW / LNW / banded SW with one plane and ANW / ASW / ASG with three; rows per lane are
      * 2, 4, 8 or 16 in every full-matrix layout; empty sequences walk along a border or not at all) */
     const unsigned char *ref = reinterpret_cast<const unsigned char *>(a.seq + pr.refIdx);
     const unsigned char *qry = reinterpret_cast<const unsigned char *>(a.seq + pr.qryIdx);
@@ -2346,7 +2398,8 @@ __global__ void __launch_bounds__(64) k_traceback_wave(const dpx_fill_args a, in
     int pos = cap;
     const int match = a.match, mismatch = a.mismatch, g = a.gapOpen, ext = a.gapExtend;
     /* H on row 0 / column 0, `len` cells from the corner (TbView::get): LNW len * gap, ANW open + len * extend (0 in the corner), LSW / ASW 0 */
-    auto bval = [&](const int len) -> int { return algo == DPX_K_LNW ? len * g : (algo == DPX_K_ANW ? (len ? g + len * ext : 0) : 0); };
+    auto bval = [&](const int len) -> int { return algo == DPX_K_LNW ? len * g : ((algo == DPX_K_ANW || algo == DPX_K_ASG) ? (len ? g + len * ext : 0) : 0); };
+    auto bvalRow = [&](const int len) -> int { return algo == DPX_K_ASG ? 0 : bval(len); }; /* ASG: row 0 is free, column 0 is ANW's */
     /* where the 16-byte piece (8 rows of a row group, one column) lies: shifts only for the two layouts whose lanes own >= 8 rows */
     const int Q = Rr >> 3, lgQ = Q == 2 ? 1 : 0;
     const int kind = Rr >= 8 ? (pr.lanes == 64 ? 0 : pr.lanes == 16 ? 1 : 2) : 2;
@@ -2468,8 +2521,8 @@ __global__ void __launch_bounds__(64) k_traceback_wave(const dpx_fill_args a, in
 #pragma unroll
                     for (int e = 0; e < 8; e += 2) {
                         const int r0b = grp * 8 + 1 + e, r1b = r0b + 1;
-                        const int v0 = jc == 0 ? (r0b >= 0 ? bval(r0b) : 0) : (r0b == 0 && jc > 0 ? bval(jc) : 0);
-                        const int v1 = jc == 0 ? (r1b >= 0 ? bval(r1b) : 0) : (r1b == 0 && jc > 0 ? bval(jc) : 0);
+                        const int v0 = jc == 0 ? (r0b >= 0 ? bval(r0b) : 0) : (r0b == 0 && jc > 0 ? bvalRow(jc) : 0);
+                        const int v1 = jc == 0 ? (r1b >= 0 ? bval(r1b) : 0) : (r1b == 0 && jc > 0 ? bvalRow(jc) : 0);
                         d[e >> 1] = ((uint32_t)(uint16_t)v1 << 16) | (uint32_t)(uint16_t)v0;
                     }
                     v[0][gi] = u32x4{d[0], d[1], d[2], d[3]};
@@ -2610,7 +2663,7 @@ __global__ void __launch_bounds__(64) k_traceback_wave(const dpx_fill_args a, in
     };
     int cur = 0; /* ANW: 0 SCORING, 1 INSERTION, 2 DELETION */
     for (;;) {
-        if ((algo == DPX_K_LSW || algo == DPX_K_ASW) ? !(i > 0 && j > 0) : !(i != 0 || j != 0)) break;
+        if ((algo == DPX_K_LSW || algo == DPX_K_ASW) ? !(i > 0 && j > 0) : (algo == DPX_K_ASG ? i == 0 : !(i != 0 || j != 0))) break; /* (ASG: row 0 ends the walk) */
         if (need_window()) { load_window(max(i, 1), max(j, 1)); wantFull = false; } /* (a window anchored on row 1 / column 1 also serves row 0 / column 0) */
         const int r = i - R0 - 1, c = j - cLo;
         if constexpr (PLANES == 1) {
@@ -2954,6 +3007,12 @@ hipError_t launch_asw_R(const dpx_fill_args &a, bool store, dim3 grid, size_t ld
                  : launch_fill_kernel(k_asw_fill<R, false>, a, grid, lds, s);
 }
 
+template <int R>
+hipError_t launch_asg_R(const dpx_fill_args &a, bool store, dim3 grid, size_t lds, hipStream_t s) {
+    return store ? launch_fill_kernel(k_asg_fill<R, true>, a, grid, lds, s)
+                 : launch_fill_kernel(k_asg_fill<R, false>, a, grid, lds, s);
+}
+
 } // namespace
 
 /* ---- host-callable launchers (used by dpx_capi.cpp) ---- */
@@ -2997,6 +3056,14 @@ hipError_t dpx_launch_fill(const dpx_fill_args &a, int algo, int R, bool store, 
         default: return hipErrorInvalidValue;
         }
     }
+    if (algo == DPX_K_ASG) {
+        switch (R) {
+        case 2: return launch_asg_R<2>(a, store, grid, ldsBytes, stream);
+        case 4: return launch_asg_R<4>(a, store, grid, ldsBytes, stream);
+        case 8: return launch_asg_R<8>(a, store, grid, ldsBytes, stream);
+        default: return hipErrorInvalidValue;
+        }
+    }
     return hipErrorInvalidValue;
 }
 
@@ -3005,9 +3072,9 @@ hipError_t dpx_launch_fill(const dpx_fill_args &a, int algo, int R, bool store, 
  * 1 for the affine one). */
 size_t dpx_lanes_stage_bytes(int algo, int R, bool store) {
     if (!store) return (size_t)kLaneScratch;
-    return (size_t)((algo == DPX_K_ANW || algo == DPX_K_ASW) ? 3 : 1) * (size_t)(R / 8) * 64u * (size_t)kStageLine;
+    return (size_t)((algo == DPX_K_ANW || algo == DPX_K_ASW || algo == DPX_K_ASG) ? 3 : 1) * (size_t)(R / 8) * 64u * (size_t)kStageLine;
 }
-int dpx_lanes_waves_per_block(int algo) { return (algo == DPX_K_ANW || algo == DPX_K_ASW) ? DPX_ALANES_THREADS / 64 : DPX_FILL_THREADS / 64; } /* (the most: small launches of the linear kernels use 1) */
+int dpx_lanes_waves_per_block(int algo) { return (algo == DPX_K_ANW || algo == DPX_K_ASW || algo == DPX_K_ASG) ? DPX_ALANES_THREADS / 64 : DPX_FILL_THREADS / 64; } /* (the most: small launches of the linear kernels use 1) */
 
 template <class K>
 static hipError_t launch_lanes_kernel(K kernel, const dpx_fill_args &a, dim3 grid, int threads, size_t lds, hipStream_t s) {
@@ -3021,7 +3088,7 @@ static hipError_t launch_lanes_kernel(K kernel, const dpx_fill_args &a, dim3 gri
 
 hipError_t dpx_launch_fill_lanes(const dpx_fill_args &a, int algo, int R, bool store, size_t ldsBytes, hipStream_t stream) {
     if (a.numPairs <= 0) return hipSuccess;
-    const int wpb = (algo == DPX_K_ANW || algo == DPX_K_ASW) ? DPX_ALANES_THREADS / 64 : (int)a.wavesPerBlock; /* (ldsBytes = per wave x this) */
+    const int wpb = (algo == DPX_K_ANW || algo == DPX_K_ASW || algo == DPX_K_ASG) ? DPX_ALANES_THREADS / 64 : (int)a.wavesPerBlock; /* (ldsBytes = per wave x this) */
     dim3 grid((unsigned)((a.numPairs + wpb - 1) / wpb));
     if (algo == DPX_K_ANW) {
         const int th = DPX_ALANES_THREADS;
@@ -3033,6 +3100,12 @@ hipError_t dpx_launch_fill_lanes(const dpx_fill_args &a, int algo, int R, bool s
         const int th = DPX_ALANES_THREADS;
         if (R == 8) return store ? launch_lanes_kernel(k_asw_lanes<8, true>, a, grid, th, ldsBytes, stream)
                                  : launch_lanes_kernel(k_asw_lanes<8, false>, a, grid, th, ldsBytes, stream);
+        return hipErrorInvalidValue;
+    }
+    if (algo == DPX_K_ASG) {
+        const int th = DPX_ALANES_THREADS;
+        if (R == 8) return store ? launch_lanes_kernel(k_asg_lanes<8, true>, a, grid, th, ldsBytes, stream)
+                                 : launch_lanes_kernel(k_asg_lanes<8, false>, a, grid, th, ldsBytes, stream);
         return hipErrorInvalidValue;
     }
     const bool local = algo == DPX_K_LSW;
@@ -3127,11 +3200,13 @@ hipError_t dpx_launch_traceback(const dpx_fill_args &a, int numPairs, int algo, 
     if (numPairs <= 0) return hipSuccess;
     const bool cachedWalk = walk == 1;
     if (walk == 2) { /* one wave per pair with an LDS window (k_traceback_wave) */
-        const size_t lds = dpx_traceback_wave_lds((algo == DPX_K_ANW || algo == DPX_K_ASW) ? 3 : 1);
+        const size_t lds = dpx_traceback_wave_lds((algo == DPX_K_ANW || algo == DPX_K_ASW || algo == DPX_K_ASG) ? 3 : 1);
         if (algo == DPX_K_ANW)
             hipLaunchKernelGGL((k_traceback_wave<3, false, DPX_K_ANW>), dim3((unsigned)numPairs), dim3(64), lds, stream, a, numPairs, R, a.endRow, a.endCol, tbOff, tb, tbLen);
         else if (algo == DPX_K_ASW)
             hipLaunchKernelGGL((k_traceback_wave<3, false, DPX_K_ASW>), dim3((unsigned)numPairs), dim3(64), lds, stream, a, numPairs, R, a.endRow, a.endCol, tbOff, tb, tbLen);
+        else if (algo == DPX_K_ASG)
+            hipLaunchKernelGGL((k_traceback_wave<3, false, DPX_K_ASG>), dim3((unsigned)numPairs), dim3(64), lds, stream, a, numPairs, R, a.endRow, a.endCol, tbOff, tb, tbLen);
         else if (algo == DPX_K_BSW)
             hipLaunchKernelGGL((k_traceback_wave<1, true, DPX_K_LSW>), dim3((unsigned)numPairs), dim3(64), lds, stream, a, numPairs, R, a.endRow, a.endCol, tbOff, tb, tbLen);
         else if (algo == DPX_K_LNW)
@@ -3142,6 +3217,9 @@ hipError_t dpx_launch_traceback(const dpx_fill_args &a, int numPairs, int algo, 
     }
     if (algo == DPX_K_ASW) /* (walk 1 caches linear-gap columns only: the ASW walk is walk 0's) */
         hipLaunchKernelGGL(k_asw_traceback, dim3((unsigned)((numPairs + 63) / 64)), dim3(64), 0, stream, a, numPairs, R, planes, a.endRow,
+                           a.endCol, tbOff, tb, tbLen);
+    else if (algo == DPX_K_ASG) /* (likewise; ASG's borders are this walk's own) */
+        hipLaunchKernelGGL(k_asg_traceback, dim3((unsigned)((numPairs + 63) / 64)), dim3(64), 0, stream, a, numPairs, R, planes, a.endRow,
                            a.endCol, tbOff, tb, tbLen);
     else
         hipLaunchKernelGGL(k_traceback, dim3((unsigned)((numPairs + 63) / 64)), dim3(64), 0, stream, a, numPairs, algo, R, planes,

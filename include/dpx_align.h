@@ -25,7 +25,7 @@ extern "C" {
 /* 1: round 1.  2: + dpx_batch_create_on, dpx_batch_fill_timed, dpx_batch_last_fill_usec, dpx_batch_output_begin/_end/_take,
  * dpx_text_free, DPX_TUNE_PLACEMENT (round 2).  3: + dpx_pool_reserve, dpx_text_reserve, dpx_batch_last_output_usec, dpx_pack2, dpx_batch_create_packed2; dpx_batch_describe reports the
  * matrix pool (round 3); + DPX_KEEP_DIRECTIONS, dpx_batch_directions (detect them by the exported symbol: the number stays 3); + DPX_ALGO_ASW
- * (detect it by creating a batch: an older library returns DPX_ERR_INVALID for algo 4); + DPX_ALGO_BASW (likewise: DPX_ERR_INVALID for algo 5).  Additions only: a caller built against an older version keeps working; dpx_abi_version() >= the version
+ * (detect it by creating a batch: an older library returns DPX_ERR_INVALID for algo 4); + DPX_ALGO_BASW (likewise: DPX_ERR_INVALID for algo 5); + DPX_ALGO_ASG (likewise: DPX_ERR_INVALID for algo 6).  Additions only: a caller built against an older version keeps working; dpx_abi_version() >= the version
  * a caller needs is the check. */
 #define DPX_ABI_VERSION 3
 
@@ -53,7 +53,7 @@ typedef enum dpx_algo {
                          the walk follows ANW's three states from there and stops where H = 0 (no end gaps); LSW's text block.  Same
                          dpx_params fields as ANW (band ignored).  Every flag ANW takes: matrices, DPX_SCORE_ONLY, DPX_KEEP_DIRECTIONS.
                          Added without an ABI bump: a library that predates it returns DPX_ERR_INVALID for algo 4. */
-    DPX_ALGO_BASW = 5 /* banded affine-gap Smith-Waterman, no reference counterpart: ASW's parameters plus BSW's band B >= 1.  A cell
+    DPX_ALGO_BASW = 5, /* banded affine-gap Smith-Waterman, no reference counterpart: ASW's parameters plus BSW's band B >= 1.  A cell
                          (i, j), 1 <= i <= m, 1 <= j <= n, is in the band when |i - j| <= B - 1 (BSW's rule).  In-band cells follow ASW's
                          recurrence and tie order: D = max(H_up + o + e, D_up + e), I = max(H_left + o + e, I_left + e), GAP_OPEN wins a
                          tie; best = H_diag + s, D >= best takes it, then I >= best takes it; H = max(0, best), move NONE where H == 0.
@@ -66,6 +66,33 @@ typedef enum dpx_algo {
                          band that does not cover the matrix is DPX_ERR_UNSUPPORTED.  gapOpen = 0 gives BSW's H matrix with linear gap
                          gapExtend.  Matrices and DPX_SCORE_ONLY; DPX_KEEP_DIRECTIONS is DPX_ERR_UNSUPPORTED, as for BSW.
                          Added without an ABI bump or a new symbol: a library that predates it returns DPX_ERR_INVALID for algo 5. */
+    DPX_ALGO_ASG = 6  /* affine-gap semi-global alignment ("fitting", "glocal", ends-free in the reference), no reference counterpart: the
+                         whole query is aligned end to end against the stretch of the reference that fits it best; the reference before
+                         and after that stretch costs nothing.  Same dpx_params fields as ANW; band is ignored.  Reference of length n
+                         along columns j, query of length m along rows i.
+                         Borders: H[0][j] = 0 for 0 <= j <= n (leading reference bases are free); H[i][0] = gapOpen + i*gapExtend for
+                         i >= 1 (ANW's column border); I and D have virtual -infinity borders exactly as in ANW, so row 1 always opens
+                         D and column 1 always opens I.
+                         Cells: ANW's recurrence and tie order, unchanged: D = max(H_up + o + e, D_up + e), I = max(H_left + o + e,
+                         I_left + e), GAP_OPEN wins a tie; best = H_diag + s (MATCH or MISMATCH), D >= best takes it (QUERY_DELETION),
+                         then I >= best takes it (QUERY_INSERTION).  There is no zero floor.
+                         Score = max over 0 <= j <= n of H[m][j]; the end cell is (m, j*) with j* the smallest such j (trailing
+                         reference bases are free).  j = 0 takes part: when the whole query as one gap beats everything else the result
+                         is (m, 0) with score o + m*e.  m = 0 gives score 0 at (0, 0); n = 0 with m > 0 gives o + m*e at (m, 0).  The
+                         score may be zero or negative with a real path.
+                         Walk: ANW's three-state walk from the end cell in state SCORING while i != 0 && j != 0; then the remaining i
+                         query characters are emitted as deletions (ANW's column-0 tail); the remaining j reference characters are NOT
+                         emitted: the walk stops at row 0.  The reference start column of the alignment is endCol minus the number of
+                         non-'_' characters of the reference line.
+                         Text: the "<pair> | <score>\n" header, then the reference, relation and query lines; the path is printed
+                         whatever the sign of the score, only m = 0 gives three empty lines (unlike LSW's zero-score case).
+                         dpx_batch_matrix: row-major (m+1) x (n+1), H with the borders above, I and D with 0 on the borders, as for
+                         ANW.  dpx_batch_directions: H plane NONE_MAIN along row 0 ((0, 0) included) and QUERY_DELETION down column 0
+                         for i >= 1; I and D planes 0 on the borders.
+                         Every flag ANW takes: matrices, DPX_SCORE_ONLY, DPX_KEEP_DIRECTIONS (int32 scores, references past 65 000
+                         columns); packed2 input, dpx_align_batch, the output pipeline, dpx_batch_create_on and a caller's stream.
+                         ASG(ref, qry).score == max over 0 <= a <= b <= n of ANW(ref[a:b], qry).score.
+                         Added without an ABI bump or a new symbol: a library that predates it returns DPX_ERR_INVALID for algo 6. */
 } dpx_algo;
 
 /* Identical in layout to the reference's `struct seqPair` (c++/parseInput.h:22-29): byte offsets into the
@@ -83,19 +110,19 @@ typedef struct dpx_params {
     int32_t algo;      /* dpx_algo */
     int32_t match;
     int32_t mismatch;
-    int32_t gapOpen;   /* linear gap for LNW/LSW/BSW; gap-open for ANW */
-    int32_t gapExtend; /* ANW only */
+    int32_t gapOpen;   /* linear gap for LNW/LSW/BSW; gap-open for ANW / ASW / BASW / ASG */
+    int32_t gapExtend; /* ANW / ASW / BASW / ASG only */
     int32_t band;      /* BSW / BASW: cells with |i-j| <= band-1 are computed */
 } dpx_params;
 
 /* dpx_batch_create flags */
-#define DPX_KEEP_MATRICES 0x0u /* default: write the int16 score matrices (H; H,I,D for ANW) to HBM */
+#define DPX_KEEP_MATRICES 0x0u /* default: write the int16 score matrices (H; H,I,D for ANW / ASW / BASW / ASG) to HBM */
 #define DPX_SCORE_ONLY    0x1u /* no matrix writeback (not HBM-bound; never used for the roofline figure) */
 #define DPX_TIME_FILLS    0x2u /* bracket every dpx_batch_fill() with HIP events: dpx_batch_last_fill_usec() */
 #define DPX_TUNE_PLACEMENT 0x4u /* the batch will be filled many times: time its matrix pool (>= 1 GiB) with hipMemset and shop for a better
                                    one with the batch's OWN FILL on four more candidate pools (the same fill runs 2 - 27 % apart on
                                    two pools of the same construction); every candidate's times go into dpx_batch_describe's pool_* fields */
-#define DPX_KEEP_DIRECTIONS 0x8u /* LNW / LSW / ANW / ASW: keep one 4-bit direction code per cell instead of the int16 score matrices, compute in
+#define DPX_KEEP_DIRECTIONS 0x8u /* LNW / LSW / ANW / ASW / ASG: keep one 4-bit direction code per cell instead of the int16 score matrices, compute in
                                     int32 (the reference's evolved kernels keep directions only, cuda/LNW/LinearNeedlemanWunschV6.cu:167).  Same
                                     scores, end cells, text and tracebacks as a DPX_KEEP_MATRICES batch; half a byte per cell plus ~32 B of stripe
                                     padding per query row (about a quarter of an int16 H batch's bytes, a twelfth of ANW's H/I/D, from
@@ -105,8 +132,8 @@ typedef struct dpx_params {
 
 /* matrix selectors for dpx_batch_matrix / dpx_batch_directions */
 #define DPX_MAT_H 0 /* scoring matrix   (reference: memo / scoringMemo)            */
-#define DPX_MAT_I 1 /* ANW / ASW / BASW horizontal-gap matrix (queryInsertionMemo)  */
-#define DPX_MAT_D 2 /* ANW / ASW / BASW vertical-gap matrix   (queryDeletionMemo)   */
+#define DPX_MAT_I 1 /* ANW / ASW / BASW / ASG horizontal-gap matrix (queryInsertionMemo)  */
+#define DPX_MAT_D 2 /* ANW / ASW / BASW / ASG vertical-gap matrix   (queryDeletionMemo)   */
 
 typedef struct dpx_batch dpx_batch; /* opaque, device-resident batch of pairs */
 
@@ -204,7 +231,7 @@ int dpx_batch_matrix(dpx_batch *b, size_t pair, int which, int16_t *out);
  * uint8 including the border row / column, values of c++/backtrack.h -- `which` DPX_MAT_H: enum directionMain (NONE_MAIN 0, MATCH 1,
  * MISMATCH 2, QUERY_INSERTION 3, QUERY_DELETION 4; LNW / ANW borders: QUERY_DELETION down column 0, QUERY_INSERTION along row 0;
  * LSW: NONE_MAIN where the best candidate is negative, c++/LinearSmithWaterman.cpp:106-109; ASW: NONE_MAIN wherever H == 0, borders
- * included); DPX_MAT_I / DPX_MAT_D (ANW / ASW):
+ * included; ASG: NONE_MAIN along row 0, QUERY_DELETION down column 0); DPX_MAT_I / DPX_MAT_D (ANW / ASW / ASG):
  * enum directionIndel (GAP_OPEN 1, GAP_EXTEND 2; 0 on the borders).  DPX_ERR_NO_MATRIX on a batch without the flag. */
 int dpx_batch_directions(dpx_batch *b, size_t pair, int which, uint8_t *out);
 
