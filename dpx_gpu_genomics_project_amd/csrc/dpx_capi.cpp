@@ -703,14 +703,18 @@ int dpx_shutdown(void) {
 
 /* ------------------------------------------------------------------------------------------ batch */
 
-/* the three-plane Gotoh algorithms: ANW (global), ASW (local), BASW (local, banded) and ASG (semi-global) */
-static bool is_affine(int algo) { return algo == DPX_ALGO_ANW || algo == DPX_ALGO_ASW || algo == DPX_ALGO_BASW || algo == DPX_ALGO_ASG; }
+/* the three-plane Gotoh algorithms: ANW (global), ASW (local), BASW (local, banded), ASG (semi-global) and BANW (global, banded) */
+static bool is_affine(int algo) {
+    return algo == DPX_ALGO_ANW || algo == DPX_ALGO_ASW || algo == DPX_ALGO_BASW || algo == DPX_ALGO_ASG || algo == DPX_ALGO_BANW;
+}
 /* the algorithms with a band parameter (and, unless the band covers the matrix, the anti-diagonal band kernels and layout) */
-static bool is_banded(int algo) { return algo == DPX_ALGO_BSW || algo == DPX_ALGO_BASW; }
+static bool is_banded(int algo) { return algo == DPX_ALGO_BSW || algo == DPX_ALGO_BASW || algo == DPX_ALGO_BANW; }
+/* ... of which the three-plane ones (dpx_basw_kernels.hip, dpx_banw_kernels.hip: chunks of three planes, no packed-int16 variant) */
+static bool is_banded_affine(int algo) { return algo == DPX_ALGO_BASW || algo == DPX_ALGO_BANW; }
 
 static int validate_params(const dpx_params *p) {
     if (!p) return DPX_ERR_INVALID;
-    if (p->algo < DPX_ALGO_LNW || p->algo > DPX_ALGO_ASG) return DPX_ERR_INVALID;
+    if (p->algo < DPX_ALGO_LNW || p->algo > DPX_ALGO_BANW) return DPX_ERR_INVALID;
     if (is_banded(p->algo) && p->band < 1) return DPX_ERR_INVALID;
     /* the int32 kernels add a weight to a cell value (|H| <= 32767 after fits_int16) and to the affine kernels' virtual
      * -2^29 borders: weights beyond +-2^20 could wrap those sums (and no int16 matrix could hold what they produce) */
@@ -743,6 +747,23 @@ static bool fits_int16(const dpx_params &p, long long m, long long n) {
     if (p.algo == DPX_ALGO_LNW) {
         const long long lo = neg(p.gapOpen) * (m + n), hi = diag + pos(p.gapOpen) * (m + n);
         return lo >= -lim && hi <= lim;
+    }
+    if (p.algo == DPX_ALGO_BANW) {
+        /* hiH is ANW's: a band only removes paths, and hiH sums the positive contributions any path can collect.
+         * loH: ANW's "every cell can fall back on the all-gap path" does not hold inside a band (that path leaves it).  A path that
+         * does stay in the band reaches every in-band cell (i, j): the diagonal from (0, 0) to (k, k), k = min(i, j), whose cells have
+         * i - j = 0, then ONE gap of |i - j| <= min(B - 1, max(m, n)) steps along row or column k, whose cells have |i' - j'| <= |i - j|.
+         * H is the maximum over in-band paths, so with w = min(match, mismatch) and g = that gap bound
+         *       H[i][j] >= k * w + (i != j ? o + |i - j| * e : 0) >= neg(w) * min(m, n) + neg(o) + neg(e) * g = loH
+         * (the in-band border cells are the case k = 0).  The diagonal term the fill and the walks form, H[i-1][j-1] + s, is >= loH by
+         * the same path with one diagonal step fewer and s in its place.  A finite I (D) is >= its open term H_left + o + e (H_up + o + e)
+         * >= loH + (o + e), and <= hiH + pos(o) + pos(e) * max(m, n) as for ANW.  So every finite stored value is >= lo >= -32767, and
+         * -32768 is free to stand for minus infinity in dpx_batch_matrix and in the walks' windows.  No m + n <= 65000: the kernel keeps
+         * no step key. */
+        const long long o = p.gapOpen, e = p.gapExtend, g = std::min<long long>(std::max<long long>(p.band - 1, 0), std::max(m, n));
+        const long long loH = neg(std::min<long long>(p.match, p.mismatch)) * std::min(m, n) + neg(o) + neg(e) * g;
+        const long long hiH = diag + (pos(o) + pos(e)) * (m + n);
+        return loH + neg(o + e) >= -lim && hiH + pos(o) + pos(e) * std::max(m, n) <= lim;
     }
     /* ANW, and ASG: every ASG cell H[i][j] is the best score of an alignment path between a reference substring ref[a:j] and the query
      * prefix qry[0:i] (the free row 0 chooses a), or the column-0 border, an all-gap path.  Such a path has at most m + n steps and at
@@ -1106,6 +1127,15 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
             delete b;
             return DPX_ERR_INVALID;
         }
+        if (params->algo == DPX_ALGO_BANW && std::llabs((long long)sp.querySize - (long long)sp.referenceSize) >= (long long)params->band) {
+            /* no global path stays inside the band: the end cell (m, n) itself is outside it */
+            t_err = "DPX_ALGO_BANW: pair " + std::to_string(i) + " (query " + std::to_string(sp.querySize) + ", reference " +
+                    std::to_string(sp.referenceSize) + ") needs band >= " +
+                    std::to_string(std::llabs((long long)sp.querySize - (long long)sp.referenceSize) + 1) + ", the batch has band " +
+                    std::to_string(params->band);
+            delete b;
+            return DPX_ERR_UNSUPPORTED;
+        }
         if (!(dirs ? fits_dir(*params, sp.querySize, sp.referenceSize) : fits_int16(*params, sp.querySize, sp.referenceSize))) { delete b; return DPX_ERR_RANGE; }
         dpx_pair_dev &pd = b->pairs[i];
         pd.refIdx = sp.referenceIdx; pd.n = sp.referenceSize;
@@ -1133,8 +1163,9 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
     b->R = R;
     int kernelAlgo = params->algo;
     if (is_banded(params->algo)) {
-        if (params->band >= std::max(b->maxM, b->maxN)) {
-            kernelAlgo = params->algo == DPX_ALGO_BSW ? DPX_ALGO_LSW : DPX_ALGO_ASW; /* the band covers every cell: identical to the unbanded recurrence */
+        /* (BANW: + 1, its band applies to the border cells too -- at B = max(m, n) the border cell (m, 0) or (0, n) is outside it) */
+        if ((long long)params->band >= (long long)std::max(b->maxM, b->maxN) + (params->algo == DPX_ALGO_BANW ? 1 : 0)) {
+            kernelAlgo = params->algo == DPX_ALGO_BSW ? DPX_ALGO_LSW : params->algo == DPX_ALGO_BASW ? DPX_ALGO_ASW : DPX_ALGO_ANW; /* the band covers every cell: identical to the unbanded recurrence */
         } else if (params->band > 512) {
             delete b;
             return DPX_ERR_UNSUPPORTED; /* band kernel holds <= 8 cells per lane (band <= 512) */
@@ -1145,7 +1176,7 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
     b->kernelAlgo = kernelAlgo;
     const bool banded = is_banded(kernelAlgo);
     const bool bandedLinear = kernelAlgo == DPX_ALGO_BSW; /* (the packed-int16 band kernel exists for linear gaps only) */
-    const int bandPlanes = kernelAlgo == DPX_ALGO_BASW ? 3 : 1;
+    const int bandPlanes = is_banded_affine(kernelAlgo) ? 3 : 1;
 
     /* matrix placement + algorithmic bytes: int16 cells incl. borders, sequences, 16 B pair record, 12 B result */
     for (size_t i = 0; i < numPairs; i++) {
@@ -1669,6 +1700,7 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
  * looks like one operation (events recorded on `s` around it time all of it). */
 static hipError_t launch_main(dpx_batch *b, hipStream_t s) { /* the one-wave-per-pair kernel of the batch's algorithm */
     if (b->kernelAlgo == DPX_ALGO_BASW) return dpx_launch_basw_fill(b->args, b->R, b->store, b->ldsBytes, s);
+    if (b->kernelAlgo == DPX_ALGO_BANW) return dpx_launch_banw_fill(b->args, b->R, b->store, b->ldsBytes, s);
     return dpx_launch_fill(b->args, b->kernelAlgo, b->R, b->store, b->ldsBytes, s);
 }
 
@@ -1875,7 +1907,9 @@ int dpx_batch_matrix(dpx_batch *b, size_t pair, int which, int16_t *out) {
     size_t dOutCap = 0;
     if (b->lastStream && b->lastStream != b->stream) HIP_TRY(hipStreamSynchronize(b->lastStream));
     HIP_TRY(g_tbDevCache.take((void **)&dOut, total * sizeof(int16_t), &dOutCap)); /* row-major scratch */
-    hipError_t e = b->kernelAlgo == DPX_ALGO_BASW
+    hipError_t e = b->kernelAlgo == DPX_ALGO_BANW
+                       ? dpx_launch_banw_export(b->dMat, pd, which, b->prm.band, b->prm.gapOpen, b->prm.gapExtend, dOut, b->stream)
+                   : b->kernelAlgo == DPX_ALGO_BASW
                        ? dpx_launch_basw_export(b->dMat, pd, which, b->prm.band, dOut, b->stream)
                        : dpx_launch_export(b->dMat, pd, b->kernelAlgo, b->R, b->planes, which, b->prm.gapOpen, b->prm.gapExtend,
                                            b->prm.band, dOut, b->stream);
@@ -1935,6 +1969,7 @@ static int output_begin(dpx_batch *b, uint64_t firstNumber) {
         /* banded affine SW: as ASW -- one wave per pair up to 20 000 pairs (k_basw_traceback_wave, band-layout window loads for the three
          * planes), one lane per pair beyond that or under DPX_TB_WALK=0 / 1 (k_basw_traceback) */
         if (b->kernelAlgo == DPX_ALGO_BASW) HIP_TRY(dpx_launch_basw_traceback(b->args, (int)np, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream));
+        else if (b->kernelAlgo == DPX_ALGO_BANW) HIP_TRY(dpx_launch_banw_traceback(b->args, (int)np, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream)); /* (banded affine NW: the same choice) */
         else if (b->dirs) HIP_TRY(dpx_launch_traceback_dir(b->dirArgs, (int)np, b->kernelAlgo, b->R, b->dTbOff, b->dTb, b->dTbLen, b->stream));
         else HIP_TRY(dpx_launch_traceback(b->args, (int)np, b->kernelAlgo, b->R, b->planes, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream));
         b->tbLinesValid = true;
@@ -2091,8 +2126,8 @@ int dpx_batch_traceback(dpx_batch *b, size_t pair, char *refLine, char *relLine,
 
 int dpx_batch_describe(dpx_batch *b, char *buf, size_t cap) {
     if (!b || !buf || !cap) return DPX_ERR_INVALID;
-    static const char *names[] = {"LNW", "LSW", "ANW", "BSW", "ASW", "BASW", "ASG"};
-    const char *kernel = b->kernelAlgo == DPX_ALGO_BASW ? "k_basw_fill" : b->kernelAlgo == DPX_ALGO_BSW ? (b->packed ? "k_banded_fill_pk" : "k_banded_fill") : b->kernelAlgo == DPX_ALGO_ANW ? (b->lanePacked ? "k_affine_lanes" : "k_affine_fill")
+    static const char *names[] = {"LNW", "LSW", "ANW", "BSW", "ASW", "BASW", "ASG", "BANW"};
+    const char *kernel = b->kernelAlgo == DPX_ALGO_BANW ? "k_banw_fill" : b->kernelAlgo == DPX_ALGO_BASW ? "k_basw_fill" : b->kernelAlgo == DPX_ALGO_BSW ? (b->packed ? "k_banded_fill_pk" : "k_banded_fill") : b->kernelAlgo == DPX_ALGO_ANW ? (b->lanePacked ? "k_affine_lanes" : "k_affine_fill")
                          : b->kernelAlgo == DPX_ALGO_ASW ? (b->lanePacked ? "k_asw_lanes" : "k_asw_fill")
                          : b->kernelAlgo == DPX_ALGO_ASG ? (b->lanePacked ? "k_asg_lanes" : "k_asg_fill")
                          : b->packed ? "k_linear_fill_pk" : b->lanesPk ? "k_linear_lanes_pk" : b->lanePacked ? "k_linear_lanes" : b->split ? "k_linear_split" : "k_linear_fill";
@@ -2102,9 +2137,12 @@ int dpx_batch_describe(dpx_batch *b, char *buf, size_t cap) {
                        names[b->prm.algo], names[b->kernelAlgo], kernel, (b->packed || b->lanesPk) ? "int16" : "int32", b->R, b->store ? 1 : 0, b->nCouples, b->nLanePairs,
                        b->nWaves, b->nSingles, (int)b->pkArgs.rowTags, b->packed2 ? "packed2" : "bytes",
                        b->dirs ? b->dirArgs.wavesPerBlock : (b->packed || b->lanePacked) ? b->pkArgs.wavesPerBlock : b->split ? (unsigned)b->splitWaves : b->args.wavesPerBlock);
-    if (b->kernelAlgo == DPX_ALGO_BASW && len > 0 && (size_t)len < cap) /* which walk the batch's traceback takes */
+    if (is_banded_affine(b->kernelAlgo) && len > 0 && (size_t)len < cap) { /* which walk the batch's traceback takes */
+        const bool wave = knobs().tbWalk >= 0 ? knobs().tbWalk >= 2 : b->numPairs <= 20000;
         len += snprintf(buf + len, cap - (size_t)len, " traceback=%s",
-                        (knobs().tbWalk >= 0 ? knobs().tbWalk >= 2 : b->numPairs <= 20000) ? "k_basw_traceback_wave" : "k_basw_traceback");
+                        b->kernelAlgo == DPX_ALGO_BANW ? (wave ? "k_banw_traceback_wave" : "k_banw_traceback")
+                                                       : (wave ? "k_basw_traceback_wave" : "k_basw_traceback"));
+    }
     if (b->dirs && len > 0 && (size_t)len < cap) /* the code layout, and where the edge rows live */
         len += snprintf(buf + len, cap - (size_t)len, " matrix=dir4 dir_edges=%s dir_scratch_bytes=%zu", b->dirScratch ? "global" : "lds", b->dirScratch);
     if (b->dMat && len > 0 && (size_t)len < cap) { /* the matrix pool: how it was built, and the memset time of every candidate that was timed */

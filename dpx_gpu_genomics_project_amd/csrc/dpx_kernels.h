@@ -15,6 +15,7 @@
 #define DPX_K_ASW 4 /* affine-gap Smith-Waterman: the ANW kernels' Gotoh recurrence with LSW's zero floor and start cell */
 #define DPX_K_BASW 5 /* banded affine-gap Smith-Waterman: ASW's recurrence on BSW's band and anti-diagonal schedule (dpx_basw_kernels.hip) */
 #define DPX_K_ASG 6 /* affine-gap semi-global alignment: the ANW kernels under a zero row-0 border, ending on the first maximum of row m */
+#define DPX_K_BANW 7 /* banded affine-gap Needleman-Wunsch: ANW's recurrence and borders inside BSW's band, minus infinity outside (dpx_banw_kernels.hip) */
 
 /* one wave per pair; DPX_FILL_THREADS/64 independent waves share a workgroup (no barriers between them) */
 #ifndef DPX_FILL_THREADS
@@ -68,6 +69,13 @@ hipError_t dpx_launch_output(const dpx_pair_dev *pairs, const int32_t *score, co
 hipError_t dpx_launch_basw_fill(const dpx_fill_args &a, int C, bool store, size_t ldsBytes, hipStream_t stream);
 hipError_t dpx_launch_basw_export(const int16_t *mat, const dpx_pair_dev &pr, int plane, int band, int16_t *out, hipStream_t stream);
 hipError_t dpx_launch_basw_traceback(const dpx_fill_args &a, int numPairs, int walk, const uint64_t *tbOff, char *tb, int32_t *tbLen,
+                                     hipStream_t stream);
+/* banded affine NW (dpx_banw_kernels.hip): the same three entry points; the export also needs the gap weights (in-band border cells are
+ * not stored) */
+hipError_t dpx_launch_banw_fill(const dpx_fill_args &a, int C, bool store, size_t ldsBytes, hipStream_t stream);
+hipError_t dpx_launch_banw_export(const int16_t *mat, const dpx_pair_dev &pr, int plane, int band, int gapOpen, int gapExtend, int16_t *out,
+                                  hipStream_t stream);
+hipError_t dpx_launch_banw_traceback(const dpx_fill_args &a, int numPairs, int walk, const uint64_t *tbOff, char *tb, int32_t *tbLen,
                                      hipStream_t stream);
 hipError_t dpx_launch_unpack2(const uint32_t *packed, uint32_t alphabet, char *out, size_t numDwords, hipStream_t stream);
 hipError_t dpx_launch_prim_eval(const int32_t *op, const uint32_t *a, const uint32_t *b, const uint32_t *c, size_t count,

@@ -25,7 +25,7 @@ extern "C" {
 /* 1: round 1.  2: + dpx_batch_create_on, dpx_batch_fill_timed, dpx_batch_last_fill_usec, dpx_batch_output_begin/_end/_take,
  * dpx_text_free, DPX_TUNE_PLACEMENT (round 2).  3: + dpx_pool_reserve, dpx_text_reserve, dpx_batch_last_output_usec, dpx_pack2, dpx_batch_create_packed2; dpx_batch_describe reports the
  * matrix pool (round 3); + DPX_KEEP_DIRECTIONS, dpx_batch_directions (detect them by the exported symbol: the number stays 3); + DPX_ALGO_ASW
- * (detect it by creating a batch: an older library returns DPX_ERR_INVALID for algo 4); + DPX_ALGO_BASW (likewise: DPX_ERR_INVALID for algo 5); + DPX_ALGO_ASG (likewise: DPX_ERR_INVALID for algo 6).  Additions only: a caller built against an older version keeps working; dpx_abi_version() >= the version
+ * (detect it by creating a batch: an older library returns DPX_ERR_INVALID for algo 4); + DPX_ALGO_BASW (likewise: DPX_ERR_INVALID for algo 5); + DPX_ALGO_ASG (likewise: DPX_ERR_INVALID for algo 6); + DPX_ALGO_BANW (likewise: DPX_ERR_INVALID for algo 7).  Additions only: a caller built against an older version keeps working; dpx_abi_version() >= the version
  * a caller needs is the check. */
 #define DPX_ABI_VERSION 3
 
@@ -66,7 +66,7 @@ typedef enum dpx_algo {
                          band that does not cover the matrix is DPX_ERR_UNSUPPORTED.  gapOpen = 0 gives BSW's H matrix with linear gap
                          gapExtend.  Matrices and DPX_SCORE_ONLY; DPX_KEEP_DIRECTIONS is DPX_ERR_UNSUPPORTED, as for BSW.
                          Added without an ABI bump or a new symbol: a library that predates it returns DPX_ERR_INVALID for algo 5. */
-    DPX_ALGO_ASG = 6  /* affine-gap semi-global alignment ("fitting", "glocal", ends-free in the reference), no reference counterpart: the
+    DPX_ALGO_ASG = 6, /* affine-gap semi-global alignment ("fitting", "glocal", ends-free in the reference), no reference counterpart: the
                          whole query is aligned end to end against the stretch of the reference that fits it best; the reference before
                          and after that stretch costs nothing.  Same dpx_params fields as ANW; band is ignored.  Reference of length n
                          along columns j, query of length m along rows i.
@@ -93,6 +93,37 @@ typedef enum dpx_algo {
                          columns); packed2 input, dpx_align_batch, the output pipeline, dpx_batch_create_on and a caller's stream.
                          ASG(ref, qry).score == max over 0 <= a <= b <= n of ANW(ref[a:b], qry).score.
                          Added without an ABI bump or a new symbol: a library that predates it returns DPX_ERR_INVALID for algo 6. */
+    DPX_ALGO_BANW = 7 /* banded affine-gap Needleman-Wunsch (global alignment between two anchors), no reference counterpart.  BASW's
+                         dpx_params fields: match, mismatch, gapOpen o, gapExtend e, band B >= 1.  Reference of length n along columns
+                         j, query of length m along rows i.
+                         Band: a cell (i, j), 0 <= i <= m, 0 <= j <= n, is in the band when |i - j| <= B - 1 (BSW's rule; here it
+                         applies to border cells too).
+                         Borders: H[0][0] = 0; H[i][0] = o + i*e for 1 <= i <= B - 1; H[0][j] = o + j*e for 1 <= j <= B - 1 (ANW's
+                         borders); I and D are -infinity on every border.  Outside the band H = I = D = -infinity.
+                         Cells: for in-band cells with i, j >= 1, ANW's recurrence and tie order, unchanged: D = max(H_up + o + e,
+                         D_up + e), I = max(H_left + o + e, I_left + e), GAP_OPEN wins a tie; best = H_diag + s (MATCH or MISMATCH),
+                         D >= best takes it (QUERY_DELETION), then I >= best takes it (QUERY_INSERTION).  No zero floor; -infinity plus
+                         anything is -infinity.  It follows that every in-band H is finite (the diagonal neighbour of an in-band cell
+                         is in band), that I of a cell on the lower edge (i - j = B - 1) is -infinity and that D of a cell on the upper
+                         edge (j - i = B - 1) is -infinity.
+                         Score = H[m][n], end cell (m, n).  m = 0 gives o + n*e (0 when n = 0 as well), n = 0 gives o + m*e.
+                         Admission: a global path exists only when |m - n| <= B - 1.  A batch that holds a pair with |m - n| >= B is
+                         refused at create with DPX_ERR_UNSUPPORTED, and dpx_last_error() names the first such pair and the band it
+                         would need; nothing is widened.  The caller chooses B, as a mapper sets its band from the length difference.
+                         Covering band: B >= max(m, n) + 1 over the batch runs as ANW, with the same results (+1: at B = max(m, n) the
+                         border cell (m, 0) is outside the band and I[m][1] is -infinity).  Otherwise B <= 512; a wider band that
+                         does not cover is DPX_ERR_UNSUPPORTED, as for BASW.
+                         Walk: ANW's three-state walk from (m, n) in SCORING while i != 0 && j != 0: I >= max(D, mm) goes to
+                         INSERTION, else D >= mm to DELETION, else the diagonal; in a gap state GAP_OPEN applies when H + o + e >=
+                         (I or D) + e at the neighbour, and a neighbour that is a border cell opens the gap.  Then ANW's two tails:
+                         the remaining i as deletions, the remaining j as insertions.  The walk cannot leave the band.
+                         Text: ANW's block (header, then the reference, relation and query lines), whatever the sign of the score.
+                         dpx_batch_matrix: row-major (m+1) x (n+1); in-band H carries the borders above, I and D are 0 on in-band
+                         borders (as for ANW), every plane is 0 outside the band (as for BASW), and an in-band I or D that is
+                         -infinity exports as -32768; the range check keeps every finite value at or above -32767.
+                         Matrices and DPX_SCORE_ONLY; DPX_KEEP_DIRECTIONS is DPX_ERR_UNSUPPORTED, as for BSW and BASW.  packed2
+                         input, dpx_align_batch, the output pipeline, dpx_batch_create_on and a caller's stream as for BASW.
+                         Added without an ABI bump or a new symbol: a library that predates it returns DPX_ERR_INVALID for algo 7. */
 } dpx_algo;
 
 /* Identical in layout to the reference's `struct seqPair` (c++/parseInput.h:22-29): byte offsets into the
@@ -110,13 +141,13 @@ typedef struct dpx_params {
     int32_t algo;      /* dpx_algo */
     int32_t match;
     int32_t mismatch;
-    int32_t gapOpen;   /* linear gap for LNW/LSW/BSW; gap-open for ANW / ASW / BASW / ASG */
-    int32_t gapExtend; /* ANW / ASW / BASW / ASG only */
-    int32_t band;      /* BSW / BASW: cells with |i-j| <= band-1 are computed */
+    int32_t gapOpen;   /* linear gap for LNW/LSW/BSW; gap-open for ANW / ASW / BASW / ASG / BANW */
+    int32_t gapExtend; /* ANW / ASW / BASW / ASG / BANW only */
+    int32_t band;      /* BSW / BASW / BANW: cells with |i-j| <= band-1 are computed */
 } dpx_params;
 
 /* dpx_batch_create flags */
-#define DPX_KEEP_MATRICES 0x0u /* default: write the int16 score matrices (H; H,I,D for ANW / ASW / BASW / ASG) to HBM */
+#define DPX_KEEP_MATRICES 0x0u /* default: write the int16 score matrices (H; H,I,D for ANW / ASW / BASW / ASG / BANW) to HBM */
 #define DPX_SCORE_ONLY    0x1u /* no matrix writeback (not HBM-bound; never used for the roofline figure) */
 #define DPX_TIME_FILLS    0x2u /* bracket every dpx_batch_fill() with HIP events: dpx_batch_last_fill_usec() */
 #define DPX_TUNE_PLACEMENT 0x4u /* the batch will be filled many times: time its matrix pool (>= 1 GiB) with hipMemset and shop for a better
@@ -128,12 +159,12 @@ typedef struct dpx_params {
                                     padding per query row (about a quarter of an int16 H batch's bytes, a twelfth of ANW's H/I/D, from
                                     a few hundred rows on; short reads keep a larger fraction); scores may exceed int16 (bounds checked against 2^28) and references 65 000 columns.
                                     dpx_batch_matrix() returns DPX_ERR_NO_MATRIX, dpx_batch_directions() exports the codes.  With
-                                    DPX_SCORE_ONLY: DPX_ERR_INVALID; with BSW / BASW: DPX_ERR_UNSUPPORTED (banded directions are not implemented). */
+                                    DPX_SCORE_ONLY: DPX_ERR_INVALID; with BSW / BASW / BANW: DPX_ERR_UNSUPPORTED (banded directions are not implemented). */
 
 /* matrix selectors for dpx_batch_matrix / dpx_batch_directions */
 #define DPX_MAT_H 0 /* scoring matrix   (reference: memo / scoringMemo)            */
-#define DPX_MAT_I 1 /* ANW / ASW / BASW / ASG horizontal-gap matrix (queryInsertionMemo)  */
-#define DPX_MAT_D 2 /* ANW / ASW / BASW / ASG vertical-gap matrix   (queryDeletionMemo)   */
+#define DPX_MAT_I 1 /* the affine algorithms' horizontal-gap matrix (queryInsertionMemo) */
+#define DPX_MAT_D 2 /* the affine algorithms' vertical-gap matrix   (queryDeletionMemo)  */
 
 typedef struct dpx_batch dpx_batch; /* opaque, device-resident batch of pairs */
 
