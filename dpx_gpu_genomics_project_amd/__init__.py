@@ -12,6 +12,7 @@ from .capi import (  # noqa: F401
     ALGO_ASW,
     ALGO_BANW,
     ALGO_BASW,
+    ALGO_BAXT,
     ALGO_BSW,
     ALGO_LNW,
     ALGO_LSW,
@@ -39,7 +40,7 @@ from .capi import (  # noqa: F401
 from .synth import SynthBatch, make_batch, parse_pairs_file, write_pairs_file  # noqa: F401
 
 __all__ = [
-    "ALGO_ANW", "ALGO_ASG", "ALGO_ASW", "ALGO_BANW", "ALGO_BASW", "ALGO_BSW", "ALGO_LNW", "ALGO_LSW", "ALGO_NAMES", "MAT_D", "MAT_H", "MAT_I", "SCORE_ONLY", "TIME_FILLS", "TUNE_PLACEMENT",
+    "ALGO_ANW", "ALGO_ASG", "ALGO_ASW", "ALGO_BANW", "ALGO_BASW", "ALGO_BAXT", "ALGO_BSW", "ALGO_LNW", "ALGO_LSW", "ALGO_NAMES", "MAT_D", "MAT_H", "MAT_I", "SCORE_ONLY", "TIME_FILLS", "TUNE_PLACEMENT",
     "KEEP_MATRICES", "KEEP_DIRECTIONS", "Batch", "DpxError", "Params", "SeqPair", "device_count", "device_info", "init",
     "lib_path", "load", "pack2", "prim_eval", "SynthBatch", "make_batch", "parse_pairs_file", "write_pairs_file",
 ]

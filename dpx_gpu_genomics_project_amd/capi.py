@@ -12,8 +12,9 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 ALGO_LNW, ALGO_LSW, ALGO_ANW, ALGO_BSW, ALGO_ASW, ALGO_BASW, ALGO_ASG, ALGO_BANW = 0, 1, 2, 3, 4, 5, 6, 7
+ALGO_BAXT = 10  # (8 and 9 are unassigned)
 ALGO_NAMES = {ALGO_LNW: "LNW", ALGO_LSW: "LSW", ALGO_ANW: "ANW", ALGO_BSW: "BSW", ALGO_ASW: "ASW", ALGO_BASW: "BASW", ALGO_ASG: "ASG",
-              ALGO_BANW: "BANW"}
+              ALGO_BANW: "BANW", ALGO_BAXT: "BAXT"}
 KEEP_MATRICES, SCORE_ONLY, TIME_FILLS, TUNE_PLACEMENT, KEEP_DIRECTIONS = 0x0, 0x1, 0x2, 0x4, 0x8
 MAT_H, MAT_I, MAT_D = 0, 1, 2
 

@@ -703,18 +703,24 @@ int dpx_shutdown(void) {
 
 /* ------------------------------------------------------------------------------------------ batch */
 
-/* the three-plane Gotoh algorithms: ANW (global), ASW (local), BASW (local, banded), ASG (semi-global) and BANW (global, banded) */
+/* the three-plane Gotoh algorithms: ANW (global), ASW (local), BASW (local, banded), ASG (semi-global), BANW (global, banded) and BAXT
+ * (extension, banded) */
 static bool is_affine(int algo) {
-    return algo == DPX_ALGO_ANW || algo == DPX_ALGO_ASW || algo == DPX_ALGO_BASW || algo == DPX_ALGO_ASG || algo == DPX_ALGO_BANW;
+    return algo == DPX_ALGO_ANW || algo == DPX_ALGO_ASW || algo == DPX_ALGO_BASW || algo == DPX_ALGO_ASG || algo == DPX_ALGO_BANW ||
+           algo == DPX_ALGO_BAXT;
 }
 /* the algorithms with a band parameter (and, unless the band covers the matrix, the anti-diagonal band kernels and layout) */
-static bool is_banded(int algo) { return algo == DPX_ALGO_BSW || algo == DPX_ALGO_BASW || algo == DPX_ALGO_BANW; }
-/* ... of which the three-plane ones (dpx_basw_kernels.hip, dpx_banw_kernels.hip: chunks of three planes, no packed-int16 variant) */
-static bool is_banded_affine(int algo) { return algo == DPX_ALGO_BASW || algo == DPX_ALGO_BANW; }
+static bool is_banded(int algo) { return algo == DPX_ALGO_BSW || algo == DPX_ALGO_BASW || algo == DPX_ALGO_BANW || algo == DPX_ALGO_BAXT; }
+/* ... of which the three-plane ones (dpx_basw_kernels.hip, dpx_banw_kernels.hip, dpx_baxt_kernels.hip: chunks of three planes, no
+ * packed-int16 variant) */
+static bool is_banded_affine(int algo) { return algo == DPX_ALGO_BASW || algo == DPX_ALGO_BANW || algo == DPX_ALGO_BAXT; }
+/* ... of which the ones whose stored planes follow BANW's rules (in-band borders carry H, edge I / D and everything without storage is
+ * minus infinity): k_banw_export and the k_banw_traceback walks read them */
+static bool is_banw_layout(int algo) { return algo == DPX_ALGO_BANW || algo == DPX_ALGO_BAXT; }
 
 static int validate_params(const dpx_params *p) {
     if (!p) return DPX_ERR_INVALID;
-    if (p->algo < DPX_ALGO_LNW || p->algo > DPX_ALGO_BANW) return DPX_ERR_INVALID;
+    if ((p->algo < DPX_ALGO_LNW || p->algo > DPX_ALGO_BANW) && p->algo != DPX_ALGO_BAXT) return DPX_ERR_INVALID; /* (8 and 9 are unassigned) */
     if (is_banded(p->algo) && p->band < 1) return DPX_ERR_INVALID;
     /* the int32 kernels add a weight to a cell value (|H| <= 32767 after fits_int16) and to the affine kernels' virtual
      * -2^29 borders: weights beyond +-2^20 could wrap those sums (and no int16 matrix could hold what they produce) */
@@ -748,7 +754,7 @@ static bool fits_int16(const dpx_params &p, long long m, long long n) {
         const long long lo = neg(p.gapOpen) * (m + n), hi = diag + pos(p.gapOpen) * (m + n);
         return lo >= -lim && hi <= lim;
     }
-    if (p.algo == DPX_ALGO_BANW) {
+    if (p.algo == DPX_ALGO_BANW || p.algo == DPX_ALGO_BAXT) {
         /* hiH is ANW's: a band only removes paths, and hiH sums the positive contributions any path can collect.
          * loH: ANW's "every cell can fall back on the all-gap path" does not hold inside a band (that path leaves it).  A path that
          * does stay in the band reaches every in-band cell (i, j): the diagonal from (0, 0) to (k, k), k = min(i, j), whose cells have
@@ -759,10 +765,16 @@ static bool fits_int16(const dpx_params &p, long long m, long long n) {
          * the same path with one diagonal step fewer and s in its place.  A finite I (D) is >= its open term H_left + o + e (H_up + o + e)
          * >= loH + (o + e), and <= hiH + pos(o) + pos(e) * max(m, n) as for ANW.  So every finite stored value is >= lo >= -32767, and
          * -32768 is free to stand for minus infinity in dpx_batch_matrix and in the walks' windows.  No m + n <= 65000: the kernel keeps
-         * no step key. */
+         * no step key.
+         * BAXT: its cells are BANW's recurrence on the same band without the admission rule, and nothing above uses |m - n| <= B - 1:
+         * the path (diagonal to (k, k), then one gap of |i - j| <= B - 1 steps) reaches every in-band cell of any m x n matrix and stays
+         * in the band, and hiH holds for every path.  So the same bounds hold for every in-band H, I and D, and the score, a maximum of
+         * H values and the 0 of (0, 0), lies in [0, hiH].  k_baxt_fill keeps a signed (H << 16 | 0xFFFF - step) key per slot: H inside
+         * int16 is this check, and the step index m + n must fit 16 bits (the same 65000 as BASW's keys). */
         const long long o = p.gapOpen, e = p.gapExtend, g = std::min<long long>(std::max<long long>(p.band - 1, 0), std::max(m, n));
         const long long loH = neg(std::min<long long>(p.match, p.mismatch)) * std::min(m, n) + neg(o) + neg(e) * g;
         const long long hiH = diag + (pos(o) + pos(e)) * (m + n);
+        if (p.algo == DPX_ALGO_BAXT && m + n > 65000) return false;
         return loH + neg(o + e) >= -lim && hiH + pos(o) + pos(e) * std::max(m, n) <= lim;
     }
     /* ANW, and ASG: every ASG cell H[i][j] is the best score of an alignment path between a reference substring ref[a:j] and the query
@@ -1164,7 +1176,9 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
     int kernelAlgo = params->algo;
     if (is_banded(params->algo)) {
         /* (BANW: + 1, its band applies to the border cells too -- at B = max(m, n) the border cell (m, 0) or (0, n) is outside it) */
-        if ((long long)params->band >= (long long)std::max(b->maxM, b->maxN) + (params->algo == DPX_ALGO_BANW ? 1 : 0)) {
+        /* (BAXT: no covering fall-back -- no unbanded extension kernel exists; a band <= 512 that covers the matrix runs k_baxt_fill) */
+        if (params->algo != DPX_ALGO_BAXT &&
+            (long long)params->band >= (long long)std::max(b->maxM, b->maxN) + (params->algo == DPX_ALGO_BANW ? 1 : 0)) {
             kernelAlgo = params->algo == DPX_ALGO_BSW ? DPX_ALGO_LSW : params->algo == DPX_ALGO_BASW ? DPX_ALGO_ASW : DPX_ALGO_ANW; /* the band covers every cell: identical to the unbanded recurrence */
         } else if (params->band > 512) {
             delete b;
@@ -1701,6 +1715,7 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
 static hipError_t launch_main(dpx_batch *b, hipStream_t s) { /* the one-wave-per-pair kernel of the batch's algorithm */
     if (b->kernelAlgo == DPX_ALGO_BASW) return dpx_launch_basw_fill(b->args, b->R, b->store, b->ldsBytes, s);
     if (b->kernelAlgo == DPX_ALGO_BANW) return dpx_launch_banw_fill(b->args, b->R, b->store, b->ldsBytes, s);
+    if (b->kernelAlgo == DPX_ALGO_BAXT) return dpx_launch_baxt_fill(b->args, b->R, b->store, b->ldsBytes, s);
     return dpx_launch_fill(b->args, b->kernelAlgo, b->R, b->store, b->ldsBytes, s);
 }
 
@@ -1907,7 +1922,7 @@ int dpx_batch_matrix(dpx_batch *b, size_t pair, int which, int16_t *out) {
     size_t dOutCap = 0;
     if (b->lastStream && b->lastStream != b->stream) HIP_TRY(hipStreamSynchronize(b->lastStream));
     HIP_TRY(g_tbDevCache.take((void **)&dOut, total * sizeof(int16_t), &dOutCap)); /* row-major scratch */
-    hipError_t e = b->kernelAlgo == DPX_ALGO_BANW
+    hipError_t e = is_banw_layout(b->kernelAlgo) /* (BAXT stores what BANW stores) */
                        ? dpx_launch_banw_export(b->dMat, pd, which, b->prm.band, b->prm.gapOpen, b->prm.gapExtend, dOut, b->stream)
                    : b->kernelAlgo == DPX_ALGO_BASW
                        ? dpx_launch_basw_export(b->dMat, pd, which, b->prm.band, dOut, b->stream)
@@ -1969,7 +1984,7 @@ static int output_begin(dpx_batch *b, uint64_t firstNumber) {
         /* banded affine SW: as ASW -- one wave per pair up to 20 000 pairs (k_basw_traceback_wave, band-layout window loads for the three
          * planes), one lane per pair beyond that or under DPX_TB_WALK=0 / 1 (k_basw_traceback) */
         if (b->kernelAlgo == DPX_ALGO_BASW) HIP_TRY(dpx_launch_basw_traceback(b->args, (int)np, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream));
-        else if (b->kernelAlgo == DPX_ALGO_BANW) HIP_TRY(dpx_launch_banw_traceback(b->args, (int)np, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream)); /* (banded affine NW: the same choice) */
+        else if (is_banw_layout(b->kernelAlgo)) HIP_TRY(dpx_launch_banw_traceback(b->args, (int)np, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream)); /* (banded affine NW, and the extension, which walks from its end cell to the anchor: the same choice) */
         else if (b->dirs) HIP_TRY(dpx_launch_traceback_dir(b->dirArgs, (int)np, b->kernelAlgo, b->R, b->dTbOff, b->dTb, b->dTbLen, b->stream));
         else HIP_TRY(dpx_launch_traceback(b->args, (int)np, b->kernelAlgo, b->R, b->planes, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream));
         b->tbLinesValid = true;
@@ -2126,21 +2141,24 @@ int dpx_batch_traceback(dpx_batch *b, size_t pair, char *refLine, char *relLine,
 
 int dpx_batch_describe(dpx_batch *b, char *buf, size_t cap) {
     if (!b || !buf || !cap) return DPX_ERR_INVALID;
-    static const char *names[] = {"LNW", "LSW", "ANW", "BSW", "ASW", "BASW", "ASG", "BANW"};
-    const char *kernel = b->kernelAlgo == DPX_ALGO_BANW ? "k_banw_fill" : b->kernelAlgo == DPX_ALGO_BASW ? "k_basw_fill" : b->kernelAlgo == DPX_ALGO_BSW ? (b->packed ? "k_banded_fill_pk" : "k_banded_fill") : b->kernelAlgo == DPX_ALGO_ANW ? (b->lanePacked ? "k_affine_lanes" : "k_affine_fill")
+    auto name = [](int algo) -> const char * { /* (sparse: 8 and 9 are unassigned) */
+        static const char *names[] = {"LNW", "LSW", "ANW", "BSW", "ASW", "BASW", "ASG", "BANW"};
+        return algo == DPX_ALGO_BAXT ? "BAXT" : (algo >= 0 && algo <= DPX_ALGO_BANW) ? names[algo] : "?";
+    };
+    const char *kernel = b->kernelAlgo == DPX_ALGO_BAXT ? "k_baxt_fill" : b->kernelAlgo == DPX_ALGO_BANW ? "k_banw_fill" : b->kernelAlgo == DPX_ALGO_BASW ? "k_basw_fill" : b->kernelAlgo == DPX_ALGO_BSW ? (b->packed ? "k_banded_fill_pk" : "k_banded_fill") : b->kernelAlgo == DPX_ALGO_ANW ? (b->lanePacked ? "k_affine_lanes" : "k_affine_fill")
                          : b->kernelAlgo == DPX_ALGO_ASW ? (b->lanePacked ? "k_asw_lanes" : "k_asw_fill")
                          : b->kernelAlgo == DPX_ALGO_ASG ? (b->lanePacked ? "k_asg_lanes" : "k_asg_fill")
                          : b->packed ? "k_linear_fill_pk" : b->lanesPk ? "k_linear_lanes_pk" : b->lanePacked ? "k_linear_lanes" : b->split ? "k_linear_split" : "k_linear_fill";
     if (b->dirs) kernel = b->kernelAlgo == DPX_ALGO_ANW ? "k_affine_dir" : b->kernelAlgo == DPX_ALGO_ASW ? "k_asw_dir" : b->kernelAlgo == DPX_ALGO_ASG ? "k_asg_dir" : "k_linear_dir";
     /* dtype = the arithmetic type of the kernel that fills (most of) the batch */
     int len = snprintf(buf, cap, "algo=%s kernel_algo=%s kernel=%s dtype=%s rows_per_lane=%d store=%d couples=%zu lane_pairs=%zu waves=%zu singles=%zu row_tags=%d seq_input=%s waves_per_workgroup=%u",
-                       names[b->prm.algo], names[b->kernelAlgo], kernel, (b->packed || b->lanesPk) ? "int16" : "int32", b->R, b->store ? 1 : 0, b->nCouples, b->nLanePairs,
+                       name(b->prm.algo), name(b->kernelAlgo), kernel, (b->packed || b->lanesPk) ? "int16" : "int32", b->R, b->store ? 1 : 0, b->nCouples, b->nLanePairs,
                        b->nWaves, b->nSingles, (int)b->pkArgs.rowTags, b->packed2 ? "packed2" : "bytes",
                        b->dirs ? b->dirArgs.wavesPerBlock : (b->packed || b->lanePacked) ? b->pkArgs.wavesPerBlock : b->split ? (unsigned)b->splitWaves : b->args.wavesPerBlock);
     if (is_banded_affine(b->kernelAlgo) && len > 0 && (size_t)len < cap) { /* which walk the batch's traceback takes */
         const bool wave = knobs().tbWalk >= 0 ? knobs().tbWalk >= 2 : b->numPairs <= 20000;
         len += snprintf(buf + len, cap - (size_t)len, " traceback=%s",
-                        b->kernelAlgo == DPX_ALGO_BANW ? (wave ? "k_banw_traceback_wave" : "k_banw_traceback")
+                        is_banw_layout(b->kernelAlgo) ? (wave ? "k_banw_traceback_wave" : "k_banw_traceback")
                                                        : (wave ? "k_basw_traceback_wave" : "k_basw_traceback"));
     }
     if (b->dirs && len > 0 && (size_t)len < cap) /* the code layout, and where the edge rows live */

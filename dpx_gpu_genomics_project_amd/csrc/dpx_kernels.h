@@ -16,6 +16,7 @@
 #define DPX_K_BASW 5 /* banded affine-gap Smith-Waterman: ASW's recurrence on BSW's band and anti-diagonal schedule (dpx_basw_kernels.hip) */
 #define DPX_K_ASG 6 /* affine-gap semi-global alignment: the ANW kernels under a zero row-0 border, ending on the first maximum of row m */
 #define DPX_K_BANW 7 /* banded affine-gap Needleman-Wunsch: ANW's recurrence and borders inside BSW's band, minus infinity outside (dpx_banw_kernels.hip) */
+#define DPX_K_BAXT 10 /* banded affine-gap extension: BANW's cells, ending on the first maximum of H over the band (dpx_baxt_kernels.hip; 8 and 9 are unassigned) */
 
 /* one wave per pair; DPX_FILL_THREADS/64 independent waves share a workgroup (no barriers between them) */
 #ifndef DPX_FILL_THREADS
@@ -77,6 +78,9 @@ hipError_t dpx_launch_banw_export(const int16_t *mat, const dpx_pair_dev &pr, in
                                   hipStream_t stream);
 hipError_t dpx_launch_banw_traceback(const dpx_fill_args &a, int numPairs, int walk, const uint64_t *tbOff, char *tb, int32_t *tbLen,
                                      hipStream_t stream);
+/* banded affine extension (dpx_baxt_kernels.hip): the fill only -- the stored layout, the edge rule and the border rule are BANW's, so
+ * dpx_launch_banw_export and dpx_launch_banw_traceback serve it (both walks start from endRow / endCol) */
+hipError_t dpx_launch_baxt_fill(const dpx_fill_args &a, int C, bool store, size_t ldsBytes, hipStream_t stream);
 hipError_t dpx_launch_unpack2(const uint32_t *packed, uint32_t alphabet, char *out, size_t numDwords, hipStream_t stream);
 hipError_t dpx_launch_prim_eval(const int32_t *op, const uint32_t *a, const uint32_t *b, const uint32_t *c, size_t count,
                                 uint32_t *res, uint32_t *pred, hipStream_t stream);

@@ -76,7 +76,7 @@ void runGroup(const std::vector<Request *> &grp, bool wantMatrices, int device) 
             const size_t cells = (grp[k]->reference->size() + 1) * (grp[k]->query->size() + 1);
             out.H.resize(cells);
             if ((rc = dpx_batch_matrix(b, k, DPX_MAT_H, out.H.data())) != DPX_OK) fail("dpx_batch_matrix(H)", rc);
-            if (first.algo == DPX_ALGO_ANW || first.algo == DPX_ALGO_ASW || first.algo == DPX_ALGO_BASW || first.algo == DPX_ALGO_ASG || first.algo == DPX_ALGO_BANW) {
+            if (first.algo == DPX_ALGO_ANW || first.algo == DPX_ALGO_ASW || first.algo == DPX_ALGO_BASW || first.algo == DPX_ALGO_ASG || first.algo == DPX_ALGO_BANW || first.algo == DPX_ALGO_BAXT) {
                 out.I.resize(cells);
                 out.D.resize(cells);
                 if ((rc = dpx_batch_matrix(b, k, DPX_MAT_I, out.I.data())) != DPX_OK) fail("dpx_batch_matrix(I)", rc);

@@ -14,7 +14,7 @@ struct DpxPairResult {
     std::vector<short> H, I, D;             // (m+1) x (n+1) row-major, only when matrices were requested
 };
 
-// algo: dpx_algo (0 LNW, 1 LSW, 2 ANW, 3 BSW, 4 ASW, 5 BASW, 6 ASG, 7 BANW)
+// algo: dpx_algo (0 LNW, 1 LSW, 2 ANW, 3 BSW, 4 ASW, 5 BASW, 6 ASG, 7 BANW, 10 BAXT)
 void dpxAlignPair(int algo, const std::string &reference, const std::string &query, int match, int mismatch, int gapOpen,
                   int gapExtend, int band, bool wantMatrices, DpxPairResult &out);
 

@@ -4,7 +4,7 @@
 // block: the algorithm is a run-time flag instead of a #define (main.cpp:22-24), pairs past the last full 400 are
 // not dropped (main.cpp:169 floors twice) and the per-thread loop is clamped to numPairs (main.cpp:61 is not).
 //
-//   dpx_class_main -pairs <file> -match M -mismatch X -open O [-extend E] [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW] [-band B]
+//   dpx_class_main -pairs <file> -match M -mismatch X -open O [-extend E] [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band B]
 #include <pthread.h>
 
 #include <cassert>
@@ -14,6 +14,7 @@
 #include "AffineNeedlemanWunsch.h"
 #include "AffineSmithWaterman.h"
 #include "AffineSemiGlobal.h"
+#include "BandedAffineExtension.h"
 #include "BandedAffineNeedlemanWunsch.h"
 #include "BandedAffineSmithWaterman.h"
 #include "BandedSmithWaterman.h"
@@ -27,7 +28,7 @@
 #define THREADS_PER_BATCH 20
 
 namespace {
-enum Algo { LSW, LNW, ANW, BSW, ASW, BASW, ASG, BANW };
+enum Algo { LSW, LNW, ANW, BSW, ASW, BASW, ASG, BANW, BAXT };
 
 struct thread_arg {
     Algo algo;
@@ -49,6 +50,7 @@ void *threadCompute(void *tmp) {
         case ASW: { AffineSmithWaterman x(ref, qry, i, a->matchWeight, a->mismatchWeight, a->gapOpenWeight, a->gapExtendWeight); x.align(); break; }
         case ASG: { AffineSemiGlobal x(ref, qry, i, a->matchWeight, a->mismatchWeight, a->gapOpenWeight, a->gapExtendWeight); x.align(); break; }
         case BANW: { BandedAffineNeedlemanWunsch x(ref, qry, i, a->matchWeight, a->mismatchWeight, a->gapOpenWeight, a->gapExtendWeight, a->band); x.align(); break; }
+        case BAXT: { BandedAffineExtension x(ref, qry, i, a->matchWeight, a->mismatchWeight, a->gapOpenWeight, a->gapExtendWeight, a->band); x.align(); break; }
         case BASW: { BandedAffineSmithWaterman x(ref, qry, i, a->matchWeight, a->mismatchWeight, a->gapOpenWeight, a->gapExtendWeight, a->band); x.align(); break; }
         case BSW: { BandedSmithWaterman x(ref, qry, a->matchWeight, a->mismatchWeight, a->gapOpenWeight, i, a->band); x.align(); break; }
         }
@@ -60,7 +62,7 @@ void *threadCompute(void *tmp) {
 int main(int argc, char *argv[]) {
     if (argc < 3) {
         fprintf(stderr, "usage: dpx_class_main -pairs <InSeqFile> -match <matchWeight> -mismatch <mismatchWeight> -open <gapWeight> "
-                        "[-extend <gapExtend>] [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW] [-band <B>]\n");
+                        "[-extend <gapExtend>] [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band <B>]\n");
         exit(EXIT_FAILURE);
     }
     const char *pairFileName = nullptr;
@@ -76,7 +78,7 @@ int main(int argc, char *argv[]) {
         else if (!strcmp(f, "-open") || !strcmp(f, "-gap")) proto.gapOpenWeight = atoi(v);
         else if (!strcmp(f, "-extend")) proto.gapExtendWeight = atoi(v);
         else if (!strcmp(f, "-band")) proto.band = atoi(v);
-        else if (!strcmp(f, "-algo")) proto.algo = !strcmp(v, "LNW") ? LNW : !strcmp(v, "ANW") ? ANW : !strcmp(v, "BSW") ? BSW : !strcmp(v, "ASW") ? ASW : !strcmp(v, "BASW") ? BASW : !strcmp(v, "ASG") ? ASG : !strcmp(v, "BANW") ? BANW : LSW;
+        else if (!strcmp(f, "-algo")) proto.algo = !strcmp(v, "LNW") ? LNW : !strcmp(v, "ANW") ? ANW : !strcmp(v, "BSW") ? BSW : !strcmp(v, "ASW") ? ASW : !strcmp(v, "BASW") ? BASW : !strcmp(v, "ASG") ? ASG : !strcmp(v, "BANW") ? BANW : !strcmp(v, "BAXT") ? BAXT : LSW;
     }
     if (!pairFileName) { fprintf(stderr, "need -pairs <file>\n"); exit(EXIT_FAILURE); }
 

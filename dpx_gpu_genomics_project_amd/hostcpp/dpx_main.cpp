@@ -8,7 +8,7 @@
 // stdout keeps the reference's lines so logs stay diff-able.
 //
 //   dpx_main -pairs <file> [-match 3] [-mismatch -1] [-open -2 | -gap -2] [-extend -1]
-//            [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW] [-band 128] [-batch N | -pool-gb 4] [-inflight K] [-tune 0|1] [-device 0] [-noprint] [-pack2] [-directions] [-producer P] [-rank r -world w]
+//            [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band 128] [-batch N | -pool-gb 4] [-inflight K] [-tune 0|1] [-device 0] [-noprint] [-pack2] [-directions] [-producer P] [-rank r -world w]
 //
 // Batch size: by default from a matrix-pool BUDGET (-pool-gb, 4 GiB): as many pairs as fit the budget, at most 20000 (the
 // reference sizes its buffers once for BATCH_SIZE = 10000 reads of 150 bases, cuda/LNW/LinearNeedlemanWunschV9.cu:26-46,
@@ -56,7 +56,7 @@ struct InFlight { // one batch between dpx_batch_create and dpx_batch_destroy
 int main(int argc, char *argv[]) {
     if (argc < 3) {
         fprintf(stderr, "usage: dpx_main -pairs <InSeqFile> -match <matchWeight> -mismatch <mismatchWeight> -open <gapWeight> "
-                        "[-extend <gapExtend>] [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW] [-band <B>] [-batch <N>] [-device <D>] [-noprint]\n");
+                        "[-extend <gapExtend>] [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band <B>] [-batch <N>] [-device <D>] [-noprint]\n");
         exit(EXIT_FAILURE);
     }
     const char *pairFileName = nullptr;
@@ -99,7 +99,7 @@ int main(int argc, char *argv[]) {
     if (world < 1 || rank < 0 || rank >= world) { fprintf(stderr, "bad -rank/-world\n"); exit(EXIT_FAILURE); }
     if (inflight < 1 || inflight > 8) { fprintf(stderr, "bad -inflight (1..8)\n"); exit(EXIT_FAILURE); }
     const int algo = algoName == "LNW" ? DPX_ALGO_LNW : algoName == "LSW" ? DPX_ALGO_LSW : algoName == "ANW" ? DPX_ALGO_ANW
-                     : algoName == "BSW" ? DPX_ALGO_BSW : algoName == "ASW" ? DPX_ALGO_ASW : algoName == "BASW" ? DPX_ALGO_BASW : algoName == "ASG" ? DPX_ALGO_ASG : algoName == "BANW" ? DPX_ALGO_BANW : -1;
+                     : algoName == "BSW" ? DPX_ALGO_BSW : algoName == "ASW" ? DPX_ALGO_ASW : algoName == "BASW" ? DPX_ALGO_BASW : algoName == "ASG" ? DPX_ALGO_ASG : algoName == "BANW" ? DPX_ALGO_BANW : algoName == "BAXT" ? DPX_ALGO_BAXT : -1;
     if (algo < 0) { fprintf(stderr, "unknown -algo %s\n", algoName.c_str()); exit(EXIT_FAILURE); }
 
     printf("[Device Details]\n");
@@ -118,8 +118,8 @@ int main(int argc, char *argv[]) {
     // (the budget is per score plane: the three planes of the affine algorithm get three times the bytes, so that a batch holds
     // as many pairs -- and fills the chip as well -- as a linear-gap batch of the same shapes)
     // (-directions: one 4-bit code per cell whatever the algorithm, so the budget stays per batch and holds 4x -- ANW 12x -- the pairs)
-    const bool threePlanes = algo == DPX_ALGO_ANW || algo == DPX_ALGO_ASW || algo == DPX_ALGO_BASW || algo == DPX_ALGO_ASG || algo == DPX_ALGO_BANW; // H, I, D
-    const bool bandAlgo = algo == DPX_ALGO_BSW || algo == DPX_ALGO_BASW || algo == DPX_ALGO_BANW;                            // band layout: 2 * band + 8 columns per row
+    const bool threePlanes = algo == DPX_ALGO_ANW || algo == DPX_ALGO_ASW || algo == DPX_ALGO_BASW || algo == DPX_ALGO_ASG || algo == DPX_ALGO_BANW || algo == DPX_ALGO_BAXT; // H, I, D
+    const bool bandAlgo = algo == DPX_ALGO_BSW || algo == DPX_ALGO_BASW || algo == DPX_ALGO_BANW || algo == DPX_ALGO_BAXT; // band layout: 2 * band + 8 columns per row
     const size_t poolBudget = (size_t)(poolGb * (double)(1ull << 30)) * (threePlanes && !directions ? 3 : 1);
     std::thread reserve;
     // (and pinned text buffers: one being printed, one per batch in flight, two spare)

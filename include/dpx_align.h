@@ -25,7 +25,7 @@ extern "C" {
 /* 1: round 1.  2: + dpx_batch_create_on, dpx_batch_fill_timed, dpx_batch_last_fill_usec, dpx_batch_output_begin/_end/_take,
  * dpx_text_free, DPX_TUNE_PLACEMENT (round 2).  3: + dpx_pool_reserve, dpx_text_reserve, dpx_batch_last_output_usec, dpx_pack2, dpx_batch_create_packed2; dpx_batch_describe reports the
  * matrix pool (round 3); + DPX_KEEP_DIRECTIONS, dpx_batch_directions (detect them by the exported symbol: the number stays 3); + DPX_ALGO_ASW
- * (detect it by creating a batch: an older library returns DPX_ERR_INVALID for algo 4); + DPX_ALGO_BASW (likewise: DPX_ERR_INVALID for algo 5); + DPX_ALGO_ASG (likewise: DPX_ERR_INVALID for algo 6); + DPX_ALGO_BANW (likewise: DPX_ERR_INVALID for algo 7).  Additions only: a caller built against an older version keeps working; dpx_abi_version() >= the version
+ * (detect it by creating a batch: an older library returns DPX_ERR_INVALID for algo 4); + DPX_ALGO_BASW (likewise: DPX_ERR_INVALID for algo 5); + DPX_ALGO_ASG (likewise: DPX_ERR_INVALID for algo 6); + DPX_ALGO_BANW (likewise: DPX_ERR_INVALID for algo 7); + DPX_ALGO_BAXT (likewise: DPX_ERR_INVALID for algo 10).  Additions only: a caller built against an older version keeps working; dpx_abi_version() >= the version
  * a caller needs is the check. */
 #define DPX_ABI_VERSION 3
 
@@ -93,7 +93,7 @@ typedef enum dpx_algo {
                          columns); packed2 input, dpx_align_batch, the output pipeline, dpx_batch_create_on and a caller's stream.
                          ASG(ref, qry).score == max over 0 <= a <= b <= n of ANW(ref[a:b], qry).score.
                          Added without an ABI bump or a new symbol: a library that predates it returns DPX_ERR_INVALID for algo 6. */
-    DPX_ALGO_BANW = 7 /* banded affine-gap Needleman-Wunsch (global alignment between two anchors), no reference counterpart.  BASW's
+    DPX_ALGO_BANW = 7, /* banded affine-gap Needleman-Wunsch (global alignment between two anchors), no reference counterpart.  BASW's
                          dpx_params fields: match, mismatch, gapOpen o, gapExtend e, band B >= 1.  Reference of length n along columns
                          j, query of length m along rows i.
                          Band: a cell (i, j), 0 <= i <= m, 0 <= j <= n, is in the band when |i - j| <= B - 1 (BSW's rule; here it
@@ -124,6 +124,37 @@ typedef enum dpx_algo {
                          Matrices and DPX_SCORE_ONLY; DPX_KEEP_DIRECTIONS is DPX_ERR_UNSUPPORTED, as for BSW and BASW.  packed2
                          input, dpx_align_batch, the output pipeline, dpx_batch_create_on and a caller's stream as for BASW.
                          Added without an ABI bump or a new symbol: a library that predates it returns DPX_ERR_INVALID for algo 7. */
+    /* 8 and 9 are unassigned: DPX_ERR_INVALID */
+    DPX_ALGO_BAXT = 10 /* banded affine-gap extension alignment (what a read mapper runs past its first and last anchor; ksw2's extz,
+                         BWA-MEM's extension), no reference counterpart: anchored at (0, 0), inside a band, ending wherever the score
+                         peaks.  BANW's dpx_params fields, band B >= 1.  Reference of length n along columns j, query of length m
+                         along rows i.
+                         Band and borders: exactly BANW's.  A cell (i, j), 0 <= i <= m, 0 <= j <= n, is in the band when
+                         |i - j| <= B - 1; H[0][0] = 0; in-band border cells carry o + k*e; I and D are -infinity on the borders;
+                         everything outside the band is -infinity.
+                         Cells: BANW's recurrence and tie order, unchanged, no zero floor.  Where BANW admits a pair, BAXT's H, I and D
+                         equal BANW's cell for cell.
+                         Score = the maximum of H over all in-band cells, border cells and (0, 0) included; it is therefore >= 0.
+                         End cell = the first cell in row-major order that holds the maximum (the LSW / BASW rule with row 0 and
+                         column 0 taking part).  A score of 0 always ends at (0, 0).
+                         BAXT(ref, qry, B).score == max over in-band (i, j) of BANW(ref[:j], qry[:i], B).score.
+                         Admission: none.  Any m and n, zero included; when |m - n| >= B the cell (m, n) is simply never reached.
+                         Walk: BANW's three-state walk from the end cell in SCORING while i != 0 && j != 0, then ANW's two tails; the
+                         path always reaches the anchor (0, 0).  The ungapped characters of the reference line are ref[:endCol],
+                         those of the query line qry[:endRow].  The walk cannot leave the band.
+                         Text: ANW's block (header, then three lines); the lines are empty when the end cell is (0, 0).
+                         dpx_batch_matrix: as for BANW (H carries the in-band borders, I and D are 0 there, every plane is 0 outside
+                         the band, an in-band -infinity exports as -32768).
+                         Band limit: B <= 512; a wider band is DPX_ERR_UNSUPPORTED even when it would cover the matrix -- no unbanded
+                         extension kernel exists to fall back on.  A band up to 512 that covers the matrix runs the banded kernel like
+                         any other band.
+                         Range: BANW's int16 bounds, and m + n <= 65000 (the kernel packs the step index into 16 bits, as BASW's);
+                         otherwise DPX_ERR_RANGE.
+                         Matrices and DPX_SCORE_ONLY; DPX_KEEP_DIRECTIONS is DPX_ERR_UNSUPPORTED, as for the other banded
+                         algorithms.  packed2 input, dpx_align_batch, the output pipeline, dpx_batch_create_on and a caller's stream
+                         as for BANW.  z-drop / x-drop termination and ksw2's "best score reaching the end of the query" are not
+                         provided.
+                         Added without an ABI bump or a new symbol: a library that predates it returns DPX_ERR_INVALID for algo 10. */
 } dpx_algo;
 
 /* Identical in layout to the reference's `struct seqPair` (c++/parseInput.h:22-29): byte offsets into the
@@ -141,13 +172,13 @@ typedef struct dpx_params {
     int32_t algo;      /* dpx_algo */
     int32_t match;
     int32_t mismatch;
-    int32_t gapOpen;   /* linear gap for LNW/LSW/BSW; gap-open for ANW / ASW / BASW / ASG / BANW */
-    int32_t gapExtend; /* ANW / ASW / BASW / ASG / BANW only */
-    int32_t band;      /* BSW / BASW / BANW: cells with |i-j| <= band-1 are computed */
+    int32_t gapOpen;   /* linear gap for LNW/LSW/BSW; gap-open for ANW / ASW / BASW / ASG / BANW / BAXT */
+    int32_t gapExtend; /* ANW / ASW / BASW / ASG / BANW / BAXT only */
+    int32_t band;      /* BSW / BASW / BANW / BAXT: cells with |i-j| <= band-1 are computed */
 } dpx_params;
 
 /* dpx_batch_create flags */
-#define DPX_KEEP_MATRICES 0x0u /* default: write the int16 score matrices (H; H,I,D for ANW / ASW / BASW / ASG / BANW) to HBM */
+#define DPX_KEEP_MATRICES 0x0u /* default: write the int16 score matrices (H; H,I,D for ANW / ASW / BASW / ASG / BANW / BAXT) to HBM */
 #define DPX_SCORE_ONLY    0x1u /* no matrix writeback (not HBM-bound; never used for the roofline figure) */
 #define DPX_TIME_FILLS    0x2u /* bracket every dpx_batch_fill() with HIP events: dpx_batch_last_fill_usec() */
 #define DPX_TUNE_PLACEMENT 0x4u /* the batch will be filled many times: time its matrix pool (>= 1 GiB) with hipMemset and shop for a better
@@ -159,7 +190,7 @@ typedef struct dpx_params {
                                     padding per query row (about a quarter of an int16 H batch's bytes, a twelfth of ANW's H/I/D, from
                                     a few hundred rows on; short reads keep a larger fraction); scores may exceed int16 (bounds checked against 2^28) and references 65 000 columns.
                                     dpx_batch_matrix() returns DPX_ERR_NO_MATRIX, dpx_batch_directions() exports the codes.  With
-                                    DPX_SCORE_ONLY: DPX_ERR_INVALID; with BSW / BASW / BANW: DPX_ERR_UNSUPPORTED (banded directions are not implemented). */
+                                    DPX_SCORE_ONLY: DPX_ERR_INVALID; with BSW / BASW / BANW / BAXT: DPX_ERR_UNSUPPORTED (banded directions are not implemented). */
 
 /* matrix selectors for dpx_batch_matrix / dpx_batch_directions */
 #define DPX_MAT_H 0 /* scoring matrix   (reference: memo / scoringMemo)            */
