@@ -17,6 +17,14 @@ from .capi import (  # noqa: F401
     ALGO_LNW,
     ALGO_LSW,
     ALGO_NAMES,
+    ALIGNMENT_DTYPE,
+    CIGAR_EXTENDED,
+    CIGAR_M,
+    CIGAR_OP_D,
+    CIGAR_OP_EQ,
+    CIGAR_OP_I,
+    CIGAR_OP_M,
+    CIGAR_OP_X,
     MAT_D,
     MAT_H,
     MAT_I,
@@ -29,6 +37,7 @@ from .capi import (  # noqa: F401
     DpxError,
     Params,
     SeqPair,
+    cigar_text,
     device_count,
     device_info,
     init,
@@ -42,5 +51,6 @@ from .synth import SynthBatch, make_batch, parse_pairs_file, write_pairs_file  #
 __all__ = [
     "ALGO_ANW", "ALGO_ASG", "ALGO_ASW", "ALGO_BANW", "ALGO_BASW", "ALGO_BAXT", "ALGO_BSW", "ALGO_LNW", "ALGO_LSW", "ALGO_NAMES", "MAT_D", "MAT_H", "MAT_I", "SCORE_ONLY", "TIME_FILLS", "TUNE_PLACEMENT",
     "KEEP_MATRICES", "KEEP_DIRECTIONS", "Batch", "DpxError", "Params", "SeqPair", "device_count", "device_info", "init",
-    "lib_path", "load", "pack2", "prim_eval", "SynthBatch", "make_batch", "parse_pairs_file", "write_pairs_file",
+    "lib_path", "load", "pack2", "prim_eval", "ALIGNMENT_DTYPE", "CIGAR_EXTENDED", "CIGAR_M", "CIGAR_OP_D", "CIGAR_OP_EQ", "CIGAR_OP_I",
+    "CIGAR_OP_M", "CIGAR_OP_X", "cigar_text", "SynthBatch", "make_batch", "parse_pairs_file", "write_pairs_file",
 ]

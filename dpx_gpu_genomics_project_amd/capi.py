@@ -17,6 +17,9 @@ ALGO_NAMES = {ALGO_LNW: "LNW", ALGO_LSW: "LSW", ALGO_ANW: "ANW", ALGO_BSW: "BSW"
               ALGO_BANW: "BANW", ALGO_BAXT: "BAXT"}
 KEEP_MATRICES, SCORE_ONLY, TIME_FILLS, TUNE_PLACEMENT, KEEP_DIRECTIONS = 0x0, 0x1, 0x2, 0x4, 0x8
 MAT_H, MAT_I, MAT_D = 0, 1, 2
+# CIGARs (dpx_batch_cigars_begin / _end): an op is (length << 4) | code with BAM's code numbers
+CIGAR_OP_M, CIGAR_OP_I, CIGAR_OP_D, CIGAR_OP_EQ, CIGAR_OP_X = 0, 1, 2, 7, 8
+CIGAR_EXTENDED, CIGAR_M = 0x0, 0x1
 
 # every symbol include/dpx_align.h declares (tests check the .so exports all of them)
 ABI_VERSION_NEEDED = 3  # include/dpx_align.h DPX_ABI_VERSION: round-3 entry points (dpx_pool_reserve, dpx_batch_last_output_usec) + the pool record in dpx_batch_describe
@@ -27,6 +30,7 @@ ABI_SYMBOLS = (
     "dpx_batch_device_results", "dpx_batch_results", "dpx_batch_matrix", "dpx_batch_traceback",
     "dpx_batch_output_begin", "dpx_batch_output_end", "dpx_batch_output_take", "dpx_text_free",
     "dpx_batch_info", "dpx_batch_describe", "dpx_batch_destroy", "dpx_align_batch", "dpx_prim_eval", "dpx_batch_directions",
+    "dpx_batch_cigars_begin", "dpx_batch_cigars_end", "dpx_cigar_text",
 )
 # declared entry points a library may lack and still load (an older build): checked when they are called
 OPTIONAL_SYMBOLS = ("dpx_batch_directions",)
@@ -50,6 +54,10 @@ class Params(C.Structure):
 
 
 PAIR_DTYPE = np.dtype([("referenceIdx", "<i4"), ("referenceSize", "<i4"), ("queryIdx", "<i4"), ("querySize", "<i4")])
+# == struct dpx_alignment (48 bytes): one record per pair from Batch.cigars_end()
+ALIGNMENT_DTYPE = np.dtype([("opsOffset", "<u8"), ("numOps", "<i4"), ("refStart", "<i4"), ("refEnd", "<i4"), ("qryStart", "<i4"),
+                            ("qryEnd", "<i4"), ("matches", "<i4"), ("mismatches", "<i4"), ("insertions", "<i4"), ("deletions", "<i4"),
+                            ("reserved", "<i4")])
 
 _lib: Optional[C.CDLL] = None
 
@@ -105,6 +113,9 @@ def load() -> C.CDLL:
     lib.dpx_prim_eval.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp]
     if hasattr(lib, "dpx_batch_directions"):
         lib.dpx_batch_directions.argtypes = [vp, C.c_size_t, C.c_int, vp]
+    lib.dpx_batch_cigars_begin.argtypes = [vp, C.c_uint]
+    lib.dpx_batch_cigars_end.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64)]
+    lib.dpx_cigar_text.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     for name in ABI_SYMBOLS:  # every declared entry point must be exported (the optional ones by libraries that have them)
         if name not in OPTIONAL_SYMBOLS:
             getattr(lib, name)
@@ -240,6 +251,19 @@ class Batch:
         raw = C.string_at(text, nbytes.value)
         return raw, np.ctypeslib.as_array(offs, shape=(self.num_pairs + 1,)).copy()
 
+    def cigars_begin(self, flags: int = CIGAR_EXTENDED) -> None:
+        """Start building the batch's alignment records and CIGAR ops on the device (asynchronous)."""
+        _check(self._lib.dpx_batch_cigars_begin(self._h, flags), "dpx_batch_cigars_begin")
+
+    def cigars_end(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(records, ops): one ALIGNMENT_DTYPE record per pair and the packed uint32 ops of the whole batch, as copies."""
+        recs, ops, n = C.c_void_p(), C.c_void_p(), C.c_uint64(0)
+        _check(self._lib.dpx_batch_cigars_end(self._h, C.byref(recs), C.byref(ops), C.byref(n)), "dpx_batch_cigars_end")
+        records = np.frombuffer(C.string_at(recs, self.num_pairs * ALIGNMENT_DTYPE.itemsize), dtype=ALIGNMENT_DTYPE).copy() \
+            if self.num_pairs else np.zeros(0, ALIGNMENT_DTYPE)
+        out = np.frombuffer(C.string_at(ops, n.value * 4), dtype=np.uint32).copy() if n.value else np.zeros(0, np.uint32)
+        return records, out
+
     def info(self) -> dict:
         npairs, cells, mb, ab = C.c_size_t(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         _check(self._lib.dpx_batch_info(self._h, C.byref(npairs), C.byref(cells), C.byref(mb), C.byref(ab)),
@@ -270,6 +294,17 @@ class Batch:
             self.close()
         except Exception:
             pass
+
+
+def cigar_text(ops) -> str:
+    """SAM text of an array of ops (dpx_cigar_text; host only, no GPU): "12=1X3D", "*" for none."""
+    lib = load()
+    arr = np.ascontiguousarray(ops, dtype=np.uint32)
+    cap = 11 * arr.size + 2  # at most ten digits and a letter per op
+    buf = C.create_string_buffer(cap)
+    n = C.c_size_t(0)
+    _check(lib.dpx_cigar_text(arr.ctypes.data if arr.size else None, arr.size, buf, cap, C.byref(n)), "dpx_cigar_text")
+    return buf.raw[:n.value].decode("ascii")
 
 
 def prim_eval(ops: Sequence[int], a: Sequence[int], b: Sequence[int], c: Sequence[int]) -> Tuple[np.ndarray, np.ndarray]:

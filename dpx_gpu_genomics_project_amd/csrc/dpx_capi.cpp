@@ -20,6 +20,7 @@
 #include <utility>
 #include <vector>
 
+#include "dpx_cigar.h"
 #include "dpx_dir.h"
 #include "dpx_kernels.h"
 #include "dpx_layout.h"
@@ -540,6 +541,16 @@ struct dpx_batch {
     bool tbLinesValid = false; /* k_traceback has run since the last fill */
     int outState = 0;          /* 0 none, 1 dpx_batch_output_begin() in flight, 2 text on the host */
     uint64_t outFirst = 0;     /* pair number of the batch's first pair in the text */
+    /* CIGARs (dpx_batch_cigars_begin / _end): built from the same traceback lines as the text, with buffers of their own so that the
+     * two output paths may follow one fill in either order */
+    int cigarState = 0;        /* 0 none, 1 dpx_batch_cigars_begin() in flight, 2 records and ops on the host */
+    unsigned cigarFlags = 0;
+    char *dCigar = nullptr;    /* device: dpx_alignment[numPairs], uint64 total, uint64 tile sums of the scan */
+    uint32_t *dCigarOps = nullptr; /* device: one op per column at worst */
+    char *hCigar = nullptr;    /* pinned: dpx_alignment[numPairs], uint64 total */
+    uint32_t *hCigarOps = nullptr; /* pinned: exactly the ops */
+    size_t dCigarCap = 0, dCigarOpsCap = 0, hCigarCap = 0, hCigarOpsCap = 0;
+    uint64_t cigarOps = 0;     /* total number of ops (state 2) */
     size_t nSingles = 0, nCouples = 0, nLanePairs = 0, nWaves = 0; /* launch-list sizes (dpx_batch_describe) */
     PoolRecord poolRec;    /* how the matrix pool behind dMat was built / timed */
     bool tunePool = false, tuneShop = false; /* DPX_TUNE_PLACEMENT: the pool is timed / shopped for at the end of dpx_batch_create */
@@ -1031,6 +1042,10 @@ int dpx_batch_destroy(dpx_batch *b) {
     g_tbDevCache.park(b->dOut, b->dOutCap);
     g_tbHostCache.park(b->hMeta, b->hMetaCap);
     g_tbHostCache.park(b->hOut, b->hOutCap);
+    g_tbDevCache.park(b->dCigar, b->dCigarCap);
+    g_tbDevCache.park(b->dCigarOps, b->dCigarOpsCap);
+    g_tbHostCache.park(b->hCigar, b->hCigarCap);
+    g_tbHostCache.park(b->hCigarOps, b->hCigarOpsCap);
     g_stageCache.park(b->hStage, b->hStageCap);
     delete b;
     trace.mark("destroy");
@@ -1560,7 +1575,9 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
         b->uploadPending = true;
     }
     if (dirGlobal) b->dirScratch = align_up(std::min<size_t>(std::max<size_t>(numSingles, 1), DPX_DIR_SCRATCH_SLOTS) * dirPerWave, 256);
-    if (b->store && (b->matElems || b->dirScratch)) {
+    /* (a batch whose pairs are all empty has no cells, but k_traceback_wave loads the pool's first 16 bytes in place of every cell without
+     * storage and masks them afterwards: such a batch gets a pool of 256 bytes, so that a.mat is an address the device may read) */
+    if (b->store && (b->matElems || b->dirScratch || numPairs)) {
         void *pool = nullptr;
         bool fresh = false;
         /* DPX_POOL_GUARD=1 (tests): 4 MiB behind the matrices are filled with a pattern here and checked by dpx_batch_sync() -- a kernel that
@@ -1568,7 +1585,7 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
         const bool guardOn = kn.poolGuard != 0;
         b->guardBytes = guardOn ? (size_t)4 << 20 : 0;
         const size_t guardAt = b->matElems * sizeof(int16_t) + b->dirScratch;
-        CREATE_TRY(g_matCache.take(&pool, guardAt + b->guardBytes, &b->matPoolBytes, &fresh));
+        CREATE_TRY(g_matCache.take(&pool, std::max<size_t>(guardAt + b->guardBytes, 256), &b->matPoolBytes, &fresh));
         if (b->guardBytes) CREATE_TRY(hipMemset((char *)pool + guardAt, 0xA5, b->guardBytes));
         if (b->guardBytes && kn.poolGuard == 2) { /* (the checker's own test: one byte of the band is already wrong) */
             CREATE_TRY(hipMemset((char *)pool + guardAt + 12345, 0, 1));
@@ -1779,6 +1796,7 @@ int dpx_batch_fill(dpx_batch *b, void *stream) {
     b->filled = true;
     b->tbLinesValid = false;
     b->outState = 0;
+    b->cigarState = 0;
     return DPX_OK;
 }
 
@@ -1827,6 +1845,7 @@ int dpx_batch_fill_timed(dpx_batch *b, int repeats, double *usecPerFill) {
     b->filled = true;
     b->tbLinesValid = false;
     b->outState = 0;
+    b->cigarState = 0;
     return DPX_OK;
 }
 
@@ -1939,6 +1958,42 @@ int dpx_batch_matrix(dpx_batch *b, size_t pair, int which, int16_t *out) {
  * (the reference's V15 packed variable-length strings, cuda/LNW/LinearNeedlemanWunschV15.cu:168-172,372-425; the blocks are
  * already formatted as c++/main.cpp prints them, so a driver writes a batch with one fwrite) */
 
+/* The device traceback of every pair into the line buffers (b->dTb must exist), on the batch's stream, unless the lines of this fill
+ * are there already: the one place that chooses the walk, for the text pipeline and the CIGAR path alike. */
+static int traceback_lines(dpx_batch *b) {
+    if (b->tbLinesValid) return DPX_OK;
+    /* How to walk (round 4, tools/tb_kernel.sh, kernel time alone; profiles/r04/traceback_walks.txt).  Walk 2 = one WAVE per pair
+     * (k_traceback_wave: runs of path steps decided by all lanes at once from an LDS window): LSW / LNW always -- 1000 x 512^2 0.13 vs
+     * 0.60 ms for one lane per pair, 16 000 x 512^2 0.50 vs 0.76, 20 000 x 300^2 0.36 vs 0.54, 100 000 short reads 0.33 vs 0.57 (LSW) /
+     * 0.71 vs 0.69 (LNW); ANW (three planes per window, 48-row banded windows) up to 20 000 pairs -- 1000 x 512^2 0.17 vs 1.16,
+     * 5000 x 1024^2 0.86 vs 2.51, 20 000 x 300^2 0.92 vs 0.98, but 100 000 short reads 1.48 vs 0.98.  Walks 0 / 1 = one lane
+     * per pair, cell by cell / through register-cached column vectors (the latter from 64k pairs on: enough lanes in flight to thrash
+     * L1 / L2 between two steps of a lane).  Banded matrices: walk 2 as well (its band-layout window loads; numbers in the same file).
+     * DPX_TB_WALK=0/1/2 forces one (tests). */
+    int walk = b->numPairs >= 65536 ? 1 : 0;
+    if (b->kernelAlgo == DPX_ALGO_LSW || b->kernelAlgo == DPX_ALGO_LNW || b->kernelAlgo == DPX_ALGO_BSW) walk = 2;
+    else if (is_affine(b->kernelAlgo) && b->numPairs <= 20000) walk = 2; /* (ASW: as ANW; its walk 1 is walk 0) */
+    { const int w = knobs().tbWalk; if (w >= 0) walk = std::min(2, w); }
+    /* banded affine SW: as ASW -- one wave per pair up to 20 000 pairs (k_basw_traceback_wave, band-layout window loads for the three
+     * planes), one lane per pair beyond that or under DPX_TB_WALK=0 / 1 (k_basw_traceback) */
+    if (b->kernelAlgo == DPX_ALGO_BASW) HIP_TRY(dpx_launch_basw_traceback(b->args, (int)b->numPairs, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream));
+    else if (is_banw_layout(b->kernelAlgo)) HIP_TRY(dpx_launch_banw_traceback(b->args, (int)b->numPairs, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream)); /* (banded affine NW, and the extension, which walks from its end cell to the anchor: the same choice) */
+    else if (b->dirs) HIP_TRY(dpx_launch_traceback_dir(b->dirArgs, (int)b->numPairs, b->kernelAlgo, b->R, b->dTbOff, b->dTb, b->dTbLen, b->stream));
+    else HIP_TRY(dpx_launch_traceback(b->args, (int)b->numPairs, b->kernelAlgo, b->R, b->planes, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream));
+    b->tbLinesValid = true;
+    return DPX_OK;
+}
+
+/* the fill ran on a caller's stream: order the batch's stream behind it without blocking the host */
+static int order_behind_fill(dpx_batch *b) {
+    if (b->lastStream && b->lastStream != b->stream) {
+        if (!b->evOrder) HIP_TRY(hipEventCreateWithFlags(&b->evOrder, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(b->evOrder, b->lastStream));
+        HIP_TRY(hipStreamWaitEvent(b->stream, b->evOrder, 0));
+    }
+    return DPX_OK;
+}
+
 /* stage 1, asynchronous on the batch's stream: kernels + D2H of the offsets / lengths */
 
 static int output_begin(dpx_batch *b, uint64_t firstNumber) {
@@ -1957,38 +2012,14 @@ static int output_begin(dpx_batch *b, uint64_t firstNumber) {
     }
     uint64_t *hOff = reinterpret_cast<uint64_t *>(b->hMeta);
     int32_t *hLen = reinterpret_cast<int32_t *>(hOff + np + 1);
-    if (b->lastStream && b->lastStream != b->stream) { /* the fill ran on a caller's stream: order behind it without blocking the host */
-        if (!b->evOrder) HIP_TRY(hipEventCreateWithFlags(&b->evOrder, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(b->evOrder, b->lastStream));
-        HIP_TRY(hipStreamWaitEvent(b->stream, b->evOrder, 0));
-    }
+    { const int rc = order_behind_fill(b); if (rc != DPX_OK) return rc; }
     const bool timeOut = (b->flags & DPX_TIME_FILLS) != 0;
     if (timeOut) {
         if (!b->evOut0) HIP_TRY(hipEventCreate(&b->evOut0));
         if (!b->evOut1) HIP_TRY(hipEventCreate(&b->evOut1));
         HIP_TRY(hipEventRecord(b->evOut0, b->stream));
     }
-    if (!b->tbLinesValid) {
-        /* How to walk (round 4, tools/tb_kernel.sh, kernel time alone; profiles/r04/traceback_walks.txt).  Walk 2 = one WAVE per pair
-         * (k_traceback_wave: runs of path steps decided by all lanes at once from an LDS window): LSW / LNW always -- 1000 x 512^2 0.13 vs
-         * 0.60 ms for one lane per pair, 16 000 x 512^2 0.50 vs 0.76, 20 000 x 300^2 0.36 vs 0.54, 100 000 short reads 0.33 vs 0.57 (LSW) /
-         * 0.71 vs 0.69 (LNW); ANW (three planes per window, 48-row banded windows) up to 20 000 pairs -- 1000 x 512^2 0.17 vs 1.16,
-         * 5000 x 1024^2 0.86 vs 2.51, 20 000 x 300^2 0.92 vs 0.98, but 100 000 short reads 1.48 vs 0.98.  Walks 0 / 1 = one lane
-         * per pair, cell by cell / through register-cached column vectors (the latter from 64k pairs on: enough lanes in flight to thrash
-         * L1 / L2 between two steps of a lane).  Banded matrices: walk 2 as well (its band-layout window loads; numbers in the same file).
-         * DPX_TB_WALK=0/1/2 forces one (tests). */
-        int walk = b->numPairs >= 65536 ? 1 : 0;
-        if (b->kernelAlgo == DPX_ALGO_LSW || b->kernelAlgo == DPX_ALGO_LNW || b->kernelAlgo == DPX_ALGO_BSW) walk = 2;
-        else if (is_affine(b->kernelAlgo) && b->numPairs <= 20000) walk = 2; /* (ASW: as ANW; its walk 1 is walk 0) */
-        { const int w = knobs().tbWalk; if (w >= 0) walk = std::min(2, w); }
-        /* banded affine SW: as ASW -- one wave per pair up to 20 000 pairs (k_basw_traceback_wave, band-layout window loads for the three
-         * planes), one lane per pair beyond that or under DPX_TB_WALK=0 / 1 (k_basw_traceback) */
-        if (b->kernelAlgo == DPX_ALGO_BASW) HIP_TRY(dpx_launch_basw_traceback(b->args, (int)np, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream));
-        else if (is_banw_layout(b->kernelAlgo)) HIP_TRY(dpx_launch_banw_traceback(b->args, (int)np, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream)); /* (banded affine NW, and the extension, which walks from its end cell to the anchor: the same choice) */
-        else if (b->dirs) HIP_TRY(dpx_launch_traceback_dir(b->dirArgs, (int)np, b->kernelAlgo, b->R, b->dTbOff, b->dTb, b->dTbLen, b->stream));
-        else HIP_TRY(dpx_launch_traceback(b->args, (int)np, b->kernelAlgo, b->R, b->planes, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream));
-        b->tbLinesValid = true;
-    }
+    { const int rc = traceback_lines(b); if (rc != DPX_OK) return rc; }
     HIP_TRY(dpx_launch_output(b->dPairs, b->dScore, b->dTbLen, b->dTbOff, b->dTb, (int)np, (unsigned long long)firstNumber,
                               reinterpret_cast<unsigned long long *>(b->dOutScratch), reinterpret_cast<unsigned long long *>(b->dOutOff), b->dOut,
                               false, false, b->stream));
@@ -2136,6 +2167,93 @@ int dpx_batch_traceback(dpx_batch *b, size_t pair, char *refLine, char *relLine,
     for (int l = 0; l < 3; l++)
         if (dst[l]) { memcpy(dst[l], lines + (size_t)l * (size_t)(k + 1), (size_t)k); dst[l][k] = 0; }
     if (len) *len = k;
+    return DPX_OK;
+}
+
+/* ---- CIGARs: the same traceback lines, run-length encoded on the device (dpx_cigar_kernels.hip) -> D2H of one record per pair,
+ * then of exactly the ops.  Buffers of its own, so the text pipeline and this one may follow the same fill in either order. */
+
+int dpx_batch_cigars_begin(dpx_batch *b, unsigned flags) {
+    if (!b || (flags & ~DPX_CIGAR_M) != 0) return DPX_ERR_INVALID;
+    if (!b->store) return DPX_ERR_NO_MATRIX;
+    if (!b->filled) return DPX_ERR_NOT_FILLED;
+    int rc = bind_device(b->device);
+    if (rc != DPX_OK) return rc;
+    const size_t np = b->numPairs, recBytes = np * sizeof(dpx_alignment);
+    const uint64_t lines = b->tbOff[np];
+    /* buffers, on first use (a failed attempt is simply repeated); ops, worst case: one per column of every line capacity */
+    if (!b->dTb) HIP_TRY(g_tbDevCache.take((void **)&b->dTb, (size_t)std::max<uint64_t>(lines, 16), &b->dTbCap));
+    if (!b->dCigar) HIP_TRY(g_tbDevCache.take((void **)&b->dCigar, recBytes + (1 + dpx_cigar_scan_tiles(np)) * sizeof(uint64_t) + 16, &b->dCigarCap));
+    if (!b->dCigarOps) HIP_TRY(g_tbDevCache.take((void **)&b->dCigarOps, (size_t)(lines / 3) * sizeof(uint32_t) + 16, &b->dCigarOpsCap));
+    if (!b->hCigar) HIP_TRY(g_tbHostCache.take((void **)&b->hCigar, recBytes + sizeof(uint64_t) + 16, &b->hCigarCap));
+    unsigned long long *dTotal = reinterpret_cast<unsigned long long *>(b->dCigar + recBytes); /* (48 bytes per record: 8-byte aligned) */
+    if (np) {
+        rc = order_behind_fill(b);
+        if (rc == DPX_OK) rc = traceback_lines(b);
+        if (rc != DPX_OK) return rc;
+        HIP_TRY(dpx_launch_cigars(b->dPairs, b->dEndRow, b->dEndCol, b->dTbLen, b->dTbOff, b->dTb, (int)np, flags,
+                                  reinterpret_cast<dpx_alignment *>(b->dCigar), dTotal + 1, dTotal, b->dCigarOps, b->stream));
+        HIP_TRY(hipMemcpyAsync(b->hCigar, b->dCigar, recBytes + sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
+    } else {
+        memset(b->hCigar, 0, sizeof(uint64_t)); /* a batch without pairs: no records, no ops */
+    }
+    b->cigarFlags = flags;
+    b->cigarState = 1;
+    return DPX_OK;
+}
+
+int dpx_batch_cigars_end(dpx_batch *b, const dpx_alignment **records, const uint32_t **ops, uint64_t *numOps) {
+    if (!b) return DPX_ERR_INVALID;
+    if (b->cigarState == 0) return DPX_ERR_NOT_FILLED; /* no dpx_batch_cigars_begin() since the last fill */
+    int rc = bind_device(b->device);
+    if (rc != DPX_OK) return rc;
+    if (b->cigarState == 1) {
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        uint64_t total = 0;
+        memcpy(&total, b->hCigar + b->numPairs * sizeof(dpx_alignment), sizeof total);
+        const size_t bytes = (size_t)total * sizeof(uint32_t);
+        if (!b->hCigarOps || b->hCigarOpsCap < bytes + 16) {
+            g_tbHostCache.park(b->hCigarOps, b->hCigarOpsCap);
+            b->hCigarOps = nullptr;
+            HIP_TRY(g_tbHostCache.take((void **)&b->hCigarOps, bytes + 16, &b->hCigarOpsCap));
+        }
+        if (bytes) {
+            HIP_TRY(hipMemcpyAsync(b->hCigarOps, b->dCigarOps, bytes, hipMemcpyDeviceToHost, b->stream));
+            HIP_TRY(hipStreamSynchronize(b->stream));
+        }
+        b->cigarOps = total;
+        b->cigarState = 2;
+    }
+    if (records) *records = reinterpret_cast<const dpx_alignment *>(b->hCigar);
+    if (ops) *ops = b->hCigarOps;
+    if (numOps) *numOps = b->cigarOps;
+    return DPX_OK;
+}
+
+int dpx_cigar_text(const uint32_t *ops, size_t numOps, char *out, size_t cap, size_t *len) {
+    if ((!ops && numOps) || (!out && cap)) return DPX_ERR_INVALID;
+    static const char letters[] = "MID....=X"; /* BAM's numbering; 3..6 (N S H P) never come out of the engine */
+    size_t need = numOps ? 0 : 1; /* "*" */
+    for (size_t k = 0; k < numOps; k++) {
+        const uint32_t code = ops[k] & 0xFu;
+        if (code > 8u || letters[code] == '.') return DPX_ERR_INVALID;
+        uint32_t v = ops[k] >> 4;
+        do { need++; v /= 10u; } while (v);
+        need++;
+    }
+    if (len) *len = need;
+    if (cap < need + 1) return DPX_ERR_INVALID;
+    char *q = out;
+    if (!numOps) *q++ = '*';
+    for (size_t k = 0; k < numOps; k++) {
+        char digits[10];
+        int d = 0;
+        uint32_t v = ops[k] >> 4;
+        do { digits[d++] = (char)('0' + (int)(v % 10u)); v /= 10u; } while (v);
+        while (d) *q++ = digits[--d];
+        *q++ = letters[ops[k] & 0xFu];
+    }
+    *q = 0;
     return DPX_OK;
 }
 

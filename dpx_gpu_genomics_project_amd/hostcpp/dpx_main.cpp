@@ -6,9 +6,12 @@
 // being written to stdout by the printer thread (the software pipeline of V19.cu:546-579).  The device formats every
 // pair's block itself (packed variable-length result strings, V15.cu:168-172,372-425), so printing a batch is one fwrite.
 // stdout keeps the reference's lines so logs stay diff-able.
+// -cigar [M]: instead of the four-line block, one tab-separated line per pair from the engine's alignment records and CIGAR ops
+// (dpx_batch_cigars_begin / _end): pair, score, qryLen, qryStart, qryEnd, refLen, refStart, refEnd, matches, alnLen, cigar -- PAF's
+// coordinates and the SAM CIGAR ('=' / 'X' ops; "-cigar M" merges them into 'M').  The lines are formatted on the host.
 //
 //   dpx_main -pairs <file> [-match 3] [-mismatch -1] [-open -2 | -gap -2] [-extend -1]
-//            [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band 128] [-batch N | -pool-gb 4] [-inflight K] [-tune 0|1] [-device 0] [-noprint] [-pack2] [-directions] [-producer P] [-rank r -world w]
+//            [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band 128] [-batch N | -pool-gb 4] [-inflight K] [-tune 0|1] [-device 0] [-noprint] [-pack2] [-directions] [-cigar [M]] [-producer P] [-rank r -world w]
 //
 // Batch size: by default from a matrix-pool BUDGET (-pool-gb, 4 GiB): as many pairs as fit the budget, at most 20000 (the
 // reference sizes its buffers once for BATCH_SIZE = 10000 reads of 150 bases, cuda/LNW/LinearNeedlemanWunschV9.cu:26-46,
@@ -56,7 +59,7 @@ struct InFlight { // one batch between dpx_batch_create and dpx_batch_destroy
 int main(int argc, char *argv[]) {
     if (argc < 3) {
         fprintf(stderr, "usage: dpx_main -pairs <InSeqFile> -match <matchWeight> -mismatch <mismatchWeight> -open <gapWeight> "
-                        "[-extend <gapExtend>] [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band <B>] [-batch <N>] [-device <D>] [-noprint]\n");
+                        "[-extend <gapExtend>] [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band <B>] [-batch <N>] [-device <D>] [-noprint] [-cigar [M]]\n");
         exit(EXIT_FAILURE);
     }
     const char *pairFileName = nullptr;
@@ -65,6 +68,8 @@ int main(int argc, char *argv[]) {
     double poolGb = 4.0;
     bool print = true, pack2 = false;
     int producerFlag = -1; // producer threads; -1: by batch size (2 for batches of many short pairs, none for few long ones)
+    bool cigar = false;      // -cigar: records + CIGAR ops instead of the text pipeline
+    unsigned cigarFlags = DPX_CIGAR_EXTENDED;
     bool directions = false; // -directions: batches keep 4-bit direction codes (DPX_KEEP_DIRECTIONS): int32 scores, a quarter of the pool per pair
     int inflight = 3;      // batches on the device at a time (= matrix pools reserved)
     int tuneFlag = -1;     // -1: by the length of the job
@@ -87,6 +92,10 @@ int main(int argc, char *argv[]) {
         else if (!strcmp(argv[i], "-noprint")) print = false;
         else if (!strcmp(argv[i], "-pack2")) pack2 = true;
         else if (!strcmp(argv[i], "-directions")) directions = true;
+        else if (!strcmp(argv[i], "-cigar")) {
+            cigar = true;
+            if (i + 1 < argc && !strcmp(argv[i + 1], "M")) { cigarFlags = DPX_CIGAR_M; i++; }
+        }
         else if (!strcmp(argv[i], "-producer")) producerFlag = atoi(next("-producer"));
         else if (!strcmp(argv[i], "-inflight")) inflight = atoi(next("-inflight"));
         else if (!strcmp(argv[i], "-tune")) tuneFlag = atoi(next("-tune"));
@@ -191,7 +200,30 @@ int main(int argc, char *argv[]) {
         uint64_t t0 = get_time();
         char *text = nullptr;
         size_t bytes = 0;
-        if (print) {
+        std::string lines; // -cigar: the batch's lines, formatted here while the batch (which owns the records and ops) is alive
+        if (print && cigar) {
+            const dpx_alignment *recs = nullptr;
+            const uint32_t *ops = nullptr;
+            uint64_t numOps = 0;
+            if ((rc = dpx_batch_cigars_end(f.b, &recs, &ops, &numOps)) != DPX_OK) die("TRACEBACK FAILED", rc);
+            std::vector<int32_t> scores(f.count);
+            if ((rc = dpx_batch_results(f.b, scores.data(), nullptr, nullptr)) != DPX_OK) die("RESULTS FAILED", rc);
+            std::vector<char> cg;
+            for (size_t k = 0; k < f.count; k++) {
+                const dpx_alignment &r = recs[k];
+                const seqPair &sp = sequenceIdxs[f.first + k];
+                size_t need = 0;
+                cg.resize((size_t)r.numOps * 11 + 2); // at most ten digits and a letter per op
+                if ((rc = dpx_cigar_text(ops + r.opsOffset, (size_t)r.numOps, cg.data(), cg.size(), &need)) != DPX_OK) die("CIGAR TEXT FAILED", rc);
+                char head[256];
+                const int h = snprintf(head, sizeof head, "%zu\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t", shardFirst + f.first + k, scores[k],
+                                       (int)sp.querySize, r.qryStart, r.qryEnd, (int)sp.referenceSize, r.refStart, r.refEnd, r.matches,
+                                       r.matches + r.mismatches + r.insertions + r.deletions);
+                lines.append(head, (size_t)h);
+                lines.append(cg.data(), need);
+                lines.push_back('\n');
+            }
+        } else if (print) {
             if ((rc = dpx_batch_output_take(f.b, &text, &bytes)) != DPX_OK) die("TRACEBACK FAILED", rc);
         } else if ((rc = dpx_batch_sync(f.b)) != DPX_OK) die("KERNEL FAILED", rc);
         double usec = 0;
@@ -205,7 +237,8 @@ int main(int argc, char *argv[]) {
         memalloc_time += get_time() - t0;
         retire_printed();
         printingText = text;
-        if (print) printer = std::thread([text, bytes]() { fwrite(text, 1, bytes, stdout); });
+        if (print && cigar) printer = std::thread([s = std::move(lines)]() { fwrite(s.data(), 1, s.size(), stdout); });
+        else if (print) printer = std::thread([text, bytes]() { fwrite(text, 1, bytes, stdout); });
     };
     size_t shardCells = 0;
     for (size_t i = shardLo; i < shardHi; i++) shardCells += (size_t)sequenceIdxs[i].referenceSize * (size_t)sequenceIdxs[i].querySize;
@@ -236,7 +269,8 @@ int main(int argc, char *argv[]) {
         create_time += get_time() - t0;
         if ((prc = dpx_batch_fill(next.b, nullptr)) != DPX_OK) die("KERNEL LAUNCH FAILED", prc);
         // global pair numbers: shardFirst + index inside the shard
-        if (print && (prc = dpx_batch_output_begin(next.b, shardFirst + first)) != DPX_OK) die("TRACEBACK LAUNCH FAILED", prc);
+        if (print && cigar) { if ((prc = dpx_batch_cigars_begin(next.b, cigarFlags)) != DPX_OK) die("TRACEBACK LAUNCH FAILED", prc); }
+        else if (print && (prc = dpx_batch_output_begin(next.b, shardFirst + first)) != DPX_OK) die("TRACEBACK LAUNCH FAILED", prc);
         return next;
     };
     auto pool_is_huge = [](const InFlight &f) { uint64_t mb = 0; dpx_batch_info(f.b, nullptr, nullptr, &mb, nullptr); return mb >= (16ull << 30); };

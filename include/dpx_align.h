@@ -25,7 +25,7 @@ extern "C" {
 /* 1: round 1.  2: + dpx_batch_create_on, dpx_batch_fill_timed, dpx_batch_last_fill_usec, dpx_batch_output_begin/_end/_take,
  * dpx_text_free, DPX_TUNE_PLACEMENT (round 2).  3: + dpx_pool_reserve, dpx_text_reserve, dpx_batch_last_output_usec, dpx_pack2, dpx_batch_create_packed2; dpx_batch_describe reports the
  * matrix pool (round 3); + DPX_KEEP_DIRECTIONS, dpx_batch_directions (detect them by the exported symbol: the number stays 3); + DPX_ALGO_ASW
- * (detect it by creating a batch: an older library returns DPX_ERR_INVALID for algo 4); + DPX_ALGO_BASW (likewise: DPX_ERR_INVALID for algo 5); + DPX_ALGO_ASG (likewise: DPX_ERR_INVALID for algo 6); + DPX_ALGO_BANW (likewise: DPX_ERR_INVALID for algo 7); + DPX_ALGO_BAXT (likewise: DPX_ERR_INVALID for algo 10).  Additions only: a caller built against an older version keeps working; dpx_abi_version() >= the version
+ * (detect it by creating a batch: an older library returns DPX_ERR_INVALID for algo 4); + DPX_ALGO_BASW (likewise: DPX_ERR_INVALID for algo 5); + DPX_ALGO_ASG (likewise: DPX_ERR_INVALID for algo 6); + DPX_ALGO_BANW (likewise: DPX_ERR_INVALID for algo 7); + DPX_ALGO_BAXT (likewise: DPX_ERR_INVALID for algo 10); + dpx_batch_cigars_begin / _end, dpx_cigar_text (detect them by the exported symbol).  Additions only: a caller built against an older version keeps working; dpx_abi_version() >= the version
  * a caller needs is the check. */
 #define DPX_ABI_VERSION 3
 
@@ -83,7 +83,7 @@ typedef enum dpx_algo {
                          Walk: ANW's three-state walk from the end cell in state SCORING while i != 0 && j != 0; then the remaining i
                          query characters are emitted as deletions (ANW's column-0 tail); the remaining j reference characters are NOT
                          emitted: the walk stops at row 0.  The reference start column of the alignment is endCol minus the number of
-                         non-'_' characters of the reference line.
+                         non-'_' characters of the reference line (refStart of the pair's dpx_alignment record).
                          Text: the "<pair> | <score>\n" header, then the reference, relation and query lines; the path is printed
                          whatever the sign of the score, only m = 0 gives three empty lines (unlike LSW's zero-score case).
                          dpx_batch_matrix: row-major (m+1) x (n+1), H with the borders above, I and D with 0 on the borders, as for
@@ -319,6 +319,54 @@ int dpx_batch_output_end(dpx_batch *b, const char **text, size_t *bytes, const u
  * from host strings while batch k runs, V19.cu:546-579).  Give the buffer back with dpx_text_free(). */
 int dpx_batch_output_take(dpx_batch *b, char **text, size_t *bytes);
 int dpx_text_free(char *text);
+
+/* ---- CIGARs and alignment coordinates of the whole batch (what a mapper writes into a SAM or PAF record) -------------------
+ * The traceback lines, run-length encoded on the device: one fixed-size record per pair and one packed array of ops for the batch,
+ * instead of three (m + n)-byte text lines per pair.  Every algorithm, DPX_KEEP_MATRICES and DPX_KEEP_DIRECTIONS batches; a
+ * DPX_SCORE_ONLY batch is DPX_ERR_NO_MATRIX.  No reference counterpart.  Added without an ABI bump: detect the three functions by
+ * the exported symbol.
+ *
+ * Columns of the three lines are classified by their relation and query-line characters:
+ *     relation '*'                      '=' (DPX_CIGAR_OP_EQ)  match, consumes both sequences
+ *     relation '|'                      'X' (DPX_CIGAR_OP_X)   mismatch, consumes both
+ *     relation ' ', query line '_'      'D' (DPX_CIGAR_OP_D)   consumes the reference only (the QUERY_INSERTION move)
+ *     relation ' ', anything else       'I' (DPX_CIGAR_OP_I)   consumes the query only (the QUERY_DELETION move)
+ * Sequences that themselves contain the byte '_' are classified by the same rule: a query '_' in a gap column of the reference reads
+ * as 'D'.  Ops are in path order from the start of the alignment to its end cell (left to right along the lines); an op is
+ * (length << 4) | code with BAM's code numbers; the lengths of a pair's ops sum to its alignment length.  Under DPX_CIGAR_M '=' and
+ * 'X' columns merge into 'M' runs (matches and mismatches are still counted apart).
+ * refEnd = the end column and qryEnd = the end row of the results call; refStart = refEnd - (matches + mismatches + deletions),
+ * qryStart = qryEnd - (matches + mismatches + insertions).  An empty alignment (a zero-score local alignment, m = 0 under ASG, a BAXT
+ * pair ending at (0, 0)) has numOps = 0 and start == end.  opsOffset is the exclusive prefix sum of numOps in batch order. */
+typedef struct dpx_alignment {      /* 48 bytes */
+    uint64_t opsOffset;             /* index of this pair's first op in the batch's ops array */
+    int32_t  numOps;
+    int32_t  refStart, refEnd;      /* half-open, 0-based: the alignment covers ref[refStart, refEnd) */
+    int32_t  qryStart, qryEnd;      /* ... and qry[qryStart, qryEnd) */
+    int32_t  matches, mismatches;   /* columns whose relation character is '*' / '|' */
+    int32_t  insertions, deletions; /* columns that consume the query only / the reference only */
+    int32_t  reserved;              /* 0 */
+} dpx_alignment;
+
+#define DPX_CIGAR_OP_M  0u
+#define DPX_CIGAR_OP_I  1u
+#define DPX_CIGAR_OP_D  2u
+#define DPX_CIGAR_OP_EQ 7u
+#define DPX_CIGAR_OP_X  8u          /* BAM's numbering; an op is (length << 4) | code */
+#define DPX_CIGAR_EXTENDED 0x0u     /* '=' and 'X' kept apart (default) */
+#define DPX_CIGAR_M        0x1u     /* '=' and 'X' columns are both M and merge into one run */
+
+/* _begin is asynchronous on the batch's stream (behind a fill on a caller's stream it orders itself with an event): the device
+ * traceback if the lines of this fill do not exist yet (the same walk the text pipeline chooses), then count, scan and write kernels
+ * and the D2H of the records.  _end waits and copies exactly numPairs records and *numOps ops to pinned host memory; the pointers
+ * stay valid until the batch is filled again, the next _begin, or destroy.  The text pipeline and this one may follow the same fill in
+ * either order.  Unknown flag bits: DPX_ERR_INVALID; not filled, or _end without a _begin since the last fill: DPX_ERR_NOT_FILLED. */
+int dpx_batch_cigars_begin(dpx_batch *b, unsigned flags);
+int dpx_batch_cigars_end(dpx_batch *b, const dpx_alignment **records, const uint32_t **ops, uint64_t *numOps);
+/* Host only (no device, no init needed): the SAM text of `numOps` ops ("12=1X3D", letters MID=X; "*" for none) and a terminating
+ * NUL into out[0..cap); *len = its length without the NUL.  A cap too small returns DPX_ERR_INVALID with *len = the length needed;
+ * an op code outside {0, 1, 2, 7, 8} returns DPX_ERR_INVALID. */
+int dpx_cigar_text(const uint32_t *ops, size_t numOps, char *out, size_t cap, size_t *len);
 
 /* Sizes: numPairs, total cells (sum refLen*queryLen, the reference's numCells, c++/parseInput.cpp:100),
  * bytes of HBM the matrices occupy, algorithmic bytes of one fill. */
