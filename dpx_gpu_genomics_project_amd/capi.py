@@ -20,6 +20,9 @@ MAT_H, MAT_I, MAT_D = 0, 1, 2
 # CIGARs (dpx_batch_cigars_begin / _end): an op is (length << 4) | code with BAM's code numbers
 CIGAR_OP_M, CIGAR_OP_I, CIGAR_OP_D, CIGAR_OP_EQ, CIGAR_OP_X = 0, 1, 2, 7, 8
 CIGAR_EXTENDED, CIGAR_M = 0x0, 0x1
+# BAXT's extension mode (dpx_batch_set_extension / dpx_batch_extensions)
+EXT_ZDROPPED, EXT_REACHED_END = 0x1, 0x2
+EXT_NO_QUERY_END = -2**31
 
 # every symbol include/dpx_align.h declares (tests check the .so exports all of them)
 ABI_VERSION_NEEDED = 3  # include/dpx_align.h DPX_ABI_VERSION: round-3 entry points (dpx_pool_reserve, dpx_batch_last_output_usec) + the pool record in dpx_batch_describe
@@ -30,7 +33,7 @@ ABI_SYMBOLS = (
     "dpx_batch_device_results", "dpx_batch_results", "dpx_batch_matrix", "dpx_batch_traceback",
     "dpx_batch_output_begin", "dpx_batch_output_end", "dpx_batch_output_take", "dpx_text_free",
     "dpx_batch_info", "dpx_batch_describe", "dpx_batch_destroy", "dpx_align_batch", "dpx_prim_eval", "dpx_batch_directions",
-    "dpx_batch_cigars_begin", "dpx_batch_cigars_end", "dpx_cigar_text",
+    "dpx_batch_cigars_begin", "dpx_batch_cigars_end", "dpx_cigar_text", "dpx_batch_set_extension", "dpx_batch_extensions",
 )
 # declared entry points a library may lack and still load (an older build): checked when they are called
 OPTIONAL_SYMBOLS = ("dpx_batch_directions",)
@@ -58,6 +61,9 @@ PAIR_DTYPE = np.dtype([("referenceIdx", "<i4"), ("referenceSize", "<i4"), ("quer
 ALIGNMENT_DTYPE = np.dtype([("opsOffset", "<u8"), ("numOps", "<i4"), ("refStart", "<i4"), ("refEnd", "<i4"), ("qryStart", "<i4"),
                             ("qryEnd", "<i4"), ("matches", "<i4"), ("mismatches", "<i4"), ("insertions", "<i4"), ("deletions", "<i4"),
                             ("reserved", "<i4")])
+# == struct dpx_extension (32 bytes): one record per pair from Batch.extensions()
+EXTENSION_DTYPE = np.dtype([("maxScore", "<i4"), ("maxRow", "<i4"), ("maxCol", "<i4"), ("qryEndScore", "<i4"), ("qryEndCol", "<i4"),
+                            ("lastDiag", "<i4"), ("flags", "<u4"), ("reserved", "<i4")])
 
 _lib: Optional[C.CDLL] = None
 
@@ -116,6 +122,8 @@ def load() -> C.CDLL:
     lib.dpx_batch_cigars_begin.argtypes = [vp, C.c_uint]
     lib.dpx_batch_cigars_end.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64)]
     lib.dpx_cigar_text.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.dpx_batch_set_extension.argtypes = [vp, C.c_int32, C.c_int32]
+    lib.dpx_batch_extensions.argtypes = [vp, vp]
     for name in ABI_SYMBOLS:  # every declared entry point must be exported (the optional ones by libraries that have them)
         if name not in OPTIONAL_SYMBOLS:
             getattr(lib, name)
@@ -263,6 +271,16 @@ class Batch:
             if self.num_pairs else np.zeros(0, ALIGNMENT_DTYPE)
         out = np.frombuffer(C.string_at(ops, n.value * 4), dtype=np.uint32).copy() if n.value else np.zeros(0, np.uint32)
         return records, out
+
+    def set_extension(self, zdrop: int = -1, end_bonus: int = -1) -> None:
+        """BAXT only: z-drop threshold and end bonus of the following fills (-1 = off; both off = plain BAXT)."""
+        _check(self._lib.dpx_batch_set_extension(self._h, zdrop, end_bonus), "dpx_batch_set_extension")
+
+    def extensions(self) -> np.ndarray:
+        """One EXTENSION_DTYPE record per pair of the last fill, which must have run in extension mode."""
+        out = np.zeros(self.num_pairs, EXTENSION_DTYPE)
+        _check(self._lib.dpx_batch_extensions(self._h, out.ctypes.data), "dpx_batch_extensions")
+        return out
 
     def info(self) -> dict:
         npairs, cells, mb, ab = C.c_size_t(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)

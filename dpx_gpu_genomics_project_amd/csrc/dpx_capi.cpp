@@ -551,6 +551,11 @@ struct dpx_batch {
     uint32_t *hCigarOps = nullptr; /* pinned: exactly the ops */
     size_t dCigarCap = 0, dCigarOpsCap = 0, hCigarCap = 0, hCigarOpsCap = 0;
     uint64_t cigarOps = 0;     /* total number of ops (state 2) */
+    /* BAXT's extension mode (dpx_batch_set_extension): the next fill runs k_zext_fill while either value is >= 0 */
+    int32_t zdrop = -1, endBonus = -1;
+    bool extFilled = false;    /* the last fill ran k_zext_fill: dExt holds its records and dpx_batch_matrix masks behind lastDiag */
+    int32_t *dExt = nullptr;   /* device: dpx_extension[numPairs] */
+    size_t dExtCap = 0;
     size_t nSingles = 0, nCouples = 0, nLanePairs = 0, nWaves = 0; /* launch-list sizes (dpx_batch_describe) */
     PoolRecord poolRec;    /* how the matrix pool behind dMat was built / timed */
     bool tunePool = false, tuneShop = false; /* DPX_TUNE_PLACEMENT: the pool is timed / shopped for at the end of dpx_batch_create */
@@ -1046,6 +1051,7 @@ int dpx_batch_destroy(dpx_batch *b) {
     g_tbDevCache.park(b->dCigarOps, b->dCigarOpsCap);
     g_tbHostCache.park(b->hCigar, b->hCigarCap);
     g_tbHostCache.park(b->hCigarOps, b->hCigarOpsCap);
+    g_tbDevCache.park(b->dExt, b->dExtCap);
     g_stageCache.park(b->hStage, b->hStageCap);
     delete b;
     trace.mark("destroy");
@@ -1729,9 +1735,15 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
  * 1024 SIMDs) then costs a latency-bound tail of its own.
  * The secondary kernels therefore go to the batch's side stream between a fork and a join event; on `s` the fill still
  * looks like one operation (events recorded on `s` around it time all of it). */
+static bool extension_on(const dpx_batch *b) { return b->zdrop >= 0 || b->endBonus >= 0; }
+
 static hipError_t launch_main(dpx_batch *b, hipStream_t s) { /* the one-wave-per-pair kernel of the batch's algorithm */
     if (b->kernelAlgo == DPX_ALGO_BASW) return dpx_launch_basw_fill(b->args, b->R, b->store, b->ldsBytes, s);
     if (b->kernelAlgo == DPX_ALGO_BANW) return dpx_launch_banw_fill(b->args, b->R, b->store, b->ldsBytes, s);
+    if (b->kernelAlgo == DPX_ALGO_BAXT && extension_on(b)) {
+        const dpx_zext_args za = {b->args, b->zdrop, b->endBonus, b->dExt};
+        return dpx_launch_zext_fill(za, b->R, b->store, b->ldsBytes, s);
+    }
     if (b->kernelAlgo == DPX_ALGO_BAXT) return dpx_launch_baxt_fill(b->args, b->R, b->store, b->ldsBytes, s);
     return dpx_launch_fill(b->args, b->kernelAlgo, b->R, b->store, b->ldsBytes, s);
 }
@@ -1794,6 +1806,7 @@ int dpx_batch_fill(dpx_batch *b, void *stream) {
     if (timed) { HIP_TRY(hipEventRecord(b->evT1, s)); b->fillTimed = true; }
     b->lastStream = s;
     b->filled = true;
+    b->extFilled = extension_on(b);
     b->tbLinesValid = false;
     b->outState = 0;
     b->cigarState = 0;
@@ -1843,6 +1856,7 @@ int dpx_batch_fill_timed(dpx_batch *b, int repeats, double *usecPerFill) {
     *usecPerFill = (double)ms * 1000.0 / repeats;
     b->lastStream = b->stream;
     b->filled = true;
+    b->extFilled = extension_on(b);
     b->tbLinesValid = false;
     b->outState = 0;
     b->cigarState = 0;
@@ -1950,8 +1964,39 @@ int dpx_batch_matrix(dpx_batch *b, size_t pair, int which, int16_t *out) {
     if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
     if (e == hipSuccess) e = hipMemcpy(out, dOut, total * sizeof(int16_t), hipMemcpyDeviceToHost);
     g_tbDevCache.park(dOut, dOutCap);
+    dpx_extension rec{};
+    if (e == hipSuccess && b->extFilled) e = hipMemcpy(&rec, b->dExt + pair * (sizeof rec / sizeof(int32_t)), sizeof rec, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail(e, "dpx_batch_matrix");
+    if (b->extFilled && rec.lastDiag < pd.m + pd.n) {
+        /* a z-dropped pair: k_zext_fill stopped on anti-diagonal lastDiag, and what the pool holds behind it is whatever was there before */
+        for (int i = 0; i <= pd.m; i++)
+            for (int j = std::max(rec.lastDiag - i + 1, 0); j <= pd.n; j++) out[(size_t)i * (size_t)(pd.n + 1) + (size_t)j] = 0;
+    }
     return DPX_OK;
+}
+
+int dpx_batch_set_extension(dpx_batch *b, int32_t zdrop, int32_t endBonus) {
+    if (!b || zdrop < -1 || zdrop > (1 << 30) || endBonus < -1 || endBonus > (1 << 30)) return DPX_ERR_INVALID;
+    if (b->prm.algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED;
+    int rc = bind_device(b->device);
+    if (rc != DPX_OK) return rc;
+    if ((zdrop >= 0 || endBonus >= 0) && !b->dExt && b->numPairs)
+        HIP_TRY(g_tbDevCache.take((void **)&b->dExt, b->numPairs * sizeof(dpx_extension), &b->dExtCap));
+    b->zdrop = zdrop;
+    b->endBonus = endBonus;
+    return DPX_OK;
+}
+
+int dpx_batch_extensions(dpx_batch *b, dpx_extension *out) {
+    if (!b || !out) return DPX_ERR_INVALID;
+    if (!b->filled) return DPX_ERR_NOT_FILLED;
+    if (!b->extFilled) return DPX_ERR_UNSUPPORTED;
+    int rc = bind_device(b->device);
+    if (rc != DPX_OK) return rc;
+    if (b->lastStream && b->lastStream != b->stream) HIP_TRY(hipStreamSynchronize(b->lastStream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (b->numPairs) HIP_TRY(hipMemcpy(out, b->dExt, b->numPairs * sizeof(dpx_extension), hipMemcpyDeviceToHost));
+    return check_guard(b);
 }
 
 /* ---- result text: device traceback -> per-pair block lengths -> exclusive scan -> packed blocks -> D2H of the real bytes ----
@@ -2267,6 +2312,7 @@ int dpx_batch_describe(dpx_batch *b, char *buf, size_t cap) {
                          : b->kernelAlgo == DPX_ALGO_ASW ? (b->lanePacked ? "k_asw_lanes" : "k_asw_fill")
                          : b->kernelAlgo == DPX_ALGO_ASG ? (b->lanePacked ? "k_asg_lanes" : "k_asg_fill")
                          : b->packed ? "k_linear_fill_pk" : b->lanesPk ? "k_linear_lanes_pk" : b->lanePacked ? "k_linear_lanes" : b->split ? "k_linear_split" : "k_linear_fill";
+    if (b->kernelAlgo == DPX_ALGO_BAXT && extension_on(b)) kernel = "k_zext_fill";
     if (b->dirs) kernel = b->kernelAlgo == DPX_ALGO_ANW ? "k_affine_dir" : b->kernelAlgo == DPX_ALGO_ASW ? "k_asw_dir" : b->kernelAlgo == DPX_ALGO_ASG ? "k_asg_dir" : "k_linear_dir";
     /* dtype = the arithmetic type of the kernel that fills (most of) the batch */
     int len = snprintf(buf, cap, "algo=%s kernel_algo=%s kernel=%s dtype=%s rows_per_lane=%d store=%d couples=%zu lane_pairs=%zu waves=%zu singles=%zu row_tags=%d seq_input=%s waves_per_workgroup=%u",
@@ -2279,6 +2325,8 @@ int dpx_batch_describe(dpx_batch *b, char *buf, size_t cap) {
                         is_banw_layout(b->kernelAlgo) ? (wave ? "k_banw_traceback_wave" : "k_banw_traceback")
                                                        : (wave ? "k_basw_traceback_wave" : "k_basw_traceback"));
     }
+    if (b->kernelAlgo == DPX_ALGO_BAXT && extension_on(b) && len > 0 && (size_t)len < cap)
+        len += snprintf(buf + len, cap - (size_t)len, " zdrop=%d end_bonus=%d", (int)b->zdrop, (int)b->endBonus);
     if (b->dirs && len > 0 && (size_t)len < cap) /* the code layout, and where the edge rows live */
         len += snprintf(buf + len, cap - (size_t)len, " matrix=dir4 dir_edges=%s dir_scratch_bytes=%zu", b->dirScratch ? "global" : "lds", b->dirScratch);
     if (b->dMat && len > 0 && (size_t)len < cap) { /* the matrix pool: how it was built, and the memset time of every candidate that was timed */

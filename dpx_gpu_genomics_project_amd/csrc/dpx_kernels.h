@@ -81,6 +81,15 @@ hipError_t dpx_launch_banw_traceback(const dpx_fill_args &a, int numPairs, int w
 /* banded affine extension (dpx_baxt_kernels.hip): the fill only -- the stored layout, the edge rule and the border rule are BANW's, so
  * dpx_launch_banw_export and dpx_launch_banw_traceback serve it (both walks start from endRow / endCol) */
 hipError_t dpx_launch_baxt_fill(const dpx_fill_args &a, int C, bool store, size_t ldsBytes, hipStream_t stream);
+/* BAXT in extension mode (dpx_zext_kernels.hip, k_zext_fill): k_baxt_fill's cells and stores with z-drop termination (zdrop >= 0), the
+ * best score of row m and the end-bonus choice (endBonus >= 0; -1 = off for either, not both).  `ext` is the device array of per-pair
+ * records, eight int32 each in dpx_extension's field order.  Export and walks are BANW's, as for dpx_launch_baxt_fill. */
+typedef struct dpx_zext_args {
+    dpx_fill_args f;
+    int32_t zdrop, endBonus;
+    int32_t *ext;
+} dpx_zext_args;
+hipError_t dpx_launch_zext_fill(const dpx_zext_args &a, int C, bool store, size_t ldsBytes, hipStream_t stream);
 hipError_t dpx_launch_unpack2(const uint32_t *packed, uint32_t alphabet, char *out, size_t numDwords, hipStream_t stream);
 hipError_t dpx_launch_prim_eval(const int32_t *op, const uint32_t *a, const uint32_t *b, const uint32_t *c, size_t count,
                                 uint32_t *res, uint32_t *pred, hipStream_t stream);

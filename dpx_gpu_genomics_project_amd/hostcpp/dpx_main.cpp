@@ -11,7 +11,7 @@
 // coordinates and the SAM CIGAR ('=' / 'X' ops; "-cigar M" merges them into 'M').  The lines are formatted on the host.
 //
 //   dpx_main -pairs <file> [-match 3] [-mismatch -1] [-open -2 | -gap -2] [-extend -1]
-//            [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band 128] [-batch N | -pool-gb 4] [-inflight K] [-tune 0|1] [-device 0] [-noprint] [-pack2] [-directions] [-cigar [M]] [-producer P] [-rank r -world w]
+//            [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band 128] [-batch N | -pool-gb 4] [-inflight K] [-tune 0|1] [-device 0] [-noprint] [-pack2] [-directions] [-cigar [M]] [-zdrop Z] [-endbonus E] [-producer P] [-rank r -world w]
 //
 // Batch size: by default from a matrix-pool BUDGET (-pool-gb, 4 GiB): as many pairs as fit the budget, at most 20000 (the
 // reference sizes its buffers once for BATCH_SIZE = 10000 reads of 150 bases, cuda/LNW/LinearNeedlemanWunschV9.cu:26-46,
@@ -56,12 +56,15 @@ struct InFlight { // one batch between dpx_batch_create and dpx_batch_destroy
 
 } // namespace
 
+static void usage() {
+    fprintf(stderr, "usage: dpx_main -pairs <InSeqFile> -match <matchWeight> -mismatch <mismatchWeight> -open <gapWeight> "
+                    "[-extend <gapExtend>] [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band <B>] [-batch <N>] [-device <D>] [-noprint] [-cigar [M]] "
+                    "[-zdrop <Z>] [-endbonus <E>] (BAXT only)\n");
+    exit(EXIT_FAILURE);
+}
+
 int main(int argc, char *argv[]) {
-    if (argc < 3) {
-        fprintf(stderr, "usage: dpx_main -pairs <InSeqFile> -match <matchWeight> -mismatch <mismatchWeight> -open <gapWeight> "
-                        "[-extend <gapExtend>] [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band <B>] [-batch <N>] [-device <D>] [-noprint] [-cigar [M]]\n");
-        exit(EXIT_FAILURE);
-    }
+    if (argc < 3) usage();
     const char *pairFileName = nullptr;
     int match = 3, mismatch = -1, gapOpen = -2, gapExtend = -1, band = 128, device = 0, rank = 0, world = 1;
     size_t batchSize = 0;     // 0: from the pool budget (the reference's BATCH_SIZE, V19.cu:9, assumes short reads)
@@ -71,6 +74,7 @@ int main(int argc, char *argv[]) {
     bool cigar = false;      // -cigar: records + CIGAR ops instead of the text pipeline
     unsigned cigarFlags = DPX_CIGAR_EXTENDED;
     bool directions = false; // -directions: batches keep 4-bit direction codes (DPX_KEEP_DIRECTIONS): int32 scores, a quarter of the pool per pair
+    int zdrop = -1, endBonus = -1; // -zdrop / -endbonus: BAXT's extension mode (dpx_batch_set_extension) on every batch; -1 = off
     int inflight = 3;      // batches on the device at a time (= matrix pools reserved)
     int tuneFlag = -1;     // -1: by the length of the job
     std::string algoName = "LSW";
@@ -96,6 +100,8 @@ int main(int argc, char *argv[]) {
             cigar = true;
             if (i + 1 < argc && !strcmp(argv[i + 1], "M")) { cigarFlags = DPX_CIGAR_M; i++; }
         }
+        else if (!strcmp(argv[i], "-zdrop")) zdrop = atoi(next("-zdrop"));
+        else if (!strcmp(argv[i], "-endbonus")) endBonus = atoi(next("-endbonus"));
         else if (!strcmp(argv[i], "-producer")) producerFlag = atoi(next("-producer"));
         else if (!strcmp(argv[i], "-inflight")) inflight = atoi(next("-inflight"));
         else if (!strcmp(argv[i], "-tune")) tuneFlag = atoi(next("-tune"));
@@ -110,6 +116,7 @@ int main(int argc, char *argv[]) {
     const int algo = algoName == "LNW" ? DPX_ALGO_LNW : algoName == "LSW" ? DPX_ALGO_LSW : algoName == "ANW" ? DPX_ALGO_ANW
                      : algoName == "BSW" ? DPX_ALGO_BSW : algoName == "ASW" ? DPX_ALGO_ASW : algoName == "BASW" ? DPX_ALGO_BASW : algoName == "ASG" ? DPX_ALGO_ASG : algoName == "BANW" ? DPX_ALGO_BANW : algoName == "BAXT" ? DPX_ALGO_BAXT : -1;
     if (algo < 0) { fprintf(stderr, "unknown -algo %s\n", algoName.c_str()); exit(EXIT_FAILURE); }
+    if ((zdrop != -1 || endBonus != -1) && algo != DPX_ALGO_BAXT) usage();
 
     printf("[Device Details]\n");
     int deviceCount = 0;
@@ -266,6 +273,7 @@ int main(int argc, char *argv[]) {
                         : dpx_batch_create(&prm, sequences, fileInfo.numBytes, reinterpret_cast<const dpx_seq_pair *>(sequenceIdxs), first, next.count,
                                            flags, &next.b);
         if (prc != DPX_OK) die("FAILED TO CREATE DEVICE BATCH", prc);
+        if ((zdrop != -1 || endBonus != -1) && (prc = dpx_batch_set_extension(next.b, zdrop, endBonus)) != DPX_OK) die("FAILED TO SET THE EXTENSION MODE", prc);
         create_time += get_time() - t0;
         if ((prc = dpx_batch_fill(next.b, nullptr)) != DPX_OK) die("KERNEL LAUNCH FAILED", prc);
         // global pair numbers: shardFirst + index inside the shard

@@ -152,8 +152,8 @@ typedef enum dpx_algo {
                          otherwise DPX_ERR_RANGE.
                          Matrices and DPX_SCORE_ONLY; DPX_KEEP_DIRECTIONS is DPX_ERR_UNSUPPORTED, as for the other banded
                          algorithms.  packed2 input, dpx_align_batch, the output pipeline, dpx_batch_create_on and a caller's stream
-                         as for BANW.  z-drop / x-drop termination and ksw2's "best score reaching the end of the query" are not
-                         provided.
+                         as for BANW.  z-drop termination, ksw2's "best score reaching the end of the query" and an end bonus are
+                         per-batch settings of this algorithm: dpx_batch_set_extension below.
                          Added without an ABI bump or a new symbol: a library that predates it returns DPX_ERR_INVALID for algo 10. */
 } dpx_algo;
 
@@ -367,6 +367,60 @@ int dpx_batch_cigars_end(dpx_batch *b, const dpx_alignment **records, const uint
  * NUL into out[0..cap); *len = its length without the NUL.  A cap too small returns DPX_ERR_INVALID with *len = the length needed;
  * an op code outside {0, 1, 2, 7, 8} returns DPX_ERR_INVALID. */
 int dpx_cigar_text(const uint32_t *ops, size_t numOps, char *out, size_t cap, size_t *len);
+
+/* ---- BAXT extension mode: z-drop termination, the query-end score and an end bonus -----------------------------------------
+ * What a read mapper's extension step needs beyond DPX_ALGO_BAXT: stop once the score has fallen far enough below its best (ksw2's
+ * zdrop, BWA-MEM's Z-dropoff), report the best score that reaches the END OF THE QUERY (ksw2's mqe / mqe_t, BWA's gscore / gtle),
+ * and choose between the clipped and the end-to-end alignment with an end bonus (minimap2's end_bonus, BWA's pen_clip).  Modelled on
+ * ksw2's extz2, NOT bit-compatible with it: the tie rules and the band definition are this library's.  No reference counterpart.
+ * Added without an ABI bump: detect the two functions by the exported symbol.  dpx_align_batch cannot set the values.
+ *
+ * Cells, band and borders are BAXT's, unchanged.  Two per-batch values: zdrop Z and endBonus E, each -1 = off or >= 0.
+ * Let pen = -gapExtend if gapExtend < 0, else 0.
+ * Scan: anti-diagonals a = i + j are visited in order a = 1, 2, ..., m + n.  cells(a) = the in-band cells of the matrix on a, border
+ * cells included; an empty cells(a) is skipped (every odd a when B = 1; every a past the band's reach).  dmax(a) = the maximum of H
+ * on a, (ia, ja) = the cell that holds it with the smallest row.  State best = 0, (bi, bj) = (0, 0).  For each non-empty a:
+ *     if dmax(a) > best:  best = dmax(a), (bi, bj) = (ia, ja)
+ *     else if Z >= 0 and ia >= bi and ja >= bj and best - dmax(a) > Z + pen * |(ia - bi) - (ja - bj)|:
+ *                         stop: lastDiag = a, the pair is z-dropped
+ * A pair that is not dropped has lastDiag = m + n.  The COMPUTED cells are the in-band cells with i + j <= lastDiag (the dropping
+ * anti-diagonal counts).  All results are taken over the computed cells only:
+ *     maxScore, (maxRow, maxCol)  BAXT's rule: the maximum of H and the first cell in row-major order that holds it; 0 at (0, 0)
+ *                                 when nothing is above 0.  maxScore == best; the cell may differ from (bi, bj) under ties, so
+ *                                 with Z = -1 these three are BAXT's results bit for bit.
+ *     qryEndScore, qryEndCol      the maximum of H[m][j] over the computed in-band cells of row m at the smallest such j (j = 0
+ *                                 takes part when (m, 0) is in the band; m = 0 makes this row 0).  When row m has no computed
+ *                                 in-band cell: DPX_EXT_NO_QUERY_END and -1.
+ *     choice                      if E >= 0, the pair is not z-dropped, row m was reached and qryEndScore + E > maxScore (strictly),
+ *                                 the pair REACHED THE END: the reported score is qryEndScore WITHOUT the bonus and the end cell is
+ *                                 (m, qryEndCol).  Otherwise the reported score and end cell are maxScore / (maxRow, maxCol).
+ *                                 E = 0 never flips a pair ("report only").
+ * The chosen score and end cell are what dpx_batch_results, dpx_batch_device_results, dpx_batch_traceback, the text pipeline and
+ * dpx_batch_cigars_* see; none of them changes otherwise (the walk from a computed cell only visits earlier anti-diagonals).  A
+ * reached-end score may be negative; the text block prints it, as BANW's does.
+ * dpx_batch_matrix: BAXT's export with every plane 0 where i + j > lastDiag.
+ * A Z below -(gapOpen + gapExtend) drops a perfect match: the odd anti-diagonal after a match cell peaks at best + gapOpen +
+ * gapExtend.  That is documented, not refused; a mapper's Z (hundreds) is far above it. */
+typedef struct dpx_extension {      /* 32 bytes */
+    int32_t  maxScore, maxRow, maxCol;
+    int32_t  qryEndScore, qryEndCol; /* DPX_EXT_NO_QUERY_END / -1 when row m was not reached */
+    int32_t  lastDiag;
+    uint32_t flags;                  /* DPX_EXT_ZDROPPED | DPX_EXT_REACHED_END */
+    int32_t  reserved;               /* 0 */
+} dpx_extension;
+
+#define DPX_EXT_ZDROPPED     0x1u
+#define DPX_EXT_REACHED_END  0x2u
+#define DPX_EXT_NO_QUERY_END INT32_MIN
+
+/* Legal any time after create; takes effect at the next fill (dpx_batch_fill, dpx_batch_fill_timed).  A batch of another algorithm:
+ * DPX_ERR_UNSUPPORTED; a value below -1 or above 1 << 30: DPX_ERR_INVALID.  (-1, -1) returns the batch to plain BAXT (k_baxt_fill).
+ * While either value is >= 0 the fill runs k_zext_fill and dpx_batch_describe adds `zdrop=` and `end_bonus=`.  Matrix and
+ * DPX_SCORE_ONLY batches, packed2 input, dpx_batch_create_on and a caller's stream as for BAXT. */
+int dpx_batch_set_extension(dpx_batch *b, int32_t zdrop, int32_t endBonus);
+/* numPairs records into host memory.  DPX_ERR_NOT_FILLED before a fill; DPX_ERR_UNSUPPORTED when the last fill ran without
+ * extension mode. */
+int dpx_batch_extensions(dpx_batch *b, dpx_extension *out);
 
 /* Sizes: numPairs, total cells (sum refLen*queryLen, the reference's numCells, c++/parseInput.cpp:100),
  * bytes of HBM the matrices occupy, algorithmic bytes of one fill. */
