@@ -2331,8 +2331,8 @@ int dpx_batch_describe(dpx_batch *b, char *buf, size_t cap) {
         len += snprintf(buf + len, cap - (size_t)len, " matrix=dir4 dir_edges=%s dir_scratch_bytes=%zu", b->dirScratch ? "global" : "lds", b->dirScratch);
     if (b->dMat && len > 0 && (size_t)len < cap) { /* the matrix pool: how it was built, and the memset time of every candidate that was timed */
         const PoolRecord &r = b->poolRec;
-        len += snprintf(buf + len, cap - (size_t)len, " pool=%s pool_bytes=%zu pool_chunk_mb=%zu pool_kept=%d pool_memset_ms=", r.mode.c_str(), b->matPoolBytes,
-                        r.chunkBytes >> 20, r.kept);
+        len += snprintf(buf + len, cap - (size_t)len, " pool=%s pool_bytes=%zu pool_addr=0x%llx pool_chunk_mb=%zu pool_kept=%d pool_memset_ms=", r.mode.c_str(), b->matPoolBytes,
+                        (unsigned long long)(uintptr_t)b->dMat, r.chunkBytes >> 20, r.kept);
         for (size_t k = 0; k < r.candidatesMs.size() && (size_t)len < cap; k++)
             len += snprintf(buf + len, cap - (size_t)len, "%s%.3f", k ? "," : "", r.candidatesMs[k]);
         if (r.candidatesMs.empty() && (size_t)len < cap) len += snprintf(buf + len, cap - (size_t)len, "untimed");
@@ -2348,7 +2348,7 @@ int dpx_batch_describe(dpx_batch *b, char *buf, size_t cap) {
             len += snprintf(buf + len, cap - (size_t)len, " pool_ranges=");
             for (size_t k = 0; k < r.ranges.size() && (size_t)len < cap; k++) len += snprintf(buf + len, cap - (size_t)len, "%s%s", k ? "," : "", r.ranges[k].c_str());
         }
-    }
+    } else if (!b->dMat && len > 0 && (size_t)len < cap) len += snprintf(buf + len, cap - (size_t)len, " pool_addr=0x0"); /* no pool: a score-only batch */
     return DPX_OK;
 }
 

@@ -430,7 +430,10 @@ int dpx_batch_info(dpx_batch *b, size_t *numPairs, uint64_t *cells, uint64_t *ma
  * rows_per_lane=16 store=1 couples=5000 lane_pairs=0 waves=0 singles=0 streams=0 row_tags=1 pool=vmm pool_bytes=22263365632
  * pool_chunk_mb=1024 pool_kept=0 pool_memset_ms=3.290` (pool_*: how the matrix pool was allocated -- `vmm` = a virtual range
  * backed by physical chunks, `malloc` = one hipMalloc -- and the hipMemset time of every candidate allocation that was timed,
- * `untimed` if none was; pool_kept indexes the one in use).  The reference prints its launch
+ * `untimed` if none was; pool_kept indexes the one in use).  `pool_addr=0x<hex>` follows pool_bytes: the device address of
+ * the block of pool_bytes bytes that holds the batch's matrices (a diagnostic: tests overwrite exactly that range between
+ * fills to show that no result depends on what it held); a batch without a pool (DPX_SCORE_ONLY) reports only
+ * `pool_addr=0x0`.  The longest line (a tuned pool's five candidates) stays below 1 KiB.  The reference prints its launch
  * geometry the same way (cuda/LNW/LinearNeedlemanWunschV19.cu:398-409); tests and bench.py read the kernel and the
  * arithmetic type from here instead of guessing the host's choice. */
 int dpx_batch_describe(dpx_batch *b, char *buf, size_t cap);

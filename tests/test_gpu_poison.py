@@ -1,0 +1,437 @@
+"""No result depends on what the matrix pool (or any other recycled buffer) held before a fill.
+
+The engine hands its device buffers from one batch to the next without clearing them, and every layout leaves cells that a fill does
+not write: stripe and lane-group padding, unused slots of the lane-packed tiles, cells outside a band, the unused nibble of a 4-bit
+direction code, everything behind lastDiag of a z-dropped pair.  The walks and export kernels load more than the cells on the path.
+Here every fill kernel, walk and export runs over a pool that tests/poison.py has overwritten with a pattern -- 0x00 (a fresh
+allocation), 0x7F (int16 32639: wins every max), 0x80 (-32640: loses every max, wraps on `- gap`), 0xFF (-1: every direction nibble
+and tag bit set) -- and everything the batch can give (results, extension records, every plane of every pair, every traceback, the
+text, the CIGARs under both flags) must equal the CPU oracle of the algorithm, bit for bit.  Each case fills twice: the second fill
+runs over a fresh pattern AND over what the first one left in the other buffers.  The ids name family, algorithm, kernel, R or band,
+walk and pattern.
+
+test_history_of_the_other_buffers covers the buffers without an address (arena, lines, text, CIGARs, extension records, pinned
+memory): a batch D of long high-scoring alignments runs to the end and is destroyed; a batch T with a byte-identical pair table but
+empty / pure-gap / early-dropped alignments then takes the same blocks (witnessed by the device pointers) and must equal the oracle.
+
+Every case prints how many int16 words still hold the pattern after its first fill (in the pool, and inside the matrices' own bytes)
+and asserts both above zero under 0x7F.  Measured on an MI355X, words left inside the matrices under 0x7F: k_linear_fill 355 578 ..
+3 105 232, k_linear_split 60 096 .. 298 368, k_linear_lanes 205 568, k_linear_lanes_pk 237 824, k_affine / k_asw / k_asg_fill 12 864 ..
+5 673 408, their _lanes kernels 223 488, the direction kernels' R2..above512 grids 27 648 .. 522 240, k_banded_fill 35 840 .. 3 903 488,
+k_banded_fill_pk 49 152 .. 5 679 104, k_basw / k_baxt_fill 107 520 .. 11 710 464, k_banw_fill 64 512 .. 9 302 016, k_zext_fill 374 784 ..
+4 225 536.  Three shapes write every word of their matrices (`dense`): the packed 8 x 1024 x 1024 batch and the direction batches
+with global edge rows and with the 1000 x 1000 pair; there the pattern survives only behind the matrices (251 904 .. 1 122 304 words)."""
+import zlib
+from dataclasses import dataclass, field
+
+import numpy as np
+import pytest
+
+import asg_ref
+import asw_ref
+import banw_ref
+import basw_ref
+import baxt_ref
+import cigar_ref as R
+import oracle_py as O
+import zext_ref
+from dpx_gpu_genomics_project_amd.synth import from_strings, make_batch, make_ragged_batch
+from poison import poison, pool_range, survivors
+
+pytestmark = pytest.mark.gpu
+
+LIN, AFF, HARSH = (3, -1, -2), (3, -1, -3, -1), (2, -3, -5, -1)
+CODE = {"LNW": 0, "LSW": 1, "ANW": 2, "BSW": 3, "ASW": 4, "BASW": 5, "ASG": 6, "BANW": 7, "BAXT": 10}
+PATTERNS = (0x00, 0x7F, 0x80, 0xFF)
+ACGT = np.frombuffer(b"ACGT", np.uint8)
+KNOBS = ("DPX_R", "DPX_PACKED", "DPX_LANES", "DPX_LANES_PK", "DPX_SPLIT", "DPX_ROW_TAGS", "DPX_RAMP_LINES", "DPX_WPB", "DPX_GROUP", "DPX_TB_WALK",
+         "DPX_POOL_PROBE", "DPX_POOL", "DPX_POOL_CHUNK_MB", "DPX_POOL_GUARD")
+NO_DROP = 1 << 30
+
+
+# ------------------------------------------------------------------------------------------------------------------- oracles
+
+@pytest.fixture(scope="module")
+def oracles(tmp_path_factory):
+    d = tmp_path_factory.mktemp("poison_oracles")
+    return {"ASW": asw_ref.build(d), "ASG": asg_ref.build(d), "BASW": basw_ref.build(d), "BANW": banw_ref.build(d), "BAXT": baxt_ref.build(d),
+            "ZEXT": zext_ref.build(d)}
+
+
+def _enc(lines):
+    return tuple(x.encode("latin-1") for x in lines)
+
+
+def _expect(orc, algo, ref, qry, w, band, ext):
+    """dict of one pair: score, end (row, col), planes (int32 arrays), dirs (uint8 arrays, unbanded only), lines (bytes), rec (extension)"""
+    m, n = len(qry), len(ref)
+    if algo in ("LSW", "BSW"):
+        o = O.lsw(ref, qry, *w[:3], band=band if algo == "BSW" else 0)
+        lines = (b"", b"", b"") if o.score == 0 else _enc(O.lsw_traceback(ref, qry, o))
+        return {"score": o.score, "end": (o.end_row, o.end_col), "planes": [o.H], "dirs": [o.dir], "lines": lines}
+    if algo == "LNW":
+        o = O.lnw(ref, qry, *w[:3])
+        return {"score": o.score, "end": (m, n), "planes": [o.H], "dirs": [o.dir], "lines": _enc(O.lnw_traceback(ref, qry, o))}
+    if algo == "ANW":
+        o = O.anw(ref, qry, *w)
+        return {"score": o.score, "end": (m, n), "planes": [o.H, o.I, o.D], "dirs": [o.dirH, o.dirI, o.dirD], "lines": _enc(O.anw_traceback(ref, qry, o))}
+    if ext is not None:
+        r = orc["ZEXT"].align(ref, qry, *w, band, *ext)
+    elif algo in ("ASW", "ASG"):
+        r = orc[algo].align(ref, qry, *w)
+    elif algo == "BASW":
+        r = orc[algo].align(ref, qry, *w, band)
+    else:
+        r = orc[algo].align(ref, qry, *w, band, raw=False)
+    return {"score": r["score"], "end": tuple(r["end"]), "planes": [r["H"], r["I"], r["D"]], "dirs": [r.get("dirH"), r.get("dirI"), r.get("dirD")],
+            "lines": r["lines"], "rec": r.get("rec")}
+
+
+_WANT = {}
+
+
+def _want(orc, algo, sb, w, band, ext):
+    """the oracle's results of a batch, computed once and shared by every walk, knob and pattern; nothing modifies them"""
+    key = (algo, zlib.crc32(sb.sequences.tobytes()), zlib.crc32(sb.pairs.tobytes()), tuple(w), band, ext)
+    if key not in _WANT:
+        _WANT[key] = [_expect(orc, algo, sb.ref(p), sb.qry(p), w, band, ext) for p in range(sb.num_pairs)]
+    return _WANT[key]
+
+
+def _read_and_compare(gpu, b, want, dirs, ext, what):
+    """everything the filled batch `b` can give against `want`"""
+    scores, rows, cols = b.results()
+    for p, r in enumerate(want):
+        assert (int(scores[p]), (int(rows[p]), int(cols[p]))) == (r["score"], r["end"]), (what, p, "score / end cell")
+    if ext is not None:
+        recs = b.extensions()
+        for p, r in enumerate(want):
+            assert {k: int(recs[k][p]) for k in zext_ref.FIELDS} == r["rec"], (what, p, "extension record")
+    for p, r in enumerate(want):
+        for which in range(len(r["planes"])):
+            got = b.directions(p, which) if dirs else b.matrix(p, which).astype(np.int32)
+            ref = r["dirs"][which] if dirs else r["planes"][which]
+            assert np.array_equal(got, ref), (what, p, "plane", which, np.argwhere(got != ref)[:4].tolist())
+    for p, r in enumerate(want):
+        assert _enc(b.traceback(p)) == r["lines"], (what, p, "traceback")
+    b.output_begin(5)
+    text, offs = b.output_end()
+    blocks = [b"%d | %d\n" % (5 + p, r["score"]) + b"".join(x + b"\n" for x in r["lines"]) for p, r in enumerate(want)]
+    assert text == b"".join(blocks), (what, "text")
+    assert offs.tolist() == np.concatenate([[0], np.cumsum([len(x) for x in blocks])]).tolist(), (what, "text offsets")
+    for flags in (R.FLAG_EXTENDED, R.FLAG_M):
+        b.cigars_begin(flags)
+        recs, ops = b.cigars_end()
+        wrecs, wops = R.batch([r["lines"] for r in want], [r["end"][0] for r in want], [r["end"][1] for r in want], flags)
+        assert ops.tolist() == wops, (what, "CIGAR ops", flags)
+        for p, wr in enumerate(wrecs):
+            assert {k: int(recs[k][p]) for k in wr} == wr, (what, p, "CIGAR record", flags)
+
+
+# --------------------------------------------------------------------------------------------------------------------- batches
+
+def _related(rng, m, n):
+    """a random reference of n bases; the query copies its start with 10 % substitutions (a random tail where it is longer)"""
+    ref = ACGT[rng.integers(0, 4, n)]
+    q = ACGT[rng.integers(0, 4, m)]
+    k = min(m, n)
+    q[:k] = ref[:k]
+    sub = rng.random(m) < 0.10
+    q[sub] = ACGT[rng.integers(0, 4, int(sub.sum()))]
+    return ref.tobytes(), q.tobytes()
+
+
+def _window(rng, m, n):
+    """a query that is a mutated window of its reference"""
+    ref = ACGT[rng.integers(0, 4, n)]
+    start = int(rng.integers(0, max(n - m, 0) + 1))
+    q = np.concatenate([ref[start:start + m], ACGT[rng.integers(0, 4, max(m - (n - start), 0))]])[:m].copy()
+    sub = rng.random(m) < 0.12
+    q[sub] = ACGT[rng.integers(0, 4, int(sub.sum()))]
+    return ref.tobytes(), q.tobytes()
+
+
+def _shapes(seed, shapes, make=_related):
+    rng = np.random.default_rng(seed)
+    return from_strings([make(rng, m, n) for m, n in shapes])
+
+
+def _linear_ragged(r):
+    """short pairs next to long ones in one launch: one row, one column, empty sequences, one lane, one stripe less a row, a stripe
+    plus a row, two stripes and a bit"""
+    return _shapes(10 + r, [(1, 1), (0, 5), (5, 0), (3, 70), (63, 64), (64 * r - 1, 100), (64 * r + 1, 67), (2 * 64 * r + 5, 130)])
+
+
+def _affine_ragged(seed, mq, nr):
+    """6 ragged pairs with one empty reference and one empty query, and a pair without a common base (score 0 under ASW: an empty
+    alignment over whatever the line buffers held)"""
+    rng = np.random.default_rng(seed)
+    texts = [_window(rng, int(rng.integers(mq[0], mq[1] + 1)), int(rng.integers(nr[0], nr[1] + 1))) for _ in range(6)]
+    texts[1] = (b"", texts[1][1])
+    texts[2] = (texts[2][0], b"")
+    texts.insert(4, (b"AAAA", b"CCCC"))
+    return from_strings(texts)
+
+
+def _dir_grid(seed, ms):
+    return _shapes(seed, [(m, n) for m in ms for n in (1, 2, 63, 64, 65, 129)], make=_window)
+
+
+def _dir_global(nedges):
+    """3 pairs whose edge rows (int32 rows of n + 2 and the staged reference) no longer fit 64 KiB of LDS"""
+    def per_wave(n):
+        return nedges * (((n + 2) * 4 + 15) // 16 * 16) + (n + 192 + 15) // 16 * 16
+    n = next(x for x in range(1000, 20000) if per_wave(x) > 64 * 1024)
+    ref = ACGT[np.random.default_rng(83).integers(0, 4, n)]
+    return from_strings([(ref.tobytes(), ref[n - 40:].tobytes()), (ref.tobytes(), ref[100:170].tobytes()), (ref[:n - 1].tobytes(), ref[n // 2:n // 2 + 30].tobytes())])
+
+
+def _band_batch(algo, band, couples=False):
+    """one-cell matrices, one row, one column, empty sequences, |m - n| >= B, a pair that leaves the head phase, and shifted copies
+    whose path runs along the band's edge.  BANW admits |m - n| < B only.  `couples`: every shape twice (the packed kernel pairs them)"""
+    rng = np.random.default_rng(2000 + band)
+    long_m, long_n = min(2 * band + 9, 700), min(2 * band + 3, 690)
+    if algo == "BANW":
+        d, e = min(band - 1, 30), min(band - 1, 5)
+        shapes = [(1, 1), (40, 40 - d), (40 - d, 40), (0, e), (e, 0), (long_m, long_m - min(band - 1, 6))]
+    else:
+        shapes = [(1, 1), (1, 40), (40, 1), (0, 5), (5, 0), (band + 5, 3), (3, band + 5), (long_m, long_n)]
+    texts = [_related(rng, m, n) for m, n in shapes]
+    core = ACGT[rng.integers(0, 4, min(2 * band + 40, 300))].tobytes()
+    shift = min(band - 1, 40)
+    texts += [(core[shift:], core), (core, core[shift:])]
+    if couples:
+        texts += [_related(rng, len(q), len(r)) for r, q in texts]
+    return from_strings(texts)
+
+
+def _cliff(rng, prefix, tail):
+    """an identical prefix, then `tail` bases that never match: the score falls off a cliff right behind the prefix"""
+    pre = ACGT[rng.integers(0, 4, prefix)].tobytes()
+    return pre + b"A" * tail, pre + b"C" * tail
+
+
+def _near_end(rng, m=60, n=80):
+    """the query is the reference's first m bases with substitutions at m-2, m-4 and m-6: the end bonus flips the chosen end"""
+    ref = rng.integers(0, 4, n)
+    q = ref[:m].copy()
+    for k in (m - 2, m - 4, m - 6):
+        q[k] = (q[k] + 1 + rng.integers(0, 3)) % 4
+    return ACGT[ref].tobytes(), ACGT[q].tobytes()
+
+
+def _ext_batch(band):
+    """cliffs at the start, far inside and 2..9 bases before the end (tests/test_gpu_zext.py), and the near-end pairs"""
+    rng = np.random.default_rng(500 + band)
+    size = 2 * band + 120
+    texts = [_cliff(rng, p, size) for p in (0, 1, 3)] + [_cliff(rng, band + 30 + k, band + 50) for k in range(2)]
+    texts += [_cliff(rng, band + 30 + (t & 1), t) for t in range(2, 10)] + [_near_end(rng) for _ in range(3)]
+    return from_strings(texts)
+
+
+_SB = {}
+
+
+def _batch_of(key, build):
+    if key not in _SB:
+        _SB[key] = build()
+    return _SB[key]
+
+
+# ----------------------------------------------------------------------------------------------------------------------- cases
+
+@dataclass
+class Case:
+    id: str
+    algo: str
+    kernel: str
+    w: tuple
+    build: object                      # () -> SynthBatch
+    band: int = 0
+    env: dict = field(default_factory=dict)
+    dirs: bool = False
+    rows_per_lane: int = 0             # asserted where the case pins it
+    ext: tuple = None                  # (Z, E): the fills run NO_DROP first, then Z on the same batch without a new pattern
+    walks: tuple = ("default", "0")
+    describe: dict = field(default_factory=dict)
+    dense: bool = False                # the fill writes every word of its matrices: survivors are asserted in the whole pool only
+
+
+def _cases():
+    out = []
+    # linear, one wave per pair
+    for algo in ("LSW", "LNW"):
+        for r in (2, 4, 8, 16):
+            for tag, extra in (("", {}), ("-ramp", {"DPX_RAMP_LINES": "1"}), ("-wpb4", {"DPX_WPB": "4"})):
+                out.append(Case(f"linear-{algo}-k_linear_fill-R{r}{tag}", algo, "k_linear_fill", LIN, lambda r=r: _linear_ragged(r),
+                                env={"DPX_SPLIT": "0", "DPX_R": str(r), **extra}, rows_per_lane=r,
+                                walks=("default", "0", "1") if r >= 8 else ("default", "0")))
+    # linear, other layouts
+    for algo in ("LSW", "LNW"):
+        for m, n in ((600, 500), (200, 330)):
+            out.append(Case(f"linear-{algo}-k_linear_split-{m}x{n}", algo, "k_linear_split", LIN, lambda m=m, n=n: make_batch(3, m, n, seed=m, first_index=95)))
+        ragged = lambda: make_ragged_batch(40, 1, 256, 1, 260, seed=40)
+        out.append(Case(f"linear-{algo}-k_linear_lanes_pk-ragged40", algo, "k_linear_lanes_pk", LIN, ragged, env={"DPX_LANES": "1"}))
+        out.append(Case(f"linear-{algo}-k_linear_lanes-ragged40", algo, "k_linear_lanes", LIN, ragged, env={"DPX_LANES": "1", "DPX_LANES_PK": "0"}))
+        out.append(Case(f"linear-{algo}-k_linear_fill_pk-8x1024x1024", algo, "k_linear_fill_pk", LIN, lambda: make_batch(8, 1024, 1024, seed=1, first_index=95),
+                        env={"DPX_PACKED": "1"}, describe={"couples": 4, "singles": 0},
+                        dense=True))  # 1024 rows = 64 lanes x 16 rows and whole chunks: no word of the matrices stays unwritten
+    # affine, three planes
+    paths = [("2", (60, 128), (50, 200), "single"), ("4", (129, 256), (100, 300), "single"), ("8", (257, 512), (200, 600), "single"),
+             ("2", (300, 600), (20, 120), "striped"), ("4", (300, 600), (20, 120), "striped"),
+             ("2", (300, 700), (128, 400), "rolling"), ("8", (600, 1100), (128, 300), "rolling")]
+    for algo, kernel in (("ANW", "k_affine"), ("ASW", "k_asw"), ("ASG", "k_asg")):
+        for r, mq, nr, path in paths:
+            out.append(Case(f"affine-{algo}-{kernel}_fill-R{r}-{path}", algo, f"{kernel}_fill", AFF,
+                            lambda r=r, mq=mq, nr=nr: _affine_ragged(zlib.crc32(f"{r}{mq}{nr}".encode()), mq, nr), env={"DPX_R": r}, rows_per_lane=int(r)))
+        out.append(Case(f"affine-{algo}-{kernel}_lanes-n90", algo, f"{kernel}_lanes", AFF,
+                        lambda: _shapes(90, [(m, 90) for m in (1, 7, 8, 9, 15, 16, 17, 63, 64, 65)], make=_window), env={"DPX_LANES": "1"}))
+    out.append(Case("affine-ASG-k_asg_fill-column0-winner", "ASG", "k_asg_fill", (1, -10, -3, -1), lambda: from_strings([(b"0000", b"1111")])))
+    # directions (one walk kernel: DPX_TB_WALK does not apply)
+    for algo, kernel, w, nedges in (("LSW", "k_linear_dir", LIN, 1), ("LNW", "k_linear_dir", LIN, 1), ("ANW", "k_affine_dir", AFF, 2),
+                                    ("ASW", "k_asw_dir", AFF, 2), ("ASG", "k_asg_dir", AFF, 2)):
+        for tag, ms in (("R2", (1, 128)), ("R4", (1, 128, 129, 256)), ("R8", (1, 257, 512)), ("above512", (1, 512, 513))):
+            out.append(Case(f"directions-{algo}-{kernel}-{tag}", algo, kernel, w, lambda tag=tag, ms=ms: _dir_grid(zlib.crc32(tag.encode()), ms), dirs=True,
+                            rows_per_lane={"R2": 2, "R4": 4, "R8": 8}.get(tag, 0), walks=("default",), describe={"dir_edges": "lds"}))
+        # (these two write whole code chunks -- the few pattern words seen inside them are written codes that look like the pattern -- and
+        #  leave the pattern in the edge-row scratch and the allocation's headroom only)
+        out.append(Case(f"directions-{algo}-{kernel}-global-edges", algo, kernel, w, lambda nedges=nedges: _dir_global(nedges), dirs=True, walks=("default",),
+                        describe={"dir_edges": "global"}, dense=True))
+        big = (40,) + tuple(w[1:])  # score 40 000: past int16, the int32 score path
+        out.append(Case(f"directions-{algo}-{kernel}-int32-1000x1000", algo, kernel, big, lambda: from_strings([(b"A" * 1000, b"A" * 1000)]), dirs=True,
+                        walks=("default",), dense=True))
+    # banded
+    for band in (1, 2, 17, 64, 65, 129, 257):
+        cpl = 1 if band <= 64 else 2 if band <= 128 else 4 if band <= 256 else 8
+        out.append(Case(f"banded-BSW-k_banded_fill-B{band}", "BSW", "k_banded_fill", LIN, lambda band=band: _band_batch("BSW", band), band=band, rows_per_lane=cpl))
+        out.append(Case(f"banded-BSW-k_banded_fill_pk-B{band}", "BSW", "k_banded_fill_pk", LIN, lambda band=band: _band_batch("BSW", band, couples=True), band=band,
+                        env={"DPX_PACKED": "1"}, rows_per_lane=cpl))
+        for algo, kernel in (("BASW", "k_basw_fill"), ("BANW", "k_banw_fill"), ("BAXT", "k_baxt_fill")):
+            out.append(Case(f"banded-{algo}-{kernel}-B{band}", algo, kernel, HARSH if algo == "BAXT" else AFF, lambda algo=algo, band=band: _band_batch(algo, band),
+                            band=band, rows_per_lane=cpl))
+    # extension mode
+    for band in (1, 17, 64, 129):
+        cpl = 1 if band <= 64 else 2 if band <= 128 else 4
+        for z in (6, 20):
+            for e in (-1, 5):
+                out.append(Case(f"extension-BAXT-k_zext_fill-B{band}-Z{z}-E{e}", "BAXT", "k_zext_fill", HARSH, lambda band=band: _ext_batch(band), band=band,
+                                rows_per_lane=cpl, ext=(z, e)))
+    return out
+
+
+CASES = _cases()
+PARAMS = [pytest.param(c, walk, pattern, id=f"{c.id}-walk_{walk}-0x{pattern:02X}") for c in CASES for walk in c.walks for pattern in PATTERNS]
+
+
+@pytest.mark.parametrize("case,walk,pattern", PARAMS)
+def test_results_do_not_depend_on_the_pool(gpu, oracles, monkeypatch, capsys, case, walk, pattern):
+    for k in KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in case.env.items():
+        monkeypatch.setenv(k, v)
+    if walk != "default":
+        monkeypatch.setenv("DPX_TB_WALK", walk)
+    sb = _batch_of(case.id, case.build)
+    # (poison?, extension): two fills over a fresh pattern; extension mode puts a complete, higher-scoring matrix behind lastDiag first
+    steps = [(True, None), (True, None)] if case.ext is None else [(True, (NO_DROP, case.ext[1])), (False, case.ext), (True, case.ext)]
+    flags = gpu.KEEP_DIRECTIONS if case.dirs else gpu.KEEP_MATRICES
+    with gpu.Batch(CODE[case.algo], sb.sequences, sb.pairs, *case.w, band=case.band, flags=flags) as b:
+        for k, (fresh_pattern, ext) in enumerate(steps):
+            if ext is not None:
+                b.set_extension(*ext)
+            d = b.describe()
+            assert d["algo"] == case.algo and d["kernel"] == case.kernel, d
+            assert not case.rows_per_lane or d["rows_per_lane"] == case.rows_per_lane, d
+            assert all(d[key] == v for key, v in case.describe.items()), d
+            if ext is not None:
+                assert (d["zdrop"], d["end_bonus"]) == ext, d
+            if "traceback" in d:
+                assert d["traceback"].endswith("_wave") == (walk == "default"), d
+            want = _want(oracles, case.algo, sb, case.w, case.band, ext)
+            if fresh_pattern:
+                poison(b, pattern)
+            b.fill()
+            if k == 0:
+                b.sync()
+                left, inside = survivors(b, pattern), survivors(b, pattern, first_bytes=min(b.info()["matrix_bytes"], pool_range(b)[1]))
+                with capsys.disabled():
+                    print(f"\nsurvivors {case.id} walk={walk} 0x{pattern:02X}: {left} words of {d['pool_bytes'] // 2} in the pool, {inside} inside the matrices", end="")
+                if pattern == 0x7F:  # the engine does not clear the pool itself, and the layout leaves cells unwritten: the case is not vacuous
+                    assert left > 0 and (inside > 0 or case.dense), (case.id, left, inside)
+            _read_and_compare(gpu, b, want, case.dirs, ext, (case.id, walk, hex(pattern), "fill", k))
+        if case.ext is not None:
+            dropped = [r["rec"]["flags"] & zext_ref.ZDROPPED for r in _want(oracles, case.algo, sb, case.w, case.band, case.ext)]
+            assert any(dropped), (case.id, "no pair drops")
+
+
+# --------------------------------------------------------------------------------------- the buffers that have no address
+
+HISTORY = {  # family: (algorithm, band, directions, D's extension, T's extension)
+    "linear-LSW": ("LSW", 0, False, None, None), "linear-LNW": ("LNW", 0, False, None, None),
+    "affine-ANW": ("ANW", 0, False, None, None), "affine-ASW": ("ASW", 0, False, None, None), "affine-ASG": ("ASG", 0, False, None, None),
+    "directions-LSW": ("LSW", 0, True, None, None), "directions-ASW": ("ASW", 0, True, None, None),
+    "banded-BSW": ("BSW", 17, False, None, None), "banded-BASW": ("BASW", 17, False, None, None), "banded-BANW": ("BANW", 17, False, None, None),
+    "banded-BAXT": ("BAXT", 17, False, None, None), "extension-BAXT": ("BAXT", 17, False, (NO_DROP, 5), (6, -1)),
+}
+HISTORY_SHAPES = [(1, 1), (0, 4), (4, 0), (5, 5), (64, 64), (65, 63), (130, 129), (200, 200), (37, 37), (255, 250)]  # |m - n| < 17: BANW admits them
+
+
+def _history_batches():
+    """D: identical sequences, or a query that alternates against a reference of A (one CIGAR op per column).  T: disjoint alphabets."""
+    rng = np.random.default_rng(1234)
+    dtexts, ttexts = [], []
+    for k, (m, n) in enumerate(HISTORY_SHAPES):
+        if k % 2:
+            s = ACGT[rng.integers(0, 4, max(m, n))].tobytes()
+            dtexts.append((s[:n], s[:m]))
+        else:
+            dtexts.append((b"A" * n, (b"AC" * m)[:m]))
+        ttexts.append((np.frombuffer(b"AC", np.uint8)[rng.integers(0, 2, n)].tobytes(), np.frombuffer(b"GT", np.uint8)[rng.integers(0, 2, m)].tobytes()))
+    return from_strings(dtexts), from_strings(ttexts)
+
+
+def _run_to_the_end(b, ext):
+    b.fill()
+    b.output_begin(5)
+    b.output_end()
+    for flags in (R.FLAG_EXTENDED, R.FLAG_M):
+        b.cigars_begin(flags)
+        b.cigars_end()
+    if ext is not None:
+        b.extensions()
+    return b.device_results(), b.describe()["pool_addr"]
+
+
+@pytest.mark.parametrize("family", list(HISTORY))
+def test_history_of_the_other_buffers(gpu, oracles, monkeypatch, family):
+    for k in KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    algo, band, dirs, dext, text_ext = HISTORY[family]
+    dsb, tsb = _history_batches()
+    assert dsb.pairs.tobytes() == tsb.pairs.tobytes() and dsb.sequences.size == tsb.sequences.size
+    linear = algo in ("LSW", "LNW", "BSW")
+    dw, tw = ((20, -1, -2), HARSH[:3]) if linear else ((20, -1, -3, -1), HARSH)
+    flags = gpu.KEEP_DIRECTIONS if dirs else gpu.KEEP_MATRICES
+    lib = gpu.load()
+    lib.dpx_shutdown(); gpu.init(0)                                  # nothing parked: D allocates every buffer afresh, T finds D's
+    try:
+        with gpu.Batch(CODE[algo], dsb.sequences, dsb.pairs, *dw, band=band, flags=flags) as d:
+            if dext is not None:
+                d.set_extension(*dext)
+            dwant = _want(oracles, algo, dsb, dw, band, dext)
+            assert sum(len(r["lines"][1]) for r in dwant) >= sum(min(m, n) - 1 for m, n in HISTORY_SHAPES)   # long alignments ...
+            assert dext is None or not any(r["rec"]["flags"] & zext_ref.ZDROPPED for r in dwant)        # ... and no drop
+            dptrs, daddr = _run_to_the_end(d, dext)
+        with gpu.Batch(CODE[algo], tsb.sequences, tsb.pairs, *tw, band=band, flags=flags) as t:
+            if text_ext is not None:
+                t.set_extension(*text_ext)
+            want = _want(oracles, algo, tsb, tw, band, text_ext)
+            if algo in ("LSW", "BSW", "ASW", "BASW"):
+                assert all(r["lines"] == (b"", b"", b"") for r in want)                                  # empty local alignments
+            if text_ext is not None:
+                assert sum(bool(r["rec"]["flags"] & zext_ref.ZDROPPED) for r in want) >= 5
+            tptrs, taddr = _run_to_the_end(t, text_ext)
+            assert tptrs == dptrs and taddr == daddr and int(str(taddr), 16), (family, dptrs, tptrs, daddr, taddr)   # T took D's blocks
+            _read_and_compare(gpu, t, want, dirs, text_ext, (family, "T after D"))
+    finally:
+        lib.dpx_shutdown(); gpu.init(0)
