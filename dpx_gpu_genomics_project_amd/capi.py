@@ -34,6 +34,7 @@ ABI_SYMBOLS = (
     "dpx_batch_output_begin", "dpx_batch_output_end", "dpx_batch_output_take", "dpx_text_free",
     "dpx_batch_info", "dpx_batch_describe", "dpx_batch_destroy", "dpx_align_batch", "dpx_prim_eval", "dpx_batch_directions",
     "dpx_batch_cigars_begin", "dpx_batch_cigars_end", "dpx_cigar_text", "dpx_batch_set_extension", "dpx_batch_extensions",
+    "dpx_batch_set_substitution",
 )
 # declared entry points a library may lack and still load (an older build): checked when they are called
 OPTIONAL_SYMBOLS = ("dpx_batch_directions",)
@@ -124,6 +125,7 @@ def load() -> C.CDLL:
     lib.dpx_cigar_text.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.dpx_batch_set_extension.argtypes = [vp, C.c_int32, C.c_int32]
     lib.dpx_batch_extensions.argtypes = [vp, vp]
+    lib.dpx_batch_set_substitution.argtypes = [vp, vp, C.c_int32, vp]
     for name in ABI_SYMBOLS:  # every declared entry point must be exported (the optional ones by libraries that have them)
         if name not in OPTIONAL_SYMBOLS:
             getattr(lib, name)
@@ -276,6 +278,24 @@ class Batch:
         """BAXT only: z-drop threshold and end bonus of the following fills (-1 = off; both off = plain BAXT)."""
         _check(self._lib.dpx_batch_set_extension(self._h, zdrop, end_bonus), "dpx_batch_set_extension")
 
+    def set_substitution(self, scores, code_of=None) -> None:
+        """BANW / BAXT only: score columns by scores[code_of[ref byte], code_of[qry byte]] in the following fills.
+
+        `scores` is an int8 array of shape (A, A), 1 <= A <= 32, `code_of` 256 uint8 values below A (see code_table).  None clears the
+        table.  Lines and results of an earlier fill are invalid afterwards."""
+        if scores is None:
+            _check(self._lib.dpx_batch_set_substitution(self._h, None, 0, None), "dpx_batch_set_substitution")
+            return
+        tab = np.ascontiguousarray(scores, dtype=np.int8)
+        if tab.ndim != 2 or tab.shape[0] != tab.shape[1] or not np.array_equal(tab, np.asarray(scores)):
+            raise ValueError("scores must be a square matrix of int8 values")
+        if code_of is None:
+            raise ValueError("code_of is required with a table")
+        code = np.ascontiguousarray(code_of, dtype=np.uint8)
+        if code.shape != (256,) or not np.array_equal(code, np.asarray(code_of).reshape(-1)):
+            raise ValueError("code_of must hold 256 values in 0..255")
+        _check(self._lib.dpx_batch_set_substitution(self._h, tab.ctypes.data, tab.shape[0], code.ctypes.data), "dpx_batch_set_substitution")
+
     def extensions(self) -> np.ndarray:
         """One EXTENSION_DTYPE record per pair of the last fill, which must have run in extension mode."""
         out = np.zeros(self.num_pairs, EXTENSION_DTYPE)
@@ -312,6 +332,23 @@ class Batch:
             self.close()
         except Exception:
             pass
+
+
+def code_table(alphabet: bytes, fold_case: bool = True) -> np.ndarray:
+    """The 256-entry byte -> code map of Batch.set_substitution for `alphabet`: letter k gets code k, every unlisted byte the code of the
+    LAST letter ('N' of b"ACGTN", '*' of an NCBI protein alphabet).  fold_case: a lower-case byte takes its upper-case letter's code."""
+    letters = bytes(alphabet)
+    if not 1 <= len(letters) <= 32 or len(set(letters)) != len(letters):
+        raise ValueError("alphabet must hold 1..32 distinct bytes")
+    code = np.full(256, len(letters) - 1, np.uint8)
+    for k, ch in enumerate(letters):
+        code[ch] = k
+    if fold_case:
+        for lo in range(ord("a"), ord("z") + 1):
+            up = lo - 32
+            if lo not in letters and up in letters:
+                code[lo] = code[up]
+    return code
 
 
 def cigar_text(ops) -> str:

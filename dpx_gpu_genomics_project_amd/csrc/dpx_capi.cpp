@@ -556,6 +556,10 @@ struct dpx_batch {
     bool extFilled = false;    /* the last fill ran k_zext_fill: dExt holds its records and dpx_batch_matrix masks behind lastDiag */
     int32_t *dExt = nullptr;   /* device: dpx_extension[numPairs] */
     size_t dExtCap = 0;
+    /* substitution table (dpx_batch_set_substitution): while substAlphabet > 0 the fills run k_subst_fill and the walks k_subst_traceback* */
+    int substAlphabet = 0;
+    unsigned char *dSubst = nullptr; /* device: the table at row stride 32 (DPX_SUBST_TABLE_BYTES), then codeOf[256] */
+    size_t dSubstCap = 0;
     size_t nSingles = 0, nCouples = 0, nLanePairs = 0, nWaves = 0; /* launch-list sizes (dpx_batch_describe) */
     PoolRecord poolRec;    /* how the matrix pool behind dMat was built / timed */
     bool tunePool = false, tuneShop = false; /* DPX_TUNE_PLACEMENT: the pool is timed / shopped for at the end of dpx_batch_create */
@@ -786,7 +790,10 @@ static bool fits_int16(const dpx_params &p, long long m, long long n) {
          * the path (diagonal to (k, k), then one gap of |i - j| <= B - 1 steps) reaches every in-band cell of any m x n matrix and stays
          * in the band, and hiH holds for every path.  So the same bounds hold for every in-band H, I and D, and the score, a maximum of
          * H values and the 0 of (0, 0), lies in [0, hiH].  k_baxt_fill keeps a signed (H << 16 | 0xFFFF - step) key per slot: H inside
-         * int16 is this check, and the step index m + n must fit 16 bits (the same 65000 as BASW's keys). */
+         * int16 is this check, and the step index m + n must fit 16 bits (the same 65000 as BASW's keys).
+         * Under a substitution table (dpx_batch_set_substitution) the caller passes the largest table entry as `match` and the smallest
+         * as `mismatch`, and the proofs carry over word for word: a diagonal step scores at least the minimum entry and at most the
+         * maximum, which is all that w and `diag` use. */
         const long long o = p.gapOpen, e = p.gapExtend, g = std::min<long long>(std::max<long long>(p.band - 1, 0), std::max(m, n));
         const long long loH = neg(std::min<long long>(p.match, p.mismatch)) * std::min(m, n) + neg(o) + neg(e) * g;
         const long long hiH = diag + (pos(o) + pos(e)) * (m + n);
@@ -1052,6 +1059,7 @@ int dpx_batch_destroy(dpx_batch *b) {
     g_tbHostCache.park(b->hCigar, b->hCigarCap);
     g_tbHostCache.park(b->hCigarOps, b->hCigarOpsCap);
     g_tbDevCache.park(b->dExt, b->dExtCap);
+    g_tbDevCache.park(b->dSubst, b->dSubstCap);
     g_stageCache.park(b->hStage, b->hStageCap);
     delete b;
     trace.mark("destroy");
@@ -1737,7 +1745,17 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
  * looks like one operation (events recorded on `s` around it time all of it). */
 static bool extension_on(const dpx_batch *b) { return b->zdrop >= 0 || b->endBonus >= 0; }
 
+/* the batch's launch arguments under its substitution table: every wave's LDS slice grows by the table image */
+static dpx_subst_args subst_args(const dpx_batch *b) {
+    dpx_subst_args sa = {b->args, reinterpret_cast<const int8_t *>(b->dSubst), b->dSubst + DPX_SUBST_TABLE_BYTES};
+    sa.f.ldsPerWave += DPX_SUBST_IMAGE_BYTES;
+    return sa;
+}
+static size_t subst_lds_bytes(const dpx_batch *b) { return b->ldsBytes + (size_t)DPX_SUBST_IMAGE_BYTES * (DPX_FILL_THREADS / 64); }
+
 static hipError_t launch_main(dpx_batch *b, hipStream_t s) { /* the one-wave-per-pair kernel of the batch's algorithm */
+    if (b->substAlphabet) /* (set only on batches whose kernel is BANW's or BAXT's, extension mode off) */
+        return dpx_launch_subst_fill(subst_args(b), b->R, b->store, b->kernelAlgo == DPX_ALGO_BAXT, subst_lds_bytes(b), s);
     if (b->kernelAlgo == DPX_ALGO_BASW) return dpx_launch_basw_fill(b->args, b->R, b->store, b->ldsBytes, s);
     if (b->kernelAlgo == DPX_ALGO_BANW) return dpx_launch_banw_fill(b->args, b->R, b->store, b->ldsBytes, s);
     if (b->kernelAlgo == DPX_ALGO_BAXT && extension_on(b)) {
@@ -1978,12 +1996,50 @@ int dpx_batch_matrix(dpx_batch *b, size_t pair, int which, int16_t *out) {
 int dpx_batch_set_extension(dpx_batch *b, int32_t zdrop, int32_t endBonus) {
     if (!b || zdrop < -1 || zdrop > (1 << 30) || endBonus < -1 || endBonus > (1 << 30)) return DPX_ERR_INVALID;
     if (b->prm.algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED;
+    if ((zdrop >= 0 || endBonus >= 0) && b->substAlphabet) return DPX_ERR_UNSUPPORTED; /* extension mode under a substitution table: not built */
     int rc = bind_device(b->device);
     if (rc != DPX_OK) return rc;
     if ((zdrop >= 0 || endBonus >= 0) && !b->dExt && b->numPairs)
         HIP_TRY(g_tbDevCache.take((void **)&b->dExt, b->numPairs * sizeof(dpx_extension), &b->dExtCap));
     b->zdrop = zdrop;
     b->endBonus = endBonus;
+    return DPX_OK;
+}
+
+int dpx_batch_set_substitution(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf) {
+    if (!b) return DPX_ERR_INVALID;
+    auto invalidate = [&]() { /* what a refill does to lines, text and CIGARs; the results go with them until the next fill */
+        b->filled = false; b->extFilled = false; b->tbLinesValid = false; b->outState = 0; b->cigarState = 0;
+    };
+    if (!scores) { /* clear: the batch runs its plain kernel again */
+        if (b->substAlphabet) invalidate();
+        b->substAlphabet = 0;
+        return DPX_OK;
+    }
+    if (alphabet < 1 || alphabet > 32 || !codeOf) return DPX_ERR_INVALID;
+    for (int x = 0; x < 256; x++) if ((int)codeOf[x] >= alphabet) return DPX_ERR_INVALID;
+    if (b->prm.algo != DPX_ALGO_BANW && b->prm.algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED;
+    if (b->kernelAlgo != b->prm.algo || b->dirs) return DPX_ERR_UNSUPPORTED; /* a covering BANW band runs as ANW, which has no table kernel */
+    if (extension_on(b)) return DPX_ERR_UNSUPPORTED;
+    if (subst_lds_bytes(b) > 160u * 1024u) return DPX_ERR_UNSUPPORTED; /* the table image no longer fits beside the staged strings */
+    /* fits_int16's BANW / BAXT bounds with the largest entry in place of match and the smallest in place of mismatch */
+    dpx_params q = b->prm;
+    q.match = -128; q.mismatch = 127;
+    for (int k = 0; k < alphabet * alphabet; k++) { q.match = std::max<int32_t>(q.match, scores[k]); q.mismatch = std::min<int32_t>(q.mismatch, scores[k]); }
+    for (const dpx_pair_dev &pd : b->pairs) if (!fits_int16(q, pd.m, pd.n)) return DPX_ERR_RANGE;
+    int rc = bind_device(b->device);
+    if (rc != DPX_OK) return rc;
+    unsigned char image[DPX_SUBST_IMAGE_BYTES];
+    memset(image, 0, sizeof image);
+    for (int r = 0; r < alphabet; r++) memcpy(image + r * 32, scores + r * alphabet, (size_t)alphabet);
+    memcpy(image + DPX_SUBST_TABLE_BYTES, codeOf, 256);
+    if (!b->dSubst) HIP_TRY(g_tbDevCache.take((void **)&b->dSubst, sizeof image, &b->dSubstCap));
+    /* a fill or a walk in flight may still read the previous table */
+    if (b->lastStream && b->lastStream != b->stream) HIP_TRY(hipStreamSynchronize(b->lastStream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipMemcpy(b->dSubst, image, sizeof image, hipMemcpyHostToDevice));
+    b->substAlphabet = alphabet;
+    invalidate();
     return DPX_OK;
 }
 
@@ -2021,7 +2077,8 @@ static int traceback_lines(dpx_batch *b) {
     { const int w = knobs().tbWalk; if (w >= 0) walk = std::min(2, w); }
     /* banded affine SW: as ASW -- one wave per pair up to 20 000 pairs (k_basw_traceback_wave, band-layout window loads for the three
      * planes), one lane per pair beyond that or under DPX_TB_WALK=0 / 1 (k_basw_traceback) */
-    if (b->kernelAlgo == DPX_ALGO_BASW) HIP_TRY(dpx_launch_basw_traceback(b->args, (int)b->numPairs, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream));
+    if (b->substAlphabet) HIP_TRY(dpx_launch_subst_traceback(subst_args(b), (int)b->numPairs, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream));
+    else if (b->kernelAlgo == DPX_ALGO_BASW) HIP_TRY(dpx_launch_basw_traceback(b->args, (int)b->numPairs, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream));
     else if (is_banw_layout(b->kernelAlgo)) HIP_TRY(dpx_launch_banw_traceback(b->args, (int)b->numPairs, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream)); /* (banded affine NW, and the extension, which walks from its end cell to the anchor: the same choice) */
     else if (b->dirs) HIP_TRY(dpx_launch_traceback_dir(b->dirArgs, (int)b->numPairs, b->kernelAlgo, b->R, b->dTbOff, b->dTb, b->dTbLen, b->stream));
     else HIP_TRY(dpx_launch_traceback(b->args, (int)b->numPairs, b->kernelAlgo, b->R, b->planes, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream));
@@ -2313,6 +2370,7 @@ int dpx_batch_describe(dpx_batch *b, char *buf, size_t cap) {
                          : b->kernelAlgo == DPX_ALGO_ASG ? (b->lanePacked ? "k_asg_lanes" : "k_asg_fill")
                          : b->packed ? "k_linear_fill_pk" : b->lanesPk ? "k_linear_lanes_pk" : b->lanePacked ? "k_linear_lanes" : b->split ? "k_linear_split" : "k_linear_fill";
     if (b->kernelAlgo == DPX_ALGO_BAXT && extension_on(b)) kernel = "k_zext_fill";
+    if (b->substAlphabet) kernel = "k_subst_fill";
     if (b->dirs) kernel = b->kernelAlgo == DPX_ALGO_ANW ? "k_affine_dir" : b->kernelAlgo == DPX_ALGO_ASW ? "k_asw_dir" : b->kernelAlgo == DPX_ALGO_ASG ? "k_asg_dir" : "k_linear_dir";
     /* dtype = the arithmetic type of the kernel that fills (most of) the batch */
     int len = snprintf(buf, cap, "algo=%s kernel_algo=%s kernel=%s dtype=%s rows_per_lane=%d store=%d couples=%zu lane_pairs=%zu waves=%zu singles=%zu row_tags=%d seq_input=%s waves_per_workgroup=%u",
@@ -2322,11 +2380,13 @@ int dpx_batch_describe(dpx_batch *b, char *buf, size_t cap) {
     if (is_banded_affine(b->kernelAlgo) && len > 0 && (size_t)len < cap) { /* which walk the batch's traceback takes */
         const bool wave = knobs().tbWalk >= 0 ? knobs().tbWalk >= 2 : b->numPairs <= 20000;
         len += snprintf(buf + len, cap - (size_t)len, " traceback=%s",
-                        is_banw_layout(b->kernelAlgo) ? (wave ? "k_banw_traceback_wave" : "k_banw_traceback")
+                        b->substAlphabet ? (wave ? "k_subst_traceback_wave" : "k_subst_traceback")
+                        : is_banw_layout(b->kernelAlgo) ? (wave ? "k_banw_traceback_wave" : "k_banw_traceback")
                                                        : (wave ? "k_basw_traceback_wave" : "k_basw_traceback"));
     }
     if (b->kernelAlgo == DPX_ALGO_BAXT && extension_on(b) && len > 0 && (size_t)len < cap)
         len += snprintf(buf + len, cap - (size_t)len, " zdrop=%d end_bonus=%d", (int)b->zdrop, (int)b->endBonus);
+    if (b->substAlphabet && len > 0 && (size_t)len < cap) len += snprintf(buf + len, cap - (size_t)len, " subst=%d", b->substAlphabet);
     if (b->dirs && len > 0 && (size_t)len < cap) /* the code layout, and where the edge rows live */
         len += snprintf(buf + len, cap - (size_t)len, " matrix=dir4 dir_edges=%s dir_scratch_bytes=%zu", b->dirScratch ? "global" : "lds", b->dirScratch);
     if (b->dMat && len > 0 && (size_t)len < cap) { /* the matrix pool: how it was built, and the memset time of every candidate that was timed */

@@ -90,6 +90,21 @@ typedef struct dpx_zext_args {
     int32_t *ext;
 } dpx_zext_args;
 hipError_t dpx_launch_zext_fill(const dpx_zext_args &a, int C, bool store, size_t ldsBytes, hipStream_t stream);
+/* BANW / BAXT under a substitution table (dpx_subst_kernels.hip, dpx_batch_set_substitution): k_banw_fill's / k_baxt_fill's cells, stores
+ * and results (`ext`: BAXT's end cell) with the diagonal term H + table[(codeOf[ref byte] << 5) + codeOf[qry byte]].  `table` is 1 KiB of
+ * int8 with a row stride of 32 (row = reference code), `codeOf` 256 bytes, both 16-byte aligned in device memory.  f.ldsPerWave and
+ * `ldsBytes` include DPX_SUBST_IMAGE_BYTES per wave behind the staged strings.  The walks are BANW's with the same diagonal term; the
+ * export is dpx_launch_banw_export. */
+#define DPX_SUBST_TABLE_BYTES 1024
+#define DPX_SUBST_IMAGE_BYTES 1280
+typedef struct dpx_subst_args {
+    dpx_fill_args f;
+    const int8_t *table;
+    const uint8_t *codeOf;
+} dpx_subst_args;
+hipError_t dpx_launch_subst_fill(const dpx_subst_args &a, int C, bool store, bool ext, size_t ldsBytes, hipStream_t stream);
+hipError_t dpx_launch_subst_traceback(const dpx_subst_args &a, int numPairs, int walk, const uint64_t *tbOff, char *tb, int32_t *tbLen,
+                                      hipStream_t stream);
 hipError_t dpx_launch_unpack2(const uint32_t *packed, uint32_t alphabet, char *out, size_t numDwords, hipStream_t stream);
 hipError_t dpx_launch_prim_eval(const int32_t *op, const uint32_t *a, const uint32_t *b, const uint32_t *c, size_t count,
                                 uint32_t *res, uint32_t *pred, hipStream_t stream);

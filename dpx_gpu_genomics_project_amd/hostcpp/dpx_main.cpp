@@ -11,7 +11,12 @@
 // coordinates and the SAM CIGAR ('=' / 'X' ops; "-cigar M" merges them into 'M').  The lines are formatted on the host.
 //
 //   dpx_main -pairs <file> [-match 3] [-mismatch -1] [-open -2 | -gap -2] [-extend -1]
-//            [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band 128] [-batch N | -pool-gb 4] [-inflight K] [-tune 0|1] [-device 0] [-noprint] [-pack2] [-directions] [-cigar [M]] [-zdrop Z] [-endbonus E] [-producer P] [-rank r -world w]
+//            [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band 128] [-batch N | -pool-gb 4] [-inflight K] [-tune 0|1] [-device 0] [-noprint] [-pack2] [-directions] [-cigar [M]] [-zdrop Z] [-endbonus E] [-matrix FILE] [-producer P] [-rank r -world w]
+//
+// -matrix FILE (BANW / BAXT, not with -zdrop / -endbonus): score columns by a substitution matrix (dpx_batch_set_substitution) instead of
+// -match / -mismatch.  NCBI text format: '#' lines are comments; one header row of 1..32 single-character column letters; then one row
+// per letter: the letter, then that many integers in -128..127.  The row letter is the REFERENCE's.  A lower-case byte takes its
+// upper-case letter's code, every other unlisted byte the last letter's ('*' in NCBI files, 'N' in a DNA file).
 //
 // Batch size: by default from a matrix-pool BUDGET (-pool-gb, 4 GiB): as many pairs as fit the budget, at most 20000 (the
 // reference sizes its buffers once for BATCH_SIZE = 10000 reads of 150 bases, cuda/LNW/LinearNeedlemanWunschV9.cu:26-46,
@@ -54,12 +59,68 @@ struct InFlight { // one batch between dpx_batch_create and dpx_batch_destroy
     size_t first = 0, count = 0;
 };
 
+// -matrix: the file into an alphabet x alphabet table and the 256-entry byte -> code map; false (with a reason) when it is malformed
+bool read_matrix(const char *path, std::vector<int8_t> &scores, int &alphabet, uint8_t (&codeOf)[256], std::string &why) {
+    FILE *f = fopen(path, "r");
+    if (!f) { why = "cannot open it"; return false; }
+    std::string letters;
+    std::vector<std::string> rows;
+    char line[4096];
+    while (fgets(line, sizeof line, f)) {
+        std::string t(line);
+        if (t.find('\n') == std::string::npos && !feof(f)) { fclose(f); why = "a line is too long"; return false; }
+        const size_t a = t.find_first_not_of(" \t\r\n");
+        if (a == std::string::npos || t[a] == '#') continue;
+        rows.push_back(t);
+    }
+    fclose(f);
+    if (rows.empty()) { why = "no header row"; return false; }
+    auto tokens = [](const std::string &t) {
+        std::vector<std::string> out;
+        size_t at = 0;
+        while ((at = t.find_first_not_of(" \t\r\n", at)) != std::string::npos) {
+            const size_t end = t.find_first_of(" \t\r\n", at);
+            out.push_back(t.substr(at, end == std::string::npos ? end : end - at));
+            at = end;
+        }
+        return out;
+    };
+    for (const std::string &tok : tokens(rows[0])) {
+        if (tok.size() != 1) { why = "a column letter is not a single character"; return false; }
+        if (letters.find(tok[0]) != std::string::npos) { why = "a column letter appears twice"; return false; }
+        letters += tok[0];
+    }
+    alphabet = (int)letters.size();
+    if (alphabet < 1 || alphabet > 32) { why = "1..32 column letters are allowed"; return false; }
+    if ((int)rows.size() != alphabet + 1) { why = "one row per column letter is needed"; return false; }
+    scores.assign((size_t)alphabet * alphabet, 0);
+    std::vector<bool> seen((size_t)alphabet, false);
+    for (int r = 1; r <= alphabet; r++) {
+        const std::vector<std::string> tok = tokens(rows[(size_t)r]);
+        if ((int)tok.size() != alphabet + 1 || tok[0].size() != 1) { why = "a row needs its letter and one integer per column"; return false; }
+        const size_t row = letters.find(tok[0][0]);
+        if (row == std::string::npos || seen[row]) { why = "a row letter is unknown or appears twice"; return false; }
+        seen[row] = true;
+        for (int c = 0; c < alphabet; c++) {
+            char *end = nullptr;
+            const long v = strtol(tok[(size_t)c + 1].c_str(), &end, 10);
+            if (end == tok[(size_t)c + 1].c_str() || *end || v < -128 || v > 127) { why = "an entry is not an integer in -128..127"; return false; }
+            scores[row * (size_t)alphabet + (size_t)c] = (int8_t)v;
+        }
+    }
+    for (int x = 0; x < 256; x++) codeOf[x] = (uint8_t)(alphabet - 1);
+    for (int k = 0; k < alphabet; k++) codeOf[(unsigned char)letters[(size_t)k]] = (uint8_t)k;
+    for (int lo = 'a'; lo <= 'z'; lo++)
+        if (letters.find((char)lo) == std::string::npos && letters.find((char)(lo - 32)) != std::string::npos) codeOf[lo] = codeOf[lo - 32];
+    return true;
+}
+
 } // namespace
 
 static void usage() {
     fprintf(stderr, "usage: dpx_main -pairs <InSeqFile> -match <matchWeight> -mismatch <mismatchWeight> -open <gapWeight> "
                     "[-extend <gapExtend>] [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band <B>] [-batch <N>] [-device <D>] [-noprint] [-cigar [M]] "
-                    "[-zdrop <Z>] [-endbonus <E>] (BAXT only)\n");
+                    "[-zdrop <Z>] [-endbonus <E>] (BAXT only) [-matrix <file>] (BANW / BAXT, not with -zdrop / -endbonus)\n");
     exit(EXIT_FAILURE);
 }
 
@@ -75,6 +136,7 @@ int main(int argc, char *argv[]) {
     unsigned cigarFlags = DPX_CIGAR_EXTENDED;
     bool directions = false; // -directions: batches keep 4-bit direction codes (DPX_KEEP_DIRECTIONS): int32 scores, a quarter of the pool per pair
     int zdrop = -1, endBonus = -1; // -zdrop / -endbonus: BAXT's extension mode (dpx_batch_set_extension) on every batch; -1 = off
+    const char *matrixFile = nullptr; // -matrix: a substitution table (dpx_batch_set_substitution) on every batch
     int inflight = 3;      // batches on the device at a time (= matrix pools reserved)
     int tuneFlag = -1;     // -1: by the length of the job
     std::string algoName = "LSW";
@@ -102,6 +164,7 @@ int main(int argc, char *argv[]) {
         }
         else if (!strcmp(argv[i], "-zdrop")) zdrop = atoi(next("-zdrop"));
         else if (!strcmp(argv[i], "-endbonus")) endBonus = atoi(next("-endbonus"));
+        else if (!strcmp(argv[i], "-matrix")) matrixFile = next("-matrix");
         else if (!strcmp(argv[i], "-producer")) producerFlag = atoi(next("-producer"));
         else if (!strcmp(argv[i], "-inflight")) inflight = atoi(next("-inflight"));
         else if (!strcmp(argv[i], "-tune")) tuneFlag = atoi(next("-tune"));
@@ -117,6 +180,17 @@ int main(int argc, char *argv[]) {
                      : algoName == "BSW" ? DPX_ALGO_BSW : algoName == "ASW" ? DPX_ALGO_ASW : algoName == "BASW" ? DPX_ALGO_BASW : algoName == "ASG" ? DPX_ALGO_ASG : algoName == "BANW" ? DPX_ALGO_BANW : algoName == "BAXT" ? DPX_ALGO_BAXT : -1;
     if (algo < 0) { fprintf(stderr, "unknown -algo %s\n", algoName.c_str()); exit(EXIT_FAILURE); }
     if ((zdrop != -1 || endBonus != -1) && algo != DPX_ALGO_BAXT) usage();
+    std::vector<int8_t> substScores;
+    int substAlphabet = 0;
+    uint8_t substCode[256];
+    if (matrixFile) {
+        if ((algo != DPX_ALGO_BANW && algo != DPX_ALGO_BAXT) || zdrop != -1 || endBonus != -1) usage();
+        std::string why;
+        if (!read_matrix(matrixFile, substScores, substAlphabet, substCode, why)) {
+            fprintf(stderr, "-matrix %s: %s\n", matrixFile, why.c_str());
+            usage();
+        }
+    }
 
     printf("[Device Details]\n");
     int deviceCount = 0;
@@ -274,6 +348,7 @@ int main(int argc, char *argv[]) {
                                            flags, &next.b);
         if (prc != DPX_OK) die("FAILED TO CREATE DEVICE BATCH", prc);
         if ((zdrop != -1 || endBonus != -1) && (prc = dpx_batch_set_extension(next.b, zdrop, endBonus)) != DPX_OK) die("FAILED TO SET THE EXTENSION MODE", prc);
+        if (matrixFile && (prc = dpx_batch_set_substitution(next.b, substScores.data(), substAlphabet, substCode)) != DPX_OK) die("FAILED TO SET THE SUBSTITUTION MATRIX", prc);
         create_time += get_time() - t0;
         if ((prc = dpx_batch_fill(next.b, nullptr)) != DPX_OK) die("KERNEL LAUNCH FAILED", prc);
         // global pair numbers: shardFirst + index inside the shard

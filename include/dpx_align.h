@@ -225,7 +225,7 @@ int dpx_abi_version(void);
 /* Copy `sequences[0..numBytes)` and pairs[firstPair .. firstPair+numPairs) to HBM and allocate result
  * storage.  Replaces cudaMalloc+cudaMemcpy of sequences/seqPair[] (V19.cu:422-440) and the per-batch matrix
  * pool (V19.cu:488-529).  Sequences are plain bytes ('\0'-separated as parseInput leaves them); any byte
- * value is legal, matching is plain byte equality.  Zero-length sequences are legal. */
+ * value is legal, matching is plain byte equality (BANW / BAXT: or a substitution table, dpx_batch_set_substitution).  Zero-length sequences are legal. */
 int dpx_batch_create(const dpx_params *params, const char *sequences, size_t numBytes, const dpx_seq_pair *pairs,
                      size_t firstPair, size_t numPairs, unsigned flags, dpx_batch **out);
 
@@ -421,6 +421,28 @@ int dpx_batch_set_extension(dpx_batch *b, int32_t zdrop, int32_t endBonus);
 /* numPairs records into host memory.  DPX_ERR_NOT_FILLED before a fill; DPX_ERR_UNSUPPORTED when the last fill ran without
  * extension mode. */
 int dpx_batch_extensions(dpx_batch *b, dpx_extension *out);
+
+/* ---- substitution-matrix scoring (BANW and BAXT batches) ----
+ * Batches score a column by byte equality (match / mismatch) unless a table is set.  With a table, for a reference byte r and a query
+ * byte q the diagonal term uses
+ *       s(r, q) = scores[codeOf[r] * alphabet + codeOf[q]]
+ * -- the row is the reference code, the column the query code, the matrix need not be symmetric.  Everything else in the BANW / BAXT
+ * definitions is unchanged: band, borders, recurrence, tie order, score, end cell, walk rules, export form.  Only H_diag + s uses the
+ * table, in the fill and in the walks; params.match / params.mismatch are ignored by both while a table is set.
+ * The TEXT stays byte equality: the relation line ('*' / '|') and the CIGAR's '=' / 'X' compare bytes, as SAM defines '='.  So 'a'
+ * against 'A' under a case-folding codeOf scores as a match and prints '|' / 'X'.
+ * The call applies to every following fill and invalidates lines, text, CIGARs and results of an earlier fill (DPX_ERR_NOT_FILLED until
+ * the next one).  scores == NULL clears it (the other arguments are ignored) and the batch runs k_banw_fill / k_baxt_fill again.  Both
+ * arrays are copied at the call.  A refused call leaves the previous setting in force.
+ *   DPX_ERR_INVALID      b == NULL, alphabet outside 1..32, codeOf == NULL, or a codeOf[x] >= alphabet
+ *   DPX_ERR_UNSUPPORTED  an algorithm other than BANW / BAXT; a BANW batch whose band covers its matrices (it runs as ANW); a batch with
+ *                        extension mode on (and dpx_batch_set_extension switching a mode on while a table is set); a batch whose staged
+ *                        sequences leave no room in LDS for the table
+ *   DPX_ERR_RANGE        the create-time range check of BANW / BAXT fails for a pair with the largest of the alphabet^2 entries in place
+ *                        of match and the smallest in place of mismatch
+ * While a table is set dpx_batch_describe reports kernel=k_subst_fill, traceback=k_subst_traceback_wave / k_subst_traceback and adds
+ * ` subst=<alphabet>`.  Matrix and DPX_SCORE_ONLY batches, packed2 input, dpx_batch_create_on and a caller's stream as for BAXT. */
+int dpx_batch_set_substitution(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf /* 256 entries */);
 
 /* Sizes: numPairs, total cells (sum refLen*queryLen, the reference's numCells, c++/parseInput.cpp:100),
  * bytes of HBM the matrices occupy, algorithmic bytes of one fill. */
