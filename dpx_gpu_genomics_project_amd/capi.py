@@ -16,6 +16,7 @@ ALGO_BAXT = 10  # (8 and 9 are unassigned)
 ALGO_NAMES = {ALGO_LNW: "LNW", ALGO_LSW: "LSW", ALGO_ANW: "ANW", ALGO_BSW: "BSW", ALGO_ASW: "ASW", ALGO_BASW: "BASW", ALGO_ASG: "ASG",
               ALGO_BANW: "BANW", ALGO_BAXT: "BAXT"}
 KEEP_MATRICES, SCORE_ONLY, TIME_FILLS, TUNE_PLACEMENT, KEEP_DIRECTIONS = 0x0, 0x1, 0x2, 0x4, 0x8
+KEEP_BAND_DIRECTIONS = 0x10  # BANW / BAXT: 4-bit direction codes per in-band cell, int32 scores (0x8 stays refused on banded algorithms)
 MAT_H, MAT_I, MAT_D = 0, 1, 2
 # CIGARs (dpx_batch_cigars_begin / _end): an op is (length << 4) | code with BAM's code numbers
 CIGAR_OP_M, CIGAR_OP_I, CIGAR_OP_D, CIGAR_OP_EQ, CIGAR_OP_X = 0, 1, 2, 7, 8

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "dpx_cigar.h"
+#include "dpx_banddir.h"
 #include "dpx_dir.h"
 #include "dpx_kernels.h"
 #include "dpx_layout.h"
@@ -568,6 +569,9 @@ struct dpx_batch {
     bool dirs = false;
     dpx_dir_args dirArgs{};
     size_t dirScratch = 0; /* bytes of that area (0: LDS) */
+    /* DPX_KEEP_BAND_DIRECTIONS on a BANW / BAXT band kernel: 4-bit codes in the band layout of dpx_banddir.h behind dMat, filled by
+     * k_bdir_fill through b->args (a covering BANW band is a `dirs` batch of ANW instead) */
+    bool bandDirs = false;
 };
 
 extern "C" {
@@ -826,6 +830,15 @@ static bool fits_dir(const dpx_params &p, long long m, long long n) {
         return neg(o + e) >= -lim && hiH + pos(o) + pos(e) * std::max(m, n) <= lim;
     }
     if (p.algo == DPX_ALGO_LNW) return neg(p.gapOpen) * (m + n) >= -lim && diag + pos(p.gapOpen) * (m + n) <= lim;
+    if (p.algo == DPX_ALGO_BANW || p.algo == DPX_ALGO_BAXT) {
+        /* DPX_KEEP_BAND_DIRECTIONS: fits_int16's loH / hiH argument for the band (the all-gap path leaves it; the diagonal to (k, k) and
+         * one gap of at most min(B - 1, max(m, n)) steps does not), in int32.  No m + n limit for BAXT: k_bdir_fill keeps the value and
+         * the position of its running maximum in separate registers. */
+        const long long o = p.gapOpen, e = p.gapExtend, g = std::min<long long>(std::max<long long>(p.band - 1, 0), std::max(m, n));
+        const long long loH = neg(std::min<long long>(p.match, p.mismatch)) * std::min(m, n) + neg(o) + neg(e) * g;
+        const long long hiH = diag + (pos(o) + pos(e)) * (m + n);
+        return loH + neg(o + e) >= -lim && hiH + pos(o) + pos(e) * std::max(m, n) <= lim;
+    }
     /* ANW, and ASG by the argument in fits_int16 (its direction fill keeps row m's first maximum as an int32 value and column: no key, no column limit) */
     const long long o = p.gapOpen, e = p.gapExtend;
     const long long loH = 2 * neg(o) + neg(e) * (m + n), hiH = diag + (pos(o) + pos(e)) * (m + n);
@@ -1138,9 +1151,11 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
         if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); return DPX_ERR_NO_DEVICE; }
         if (device >= n) return DPX_ERR_INVALID;
     } else if (device != -1) return DPX_ERR_INVALID;
-    const bool dirs = (flags & DPX_KEEP_DIRECTIONS) != 0;
-    if (dirs && (flags & DPX_SCORE_ONLY)) return DPX_ERR_INVALID;
-    if (dirs && is_banded(params->algo)) return DPX_ERR_UNSUPPORTED; /* banded directions: not implemented */
+    bool dirs = (flags & DPX_KEEP_DIRECTIONS) != 0;
+    const bool bandDirFlag = (flags & DPX_KEEP_BAND_DIRECTIONS) != 0;
+    if ((dirs || bandDirFlag) && (flags & DPX_SCORE_ONLY)) return DPX_ERR_INVALID;
+    if (dirs && is_banded(params->algo)) return DPX_ERR_UNSUPPORTED; /* 0x8 on a banded algorithm stays refused, with or without 0x10 */
+    if (bandDirFlag && params->algo != DPX_ALGO_BANW && params->algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED; /* (BSW / BASW: not built) */
     rc = bind_device(device);
     if (rc != DPX_OK) return rc;
 
@@ -1177,7 +1192,7 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
             delete b;
             return DPX_ERR_UNSUPPORTED;
         }
-        if (!(dirs ? fits_dir(*params, sp.querySize, sp.referenceSize) : fits_int16(*params, sp.querySize, sp.referenceSize))) { delete b; return DPX_ERR_RANGE; }
+        if (!((dirs || bandDirFlag) ? fits_dir(*params, sp.querySize, sp.referenceSize) : fits_int16(*params, sp.querySize, sp.referenceSize))) { delete b; return DPX_ERR_RANGE; }
         dpx_pair_dev &pd = b->pairs[i];
         pd.refIdx = sp.referenceIdx; pd.n = sp.referenceSize;
         pd.qryIdx = sp.queryIdx;     pd.m = sp.querySize;
@@ -1187,6 +1202,11 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
         if (pd.n != b->pairs[0].n || pd.m != b->pairs[0].m) ragged = true;
     }
 
+    /* DPX_KEEP_BAND_DIRECTIONS: a covering BANW band takes the matrix batch's fall-back to ANW, as an ANW direction batch; every other band
+     * runs k_bdir_fill (decided below, where the band kernels are chosen) */
+    const bool bandDirCovering = bandDirFlag && params->algo == DPX_ALGO_BANW && (long long)params->band >= (long long)std::max(b->maxM, b->maxN) + 1;
+    if (bandDirCovering) { dirs = true; b->dirs = true; }
+    const bool bandDirs = bandDirFlag && !bandDirCovering;
     trace.mark("create: validation");
     /* rows per lane: smallest tile that keeps short queries in one stripe, 8 (or DPX_R) otherwise */
     /* linear gaps: 16 rows per lane once a query is longer than 512 (one stripe up to 1024 rows, two 1-KiB sub-tiles per
@@ -1214,6 +1234,7 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
             return DPX_ERR_UNSUPPORTED; /* band kernel holds <= 8 cells per lane (band <= 512) */
         } else {
             b->R = dpx_band_cpl(params->band);
+            b->bandDirs = bandDirs;
         }
     }
     b->kernelAlgo = kernelAlgo;
@@ -1231,6 +1252,10 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
         b->algBytes += (uint64_t)pd.m + (uint64_t)pd.n + 16u + 12u;
         if (dirs) {
             b->algBytes += ((uint64_t)(pd.m + 1) * (uint64_t)(pd.n + 1) + 1) / 2; /* half a byte per cell */
+        } else if (bandDirs) { /* half a byte per in-band cell */
+            const uint64_t inband = band_cells(pd.m, pd.n, params->band);
+            b->bandCells += inband;
+            b->algBytes += (inband + 1) / 2;
         } else if (b->store) {
             if (banded) { /* 2 B per in-band cell and plane */
                 const uint64_t inband = band_cells(pd.m, pd.n, params->band);
@@ -1260,6 +1285,10 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
     const size_t dirPerWave = dirEdgeBytes * nEdges + align_up((size_t)b->maxN + 192, 16);
     const bool dirGlobal = dirs && dirPerWave > 64u * 1024u;
     if (dirs) b->ldsBytes = 0;
+    /* band directions: BANW's staging; when four waves' strings do not fit one workgroup's LDS (long references are what these batches
+     * are for) the fill runs one-wave workgroups, and the batch is refused only when one wave's strings do not fit */
+    const bool bandDirOneWave = bandDirs && b->ldsBytes > 160u * 1024u && perWave <= 160u * 1024u;
+    if (bandDirOneWave) b->ldsBytes = perWave;
     if (b->ldsBytes > 160u * 1024u) { delete b; return DPX_ERR_UNSUPPORTED; }
 
 #define CREATE_TRY(call)                                                      \
@@ -1530,9 +1559,10 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
     if (b->store) {
         int group = 64;
         if (kn.group >= 1 && kn.group <= 1000000) group = kn.group;
-        const uint32_t chunkElems = banded ? dpx_band_chunk_elems(bandPlanes) : (b->split || dirs) ? 512u : dpx_tiled_chunk_elems(b->R, b->planes); /* (dirs: 1-KiB code chunks) */
+        const uint32_t chunkElems = bandDirs ? 512u : banded ? dpx_band_chunk_elems(bandPlanes) : (b->split || dirs) ? 512u : dpx_tiled_chunk_elems(b->R, b->planes); /* (dirs: 1-KiB code chunks) */
         auto chunksOf = [&](const dpx_pair_dev &pd) -> uint64_t {
             if (dirs) return dpx_dir_chunks(pd.m, pd.n, b->R);
+            if (bandDirs) return dpx_banddir_chunks(pd.m, pd.n, params->band);
             if (pd.lanes == 32) return dpx_split_chunks(pd.m, pd.n, b->R);
             return banded ? dpx_band_chunks(pd.m, pd.n, params->band) : dpx_tiled_chunks(pd.m, pd.n, b->R);
         };
@@ -1636,7 +1666,7 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
     a.pairs = b->dPairs;
     a.order = b->dOrder;
     a.numPairs = (int32_t)numSingles;
-    a.wavesPerBlock = fill_waves_per_block(numSingles);
+    a.wavesPerBlock = bandDirOneWave ? 1u : fill_waves_per_block(numSingles);
     a.match = params->match; a.mismatch = params->mismatch;
     a.gapOpen = params->gapOpen; a.gapExtend = params->gapExtend; a.band = params->band;
     a.mat = b->dMat;
@@ -1754,6 +1784,7 @@ static dpx_subst_args subst_args(const dpx_batch *b) {
 static size_t subst_lds_bytes(const dpx_batch *b) { return b->ldsBytes + (size_t)DPX_SUBST_IMAGE_BYTES * (DPX_FILL_THREADS / 64); }
 
 static hipError_t launch_main(dpx_batch *b, hipStream_t s) { /* the one-wave-per-pair kernel of the batch's algorithm */
+    if (b->bandDirs) return dpx_launch_bdir_fill(b->args, b->R, b->kernelAlgo == DPX_ALGO_BAXT, s);
     if (b->substAlphabet) /* (set only on batches whose kernel is BANW's or BAXT's, extension mode off) */
         return dpx_launch_subst_fill(subst_args(b), b->R, b->store, b->kernelAlgo == DPX_ALGO_BAXT, subst_lds_bytes(b), s);
     if (b->kernelAlgo == DPX_ALGO_BASW) return dpx_launch_basw_fill(b->args, b->R, b->store, b->ldsBytes, s);
@@ -1943,7 +1974,7 @@ int dpx_batch_results(dpx_batch *b, int32_t *scores, int32_t *endRow, int32_t *e
 
 int dpx_batch_directions(dpx_batch *b, size_t pair, int which, uint8_t *out) {
     if (!b || !out || pair >= b->numPairs || which < 0 || which >= b->planes) return DPX_ERR_INVALID;
-    if (!b->dirs) return DPX_ERR_NO_MATRIX;
+    if (!b->dirs && !b->bandDirs) return DPX_ERR_NO_MATRIX;
     if (!b->filled) return DPX_ERR_NOT_FILLED;
     int rc = bind_device(b->device);
     if (rc != DPX_OK) return rc;
@@ -1953,7 +1984,8 @@ int dpx_batch_directions(dpx_batch *b, size_t pair, int which, uint8_t *out) {
     size_t dOutCap = 0;
     if (b->lastStream && b->lastStream != b->stream) HIP_TRY(hipStreamSynchronize(b->lastStream));
     HIP_TRY(g_tbDevCache.take((void **)&dOut, std::max<size_t>(total, 16), &dOutCap)); /* row-major scratch */
-    hipError_t e = dpx_launch_export_dir(reinterpret_cast<const uint8_t *>(b->dMat), pd, b->dSeq, b->kernelAlgo, b->R, which, dOut, b->stream);
+    hipError_t e = b->bandDirs ? dpx_launch_bdir_export(reinterpret_cast<const uint8_t *>(b->dMat), pd, b->dSeq, b->prm.band, which, dOut, b->stream)
+                               : dpx_launch_export_dir(reinterpret_cast<const uint8_t *>(b->dMat), pd, b->dSeq, b->kernelAlgo, b->R, which, dOut, b->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
     if (e == hipSuccess) e = hipMemcpy(out, dOut, total, hipMemcpyDeviceToHost);
     g_tbDevCache.park(dOut, dOutCap);
@@ -1963,7 +1995,7 @@ int dpx_batch_directions(dpx_batch *b, size_t pair, int which, uint8_t *out) {
 
 int dpx_batch_matrix(dpx_batch *b, size_t pair, int which, int16_t *out) {
     if (!b || !out || pair >= b->numPairs || which < 0 || which >= b->planes) return DPX_ERR_INVALID;
-    if (!b->store || b->dirs) return DPX_ERR_NO_MATRIX;
+    if (!b->store || b->dirs || b->bandDirs) return DPX_ERR_NO_MATRIX;
     if (!b->filled) return DPX_ERR_NOT_FILLED;
     int rc = bind_device(b->device);
     if (rc != DPX_OK) return rc;
@@ -1996,6 +2028,7 @@ int dpx_batch_matrix(dpx_batch *b, size_t pair, int which, int16_t *out) {
 int dpx_batch_set_extension(dpx_batch *b, int32_t zdrop, int32_t endBonus) {
     if (!b || zdrop < -1 || zdrop > (1 << 30) || endBonus < -1 || endBonus > (1 << 30)) return DPX_ERR_INVALID;
     if (b->prm.algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED;
+    if (b->bandDirs) return DPX_ERR_UNSUPPORTED; /* extension mode on a band-direction batch: not built */
     if ((zdrop >= 0 || endBonus >= 0) && b->substAlphabet) return DPX_ERR_UNSUPPORTED; /* extension mode under a substitution table: not built */
     int rc = bind_device(b->device);
     if (rc != DPX_OK) return rc;
@@ -2019,7 +2052,7 @@ int dpx_batch_set_substitution(dpx_batch *b, const int8_t *scores, int32_t alpha
     if (alphabet < 1 || alphabet > 32 || !codeOf) return DPX_ERR_INVALID;
     for (int x = 0; x < 256; x++) if ((int)codeOf[x] >= alphabet) return DPX_ERR_INVALID;
     if (b->prm.algo != DPX_ALGO_BANW && b->prm.algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED;
-    if (b->kernelAlgo != b->prm.algo || b->dirs) return DPX_ERR_UNSUPPORTED; /* a covering BANW band runs as ANW, which has no table kernel */
+    if (b->kernelAlgo != b->prm.algo || b->dirs || b->bandDirs) return DPX_ERR_UNSUPPORTED; /* (band directions: not built;) a covering BANW band runs as ANW, which has no table kernel */
     if (extension_on(b)) return DPX_ERR_UNSUPPORTED;
     if (subst_lds_bytes(b) > 160u * 1024u) return DPX_ERR_UNSUPPORTED; /* the table image no longer fits beside the staged strings */
     /* fits_int16's BANW / BAXT bounds with the largest entry in place of match and the smallest in place of mismatch */
@@ -2077,7 +2110,8 @@ static int traceback_lines(dpx_batch *b) {
     { const int w = knobs().tbWalk; if (w >= 0) walk = std::min(2, w); }
     /* banded affine SW: as ASW -- one wave per pair up to 20 000 pairs (k_basw_traceback_wave, band-layout window loads for the three
      * planes), one lane per pair beyond that or under DPX_TB_WALK=0 / 1 (k_basw_traceback) */
-    if (b->substAlphabet) HIP_TRY(dpx_launch_subst_traceback(subst_args(b), (int)b->numPairs, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream));
+    if (b->bandDirs) HIP_TRY(dpx_launch_bdir_traceback(b->args, (int)b->numPairs, b->dTbOff, b->dTb, b->dTbLen, b->stream)); /* (one walk: DPX_TB_WALK has no effect) */
+    else if (b->substAlphabet) HIP_TRY(dpx_launch_subst_traceback(subst_args(b), (int)b->numPairs, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream));
     else if (b->kernelAlgo == DPX_ALGO_BASW) HIP_TRY(dpx_launch_basw_traceback(b->args, (int)b->numPairs, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream));
     else if (is_banw_layout(b->kernelAlgo)) HIP_TRY(dpx_launch_banw_traceback(b->args, (int)b->numPairs, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream)); /* (banded affine NW, and the extension, which walks from its end cell to the anchor: the same choice) */
     else if (b->dirs) HIP_TRY(dpx_launch_traceback_dir(b->dirArgs, (int)b->numPairs, b->kernelAlgo, b->R, b->dTbOff, b->dTb, b->dTbLen, b->stream));
@@ -2371,6 +2405,7 @@ int dpx_batch_describe(dpx_batch *b, char *buf, size_t cap) {
                          : b->packed ? "k_linear_fill_pk" : b->lanesPk ? "k_linear_lanes_pk" : b->lanePacked ? "k_linear_lanes" : b->split ? "k_linear_split" : "k_linear_fill";
     if (b->kernelAlgo == DPX_ALGO_BAXT && extension_on(b)) kernel = "k_zext_fill";
     if (b->substAlphabet) kernel = "k_subst_fill";
+    if (b->bandDirs) kernel = "k_bdir_fill";
     if (b->dirs) kernel = b->kernelAlgo == DPX_ALGO_ANW ? "k_affine_dir" : b->kernelAlgo == DPX_ALGO_ASW ? "k_asw_dir" : b->kernelAlgo == DPX_ALGO_ASG ? "k_asg_dir" : "k_linear_dir";
     /* dtype = the arithmetic type of the kernel that fills (most of) the batch */
     int len = snprintf(buf, cap, "algo=%s kernel_algo=%s kernel=%s dtype=%s rows_per_lane=%d store=%d couples=%zu lane_pairs=%zu waves=%zu singles=%zu row_tags=%d seq_input=%s waves_per_workgroup=%u",
@@ -2380,13 +2415,15 @@ int dpx_batch_describe(dpx_batch *b, char *buf, size_t cap) {
     if (is_banded_affine(b->kernelAlgo) && len > 0 && (size_t)len < cap) { /* which walk the batch's traceback takes */
         const bool wave = knobs().tbWalk >= 0 ? knobs().tbWalk >= 2 : b->numPairs <= 20000;
         len += snprintf(buf + len, cap - (size_t)len, " traceback=%s",
-                        b->substAlphabet ? (wave ? "k_subst_traceback_wave" : "k_subst_traceback")
+                        b->bandDirs ? "k_bdir_traceback"
+                        : b->substAlphabet ? (wave ? "k_subst_traceback_wave" : "k_subst_traceback")
                         : is_banw_layout(b->kernelAlgo) ? (wave ? "k_banw_traceback_wave" : "k_banw_traceback")
                                                        : (wave ? "k_basw_traceback_wave" : "k_basw_traceback"));
     }
     if (b->kernelAlgo == DPX_ALGO_BAXT && extension_on(b) && len > 0 && (size_t)len < cap)
         len += snprintf(buf + len, cap - (size_t)len, " zdrop=%d end_bonus=%d", (int)b->zdrop, (int)b->endBonus);
     if (b->substAlphabet && len > 0 && (size_t)len < cap) len += snprintf(buf + len, cap - (size_t)len, " subst=%d", b->substAlphabet);
+    if (b->bandDirs && len > 0 && (size_t)len < cap) len += snprintf(buf + len, cap - (size_t)len, " matrix=banddir4");
     if (b->dirs && len > 0 && (size_t)len < cap) /* the code layout, and where the edge rows live */
         len += snprintf(buf + len, cap - (size_t)len, " matrix=dir4 dir_edges=%s dir_scratch_bytes=%zu", b->dirScratch ? "global" : "lds", b->dirScratch);
     if (b->dMat && len > 0 && (size_t)len < cap) { /* the matrix pool: how it was built, and the memset time of every candidate that was timed */

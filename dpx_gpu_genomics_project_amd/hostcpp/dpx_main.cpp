@@ -135,6 +135,7 @@ int main(int argc, char *argv[]) {
     bool cigar = false;      // -cigar: records + CIGAR ops instead of the text pipeline
     unsigned cigarFlags = DPX_CIGAR_EXTENDED;
     bool directions = false; // -directions: batches keep 4-bit direction codes (DPX_KEEP_DIRECTIONS): int32 scores, a quarter of the pool per pair
+                             // (-algo BANW | BAXT: DPX_KEEP_BAND_DIRECTIONS, one code per in-band cell)
     int zdrop = -1, endBonus = -1; // -zdrop / -endbonus: BAXT's extension mode (dpx_batch_set_extension) on every batch; -1 = off
     const char *matrixFile = nullptr; // -matrix: a substitution table (dpx_batch_set_substitution) on every batch
     int inflight = 3;      // batches on the device at a time (= matrix pools reserved)
@@ -235,7 +236,13 @@ int main(int argc, char *argv[]) {
         const long long mq = fileInfo.maxQueryLength, dR = mq <= 128 ? 2 : mq <= 256 ? 4 : (mq <= 512 || algo != DPX_ALGO_LNW) ? 8 : 16;
         const double dirRows = (double)((mq + 64 * dR - 1) / (64 * dR) * 64 * dR);
         const double dirCols = (double)(((long long)fileInfo.maxReferenceLength + 63 + 32 / dR - 1) / (32 / dR) * (32 / dR));
-        const double perPair = directions ? 0.5 * dirRows * dirCols + 1024.0
+        // (-directions on BANW / BAXT: ceil((m + n - 1) / Gd) chunks of 1 KiB, Gd = 32 / C steps per chunk, C = cells per lane of the
+        // band -- the layout of csrc/dpx_banddir.h)
+        const bool bandDirections = directions && (algo == DPX_ALGO_BANW || algo == DPX_ALGO_BAXT);
+        const long long bC0 = ((long long)band + 63) / 64, bC = bC0 <= 1 ? 1 : bC0 <= 2 ? 2 : bC0 <= 4 ? 4 : 8, bGd = 32 / bC;
+        const double bandDirChunks = (double)((mq + (long long)fileInfo.maxReferenceLength - 1 + bGd - 1) / bGd);
+        const double perPair = bandDirections ? 1024.0 * bandDirChunks + 1024.0
+                             : directions ? 0.5 * dirRows * dirCols + 1024.0
                                           : 2.0 * (threePlanes ? 3 : 1) * ((double)fileInfo.maxQueryLength + 64) * cols;
         const double fit = (double)poolBudget / (perPair > 0 ? perPair : 1);
         batchSize = (size_t)std::min(20000.0, std::max(64.0, fit));
@@ -341,7 +348,8 @@ int main(int argc, char *argv[]) {
         next.first = first;
         next.count = std::min(batchSize, shardHi - first);
         const uint64_t t0 = get_time();
-        const unsigned flags = (directions ? DPX_KEEP_DIRECTIONS : DPX_KEEP_MATRICES) | DPX_TIME_FILLS | ((tunePools && tuned.fetch_add(1) < inflight) ? DPX_TUNE_PLACEMENT : 0u);
+        const bool bandDirections = directions && (algo == DPX_ALGO_BANW || algo == DPX_ALGO_BAXT);
+        const unsigned flags = (bandDirections ? DPX_KEEP_BAND_DIRECTIONS : directions ? DPX_KEEP_DIRECTIONS : DPX_KEEP_MATRICES) | DPX_TIME_FILLS | ((tunePools && tuned.fetch_add(1) < inflight) ? DPX_TUNE_PLACEMENT : 0u);
         int prc = pack2 ? dpx_batch_create_packed2(-1, &prm, packed.data(), fileInfo.numBytes, alphabet, reinterpret_cast<const dpx_seq_pair *>(sequenceIdxs),
                                                    first, next.count, flags, &next.b)
                         : dpx_batch_create(&prm, sequences, fileInfo.numBytes, reinterpret_cast<const dpx_seq_pair *>(sequenceIdxs), first, next.count,

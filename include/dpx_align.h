@@ -121,7 +121,8 @@ typedef enum dpx_algo {
                          dpx_batch_matrix: row-major (m+1) x (n+1); in-band H carries the borders above, I and D are 0 on in-band
                          borders (as for ANW), every plane is 0 outside the band (as for BASW), and an in-band I or D that is
                          -infinity exports as -32768; the range check keeps every finite value at or above -32767.
-                         Matrices and DPX_SCORE_ONLY; DPX_KEEP_DIRECTIONS is DPX_ERR_UNSUPPORTED, as for BSW and BASW.  packed2
+                         Matrices and DPX_SCORE_ONLY; DPX_KEEP_DIRECTIONS is DPX_ERR_UNSUPPORTED, as for BSW and BASW (4-bit
+                         directions and int32 scores: DPX_KEEP_BAND_DIRECTIONS).  packed2
                          input, dpx_align_batch, the output pipeline, dpx_batch_create_on and a caller's stream as for BASW.
                          Added without an ABI bump or a new symbol: a library that predates it returns DPX_ERR_INVALID for algo 7. */
     /* 8 and 9 are unassigned: DPX_ERR_INVALID */
@@ -151,7 +152,7 @@ typedef enum dpx_algo {
                          Range: BANW's int16 bounds, and m + n <= 65000 (the kernel packs the step index into 16 bits, as BASW's);
                          otherwise DPX_ERR_RANGE.
                          Matrices and DPX_SCORE_ONLY; DPX_KEEP_DIRECTIONS is DPX_ERR_UNSUPPORTED, as for the other banded
-                         algorithms.  packed2 input, dpx_align_batch, the output pipeline, dpx_batch_create_on and a caller's stream
+                         algorithms (4-bit directions, int32 scores and no m + n limit: DPX_KEEP_BAND_DIRECTIONS).  packed2 input, dpx_align_batch, the output pipeline, dpx_batch_create_on and a caller's stream
                          as for BANW.  z-drop termination, ksw2's "best score reaching the end of the query" and an end bonus are
                          per-batch settings of this algorithm: dpx_batch_set_extension below.
                          Added without an ABI bump or a new symbol: a library that predates it returns DPX_ERR_INVALID for algo 10. */
@@ -190,7 +191,33 @@ typedef struct dpx_params {
                                     padding per query row (about a quarter of an int16 H batch's bytes, a twelfth of ANW's H/I/D, from
                                     a few hundred rows on; short reads keep a larger fraction); scores may exceed int16 (bounds checked against 2^28) and references 65 000 columns.
                                     dpx_batch_matrix() returns DPX_ERR_NO_MATRIX, dpx_batch_directions() exports the codes.  With
-                                    DPX_SCORE_ONLY: DPX_ERR_INVALID; with BSW / BASW / BANW / BAXT: DPX_ERR_UNSUPPORTED (banded directions are not implemented). */
+                                    DPX_SCORE_ONLY: DPX_ERR_INVALID; with BSW / BASW / BANW / BAXT: DPX_ERR_UNSUPPORTED, with or without 0x10
+                                    (BANW and BAXT keep directions under DPX_KEEP_BAND_DIRECTIONS below; BSW / BASW directions are not implemented). */
+#define DPX_KEEP_BAND_DIRECTIONS 0x10u /* BANW / BAXT: keep one 4-bit direction code per IN-BAND cell instead of the three int16 planes, compute in int32
+                                    (k_bdir_fill; half a byte per in-band cell in whole 1-KiB chunks, a twelfth of the matrix batch's bytes).
+                                    The definitions of BANW and BAXT do not change: same scores, end cells, traceback lines, text blocks and
+                                    CIGAR records as a DPX_KEEP_MATRICES batch wherever that batch is admitted -- and batches it refuses with
+                                    DPX_ERR_RANGE run: bounds are BANW's, checked against 2^28, and BAXT has no m + n <= 65000 limit here.
+                                    dpx_batch_matrix() returns DPX_ERR_NO_MATRIX.  dpx_batch_directions() exports c++/backtrack.h enums: in-band
+                                    cells with i, j >= 1 carry MATCH / MISMATCH / QUERY_INSERTION / QUERY_DELETION in DPX_MAT_H and GAP_OPEN /
+                                    GAP_EXTEND in DPX_MAT_I / DPX_MAT_D (I on the band's lower edge and D on its upper edge: GAP_OPEN,
+                                    -infinity >= -infinity); in-band borders of H are ANW's (QUERY_DELETION down column 0, QUERY_INSERTION
+                                    along row 0, NONE_MAIN at (0, 0)), borders of I and D are 0; every plane is 0 outside the band.
+                                    A separate bit because 0x8 on a banded algorithm is pinned to DPX_ERR_UNSUPPORTED, and stays so.
+                                    With DPX_SCORE_ONLY: DPX_ERR_INVALID.  With another algorithm than BANW / BAXT: DPX_ERR_UNSUPPORTED (BSW /
+                                    BASW are follow-ups).  Band > 512 (BANW: not covering): DPX_ERR_UNSUPPORTED, BANW's admission rule
+                                    |m - n| < B unchanged, as for matrix batches.  A BANW band that covers the matrix (B >= max(m, n) + 1)
+                                    runs as an ANW DPX_KEEP_DIRECTIONS batch (kernel_algo=ANW), the fall-back the matrix batch takes.
+                                    dpx_batch_set_extension and dpx_batch_set_substitution on such a batch: DPX_ERR_UNSUPPORTED, the batch is
+                                    left as it was (both are follow-ups).  DPX_TIME_FILLS, dpx_batch_fill_timed, repeated fills, a caller's
+                                    stream, dpx_batch_create_on, packed2 input, the output pipeline and dpx_batch_cigars_* as for a BANW
+                                    matrix batch; DPX_TB_WALK has no effect (one walk, k_bdir_traceback).  Strings are staged in LDS as for
+                                    BANW; where four waves' strings do not fit a workgroup the fill runs one-wave workgroups, and a pair
+                                    whose two strings exceed ~160 KB is DPX_ERR_UNSUPPORTED.
+                                    Added without an ABI bump or a new symbol.  Detecting it: a library that predates the flag ignores the
+                                    bit and builds an int16 matrix batch -- dpx_batch_describe then shows kernel=k_banw_fill / k_baxt_fill
+                                    (this library: kernel=k_bdir_fill, or k_affine_dir under a covering BANW band) and dpx_batch_directions
+                                    returns DPX_ERR_NO_MATRIX. */
 
 /* matrix selectors for dpx_batch_matrix / dpx_batch_directions */
 #define DPX_MAT_H 0 /* scoring matrix   (reference: memo / scoringMemo)            */
@@ -416,7 +443,8 @@ typedef struct dpx_extension {      /* 32 bytes */
 /* Legal any time after create; takes effect at the next fill (dpx_batch_fill, dpx_batch_fill_timed).  A batch of another algorithm:
  * DPX_ERR_UNSUPPORTED; a value below -1 or above 1 << 30: DPX_ERR_INVALID.  (-1, -1) returns the batch to plain BAXT (k_baxt_fill).
  * While either value is >= 0 the fill runs k_zext_fill and dpx_batch_describe adds `zdrop=` and `end_bonus=`.  Matrix and
- * DPX_SCORE_ONLY batches, packed2 input, dpx_batch_create_on and a caller's stream as for BAXT. */
+ * DPX_SCORE_ONLY batches, packed2 input, dpx_batch_create_on and a caller's stream as for BAXT.  A DPX_KEEP_BAND_DIRECTIONS batch:
+ * DPX_ERR_UNSUPPORTED (a follow-up), the batch is left as it was. */
 int dpx_batch_set_extension(dpx_batch *b, int32_t zdrop, int32_t endBonus);
 /* numPairs records into host memory.  DPX_ERR_NOT_FILLED before a fill; DPX_ERR_UNSUPPORTED when the last fill ran without
  * extension mode. */
@@ -441,7 +469,8 @@ int dpx_batch_extensions(dpx_batch *b, dpx_extension *out);
  *   DPX_ERR_RANGE        the create-time range check of BANW / BAXT fails for a pair with the largest of the alphabet^2 entries in place
  *                        of match and the smallest in place of mismatch
  * While a table is set dpx_batch_describe reports kernel=k_subst_fill, traceback=k_subst_traceback_wave / k_subst_traceback and adds
- * ` subst=<alphabet>`.  Matrix and DPX_SCORE_ONLY batches, packed2 input, dpx_batch_create_on and a caller's stream as for BAXT. */
+ * ` subst=<alphabet>`.  Matrix and DPX_SCORE_ONLY batches, packed2 input, dpx_batch_create_on and a caller's stream as for BAXT.  A
+ * DPX_KEEP_BAND_DIRECTIONS batch: DPX_ERR_UNSUPPORTED (a follow-up), the batch is left as it was. */
 int dpx_batch_set_substitution(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf /* 256 entries */);
 
 /* Sizes: numPairs, total cells (sum refLen*queryLen, the reference's numCells, c++/parseInput.cpp:100),
