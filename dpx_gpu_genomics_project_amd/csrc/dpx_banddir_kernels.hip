@@ -22,30 +22,12 @@
  * so the tracker holds the lane's first maximum in row-major order; a wave reduction takes the maximum score, then the smallest row,
  * then the smallest column.  Only H > 0 displaces (0, 0).
  */
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
+#include "dpx_band_affine.hpp"
 #include "dpx_banddir.h"
-#include "dpx_kernels.h"
-#include "dpx_layout.h"
-#include "dpx_prims.hpp"
 
 namespace {
 
-using dpx::wave_shl1;
-using dpx::wave_shr1;
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-/* a string copied into LDS with aligned 16-byte loads; it lands `src & 15` bytes into the buffer (as in dpx_banw_kernels.hip) */
-__device__ __forceinline__ unsigned char *stage_bytes(unsigned char *dst16, const unsigned char *src, const int n, const int l, const int G) {
-    const unsigned a = (unsigned)(reinterpret_cast<uintptr_t>(src) & 15u);
-    const u32x4 *from = reinterpret_cast<const u32x4 *>(src - a);
-    u32x4 *to = reinterpret_cast<u32x4 *>(dst16);
-    const int blocks = n > 0 ? (int)((a + (unsigned)n + 15u) >> 4) : 0;
-    for (int k = l; k < blocks; k += G) to[k] = from[k];
-    return dst16 + a;
-}
+using namespace dpx_band;
 
 template <int C, bool EXT>
 struct BdirState {
@@ -295,13 +277,6 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_bdir_fill(const dpx_fill_a
     }
 }
 
-/* ---- geometry shared by the walk and the export: a cell (i, j), borders included, is in the band when |i - j| <= B-1; the fill stores a
- * code for the in-band cells with i, j >= 1 ---- */
-__device__ __forceinline__ bool bdir_in_band(const int i, const int j, const int band) {
-    const int dlt = i - j;
-    return dlt <= band - 1 && -dlt <= band - 1;
-}
-
 /* -----------------------------------------------------------------------------------------------------
  * Traceback: one WAVE per pair, k_traceback_dir's run scheme (dpx_dir_kernels.hip) over an LDS ring of code chunks.  The walk moves to
  * strictly smaller anti-diagonals and one chunk holds Gd whole anti-diagonals of the band, so the chunks a path needs are known in
@@ -349,7 +324,7 @@ __global__ void __launch_bounds__(64) k_bdir_traceback(const dpx_fill_args a, in
     };
     /* the code of cell (ci, cj): -1 when it has none (border, outside the band or the matrix), -2 when its chunk is below the ring */
     auto code = [&](const int ci, const int cj) -> int {
-        if (ci < 1 || cj < 1 || !bdir_in_band(ci, cj, B)) return -1;
+        if (ci < 1 || cj < 1 || !in_band(ci, cj, B)) return -1;
         if (((ci + cj - 2) >> sg) < (hTop - 1) * kHalf) return -2;
         int sh;
         const uint64_t off = dpx_banddir_byte(ci, cj, B, DPX_BANDDIR_CHUNK_BYTES, &sh);
@@ -423,7 +398,7 @@ __global__ void __launch_bounds__(256) k_bdir_export(const unsigned char *codes,
     for (uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (uint64_t)gridDim.x * blockDim.x) {
         const int i = (int)(idx / (uint64_t)(n + 1)), j = (int)(idx % (uint64_t)(n + 1));
         uint8_t v = 0;
-        if (bdir_in_band(i, j, band)) {
+        if (in_band(i, j, band)) {
             if (i == 0 || j == 0) {
                 v = (which != 0 || (i | j) == 0) ? 0 : (j == 0 ? 4 : 3); /* column 0: QUERY_DELETION, row 0: QUERY_INSERTION */
             } else if ((which == 1 && i - j == band - 1) || (which == 2 && j - i == band - 1)) {
@@ -444,6 +419,7 @@ __global__ void __launch_bounds__(256) k_bdir_export(const unsigned char *codes,
     }
 }
 
+/* (a direction batch sizes its LDS per wave, not as a four-wave request) */
 template <class K>
 hipError_t launch_bdir_kernel(K kernel, const dpx_fill_args &a, hipStream_t s) {
     const unsigned wpb = a.wavesPerBlock ? a.wavesPerBlock : 1u;
@@ -457,24 +433,13 @@ hipError_t launch_bdir_kernel(K kernel, const dpx_fill_args &a, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <int C>
-hipError_t launch_bdir_C(const dpx_fill_args &a, bool ext, hipStream_t s) {
-    const bool pb = ((a.band + 1) & 1) != 0; /* parity of step A = 0 */
-    if (pb) return ext ? launch_bdir_kernel(k_bdir_fill<C, true, true>, a, s) : launch_bdir_kernel(k_bdir_fill<C, true, false>, a, s);
-    return ext ? launch_bdir_kernel(k_bdir_fill<C, false, true>, a, s) : launch_bdir_kernel(k_bdir_fill<C, false, false>, a, s);
-}
-
 } // namespace
 
 hipError_t dpx_launch_bdir_fill(const dpx_fill_args &a, int C, bool ext, hipStream_t stream) {
     if (a.numPairs <= 0) return hipSuccess;
-    switch (C) {
-    case 1: return launch_bdir_C<1>(a, ext, stream);
-    case 2: return launch_bdir_C<2>(a, ext, stream);
-    case 4: return launch_bdir_C<4>(a, ext, stream);
-    case 8: return launch_bdir_C<8>(a, ext, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_fill(C, a.band, ext, [&](auto c, auto pb, auto e) {
+        return launch_bdir_kernel(k_bdir_fill<decltype(c)::value, decltype(pb)::value, decltype(e)::value>, a, stream);
+    });
 }
 
 hipError_t dpx_launch_bdir_traceback(const dpx_fill_args &a, int numPairs, const uint64_t *tbOff, char *tb, int32_t *tbLen, hipStream_t stream) {

@@ -9,7 +9,7 @@
  * (0, 0) included (so it is >= 0), and the end cell is the first cell in row-major order that holds it.  There is no admission rule:
  * when |m - n| >= B the corner (m, n) is simply never reached.
  *
- * Schedule, stores and the three phases are k_banw_fill's (anti-diagonals a = i+j, slot s = (i-j+B-1)>>1, lane l owns the C = ceil(B/64)
+ * The step is dpx_band_affine.hpp's slot_key_step, which k_zext_fill runs too.  Schedule, stores and the three phases are k_banw_fill's (anti-diagonals a = i+j, slot s = (i-j+B-1)>>1, lane l owns the C = ceil(B/64)
  * slots [l*C, l*C+C), two values per step by DPP, border slots hand on o + a*e in the head phase, 16-byte stores of three planes in the
  * band layout of dpx_layout.h).  In place of BANW's end-cell pick-up every slot keeps k_basw_fill's running key (score << 16 | 0xFFFF -
  * step): a slot sees the cells of its two diagonals in row order -- border slots too -- so the first maximum of a slot is its first
@@ -23,138 +23,11 @@
  * low 16 bits are 0, so it enters as score 0.  Only a cell with H > 0 can displace (0, 0), so scores <= 0 need not be told apart, and the
  * signed form saves the max(h, 0) of the unsigned one.
  */
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "dpx_kernels.h"
-#include "dpx_layout.h"
-#include "dpx_prims.hpp"
+#include "dpx_band_affine.hpp"
 
 namespace {
 
-using dpx::pack_lo16;
-using dpx::wave_shl1;
-using dpx::wave_shr1;
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-/* a string copied into LDS with aligned 16-byte loads; it lands `src & 15` bytes into the buffer (as in dpx_kernels.hip) */
-__device__ __forceinline__ unsigned char *stage_bytes(unsigned char *dst16, const unsigned char *src, const int n, const int l, const int G) {
-    const unsigned a = (unsigned)(reinterpret_cast<uintptr_t>(src) & 15u);
-    const u32x4 *from = reinterpret_cast<const u32x4 *>(src - a);
-    u32x4 *to = reinterpret_cast<u32x4 *>(dst16);
-    const int blocks = n > 0 ? (int)((a + (unsigned)n + 15u) >> 4) : 0;
-    for (int k = l; k < blocks; k += G) to[k] = from[k];
-    return dst16 + a;
-}
-
-/* eight int32 values -> eight int16, one 16-byte store */
-__device__ __forceinline__ void store8(int16_t *dst, const int (&v)[8]) {
-    u32x4 w = {pack_lo16(v[0], v[1]), pack_lo16(v[2], v[3]), pack_lo16(v[4], v[5]), pack_lo16(v[6], v[7])};
-    *reinterpret_cast<u32x4 *>(dst) = w;
-}
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        unsigned long long o = __shfl_xor(v, off, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-/* (score, min row, min column) as one unsigned key; score > 0 */
-__device__ __forceinline__ unsigned long long end_key(const int hv, const int i, const int j) {
-    return ((unsigned long long)(unsigned)hv << 40) | ((unsigned long long)(0xFFFFFu - (unsigned)i) << 20) |
-           (unsigned long long)(0xFFFFFu - (unsigned)j);
-}
-
-template <int C>
-struct BaxtState {
-    int prevH[C], prev2H[C]; /* H on anti-diagonals a-1 and a-2 */
-    int prevI[C], prevD[C];  /* I and D on anti-diagonal a-1 */
-    int qch[C], rch[C];      /* query / reference character of each slot's cell */
-    int key[C];              /* running signed max of (H << 16 | 0xFFFF - A): max score, then earliest step */
-    int lim;                 /* B-1 - lane*C: slot c is inside the band on a step of parity p when c + p <= lim */
-};
-
-/* INTERIOR: every in-band slot of this anti-diagonal lies inside the matrix, so validity is one compare against the per-lane
- * constant `lim` instead of two against the step's slot window, and there is no border slot */
-template <int C, bool P1, bool INTERIOR>
-__device__ __forceinline__ void baxt_step(BaxtState<C> &st, const int A, int &i0, int &j0, const int lane, const int m, const int n,
-                                          const int B, const int match, const int mismatch, const int o, const int oe, const int e,
-                                          const unsigned char *qL, const unsigned char *rL, int *outH, int *outI, int *outD) {
-    const int p = P1 ? 1 : 0;
-    if constexpr (P1) i0++; else j0++;
-    const int smin = INTERIOR ? 0 : max(max(1 - i0, j0 - n), 0);
-    const int smax = INTERIOR ? 0 : min(min(m - i0, j0 - 1), B - 1 - p);
-    /* the in-band border cells of this anti-diagonal: (0, a) in slot -i0 and (a, 0) in slot j0, both H = o + a * e, while a <= B-1 */
-    const int a = A + 2;
-    const int bord = (INTERIOR || a > B - 1) ? DPX_NEG : o + a * e;
-    const int sTop = (INTERIOR || a > n) ? -1 : -i0, sLeft = (INTERIOR || a > m) ? -1 : j0;
-    const int lo = smin - lane * C, cnt = max(smax - smin + 1, 0), cTop = sTop - lane * C, cLeft = sLeft - lane * C;
-    int upH[C], upD[C], leftH[C], leftI[C];
-    if constexpr (P1) {
-        const int newq = INTERIOR ? qL[i0 + 64 * C - 2] : qL[min(max(i0 + 64 * C - 2, 0), m - 1)];
-        const int tq = wave_shl1(st.qch[0], newq);
-#pragma unroll
-        for (int c = 0; c < C - 1; c++) st.qch[c] = st.qch[c + 1];
-        st.qch[C - 1] = tq;
-        const int nbH = wave_shl1(st.prevH[0], DPX_NEG);
-        const int nbI = wave_shl1(st.prevI[0], DPX_NEG);
-#pragma unroll
-        for (int c = 0; c < C; c++) {
-            upH[c] = st.prevH[c];
-            upD[c] = st.prevD[c];
-            leftH[c] = (c < C - 1) ? st.prevH[c + 1] : nbH;
-            leftI[c] = (c < C - 1) ? st.prevI[c + 1] : nbI;
-        }
-    } else {
-        const int newr = INTERIOR ? rL[j0 - 1] : rL[min(max(j0 - 1, 0), n - 1)];
-        const int tr = wave_shr1(st.rch[C - 1], newr);
-#pragma unroll
-        for (int c = C - 1; c > 0; c--) st.rch[c] = st.rch[c - 1];
-        st.rch[0] = tr;
-        const int nbH = wave_shr1(st.prevH[C - 1], DPX_NEG);
-        const int nbD = wave_shr1(st.prevD[C - 1], DPX_NEG);
-#pragma unroll
-        for (int c = 0; c < C; c++) {
-            leftH[c] = st.prevH[c];
-            leftI[c] = st.prevI[c];
-            upH[c] = (c > 0) ? st.prevH[c - 1] : nbH;
-            upD[c] = (c > 0) ? st.prevD[c - 1] : nbD;
-        }
-    }
-    const int negA = 0xFFFF - A;
-#pragma unroll
-    for (int c = 0; c < C; c++) {
-        const int sc = (st.qch[c] == st.rch[c]) ? match : mismatch;
-        int d = max(upH[c] + oe, upD[c] + e);
-        int ii = max(leftH[c] + oe, leftI[c] + e);
-        int h = max(max(d, ii), st.prev2H[c] + sc); /* (no floor; the diagonal neighbour of an in-band cell is in band, so h is finite) */
-        if constexpr (INTERIOR) {
-            const bool valid = (c + p) <= st.lim;
-            h = valid ? h : DPX_NEG;
-            d = valid ? d : DPX_NEG;
-            ii = valid ? ii : DPX_NEG;
-        } else {
-            /* slot lane * C + c against the step's window [smin, smax] and its two border slots, as compares of the constant c with
-             * per-lane values: one unsigned range compare (cnt = 0 when the window is empty) */
-            const bool valid = (unsigned)(c - lo) < (unsigned)cnt;
-            h = valid ? h : ((c == cTop || c == cLeft) ? bord : DPX_NEG);
-            d = valid ? d : DPX_NEG;
-            ii = valid ? ii : DPX_NEG;
-        }
-        st.key[c] = max(st.key[c], (int)(((unsigned)h << 16) | (unsigned)negA)); /* (after the border select: border cells take part) */
-        st.prev2H[c] = st.prevH[c];
-        st.prevH[c] = h;
-        st.prevI[c] = ii;
-        st.prevD[c] = d;
-        outH[c] = h;
-        outI[c] = ii;
-        outD[c] = d;
-    }
-}
+using namespace dpx_band;
 
 template <int C, bool PB, bool STORE>
 __global__ void __launch_bounds__(DPX_FILL_THREADS) k_baxt_fill(const dpx_fill_args a) {
@@ -189,7 +62,7 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_baxt_fill(const dpx_fill_a
     const unsigned char *qL = stage_bytes(my, qry, m, lane, 64);
     const unsigned char *rL = stage_bytes(my + a.ldsRefOff, ref, n, lane, 64);
 
-    BaxtState<C> st;
+    SlotKeyState<C> st;
     st.lim = B - 1 - lane * C;
     { /* anti-diagonals a = 1 (prev: the border cells (0, 1) and (1, 0), in band when B >= 2) and a = 0 (prev2: H[0][0] = 0, which
        * shares its slot with cell (1, 1)); the character windows are those of a = 1, the first real step then slides one of them */
@@ -231,12 +104,12 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_baxt_fill(const dpx_fill_a
     }
 #define DPX_BAXT_BODY(INTERIOR_)                                                                                          \
     _Pragma("unroll") for (int g = 0; g < GG; g += 2) {                                                                  \
-        baxt_step<C, PB, INTERIOR_>(st, A0 + g, i0, j0, lane, m, n, B, match, mismatch, o, oe, e, qL, rL,                 \
+        slot_key_step<C, PB, INTERIOR_>(st, A0 + g, i0, j0, lane, m, n, B, match, mismatch, o, oe, e, qL, rL,             \
                                     &accH[(g % G) * C], &accI[(g % G) * C], &accD[(g % G) * C]);                          \
         if constexpr (STORE && G == 1) {                                                                                  \
             if (INTERIOR_ || A0 + g < numGroups) DPX_BAXT_STORE(A0 + g)                                                   \
         }                                                                                                                 \
-        baxt_step<C, !PB, INTERIOR_>(st, A0 + g + 1, i0, j0, lane, m, n, B, match, mismatch, o, oe, e, qL, rL,            \
+        slot_key_step<C, !PB, INTERIOR_>(st, A0 + g + 1, i0, j0, lane, m, n, B, match, mismatch, o, oe, e, qL, rL,        \
                                      &accH[((g + 1) % G) * C], &accI[((g + 1) % G) * C], &accD[((g + 1) % G) * C]);       \
         if constexpr (STORE) {                                                                                            \
             if (((g + 1) % G) == G - 1) {                                                                                 \
@@ -283,37 +156,11 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_baxt_fill(const dpx_fill_a
     }
 }
 
-template <class K>
-hipError_t launch_baxt_kernel(K kernel, const dpx_fill_args &a, dim3 grid, size_t lds, hipStream_t s) {
-    if (lds > 64u * 1024u) { /* opt in to more than the default 64 KiB of dynamic LDS */
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    const unsigned wpb = a.wavesPerBlock; /* `lds` is the request of a four-wave workgroup */
-    hipLaunchKernelGGL(kernel, grid, dim3(64u * wpb), lds / 4u * wpb, s, a);
-    return hipGetLastError();
-}
-
-template <int C>
-hipError_t launch_baxt_C(const dpx_fill_args &a, bool store, dim3 grid, size_t lds, hipStream_t s) {
-    const bool pb = ((a.band + 1) & 1) != 0; /* parity of step A = 0 */
-    if (pb) return store ? launch_baxt_kernel(k_baxt_fill<C, true, true>, a, grid, lds, s)
-                         : launch_baxt_kernel(k_baxt_fill<C, true, false>, a, grid, lds, s);
-    return store ? launch_baxt_kernel(k_baxt_fill<C, false, true>, a, grid, lds, s)
-                 : launch_baxt_kernel(k_baxt_fill<C, false, false>, a, grid, lds, s);
-}
-
 } // namespace
 
 hipError_t dpx_launch_baxt_fill(const dpx_fill_args &a, int C, bool store, size_t ldsBytes, hipStream_t stream) {
     if (a.numPairs <= 0) return hipSuccess;
-    const int wavesPerBlock = (int)a.wavesPerBlock;
-    dim3 grid((unsigned)((a.numPairs + wavesPerBlock - 1) / wavesPerBlock));
-    switch (C) {
-    case 1: return launch_baxt_C<1>(a, store, grid, ldsBytes, stream);
-    case 2: return launch_baxt_C<2>(a, store, grid, ldsBytes, stream);
-    case 4: return launch_baxt_C<4>(a, store, grid, ldsBytes, stream);
-    case 8: return launch_baxt_C<8>(a, store, grid, ldsBytes, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_fill(C, a.band, store, [&](auto c, auto pb, auto st) {
+        return launch_fill(k_baxt_fill<decltype(c)::value, decltype(pb)::value, decltype(st)::value>, a, a, ldsBytes, stream);
+    });
 }

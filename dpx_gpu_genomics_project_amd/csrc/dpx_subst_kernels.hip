@@ -13,57 +13,16 @@
  * address add and one signed-byte LDS read where the plain kernels have a compare and a select.  The text is produced by the walks from
  * the sequence bytes, so nothing downstream sees the codes.
  *
- * The walks are BANW's two (one lane per pair; one wave per pair with an LDS window) with mm = H_diag + s(r, q); the relation character
+ * The walks are BANW's two (one lane per pair; one wave per pair with an LDS window), the same templates under TableScorer
+ * (dpx_band_affine.hpp: band_walk_lane, band_walk_wave), with mm = H_diag + s(r, q); the relation character
  * is still the byte compare.  The one-lane walk reads table and map from global memory (1280 bytes, resident in L1 after the first
  * steps); the wave walk keeps the table in LDS behind its window and translates a lane's two characters when it loads a window.
  */
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <type_traits>
-
-#include "dpx_kernels.h"
-#include "dpx_layout.h"
-#include "dpx_prims.hpp"
+#include "dpx_band_affine.hpp"
 
 namespace {
 
-using dpx::pack_lo16;
-using dpx::wave_shl1;
-using dpx::wave_shr1;
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-/* a string copied into LDS with aligned 16-byte loads; it lands `src & 15` bytes into the buffer (as in dpx_kernels.hip) */
-__device__ __forceinline__ unsigned char *stage_bytes(unsigned char *dst16, const unsigned char *src, const int n, const int l, const int G) {
-    const unsigned a = (unsigned)(reinterpret_cast<uintptr_t>(src) & 15u);
-    const u32x4 *from = reinterpret_cast<const u32x4 *>(src - a);
-    u32x4 *to = reinterpret_cast<u32x4 *>(dst16);
-    const int blocks = n > 0 ? (int)((a + (unsigned)n + 15u) >> 4) : 0;
-    for (int k = l; k < blocks; k += G) to[k] = from[k];
-    return dst16 + a;
-}
-
-/* eight int32 values -> eight int16, one 16-byte store */
-__device__ __forceinline__ void store8(int16_t *dst, const int (&v)[8]) {
-    u32x4 w = {pack_lo16(v[0], v[1]), pack_lo16(v[2], v[3]), pack_lo16(v[4], v[5]), pack_lo16(v[6], v[7])};
-    *reinterpret_cast<u32x4 *>(dst) = w;
-}
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        unsigned long long o = __shfl_xor(v, off, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-/* (score, min row, min column) as one unsigned key; score > 0 */
-__device__ __forceinline__ unsigned long long end_key(const int hv, const int i, const int j) {
-    return ((unsigned long long)(unsigned)hv << 40) | ((unsigned long long)(0xFFFFFu - (unsigned)i) << 20) |
-           (unsigned long long)(0xFFFFFu - (unsigned)j);
-}
+using namespace dpx_band;
 
 template <int C, bool EXT>
 struct SubstState {
@@ -75,7 +34,7 @@ struct SubstState {
     int fin;                 /* !EXT: H[m][n], picked up on the last anti-diagonal by the lane that owns its slot */
 };
 
-/* banw_step / baxt_step with the table lookup.  INTERIOR: every in-band slot of this anti-diagonal lies inside the matrix, so validity
+/* banw_step / slot_key_step with the table lookup.  INTERIOR: every in-band slot of this anti-diagonal lies inside the matrix, so validity
  * is one compare against the per-lane constant `lim`; no border slot and (!EXT) not the last anti-diagonal */
 template <int C, bool P1, bool INTERIOR, bool EXT>
 __device__ __forceinline__ void subst_step(SubstState<C, EXT> &st, const int A, int &i0, int &j0, const int lane, const int m, const int n,
@@ -302,399 +261,37 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_subst_fill(const dpx_subst
     }
 }
 
-/* ---- geometry of the walks (dpx_banw_kernels.hip shares it with its export).  A cell (i, j), borders included, is in the band when |i - j| <= B-1; the fill stores
- * the in-band cells with i, j >= 1; I on the lower edge and D on the upper edge are -infinity whatever the fill stored there ---- */
-__device__ __forceinline__ bool sb_in_band(const int i, const int j, const int band) {
-    const int dlt = i - j;
-    return dlt <= band - 1 && -dlt <= band - 1;
-}
-__device__ __forceinline__ bool sb_cell_in_band(const int i, const int j, const int band) { /* ... and has storage */
-    return i >= 1 && j >= 1 && sb_in_band(i, j, band);
-}
-/* H of the in-band border cell (i, j), i == 0 or j == 0 */
-__device__ __forceinline__ int sb_border(const int i, const int j, const int o, const int e) { return (i | j) == 0 ? 0 : o + (i + j) * e; }
-/* is `plane` of the stored cell (i, j) minus infinity? */
-__device__ __forceinline__ bool sb_edge(const int i, const int j, const int band, const int plane) {
-    return (plane == 1 && i - j == band - 1) || (plane == 2 && j - i == band - 1);
-}
-
-/* ---- traceback: one lane per pair, ANW's three-state walk (dpx_kernels.hip: tb_walk_lane) over the band layout, with ANW's two tails.
- * The walk stands on stored cells only; the neighbours it reads are in band (the diagonal one always; the left / upper one because the
- * gap it came through is finite) or border cells, which open the gap. ---- */
-struct SubstView {
-    const int16_t *mat;
-    uint64_t off;
-    uint32_t cs;
-    int band, o, e;
-    /* a stored cell, or (plane 0) an in-band border cell */
-    __device__ __forceinline__ int get(int i, int j, int plane) const {
-        if (i == 0 || j == 0) return plane == 0 ? sb_border(i, j, o, e) : DPX_NEG;
-        if (sb_edge(i, j, band, plane) || !sb_in_band(i, j, band)) return DPX_NEG;
-        return (int)mat[off + dpx_band_plane_index(i, j, band, plane, cs)];
-    }
-};
-
-/* a byte string read back to front through one register: four characters per aligned dword load */
-struct CharWin {
-    const unsigned char *s;
-    uintptr_t at = 1;
-    uint32_t w = 0;
-    __device__ __forceinline__ int get(int x) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(s + x), al = a & ~(uintptr_t)3;
-        if (al != at) { at = al; w = *reinterpret_cast<const uint32_t *>(al); } /* never leaves the 256-byte aligned arena */
-        return (int)((w >> (8 * (int)(a & 3))) & 0xFFu);
-    }
-};
-
+/* the one-lane walk reads table and map from global memory (1280 bytes, resident in L1 after the first steps) */
 __global__ void k_subst_traceback(const dpx_subst_args sa, int numPairs, const int32_t *endRow, const int32_t *endCol,
                                   const uint64_t *tbOff, char *tb, int32_t *tbLen) {
-    const dpx_fill_args &a = sa.f;
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= numPairs) return;
-    const dpx_pair_dev pr = a.pairs[p];
-    const int n = pr.n, m = pr.m, band = a.band;
-    const unsigned char *ref = reinterpret_cast<const unsigned char *>(a.seq + pr.refIdx);
-    const unsigned char *qry = reinterpret_cast<const unsigned char *>(a.seq + pr.qryIdx);
-    const int cap = (m + n + 1 + 3) & ~3; /* line capacity, dword-aligned like tbOff[] */
-    char *lr = tb + tbOff[p], *lx = lr + cap, *lq = lx + cap;
-    int pos = cap; /* lines grow from the back */
-    uint32_t accR = 0, accX = 0, accQ = 0; /* the last <= 4 characters of each line, earliest in the highest byte */
-    const int o = a.gapOpen, e = a.gapExtend;
-    const signed char *tab = reinterpret_cast<const signed char *>(sa.table);
-    const unsigned char *code = sa.codeOf;
-    const SubstView v{a.mat, pr.matOff, pr.chunkStride, band, o, e};
-#define EMIT(rc_, xc_, qc_)                                                                      \
-    {                                                                                            \
-        --pos;                                                                                   \
-        accR = (accR << 8) | (uint32_t)(unsigned char)(rc_);                                     \
-        accX = (accX << 8) | (uint32_t)(unsigned char)(xc_);                                     \
-        accQ = (accQ << 8) | (uint32_t)(unsigned char)(qc_);                                     \
-        if ((pos & 3) == 0) {                                                                    \
-            *reinterpret_cast<uint32_t *>(lr + pos) = accR;                                      \
-            *reinterpret_cast<uint32_t *>(lx + pos) = accX;                                      \
-            *reinterpret_cast<uint32_t *>(lq + pos) = accQ;                                      \
-        }                                                                                        \
-    }
-    int i = endRow[p], j = endCol[p];
-    CharWin qw{qry}, rw{ref};
-    int cur = 0; /* 0 SCORING, 1 INSERTION, 2 DELETION */
-    while (i != 0 && j != 0) {
-        if (cur == 0) {
-            const int qc = qw.get(i - 1), rc = rw.get(j - 1);
-            const bool eq = qc == rc; /* the relation character stays the byte compare */
-            const int mm = v.get(i - 1, j - 1, 0) + (int)tab[((int)code[rc] << 5) + (int)code[qc]];
-            const int D = v.get(i, j, 2), I = v.get(i, j, 1);
-            const int vmax = max(D, mm);
-            if (I >= vmax) cur = 1;
-            else if (D >= mm) cur = 2;
-            else { EMIT(rw.get(j - 1), eq ? '*' : '|', qw.get(i - 1)); i--; j--; }
-        } else if (cur == 1) {
-            const bool open = (j == 1) || (v.get(i, j - 1, 0) + o + e >= v.get(i, j - 1, 1) + e); /* (a border neighbour opens the gap) */
-            if (open) cur = 0;
-            EMIT(rw.get(j - 1), ' ', '_'); j--;
-        } else {
-            const bool open = (i == 1) || (v.get(i - 1, j, 0) + o + e >= v.get(i - 1, j, 2) + e);
-            if (open) cur = 0;
-            EMIT('_', ' ', qw.get(i - 1)); i--;
-        }
-    }
-    while (i > 0) { EMIT('_', ' ', qw.get(i - 1)); i--; }  /* column-0 border: QUERY_DELETION */
-    while (j > 0) { EMIT(rw.get(j - 1), ' ', '_'); j--; }  /* row-0 border: QUERY_INSERTION */
-#undef EMIT
-    if (pos & 3) { /* the 1-3 newest characters have not filled a dword: the newest sits in the lowest byte, at `pos` */
-        const int left = 4 - (pos & 3);
-        for (int t = 0; t < left; t++) {
-            lr[pos + t] = (char)(accR >> (8 * t)); lx[pos + t] = (char)(accX >> (8 * t)); lq[pos + t] = (char)(accQ >> (8 * t));
-        }
-    }
-    tbLen[p] = cap - pos;
+    band_walk_lane(sa.f, TableScorer{reinterpret_cast<const signed char *>(sa.table), sa.codeOf}, numPairs, endRow, endCol, tbOff, tb, tbLen);
 }
 
-/* -----------------------------------------------------------------------------------------------------
- * Wave-cooperative traceback: k_traceback_wave's scheme (dpx_kernels.hip) for the three band-layout planes.  One WAVE owns a pair; lane c
- * fetches column cLo + c of a window of 48 rows x 64 columns of H, I and D around the walker into LDS (one 112-byte line per column and
- * plane; in-band border cells carry their H, every other cell without storage and every edge I / D is -32768, the window's minus
- * infinity, which cell() turns into DPX_NEG) -- only the three 8-row groups around the walker's diagonal unless the
- * walk left the last window sideways -- and the walk takes RUNS: every lane decides one cell of the line the path would follow next (the
- * walker's diagonal in SCORING, its row in INSERTION, its column in DELETION) and a ballot gives the number of steps the path really
- * follows.  The band layout has no 16-byte column pieces (the rows of a column lie on consecutive anti-diagonals): 2-byte loads through
- * dpx_band_plane_index, as the linear-gap banded walk does.  Unlike k_basw_traceback_wave's window, a cell without storage must not read 0:
- * scores are negative here, and a 0 in I or D would win "I >= max(D, mm)".  After the runs come ANW's two tails (the rest of column 0 as
- * deletions, the rest of row 0 as insertions), written by all lanes at once.
- * ----------------------------------------------------------------------------------------------------- */
-struct SubstWin {
-    static constexpr int G = 6;             /* row groups of a window */
-    static constexpr int GL = 3;            /* row groups of a banded (diagonal-following) window column */
-    static constexpr int WR = 8 * G;        /* rows R0+1 .. R0+WR; columns cLo .. cLo+63, one per lane */
-    static constexpr int CS = WR + 8;       /* int16 elements between two columns in LDS */
-    static constexpr int kBytes = 3 * 64 * CS * 2;
-};
-
+/* the wave walk keeps the table in LDS behind its window and reads the map from global memory */
 __global__ void __launch_bounds__(64) k_subst_traceback_wave(const dpx_subst_args sa, int numPairs, const int32_t *endRow, const int32_t *endCol,
                                                              const uint64_t *tbOff, char *tb, int32_t *tbLen) {
-    const dpx_fill_args &a = sa.f;
-    constexpr int G = SubstWin::G, GL = SubstWin::GL, WR = SubstWin::WR, CS = SubstWin::CS;
     extern __shared__ __attribute__((aligned(16))) unsigned char smemTb[];
-    int16_t *win = reinterpret_cast<int16_t *>(smemTb); /* win[(plane * 64 + (jj - cLo)) * CS + (ii - R0 - 1)] = plane[ii][jj] */
-    const signed char *tabL = reinterpret_cast<const signed char *>(smemTb + SubstWin::kBytes); /* the table, behind the window */
-    const unsigned char *code = sa.codeOf;
-    const int p = blockIdx.x;
-    const int lane = threadIdx.x;
-    if (p >= numPairs) return;
-    reinterpret_cast<u32x4 *>(smemTb + SubstWin::kBytes)[lane] = reinterpret_cast<const u32x4 *>(sa.table)[lane]; /* 64 x 16 B = the 1-KiB table; load_window's fences order it before the first read */
-    const dpx_pair_dev pr = a.pairs[p];
-    const int n = pr.n, m = pr.m, B = a.band;
-    const unsigned char *ref = reinterpret_cast<const unsigned char *>(a.seq + pr.refIdx);
-    const unsigned char *qry = reinterpret_cast<const unsigned char *>(a.seq + pr.qryIdx);
-    const int16_t *base = a.mat + pr.matOff;
-    const uint32_t cs = pr.chunkStride;
-    const int cap = (m + n + 1 + 3) & ~3;
-    char *lr = tb + tbOff[p], *lx = lr + cap, *lq = lx + cap;
-    int pos = cap;
-    const int g = a.gapOpen, ext = a.gapExtend;
-    constexpr uint32_t kNegInf16 = 0x8000u; /* -32768: below every finite value the range check admits */
-    int i = __builtin_amdgcn_readfirstlane(endRow[p]), j = __builtin_amdgcn_readfirstlane(endCol[p]);
-    int R0 = 1 << 28, cLo = 1 << 28;
-    int diag0 = 0;         /* i - j of the cell the window was anchored on */
-    bool banded = false;   /* ... and whether only the groups around that diagonal were fetched */
-    bool wantFull = false; /* the walk left the last window sideways (a long gap): fetch whole columns next time */
-    uint32_t chR = 0u, chQ = 0u; /* reference character of this lane's column; query character of window row `lane` (its code in bits 8..) */
-    uint32_t cdR = 0u;           /* code << 5 of chR */
-    auto stored = [&](const int ii, const int jj) -> bool { return ii <= m && jj <= n && sb_cell_in_band(ii, jj, B); };
-    /* the loads of NPL planes (from plane PL0) of a window, nothing else: every load is in flight before the wave waits for the first */
-    auto issue = [&](auto pl0C, auto nplC, auto cntC, auto &raw, const int gBase, const int gFirst, const int jc) {
-        constexpr int PL0 = decltype(pl0C)::value, NPL = decltype(nplC)::value, CNT = decltype(cntC)::value;
-#pragma unroll
-        for (int gi = 0; gi < CNT; gi++) {
-#pragma unroll
-            for (int e = 0; e < 8; e++) {
-                const int ii2 = (gBase + gFirst + gi) * 8 + 1 + e;
-                const bool ok = stored(ii2, jc);
-                const int16_t *at = ok ? base + dpx_band_plane_index(ii2, jc, B, PL0, cs) : a.mat; /* (no storage: the pool's first bytes, masked below) */
-#pragma unroll
-                for (int pl = 0; pl < NPL; pl++)
-                    raw[(pl * CNT + gi) * 8 + e] = (uint32_t)*reinterpret_cast<const uint16_t *>(at + (ok ? pl * DPX_BAND_PLANE_ELEMS : 0));
-            }
-        }
-    };
-    /* what issue() loaded becomes the window in LDS: stored cells (edge I / D as minus infinity), the H of in-band border cells, minus
-     * infinity everywhere else */
-    auto commit = [&](auto pl0C, auto nplC, auto cntC, const auto &raw, const int gBase, const int gFirst, const int jc) {
-        constexpr int PL0 = decltype(pl0C)::value, NPL = decltype(nplC)::value, CNT = decltype(cntC)::value;
-#pragma unroll
-        for (int pl = 0; pl < NPL; pl++) {
-#pragma unroll
-            for (int gi = 0; gi < CNT; gi++) {
-                uint32_t d[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-                for (int e = 0; e < 8; e++) {
-                    const int ii2 = (gBase + gFirst + gi) * 8 + 1 + e;
-                    uint32_t val = kNegInf16;
-                    if (stored(ii2, jc)) val = sb_edge(ii2, jc, B, PL0 + pl) ? kNegInf16 : raw[(pl * CNT + gi) * 8 + e];
-                    else if (PL0 + pl == 0 && (ii2 == 0 || jc == 0) && ii2 >= 0 && jc >= 0 && ii2 <= m && jc <= n && sb_in_band(ii2, jc, B))
-                        val = (uint32_t)sb_border(ii2, jc, g, ext) & 0xFFFFu;
-                    d[e >> 1] |= val << ((e & 1) * 16);
-                }
-                *reinterpret_cast<u32x4 *>(win + ((PL0 + pl) * 64 + lane) * CS + (gFirst + gi) * 8) = u32x4{d[0], d[1], d[2], d[3]};
-            }
-        }
-    };
-    /* first fetched row group (relative to the window's first) of this lane's column in a banded window whose last column holds the
-     * diagonal's row iiDiag */
-    auto band_first = [&](const int iiDiag, const int r0) -> int {
-        const int dl = (iiDiag - r0 - 1) - 63 + lane;
-        return min(max((dl - 8) >> 3, 0), G - GL);
-    };
-    using std::integral_constant;
-    auto load_window = [&](const int ii, const int jj) {
-        const int gBase = ((ii - 1) >> 3) - (G - 1);
-        R0 = gBase * 8;
-        cLo = jj - 63;
-        const int jc = cLo + lane;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local"); /* the previous window's reads are done before it is overwritten */
-        __builtin_amdgcn_wave_barrier();
-        diag0 = ii - jj;
-        banded = !wantFull;
-        const int gFirst = banded ? band_first(ii, R0) : 0;
-        /* the lane's two characters: the query character of row R0 + 1 + lane, the reference character of its column */
-        const int qi = R0 + lane;
-        const bool okQ = lane < WR && qi >= 0 && qi < m, okR = jc >= 1 && jc <= n;
-        const uint32_t rq = *(okQ ? qry + qi : reinterpret_cast<const unsigned char *>(a.seq));
-        const uint32_t rr = *(okR ? ref + (jc - 1) : reinterpret_cast<const unsigned char *>(a.seq));
-        using I0 = integral_constant<int, 0>;
-        using I1 = integral_constant<int, 1>;
-        using I2 = integral_constant<int, 2>;
-        using I3 = integral_constant<int, 3>;
-        if (banded) { /* the usual window: three row groups of all three planes at once (72 two-byte loads in flight) */
-            uint32_t raw[3 * GL * 8];
-            issue(I0{}, I3{}, integral_constant<int, GL>{}, raw, gBase, gFirst, jc);
-            commit(I0{}, I3{}, integral_constant<int, GL>{}, raw, gBase, gFirst, jc);
-        } else { /* whole columns (after a long gap; rare): plane by plane, 48 loads in flight, to keep the kernel's registers down */
-            uint32_t raw[G * 8];
-            issue(I0{}, I1{}, integral_constant<int, G>{}, raw, gBase, gFirst, jc);
-            commit(I0{}, I1{}, integral_constant<int, G>{}, raw, gBase, gFirst, jc);
-            issue(I1{}, I1{}, integral_constant<int, G>{}, raw, gBase, gFirst, jc);
-            commit(I1{}, I1{}, integral_constant<int, G>{}, raw, gBase, gFirst, jc);
-            issue(I2{}, I1{}, integral_constant<int, G>{}, raw, gBase, gFirst, jc);
-            commit(I2{}, I1{}, integral_constant<int, G>{}, raw, gBase, gFirst, jc);
-        }
-        chR = okR ? rr : 0u;
-        cdR = (uint32_t)code[chR] << 5; /* the lane's two characters are translated here, once per window */
-        chQ = okQ ? rq : 0u;
-        chQ |= (uint32_t)code[chQ] << 8;
-        asm volatile("" : "+v"(chQ), "+v"(chR), "+v"(cdR)); /* the two characters are waited for here, not in every trip of the walk */
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-    };
-    /* rows i-1, i and columns j-1, j must lie inside the window */
-    auto need_window = [&]() -> bool {
-        if (i - 1 <= R0 || i > R0 + WR || j - 1 < cLo || j > cLo + 63) return true;
-        if (banded) { const int dev = (i - j) - diag0; if (dev < -7 || dev > 6) { wantFull = true; return true; } } /* outside the fetched groups */
-        return false;
-    };
-    auto cell = [&](const int pl, const int col, const int row) -> int {
-        const int v = (int)win[(pl * 64 + col) * CS + row];
-        return v == -32768 ? DPX_NEG : v;
-    };
-    /* number of lanes that continue a run which starts at lane `from` and goes DOWN the lanes while `on` holds (lane 0 is never on) */
-    auto run_down = [&](const bool on, const int from) -> int {
-        const unsigned long long inv = ~__builtin_amdgcn_ballot_w64(on) << (63 - from);
-        return inv ? __builtin_clzll(inv) : 64;
-    };
-    /* SCORING decision of window cell (rq, cq) (>= 1 each): 0 diagonal, 1 to INSERTION, 2 to DELETION, 3 not a cell (row / column <= 0) */
-    auto decide_cell = [&](const int rq, const int cq, int &qcOut) -> uint32_t {
-        const int qpk = __builtin_amdgcn_ds_bpermute(rq << 2, (int)chQ); /* byte | code << 8 */
-        qcOut = qpk & 0xFF;
-        const int ii = R0 + 1 + rq, jc = cLo + cq;
-        const int dg = cell(0, cq - 1, rq - 1), I = cell(1, cq, rq), D = cell(2, cq, rq);
-        const int mm = dg + (int)tabL[(int)cdR + (qpk >> 8)];
-        uint32_t d = I >= max(D, mm) ? 1u : (D >= mm ? 2u : 0u);
-        if (ii <= 0 || jc <= 0) d = 3u;
-        return d;
-    };
-    /* (r, c) = the walker's window cell; lane l decides the cell of the walker's diagonal in its own column */
-    auto decide_diag = [&](const int r, const int c, int &qcOut) -> uint32_t {
-        const int rr = r - (c - lane);
-        const bool usable = lane <= c && lane >= 1 && rr >= 1;
-        const uint32_t d = decide_cell(usable ? rr : 1, usable ? lane : 1, qcOut);
-        return usable ? d : 3u;
-    };
-    auto emit_diag = [&](const int c, const int len, const int qc) {
-        const int k = c - lane;
-        if (k >= 0 && k < len) {
-            const int at = pos - 1 - k;
-            lr[at] = (char)chR; lx[at] = ((uint32_t)qc == chR) ? '*' : '|'; lq[at] = (char)qc;
-        }
-        pos -= len;
-    };
-    auto emit_left = [&](const int c, const int len) {
-        const int k = c - lane;
-        if (k >= 0 && k < len) { const int at = pos - 1 - k; lr[at] = (char)chR; lx[at] = ' '; lq[at] = '_'; }
-        pos -= len;
-    };
-    auto emit_up = [&](const int r, const int len) {
-        const int qc = __builtin_amdgcn_ds_bpermute(max(r - lane, 0) << 2, (int)chQ) & 0xFF;
-        if (lane < len) { const int at = pos - 1 - lane; lr[at] = '_'; lx[at] = ' '; lq[at] = (char)qc; }
-        pos -= len;
-    };
-    int cur = 0; /* 0 SCORING, 1 INSERTION, 2 DELETION */
-    while (i > 0 && j > 0) {
-        if (need_window()) { load_window(i, j); wantFull = false; }
-        const int r = i - R0 - 1, c = j - cLo;
-        if (cur == 0) {
-            int qc;
-            const uint32_t d = decide_diag(r, c, qc);
-            const int run = run_down(d == 0u, c);
-            if (run) {
-                emit_diag(c, run, qc); i -= run; j -= run;
-                const int cx = c - run, rx = r - run; /* the cell that ends the run has been decided with it */
-                if (cx >= 1 && rx >= 1 && i > 0 && j > 0) {
-                    const int dx = __builtin_amdgcn_readlane((int)d, cx);
-                    if (dx == 1 || dx == 2) cur = dx;
-                }
-                continue;
-            }
-            cur = __builtin_amdgcn_readlane((int)d, c); /* 1: to INSERTION, 2: to DELETION */
-            if (cur == 3) break;                         /* (cannot happen: the walker stands on a cell) */
-        } else if (cur == 1) {
-            /* INSERTION: steps to the left along row i until (and including) the cell where the gap was opened; lane l decides the cell in
-             * column l.  The left neighbour in column 0: opened; on the band's lower edge: its I is minus infinity, opened. */
-            const int cq = max(lane, 1), jc = cLo + cq;
-            const bool opened = !sb_cell_in_band(i, jc - 1, B) || cell(0, cq - 1, r) + g + ext >= cell(1, cq - 1, r) + ext;
-            const bool usable = lane <= c && lane >= 1 && jc >= 1 && (!banded || (i - j) - diag0 + (c - lane) <= 6);
-            const int cont = run_down(usable && !opened, c); /* cells the gap passes through */
-            const bool stops = c - cont >= 1 && cLo + c - cont >= 1 && (!banded || (i - j) - diag0 + cont <= 6); /* ... then a usable cell that opened it (else: the window's edge) */
-            const int len = cont + (stops ? 1 : 0);
-            emit_left(c, len); j -= len;
-            if (stops) cur = 0;
-        } else {
-            /* DELETION: steps up along column j; lane k decides the cell k rows above the walker.  The upper neighbour in row 0: opened; on the
-             * band's upper edge: its D is minus infinity, opened. */
-            const int rq = max(r - lane, 1), ii = R0 + 1 + rq;
-            const bool opened = !sb_cell_in_band(ii - 1, j, B) || cell(0, c, rq - 1) + g + ext >= cell(2, c, rq - 1) + ext;
-            const bool usable = r - lane >= 1 && ii >= 1 && (!banded || (i - j) - diag0 - lane >= -7);
-            const unsigned long long m64 = __builtin_amdgcn_ballot_w64(!(usable && !opened)); /* first lane that ends the run */
-            const int cont = m64 ? __builtin_ctzll(m64) : 64;
-            const bool stops = r - cont >= 1 && R0 + 1 + r - cont >= 1 && (!banded || (i - j) - diag0 - cont >= -7);
-            const int len = cont + (stops ? 1 : 0);
-            emit_up(r, len); i -= len;
-            if (stops) cur = 0;
-        }
-    }
-    /* ANW's tails: the rest of column 0 as deletions, then the rest of row 0 as insertions (at most one of the two is left) */
-    for (int k = lane; k < i; k += 64) { const int at = pos - 1 - k; lr[at] = '_'; lx[at] = ' '; lq[at] = (char)qry[i - 1 - k]; }
-    pos -= max(i, 0);
-    for (int k = lane; k < j; k += 64) { const int at = pos - 1 - k; lr[at] = (char)ref[j - 1 - k]; lx[at] = ' '; lq[at] = '_'; }
-    pos -= max(j, 0);
-    if (lane == 0) tbLen[p] = cap - pos;
-}
-
-template <class K>
-hipError_t launch_subst_kernel(K kernel, const dpx_subst_args &a, dim3 grid, size_t lds, hipStream_t s) {
-    if (lds > 64u * 1024u) { /* opt in to more than the default 64 KiB of dynamic LDS */
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    const unsigned wpb = a.f.wavesPerBlock; /* `lds` is the request of a four-wave workgroup */
-    hipLaunchKernelGGL(kernel, grid, dim3(64u * wpb), lds / 4u * wpb, s, a);
-    return hipGetLastError();
-}
-
-template <int C, bool EXT>
-hipError_t launch_subst_C(const dpx_subst_args &a, bool store, dim3 grid, size_t lds, hipStream_t s) {
-    const bool pb = ((a.f.band + 1) & 1) != 0; /* parity of step A = 0 */
-    if (pb) return store ? launch_subst_kernel(k_subst_fill<C, true, true, EXT>, a, grid, lds, s)
-                         : launch_subst_kernel(k_subst_fill<C, true, false, EXT>, a, grid, lds, s);
-    return store ? launch_subst_kernel(k_subst_fill<C, false, true, EXT>, a, grid, lds, s)
-                 : launch_subst_kernel(k_subst_fill<C, false, false, EXT>, a, grid, lds, s);
-}
-
-template <bool EXT>
-hipError_t launch_subst_E(const dpx_subst_args &a, int C, bool store, dim3 grid, size_t lds, hipStream_t s) {
-    switch (C) {
-    case 1: return launch_subst_C<1, EXT>(a, store, grid, lds, s);
-    case 2: return launch_subst_C<2, EXT>(a, store, grid, lds, s);
-    case 4: return launch_subst_C<4, EXT>(a, store, grid, lds, s);
-    case 8: return launch_subst_C<8, EXT>(a, store, grid, lds, s);
-    default: return hipErrorInvalidValue;
-    }
+    band_walk_wave(sa.f, TableScorer{reinterpret_cast<const signed char *>(smemTb + BandWin::kBytes), sa.codeOf}, sa.table, smemTb, numPairs,
+                   endRow, endCol, tbOff, tb, tbLen);
 }
 
 } // namespace
 
 hipError_t dpx_launch_subst_fill(const dpx_subst_args &a, int C, bool store, bool ext, size_t ldsBytes, hipStream_t stream) {
     if (a.f.numPairs <= 0) return hipSuccess;
-    const int wavesPerBlock = (int)a.f.wavesPerBlock;
-    dim3 grid((unsigned)((a.f.numPairs + wavesPerBlock - 1) / wavesPerBlock));
-    return ext ? launch_subst_E<true>(a, C, store, grid, ldsBytes, stream) : launch_subst_E<false>(a, C, store, grid, ldsBytes, stream);
+    return dispatch_fill(C, a.f.band, store, [&](auto c, auto pb, auto st) {
+        constexpr int kC = decltype(c)::value;
+        constexpr bool kPB = decltype(pb)::value, kStore = decltype(st)::value;
+        return ext ? launch_fill(k_subst_fill<kC, kPB, kStore, true>, a, a.f, ldsBytes, stream)
+                   : launch_fill(k_subst_fill<kC, kPB, kStore, false>, a, a.f, ldsBytes, stream);
+    });
 }
 
 hipError_t dpx_launch_subst_traceback(const dpx_subst_args &a, int numPairs, int walk, const uint64_t *tbOff, char *tb, int32_t *tbLen,
                                       hipStream_t stream) {
     if (numPairs <= 0) return hipSuccess;
     if (walk == 2) /* one wave per pair with an LDS window, the table behind it */
-        hipLaunchKernelGGL(k_subst_traceback_wave, dim3((unsigned)numPairs), dim3(64), (size_t)SubstWin::kBytes + DPX_SUBST_TABLE_BYTES, stream, a,
+        hipLaunchKernelGGL(k_subst_traceback_wave, dim3((unsigned)numPairs), dim3(64), (size_t)BandWin::kBytes + DPX_SUBST_TABLE_BYTES, stream, a,
                            numPairs, a.f.endRow, a.f.endCol, tbOff, tb, tbLen);
     else
         hipLaunchKernelGGL(k_subst_traceback, dim3((unsigned)((numPairs + 63) / 64)), dim3(64), 0, stream, a, numPairs, a.f.endRow, a.f.endCol,
