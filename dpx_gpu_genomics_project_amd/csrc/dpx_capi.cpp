@@ -15,16 +15,12 @@
 #include <cstring>
 #include <map>
 #include <mutex>
-#include <numeric>
 #include <string>
 #include <utility>
 #include <vector>
 
 #include "dpx_cigar.h"
-#include "dpx_banddir.h"
-#include "dpx_dir.h"
-#include "dpx_kernels.h"
-#include "dpx_layout.h"
+#include "dpx_plan.h" /* (brings dpx_kernels.h, dpx_dir.h, dpx_banddir.h and dpx_layout.h) */
 
 namespace {
 
@@ -60,29 +56,9 @@ int bind_device(int device = -1) {
     return DPX_OK;
 }
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 constexpr size_t kSmallResultBytes = 12288; /* score / end row / end column of a small batch, as they lie in the arena (dpx_batch_output_begin) */
 
-/* Development and test knobs.  The environment is read in ONE place, when dpx_init() binds a device and again at the start of every
- * dpx_batch_create*() (the tests flip a knob between two batches of one process); everything else reads this snapshot.  -1 / 0 = not
- * set.  None of them changes a result: they force or forbid a kernel family, change the launch shape or trace the runtime. */
-struct Knobs {
-    int rowsPerLane = 0;   /* DPX_R=2|4|8|16 */
-    int packed = -1;       /* DPX_PACKED=0|1: the two-pairs-per-wave int16 kernels */
-    int lanes = -1;        /* DPX_LANES=0|1: the lane-packed (several pairs per wave) kernels */
-    int lanesPk = -1;      /* DPX_LANES_PK=0: keep the lane-packed batches on the int32 kernels */
-    int split = -1;        /* DPX_SPLIT=0|1: one wave per stripe */
-    int rowTags = -1;      /* DPX_ROW_TAGS=0: per-row start-cell keys in the packed SW kernel */
-    int rampLines = -1;    /* DPX_RAMP_LINES=0|1: skew ramps store lines / whole chunks */
-    int wavesPerBlock = 0; /* DPX_WPB=1|4 */
-    int group = 0;         /* DPX_GROUP: pairs per interleaved block of the matrix layout */
-    int tbWalk = -1;       /* DPX_TB_WALK=0|1|2 */
-    int poolProbe = -1;    /* DPX_POOL_PROBE=0|1|2: nothing / time the pool / time + shop, whatever DPX_TUNE_PLACEMENT says */
-    bool poolMalloc = false;  /* DPX_POOL=malloc: one hipMalloc instead of the chunked virtual range */
-    size_t poolChunkBytes = 0; /* DPX_POOL_CHUNK_MB */
-    int poolGuard = 0;     /* DPX_POOL_GUARD: 1 = pattern band behind the matrices, 2 = "selftest" (the band is born damaged) */
-    bool trace = false, traceVmm = false; /* DPX_TRACE / DPX_TRACE_VMM: phase timings / pool mapping calls on stderr */
-};
+/* The environment is read here and nowhere else; the snapshot everything else reads is dpx_plan.h's Knobs. */
 std::mutex g_knobsMu;
 Knobs g_knobs;
 void refresh_knobs() {
@@ -108,9 +84,6 @@ void refresh_knobs() {
     g_knobs = k;
 }
 Knobs knobs() { std::lock_guard<std::mutex> lk(g_knobsMu); return g_knobs; }
-
-/* LDS request that caps residency at 16 fill waves per CU (9 KiB per wave of the workgroup) */
-constexpr size_t kLdsFloor = 36u * 1024u * (DPX_FILL_THREADS / 64) / 4;
 
 /* Parked buffers.  The matrix pool is by far the largest allocation (22 GB for the headline batch) and hipMalloc/hipFree
  * of that size cost 50-1000 ms -- the "memory management" slice that dominated the reference's V12 profile (187 of 440 ms)
@@ -476,22 +449,13 @@ static PoolRecord fresh_pool_record(void *pool, size_t bytes) {
     return rec;
 }
 
-struct dpx_batch {
+/* A batch is its plan (dpx_plan.h: what was decided, the pair table, the launch arguments) plus everything that lives on the device. */
+struct dpx_batch : dpx_plan {
     int device = -1; /* the device the batch lives on */
-    dpx_params prm{};
-    unsigned flags = 0;
-    size_t numPairs = 0;
-    int R = 8;          /* rows per lane (full-matrix kernels) or cells per lane (band kernel) */
-    int kernelAlgo = 0; /* algorithm the kernel runs (BSW with a covering band runs as LSW) */
-    int planes = 1;
-    bool store = true;
     bool filled = false;
-    uint64_t cells = 0, matElems = 0, algBytes = 0, bandCells = 0;
     size_t matPoolBytes = 0; /* bytes of the block behind dMat (may exceed matElems*2 when a parked pool was reused) */
     size_t guardBytes = 0;   /* DPX_POOL_GUARD: pattern bytes behind the matrices, checked by dpx_batch_sync() */
     bool guardSelfTest = false;
-    int maxN = 0, maxM = 0;
-    std::vector<dpx_pair_dev> pairs; /* host mirror of the device pair table */
     char *dSeq = nullptr;
     dpx_pair_dev *dPairs = nullptr;
     int32_t *dOrder = nullptr;
@@ -509,20 +473,7 @@ struct dpx_batch {
     bool outTimed = false;
     bool fillTimed = false;
     hipStream_t lastStream = nullptr; /* stream of the most recent fill (caller's or own) */
-    dpx_fill_args args{};
-    size_t ldsBytes = 0;
-    /* packed two-pairs-per-wave path (LNW/LSW with matrices): couples of equal-shaped pairs + leftover singles */
-    bool packed = false;
-    bool split = false;    /* small batch: one workgroup per pair, one wave per stripe (k_linear_split) */
-    bool packed2 = false;  /* the sequences arrived as 2-bit codes (dpx_batch_create_packed2) */
-    bool lanesPk = false;  /* lane-packed batch on k_linear_lanes_pk (two row blocks of a pair in the halves of every register) */
-    int splitWaves = 0;
-    size_t splitLds = 0;
-    bool lanePacked = false; /* short queries: several pairs per wave (k_linear_lanes / k_affine_lanes, 8 x 8 tile layout); wave
-                              descriptors in dCouples, launch arguments in pkArgs */
-    int32_t *dCouples = nullptr;
-    dpx_fill_args pkArgs{};
-    size_t pkLdsBytes = 0;
+    int32_t *dCouples = nullptr; /* the couples of the packed kernels, or the wave descriptors of the lane-packed ones */
     /* result text (lazy): device line buffers of k_traceback, the packed blocks built from them, pinned host mirrors */
     uint64_t *dTbOff = nullptr;
     char *dTb = nullptr;
@@ -534,7 +485,6 @@ struct dpx_batch {
     bool resultsCopied = false; /* ... and of score / end row / end column, into the tail of hMeta */
     bool textCopied = false;    /* dpx_batch_output_begin() has queued the text's D2H itself (small batches) */
     bool uploadPending = false; /* ... and its one asynchronous H2D on b->stream has not been waited for by anybody yet */
-    std::vector<uint64_t> tbOff;
     char *hMeta = nullptr; /* pinned: uint64 offsets[numPairs + 1], then int32 alignment lengths[numPairs] */
     char *hOut = nullptr;  /* pinned: the packed text */
     size_t hOutBytes = 0;
@@ -561,17 +511,8 @@ struct dpx_batch {
     int substAlphabet = 0;
     unsigned char *dSubst = nullptr; /* device: the table at row stride 32 (DPX_SUBST_TABLE_BYTES), then codeOf[256] */
     size_t dSubstCap = 0;
-    size_t nSingles = 0, nCouples = 0, nLanePairs = 0, nWaves = 0; /* launch-list sizes (dpx_batch_describe) */
     PoolRecord poolRec;    /* how the matrix pool behind dMat was built / timed */
     bool tunePool = false, tuneShop = false; /* DPX_TUNE_PLACEMENT: the pool is timed / shopped for at the end of dpx_batch_create */
-    /* DPX_KEEP_DIRECTIONS: 4-bit codes in the pool behind dMat (matElems counts them in int16 units, dpx_dir.h), filled by
-     * k_linear_dir / k_affine_dir; references too long for LDS get a per-wave area of edge rows + staged reference behind the codes */
-    bool dirs = false;
-    dpx_dir_args dirArgs{};
-    size_t dirScratch = 0; /* bytes of that area (0: LDS) */
-    /* DPX_KEEP_BAND_DIRECTIONS on a BANW / BAXT band kernel: 4-bit codes in the band layout of dpx_banddir.h behind dMat, filled by
-     * k_bdir_fill through b->args (a covering BANW band is a `dirs` batch of ANW instead) */
-    bool bandDirs = false;
 };
 
 extern "C" {
@@ -727,224 +668,6 @@ int dpx_shutdown(void) {
 
 /* ------------------------------------------------------------------------------------------ batch */
 
-/* the three-plane Gotoh algorithms: ANW (global), ASW (local), BASW (local, banded), ASG (semi-global), BANW (global, banded) and BAXT
- * (extension, banded) */
-static bool is_affine(int algo) {
-    return algo == DPX_ALGO_ANW || algo == DPX_ALGO_ASW || algo == DPX_ALGO_BASW || algo == DPX_ALGO_ASG || algo == DPX_ALGO_BANW ||
-           algo == DPX_ALGO_BAXT;
-}
-/* the algorithms with a band parameter (and, unless the band covers the matrix, the anti-diagonal band kernels and layout) */
-static bool is_banded(int algo) { return algo == DPX_ALGO_BSW || algo == DPX_ALGO_BASW || algo == DPX_ALGO_BANW || algo == DPX_ALGO_BAXT; }
-/* ... of which the three-plane ones (dpx_basw_kernels.hip, dpx_banw_kernels.hip, dpx_baxt_kernels.hip: chunks of three planes, no
- * packed-int16 variant) */
-static bool is_banded_affine(int algo) { return algo == DPX_ALGO_BASW || algo == DPX_ALGO_BANW || algo == DPX_ALGO_BAXT; }
-/* ... of which the ones whose stored planes follow BANW's rules (in-band borders carry H, edge I / D and everything without storage is
- * minus infinity): k_banw_export and the k_banw_traceback walks read them */
-static bool is_banw_layout(int algo) { return algo == DPX_ALGO_BANW || algo == DPX_ALGO_BAXT; }
-
-static int validate_params(const dpx_params *p) {
-    if (!p) return DPX_ERR_INVALID;
-    if ((p->algo < DPX_ALGO_LNW || p->algo > DPX_ALGO_BANW) && p->algo != DPX_ALGO_BAXT) return DPX_ERR_INVALID; /* (8 and 9 are unassigned) */
-    if (is_banded(p->algo) && p->band < 1) return DPX_ERR_INVALID;
-    /* the int32 kernels add a weight to a cell value (|H| <= 32767 after fits_int16) and to the affine kernels' virtual
-     * -2^29 borders: weights beyond +-2^20 could wrap those sums (and no int16 matrix could hold what they produce) */
-    const long long lim = 1ll << 20;
-    for (long long w : {(long long)p->match, (long long)p->mismatch, (long long)p->gapOpen,
-                        is_affine(p->algo) ? (long long)p->gapExtend : 0ll})
-        if (w > lim || w < -lim) return DPX_ERR_RANGE;
-    return DPX_OK;
-}
-
-/* Can every value the algorithm stores for an (m x n) pair be held in an int16 cell?  Rigorous bounds: every H cell is
- * the maximum over alignment paths, so it is >= the score of the all-gap path and <= the sum of the positive
- * contributions any path can collect; the affine gap matrices are one open/extension away from an H cell. */
-static bool fits_int16(const dpx_params &p, long long m, long long n) {
-    auto pos = [](long long v) { return v > 0 ? v : 0; };
-    auto neg = [](long long v) { return v < 0 ? v : 0; };
-    const long long lim = 32767, diag = pos(std::max<long long>(p.match, p.mismatch)) * std::min(m, n);
-    if (p.algo == DPX_ALGO_LSW || p.algo == DPX_ALGO_BSW) {
-        /* 0 <= H <= best diagonal run (+ positive gaps); the kernels also pack a column / step index into 16 bits */
-        const long long top = diag + pos(p.gapOpen) * (m + n);
-        return top <= lim && n <= 65000 && (m + n) <= 65000;
-    }
-    if (p.algo == DPX_ALGO_ASW || p.algo == DPX_ALGO_BASW) { /* (BASW: a band only removes paths, and its kernel packs the step index m + n into 16 bits as BSW's does) */
-        /* 0 <= H <= hiH as for ANW; I, D >= o + e (an open from H >= 0, then extensions never below it: D = max(H + o + e, ...));
-         * I, D <= hiH + o + e * max(m, n); the 16-bit column keys as for LSW */
-        const long long o = p.gapOpen, e = p.gapExtend;
-        const long long hiH = diag + (pos(o) + pos(e)) * (m + n);
-        return neg(o + e) >= -lim && hiH + pos(o) + pos(e) * std::max(m, n) <= lim && n <= 65000 && (m + n) <= 65000;
-    }
-    if (p.algo == DPX_ALGO_LNW) {
-        const long long lo = neg(p.gapOpen) * (m + n), hi = diag + pos(p.gapOpen) * (m + n);
-        return lo >= -lim && hi <= lim;
-    }
-    if (p.algo == DPX_ALGO_BANW || p.algo == DPX_ALGO_BAXT) {
-        /* hiH is ANW's: a band only removes paths, and hiH sums the positive contributions any path can collect.
-         * loH: ANW's "every cell can fall back on the all-gap path" does not hold inside a band (that path leaves it).  A path that
-         * does stay in the band reaches every in-band cell (i, j): the diagonal from (0, 0) to (k, k), k = min(i, j), whose cells have
-         * i - j = 0, then ONE gap of |i - j| <= min(B - 1, max(m, n)) steps along row or column k, whose cells have |i' - j'| <= |i - j|.
-         * H is the maximum over in-band paths, so with w = min(match, mismatch) and g = that gap bound
-         *       H[i][j] >= k * w + (i != j ? o + |i - j| * e : 0) >= neg(w) * min(m, n) + neg(o) + neg(e) * g = loH
-         * (the in-band border cells are the case k = 0).  The diagonal term the fill and the walks form, H[i-1][j-1] + s, is >= loH by
-         * the same path with one diagonal step fewer and s in its place.  A finite I (D) is >= its open term H_left + o + e (H_up + o + e)
-         * >= loH + (o + e), and <= hiH + pos(o) + pos(e) * max(m, n) as for ANW.  So every finite stored value is >= lo >= -32767, and
-         * -32768 is free to stand for minus infinity in dpx_batch_matrix and in the walks' windows.  No m + n <= 65000: the kernel keeps
-         * no step key.
-         * BAXT: its cells are BANW's recurrence on the same band without the admission rule, and nothing above uses |m - n| <= B - 1:
-         * the path (diagonal to (k, k), then one gap of |i - j| <= B - 1 steps) reaches every in-band cell of any m x n matrix and stays
-         * in the band, and hiH holds for every path.  So the same bounds hold for every in-band H, I and D, and the score, a maximum of
-         * H values and the 0 of (0, 0), lies in [0, hiH].  k_baxt_fill keeps a signed (H << 16 | 0xFFFF - step) key per slot: H inside
-         * int16 is this check, and the step index m + n must fit 16 bits (the same 65000 as BASW's keys).
-         * Under a substitution table (dpx_batch_set_substitution) the caller passes the largest table entry as `match` and the smallest
-         * as `mismatch`, and the proofs carry over word for word: a diagonal step scores at least the minimum entry and at most the
-         * maximum, which is all that w and `diag` use. */
-        const long long o = p.gapOpen, e = p.gapExtend, g = std::min<long long>(std::max<long long>(p.band - 1, 0), std::max(m, n));
-        const long long loH = neg(std::min<long long>(p.match, p.mismatch)) * std::min(m, n) + neg(o) + neg(e) * g;
-        const long long hiH = diag + (pos(o) + pos(e)) * (m + n);
-        if (p.algo == DPX_ALGO_BAXT && m + n > 65000) return false;
-        return loH + neg(o + e) >= -lim && hiH + pos(o) + pos(e) * std::max(m, n) <= lim;
-    }
-    /* ANW, and ASG: every ASG cell H[i][j] is the best score of an alignment path between a reference substring ref[a:j] and the query
-     * prefix qry[0:i] (the free row 0 chooses a), or the column-0 border, an all-gap path.  Such a path has at most m + n steps and at
-     * most min(m, n) diagonal ones, so ANW's bounds hold for it: hiH sums the positive contributions a path can collect, loH is below
-     * the all-gap path every cell can fall back on (o + i*e after a free row 0, or ANW's own).  I and D are one open / extension away
-     * as for ANW.  ASG's fills also keep ((H + 32768) << 16 | 65535 - j) keys for row m: H inside int16 is this check, and the column
-     * must fit 16 bits (the same 65000 as LSW's and ASW's keys). */
-    const long long o = p.gapOpen, e = p.gapExtend;
-    const long long loH = 2 * neg(o) + neg(e) * (m + n), hiH = diag + (pos(o) + pos(e)) * (m + n);
-    const long long lo = loH + neg(o + e), hi = hiH + pos(o) + pos(e) * std::max(m, n);
-    if (p.algo == DPX_ALGO_ASG && n > 65000) return false;
-    return lo >= -lim && hi <= lim;
-}
-
-/* The same rigorous bounds for a DPX_KEEP_DIRECTIONS batch: int32 arithmetic, checked against 2^28 so that every value stays clear
- * of the affine kernels' -2^29 virtual borders; no column limit (no 16-bit column keys). */
-static bool fits_dir(const dpx_params &p, long long m, long long n) {
-    auto pos = [](long long v) { return v > 0 ? v : 0; };
-    auto neg = [](long long v) { return v < 0 ? v : 0; };
-    const long long lim = 1ll << 28, diag = pos(std::max<long long>(p.match, p.mismatch)) * std::min(m, n);
-    if (p.algo == DPX_ALGO_LSW) return diag + pos(p.gapOpen) * (m + n) <= lim;
-    if (p.algo == DPX_ALGO_ASW) { /* fits_int16's ASW bounds without the column keys (the direction fill keeps an int32 column per row) */
-        const long long o = p.gapOpen, e = p.gapExtend;
-        const long long hiH = diag + (pos(o) + pos(e)) * (m + n);
-        return neg(o + e) >= -lim && hiH + pos(o) + pos(e) * std::max(m, n) <= lim;
-    }
-    if (p.algo == DPX_ALGO_LNW) return neg(p.gapOpen) * (m + n) >= -lim && diag + pos(p.gapOpen) * (m + n) <= lim;
-    if (p.algo == DPX_ALGO_BANW || p.algo == DPX_ALGO_BAXT) {
-        /* DPX_KEEP_BAND_DIRECTIONS: fits_int16's loH / hiH argument for the band (the all-gap path leaves it; the diagonal to (k, k) and
-         * one gap of at most min(B - 1, max(m, n)) steps does not), in int32.  No m + n limit for BAXT: k_bdir_fill keeps the value and
-         * the position of its running maximum in separate registers. */
-        const long long o = p.gapOpen, e = p.gapExtend, g = std::min<long long>(std::max<long long>(p.band - 1, 0), std::max(m, n));
-        const long long loH = neg(std::min<long long>(p.match, p.mismatch)) * std::min(m, n) + neg(o) + neg(e) * g;
-        const long long hiH = diag + (pos(o) + pos(e)) * (m + n);
-        return loH + neg(o + e) >= -lim && hiH + pos(o) + pos(e) * std::max(m, n) <= lim;
-    }
-    /* ANW, and ASG by the argument in fits_int16 (its direction fill keeps row m's first maximum as an int32 value and column: no key, no column limit) */
-    const long long o = p.gapOpen, e = p.gapExtend;
-    const long long loH = 2 * neg(o) + neg(e) * (m + n), hiH = diag + (pos(o) + pos(e)) * (m + n);
-    return loH + neg(o + e) >= -lim && hiH + pos(o) + pos(e) * std::max(m, n) <= lim;
-}
-
-/* The "+Opt" packed kernel (k_linear_fill_pk) does EVERY add in wrapping 16-bit halves (v_pk_add_i16 / v_pk_mad_i16), so
- * not only the stored H values but the weights themselves and the intermediates `diag + s` and `max(up, left) + gap`
- * must stay inside int16: H lies in [lo, hi] (fits_int16's bounds), an intermediate is one weight away from an H value
- * or a border value.  Batches that fail this run on the int32 kernels (same results, whatever the batch size). */
-static bool packed_safe(const dpx_params &p, long long m, long long n) {
-    if (p.algo != DPX_ALGO_LNW && p.algo != DPX_ALGO_LSW && p.algo != DPX_ALGO_BSW) return false;
-    auto pos = [](long long v) { return v > 0 ? v : 0; };
-    auto neg = [](long long v) { return v < 0 ? v : 0; };
-    const long long wmin = std::min<long long>({p.match, p.mismatch, p.gapOpen, 0}), wmax = std::max<long long>({p.match, p.mismatch, p.gapOpen, 0});
-    if (wmin < -32768 || wmax > 32767) return false;
-    const long long diag = pos(std::max<long long>(p.match, p.mismatch)) * std::min(m, n);
-    const long long hi = diag + pos(p.gapOpen) * (m + n);
-    const long long lo = p.algo == DPX_ALGO_LNW ? neg(p.gapOpen) * (m + n) : 0;
-    return lo + wmin >= -32768 && hi + wmax <= 32767 && n <= 65535;
-}
-
-/* rows per lane of the lane-packed kernels: a pair of m rows takes ceil(m / 8) lanes (m <= 512); 16 rows per lane (two row
- * blocks) for the linear-gap kernels up to 1024 rows */
-static int lanes_rows(int maxM, int algo) { return (maxM <= 512 || is_affine(algo)) ? 8 : 16; }
-
-/* Pack pairs (`idx`, sorted by reference length, longest first) into waves of 64 lanes for the lane-packed kernels:
- * a pair takes ceil(m / R) consecutive lanes, a wave up to DPX_WAVE_SLOTS pairs whose staged references fit the wave's
- * LDS reference area.  Best fit over a window of open waves, so that the pairs of a wave have nearly the same reference
- * length (the wave runs max(n + lanes) steps) and the lanes fill up: 100k short reads (queries 80-130) reach 94 % lane
- * occupancy.  Returns the reference area in bytes; `idx` comes back in slot order (= matrix placement order). */
-static size_t pack_waves(const std::vector<dpx_pair_dev> &pairs, std::vector<int32_t> &idx, int R, int maxN, size_t refFloor, int maxSlots,
-                         std::vector<dpx_wave_desc> &waves) {
-    struct Bin { dpx_wave_desc d; int lanes = 0, slots = 0; size_t ref = 0; bool closed = false; };
-    const size_t refCap = std::max<size_t>(refFloor, align_up((size_t)maxN + 31, 16)); /* bytes of staged references per wave */
-    constexpr size_t kWindow = 256; /* open waves: pairs arrive sorted by reference length, so a window keeps a wave's pairs alike */
-    std::vector<Bin> bins;          /* in opening order = emission order */
-    std::vector<int32_t> byFree[65]; /* open bins by free lanes (entries go stale when a bin moves on: checked on use) */
-    uint64_t nonEmpty = 0;           /* bit f-1: byFree[f] holds entries (the search skips the empty buckets with one ctz) */
-    size_t oldestOpen = 0, numOpen = 0;
-    bins.reserve(idx.size() / 3 + 8);
-    for (int32_t i : idx) {
-        const dpx_pair_dev &pd = pairs[i];
-        const int L = (pd.m + R - 1) / R;
-        const size_t need = align_up((size_t)pd.n + 31, 16);
-        int best = -1;
-        for (uint64_t cand = L <= 64 ? nonEmpty & (~0ull << (L - 1)) : 0; cand && best < 0; cand &= cand - 1) { /* tightest fit first */
-            const int f = __builtin_ctzll(cand) + 1;
-            std::vector<int32_t> &lst = byFree[f];
-            while (!lst.empty()) {
-                const int32_t k = lst.back();
-                const Bin &bn = bins[k];
-                if (bn.closed || 64 - bn.lanes != f) { lst.pop_back(); continue; } /* stale entry */
-                if (bn.slots >= maxSlots || bn.ref + need > refCap) break;   /* this bucket's newest bin is full in another way */
-                best = k;
-                lst.pop_back();
-                break;
-            }
-            if (lst.empty()) nonEmpty &= ~(1ull << (f - 1));
-        }
-        if (best < 0) {
-            if (numOpen >= kWindow) { /* retire the oldest open wave */
-                while (bins[oldestOpen].closed) oldestOpen++;
-                bins[oldestOpen].closed = true;
-                numOpen--;
-            }
-            bins.emplace_back();
-            memset(&bins.back().d, 0, sizeof(dpx_wave_desc));
-            best = (int)bins.size() - 1;
-            numOpen++;
-        }
-        Bin &bn = bins[best];
-        bn.d.pair[bn.slots] = i;
-        bn.d.first[bn.slots] = (uint8_t)bn.lanes;
-        bn.d.num[bn.slots] = (uint8_t)L;
-        bn.d.refOff[bn.slots] = (uint16_t)(bn.ref >> 4);
-        bn.lanes += L;
-        bn.slots++;
-        bn.ref += need;
-        if (bn.lanes < 64 && bn.slots < maxSlots) { byFree[64 - bn.lanes].push_back(best); nonEmpty |= 1ull << (64 - bn.lanes - 1); }
-        else { bn.closed = true; numOpen--; }
-    }
-    std::vector<int32_t> order;
-    order.reserve(idx.size());
-    size_t area = 0;
-    waves.reserve(bins.size());
-    for (const Bin &bn : bins) {
-        waves.push_back(bn.d);
-        for (int k = 0; k < bn.slots; k++) order.push_back(bn.d.pair[k]);
-        area = std::max(area, bn.ref);
-    }
-    idx.swap(order);
-    return area;
-}
-
-/* cells (i, j) with 1 <= i <= m, 1 <= j <= n, |i - j| <= B - 1: sum over the rows of min(n, i+B-1) - max(1, i-B+1) + 1 */
-static uint64_t band_cells(long long m, long long n, long long B) {
-    if (m <= 0 || n <= 0 || B <= 0) return 0;
-    const long long M = std::min(m, n + B - 1);                 /* rows that still reach the band */
-    const long long a = std::max(0ll, std::min(n - B + 1, M));  /* rows whose right end is i + B - 1 (not clipped at n) */
-    const long long s1 = a * (a + 1) / 2 + a * (B - 1) + (M - a) * n;
-    const long long b = std::min(B, M);                         /* rows whose left end is clipped at column 1 */
-    const long long s2 = b + (M > B ? (M - B + 1) * (M - B + 2) / 2 - 1 : 0);
-    return (uint64_t)(s1 - s2 + M);
-}
-
 /* hipMemset time of a pool (the record of a pool that a resident-batch caller is going to fill many times; 2 x 3.5 ms for 22 GB) */
 static float time_memset(void *p, size_t bytes, hipStream_t s) {
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -962,16 +685,6 @@ static float time_memset(void *p, size_t bytes, hipStream_t s) {
 }
 
 static hipError_t launch_all(dpx_batch *b, hipStream_t s);
-
-/* Waves per workgroup of the one-wave-per-pair / -couple kernels.  Their waves share nothing, so the workgroup is only the unit in which
- * the dispatcher hands waves to CUs: with four-wave workgroups 1250 waves are 313 workgroups on 256 CUs -- 57 CUs get eight waves, the
- * others four, and the launch takes as long as eight (tools/pairs_sweep.py: 2500 pairs of 1024^2 on the packed kernel 2322 GCUPS, 1900
- * pairs = 238 workgroups 3265).  Small launches therefore use one-wave workgroups (the CUs differ by at most one wave); big ones keep
- * four (a few per cent faster there: fewer workgroups to dispatch, profiles/r03/ab_nontemporal_stores_and_wg64.txt).  DPX_WPB=1|4 forces one. */
-static uint32_t fill_waves_per_block(size_t waves) {
-    { const int v = knobs().wavesPerBlock; if (v == 1 || v == 4) return (uint32_t)v; }
-    return waves <= 4096 ? 1u : 4u;
-}
 
 /* DPX_TUNE_PLACEMENT (callers that fill a resident batch many times: bench.py, iterative drivers).  The same fill runs up to
  * 27 % apart on two pools of the same construction (ANW 1000 x 1024^2: 1.05 vs 1.20 ms, alternating from one allocation to the
@@ -1151,10 +864,9 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
         if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); return DPX_ERR_NO_DEVICE; }
         if (device >= n) return DPX_ERR_INVALID;
     } else if (device != -1) return DPX_ERR_INVALID;
-    bool dirs = (flags & DPX_KEEP_DIRECTIONS) != 0;
-    const bool bandDirFlag = (flags & DPX_KEEP_BAND_DIRECTIONS) != 0;
-    if ((dirs || bandDirFlag) && (flags & DPX_SCORE_ONLY)) return DPX_ERR_INVALID;
-    if (dirs && is_banded(params->algo)) return DPX_ERR_UNSUPPORTED; /* 0x8 on a banded algorithm stays refused, with or without 0x10 */
+    const bool dirFlag = (flags & DPX_KEEP_DIRECTIONS) != 0, bandDirFlag = (flags & DPX_KEEP_BAND_DIRECTIONS) != 0;
+    if ((dirFlag || bandDirFlag) && (flags & DPX_SCORE_ONLY)) return DPX_ERR_INVALID;
+    if (dirFlag && is_banded(params->algo)) return DPX_ERR_UNSUPPORTED; /* 0x8 on a banded algorithm stays refused, with or without 0x10 */
     if (bandDirFlag && params->algo != DPX_ALGO_BANW && params->algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED; /* (BSW / BASW: not built) */
     rc = bind_device(device);
     if (rc != DPX_OK) return rc;
@@ -1164,132 +876,10 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
     PhaseTrace trace;
     dpx_batch *b = new (std::nothrow) dpx_batch();
     if (!b) return DPX_ERR_NOMEM;
+    rc = dpx_plan_batch(*params, pairs, firstPair, numPairs, numBytes, alphabet != nullptr, flags, kn, *b, t_err); /* (the batch IS the plan) */
+    if (rc != DPX_OK) { delete b; return rc; }
     b->device = t_device;
-    b->prm = *params;
-    b->flags = flags;
-    b->numPairs = numPairs;
-    b->store = !(flags & DPX_SCORE_ONLY);
-    b->planes = is_affine(params->algo) ? 3 : 1;
-    b->dirs = dirs;
-    b->pairs.resize(numPairs);
-
-    /* geometry, validation */
-    bool ragged = false;
-    for (size_t i = 0; i < numPairs; i++) {
-        const dpx_seq_pair &sp = pairs[firstPair + i];
-        if (sp.referenceSize < 0 || sp.querySize < 0 || sp.referenceIdx < 0 || sp.queryIdx < 0 ||
-            (size_t)sp.referenceIdx + (size_t)sp.referenceSize > numBytes ||
-            (size_t)sp.queryIdx + (size_t)sp.querySize > numBytes) {
-            delete b;
-            return DPX_ERR_INVALID;
-        }
-        if (params->algo == DPX_ALGO_BANW && std::llabs((long long)sp.querySize - (long long)sp.referenceSize) >= (long long)params->band) {
-            /* no global path stays inside the band: the end cell (m, n) itself is outside it */
-            t_err = "DPX_ALGO_BANW: pair " + std::to_string(i) + " (query " + std::to_string(sp.querySize) + ", reference " +
-                    std::to_string(sp.referenceSize) + ") needs band >= " +
-                    std::to_string(std::llabs((long long)sp.querySize - (long long)sp.referenceSize) + 1) + ", the batch has band " +
-                    std::to_string(params->band);
-            delete b;
-            return DPX_ERR_UNSUPPORTED;
-        }
-        if (!((dirs || bandDirFlag) ? fits_dir(*params, sp.querySize, sp.referenceSize) : fits_int16(*params, sp.querySize, sp.referenceSize))) { delete b; return DPX_ERR_RANGE; }
-        dpx_pair_dev &pd = b->pairs[i];
-        pd.refIdx = sp.referenceIdx; pd.n = sp.referenceSize;
-        pd.qryIdx = sp.queryIdx;     pd.m = sp.querySize;
-        b->maxN = std::max(b->maxN, pd.n);
-        b->maxM = std::max(b->maxM, pd.m);
-        b->cells += (uint64_t)pd.n * (uint64_t)pd.m;
-        if (pd.n != b->pairs[0].n || pd.m != b->pairs[0].m) ragged = true;
-    }
-
-    /* DPX_KEEP_BAND_DIRECTIONS: a covering BANW band takes the matrix batch's fall-back to ANW, as an ANW direction batch; every other band
-     * runs k_bdir_fill (decided below, where the band kernels are chosen) */
-    const bool bandDirCovering = bandDirFlag && params->algo == DPX_ALGO_BANW && (long long)params->band >= (long long)std::max(b->maxM, b->maxN) + 1;
-    if (bandDirCovering) { dirs = true; b->dirs = true; }
-    const bool bandDirs = bandDirFlag && !bandDirCovering;
-    trace.mark("create: validation");
-    /* rows per lane: smallest tile that keeps short queries in one stripe, 8 (or DPX_R) otherwise */
-    /* linear gaps: 16 rows per lane once a query is longer than 512 (one stripe up to 1024 rows, two 1-KiB sub-tiles per
-     * step: measured 4 % faster than 8 rows x 2 rolling stripes); the affine kernel carries three chains and stays at 8 */
-    int R = b->maxM <= 128 ? 2 : b->maxM <= 256 ? 4 : (b->maxM <= 512 || is_affine(params->algo)) ? 8 : 16;
-    if (kn.rowsPerLane) {
-        const int v = kn.rowsPerLane;
-        if (v == 2 || v == 4 || v == 8 || (v == 16 && !is_affine(params->algo))) R = v;
-    }
-    if (dirs) { /* direction kernels: LSW keeps per-row best cells and stays at <= 8 rows per lane (VGPRs), ANW at <= 8 as always */
-        R = b->maxM <= 128 ? 2 : b->maxM <= 256 ? 4 : (b->maxM <= 512 || params->algo != DPX_ALGO_LNW) ? 8 : 16;
-        const int v = kn.rowsPerLane;
-        if (v == 2 || v == 4 || v == 8 || (v == 16 && params->algo == DPX_ALGO_LNW)) R = v;
-    }
-    b->R = R;
-    int kernelAlgo = params->algo;
-    if (is_banded(params->algo)) {
-        /* (BANW: + 1, its band applies to the border cells too -- at B = max(m, n) the border cell (m, 0) or (0, n) is outside it) */
-        /* (BAXT: no covering fall-back -- no unbanded extension kernel exists; a band <= 512 that covers the matrix runs k_baxt_fill) */
-        if (params->algo != DPX_ALGO_BAXT &&
-            (long long)params->band >= (long long)std::max(b->maxM, b->maxN) + (params->algo == DPX_ALGO_BANW ? 1 : 0)) {
-            kernelAlgo = params->algo == DPX_ALGO_BSW ? DPX_ALGO_LSW : params->algo == DPX_ALGO_BASW ? DPX_ALGO_ASW : DPX_ALGO_ANW; /* the band covers every cell: identical to the unbanded recurrence */
-        } else if (params->band > 512) {
-            delete b;
-            return DPX_ERR_UNSUPPORTED; /* band kernel holds <= 8 cells per lane (band <= 512) */
-        } else {
-            b->R = dpx_band_cpl(params->band);
-            b->bandDirs = bandDirs;
-        }
-    }
-    b->kernelAlgo = kernelAlgo;
-    const bool banded = is_banded(kernelAlgo);
-    const bool bandedLinear = kernelAlgo == DPX_ALGO_BSW; /* (the packed-int16 band kernel exists for linear gaps only) */
-    const int bandPlanes = is_banded_affine(kernelAlgo) ? 3 : 1;
-
-    /* matrix placement + algorithmic bytes: int16 cells incl. borders, sequences, 16 B pair record, 12 B result */
-    for (size_t i = 0; i < numPairs; i++) {
-        dpx_pair_dev &pd = b->pairs[i];
-        pd.matOff = 0;
-        pd.chunkStride = 0;
-        pd.lanes = 64;
-        pd.rows = 0;
-        b->algBytes += (uint64_t)pd.m + (uint64_t)pd.n + 16u + 12u;
-        if (dirs) {
-            b->algBytes += ((uint64_t)(pd.m + 1) * (uint64_t)(pd.n + 1) + 1) / 2; /* half a byte per cell */
-        } else if (bandDirs) { /* half a byte per in-band cell */
-            const uint64_t inband = band_cells(pd.m, pd.n, params->band);
-            b->bandCells += inband;
-            b->algBytes += (inband + 1) / 2;
-        } else if (b->store) {
-            if (banded) { /* 2 B per in-band cell and plane */
-                const uint64_t inband = band_cells(pd.m, pd.n, params->band);
-                b->bandCells += inband;
-                b->algBytes += 2ull * (uint64_t)bandPlanes * inband;
-            } else {
-                b->algBytes += 2ull * (uint64_t)b->planes * (uint64_t)(pd.m + 1) * (uint64_t)(pd.n + 1);
-            }
-        }
-    }
-
-    /* LDS per wave: edge row(s) of int16 [n+2] + staged reference [n+128] */
-    const size_t edgeBytes = align_up((size_t)(b->maxN + 2) * 2, 16);
-    const size_t nEdges = is_affine(params->algo) ? 2 : 1; /* H and D */
-    /* (+16 everywhere: a staged string starts up to 15 bytes into its buffer, at its own address mod 16 -- stage_bytes) */
-    const size_t refBytes = align_up((size_t)b->maxN + 128 + 16, 16);
-    const size_t qBytes = align_up((size_t)b->maxM + 64 + 32, 16); /* banded kernel: staged query + 64 B of index slack */
-    const size_t rollQ = align_up((size_t)b->maxM + 64 * 16 + 32, 16); /* staged query of the rolling multi-stripe schedule */
-    const size_t perWave = banded ? qBytes + refBytes : edgeBytes * nEdges + refBytes + rollQ;
-    b->ldsBytes = perWave * (DPX_FILL_THREADS / 64);
-    /* Store-bound fills run ~2 % faster with 3-4 waves per SIMD than with 6-7 (fewer write streams in flight,
-     * profiles/README.md): cap residency at 4 workgroups per CU through the LDS request. */
-    if (b->store && !banded && !dirs && b->ldsBytes < kLdsFloor) b->ldsBytes = kLdsFloor;
-    /* direction kernels: int32 edge row(s) [n+2] + staged reference [n+192]; per wave in LDS, or -- when even a one-wave workgroup
-     * could not hold that -- in the batch's allocation */
-    const size_t dirEdgeBytes = align_up((size_t)(b->maxN + 2) * 4, 16);
-    const size_t dirPerWave = dirEdgeBytes * nEdges + align_up((size_t)b->maxN + 192, 16);
-    const bool dirGlobal = dirs && dirPerWave > 64u * 1024u;
-    if (dirs) b->ldsBytes = 0;
-    /* band directions: BANW's staging; when four waves' strings do not fit one workgroup's LDS (long references are what these batches
-     * are for) the fill runs one-wave workgroups, and the batch is refused only when one wave's strings do not fit */
-    const bool bandDirOneWave = bandDirs && b->ldsBytes > 160u * 1024u && perWave <= 160u * 1024u;
-    if (bandDirOneWave) b->ldsBytes = perWave;
-    if (b->ldsBytes > 160u * 1024u) { delete b; return DPX_ERR_UNSUPPORTED; }
+    trace.mark("create: validate+geometry+launch lists"); /* (the planner marks no phases of its own) */
 
 #define CREATE_TRY(call)                                                      \
     do {                                                                      \
@@ -1297,202 +887,18 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
         if (e__ != hipSuccess) { int r__ = hip_fail(e__, #call); dpx_batch_destroy(b); return r__; } \
     } while (0)
 
-    /* launch lists.  Packed path: couple pairs of identical (m, n); everything else runs one pair per wave, longest first. */
-    std::vector<int32_t> singles, couples;
-    /* "+Opt" packed path (two equal-shaped pairs per wave on the v_pk_*_i16 pipe).  The fill is bound by store
-     * instructions per CU-cycle, so halving the VALU work buys no cycles -- it buys clock: the chip holds ~2.3 GHz
-     * instead of ~2.1 GHz under the lighter instruction stream (profiles/README.md), 4-7 % wall time.  Used when every
-     * query fits one stripe (the packed kernel has no rolling schedule); DPX_PACKED=0/1 overrides. */
-    /* Lane-packed path (short reads, the reference's own dataset shape): queries of <= 512 rows in a batch large enough to
-     * fill the chip with a fraction of the waves run several pairs per wave, ceil(m/8) lanes each (k_linear_lanes /
-     * k_affine_lanes, tile layout); DPX_LANES=0/1 overrides. */
-    const bool linearAlgo = kernelAlgo == DPX_ALGO_LNW || kernelAlgo == DPX_ALGO_LSW;
-    const bool lanesAlgo = linearAlgo || (is_affine(kernelAlgo) && !banded); /* (ANW: k_affine_lanes, ASW: k_asw_lanes, ASG: k_asg_lanes) */
-    /* (the staged references of a wave's pairs share its LDS: keep the path to references that leave the request small) */
-    /* Packed lane kernel (round 3, k_linear_lanes_pk): 16 rows per lane as two 8-row blocks of the SAME pair in the two halves of every
-     * register.  Needs the 16-bit wrapping adds to be safe (packed_safe), room below the smallest border for its "minus infinity"
-     * (the low half's column 0), and for SW: score * 8 + 7 in 16 bits (row tags) and gap <= 0, mismatch <= 0 (rows past the query's
-     * end are not masked: with such weights they never exceed the real rows above them).  DPX_LANES_PK=0 keeps the int32 kernels. */
-    bool lanesPk = false;
-    if (linearAlgo && b->store && !dirs && b->maxM > 0 && b->maxM <= 1024) {
-        dpx_params kp = *params;
-        kp.algo = kernelAlgo;
-        auto pos = [](long long v) { return v > 0 ? v : 0; };
-        const long long wmin = std::min<long long>({params->match, params->mismatch, params->gapOpen, 0});
-        const long long wmax = std::max<long long>({params->match, params->mismatch, params->gapOpen, 0});
-        const long long lowest = kernelAlgo == DPX_ALGO_LNW ? std::min<long long>(params->gapOpen, 0) * ((long long)b->maxM + b->maxN) : 0;
-        const long long top = pos(std::max<long long>(params->match, params->mismatch)) * std::min<long long>(b->maxM, b->maxN) +
-                              pos(params->gapOpen) * ((long long)b->maxM + b->maxN);
-        lanesPk = packed_safe(kp, b->maxM, b->maxN) && (-32768 - wmin + wmax <= lowest) &&
-                  (kernelAlgo != DPX_ALGO_LSW || (top * 8 + 7 <= 65535 && params->gapOpen <= 0 && params->mismatch <= 0));
-        if (kn.lanesPk >= 0) lanesPk = lanesPk && kn.lanesPk != 0;
-    }
-    const int kLanesR = lanesPk ? 16 : lanes_rows(b->maxM, kernelAlgo);
-    const bool lanesShape = lanesAlgo && b->maxM <= 64 * kLanesR && b->maxM > 0 && b->maxN <= 4096;
-    /* measured (tools/lanes_threshold.py): short reads x2048 56 vs 66 us, x4096 56 vs 114, x16384 121 vs 222 (below 2048 pairs the
-     * split / one-wave-per-pair kernels win); 20000 x 250x300 (32 lanes per pair, two per wave) 608 vs 645 us, but 300x300 (38 lanes, one
-     * per wave) 1074 vs 818 and 180x200 (23 lanes, two per wave) 395 vs 363: the path pays when the packing fills the lanes */
-    bool useLanes = lanesShape && b->maxM <= 256 && numPairs >= 2048;
-    bool lanesForced = false;
-    if (kn.lanes >= 0) { useLanes = kn.lanes != 0 && lanesShape; lanesForced = true; }
-    if (dirs) useLanes = false; /* every pair on k_linear_dir / k_affine_dir */
-    std::vector<dpx_wave_desc> waves;
-    size_t lanesRefArea = 0, lanesPairs = 0;
-    if (useLanes) {
-        b->R = kLanesR; /* empty pairs, if any, run on the one-pair-per-wave kernel at this tile height (they have no cells) */
-        for (size_t i = 0; i < numPairs; i++) {
-            dpx_pair_dev &pd = b->pairs[i];
-            if (pd.m > 0 && pd.n > 0) { couples.push_back((int32_t)i); pd.lanes = 16; pd.rows = kLanesR; }
-            else singles.push_back((int32_t)i);
-        }
-        /* a wave runs max(n + lanes) steps: neighbours of similar reference length, longest first (then longest query first).
-         * Both keys are small integers: two stable counting passes instead of a comparison sort (12 ms per 100k pairs) */
-        {
-            std::vector<int32_t> tmp(couples.size());
-            auto pass = [&](const std::vector<int32_t> &in, std::vector<int32_t> &out, int maxKey, auto key) {
-                std::vector<uint32_t> cnt((size_t)maxKey + 2, 0);
-                for (int32_t c : in) cnt[(size_t)(maxKey - key(c)) + 1]++; /* descending */
-                for (size_t k = 1; k < cnt.size(); k++) cnt[k] += cnt[k - 1];
-                for (int32_t c : in) out[cnt[(size_t)(maxKey - key(c))]++] = c;
-            };
-            pass(couples, tmp, b->maxM, [&](int32_t c) { return b->pairs[c].m; });
-            pass(tmp, couples, b->maxN, [&](int32_t c) { return b->pairs[c].n; });
-        }
-        trace.mark("create: lanes sort");
-        lanesPairs = couples.size();
-        b->lanePacked = !couples.empty();
-        if (b->lanePacked) {
-            /* (reference area: 1 KiB keeps four workgroups of the 8-rows-per-lane kernels on a CU, up to 8 pairs per wave as in round 2; the
-             * packed kernel's pairs take half the lanes, so its waves hold up to 12 pairs in 2 KiB: 2 x (18 + 2) KiB x 4 waves = 160 KiB) */
-            lanesRefArea = pack_waves(b->pairs, couples, kLanesR, b->maxN, lanesPk ? 2048 : 1024, lanesPk ? DPX_WAVE_SLOTS : 8, waves); /* `couples` comes back in slot order */
-            trace.mark("create: pack_waves");
-            size_t lanesUsed = 0;
-            for (const dpx_wave_desc &wd : waves) for (int k = 0; k < DPX_WAVE_SLOTS; k++) lanesUsed += wd.num[k];
-            if (!lanesForced && lanesUsed * 100 < waves.size() * 64 * 85) b->lanePacked = false; /* under 85 % of the lanes own rows: not worth it */
-        }
-        b->lanesPk = b->lanePacked && lanesPk;
-        if (!b->lanePacked) { /* back to the other kernels */
-            b->R = R;
-            singles.clear();
-            couples.clear();
-            waves.clear();
-            lanesPairs = 0;
-            for (size_t i = 0; i < numPairs; i++) { b->pairs[i].lanes = 64; b->pairs[i].rows = 0; }
-        }
-    }
-    /* small batches need every wave they can get: one pair per wave there.  Measured with one-wave workgroups (round 3,
-     * tools/pairs_sweep.py, profiles/r03/kernel_choice_by_batch_size.txt; GCUPS packed / one wave per pair / split): 1024 x 1024 at 1000
-     * pairs 2014 / 2813 / 2615, 1500: 2971 / 2622 / 2487, 1900: 3052 / 2770 / 2650, 2500: 2749 / 2731 / 2683, 4000: 3226 / 2993 / 2650 --
-     * the 16-rows-per-lane packed kernel wins from ~700 couples on; 512 x 512 (8 rows per lane) at 1500: 2235 / 2060 / 1987, 2000: 2432 /
-     * 2495 / 2211, 3000: 2334 / 2744 / 2446, 4000: 2877 / 2811 / 2478 -- there only from ~2000 couples on */
-    const size_t pkMinPairs = (linearAlgo && b->R == 16) ? 1400 : 4096;
-    bool usePacked = !b->lanePacked && b->store && ((linearAlgo && dpx_tiled_stripes(b->maxM, b->R) == 1) || bandedLinear) &&
-                     numPairs >= pkMinPairs;
-    if (b->lanePacked) usePacked = false;
-    else
-    if (kn.packed >= 0) usePacked = kn.packed != 0 && b->store && (linearAlgo || bandedLinear);
-    if (dirs) usePacked = false;
-    /* 16-bit wrapping arithmetic: only when weights and every intermediate provably fit (also under DPX_PACKED=1) */
-    if (usePacked) {
-        dpx_params kp = *params;
-        kp.algo = kernelAlgo;
-        usePacked = packed_safe(kp, b->maxM, b->maxN) && (!banded || params->gapOpen <= 0); /* (the packed band kernel's gap term saturates at 0) */
-        /* 4-byte edge entries + 2-byte reference entries per wave: very long references do not fit the LDS twice over
-         * (band kernel: 2-byte query and reference entries) */
-        const size_t pkNeed = (banded ? align_up(((size_t)b->maxM + 96) * 2, 16) + align_up(((size_t)b->maxN + 32) * 2, 16)
-                                      : align_up((size_t)(b->maxN + 2) * 4, 16) + align_up(((size_t)b->maxN + 128) * 2, 16)) * (DPX_FILL_THREADS / 64);
-        if (pkNeed > 160u * 1024u) usePacked = false;
-    }
-    if (usePacked) {
-        std::vector<int32_t> idx;
-        idx.reserve(numPairs);
-        for (size_t i = 0; i < numPairs; i++) {
-            if (b->pairs[i].m > 0 && b->pairs[i].n > 0) idx.push_back((int32_t)i);
-            else singles.push_back((int32_t)i);
-        }
-        if (ragged)
-            std::stable_sort(idx.begin(), idx.end(), [&](int32_t x, int32_t y) {
-                const dpx_pair_dev &X = b->pairs[x], &Y = b->pairs[y];
-                const uint64_t cx = (uint64_t)X.m * X.n, cy = (uint64_t)Y.m * Y.n;
-                if (cx != cy) return cx > cy; /* longest first */
-                if (X.m != Y.m) return X.m > Y.m;
-                return X.n > Y.n;
-            });
-        for (size_t i = 0; i < idx.size();) {
-            if (i + 1 < idx.size() && b->pairs[idx[i]].m == b->pairs[idx[i + 1]].m && b->pairs[idx[i]].n == b->pairs[idx[i + 1]].n) {
-                couples.push_back(idx[i]);
-                couples.push_back(idx[i + 1]);
-                i += 2;
-            } else {
-                singles.push_back(idx[i]);
-                i += 1;
-            }
-        }
-        b->packed = !couples.empty();
-    }
-    /* Split path (small batches: fewer pairs than the chip has wave slots worth filling): one workgroup per pair, one wave per
-     * stripe of 64 * R rows with R = 4 (2 for queries up to 256 rows), stripes concurrent (k_linear_split).  1000 pairs of
-     * 512 x 512 become 2000 waves with half the dependent chain per step.  DPX_SPLIT=0/1 overrides. */
-    {
-        bool anyEmpty = false;
-        for (size_t i = 0; i < numPairs && !anyEmpty; i++) anyEmpty = b->pairs[i].m <= 0 || b->pairs[i].n <= 0;
-        /* (queries over 4096 rows would need more than 16 stripes: not split.  Twice the stripes at 2 rows per lane -- four waves per 512-row pair --
-         * lose: 1000 x 512^2 0.146 vs 0.120 ms, profiles/r04/configs1_split_variants.txt: the kernel is bound by its instruction stream, not by waves) */
-        const int sR = b->maxM > 256 ? 4 : 2;
-        const int sW = dpx_tiled_stripes(b->maxM, sR);
-        const size_t edgeStride = align_up((size_t)b->maxN + 2, 8); /* int16 elements */
-        const size_t lds = 512 + align_up((size_t)b->maxN + 128 + 16, 16) + (size_t)std::max(sW - 1, 0) * edgeStride * 2;
-        const bool shape = linearAlgo && b->store && !dirs && !b->lanePacked && !b->packed && !anyEmpty && numPairs > 0 && sW >= 2 && sW <= 16 && lds <= 160u * 1024u;
-        /* measured (bench.py --pairs N, DPX_SPLIT=0/1, HIP events around every fill; GCUPS split vs one wave per pair):
-         *   1024 x 1024 (4 stripes of 4 rows per lane against ONE 16-rows-per-lane wave): 600 pairs 1864 vs 1768, 1200: 2229 vs 1765,
-         *   2500: 2483 vs 2315, 3500: 2592 vs 2393, 4096: 2603 vs 2671 (and the packed kernel takes over);
-         *   512 x 512 (2 stripes against one 8-rows-per-lane wave): 500 pairs 1021 vs 1003, 1000: 2084 vs 2003, 1500: 1841 vs 1935.
-         * So: any shape up to ~1100 pairs, shapes of four or more stripes up to the packed kernel's threshold.
-         * Round 3, with one-wave workgroups for the one-wave-per-pair kernels (tools/pairs_sweep.py; split vs one wave per pair): 1024 x 1024
-         * 300 pairs 1373 vs 855, 600: 2111 vs 1699, 1000: 2615 vs 2805, 1500: 2487 vs 2622, 3000: 2636 vs 2779-2962; 512 x 512 600 pairs 1323 vs
-         * 1173, 1000: 1943 vs 1932, 1500: 1987 vs 2060, 3000: 2446 vs 2744 -- queries that fit one stripe of the other kernels (<= 1024
-         * rows) split only up to ~900 pairs (up to 512 rows: ~1100, a tie from there on); longer ones (the other kernels roll over several stripes) as before. */
-        bool useSplit = shape && (b->maxM > 1024 ? (numPairs <= 1100 || (sW >= 4 && numPairs < 4096)) : numPairs <= (b->maxM > 512 ? 900u : 1100u));
-        if (kn.split >= 0) useSplit = kn.split != 0 && shape;
-        if (useSplit) {
-            b->split = true;
-            b->R = sR;
-            b->splitWaves = sW;
-            b->splitLds = lds;
-            for (size_t i = 0; i < numPairs; i++) { b->pairs[i].lanes = 32; b->pairs[i].rows = (uint16_t)sR; }
-            /* (round 3's packed variant of this kernel -- couples of equal-shaped pairs, two per workgroup on the VOP3P pipe -- halved the waves as
-             * well as the instructions and lost wherever the split kernel is used: 1000 x 512^2 0.158 vs 0.119 ms, 2000 x 512^2 0.209 vs 0.206;
-             * deleted in round 4, profiles/r04/configs1_split_variants.txt) */
-        }
-    }
-    trace.mark("create: validate+geometry+launch lists");
     CREATE_TRY(stream_take(&b->stream));
     trace.mark("create: stream");
-    int32_t *arenaOrder = nullptr, *arenaCouples = nullptr;
-    /* only the bytes this batch's pairs touch go to the device (a driver that cuts one big file into batches hands the
-     * whole file to every dpx_batch_create): upload [seqLo, seqHi) and rebase the device-side indices */
-    size_t seqLo = numBytes, seqHi = 0;
-    for (size_t i = 0; i < numPairs; i++) {
-        const dpx_pair_dev &pd = b->pairs[i];
-        seqLo = std::min(seqLo, (size_t)std::min(pd.refIdx, pd.qryIdx));
-        seqHi = std::max(seqHi, std::max((size_t)pd.refIdx + (size_t)pd.n, (size_t)pd.qryIdx + (size_t)pd.m));
-    }
-    if (seqHi <= seqLo) seqLo = seqHi = 0;
-    if (alphabet) seqLo &= ~(size_t)15; /* 2-bit input: the device expands whole dwords of 16 bases */
-    for (size_t i = 0; i < numPairs; i++) { b->pairs[i].refIdx -= (int32_t)seqLo; b->pairs[i].qryIdx -= (int32_t)seqLo; }
-    const size_t packedTotal = alphabet ? (numBytes + 3) / 4 : 0; /* bytes of the caller's packed buffer */
-    sequences += alphabet ? seqLo / 4 : seqLo;
-    numBytes = seqHi - seqLo;
-    const size_t packedDwords = alphabet ? (numBytes + 15) / 16 : 0;
-    const size_t packedCopy = alphabet ? std::min(packedDwords * 4, packedTotal - std::min(packedTotal, seqLo / 4)) : 0;
+    sequences += alphabet ? b->seqLo / 4 : b->seqLo; /* the uploaded window of the caller's buffer (dpx_plan.h: seqLo, seqHi) */
+    numBytes = b->seqHi - b->seqLo;
     char *dPacked = nullptr;
     size_t stageBytes = 0;
     {
         const size_t np1 = std::max<size_t>(numPairs, 1);
-        const size_t szSeq = align_up(std::max<size_t>(std::max(numBytes, packedDwords * 16), 16), 256), szPairs = align_up(np1 * sizeof(dpx_pair_dev), 256);
-        const size_t szPacked = alphabet ? align_up(std::max<size_t>(packedDwords * 4, 16), 256) : 0;
+        const size_t szSeq = align_up(std::max<size_t>(std::max(numBytes, b->packedDwords * 16), 16), 256), szPairs = align_up(np1 * sizeof(dpx_pair_dev), 256);
+        const size_t szPacked = alphabet ? align_up(std::max<size_t>(b->packedDwords * 4, 16), 256) : 0;
         const size_t szI32 = align_up(np1 * sizeof(int32_t), 256), szOff = align_up((np1 + 1) * sizeof(uint64_t), 256);
-        const size_t szCouples = std::max(szI32, align_up(waves.size() * sizeof(dpx_wave_desc), 256)); /* couples, or the wave descriptors */
+        const size_t szCouples = std::max(szI32, align_up(b->waves.size() * sizeof(dpx_wave_desc), 256)); /* couples, or the wave descriptors */
         const size_t szScan = align_up((dpx_out_scan_tiles(np1) + 1) * sizeof(uint64_t), 256);
         const size_t need = szSeq + szPairs + 5 * szI32 + szCouples + 2 * szOff + szScan + szPacked; /* score, endRow, endCol, order, couples, tbLen; tbOff, outOff, scan; 2-bit staging */
         CREATE_TRY(g_arenaCache.take((void **)&b->arena, need, &b->arenaCap));
@@ -1502,8 +908,10 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
         b->dScore = (int32_t *)q;     q += szI32;
         b->dEndRow = (int32_t *)q;    q += szI32;
         b->dEndCol = (int32_t *)q;    q += szI32;
-        b->dOrder = nullptr;          arenaOrder = (int32_t *)q; q += szI32;
-        b->dCouples = nullptr;        arenaCouples = (int32_t *)q; q += szCouples;
+        if (!b->singles.empty()) b->dOrder = (int32_t *)q;
+        q += szI32;
+        if (b->packed || b->lanePacked) b->dCouples = (int32_t *)q;
+        q += szCouples;
         b->dTbLen = (int32_t *)q;     q += szI32;
         b->dTbOff = (uint64_t *)q;    q += szOff;
         b->dOutOff = (uint64_t *)q;   q += szOff;
@@ -1527,98 +935,24 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
     };
     trace.mark("create: arena");
     if (alphabet) { /* a quarter of the bytes over PCIe, expanded by k_unpack2 into the byte buffer the kernels read */
-        if (packedCopy) CREATE_TRY(hipMemcpy(dPacked, sequences, packedCopy, hipMemcpyHostToDevice));
+        if (b->packedCopy) CREATE_TRY(hipMemcpy(dPacked, sequences, b->packedCopy, hipMemcpyHostToDevice));
         const uint32_t alpha = (uint32_t)alphabet[0] | ((uint32_t)alphabet[1] << 8) | ((uint32_t)alphabet[2] << 16) | ((uint32_t)alphabet[3] << 24);
-        CREATE_TRY(dpx_launch_unpack2(reinterpret_cast<const uint32_t *>(dPacked), alpha, b->dSeq, packedDwords, b->stream));
+        CREATE_TRY(dpx_launch_unpack2(reinterpret_cast<const uint32_t *>(dPacked), alpha, b->dSeq, b->packedDwords, b->stream));
         CREATE_TRY(hipStreamSynchronize(b->stream)); /* (a fill may run on a caller's stream) */
-        b->packed2 = true;
     } else if (numBytes) CREATE_TRY(upload(b->dSeq, sequences, numBytes));
     trace.mark("create: H2D sequences");
-    if (b->lanePacked) {
-        b->dCouples = arenaCouples;
-        CREATE_TRY(upload(b->dCouples, waves.data(), waves.size() * sizeof(dpx_wave_desc)));
-    } else if (b->packed) {
-        b->dCouples = arenaCouples;
-        CREATE_TRY(upload(b->dCouples, couples.data(), couples.size() * sizeof(int32_t)));
-    } else if (ragged) {
-        singles.resize(numPairs);
-        std::iota(singles.begin(), singles.end(), 0);
-    }
-    if (!singles.empty()) {
-        std::stable_sort(singles.begin(), singles.end(), [&](int32_t x, int32_t y) {
-            return (uint64_t)b->pairs[x].m * b->pairs[x].n > (uint64_t)b->pairs[y].m * b->pairs[y].n;
-        });
-        b->dOrder = arenaOrder;
-        CREATE_TRY(upload(b->dOrder, singles.data(), singles.size() * sizeof(int32_t)));
-    }
-    const size_t numSingles = (b->packed || b->lanePacked) ? singles.size() : numPairs;
-    const size_t numCouples = couples.size() / 2;
-
-    /* matrix placement (dpx_layout.h): pairs that are launched next to each other are interleaved chunk by chunk in
-     * groups of `group` waves, so a group writes one compact moving window instead of `group` far-apart streams */
-    if (b->store) {
-        int group = 64;
-        if (kn.group >= 1 && kn.group <= 1000000) group = kn.group;
-        const uint32_t chunkElems = bandDirs ? 512u : banded ? dpx_band_chunk_elems(bandPlanes) : (b->split || dirs) ? 512u : dpx_tiled_chunk_elems(b->R, b->planes); /* (dirs: 1-KiB code chunks) */
-        auto chunksOf = [&](const dpx_pair_dev &pd) -> uint64_t {
-            if (dirs) return dpx_dir_chunks(pd.m, pd.n, b->R);
-            if (bandDirs) return dpx_banddir_chunks(pd.m, pd.n, params->band);
-            if (pd.lanes == 32) return dpx_split_chunks(pd.m, pd.n, b->R);
-            return banded ? dpx_band_chunks(pd.m, pd.n, params->band) : dpx_tiled_chunks(pd.m, pd.n, b->R);
-        };
-        uint64_t off = 0;
-        auto place = [&](const std::vector<int32_t> &slots, size_t slotsPerGroup, uint32_t chunkElems) { /* slots in launch order */
-            for (size_t s0 = 0; s0 < slots.size(); s0 += slotsPerGroup) {
-                const size_t cnt = std::min(slotsPerGroup, slots.size() - s0);
-                uint64_t maxChunks = 0;
-                for (size_t g = 0; g < cnt; g++) maxChunks = std::max(maxChunks, chunksOf(b->pairs[slots[s0 + g]]));
-                for (size_t g = 0; g < cnt; g++) {
-                    dpx_pair_dev &pd = b->pairs[slots[s0 + g]];
-                    pd.matOff = off + (uint64_t)g * chunkElems;
-                    pd.chunkStride = (uint32_t)(cnt * chunkElems);
-                }
-                off += maxChunks * (uint64_t)cnt * chunkElems;
-            }
-        };
-        if (b->packed) place(couples, (size_t)group * 2, chunkElems); /* one wave (workgroup) = two adjacent slots */
-        else if (b->lanePacked) { /* tile layout (dpx_layout.h): every wave a contiguous stream of chunks, one per step; its pairs share the base */
-            const uint32_t stepElems = dpx_wtile_step_elems(b->R / 8, b->planes);
-            for (const dpx_wave_desc &wd : waves) {
-                uint64_t steps = 0;
-                for (int k = 0; k < DPX_WAVE_SLOTS; k++) {
-                    if (!wd.num[k]) continue;
-                    dpx_pair_dev &pd = b->pairs[wd.pair[k]];
-                    pd.matOff = off;
-                    pd.chunkStride = wd.first[k];
-                    steps = std::max(steps, dpx_wtile_steps(pd.m, pd.n, b->R, wd.first[k]));
-                }
-                off += steps * (uint64_t)stepElems;
-            }
-        }
-        if (b->packed || b->lanePacked || !singles.empty()) {
-            place(singles, (size_t)group, chunkElems);
-        } else { /* launch order == pair order */
-            std::vector<int32_t> ident(numPairs);
-            std::iota(ident.begin(), ident.end(), 0);
-            place(ident, (size_t)group, chunkElems);
-        }
-        b->matElems = off;
-    }
-    trace.mark("create: launch lists+placement");
+    if (b->lanePacked) CREATE_TRY(upload(b->dCouples, b->waves.data(), b->waves.size() * sizeof(dpx_wave_desc)));
+    else if (b->packed) CREATE_TRY(upload(b->dCouples, b->couples.data(), b->couples.size() * sizeof(int32_t)));
+    if (b->dOrder) CREATE_TRY(upload(b->dOrder, b->singles.data(), b->singles.size() * sizeof(int32_t)));
+    trace.mark("create: H2D launch lists"); /* (placement is the planner's) */
     if (numPairs) CREATE_TRY(upload(b->dPairs, b->pairs.data(), numPairs * sizeof(dpx_pair_dev)));
-    if (b->store) { /* where k_traceback puts a pair's three lines (each with a dword-aligned capacity of m + n + 1): needed by the
-                       output path, uploaded here so that dpx_batch_output_begin() never has to wait for the host */
-        b->tbOff.resize(numPairs + 1);
-        uint64_t off = 0;
-        for (size_t i = 0; i < numPairs; i++) { b->tbOff[i] = off; off += 3ull * (uint64_t)((b->pairs[i].m + b->pairs[i].n + 1 + 3) & ~3); }
-        b->tbOff[numPairs] = off;
-        CREATE_TRY(upload(b->dTbOff, b->tbOff.data(), (numPairs + 1) * sizeof(uint64_t)));
-    }
+    if (b->store) CREATE_TRY(upload(b->dTbOff, b->tbOff.data(), (numPairs + 1) * sizeof(uint64_t)));
     if (b->hStage) { /* the one copy; the image stays untouched until dpx_batch_destroy() has waited for the stream */
         CREATE_TRY(hipMemcpyAsync(b->arena, b->hStage, stageBytes, hipMemcpyHostToDevice, b->stream));
         b->uploadPending = true;
     }
-    if (dirGlobal) b->dirScratch = align_up(std::min<size_t>(std::max<size_t>(numSingles, 1), DPX_DIR_SCRATCH_SLOTS) * dirPerWave, 256);
+    /* (the device, or the image, has the launch lists now; the pair table and the line offsets stay: the output path reads them) */
+    b->singles = std::vector<int32_t>(); b->couples = std::vector<int32_t>(); b->waves = std::vector<dpx_wave_desc>();
     /* (a batch whose pairs are all empty has no cells, but k_traceback_wave loads the pool's first 16 bytes in place of every cell without
      * storage and masks them afterwards: such a batch gets a pool of 256 bytes, so that a.mat is an address the device may read) */
     if (b->store && (b->matElems || b->dirScratch || numPairs)) {
@@ -1656,108 +990,32 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
         b->dMat = (int16_t *)pool;
         b->poolRec = rec;
         { std::lock_guard<std::mutex> lk(g_poolRecMu); g_poolRecords[pool] = rec; }
-
     }
     trace.mark("create: H2D pairs+matrix pool");
 #undef CREATE_TRY
 
-    dpx_fill_args &a = b->args;
-    a.seq = b->dSeq;
-    a.pairs = b->dPairs;
-    a.order = b->dOrder;
-    a.numPairs = (int32_t)numSingles;
-    a.wavesPerBlock = bandDirOneWave ? 1u : fill_waves_per_block(numSingles);
-    a.match = params->match; a.mismatch = params->mismatch;
-    a.gapOpen = params->gapOpen; a.gapExtend = params->gapExtend; a.band = params->band;
-    a.mat = b->dMat;
-    a.score = b->dScore; a.endRow = b->dEndRow; a.endCol = b->dEndCol;
-    a.ldsPerWave = (uint32_t)perWave;
-    a.ldsEdge2Off = (uint32_t)edgeBytes;
-    a.ldsRefOff = banded ? (uint32_t)qBytes : (uint32_t)(edgeBytes * nEdges);
-    a.ldsQryOff = banded ? 0u : (uint32_t)(edgeBytes * nEdges + refBytes);
-    a.ldsBufStride = 0;
-    a.rowTags = 0;
-    /* big batches are bound by the bytes they write: their ramp steps store only the lines that hold cells (6 % fewer bytes at
-     * 1024 x 1024: +3 % LSW, +5 % LNW); small ones are bound by step latency and keep the cheaper whole-chunk stores */
-    a.rampLines = numPairs >= 2048 ? 1 : 0;
-    if (kn.rampLines >= 0) a.rampLines = kn.rampLines != 0;
-    if (b->split) { /* [control 512 B][staged reference][edge rows, one per stripe boundary] */
-        a.ldsRefOff = 512u;
-        a.ldsQryOff = (uint32_t)(512 + align_up((size_t)b->maxN + 128 + 16, 16));
-        a.ldsBufStride = (uint32_t)align_up((size_t)b->maxN + 2, 8);
+    /* the plan's launch arguments get their device pointers */
+    for (dpx_fill_args *x : {&b->args, &b->pkArgs}) {
+        if (x == &b->pkArgs && !b->packed && !b->lanePacked) break; /* (stays zero) */
+        x->seq = b->dSeq; x->pairs = b->dPairs; x->mat = b->dMat;
+        x->score = b->dScore; x->endRow = b->dEndRow; x->endCol = b->dEndCol;
     }
-    if (b->packed && banded) { /* packed band kernel: 2-byte query and reference entries (two chars each) */
-        dpx_fill_args &k = b->pkArgs;
-        k = a;
-        k.order = b->dCouples;
-        k.numPairs = (int32_t)numCouples;
-        k.wavesPerBlock = fill_waves_per_block(numCouples);
-        const size_t q2 = align_up(((size_t)b->maxM + 96) * 2, 16), r2 = align_up(((size_t)b->maxN + 32) * 2, 16);
-        k.ldsPerWave = (uint32_t)(q2 + r2);
-        k.ldsRefOff = (uint32_t)q2;
-        b->pkLdsBytes = (q2 + r2) * (DPX_FILL_THREADS / 64);
-    } else if (b->packed) { /* packed kernel: 4-byte edge entries (two int16), 2-byte reference entries (two chars) */
-        dpx_fill_args &k = b->pkArgs;
-        k = a;
-        k.order = b->dCouples;
-        k.numPairs = (int32_t)numCouples;
-        k.wavesPerBlock = fill_waves_per_block(numCouples);
-        const size_t pkEdge = align_up((size_t)(b->maxN + 2) * 4, 16);
-        const size_t pkRef = align_up(((size_t)b->maxN + 128) * 2, 16);
-        k.ldsPerWave = (uint32_t)(pkEdge + pkRef);
-        k.ldsRefOff = (uint32_t)pkEdge;
-        b->pkLdsBytes = (pkEdge + pkRef) * (DPX_FILL_THREADS / 64);
-        if (b->pkLdsBytes > 160u * 1024u) { dpx_batch_destroy(b); return DPX_ERR_UNSUPPORTED; }
-        /* SW start cell: one (score, row-in-lane, column) key per pair and lane where score * R + R-1 provably fits 16 bits
-         * (1024 x 1024 at match 3: 3072 * 16 + 15), else one (score, column) key per pair and row (32 more registers at R = 16) */
-        {
-            auto pos = [](long long v) { return v > 0 ? v : 0; };
-            const long long top = pos(std::max<long long>(params->match, params->mismatch)) * std::min<long long>(b->maxM, b->maxN) +
-                                  pos(params->gapOpen) * ((long long)b->maxM + b->maxN); /* fits_int16()'s bound on H */
-            k.rowTags = (kernelAlgo == DPX_ALGO_LSW && top * b->R + b->R - 1 <= 65535 && params->gapOpen <= 0) ? 1 : 0; /* (gap <= 0: the saturating gap term) */
-            if (kn.rowTags >= 0) k.rowTags = (kn.rowTags != 0 && k.rowTags) ? 1 : 0; /* (tests: 0 = the per-row keys) */
-        }
+    b->args.order = b->dOrder;
+    if (b->packed) b->pkArgs.order = b->dCouples;
+    if (b->lanePacked) b->pkArgs.waves = reinterpret_cast<const dpx_wave_desc *>(b->dCouples);
+    if (b->dirs) {
+        dpx_dir_args &d = b->dirArgs;
+        d.seq = b->dSeq; d.pairs = b->dPairs; d.order = b->dOrder;
+        d.codes = reinterpret_cast<uint8_t *>(b->dMat);
+        d.score = b->dScore; d.endRow = b->dEndRow; d.endCol = b->dEndCol;
+        d.scratch = b->dirScratch ? reinterpret_cast<unsigned char *>(b->dMat) + b->matElems * sizeof(int16_t) : nullptr;
     }
-    if (b->lanePacked) { /* per wave: the line stage of the writeback (dpx_kernels.hip: LineStage) + the staged references of its pairs */
-        dpx_fill_args &k = b->pkArgs;
-        k = a;
-        k.order = nullptr;
-        k.waves = reinterpret_cast<const dpx_wave_desc *>(b->dCouples);
-        k.numPairs = (int32_t)waves.size();
-        k.ldsPerWave = (uint32_t)(dpx_lanes_stage_bytes(kernelAlgo, kLanesR, b->store) + lanesRefArea);
-        /* (the lane-packed kernels keep their four-wave workgroups at every size: 20 000 short reads 131-148 us against 150-153 with one-wave
-         * workgroups, 100 000 the same; DPX_WPB=1 forces the latter) */
-        k.wavesPerBlock = is_affine(kernelAlgo) ? 1u : (kn.wavesPerBlock == 1 ? 1u : (uint32_t)dpx_lanes_waves_per_block(kernelAlgo));
-        b->pkLdsBytes = (size_t)k.ldsPerWave * (size_t)k.wavesPerBlock;
-        if (b->pkLdsBytes > 160u * 1024u) { dpx_batch_destroy(b); return DPX_ERR_UNSUPPORTED; }
-    }
-    if ((b->packed || b->lanePacked) && numSingles > 0) {
+    if ((b->packed || b->lanePacked) && b->nSingles > 0) {
         /* more than one kernel per fill: a side stream + fork/join events (failure here only costs the overlap) */
         if (stream_take(&b->sideStream) != hipSuccess) { b->sideStream = nullptr; (void)hipGetLastError(); }
         if (b->sideStream && (hipEventCreateWithFlags(&b->evFork, hipEventDisableTiming) != hipSuccess ||
                               hipEventCreateWithFlags(&b->evJoin, hipEventDisableTiming) != hipSuccess)) (void)hipGetLastError();
     }
-    if (dirs) {
-        dpx_dir_args &d = b->dirArgs;
-        d.seq = b->dSeq;
-        d.pairs = b->dPairs;
-        d.order = b->dOrder;
-        d.numPairs = (int32_t)numSingles;
-        d.match = params->match; d.mismatch = params->mismatch;
-        d.gapOpen = params->gapOpen; d.gapExtend = params->gapExtend;
-        d.codes = reinterpret_cast<uint8_t *>(b->dMat);
-        d.score = b->dScore; d.endRow = b->dEndRow; d.endCol = b->dEndCol;
-        d.ldsPerWave = (uint32_t)dirPerWave;
-        d.ldsEdge2Off = (uint32_t)dirEdgeBytes;
-        d.ldsRefOff = (uint32_t)(dirEdgeBytes * nEdges);
-        d.scratch = b->dirScratch ? reinterpret_cast<unsigned char *>(b->dMat) + b->matElems * sizeof(int16_t) : nullptr;
-        /* four waves per workgroup when their LDS fits, one otherwise */
-        d.wavesPerBlock = (d.scratch || dirPerWave * 4 > 160u * 1024u) ? 1u : fill_waves_per_block(numSingles);
-    }
-    b->nSingles = numSingles;
-    b->nCouples = b->packed ? numCouples : 0;
-    b->nLanePairs = b->lanePacked ? lanesPairs : 0;
-    b->nWaves = b->lanePacked ? waves.size() : 0;
     if (b->tuneShop && b->dMat && !b->guardBytes) {
         shop_pool_by_fill(b, b->poolRec, trace);
         std::lock_guard<std::mutex> lk(g_poolRecMu);
@@ -2395,37 +1653,7 @@ int dpx_cigar_text(const uint32_t *ops, size_t numOps, char *out, size_t cap, si
 
 int dpx_batch_describe(dpx_batch *b, char *buf, size_t cap) {
     if (!b || !buf || !cap) return DPX_ERR_INVALID;
-    auto name = [](int algo) -> const char * { /* (sparse: 8 and 9 are unassigned) */
-        static const char *names[] = {"LNW", "LSW", "ANW", "BSW", "ASW", "BASW", "ASG", "BANW"};
-        return algo == DPX_ALGO_BAXT ? "BAXT" : (algo >= 0 && algo <= DPX_ALGO_BANW) ? names[algo] : "?";
-    };
-    const char *kernel = b->kernelAlgo == DPX_ALGO_BAXT ? "k_baxt_fill" : b->kernelAlgo == DPX_ALGO_BANW ? "k_banw_fill" : b->kernelAlgo == DPX_ALGO_BASW ? "k_basw_fill" : b->kernelAlgo == DPX_ALGO_BSW ? (b->packed ? "k_banded_fill_pk" : "k_banded_fill") : b->kernelAlgo == DPX_ALGO_ANW ? (b->lanePacked ? "k_affine_lanes" : "k_affine_fill")
-                         : b->kernelAlgo == DPX_ALGO_ASW ? (b->lanePacked ? "k_asw_lanes" : "k_asw_fill")
-                         : b->kernelAlgo == DPX_ALGO_ASG ? (b->lanePacked ? "k_asg_lanes" : "k_asg_fill")
-                         : b->packed ? "k_linear_fill_pk" : b->lanesPk ? "k_linear_lanes_pk" : b->lanePacked ? "k_linear_lanes" : b->split ? "k_linear_split" : "k_linear_fill";
-    if (b->kernelAlgo == DPX_ALGO_BAXT && extension_on(b)) kernel = "k_zext_fill";
-    if (b->substAlphabet) kernel = "k_subst_fill";
-    if (b->bandDirs) kernel = "k_bdir_fill";
-    if (b->dirs) kernel = b->kernelAlgo == DPX_ALGO_ANW ? "k_affine_dir" : b->kernelAlgo == DPX_ALGO_ASW ? "k_asw_dir" : b->kernelAlgo == DPX_ALGO_ASG ? "k_asg_dir" : "k_linear_dir";
-    /* dtype = the arithmetic type of the kernel that fills (most of) the batch */
-    int len = snprintf(buf, cap, "algo=%s kernel_algo=%s kernel=%s dtype=%s rows_per_lane=%d store=%d couples=%zu lane_pairs=%zu waves=%zu singles=%zu row_tags=%d seq_input=%s waves_per_workgroup=%u",
-                       name(b->prm.algo), name(b->kernelAlgo), kernel, (b->packed || b->lanesPk) ? "int16" : "int32", b->R, b->store ? 1 : 0, b->nCouples, b->nLanePairs,
-                       b->nWaves, b->nSingles, (int)b->pkArgs.rowTags, b->packed2 ? "packed2" : "bytes",
-                       b->dirs ? b->dirArgs.wavesPerBlock : (b->packed || b->lanePacked) ? b->pkArgs.wavesPerBlock : b->split ? (unsigned)b->splitWaves : b->args.wavesPerBlock);
-    if (is_banded_affine(b->kernelAlgo) && len > 0 && (size_t)len < cap) { /* which walk the batch's traceback takes */
-        const bool wave = knobs().tbWalk >= 0 ? knobs().tbWalk >= 2 : b->numPairs <= 20000;
-        len += snprintf(buf + len, cap - (size_t)len, " traceback=%s",
-                        b->bandDirs ? "k_bdir_traceback"
-                        : b->substAlphabet ? (wave ? "k_subst_traceback_wave" : "k_subst_traceback")
-                        : is_banw_layout(b->kernelAlgo) ? (wave ? "k_banw_traceback_wave" : "k_banw_traceback")
-                                                       : (wave ? "k_basw_traceback_wave" : "k_basw_traceback"));
-    }
-    if (b->kernelAlgo == DPX_ALGO_BAXT && extension_on(b) && len > 0 && (size_t)len < cap)
-        len += snprintf(buf + len, cap - (size_t)len, " zdrop=%d end_bonus=%d", (int)b->zdrop, (int)b->endBonus);
-    if (b->substAlphabet && len > 0 && (size_t)len < cap) len += snprintf(buf + len, cap - (size_t)len, " subst=%d", b->substAlphabet);
-    if (b->bandDirs && len > 0 && (size_t)len < cap) len += snprintf(buf + len, cap - (size_t)len, " matrix=banddir4");
-    if (b->dirs && len > 0 && (size_t)len < cap) /* the code layout, and where the edge rows live */
-        len += snprintf(buf + len, cap - (size_t)len, " matrix=dir4 dir_edges=%s dir_scratch_bytes=%zu", b->dirScratch ? "global" : "lds", b->dirScratch);
+    int len = dpx_plan_describe(*b, knobs().tbWalk, b->zdrop, b->endBonus, b->substAlphabet, buf, cap);
     if (b->dMat && len > 0 && (size_t)len < cap) { /* the matrix pool: how it was built, and the memset time of every candidate that was timed */
         const PoolRecord &r = b->poolRec;
         len += snprintf(buf + len, cap - (size_t)len, " pool=%s pool_bytes=%zu pool_addr=0x%llx pool_chunk_mb=%zu pool_kept=%d pool_memset_ms=", r.mode.c_str(), b->matPoolBytes,

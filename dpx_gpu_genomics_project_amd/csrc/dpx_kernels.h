@@ -18,11 +18,6 @@
 #define DPX_K_BANW 7 /* banded affine-gap Needleman-Wunsch: ANW's recurrence and borders inside BSW's band, minus infinity outside (dpx_banw_kernels.hip) */
 #define DPX_K_BAXT 10 /* banded affine-gap extension: BANW's cells, ending on the first maximum of H over the band (dpx_baxt_kernels.hip; 8 and 9 are unassigned) */
 
-/* one wave per pair; DPX_FILL_THREADS/64 independent waves share a workgroup (no barriers between them) */
-#ifndef DPX_FILL_THREADS
-#define DPX_FILL_THREADS 256
-#endif
-
 
 typedef struct dpx_fill_args {
     const char *seq;            /* flat sequence bytes (device copy of parseInput's buffer) */
@@ -46,10 +41,6 @@ typedef struct dpx_fill_args {
 
 hipError_t dpx_launch_fill(const dpx_fill_args &a, int algo, int R, bool store, size_t ldsBytes, hipStream_t stream);
 hipError_t dpx_launch_fill_lanes(const dpx_fill_args &a, int algo, int R, bool store, size_t ldsBytes, hipStream_t stream);
-/* LDS in front of the staged references of a lane-packed wave (line stage, or the lane scratch when score-only), and
- * waves per workgroup of the kernel for `algo` */
-size_t dpx_lanes_stage_bytes(int algo, int R, bool store);
-int dpx_lanes_waves_per_block(int algo);
 hipError_t dpx_launch_fill_lanes_packed(const dpx_fill_args &a, int algo, size_t ldsBytes, hipStream_t stream);
 hipError_t dpx_launch_fill_split(const dpx_fill_args &a, int algo, int R, int waves, size_t ldsBytes, hipStream_t stream);
 hipError_t dpx_launch_banded_packed(const dpx_fill_args &a, int C, size_t ldsBytes, hipStream_t stream);

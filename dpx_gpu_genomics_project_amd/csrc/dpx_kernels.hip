@@ -531,8 +531,6 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_linear_fill(const dpx_fill
  * groups of MI355X_MICROARCH.md (4 x 16 lanes).  The store of the lines read in step t is issued in step t+1, behind
  * that step's arithmetic.
  * ===================================================================================================== */
-constexpr int kStageLine = 144; /* bytes between two LDS lines: 128 of cells + 16 of routing (StagePad) */
-constexpr int kLaneScratch = 1024; /* per wave: 16 B per lane for the end-of-pair reduction (aliases the line stage, which is dead by then) */
 
 template <int Q, int PLANES>
 struct LineStage {
@@ -1592,7 +1590,6 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_asg_fill(const dpx_fill_ar
  * k_linear_lanes (`up` of H and D through wave_shr:1, a slot's first lane takes the row-0 borders); the three planes H,
  * I, D leave through the same LDS line stage into the 8 x 8 tile layout, three whole-line stores per step.  One wave per
  * workgroup: the stage needs 27 KiB of LDS per wave (three planes), so small workgroups keep five of them on a CU. */
-#define DPX_ALANES_THREADS 64
 /* Round 3: the cell update keeps its state as H + (o+e), I + e, D + e (aff_cells_g: 9 vector instructions per cell instead of 10, rows
  * in place), eight steps per trip, routing in registers, loop control on the scalar unit -- as in k_linear_lanes.  Tried and dropped:
  * a HALF-LINE stage (4 columns per lane and plane, 15 KiB of LDS per wave instead of 27: ten waves per CU instead of five; the two
@@ -3070,11 +3067,6 @@ hipError_t dpx_launch_fill(const dpx_fill_args &a, int algo, int R, bool store, 
 /* lane-packed kernels (short / medium queries): a.waves = one descriptor per wave, a.numPairs = number of waves.
  * ldsBytes is per workgroup: (dpx_lanes_stage_bytes() + reference area) x waves per workgroup (4 for the linear kernels,
  * 1 for the affine one). */
-size_t dpx_lanes_stage_bytes(int algo, int R, bool store) {
-    if (!store) return (size_t)kLaneScratch;
-    return (size_t)((algo == DPX_K_ANW || algo == DPX_K_ASW || algo == DPX_K_ASG) ? 3 : 1) * (size_t)(R / 8) * 64u * (size_t)kStageLine;
-}
-int dpx_lanes_waves_per_block(int algo) { return (algo == DPX_K_ANW || algo == DPX_K_ASW || algo == DPX_K_ASG) ? DPX_ALANES_THREADS / 64 : DPX_FILL_THREADS / 64; } /* (the most: small launches of the linear kernels use 1) */
 
 template <class K>
 static hipError_t launch_lanes_kernel(K kernel, const dpx_fill_args &a, dim3 grid, int threads, size_t lds, hipStream_t s) {

@@ -30,6 +30,7 @@
 #ifndef DPX_LAYOUT_H
 #define DPX_LAYOUT_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -54,7 +55,7 @@ typedef struct dpx_pair_dev {
 
 /* Lane-packed kernels (k_linear_lanes / k_affine_lanes): what one wave aligns.  Up to DPX_WAVE_SLOTS pairs share the 64
  * lanes; slot k owns lanes [first[k], first[k] + num[k]) with num = ceil(m / rows per lane).  Built by the host
- * (dpx_capi.cpp: pack_waves), read through scalar loads. */
+ * (dpx_plan.cpp: pack_waves), read through scalar loads. */
 #define DPX_WAVE_SLOTS 12 /* (a multiple of 4: the kernels read the descriptor as dwords; 12 pairs of 5 lanes fill a wave of the packed lane kernel) */
 typedef struct dpx_wave_desc {
     int32_t pair[DPX_WAVE_SLOTS];    /* batch index of the slot's pair */
@@ -184,5 +185,22 @@ DPX_HD uint32_t dpx_band_chunk_elems(int planes) { return (uint32_t)(planes * DP
 DPX_HD uint64_t dpx_band_plane_index(int i, int j, int band, int plane, uint32_t chunkStride) {
     return dpx_band_index(i, j, band, chunkStride) + (uint64_t)(plane * DPX_BAND_PLANE_ELEMS);
 }
+
+/* one wave per pair; DPX_FILL_THREADS/64 independent waves share a workgroup (no barriers between them) */
+#ifndef DPX_FILL_THREADS
+#define DPX_FILL_THREADS 256
+#endif
+#define DPX_ALANES_THREADS 64 /* the affine lane-packed kernels: one wave per workgroup */
+
+/* Lane-packed kernels, LDS of one wave: the line stage of the writeback, then the staged references of its pairs */
+constexpr int kStageLine = 144; /* bytes between two LDS lines: 128 of cells + 16 of routing (StagePad) */
+constexpr int kLaneScratch = 1024; /* per wave: 16 B per lane for the end-of-pair reduction (aliases the line stage, which is dead by then) */
+/* LDS in front of the staged references of a lane-packed wave (line stage, or the lane scratch when score-only), and
+ * waves per workgroup of the kernel for `algo` (2, 4, 6 = DPX_K_ANW, DPX_K_ASW, DPX_K_ASG: the three-plane kernels) */
+DPX_HD size_t dpx_lanes_stage_bytes(int algo, int R, bool store) {
+    if (!store) return (size_t)kLaneScratch;
+    return (size_t)((algo == 2 || algo == 4 || algo == 6) ? 3 : 1) * (size_t)(R / 8) * 64u * (size_t)kStageLine;
+}
+DPX_HD int dpx_lanes_waves_per_block(int algo) { return (algo == 2 || algo == 4 || algo == 6) ? DPX_ALANES_THREADS / 64 : DPX_FILL_THREADS / 64; } /* (the most: small launches of the linear kernels use 1) */
 
 #endif

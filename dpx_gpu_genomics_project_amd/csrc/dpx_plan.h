@@ -1,0 +1,87 @@
+/* dpx_plan.h -- the host-only half of dpx_batch_create: what a batch decides before it touches the device, as a pure function of the
+ * parameters, the pairs' sizes and indices, the flags and a Knobs snapshot.  No sequence byte is read and no HIP function called
+ * (dpx_kernels.h: the argument structs only), so hostcpp/plan_tool runs it without a GPU.  dpx_capi.cpp does the device work. */
+#ifndef DPX_PLAN_H
+#define DPX_PLAN_H
+
+#include <string>
+#include <vector>
+
+#include "../../include/dpx_align.h"
+#include "dpx_dir.h" /* (first: it brings dpx_kernels.h, whose hip_runtime.h the layout headers need under hipcc) */
+#include "dpx_banddir.h"
+
+#pragma GCC visibility push(hidden) /* (internal to libdpxalign.so: not part of its ABI) */
+
+/* Development and test knobs.  The environment is read in ONE place (dpx_capi.cpp: refresh_knobs), when dpx_init() binds a device and
+ * again at the start of every dpx_batch_create*() (the tests flip a knob between two batches of one process); everything else reads this
+ * snapshot.  -1 / 0 = not set.  None of them changes a result: they force or forbid a kernel family, change the launch shape or trace
+ * the runtime. */
+struct Knobs {
+    int rowsPerLane = 0;   /* DPX_R=2|4|8|16 */
+    int packed = -1;       /* DPX_PACKED=0|1: the two-pairs-per-wave int16 kernels */
+    int lanes = -1;        /* DPX_LANES=0|1: the lane-packed (several pairs per wave) kernels */
+    int lanesPk = -1;      /* DPX_LANES_PK=0: keep the lane-packed batches on the int32 kernels */
+    int split = -1;        /* DPX_SPLIT=0|1: one wave per stripe */
+    int rowTags = -1;      /* DPX_ROW_TAGS=0: per-row start-cell keys in the packed SW kernel */
+    int rampLines = -1;    /* DPX_RAMP_LINES=0|1: skew ramps store lines / whole chunks */
+    int wavesPerBlock = 0; /* DPX_WPB=1|4 */
+    int group = 0;         /* DPX_GROUP: pairs per interleaved block of the matrix layout */
+    int tbWalk = -1;       /* DPX_TB_WALK=0|1|2 */
+    int poolProbe = -1;    /* DPX_POOL_PROBE=0|1|2: nothing / time the pool / time + shop, whatever DPX_TUNE_PLACEMENT says */
+    bool poolMalloc = false;  /* DPX_POOL=malloc: one hipMalloc instead of the chunked virtual range */
+    size_t poolChunkBytes = 0; /* DPX_POOL_CHUNK_MB */
+    int poolGuard = 0;     /* DPX_POOL_GUARD: 1 = pattern band behind the matrices, 2 = "selftest" (the band is born damaged) */
+    bool trace = false, traceVmm = false; /* DPX_TRACE / DPX_TRACE_VMM: phase timings / pool mapping calls on stderr */
+};
+
+/* What dpx_plan_batch decides.  dpx_batch (dpx_capi.cpp) takes it over by move and fills in the device pointers. */
+struct dpx_plan {
+    dpx_params prm{}; unsigned flags = 0; size_t numPairs = 0;
+    bool packed2 = false;  /* the sequences arrive as 2-bit codes (dpx_batch_create_packed2) */
+    int kernelAlgo = 0;    /* algorithm the kernel runs (BSW with a covering band runs as LSW) */
+    int R = 8;             /* rows per lane (full-matrix kernels) or cells per lane (band kernels) */
+    int planes = 1;
+    bool store = true;
+    bool dirs = false;     /* DPX_KEEP_DIRECTIONS: 4-bit codes in the pool (matElems counts them in int16 units, dpx_dir.h), k_linear_dir / k_affine_dir */
+    bool bandDirs = false; /* DPX_KEEP_BAND_DIRECTIONS on a BANW / BAXT band kernel: codes in dpx_banddir.h's layout, k_bdir_fill through `args`
+                              (a covering BANW band is a `dirs` batch of ANW instead) */
+    bool packed = false;     /* LNW / LSW / BSW with matrices: couples of equal-shaped pairs, two per wave + leftover singles */
+    bool split = false;      /* small batch: one workgroup per pair, one wave per stripe (k_linear_split) */
+    bool lanePacked = false; /* short queries: several pairs per wave (k_linear_lanes / k_affine_lanes, 8 x 8 tile layout) */
+    bool lanesPk = false;    /* lane-packed batch on k_linear_lanes_pk (two row blocks of a pair in the halves of every register) */
+    int splitWaves = 0, maxM = 0, maxN = 0;
+    size_t splitLds = 0;
+    uint64_t cells = 0, matElems = 0, algBytes = 0, bandCells = 0;
+    std::vector<dpx_pair_dev> pairs; /* the device pair table, indices relative to seqLo */
+    std::vector<int32_t> singles;     /* launch order of the one-wave-per-pair kernel (longest first); empty: pair order */
+    std::vector<int32_t> couples;     /* packed kernels: two adjacent entries per wave */
+    std::vector<dpx_wave_desc> waves; /* lane-packed kernels: one descriptor per wave */
+    std::vector<uint64_t> tbOff;      /* where k_traceback puts a pair's three lines (numPairs + 1 entries; empty when score-only) */
+    size_t seqLo = 0, seqHi = 0;      /* the bytes (bases) of the caller's buffer that the pairs touch: only these are uploaded */
+    size_t packedDwords = 0, packedCopy = 0; /* 2-bit input: dwords k_unpack2 expands, bytes of the caller's packed buffer to copy */
+    size_t dirScratch = 0; /* direction batches whose edge rows do not fit LDS: bytes of the per-wave areas behind the codes (0: LDS) */
+    dpx_fill_args args{};   /* the one-wave-per-pair / split kernel; every pointer null */
+    dpx_fill_args pkArgs{}; /* the packed or lane-packed kernel; every pointer null */
+    dpx_dir_args dirArgs{}; /* the direction kernels; every pointer null */
+    size_t ldsBytes = 0, pkLdsBytes = 0;
+    size_t nSingles = 0, nCouples = 0, nLanePairs = 0, nWaves = 0; /* launch-list sizes (dpx_batch_describe) */
+};
+
+bool is_affine(int algo), is_banded(int algo), is_banded_affine(int algo), is_banw_layout(int algo);
+size_t align_up(size_t v, size_t a);
+int validate_params(const dpx_params *p);
+bool fits_int16(const dpx_params &p, long long m, long long n), fits_dir(const dpx_params &p, long long m, long long n);
+bool packed_safe(const dpx_params &p, long long m, long long n);
+
+/* The status dpx_batch_create*() returns for this input once validate_params, the flag checks and the device have passed, and on DPX_OK the
+ * plan.  `numBytes`: bytes (2-bit input: bases) of the caller's buffer.  `err` receives the text for dpx_last_error(). */
+int dpx_plan_batch(const dpx_params &params, const dpx_seq_pair *pairs, size_t firstPair, size_t numPairs, size_t numBytes, bool packed2Input,
+                   unsigned flags, const Knobs &knobs, dpx_plan &out, std::string &err);
+
+/* dpx_batch_describe()'s text up to the pool fields.  What a batch can change after its creation comes as arguments: the traceback walk
+ * knob, BAXT's extension mode (-1, -1: off) and the substitution alphabet (0: none).  Returns the length written (snprintf's rules). */
+int dpx_plan_describe(const dpx_plan &p, int tbWalk, int zdrop, int endBonus, int substAlphabet, char *buf, size_t cap);
+
+#pragma GCC visibility pop
+#endif
