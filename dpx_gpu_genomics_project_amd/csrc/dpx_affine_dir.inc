@@ -30,7 +30,7 @@
     else my = smem + (size_t)wv * a.ldsPerWave;
     int32_t *edgeH = reinterpret_cast<int32_t *>(my);
     int32_t *edgeD = reinterpret_cast<int32_t *>(my + a.ldsEdge2Off);
-    const unsigned char *refl = dir_stage(my + a.ldsRefOff + 64, ref, n, lane) - 64;
+    const unsigned char *refl = stage_bytes(my + a.ldsRefOff + 64, ref, n, lane, 64) - 64;
     for (int x = lane; x <= n + 1; x += 64) { edgeH[x] = (LOCAL || SEMI) ? 0 : o + x * e; edgeD[x] = DPX_NEG; } /* H[0][j] (:50-53; ASW / ASG 0), virtual D[0][j] */
     if constexpr (GLOBAL) __threadfence_block();
 
@@ -124,7 +124,7 @@
     }
     if constexpr (LOCAL) { /* first strict maximum in row-major order (k_linear_dir) */
         const unsigned long long mine = ((unsigned long long)(unsigned)bestv << 32) | (unsigned)(0x7FFFFFFF - bestrow);
-        const unsigned long long top = dir_wave_max_u64(mine);
+        const unsigned long long top = wave_max_u64(mine);
         if ((int)(top >> 32) == 0) {
             if (lane == 0) { a.score[p] = 0; a.endRow[p] = 0; a.endCol[p] = 0; }
         } else if (mine == top) {

@@ -1,4 +1,4 @@
-/* dpx_affine_fill.inc -- body of the one-wave-per-pair affine-gap fill kernels, included by dpx_kernels.hip inside k_affine_fill (ANW,
+/* dpx_affine_fill.inc -- body of the one-wave-per-pair affine-gap fill kernels, included by dpx_affine_kernels.hip inside k_affine_fill (ANW,
  * LOCAL = false), k_asw_fill (ASW, LOCAL = true) and k_asg_fill (ASG, SEMI = true: ANW's cells under a zero row-0 border, the end cell is
  * the first maximum of row m, column 0 included).  The body sits in each kernel itself rather than in a shared __device__ function:
  * passing the kernel argument block to a function changed the scheduling of the ANW kernel (its gfx950 code differed, and 4000 x 512^2
@@ -75,7 +75,7 @@
             const int upH = wave_shr1(st.Hl[R - 1], eH);
             const int upD = wave_shr1(st.Dl[R - 1], eD);
             if (sw) {
-                if constexpr (LOCAL) aff_fold_keys<R>(st, row0, nrows, bestv, bestrow, bestcol);
+                if constexpr (LOCAL) fold_row_keys<R>(st.key, row0, nrows, bestv, bestrow, bestcol);
                 row0 += 64 * R;
                 nrows = min(max(m - row0, 0), R);
 #pragma unroll
@@ -113,7 +113,7 @@
             roll_step(T + 1);
         }
         if (T < total) roll_step(T);
-        if constexpr (LOCAL) aff_fold_keys<R>(st, row0, nrows, bestv, bestrow, bestcol);
+        if constexpr (LOCAL) fold_row_keys<R>(st.key, row0, nrows, bestv, bestrow, bestcol);
     } else {
     for (int k = 0; k < S; k++) {
             const int base = k * 64 * R;
@@ -168,7 +168,7 @@
                 for (int t = 0; t < W; t++) DPX_AFF_STEP(true, false, laneHasRows)
             }
     #undef DPX_AFF_STEP
-            if constexpr (LOCAL) aff_fold_keys<R>(st, row0, nrows, bestv, bestrow, bestcol);
+            if constexpr (LOCAL) fold_row_keys<R>(st.key, row0, nrows, bestv, bestrow, bestcol);
         }
 }
     if constexpr (LOCAL) {

@@ -1,4 +1,4 @@
-/* dpx_affine_lanes.inc -- body of the lane-packed affine-gap kernels, included by dpx_kernels.hip inside k_affine_lanes (ANW, LOCAL = false)
+/* dpx_affine_lanes.inc -- body of the lane-packed affine-gap kernels, included by dpx_affine_kernels.hip inside k_affine_lanes (ANW, LOCAL = false)
  * k_asw_lanes (ASW, LOCAL = true) and k_asg_lanes (ASG, SEMI = true), for the reason given in dpx_affine_fill.inc.  In scope: `a`, R, STORE,
  * LOCAL and SEMI. */
     constexpr int MODE = LOCAL ? 1 : (SEMI ? 2 : 0); /* aff_cells_g: ANW, ASW, ASG */

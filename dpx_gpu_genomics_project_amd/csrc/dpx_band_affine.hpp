@@ -4,10 +4,10 @@
  * (either, storing direction codes).  dpx_basw_kernels.hip, whose step has a zero floor and a start cell, is a different kernel and does
  * not include it.  Everything here is a __forceinline__ function or a template: each kernel stays in its own unit under its own name.
  *
- * Shared are the helpers (stage_bytes, store8, wave_max_u64, end_key, CharWin), the band geometry and BandView, the step of the two
- * fills that track slot keys (slot_key_step: k_baxt_fill and k_zext_fill), both walks over the stored planes as templates on a Scorer
- * (band_walk_lane, band_walk_wave: BANW's with the byte compare, the substitution walks with the table), and the launch helper and
- * dispatcher of every fill.
+ * Shared are end_key, the band geometry and BandView, the step of the two fills that track slot keys (slot_key_step: k_baxt_fill and
+ * k_zext_fill) and both walks over the stored planes as templates on a Scorer (band_walk_lane, band_walk_wave: BANW's with the byte
+ * compare, the substitution walks with the table).  The helpers of every family (stage_bytes, store8, wave_max_u64, CharWin) and the
+ * launch helper and dispatcher of every fill (launch_fill, dispatch_fill) come from dpx_device.hpp under their old names.
  *
  * NOT shared is one step for all fills.  band_step<C, P1, INTERIOR, Scorer, Tracker> over shared geometry / slide-and-gather / select
  * pieces, a shared prologue and shared phase loops computed every value the five steps compute and left every GPU test passing, but
@@ -37,6 +37,7 @@
 
 #include <type_traits>
 
+#include "dpx_device.hpp"
 #include "dpx_kernels.h"
 #include "dpx_layout.h"
 #include "dpx_prims.hpp"
@@ -47,57 +48,21 @@ using dpx::pack_lo16;
 using dpx::wave_shl1;
 using dpx::wave_shr1;
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-template <bool V>
-using bool_c = std::integral_constant<bool, V>;
-template <int V>
-using int_c = std::integral_constant<int, V>;
-
-/* ---------------------------------------------------------- helpers ---------------------------------------------------------- */
-
-/* a string copied into LDS with aligned 16-byte loads; it lands `src & 15` bytes into the buffer (as in dpx_kernels.hip) */
-__device__ __forceinline__ unsigned char *stage_bytes(unsigned char *dst16, const unsigned char *src, const int n, const int l, const int G) {
-    const unsigned a = (unsigned)(reinterpret_cast<uintptr_t>(src) & 15u);
-    const u32x4 *from = reinterpret_cast<const u32x4 *>(src - a);
-    u32x4 *to = reinterpret_cast<u32x4 *>(dst16);
-    const int blocks = n > 0 ? (int)((a + (unsigned)n + 15u) >> 4) : 0;
-    for (int k = l; k < blocks; k += G) to[k] = from[k];
-    return dst16 + a;
-}
-
-/* eight int32 values -> eight int16, one 16-byte store */
-__device__ __forceinline__ void store8(int16_t *dst, const int (&v)[8]) {
-    u32x4 w = {pack_lo16(v[0], v[1]), pack_lo16(v[2], v[3]), pack_lo16(v[4], v[5]), pack_lo16(v[6], v[7])};
-    *reinterpret_cast<u32x4 *>(dst) = w;
-}
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        unsigned long long o = __shfl_xor(v, off, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
+using dpx_dev::bool_c;
+using dpx_dev::CharWin;
+using dpx_dev::dispatch_fill;
+using dpx_dev::int_c;
+using dpx_dev::launch_fill;
+using dpx_dev::stage_bytes;
+using dpx_dev::store8;
+using dpx_dev::u32x4;
+using dpx_dev::wave_max_u64;
 
 /* (score, min row, min column) as one unsigned key; score > 0 */
 __device__ __forceinline__ unsigned long long end_key(const int hv, const int i, const int j) {
     return ((unsigned long long)(unsigned)hv << 40) | ((unsigned long long)(0xFFFFFu - (unsigned)i) << 20) |
            (unsigned long long)(0xFFFFFu - (unsigned)j);
 }
-
-/* a byte string read back to front through one register: four characters per aligned dword load */
-struct CharWin {
-    const unsigned char *s;
-    uintptr_t at = 1;
-    uint32_t w = 0;
-    __device__ __forceinline__ int get(int x) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(s + x), al = a & ~(uintptr_t)3;
-        if (al != at) { at = al; w = *reinterpret_cast<const uint32_t *>(al); } /* never leaves the 256-byte aligned arena */
-        return (int)((w >> (8 * (int)(a & 3))) & 0xFFu);
-    }
-};
 
 /* ---- geometry shared by the exports and the walks.  A cell (i, j), borders included, is in the band when |i - j| <= B-1; the fill stores
  * the in-band cells with i, j >= 1; I on the lower edge and D on the upper edge are -infinity whatever the fill stored there ---- */
@@ -240,7 +205,7 @@ __device__ __forceinline__ void slot_key_step(SlotKeyState<C> &st, const int A, 
 
 /* ---------------------------------------------------------- the walks -------------------------------------------------------- */
 
-/* ---- traceback: one lane per pair, ANW's three-state walk (dpx_kernels.hip: tb_walk_lane) over the band layout, with ANW's two tails.
+/* ---- traceback: one lane per pair, ANW's three-state walk (dpx_traceback_kernels.hip: tb_walk_lane) over the band layout, with ANW's two tails.
  * The walk stands on stored cells only; the neighbours it reads are in band (the diagonal one always; the left / upper one because the
  * gap it came through is finite) or border cells, which open the gap.  mm = H_diag + the scorer's term; the relation character is the
  * byte compare whatever the scorer. ---- */
@@ -307,7 +272,7 @@ __device__ __forceinline__ void band_walk_lane(const dpx_fill_args &a, const Sco
 }
 
 /* -----------------------------------------------------------------------------------------------------
- * Wave-cooperative traceback: k_traceback_wave's scheme (dpx_kernels.hip) for the three band-layout planes.  One WAVE owns a pair; lane c
+ * Wave-cooperative traceback: k_traceback_wave's scheme (dpx_traceback_kernels.hip) for the three band-layout planes.  One WAVE owns a pair; lane c
  * fetches column cLo + c of a window of 48 rows x 64 columns of H, I and D around the walker into LDS (one 112-byte line per column and
  * plane; in-band border cells carry their H, every other cell without storage and every edge I / D is -32768, the window's minus
  * infinity, which cell() turns into DPX_NEG) -- only the three 8-row groups around the walker's diagonal unless the
@@ -561,38 +526,6 @@ __device__ __forceinline__ void band_walk_wave(const dpx_fill_args &a, Scorer sc
     for (int k = lane; k < j; k += 64) { const int at = pos - 1 - k; lr[at] = (char)ref[j - 1 - k]; lx[at] = ' '; lq[at] = '_'; }
     pos -= max(j, 0);
     if (lane == 0) tbLen[p] = cap - pos;
-}
-
-/* ---------------------------------------------------------- launches --------------------------------------------------------- */
-
-/* a fill: one wave per pair, f.wavesPerBlock waves per workgroup; `lds` is the request of a four-wave workgroup */
-template <class K, class Args>
-hipError_t launch_fill(K kernel, const Args &args, const dpx_fill_args &f, size_t lds, hipStream_t s) {
-    if (lds > 64u * 1024u) { /* opt in to more than the default 64 KiB of dynamic LDS */
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    const unsigned wpb = f.wavesPerBlock;
-    const dim3 grid(((unsigned)f.numPairs + wpb - 1) / wpb);
-    hipLaunchKernelGGL(kernel, grid, dim3(64u * wpb), lds / 4u * wpb, s, args);
-    return hipGetLastError();
-}
-
-/* launch(int_c<C>, bool_c<PB>, bool_c<FLAG>) for the cells per lane C, the parity PB of step 0 under `band`, and one more switch */
-template <class Launch>
-hipError_t dispatch_fill(const int C, const int band, const bool flag, Launch launch) {
-    const bool pb = ((band + 1) & 1) != 0; /* parity of step A = 0 */
-    auto with_c = [&](auto c) -> hipError_t {
-        if (pb) return flag ? launch(c, bool_c<true>{}, bool_c<true>{}) : launch(c, bool_c<true>{}, bool_c<false>{});
-        return flag ? launch(c, bool_c<false>{}, bool_c<true>{}) : launch(c, bool_c<false>{}, bool_c<false>{});
-    };
-    switch (C) {
-    case 1: return with_c(int_c<1>{});
-    case 2: return with_c(int_c<2>{});
-    case 4: return with_c(int_c<4>{});
-    case 8: return with_c(int_c<8>{});
-    default: return hipErrorInvalidValue;
-    }
 }
 
 } // namespace dpx_band

@@ -3,7 +3,7 @@
  *
  * The recurrence is ASW's Gotoh recurrence (dpx_affine_fill.inc) restricted to the band |i-j| <= B-1; every neighbour that is a
  * border cell or lies outside the band reads H = 0, I = D = -infinity (DPX_NEG), so the first in-band cell of a row or column always
- * opens its gap.  The schedule is k_banded_fill's (dpx_kernels.hip): the wave walks anti-diagonals a = i+j, slot s = (i-j+B-1)>>1,
+ * opens its gap.  The schedule is k_banded_fill's (dpx_bsw_kernels.hip): the wave walks anti-diagonals a = i+j, slot s = (i-j+B-1)>>1,
  * lane l owns the C = ceil(B/64) slots [l*C, l*C+C), all 64 lanes work on every step.  With p = (a+B-1)&1
  *       p=1: up = prev[s], left = prev[s+1]        p=0: up = prev[s-1], left = prev[s]
  * D needs H and D of the up neighbour, I needs H and I of the left neighbour, H needs the diagonal (prev2H[s]).  Only ONE of the two
@@ -21,6 +21,7 @@
 
 #include <type_traits>
 
+#include "dpx_device.hpp"
 #include "dpx_kernels.h"
 #include "dpx_layout.h"
 #include "dpx_prims.hpp"
@@ -31,32 +32,7 @@ using dpx::pack_lo16;
 using dpx::wave_shl1;
 using dpx::wave_shr1;
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-/* a string copied into LDS with aligned 16-byte loads; it lands `src & 15` bytes into the buffer (as in dpx_kernels.hip) */
-__device__ __forceinline__ unsigned char *stage_bytes(unsigned char *dst16, const unsigned char *src, const int n, const int l, const int G) {
-    const unsigned a = (unsigned)(reinterpret_cast<uintptr_t>(src) & 15u);
-    const u32x4 *from = reinterpret_cast<const u32x4 *>(src - a);
-    u32x4 *to = reinterpret_cast<u32x4 *>(dst16);
-    const int blocks = n > 0 ? (int)((a + (unsigned)n + 15u) >> 4) : 0;
-    for (int k = l; k < blocks; k += G) to[k] = from[k];
-    return dst16 + a;
-}
-
-/* eight int32 values -> eight int16, one 16-byte store */
-__device__ __forceinline__ void store8(int16_t *dst, const int (&v)[8]) {
-    u32x4 w = {pack_lo16(v[0], v[1]), pack_lo16(v[2], v[3]), pack_lo16(v[4], v[5]), pack_lo16(v[6], v[7])};
-    *reinterpret_cast<u32x4 *>(dst) = w;
-}
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        unsigned long long o = __shfl_xor(v, off, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
+using namespace dpx_dev; /* stage_bytes, store8, wave_max_u64, CharWin, launch_fill, dispatch_fill */
 
 template <int C>
 struct BaswState {
@@ -249,6 +225,7 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_basw_fill(const dpx_fill_a
 }
 
 /* ---- one pair's plane as the row-major (m+1) x (n+1) matrix: borders and cells outside the band are 0 in every plane ---- */
+/* (dpx_band::cell_in_band is this test written over in_band(); with it k_basw_export and both walks compile to other instructions) */
 __device__ __forceinline__ bool basw_in_band(const int i, const int j, const int band) {
     const int dlt = i - j;
     return i >= 1 && j >= 1 && dlt <= band - 1 && -dlt <= band - 1;
@@ -264,7 +241,7 @@ __global__ void k_basw_export(const int16_t *mat, dpx_pair_dev pr, int plane, in
     }
 }
 
-/* ---- traceback: one lane per pair, ASW's three-state walk (dpx_kernels.hip: tb_walk_lane) over the band layout.  The stored I / D
+/* ---- traceback: one lane per pair, ASW's three-state walk (dpx_traceback_kernels.hip: tb_walk_lane) over the band layout.  The stored I / D
  * of a border or out-of-band neighbour are 0, not -infinity: such a neighbour is "always GAP_OPEN", as row 1 / column 1 are in ASW. ---- */
 struct BaswView {
     const int16_t *mat;
@@ -273,18 +250,6 @@ struct BaswView {
     int band;
     __device__ __forceinline__ int get(int i, int j, int plane) const {
         return basw_in_band(i, j, band) ? (int)mat[off + dpx_band_plane_index(i, j, band, plane, cs)] : 0;
-    }
-};
-
-/* a byte string read back to front through one register: four characters per aligned dword load */
-struct CharWin {
-    const unsigned char *s;
-    uintptr_t at = 1;
-    uint32_t w = 0;
-    __device__ __forceinline__ int get(int x) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(s + x), al = a & ~(uintptr_t)3;
-        if (al != at) { at = al; w = *reinterpret_cast<const uint32_t *>(al); } /* never leaves the 256-byte aligned arena */
-        return (int)((w >> (8 * (int)(a & 3))) & 0xFFu);
     }
 };
 
@@ -348,7 +313,7 @@ __global__ void k_basw_traceback(const dpx_fill_args a, int numPairs, const int3
 }
 
 /* -----------------------------------------------------------------------------------------------------
- * Wave-cooperative traceback: k_traceback_wave's scheme (dpx_kernels.hip) for the three band-layout planes.  One WAVE owns a pair; lane c
+ * Wave-cooperative traceback: k_traceback_wave's scheme (dpx_traceback_kernels.hip) for the three band-layout planes.  One WAVE owns a pair; lane c
  * fetches column cLo + c of a window of 48 rows x 64 columns of H, I and D around the walker into LDS (one 112-byte line per column and
  * plane; cells outside the band, the matrix or on the borders are 0) -- only the three 8-row groups around the walker's diagonal unless the
  * walk left the last window sideways -- and the walk takes RUNS: every lane decides one cell of the line the path would follow next (the
@@ -566,39 +531,13 @@ __global__ void __launch_bounds__(64) k_basw_traceback_wave(const dpx_fill_args 
     if (lane == 0) tbLen[p] = cap - pos;
 }
 
-template <class K>
-hipError_t launch_basw_kernel(K kernel, const dpx_fill_args &a, dim3 grid, size_t lds, hipStream_t s) {
-    if (lds > 64u * 1024u) { /* opt in to more than the default 64 KiB of dynamic LDS */
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    const unsigned wpb = a.wavesPerBlock; /* `lds` is the request of a four-wave workgroup */
-    hipLaunchKernelGGL(kernel, grid, dim3(64u * wpb), lds / 4u * wpb, s, a);
-    return hipGetLastError();
-}
-
-template <int C>
-hipError_t launch_basw_C(const dpx_fill_args &a, bool store, dim3 grid, size_t lds, hipStream_t s) {
-    const bool pb = ((a.band + 1) & 1) != 0; /* parity of step A = 0 */
-    if (pb) return store ? launch_basw_kernel(k_basw_fill<C, true, true>, a, grid, lds, s)
-                         : launch_basw_kernel(k_basw_fill<C, true, false>, a, grid, lds, s);
-    return store ? launch_basw_kernel(k_basw_fill<C, false, true>, a, grid, lds, s)
-                 : launch_basw_kernel(k_basw_fill<C, false, false>, a, grid, lds, s);
-}
-
 } // namespace
 
 hipError_t dpx_launch_basw_fill(const dpx_fill_args &a, int C, bool store, size_t ldsBytes, hipStream_t stream) {
     if (a.numPairs <= 0) return hipSuccess;
-    const int wavesPerBlock = (int)a.wavesPerBlock;
-    dim3 grid((unsigned)((a.numPairs + wavesPerBlock - 1) / wavesPerBlock));
-    switch (C) {
-    case 1: return launch_basw_C<1>(a, store, grid, ldsBytes, stream);
-    case 2: return launch_basw_C<2>(a, store, grid, ldsBytes, stream);
-    case 4: return launch_basw_C<4>(a, store, grid, ldsBytes, stream);
-    case 8: return launch_basw_C<8>(a, store, grid, ldsBytes, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_fill(C, a.band, store, [&](auto c, auto pb, auto st) {
+        return launch_fill(k_basw_fill<decltype(c)::value, decltype(pb)::value, decltype(st)::value>, a, a, ldsBytes, stream);
+    });
 }
 
 hipError_t dpx_launch_basw_export(const int16_t *mat, const dpx_pair_dev &pr, int plane, int band, int16_t *out, hipStream_t stream) {

@@ -1,7 +1,7 @@
 /*
  * dpx_capi.cpp -- implementation of include/dpx_align.h on the HIP runtime (host side of libdpxalign.so).
  *
- * Owns device memory, streams and launch geometry; the arithmetic is in dpx_kernels.hip.  There is no CPU
+ * Owns device memory, streams and launch geometry; the arithmetic is in the kernel units (dpx_kernels.hip and the other *_kernels.hip).  There is no CPU
  * fallback anywhere in this file: without a gfx950 device every entry point fails with DPX_ERR_NO_DEVICE.
  */
 #include "../../include/dpx_align.h"

@@ -22,8 +22,11 @@
 #include <stdint.h>
 
 #include "dpx_cigar.h"
+#include "dpx_device.hpp"
 
 namespace {
+
+using namespace dpx_dev;
 
 constexpr int kCigarThreads = 256;                  /* four independent waves per workgroup, one pair each (as k_out_compact) */
 constexpr int kTripCols = 4 * DPX_WAVE;             /* one dword per lane */
@@ -173,27 +176,8 @@ __global__ void __launch_bounds__(kCigarThreads) k_cigar_write(const dpx_pair_de
     if (lane == 0 && openOp >= 0) dst[openOp] = cigar_op(openClass, L.len - openCol); /* the line ends: so does the last run */
 }
 
-/* ---- exclusive prefix of numOps over the pairs: the tile scheme of k_out_scan / k_out_scan_tiles (dpx_kernels.hip) ---- */
-
-constexpr int kScanThreads = 256, kScanPerThread = 8, kScanTile = kScanThreads * kScanPerThread;
-
-/* inclusive scan of one value per thread across the workgroup; returns the exclusive prefix, *total = sum over the group */
-__device__ __forceinline__ unsigned long long cigar_group_exclusive(unsigned long long v, unsigned long long *lds, unsigned long long *total) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    unsigned long long x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned long long o = __shfl_up(x, off, 64);
-        if (lane >= off) x += o;
-    }
-    if (lane == 63) lds[wv] = x;
-    __syncthreads();
-    unsigned long long base = 0, all = 0;
-    for (int k = 0; k < kScanThreads / 64; k++) { const unsigned long long w = lds[k]; if (k < wv) base += w; all += w; }
-    __syncthreads();
-    *total = all;
-    return base + x - v;
-}
+/* ---- exclusive prefix of numOps over the pairs: the tile scheme of k_out_scan / k_out_scan_tiles (dpx_output_kernels.hip); the scan
+ * itself is dpx_device.hpp's ---- */
 
 /* phase 1: per-tile totals of numOps; phase 3 (FINAL): opsOffset = tile base + exclusive prefix, and the batch's total.  A batch of
  * one tile runs phase 3 alone (tileSums == nullptr: its base is 0). */
@@ -210,7 +194,7 @@ __global__ void __launch_bounds__(kScanThreads) k_cigar_scan(dpx_alignment *reco
         mine += v[k];
     }
     unsigned long long total;
-    unsigned long long ex = cigar_group_exclusive(mine, lds, &total);
+    unsigned long long ex = group_exclusive(mine, lds, &total);
     if constexpr (!FINAL) {
         if (threadIdx.x == 0) tileSums[blockIdx.x] = total;
     } else {
@@ -233,7 +217,7 @@ __global__ void __launch_bounds__(kScanThreads) k_cigar_scan_tiles(unsigned long
         const int t = t0 + (int)threadIdx.x;
         const unsigned long long v = t < numTiles ? tileSums[t] : 0ull;
         unsigned long long total;
-        const unsigned long long ex = cigar_group_exclusive(v, lds, &total);
+        const unsigned long long ex = group_exclusive(v, lds, &total);
         if (t < numTiles) tileSums[t] = carry + ex;
         carry += total;
     }

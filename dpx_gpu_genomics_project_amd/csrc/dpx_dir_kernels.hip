@@ -20,24 +20,16 @@
 
 #include <algorithm>
 
+#include "dpx_device.hpp"
 #include "dpx_dir.h"
 #include "dpx_prims.hpp"
 
 namespace {
 
 using dpx::wave_shr1;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-/* a string into a 16-byte aligned buffer with aligned 16-byte copies; returns the address of its first character (the copy starts
- * at the 16-byte block that holds it).  The buffer needs n + 31 bytes; the blocks read never leave the 256-byte aligned arena. */
-__device__ __forceinline__ unsigned char *dir_stage(unsigned char *dst16, const unsigned char *src, const int n, const int lane) {
-    const unsigned a = (unsigned)(reinterpret_cast<uintptr_t>(src) & 15u);
-    const u32x4 *from = reinterpret_cast<const u32x4 *>(src - a);
-    u32x4 *to = reinterpret_cast<u32x4 *>(dst16);
-    const int blocks = n > 0 ? (int)((a + (unsigned)n + 15u) >> 4) : 0;
-    for (int k = lane; k < blocks; k += 64) to[k] = from[k];
-    return dst16 + a;
-}
+using dpx_dev::stage_bytes;
+using dpx_dev::u32x4;
+using dpx_dev::wave_max_u64;
 
 /* the R codes of one lane and step (4 bits each, row r in bits 4r) into the lane's 32-nibble store word: step q of the group */
 template <int R>
@@ -57,15 +49,6 @@ __device__ __forceinline__ void dir_put(uint32_t (&acc)[4], const int q, const u
 __device__ __forceinline__ void dir_store(unsigned char *dst, const uint32_t (&acc)[4]) {
     const u32x4 v = {acc[0], acc[1], acc[2], acc[3]};
     *reinterpret_cast<u32x4 *>(dst) = v; /* global_store_dwordx4: the wave writes one whole KiB */
-}
-
-__device__ __forceinline__ unsigned long long dir_wave_max_u64(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(v, off, 64);
-        v = o > v ? o : v;
-    }
-    return v;
 }
 
 /* =====================================================================================================
@@ -98,7 +81,7 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_linear_dir(const dpx_dir_a
     if constexpr (GLOBAL) my = a.scratch + (size_t)slot * a.ldsPerWave;
     else my = smem + (size_t)wv * a.ldsPerWave;
     int32_t *edge = reinterpret_cast<int32_t *>(my); /* edge[j], j = 0..n+1: H of the row above the current stripe */
-    const unsigned char *refl = dir_stage(my + a.ldsRefOff + 64, ref, n, lane) - 64; /* refl[64 + (j-1)] */
+    const unsigned char *refl = stage_bytes(my + a.ldsRefOff + 64, ref, n, lane, 64) - 64; /* refl[64 + (j-1)] */
     for (int x = lane; x <= n + 1; x += 64) edge[x] = LOCAL ? 0 : x * gap; /* row-0 border (LinearNeedlemanWunsch.cpp:38-41) */
     if constexpr (GLOBAL) __threadfence_block();
 
@@ -179,7 +162,7 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_linear_dir(const dpx_dir_a
         /* first strict maximum in row-major order (LinearSmithWaterman.cpp:145-157): max score, then smallest row; a row's first
          * column is what its lane kept */
         const unsigned long long mine = ((unsigned long long)(unsigned)bestv << 32) | (unsigned)(0x7FFFFFFF - bestrow);
-        const unsigned long long top = dir_wave_max_u64(mine);
+        const unsigned long long top = wave_max_u64(mine);
         if ((int)(top >> 32) == 0) {
             if (lane == 0) { a.score[p] = 0; a.endRow[p] = 0; a.endCol[p] = 0; }
         } else if (mine == top) {
@@ -355,20 +338,11 @@ __global__ void __launch_bounds__(256) k_export_dir(const unsigned char *codes, 
 template <class K>
 hipError_t dir_launch(K kernel, const dpx_dir_args &a, hipStream_t s) {
     const unsigned wpb = a.wavesPerBlock ? a.wavesPerBlock : 1u;
-    const size_t lds = a.scratch ? 0 : (size_t)a.ldsPerWave * wpb;
-    if (lds > 64u * 1024u) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    if (!a.scratch) {
-        const unsigned grid = ((unsigned)a.numPairs + wpb - 1) / wpb;
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(64u * wpb), lds, s, a);
-        return hipGetLastError();
-    }
-    dpx_dir_args c = a; /* global edge rows: DPX_DIR_SCRATCH_SLOTS waves per launch, each launch reusing the scratch */
+    if (!a.scratch) return dpx_dev::launch_lds(kernel, dim3(((unsigned)a.numPairs + wpb - 1) / wpb), dim3(64u * wpb), (size_t)a.ldsPerWave * wpb, s, a);
+    dpx_dir_args c = a; /* global edge rows (no LDS): DPX_DIR_SCRATCH_SLOTS waves per launch, each launch reusing the scratch */
     for (c.firstSlot = 0; c.firstSlot < a.numPairs; c.firstSlot += DPX_DIR_SCRATCH_SLOTS) {
         const unsigned waves = (unsigned)std::min(a.numPairs - c.firstSlot, DPX_DIR_SCRATCH_SLOTS);
-        hipLaunchKernelGGL(kernel, dim3((waves + wpb - 1) / wpb), dim3(64u * wpb), lds, s, c);
+        hipLaunchKernelGGL(kernel, dim3((waves + wpb - 1) / wpb), dim3(64u * wpb), 0, s, c);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

@@ -1,4 +1,5 @@
-/* dpx_kernels.h -- interface between the C-ABI layer (dpx_capi.cpp) and the HIP kernels (dpx_kernels.hip). */
+/* dpx_kernels.h -- interface between the C-ABI layer (dpx_capi.cpp) and the HIP kernel units: dpx_kernels.hip (linear-gap fills),
+ * dpx_affine_kernels.hip, dpx_bsw_kernels.hip, dpx_traceback_kernels.hip, dpx_output_kernels.hip and the banded affine units. */
 #ifndef DPX_KERNELS_H
 #define DPX_KERNELS_H
 
@@ -41,6 +42,11 @@ typedef struct dpx_fill_args {
 
 hipError_t dpx_launch_fill(const dpx_fill_args &a, int algo, int R, bool store, size_t ldsBytes, hipStream_t stream);
 hipError_t dpx_launch_fill_lanes(const dpx_fill_args &a, int algo, int R, bool store, size_t ldsBytes, hipStream_t stream);
+/* between units, not for dpx_capi.cpp: what the two dispatchers above (dpx_kernels.hip) hand the other families' batches to.
+ * dpx_affine_kernels.hip takes ANW / ASW / ASG, dpx_bsw_kernels.hip BSW (C = cells per lane); a.numPairs > 0 */
+hipError_t dpx_launch_affine_fill(const dpx_fill_args &a, int algo, int R, bool store, size_t ldsBytes, hipStream_t stream);
+hipError_t dpx_launch_affine_lanes(const dpx_fill_args &a, int algo, int R, bool store, size_t ldsBytes, hipStream_t stream);
+hipError_t dpx_launch_bsw_fill(const dpx_fill_args &a, int C, bool store, size_t ldsBytes, hipStream_t stream);
 hipError_t dpx_launch_fill_lanes_packed(const dpx_fill_args &a, int algo, size_t ldsBytes, hipStream_t stream);
 hipError_t dpx_launch_fill_split(const dpx_fill_args &a, int algo, int R, int waves, size_t ldsBytes, hipStream_t stream);
 hipError_t dpx_launch_banded_packed(const dpx_fill_args &a, int C, size_t ldsBytes, hipStream_t stream);

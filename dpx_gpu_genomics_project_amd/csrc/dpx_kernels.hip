@@ -1,5 +1,8 @@
 /*
- * dpx_kernels.hip -- hand-written gfx950 (CDNA4) kernels of the pairwise-alignment DP fill.
+ * dpx_kernels.hip -- hand-written gfx950 (CDNA4) kernels of the pairwise-alignment DP fill: the linear-gap fills (LNW / LSW), the
+ * headline.  The other families have units of their own: dpx_affine_kernels.hip (Gotoh fills), dpx_bsw_kernels.hip (banded SW),
+ * dpx_traceback_kernels.hip (matrix export and the walks), dpx_output_kernels.hip (result text); dpx_device.hpp and
+ * dpx_fill_common.hpp hold what they share.
  *
  * One 64-lane wavefront per alignment pair.  Lane l owns R consecutive query rows of a 64*R-row stripe and
  * sweeps the reference columns with a skew of one column per lane, so the wave is always on one anti-diagonal
@@ -20,6 +23,7 @@
 
 #include <type_traits>
 
+#include "dpx_fill_common.hpp"
 #include "dpx_kernels.h"
 #include "dpx_layout.h"
 #include "dpx_prims.hpp"
@@ -34,113 +38,8 @@ using dpx::u16x2;
 using dpx::as_s16x2;
 using dpx::as_u16x2;
 using dpx::as_u32;
-
-/* ---- coalesced tile store: R int32 scores -> R int16, 2*R bytes per lane, lanes contiguous ---- */
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-/* matrices are written once and never re-read by the fill: DPX_NT_STORES selects `global_store ... nt` */
-#ifndef DPX_NT_STORES
-#define DPX_NT_STORES 0
-#endif
-#ifndef DPX_EXP_NOCOMPUTE
-#define DPX_EXP_NOCOMPUTE 0
-#endif
-#ifndef DPX_EXP_NORAMPSTORE
-#define DPX_EXP_NORAMPSTORE 0
-#endif
-/* ablation builds of the lane-packed kernels (tools/ab_quad.sh): 1 = no global stores, 2 = stores without the LDS round trip */
-#ifndef DPX_EXP_QUAD
-#define DPX_EXP_QUAD 0
-#endif
-
-/* ---- sequence staging: wide loads instead of one byte per lane and instruction ----------------------------------
- * Sequences sit at arbitrary byte offsets of the flat parseInput buffer (c++/parseInput.cpp:78-112 keeps the file's
- * bytes where they are).  stage_bytes() copies a string into LDS with aligned 16-byte loads and stores: the copy
- * starts at the 16-byte block that holds the first character, so the string lands `src & 15` bytes into the
- * (16-byte aligned) LDS buffer; the returned pointer is its first character.  The buffer needs n + 31 bytes.  The
- * device arena is 256-byte aligned and padded, so the blocks read never leave it.  `l` = the calling lane's index
- * among the G lanes that share the copy. */
-__device__ __forceinline__ unsigned char *stage_bytes(unsigned char *dst16, const unsigned char *src, const int n, const int l, const int G) {
-    const unsigned a = (unsigned)(reinterpret_cast<uintptr_t>(src) & 15u);
-    const u32x4 *from = reinterpret_cast<const u32x4 *>(src - a);
-    u32x4 *to = reinterpret_cast<u32x4 *>(dst16);
-    const int blocks = n > 0 ? (int)((a + (unsigned)n + 15u) >> 4) : 0;
-    for (int k = l; k < blocks; k += G) to[k] = from[k];
-    return dst16 + a;
-}
-
-/* four bytes from an arbitrary address: two aligned dword loads + v_alignbyte_b32 */
-__device__ __forceinline__ uint32_t load4(const unsigned char *p) {
-    const unsigned sh = (unsigned)(reinterpret_cast<uintptr_t>(p) & 3u);
-    const uint32_t *al = reinterpret_cast<const uint32_t *>(p - sh);
-    return __builtin_amdgcn_alignbyte(al[1], al[0], sh);
-}
-
-/* the R query characters of a lane's rows (row0 .. row0+R-1 of `qry`) from R/4 + 1 aligned dword loads and
- * v_alignbyte_b32 instead of R byte loads; rows past the query's end get 0x100 (matches no byte) */
-template <int R>
-__device__ __forceinline__ void load_query_rows(int (&qc)[R], const unsigned char *qry, const int row0, const int nrows) {
-    if (nrows <= 0) {
-#pragma unroll
-        for (int r = 0; r < R; r++) qc[r] = 0x100;
-        return;
-    }
-    constexpr int W = (R + 3) / 4;
-    const unsigned char *at = qry + row0;
-    const unsigned sh = (unsigned)(reinterpret_cast<uintptr_t>(at) & 3u);
-    const uint32_t *al = reinterpret_cast<const uint32_t *>(at - sh);
-    uint32_t d[W + 1];
-#pragma unroll
-    for (int k = 0; k <= W; k++) d[k] = al[k];
-#pragma unroll
-    for (int k = 0; k < W; k++) {
-        const uint32_t v = __builtin_amdgcn_alignbyte(d[k + 1], d[k], sh); /* bytes 4k .. 4k+3 of the lane's rows */
-#pragma unroll
-        for (int bq = 0; bq < 4 && 4 * k + bq < R; bq++) {
-            const int r = 4 * k + bq;
-            qc[r] = (r < nrows) ? (int)((v >> (8 * bq)) & 0xFFu) : 0x100;
-        }
-    }
-}
-
-template <class V>
-__device__ __forceinline__ void stream_store(V *dst, V v) {
-#if DPX_NT_STORES
-    __builtin_nontemporal_store(v, dst);
-#else
-    *dst = v;
-#endif
-}
-
-template <int R>
-__device__ __forceinline__ void store_tile(int16_t *dst, const int (&v)[R]) {
-    if constexpr (R == 1) {
-        *dst = (int16_t)v[0];
-    } else if constexpr (R == 2) {
-        stream_store(reinterpret_cast<uint32_t *>(dst), pack_lo16(v[0], v[1]));
-    } else if constexpr (R == 4) {
-        u32x2 w = {pack_lo16(v[0], v[1]), pack_lo16(v[2], v[3])};
-        stream_store(reinterpret_cast<u32x2 *>(dst), w);
-    } else {
-#pragma unroll
-        for (int q = 0; q < R / 8; q++) {
-            u32x4 w = {pack_lo16(v[8 * q + 0], v[8 * q + 1]), pack_lo16(v[8 * q + 2], v[8 * q + 3]),
-                       pack_lo16(v[8 * q + 4], v[8 * q + 5]), pack_lo16(v[8 * q + 6], v[8 * q + 7])};
-            stream_store(reinterpret_cast<u32x4 *>(dst + q * 512), w); /* sub-tile q: its own 1 KiB [lane][8] block */
-        }
-    }
-}
-
-/* 64-lane max-reduction of a 64-bit key (once per pair; cost irrelevant) */
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        unsigned long long o = __shfl_xor(v, off, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
+using namespace dpx_dev;
+using namespace dpx_fill;
 
 /* =====================================================================================================
  * Linear-gap fill: LinearNeedlemanWunsch (LOCAL = false) and LinearSmithWaterman (LOCAL = true).
@@ -154,37 +53,6 @@ struct LinState {
     unsigned key[R];  /* SW: per-row running max of (H << 16 | 0xFFFF - j): max score, then smallest column */
     int dtop;         /* H[row0][j-1]: diagonal of the lane's top row */
 };
-
-/* Single-stripe pairs shorter than 64*R rows leave the upper lanes without rows; those lanes need not store.  Returns
- * the number of lanes that do: the row-owning lanes rounded up to whole 128-byte lines of the store (a line written
- * in part costs a read-modify-write at the memory side: rounding to 64-byte sectors measured 25 % slower on the
- * short-read batch, profiles/README.md). */
-template <int R>
-__device__ __forceinline__ int store_lanes(const int m) {
-    constexpr int perLine = 128 / (2 * (R < 8 ? R : 8)); /* lanes per 128-byte line: 32 / 16 / 8 for R = 2 / 4 / >= 8 */
-    const int owning = (m + R - 1) / R;
-    return min(64, (owning + perLine - 1) / perLine * perLine);
-}
-
-/* Skew ramps: in step t of a stripe of n columns only the lanes t-n+1 .. t are on a real cell.  Storing the whole chunk writes
- * 6 % of padding at 1024 x 1024 (12 % at 512 x 512); storing exactly the lanes on a cell leaves partly written 128-byte lines,
- * which cost more than they save (profiles/README.md).  So the ramp steps store the lanes on a cell ROUNDED OUT TO WHOLE LINES
- * (8 lanes x 16 B; 16 / 32 lanes for 4 / 2 rows per lane): nearly all of the padding stays unwritten, every written line is
- * whole.  DPX_EXP_FULLRAMP=1 builds the round-1 behaviour (whole chunks) for A/B runs. */
-#ifndef DPX_EXP_FULLRAMP
-#define DPX_EXP_FULLRAMP 0
-#endif
-template <int R>
-__device__ __forceinline__ bool ramp_stores(const int lane, const int t, const int n, const int rampLines) {
-#if DPX_EXP_FULLRAMP
-    return true;
-#else
-    if (!rampLines) return true; /* small batches are bound by the latency of a step, not by bytes: whole chunks are cheaper there */
-    constexpr int perLine = 128 / (2 * (R < 8 ? R : 8));
-    const int lo = max(t - n + 1, 0) & ~(perLine - 1), hi = (min(t, 63) + perLine) & ~(perLine - 1);
-    return lane >= lo && lane < hi;
-#endif
-}
 
 /* the R chained cells of one lane for one column (shared by the striped and the rolling schedule) */
 template <int R, bool LOCAL, bool KEYS>
@@ -261,22 +129,6 @@ __device__ __forceinline__ void store_words(int16_t *dst, const uint32_t (&w)[(R
         for (int q = 0; q < R / 8; q++) {
             u32x4 v = {w[4 * q + 0], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]};
             stream_store(reinterpret_cast<u32x4 *>(dst + q * 512), v); /* sub-tile q: its own 1 KiB [lane][8] block */
-        }
-    }
-}
-
-/* SW: fold the finished stripe's per-row keys into the lane's best (rows ascend with r and with the stripe index,
- * so a strict '>' keeps the first row holding the lane's maximum) */
-template <int R, bool LOCAL>
-__device__ __forceinline__ void lin_fold_keys(const LinState<R, LOCAL> &st, const int row0, const int nrows, int &bestv,
-                                              int &bestrow, int &bestcol) {
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const int hv = (int)(st.key[r] >> 16), col = 0xFFFF - (int)(st.key[r] & 0xFFFFu);
-        if (r < nrows && hv > bestv) {
-            bestv = hv;
-            bestrow = row0 + 1 + r;
-            bestcol = col;
         }
     }
 }
@@ -386,7 +238,7 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_linear_fill(const dpx_fill
             const int upin = wave_shr1(st.Hl[R - 1], e0 + gap);
             if (sw) { /* stripe switch (one lane per step for 64 steps around each stripe boundary) */
                 if constexpr (LOCAL) {
-                    lin_fold_keys<R, LOCAL>(st, row0, nrows, bestv, bestrow, bestcol);
+                    fold_row_keys<R>(st.key, row0, nrows, bestv, bestrow, bestcol);
                 }
                 row0 += 64 * R;
                 nrows = min(max(m - row0, 0), R);
@@ -423,7 +275,7 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_linear_fill(const dpx_fill
             roll_step(T + 1);
         }
         if (T < total) roll_step(T);
-        if constexpr (LOCAL) lin_fold_keys<R, LOCAL>(st, row0, nrows, bestv, bestrow, bestcol);
+        if constexpr (LOCAL) fold_row_keys<R>(st.key, row0, nrows, bestv, bestrow, bestcol);
     } else {
         /* ---------- striped schedule (single stripe, or references too short to roll) ---------- */
         const int W = n + 63;
@@ -474,7 +326,7 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_linear_fill(const dpx_fill
                 for (int t = 0; t < W; t++) DPX_LIN_STEP(t, true, false, laneHasRows)
             }
 #undef DPX_LIN_STEP
-            if constexpr (LOCAL) lin_fold_keys<R, LOCAL>(st, row0, nrows, bestv, bestrow, bestcol);
+            if constexpr (LOCAL) fold_row_keys<R>(st.key, row0, nrows, bestv, bestrow, bestcol);
         }
     }
 
@@ -588,31 +440,6 @@ struct LineStage {
 #endif
     }
 };
-
-/* what a lane learns from the wave's descriptor */
-struct LaneSlot {
-    bool has;
-    int p, l, num, d; /* pair, lane inside the slot, lanes of the slot, start delay (first lane mod 8) */
-    uint32_t refOff;  /* LDS byte offset of the slot's staged reference inside the wave's reference area */
-};
-__device__ __forceinline__ LaneSlot find_slot(const dpx_wave_desc *wd, const int lane) {
-    LaneSlot s{false, 0, 0, 0, 0, 0u};
-    const uint32_t *w = reinterpret_cast<const uint32_t *>(wd); /* wave-uniform address: 2 dwords per slot through scalar loads */
-    static_assert(DPX_WAVE_SLOTS % 4 == 0 && sizeof(dpx_wave_desc) == 8 * DPX_WAVE_SLOTS, "descriptor is read as dwords");
-    constexpr int kFirst = DPX_WAVE_SLOTS, kNum = DPX_WAVE_SLOTS + DPX_WAVE_SLOTS / 4, kRef = DPX_WAVE_SLOTS + DPX_WAVE_SLOTS / 2; /* dword offsets */
-#pragma unroll
-    for (int k = 0; k < DPX_WAVE_SLOTS; k++) {
-        const int f = (int)((w[kFirst + (k >> 2)] >> (8 * (k & 3))) & 0xFFu), c = (int)((w[kNum + (k >> 2)] >> (8 * (k & 3))) & 0xFFu);
-        const uint32_t ro = (w[kRef + (k >> 1)] >> (16 * (k & 1))) & 0xFFFFu;
-        if (lane >= f && lane < f + c) { s.has = true; s.p = (int)w[k]; s.l = lane - f; s.num = c; s.d = f & 7; s.refOff = ro << 4; }
-    }
-    return s;
-}
-__device__ __forceinline__ int wave_max_i32(int v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
-    return v;
-}
 
 template <int R, bool LOCAL, bool STORE>
 __global__ void __launch_bounds__(DPX_FILL_THREADS) k_linear_lanes(const dpx_fill_args a) {
@@ -760,7 +587,7 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_linear_lanes(const dpx_fil
         /* first strict maximum in row-major order over the slot's lanes (rows ascend with the lane): the slot's first lane
          * scans its lanes' (score, row, column) in the lane scratch */
         int bestv = 0, bestrow = 0, bestcol = 0;
-        lin_fold_keys<R, LOCAL>(st, row0, nrows, bestv, bestrow, bestcol);
+        fold_row_keys<R>(st.key, row0, nrows, bestv, bestrow, bestcol);
         int *mine = reinterpret_cast<int *>(scratch + lane * 16);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); /* (the line stage this aliases has been read to the end) */
         __builtin_amdgcn_wave_barrier();
@@ -911,7 +738,7 @@ __global__ void __launch_bounds__(64 * DPX_SPLIT_MAX_WAVES) k_linear_split(const
     /* results: every wave leaves its candidate in LDS; the wave that arrives last combines them */
     int bestv = 0, bestrow = 0, bestcol = 0;
     if constexpr (LOCAL) {
-        lin_fold_keys<R, LOCAL>(st, row0, nrows, bestv, bestrow, bestcol);
+        fold_row_keys<R>(st.key, row0, nrows, bestv, bestrow, bestcol);
         const unsigned long long mine = ((unsigned long long)(unsigned)bestv << 32) | (unsigned)(0x7FFFFFFF - bestrow);
         const unsigned long long top = wave_max_u64(mine);
         if (mine == top && (bestv > 0 ? true : lane == 0)) { result[4 * w] = bestv; result[4 * w + 1] = bestrow; result[4 * w + 2] = bestcol; }
@@ -980,16 +807,6 @@ __device__ __forceinline__ uint32_t pk_row_tag_of(uint32_t h, const int r) {
     default: return 0u;
     }
 #undef DPX_TAG_CASE
-}
-
-__device__ __forceinline__ uint32_t pk_hi16(uint32_t lo, uint32_t hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302u); } /* {lo.hi16, hi.hi16} */
-
-/* SW with gap <= 0 (round 3): max(up, left) - |gap| SATURATING at 0 (v_pk_sub_u16 ... clamp; SW cells are never negative, so the signed
- * maximum of two of them is their unsigned one).  The gap term is then >= 0, so H = max(gap term, diag + s) >= 0 without the extra
- * v_pk_max_i16(H, 0) of c++/LinearSmithWaterman.cpp:103 -- the SW cell costs what the NW cell costs.  The host sends a batch to the
- * kernels that use this only if gap <= 0. */
-__device__ __forceinline__ s16x2 pk_gap_sat(const uint32_t up, const uint32_t left, const uint32_t gabsP) {
-    return as_s16x2(as_u32(__builtin_elementwise_sub_sat(as_u16x2(as_u32(dpx::pk_max(as_s16x2(up), as_s16x2(left)))), as_u16x2(gabsP))));
 }
 
 template <int R>
@@ -1430,1829 +1247,70 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_linear_lanes_pk(const dpx_
     }
 }
 
-/* =====================================================================================================
- * Affine-gap (Gotoh) global fill: AffineNeedlemanWunsch (c++/AffineNeedlemanWunsch.cpp:167-240).
- *   D[i][j] = (i==1) ? H[i-1][j]+o+e : max(H[i-1][j]+o+e, D[i-1][j]+e)      vertical gap   (:185-197)
- *   I[i][j] = (j==1) ? H[i][j-1]+o+e : max(H[i][j-1]+o+e, I[i][j-1]+e)      horizontal gap (:201-213)
- *   H[i][j] = max(I, max(D, H[i-1][j-1]+s))                                                (:229-236)
- * The i==1 / j==1 special cases are expressed by virtual borders D[0][j] = I[i][0] = DPX_NEG, which gives the
- * identical values for every stored cell.  Three int16 planes (H, I, D) are written per step.
- * Affine-gap Smith-Waterman (ASW, LOCAL = true) shares the body: H = max(0, ...) with zero borders, and the start cell is tracked
- * as in k_linear_fill (per-row (H << 16 | 0xFFFF - j) keys folded per stripe, one wave reduction at the end).
- * ===================================================================================================== */
-template <int R>
-struct AffState {
-    int Hl[R], Il[R]; /* H[row][j-1], I[row][j-1] */
-    int Dl[R];        /* D[row][j] just computed (needed only for the store and the lane hand-off) */
-    int qc[R];
-    unsigned key[R];  /* ASW: per-row running max of (H << 16 | 0xFFFF - j); ASG: key[0] alone, of ((H + 0x8000) << 16 | 0xFFFF - j) in register rsel */
-    int dtop;
-};
-
-template <int R, int MODE> /* 0 ANW, 1 ASW, 2 ASG */
-__device__ __forceinline__ void aff_cells(AffState<R> &st, const int upH, const int upD, const int rc, const int match,
-                                          const int mismatch, const int oe, const int e, const unsigned negj, [[maybe_unused]] const int rsel = 0) {
-    int uH = upH, uD = upD, d = st.dtop;
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const int lH = st.Hl[r];
-        const int s = (st.qc[r] == rc) ? match : mismatch;
-        const int Dn = max(uH + oe, uD + e);
-        const int In = max(lH + oe, st.Il[r] + e);
-        int h = max(max(Dn, d + s), In); /* v_max3_i32 */
-        if constexpr (MODE == 1) {
-            h = max(h, 0);
-            st.key[r] = max(st.key[r], ((unsigned)h << 16) | negj);
-        }
-        d = lH;
-        uH = h;
-        uD = Dn;
-        st.Hl[r] = h;
-        st.Il[r] = In;
-        st.Dl[r] = Dn;
-    }
-    st.dtop = upH;
-    if constexpr (MODE == 2) { /* ASG: no floor; the running (max, first column) of ONE row, register rsel = (m-1) % R of every lane (the lane
-                                * that owns row m reads it).  H may be negative: biased into 0 .. 65535.  A select chain on the wave-uniform
-                                * rsel, not an indexed read: the registers stay registers. */
-        int hm = st.Hl[0];
-#pragma unroll
-        for (int r = 1; r < R; r++) hm = (r == rsel) ? st.Hl[r] : hm;
-        st.key[0] = max(st.key[0], ((unsigned)(hm + 0x8000) << 16) | negj);
-    }
-}
-
-template <int R, int MODE, bool STORE, bool MASKED, bool WHOLE>
-__device__ __forceinline__ void aff_step(AffState<R> &st, const int t, const int lane, const int n, const bool laneHasRows,
-                                         const int match, const int mismatch, const int oe, const int e, const int e0H,
-                                         const int e0D, const int rc, int16_t *edgeH, int16_t *edgeD,
-                                         const bool writeEdge, int16_t *tileDst, const int storeLanes, const int rampLines,
-                                         [[maybe_unused]] const int rsel = 0) {
-    const int j = t - lane + 1;
-    const int upH = wave_shr1(st.Hl[R - 1], e0H);
-    const int upD = wave_shr1(st.Dl[R - 1], e0D);
-    bool active = true;
-    if constexpr (MASKED) active = laneHasRows && (j >= 1) && (j <= n);
-    if (active) {
-        aff_cells<R, MODE>(st, upH, upD, rc, match, mismatch, oe, e, 0xFFFFu - (unsigned)j, rsel);
-        if (writeEdge && lane == 63) {
-            edgeH[j] = (int16_t)st.Hl[R - 1];
-            edgeD[j] = (int16_t)st.Dl[R - 1];
-        }
-        if constexpr (STORE && MASKED && !WHOLE) {
-            store_tile<R>(tileDst, st.Hl);
-            store_tile<R>(tileDst + 64 * R, st.Il);
-            store_tile<R>(tileDst + 128 * R, st.Dl);
-        }
-    }
-    if constexpr (STORE && (!MASKED || WHOLE)) { /* whole lines, also on the skew ramps (see lin_step) */
-        bool doStore = lane < storeLanes;
-        if constexpr (MASKED) doStore = doStore && ramp_stores<R>(lane, t, n, rampLines);
-        if (doStore) {
-            store_tile<R>(tileDst, st.Hl);
-            store_tile<R>(tileDst + 64 * R, st.Il);
-            store_tile<R>(tileDst + 128 * R, st.Dl);
-        }
-    }
-}
-
-/* ASW: fold per-row (H << 16 | 0xFFFF - j) keys into the lane's best (lin_fold_keys) */
-template <int R>
-__device__ __forceinline__ void fold_row_keys(const unsigned (&key)[R], const int row0, const int nrows, int &bestv, int &bestrow, int &bestcol) {
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const int hv = (int)(key[r] >> 16), col = 0xFFFF - (int)(key[r] & 0xFFFFu);
-        if (r < nrows && hv > bestv) {
-            bestv = hv;
-            bestrow = row0 + 1 + r;
-            bestcol = col;
-        }
-    }
-}
-
-/* ASW: fold a finished stripe's per-row keys into the lane's best (lin_fold_keys) */
-template <int R>
-__device__ __forceinline__ void aff_fold_keys(const AffState<R> &st, const int row0, const int nrows, int &bestv, int &bestrow, int &bestcol) {
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const int hv = (int)(st.key[r] >> 16), col = 0xFFFF - (int)(st.key[r] & 0xFFFFu);
-        if (r < nrows && hv > bestv) {
-            bestv = hv;
-            bestrow = row0 + 1 + r;
-            bestcol = col;
-        }
-    }
-}
-
-/* first strict maximum in row-major order over the lanes' bests (k_linear_fill, c++/LinearSmithWaterman.cpp:145-157) */
-__device__ __forceinline__ void sw_publish(const dpx_fill_args &a, const int p, const int lane, const int bestv, const int bestrow, const int bestcol) {
-    const unsigned long long mine = ((unsigned long long)(unsigned)bestv << 32) | (unsigned)(0x7FFFFFFF - bestrow);
-    const unsigned long long top = wave_max_u64(mine);
-    if ((int)(top >> 32) == 0) {
-        if (lane == 0) { a.score[p] = 0; a.endRow[p] = 0; a.endCol[p] = 0; }
-    } else if (mine == top) { /* rows are unique per lane: exactly one lane matches, and it holds the row's first column */
-        a.score[p] = bestv;
-        a.endRow[p] = bestrow;
-        a.endCol[p] = bestcol;
-    }
-}
-
-/* ASG: score and end cell of row m from that row's biased key (the lane that owns row m calls this with its own key): the first
- * maximum over columns 0 .. n, column 0 being the border H[m][0] = o + m*e, which wins a tie as the smallest column */
-__device__ __forceinline__ void asg_publish(const dpx_fill_args &a, const int p, const int m, const unsigned key, const int colZero) {
-    const int hv = (int)(key >> 16) - 0x8000, col = 0xFFFF - (int)(key & 0xFFFFu);
-    const bool zero = colZero >= hv;
-    a.score[p] = zero ? colZero : hv;
-    a.endRow[p] = m;
-    a.endCol[p] = zero ? 0 : col;
-}
-
-/* one wave per pair: k_affine_fill (ANW), k_asw_fill (ASW) and k_asg_fill (ASG) share their body, dpx_affine_fill.inc */
-template <int R, bool STORE>
-__global__ void __launch_bounds__(DPX_FILL_THREADS) k_affine_fill(const dpx_fill_args a) {
-    constexpr bool LOCAL = false, SEMI = false;
-#include "dpx_affine_fill.inc"
-}
-
-template <int R, bool STORE>
-__global__ void __launch_bounds__(DPX_FILL_THREADS) k_asw_fill(const dpx_fill_args a) {
-    constexpr bool LOCAL = true, SEMI = false;
-#include "dpx_affine_fill.inc"
-}
-
-template <int R, bool STORE>
-__global__ void __launch_bounds__(DPX_FILL_THREADS) k_asg_fill(const dpx_fill_args a) {
-    constexpr bool LOCAL = false, SEMI = true;
-#include "dpx_affine_fill.inc"
-}
-
-/* Affine lane-packed kernel: the Gotoh recurrence of k_affine_fill on the several-pairs-per-wave schedule of
- * k_linear_lanes (`up` of H and D through wave_shr:1, a slot's first lane takes the row-0 borders); the three planes H,
- * I, D leave through the same LDS line stage into the 8 x 8 tile layout, three whole-line stores per step.  One wave per
- * workgroup: the stage needs 27 KiB of LDS per wave (three planes), so small workgroups keep five of them on a CU. */
-/* Round 3: the cell update keeps its state as H + (o+e), I + e, D + e (aff_cells_g: 9 vector instructions per cell instead of 10, rows
- * in place), eight steps per trip, routing in registers, loop control on the scalar unit -- as in k_linear_lanes.  Tried and dropped:
- * a HALF-LINE stage (4 columns per lane and plane, 15 KiB of LDS per wave instead of 27: ten waves per CU instead of five; the two
- * 64-byte halves of a line stored four steps apart by the same wave) -- bit-exact, 2.42 ms instead of 1.67 on 100k short reads: a
- * 128-byte line that is written in two pieces costs far more than the residency buys. */
-
-template <int R>
-struct AffStateG {
-    int Hoe[R], Ie[R]; /* H[row][j-1] + (o+e), I[row][j-1] + e */
-    int qc[R];
-    int dtopOe;        /* H[row0][j-1] + (o+e) */
-    int DeLast;        /* D[row0+R][j] + e of the column just computed (the next lane's "D above") */
-    unsigned key[R];   /* ASW: per-row running max of (H << 16 | 0xFFFF - j); ASG: key[0] alone, of ((H + 0x8000) << 16 | 0xFFFF - j) in register rsel */
-};
-
-/* D = max(H_up + oe, D_up + e);  I = max(H_left + oe, I_left + e);  H = max3(D, H_diag + s, I)   (c++/AffineNeedlemanWunsch.cpp:185-236) */
-template <int R, int MODE> /* 0 ANW, 1 ASW, 2 ASG */
-__device__ __forceinline__ void aff_cells_g(AffStateG<R> &st, const int upHoe, const int upDe, const int rc, const int matchG, const int mismatchG,
-                                            const int oe, const int e, int (&Hv)[R], int (&Iv)[R], int (&Dv)[R], const unsigned negj,
-                                            [[maybe_unused]] const int rsel = 0) {
-    int dterm[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) dterm[r] = ((r == 0) ? st.dtopOe : st.Hoe[r - 1]) + ((st.qc[r] == rc) ? matchG : mismatchG); /* (s - oe) */
-    int ug = upHoe, ud = upDe;
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const int Dn = max(ug, ud);
-        const int In = max(st.Hoe[r], st.Ie[r]);
-        int h = max(max(Dn, dterm[r]), In); /* v_max3_i32 */
-        if constexpr (MODE == 1) { /* ASW: the zero floor, and the row's start-cell key */
-            h = max(h, 0);
-            st.key[r] = max(st.key[r], ((unsigned)h << 16) | negj);
-        }
-        Hv[r] = h; Iv[r] = In; Dv[r] = Dn;
-        ug = h + oe;
-        ud = Dn + e;
-        st.Hoe[r] = ug;
-        st.Ie[r] = In + e;
-    }
-    st.DeLast = ud;
-    st.dtopOe = upHoe;
-    if constexpr (MODE == 2) { /* ASG: the biased key of one row, register rsel = (m-1) % 8 of the slot's lanes (aff_cells) */
-        int hm = Hv[0];
-#pragma unroll
-        for (int r = 1; r < R; r++) hm = (r == rsel) ? Hv[r] : hm;
-        st.key[0] = max(st.key[0], ((unsigned)(hm + 0x8000) << 16) | negj);
-    }
-}
-
-template <int R, bool STORE>
-__global__ void __launch_bounds__(DPX_ALANES_THREADS) k_affine_lanes(const dpx_fill_args a) {
-    constexpr bool LOCAL = false, SEMI = false;
-#include "dpx_affine_lanes.inc"
-}
-
-template <int R, bool STORE>
-__global__ void __launch_bounds__(DPX_ALANES_THREADS) k_asw_lanes(const dpx_fill_args a) {
-    constexpr bool LOCAL = true, SEMI = false;
-#include "dpx_affine_lanes.inc"
-}
-
-template <int R, bool STORE>
-__global__ void __launch_bounds__(DPX_ALANES_THREADS) k_asg_lanes(const dpx_fill_args a) {
-    constexpr bool LOCAL = false, SEMI = true;
-#include "dpx_affine_lanes.inc"
-}
-
-/* =====================================================================================================
- * Banded Smith-Waterman (python/LinearBandedSmithWaterman.py:62-104): the LSW recurrence restricted to
- * |i-j| <= B-1; every cell outside the band (and the borders) reads as 0.
- *
- * The band is walked by anti-diagonals a = i+j.  One anti-diagonal holds at most B in-band cells
- * (slot s = (i-j+B-1)>>1); lane l owns the C = ceil(B/64) slots [l*C, l*C+C), so all 64 lanes work on every
- * step -- no stripes, no skew, no LDS edge row.  With p = (a+B-1)&1 the neighbours on the previous
- * anti-diagonal are   p=1: up = prev[s], left = prev[s+1]      p=0: up = prev[s-1], left = prev[s]
- * and the diagonal is prev2[s]; the one value that crosses a lane boundary moves with a single DPP
- * (wave_shl:1 / wave_shr:1).  Query / reference characters ride along in registers: entering a p=1 step the
- * query window slides one slot down, entering a p=0 step the reference window slides one slot up.
- * ===================================================================================================== */
-template <int C>
-struct BandState {
-    int prev[C], prev2[C]; /* anti-diagonals a-1 and a-2 */
-    int qch[C], rch[C];    /* query / reference character of each slot's cell */
-    unsigned key[C];       /* running max of (H << 16 | 0xFFFF - A): max score, then earliest step */
-    int inBand[2][C];      /* ~0 / 0: is slot s inside the band on a step of parity p (s <= B-1-p)? */
-};
-
-/* INTERIOR: every in-band slot of this anti-diagonal lies inside the matrix, so validity is the per-lane constant
- * inBand mask (one v_and) instead of two compares against the step's slot window */
-template <int C, bool P1, bool INTERIOR>
-__device__ __forceinline__ void band_step(BandState<C> &st, const int A, int &i0, int &j0, const int lane, const int m,
-                                          const int n, const int B, const int match, const int mismatch, const int gap,
-                                          const unsigned char *qL, const unsigned char *rL, int *out) {
-    const int p = P1 ? 1 : 0;
-    /* (i0, j0) = row / column of slot 0 on this anti-diagonal, kept incrementally (wave-uniform): entering a p=1 step
-     * the row advances, entering a p=0 step the column does.  i0 = (A+2 + p - (B-1)) >> 1 may be <= 0. */
-    if constexpr (P1) i0++; else j0++;
-    const int smin = INTERIOR ? 0 : max(max(1 - i0, j0 - n), 0);
-    const int smax = INTERIOR ? 0 : min(min(m - i0, j0 - 1), B - 1 - p);
-    int up[C], left[C];
-    if constexpr (P1) {
-        /* interior: 1 <= i0 and i0 + (B-1-p) <= m, so the index stays below m + 64 (the staged query has 64 B of slack) */
-        const int newq = INTERIOR ? qL[i0 + 64 * C - 2] : qL[min(max(i0 + 64 * C - 2, 0), m - 1)];
-        const int tq = wave_shl1(st.qch[0], newq);
-#pragma unroll
-        for (int c = 0; c < C - 1; c++) st.qch[c] = st.qch[c + 1];
-        st.qch[C - 1] = tq;
-        const int nb = wave_shl1(st.prev[0], 0);
-#pragma unroll
-        for (int c = 0; c < C; c++) { up[c] = st.prev[c]; left[c] = (c < C - 1) ? st.prev[c + 1] : nb; }
-    } else {
-        const int newr = INTERIOR ? rL[j0 - 1] : rL[min(max(j0 - 1, 0), n - 1)]; /* interior: 1 <= j0 <= n */
-        const int tr = wave_shr1(st.rch[C - 1], newr);
-#pragma unroll
-        for (int c = C - 1; c > 0; c--) st.rch[c] = st.rch[c - 1];
-        st.rch[0] = tr;
-        const int nb = wave_shr1(st.prev[C - 1], 0);
-#pragma unroll
-        for (int c = 0; c < C; c++) { left[c] = st.prev[c]; up[c] = (c > 0) ? st.prev[c - 1] : nb; }
-    }
-    const unsigned negA = 0xFFFFu - (unsigned)A;
-#pragma unroll
-    for (int c = 0; c < C; c++) {
-        const int sc = (st.qch[c] == st.rch[c]) ? match : mismatch;
-        int h = max(max(max(up[c], left[c]) + gap, st.prev2[c] + sc), 0);
-        if constexpr (INTERIOR) {
-            h &= st.inBand[P1 ? 1 : 0][c];
-        } else {
-            const int s = lane * C + c;
-            h = ((s >= smin) && (s <= smax)) ? h : 0;
-        }
-        st.key[c] = max(st.key[c], ((unsigned)h << 16) | negA);
-        st.prev2[c] = st.prev[c];
-        st.prev[c] = h;
-        out[c] = h;
-    }
-}
-
-template <int C, bool PB, bool STORE>
-__global__ void __launch_bounds__(DPX_FILL_THREADS) k_banded_fill(const dpx_fill_args a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int G = (C >= 8) ? 1 : 8 / C; /* steps per 16-byte store */
-    constexpr int GG = (G < 2) ? 2 : G;     /* steps per loop iteration (parity pattern repeats every 2) */
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int p = blockIdx.x * (int)a.wavesPerBlock + wv;
-    if (p >= a.numPairs) return;
-    if (a.order) p = a.order[p];
-    const dpx_pair_dev pr = a.pairs[p];
-    const int n = pr.n, m = pr.m, B = a.band;
-    const int match = a.match, mismatch = a.mismatch, gap = a.gapOpen;
-    if (m <= 0 || n <= 0) {
-        if (lane == 0) { a.score[p] = 0; a.endRow[p] = 0; a.endCol[p] = 0; }
-        return;
-    }
-    const unsigned char *ref = reinterpret_cast<const unsigned char *>(a.seq + pr.refIdx);
-    const unsigned char *qry = reinterpret_cast<const unsigned char *>(a.seq + pr.qryIdx);
-    unsigned char *my = smem + (size_t)wv * a.ldsPerWave;
-    const unsigned char *qL = stage_bytes(my, qry, m, lane, 64);            /* 16-byte loads; each buffer has 16 spare bytes for the shift */
-    const unsigned char *rL = stage_bytes(my + a.ldsRefOff, ref, n, lane, 64);
-
-    BandState<C> st;
-    { /* character windows of the virtual anti-diagonal a = 1 (the first real step then slides one of them) */
-        const int p1 = B & 1; /* (1 + B - 1) & 1 */
-        const int i0 = (1 + p1 - (B - 1)) >> 1;
-        const int j0 = 1 - i0;
-#pragma unroll
-        for (int c = 0; c < C; c++) {
-            const int s = lane * C + c;
-            st.qch[c] = qL[min(max(i0 + s - 1, 0), m - 1)];
-            st.rch[c] = rL[min(max(j0 - s - 1, 0), n - 1)];
-            st.prev[c] = 0;
-            st.prev2[c] = 0;
-            st.key[c] = 0u;
-            st.inBand[0][c] = (s <= B - 1) ? -1 : 0;
-            st.inBand[1][c] = (s <= B - 2) ? -1 : 0;
-        }
-    }
-    /* is every in-band slot of anti-diagonal A inside the matrix?  (true for one contiguous range of A) */
-    auto interior = [&](const int A) -> bool {
-        const int aa = A + 2, pp = (aa + B - 1) & 1;
-        const int i0 = (aa + pp - (B - 1)) >> 1, j0 = aa - i0, top = B - 1 - pp;
-        return i0 >= 1 && i0 + top <= m && j0 - top >= 1 && j0 <= n;
-    };
-    const int NS = m + n - 1;               /* anti-diagonals a = 2 .. m+n */
-    const int numGroups = (NS + G - 1) / G;
-    int16_t *Hp = a.mat + pr.matOff + (size_t)lane * 8u;
-    const size_t cs = pr.chunkStride;
-    int acc[8];
-    /* slot 0's (row, column) on the virtual anti-diagonal a = 1; band_step advances them */
-    int i0 = (1 + (B & 1) - (B - 1)) >> 1;
-    int j0 = 1 - i0;
-#define DPX_BAND_BODY(INTERIOR_)                                                                                          \
-    _Pragma("unroll") for (int g = 0; g < GG; g += 2) {                                                                  \
-        band_step<C, PB, INTERIOR_>(st, A0 + g, i0, j0, lane, m, n, B, match, mismatch, gap, qL, rL, &acc[(g % G) * C]);  \
-        if constexpr (STORE && G == 1) {                                                                                  \
-            if (INTERIOR_ || A0 + g < numGroups) store_tile<8>(Hp + (size_t)(A0 + g) * cs, acc);                         \
-        }                                                                                                                 \
-        band_step<C, !PB, INTERIOR_>(st, A0 + g + 1, i0, j0, lane, m, n, B, match, mismatch, gap, qL, rL,                 \
-                                     &acc[((g + 1) % G) * C]);                                                            \
-        if constexpr (STORE) {                                                                                            \
-            if (((g + 1) % G) == G - 1) {                                                                                 \
-                const int grp = (A0 + g + 1) / G;                                                                         \
-                if (INTERIOR_ || grp < numGroups) store_tile<8>(Hp + (size_t)grp * cs, acc);                             \
-            }                                                                                                             \
-        }                                                                                                                 \
-    }
-    /* parity of step A is (A + B + 1) & 1; A0 is even, so even steps have parity PB and odd steps !PB.
-     * Three phases: head (some slots outside the matrix), interior, tail. */
-    int A0 = 0;
-    for (; A0 < NS && !(interior(A0) && interior(A0 + GG - 1)); A0 += GG) { DPX_BAND_BODY(false) }
-    for (; A0 + GG <= NS && interior(A0 + GG - 1); A0 += GG) { DPX_BAND_BODY(true) }
-    for (; A0 < NS; A0 += GG) { DPX_BAND_BODY(false) }
-#undef DPX_BAND_BODY
-    /* candidates: every slot's first maximum; rows/cols recovered from (step, slot).  Within a slot cells arrive in
-     * row-major order, so the earliest step is the slot's first maximum; across slots pick max score, min row, min col */
-    unsigned long long mine = 0ull;
-#pragma unroll
-    for (int c = 0; c < C; c++) {
-        const int hv = (int)(st.key[c] >> 16);
-        if (hv > 0) {
-            const int A = 0xFFFF - (int)(st.key[c] & 0xFFFFu);
-            const int aa = A + 2;
-            const int pp = (aa + B - 1) & 1;
-            const int u = 2 * (lane * C + c) + pp;
-            const int i = (aa + u - (B - 1)) >> 1;
-            const int j = aa - i;
-            const unsigned long long k = ((unsigned long long)(unsigned)hv << 40) | ((unsigned long long)(0xFFFFFu - (unsigned)i) << 20) |
-                                         (unsigned long long)(0xFFFFFu - (unsigned)j);
-            mine = k > mine ? k : mine;
-        }
-    }
-    const unsigned long long top = wave_max_u64(mine);
-    if (lane == 0) {
-        const int hv = (int)(top >> 40);
-        a.score[p] = hv;
-        a.endRow[p] = hv > 0 ? (int)(0xFFFFFu - (unsigned)((top >> 20) & 0xFFFFFu)) : 0;
-        a.endCol[p] = hv > 0 ? (int)(0xFFFFFu - (unsigned)(top & 0xFFFFFu)) : 0;
-    }
-}
-
-/* =====================================================================================================
- * "+Opt" for the band: two equal-shaped pairs per wave, pair A in the high and pair B in the low half of every register,
- * the cell update on the packed-int16 pipe as in k_linear_fill_pk (the reference's V18/V19 idea, cuda/LNW/
- * LinearNeedlemanWunschV18.cu:112-341), the anti-diagonal schedule of k_banded_fill unchanged: one DPP move carries both
- * pairs' neighbour cell, the per-lane in-band masks and the head / tail window tests are the same for both (same shape).
- * The one-pair kernel needs ~36 vector instructions per step for its 2 cells per lane (band 128) and sits between the
- * VALU and the write limit; two pairs per instruction leave it to the stores.  SW start cell per half: packed running
- * maximum + the step at which it was first reached (5 packed ops per slot and step, see PkState).
- * ===================================================================================================== */
-template <int C>
-struct BandStatePk {
-    uint32_t prev[C], prev2[C]; /* anti-diagonals a-1 and a-2, {A, B} */
-    uint32_t qch[C], rch[C];    /* query / reference characters in 16-bit lanes, {A, B} */
-    uint32_t rmax[C], rstep[C]; /* per slot: running maximum of the key (H << 16 | 0xFFFF - step) of pair A / of pair B */
-    uint32_t inBand[2][C];      /* ~0 / 0: is slot s inside the band on a step of parity p (s <= B-1-p)? */
-};
-
-__device__ __forceinline__ uint32_t pk_chars(const uint16_t both) { return __builtin_amdgcn_perm(0u, (uint32_t)both, 0x0c010c00u); } /* A<<8|B -> {A, B} */
-
-template <int C, bool P1, bool INTERIOR>
-__device__ __forceinline__ void band_step_pk(BandStatePk<C> &st, const int A, int &i0, int &j0, const int lane, const int m, const int n,
-                                             const int B, const uint32_t matchP, const uint32_t negDeltaP, const uint32_t gapP,
-                                             const uint16_t *qL, const uint16_t *rL, uint32_t *out) {
-    const int p = P1 ? 1 : 0;
-    if constexpr (P1) i0++; else j0++;
-    const int smin = INTERIOR ? 0 : max(max(1 - i0, j0 - n), 0);
-    const int smax = INTERIOR ? 0 : min(min(m - i0, j0 - 1), B - 1 - p);
-    uint32_t up[C], left[C];
-    if constexpr (P1) {
-        const uint32_t newq = pk_chars(INTERIOR ? qL[i0 + 64 * C - 2] : qL[min(max(i0 + 64 * C - 2, 0), m - 1)]);
-        const uint32_t tq = (uint32_t)wave_shl1((int)st.qch[0], (int)newq);
-#pragma unroll
-        for (int c = 0; c < C - 1; c++) st.qch[c] = st.qch[c + 1];
-        st.qch[C - 1] = tq;
-        const uint32_t nb = (uint32_t)wave_shl1((int)st.prev[0], 0);
-#pragma unroll
-        for (int c = 0; c < C; c++) { up[c] = st.prev[c]; left[c] = (c < C - 1) ? st.prev[c + 1] : nb; }
-    } else {
-        const uint32_t newr = pk_chars(INTERIOR ? rL[j0 - 1] : rL[min(max(j0 - 1, 0), n - 1)]);
-        const uint32_t tr = (uint32_t)wave_shr1((int)st.rch[C - 1], (int)newr);
-#pragma unroll
-        for (int c = C - 1; c > 0; c--) st.rch[c] = st.rch[c - 1];
-        st.rch[0] = tr;
-        const uint32_t nb = (uint32_t)wave_shr1((int)st.prev[C - 1], 0);
-#pragma unroll
-        for (int c = 0; c < C; c++) { left[c] = st.prev[c]; up[c] = (c > 0) ? st.prev[c - 1] : nb; }
-    }
-    const uint32_t onesP = 0x00010001u;
-    const uint32_t negA = 0xFFFFu - (uint32_t)A;
-#pragma unroll
-    for (int c = 0; c < C; c++) {
-        const uint32_t differs = dpx::pk_min_u16_raw(st.qch[c] ^ st.rch[c], onesP);
-        const s16x2 sc = as_s16x2(dpx::pk_mad_i16_raw(differs, negDeltaP, matchP));
-        uint32_t h = as_u32(dpx::pk_max(pk_gap_sat(up[c], left[c], gapP), (s16x2)(as_s16x2(st.prev2[c]) + sc))); /* gap <= 0 (host): gapP = |gap| */
-        if constexpr (INTERIOR) {
-            h &= st.inBand[P1 ? 1 : 0][c];
-        } else {
-            const int s = lane * C + c;
-            h = ((s >= smin) && (s <= smax)) ? h : 0u;
-        }
-        st.rmax[c] = max(st.rmax[c], (h & 0xFFFF0000u) | negA);  /* (score, earliest step) keys as in k_banded_fill, one per half */
-        st.rstep[c] = max(st.rstep[c], (h << 16) | negA);
-        st.prev2[c] = st.prev[c];
-        st.prev[c] = h;
-        out[c] = h;
-    }
-}
-
-template <int C, bool PB>
-__global__ void __launch_bounds__(DPX_FILL_THREADS) k_banded_fill_pk(const dpx_fill_args a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int G = (C >= 8) ? 1 : 8 / C;
-    constexpr int GG = (G < 2) ? 2 : G;
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int cpl = blockIdx.x * (int)a.wavesPerBlock + wv; /* couple index */
-    if (cpl >= a.numPairs) return;
-    const int pA = a.order[2 * cpl], pB = a.order[2 * cpl + 1];
-    const dpx_pair_dev prA = a.pairs[pA], prB = a.pairs[pB];
-    const int n = prA.n, m = prA.m, B = a.band; /* host guarantees equal shapes, both > 0 */
-    const uint32_t matchP = ((uint32_t)(uint16_t)a.match << 16) | (uint16_t)a.match;
-    const uint32_t negDeltaP = ((uint32_t)(uint16_t)(a.mismatch - a.match) << 16) | (uint16_t)(a.mismatch - a.match);
-    const uint32_t gapP = ((uint32_t)(uint16_t)(-a.gapOpen) << 16) | (uint16_t)(-a.gapOpen); /* |gap| (gap <= 0, checked by the host): pk_gap_sat */
-    const unsigned char *refA = reinterpret_cast<const unsigned char *>(a.seq + prA.refIdx), *refB = reinterpret_cast<const unsigned char *>(a.seq + prB.refIdx);
-    const unsigned char *qryA = reinterpret_cast<const unsigned char *>(a.seq + prA.qryIdx), *qryB = reinterpret_cast<const unsigned char *>(a.seq + prB.qryIdx);
-    unsigned char *my = smem + (size_t)wv * a.ldsPerWave;
-    uint16_t *qL = reinterpret_cast<uint16_t *>(my);               /* entry i: query A char << 8 | query B char */
-    uint16_t *rL = reinterpret_cast<uint16_t *>(my + a.ldsRefOff); /* entry j: reference A char << 8 | reference B char */
-    auto stage2 = [&](uint16_t *dst, const unsigned char *sa, const unsigned char *sb, const int len) {
-        for (int x = 4 * lane; x < len; x += 256) { /* four entries per lane and trip (see k_linear_fill_pk) */
-            const uint32_t a4 = load4(sa + x), b4 = load4(sb + x);
-            uint2 w;
-            w.x = __builtin_amdgcn_perm(a4, b4, 0x05010400u);
-            w.y = __builtin_amdgcn_perm(a4, b4, 0x07030602u);
-            *reinterpret_cast<uint2 *>(dst + x) = w;
-        }
-    };
-    stage2(qL, qryA, qryB, m);
-    stage2(rL, refA, refB, n);
-
-    BandStatePk<C> st;
-    {
-        const int p1 = B & 1;
-        const int i0 = (1 + p1 - (B - 1)) >> 1;
-        const int j0 = 1 - i0;
-#pragma unroll
-        for (int c = 0; c < C; c++) {
-            const int s = lane * C + c;
-            st.qch[c] = pk_chars(qL[min(max(i0 + s - 1, 0), m - 1)]);
-            st.rch[c] = pk_chars(rL[min(max(j0 - s - 1, 0), n - 1)]);
-            st.prev[c] = 0u; st.prev2[c] = 0u; st.rmax[c] = 0u; st.rstep[c] = 0u;
-            st.inBand[0][c] = (s <= B - 1) ? ~0u : 0u;
-            st.inBand[1][c] = (s <= B - 2) ? ~0u : 0u;
-        }
-    }
-    auto interior = [&](const int A) -> bool {
-        const int aa = A + 2, pp = (aa + B - 1) & 1;
-        const int i0 = (aa + pp - (B - 1)) >> 1, j0 = aa - i0, top = B - 1 - pp;
-        return i0 >= 1 && i0 + top <= m && j0 - top >= 1 && j0 <= n;
-    };
-    const int NS = m + n - 1;
-    const int numGroups = (NS + G - 1) / G;
-    int16_t *HpA = a.mat + prA.matOff + (size_t)lane * 8u, *HpB = a.mat + prB.matOff + (size_t)lane * 8u;
-    const size_t csA = prA.chunkStride, csB = prB.chunkStride;
-    uint32_t acc[8];
-    int i0 = (1 + (B & 1) - (B - 1)) >> 1;
-    int j0 = 1 - i0;
-    auto store_group = [&](const int grp) {
-        uint4 va, vb;
-        va.x = pk_hi16(acc[0], acc[1]); va.y = pk_hi16(acc[2], acc[3]); va.z = pk_hi16(acc[4], acc[5]); va.w = pk_hi16(acc[6], acc[7]);
-        vb.x = pack_lo16((int)acc[0], (int)acc[1]); vb.y = pack_lo16((int)acc[2], (int)acc[3]);
-        vb.z = pack_lo16((int)acc[4], (int)acc[5]); vb.w = pack_lo16((int)acc[6], (int)acc[7]);
-        *reinterpret_cast<uint4 *>(HpA + (size_t)grp * csA) = va;
-        *reinterpret_cast<uint4 *>(HpB + (size_t)grp * csB) = vb;
-    };
-#define DPX_BANDPK_BODY(INTERIOR_)                                                                                          \
-    _Pragma("unroll") for (int g = 0; g < GG; g += 2) {                                                                    \
-        band_step_pk<C, PB, INTERIOR_>(st, A0 + g, i0, j0, lane, m, n, B, matchP, negDeltaP, gapP, qL, rL, &acc[(g % G) * C]); \
-        if constexpr (G == 1) {                                                                                             \
-            if (INTERIOR_ || A0 + g < numGroups) store_group(A0 + g);                                                      \
-        }                                                                                                                   \
-        band_step_pk<C, !PB, INTERIOR_>(st, A0 + g + 1, i0, j0, lane, m, n, B, matchP, negDeltaP, gapP, qL, rL,             \
-                                        &acc[((g + 1) % G) * C]);                                                           \
-        if (((g + 1) % G) == G - 1) {                                                                                       \
-            const int grp = (A0 + g + 1) / G;                                                                               \
-            if (INTERIOR_ || grp < numGroups) store_group(grp);                                                            \
-        }                                                                                                                   \
-    }
-    int A0 = 0;
-    for (; A0 < NS && !(interior(A0) && interior(A0 + GG - 1)); A0 += GG) { DPX_BANDPK_BODY(false) }
-    for (; A0 + GG <= NS && interior(A0 + GG - 1); A0 += GG) { DPX_BANDPK_BODY(true) }
-    for (; A0 < NS; A0 += GG) { DPX_BANDPK_BODY(false) }
-#undef DPX_BANDPK_BODY
-    /* candidates per half: every slot's first maximum; rows / columns recovered from (step, slot) as in k_banded_fill */
-    unsigned long long mine[2] = {0ull, 0ull};
-#pragma unroll
-    for (int c = 0; c < C; c++) {
-#pragma unroll
-        for (int half = 0; half < 2; half++) {
-            const uint32_t key = half ? st.rstep[c] : st.rmax[c];
-            const int hv = (int)(key >> 16);
-            if (hv > 0) {
-                const int A = 0xFFFF - (int)(key & 0xFFFFu);
-                const int aa = A + 2;
-                const int pp = (aa + B - 1) & 1;
-                const int u = 2 * (lane * C + c) + pp;
-                const int i = (aa + u - (B - 1)) >> 1;
-                const int j = aa - i;
-                const unsigned long long k = ((unsigned long long)(unsigned)hv << 40) | ((unsigned long long)(0xFFFFFu - (unsigned)i) << 20) |
-                                             (unsigned long long)(0xFFFFFu - (unsigned)j);
-                mine[half] = k > mine[half] ? k : mine[half];
-            }
-        }
-    }
-    const unsigned long long topA = wave_max_u64(mine[0]), topB = wave_max_u64(mine[1]);
-    if (lane == 0) {
-        const int hA = (int)(topA >> 40), hB = (int)(topB >> 40);
-        a.score[pA] = hA;
-        a.endRow[pA] = hA > 0 ? (int)(0xFFFFFu - (unsigned)((topA >> 20) & 0xFFFFFu)) : 0;
-        a.endCol[pA] = hA > 0 ? (int)(0xFFFFFu - (unsigned)(topA & 0xFFFFFu)) : 0;
-        a.score[pB] = hB;
-        a.endRow[pB] = hB > 0 ? (int)(0xFFFFFu - (unsigned)((topB >> 20) & 0xFFFFFu)) : 0;
-        a.endCol[pB] = hB > 0 ? (int)(0xFFFFFu - (unsigned)(topB & 0xFFFFFu)) : 0;
-    }
-}
-
-/* =====================================================================================================
- * Export: un-tile one pair's plane into the reference's row-major (m+1) x (n+1) layout, borders included.
- * ===================================================================================================== */
-__global__ void k_export_matrix(const int16_t *mat, dpx_pair_dev pr, int algo, int R, int planes, int plane, int gapOpen,
-                                int gapExtend, int band, int16_t *out) {
-    const int n = pr.n, m = pr.m;
-    if (pr.rows) R = pr.rows;
-    const size_t total = (size_t)(m + 1) * (size_t)(n + 1);
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-        const int i = (int)(idx / (size_t)(n + 1));
-        const int j = (int)(idx % (size_t)(n + 1));
-        int v;
-        if (i == 0 || j == 0) {
-            const int len = i + j; /* one of them is 0 */
-            if (plane != 0) v = 0;                                   /* I / D are zero-initialised (ANW.cpp:24-27) */
-            else if (algo == DPX_K_LNW) v = len * gapOpen;           /* LNW.cpp:31-41 */
-            else if (algo == DPX_K_ANW) v = len == 0 ? 0 : gapOpen + len * gapExtend; /* ANW.cpp:43-53 */
-            else if (algo == DPX_K_ASG) v = i == 0 ? 0 : gapOpen + i * gapExtend; /* ASG: free row 0, ANW's column 0 */
-            else v = 0;                                              /* LSW / BSW / ASW */
-        } else if (algo == DPX_K_BSW) {
-            const int dlt = i - j;
-            v = (dlt <= band - 1 && -dlt <= band - 1) ? mat[pr.matOff + dpx_band_index(i, j, band, pr.chunkStride)] : 0;
-        } else {
-            v = mat[pr.matOff + dpx_cell_index(i, j, n, R, plane, planes, pr.chunkStride, pr.lanes)];
-        }
-        out[idx] = (int16_t)v;
-    }
-}
-
-/* =====================================================================================================
- * Device traceback (the reference's on-device backtracking(), cuda/LNW/
- * LinearNeedlemanWunschV19.cu:26-110, and host back-trackers c++/backtrack.cpp:21-356).
- * One lane per pair walks back from the end cell.  Directions are not stored: they are recomputed from the
- * int16 score matrices with the reference's own tie rules (a >= b wins for the FIRST argument of __vibmax):
- *   LSW (c++/LinearSmithWaterman.cpp:106-108): UPPER, then LEFT, then CORNER; stop when the next cell is 0 (:222)
- *   LNW (c++/LinearNeedlemanWunsch.cpp:122-125): INSERTION if left >= max(up, diag), else DELETION if up >= diag
- *   ANW (c++/AffineNeedlemanWunsch.cpp:185-233, :258-360): 3-state walk over H / I / D, GAP_OPEN wins ties
- * The three lines (reference / relation / query) are written right-aligned into the pair's buffer.
- * ===================================================================================================== */
-struct TbView {
-    const int16_t *mat;
-    uint64_t off;
-    uint32_t cs, lanes;
-    int n, m, R, planes, algo, band, gapOpen, gapExtend;
-    __device__ __forceinline__ int get(int i, int j, int plane) const {
-        if (i == 0 || j == 0) { /* closed-form borders, as in k_export_matrix */
-            const int len = i + j;
-            if (plane != 0) return 0;
-            if (algo == DPX_K_LNW) return len * gapOpen;
-            if (algo == DPX_K_ANW) return len == 0 ? 0 : gapOpen + len * gapExtend;
-            return 0;
-        }
-        if (algo == DPX_K_BSW) {
-            const int dlt = i - j;
-            if (dlt > band - 1 || -dlt > band - 1) return 0;
-            return mat[off + dpx_band_index(i, j, band, cs)];
-        }
-        return mat[off + dpx_cell_index(i, j, n, R, plane, planes, cs, lanes)];
-    }
-};
-
-/* A byte string read back to front through one register: four characters per aligned dword load (the walk reads
- * query[i-1] and reference[j-1] on every step; with ~100k lanes in flight neither L1 nor L2 keeps a sector between two
- * steps of the same lane, so every byte load was an HBM sector fetch -- profiles/README.md). */
-struct CharWin {
-    const unsigned char *s;
-    uintptr_t at = 1; /* address of the dword held in `w` (1 = none) */
-    uint32_t w = 0;
-    __device__ __forceinline__ int get(int x) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(s + x), al = a & ~(uintptr_t)3;
-        if (al != at) { at = al; w = *reinterpret_cast<const uint32_t *>(al); } /* never leaves the 256-byte aligned arena */
-        return (int)((w >> (8 * (int)(a & 3))) & 0xFFu);
-    }
-};
-
-/* The H plane seen through two registers-resident column vectors.  In the wavefront-tiled and the tile layout with R >= 8 the 8 rows
- * (i0 & ~7 .. +7) of one column are 16 contiguous, 16-byte aligned bytes: `cur` holds them for column j, `prev` for
- * column j-1.  A path step then needs at most ONE new 16-byte load (the next column on a left / diagonal move; two when
- * the walk climbs into the 8-row group above) instead of three 2-byte loads that each miss every cache. */
-struct TileWalker {
-    const int16_t *mat;
-    uint64_t off;
-    uint32_t cs, lanes;
-    int n, sr, border; /* sr = log2(rows per lane); border: value of H on row 0 / column 0 is border * (i + j) */
-    int i = 0, j = 0;
-    u32x4 cur, prev;
-
-    __device__ __forceinline__ u32x4 column(int i0, int jj) const { /* the 8-row group of row i0 (0-based), column jj >= 1 */
-        const int r = i0 & ((1 << sr) - 1), sub = r >> 3;
-        uint64_t T, tile;
-        if (lanes == 16) { /* tile layout: the column's 8 rows are one 16-byte piece of a line of the wave's stream (cs = first lane) */
-            return *reinterpret_cast<const u32x4 *>(mat + off + (dpx_wtile_index(i0 + 1, jj, 0, 1, 1 << sr, cs) & ~(uint64_t)7));
-        } else {
-            const int k = i0 >> (sr + 6), l = (i0 >> sr) & 63;
-            T = (uint64_t)k * (uint64_t)n + (uint64_t)(jj - 1) + (uint64_t)l;
-            tile = (uint64_t)(((sub << 6) + l) << 3);
-        }
-        return *reinterpret_cast<const u32x4 *>(mat + off + T * (uint64_t)cs + tile);
-    }
-    static __device__ __forceinline__ int elem(const u32x4 &v, int rr) { /* int16 number rr (0..7) of the vector */
-        const uint32_t d = rr < 4 ? (rr < 2 ? v.x : v.y) : (rr < 6 ? v.z : v.w);
-        return (int)(int16_t)(d >> (16 * (rr & 1)));
-    }
-    __device__ __forceinline__ void load_both() {
-        if (i >= 1 && j >= 1) cur = column(i - 1, j);
-        if (i >= 1 && j >= 2) prev = column(i - 1, j - 1);
-    }
-    __device__ __forceinline__ void start(int i_, int j_) { i = i_; j = j_; load_both(); }
-    /* a single cell outside the two cached columns' 8-row group (the row above the group): plain 2-byte load */
-    __device__ __forceinline__ int single(int ii, int jj) const {
-        if (ii == 0 || jj == 0) return border * (ii + jj);
-        return mat[off + dpx_cell_index(ii, jj, n, 1 << sr, 0, 1, cs, lanes)];
-    }
-    __device__ __forceinline__ int here() const { return (i == 0 || j == 0) ? border * (i + j) : elem(cur, (i - 1) & 7); }
-    __device__ __forceinline__ int up() const {
-        if (i <= 1 || j == 0) return border * (i - 1 + j);
-        const int rr = (i - 1) & 7;
-        return rr ? elem(cur, rr - 1) : single(i - 1, j);
-    }
-    __device__ __forceinline__ int left() const {
-        if (j <= 1 || i == 0) return border * (i + j - 1);
-        return elem(prev, (i - 1) & 7);
-    }
-    __device__ __forceinline__ int diag() const {
-        if (i <= 1 || j <= 1) return border * (i - 1 + j - 1);
-        const int rr = (i - 1) & 7;
-        return rr ? elem(prev, rr - 1) : single(i - 1, j - 1);
-    }
-    __device__ __forceinline__ void move(bool rowUp, bool colLeft) {
-        const bool newGroup = rowUp && (((i - 1) & 7) == 0); /* leaving the 8-row group through its top row */
-        i -= rowUp ? 1 : 0;
-        j -= colLeft ? 1 : 0;
-        if (i == 0 || j == 0) return; /* on the border: closed form from here on */
-        if (newGroup) {
-            load_both();
-        } else if (colLeft) {
-            cur = prev;
-            if (j >= 2) prev = column(i - 1, j - 1);
-        }
-    }
-};
-
-/* one lane walks one pair (MODE 1: k_asw_traceback, algo DPX_K_ASW, the ANW walk's local form; MODE 2: k_asg_traceback, algo DPX_K_ASG, the ANW
- * walk under ASG's borders, which stops on row 0) */
-template <int MODE>
-__device__ void tb_walk_lane(const dpx_fill_args &a, const int p, int algo, int R, int planes, int cachedWalk, const int32_t *endRow,
-                             const int32_t *endCol, const uint64_t *tbOff, char *tb, int32_t *tbLen) {
-    const dpx_pair_dev pr = a.pairs[p];
-    const int n = pr.n, m = pr.m;
-    const unsigned char *ref = reinterpret_cast<const unsigned char *>(a.seq + pr.refIdx);
-    const unsigned char *qry = reinterpret_cast<const unsigned char *>(a.seq + pr.qryIdx);
-    const int cap = (m + n + 1 + 3) & ~3; /* line capacity, dword-aligned like tbOff[] (see EMIT) */
-    char *lr = tb + tbOff[p], *lx = lr + cap, *lq = lx + cap;
-    int pos = cap; /* lines grow from the back */
-    uint32_t accR = 0, accX = 0, accQ = 0; /* the last <= 4 characters of each line, earliest in the highest byte */
-    const int match = a.match, mismatch = a.mismatch;
-    TbView v{a.mat, pr.matOff, pr.chunkStride, pr.lanes, n, m, pr.rows ? (int)pr.rows : R, planes, algo, a.band, a.gapOpen, a.gapExtend};
-    /* Characters are produced back to front; four of them are collected per line and written as one aligned dword
-     * (three scattered dword stores per four path steps instead of twelve byte stores). */
-#define EMIT(rc_, xc_, qc_)                                                                      \
-    {                                                                                            \
-        --pos;                                                                                   \
-        accR = (accR << 8) | (uint32_t)(unsigned char)(rc_);                                     \
-        accX = (accX << 8) | (uint32_t)(unsigned char)(xc_);                                     \
-        accQ = (accQ << 8) | (uint32_t)(unsigned char)(qc_);                                     \
-        if ((pos & 3) == 0) {                                                                    \
-            *reinterpret_cast<uint32_t *>(lr + pos) = accR;                                      \
-            *reinterpret_cast<uint32_t *>(lx + pos) = accX;                                      \
-            *reinterpret_cast<uint32_t *>(lq + pos) = accQ;                                      \
-        }                                                                                        \
-    }
-    int i = endRow[p], j = endCol[p];
-    CharWin qw{qry}, rw{ref};
-    /* register-cached columns: LSW / LNW on the wavefront-tiled or the tile layout with 8-row sub-tiles (rows per lane >= 8), for
-     * batches with enough lanes in flight that the walk is bound by sector requests (measured: 100k short pairs -25 %);
-     * smaller batches are bound by the latency of one dependent load per step instead, and there the plain
-     * three-loads-in-parallel step is the shorter chain (5000 x 1024^2: cached +40 %, 20k x 300^2: +10 %).  The host decides. */
-    const bool cached = (algo == DPX_K_LSW || algo == DPX_K_LNW) && v.R >= 8 && cachedWalk && pr.lanes != 32;
-    if (cached) {
-        const int g = a.gapOpen;
-        TileWalker w{a.mat, pr.matOff, pr.chunkStride, pr.lanes, n, dpx_log2(v.R), algo == DPX_K_LNW ? g : 0};
-        w.start(i, j);
-        if (algo == DPX_K_LSW) {
-            int h = (i > 0 && j > 0) ? w.here() : 0;
-            while (h > 0) {
-                const int up = w.up(), left = w.left();
-                if (up + g == h) { EMIT('_', ' ', qw.get(w.i - 1)); w.move(true, false); h = up; }
-                else if (left + g == h) { EMIT(rw.get(w.j - 1), ' ', '_'); w.move(false, true); h = left; }
-                else {
-                    const int dg = w.diag(), qc = qw.get(w.i - 1), rc = rw.get(w.j - 1);
-                    EMIT(rc, qc == rc ? '*' : '|', qc);
-                    w.move(true, true);
-                    h = dg;
-                }
-            }
-        } else {
-            while (w.i != 0 || w.j != 0) {
-                if (w.i == 0) { EMIT(rw.get(w.j - 1), ' ', '_'); w.move(false, true); continue; }  /* row-0 border: QUERY_INSERTION */
-                if (w.j == 0) { EMIT('_', ' ', qw.get(w.i - 1)); w.move(true, false); continue; }  /* column-0 border: QUERY_DELETION */
-                const int qc = qw.get(w.i - 1), rc = rw.get(w.j - 1);
-                const bool eq = qc == rc;
-                const int mm = w.diag() + (eq ? match : mismatch);
-                const int del = w.up() + g, ins = w.left() + g;
-                const int vmax = max(del, mm);
-                if (ins >= vmax) { EMIT(rc, ' ', '_'); w.move(false, true); }
-                else if (del >= mm) { EMIT('_', ' ', qc); w.move(true, false); }
-                else { EMIT(rc, eq ? '*' : '|', qc); w.move(true, true); }
-            }
-        }
-    } else if (algo == DPX_K_LSW || algo == DPX_K_BSW) {
-        const int g = a.gapOpen;
-        int h = (i > 0 && j > 0) ? v.get(i, j, 0) : 0;
-        while (h > 0) {
-            const int up = v.get(i - 1, j, 0), left = v.get(i, j - 1, 0), dg = v.get(i - 1, j - 1, 0);
-            if (up + g == h) { EMIT('_', ' ', qw.get(i - 1)); i--; h = up; }
-            else if (left + g == h) { EMIT(rw.get(j - 1), ' ', '_'); j--; h = left; }
-            else { const int qc = qw.get(i - 1), rc = rw.get(j - 1); EMIT(rc, qc == rc ? '*' : '|', qc); i--; j--; h = dg; }
-        }
-    } else if (algo == DPX_K_LNW) {
-        const int g = a.gapOpen;
-        while (i != 0 || j != 0) {
-            if (i == 0) { EMIT(rw.get(j - 1), ' ', '_'); j--; continue; }  /* row-0 border: QUERY_INSERTION */
-            if (j == 0) { EMIT('_', ' ', qw.get(i - 1)); i--; continue; }  /* column-0 border: QUERY_DELETION */
-            const int qc = qw.get(i - 1), rc = rw.get(j - 1);
-            const bool eq = qc == rc;
-            const int mm = v.get(i - 1, j - 1, 0) + (eq ? match : mismatch);
-            const int del = v.get(i - 1, j, 0) + g, ins = v.get(i, j - 1, 0) + g;
-            const int vmax = max(del, mm);
-            if (ins >= vmax) { EMIT(rc, ' ', '_'); j--; }
-            else if (del >= mm) { EMIT('_', ' ', qc); i--; }
-            else { EMIT(rc, eq ? '*' : '|', qc); i--; j--; }
-        }
-    } else { /* ANW; ASW (k_asw_traceback): the same walk, which stops where H = 0 and has no end gaps; ASG (k_asg_traceback): no row-0 tail */
-        const int o = a.gapOpen, e = a.gapExtend;
-        int cur = 0; /* 0 SCORING, 1 INSERTION, 2 DELETION */
-        while (i != 0 && j != 0) {
-            if (cur == 0) {
-                if constexpr (MODE == 1) {
-                    if (v.get(i, j, 0) <= 0) break;
-                }
-                const bool eq = qw.get(i - 1) == rw.get(j - 1);
-                int dg;
-                if constexpr (MODE == 2) dg = i == 1 ? 0 : (j == 1 ? o + (i - 1) * e : v.get(i - 1, j - 1, 0)); /* ASG's borders (the only border cell this walk reads) */
-                else dg = v.get(i - 1, j - 1, 0);
-                const int mm = dg + (eq ? match : mismatch);
-                const int D = v.get(i, j, 2), I = v.get(i, j, 1);
-                const int vmax = max(D, mm);
-                if (I >= vmax) cur = 1;
-                else if (D >= mm) cur = 2;
-                else { EMIT(rw.get(j - 1), eq ? '*' : '|', qw.get(i - 1)); i--; j--; }
-            } else if (cur == 1) {
-                const bool open = (j == 1) || (v.get(i, j - 1, 0) + o + e >= v.get(i, j - 1, 1) + e);
-                if (open) cur = 0;
-                EMIT(rw.get(j - 1), ' ', '_'); j--;
-            } else {
-                const bool open = (i == 1) || (v.get(i - 1, j, 0) + o + e >= v.get(i - 1, j, 2) + e);
-                if (open) cur = 0;
-                EMIT('_', ' ', qw.get(i - 1)); i--;
-            }
-        }
-        if constexpr (MODE != 1) {
-            while (i > 0) { EMIT('_', ' ', qw.get(i - 1)); i--; }
-            if constexpr (MODE == 0) {
-                while (j > 0) { EMIT(rw.get(j - 1), ' ', '_'); j--; }
-            }
-        }
-    }
-#undef EMIT
-    if (pos & 3) { /* the 1-3 newest characters have not filled a dword: the newest sits in the lowest byte, at `pos` */
-        const int left = 4 - (pos & 3);
-        for (int t = 0; t < left; t++) {
-            lr[pos + t] = (char)(accR >> (8 * t)); lx[pos + t] = (char)(accX >> (8 * t)); lq[pos + t] = (char)(accQ >> (8 * t));
-        }
-    }
-    tbLen[p] = cap - pos;
-}
-
-__global__ void k_traceback(const dpx_fill_args a, int numPairs, int algo, int R, int planes, int cachedWalk, const int32_t *endRow,
-                            const int32_t *endCol, const uint64_t *tbOff, char *tb, int32_t *tbLen) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= numPairs) return;
-    tb_walk_lane<0>(a, p, algo, R, planes, cachedWalk, endRow, endCol, tbOff, tb, tbLen);
-}
-
-__global__ void k_asw_traceback(const dpx_fill_args a, int numPairs, int R, int planes, const int32_t *endRow, const int32_t *endCol,
-                                const uint64_t *tbOff, char *tb, int32_t *tbLen) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= numPairs) return;
-    tb_walk_lane<1>(a, p, DPX_K_ASW, R, planes, 0, endRow, endCol, tbOff, tb, tbLen);
-}
-
-__global__ void k_asg_traceback(const dpx_fill_args a, int numPairs, int R, int planes, const int32_t *endRow, const int32_t *endCol,
-                                const uint64_t *tbOff, char *tb, int32_t *tbLen) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= numPairs) return;
-    tb_walk_lane<2>(a, p, DPX_K_ASG, R, planes, 0, endRow, endCol, tbOff, tb, tbLen);
-}
-
-/* -----------------------------------------------------------------------------------------------------
- * Wave-cooperative traceback (LSW / LNW / ANW / banded SW, every matrix layout of the fill kernels).
- * The lane-per-pair walk above pays one dependent HBM round trip per path step (1100 of them on a 1024 x 1024 pair).  Here
- * one WAVE owns a pair: lane c fetches column cLo + c of a window of the matrix around the walker -- 64 rows (ANW: 48 rows of
- * every plane) x 64 columns, the 8 rows of a row group with one 16-byte load (layouts with fewer than 8 rows per lane: 8- or
- * 4-byte pieces) -- into LDS (one 144-byte line per column and plane, borders included as ordinary cells), and the walk runs
- * until it leaves the window through its top or its left edge: one HBM round trip per ~64 steps of a diagonal path.
- * Round 4: the walk takes RUNS, not steps.  Round 3 walked on the scalar unit, one cell per trip: an LDS round trip for three
- * scores and two characters, five v_readfirstlane and the branches on them -- about 340 issue cycles per path step, and the
- * traceback of a batch cost as much as its fill (10 000 pairs of 1024 x 1024: 4.4 ms against 3.2 ms).  Which way the path leaves a
- * cell depends on that cell's neighbourhood only, so the 64 lanes each decide ONE cell of the line the path would follow next --
- * lane l the cell of the walker's diagonal in column l; in ANW's gap states the cells of the walker's row (INSERTION) or column
- * (DELETION) -- from four LDS reads at their own address, and a ballot gives the number of steps the path really follows that
- * line: the length of the run of "diagonal" decisions below the walker's lane (LSW: up / left / diagonal / stop at H = 0; LNW:
- * INSERTION over DELETION over diagonal, borders included; ANW: the SCORING state's choice, "the gap was opened here" for the two
- * gap states, c++/backtrack.cpp:214-356).  The lanes of the run store their own three characters.  Alignments worth computing
- * are mostly long diagonal runs: a 1024 x 1024 pair of the benchmark is ~90 trips instead of ~2050 -- ~50 since a trip also takes the
- * step that ENDS its run (the lane below the run has decided that cell in the same pass: a diagonal run and the single gap step
- * after it are one trip).  Measured per wave (s_memrealtime around the phases, 1024 x 1024 LSW): 19 windows of ~1.3 us load latency
- * on an idle chip (4 us with 1700 waves loading at once: ~200 distinct lines per wave and window against the CUs' miss queues) and
- * ~50 trips of 0.43 us; the batch's kernel time is its SLOWEST pair -- the benchmark's 1 % unrelated pairs, whose alignments under
- * +3 / -1 / -2 are 300 short runs: 0.19-0.25 ms against 0.06-0.13 for the others.  A prefetch of the next window along the diagonal
- * was built and measured (19 of 21 windows adopted): no gain with 1700 waves in flight (the loads are queued, not late), removed.
- * Banded SW (round 4, BAND): the same walk with LSW's rule; the window is gathered from the anti-diagonal-major band layout with
- * 2-byte loads (issue<3, .>), cells outside the band are 0.  4000 pairs of 4096 x 4096, band 128: 1.7 ms per batch of 1712 against
- * 10 ms for one lane per pair.
- * ----------------------------------------------------------------------------------------------------- */
-template <int PLANES> struct TbWin {
-    static constexpr int G = PLANES == 3 ? 6 : 8;      /* row groups of a window */
-    static constexpr int WR = 8 * G;                   /* rows R0+1 .. R0+WR; columns cLo .. cLo+63, one per lane */
-    static constexpr int CS = WR + 8;                  /* int16 elements between two columns in LDS: 16-byte aligned lines, banks spread */
-    static constexpr int kBytes = PLANES * 64 * CS * 2;
-};
-size_t dpx_traceback_wave_lds(int planes) { return planes == 3 ? (size_t)TbWin<3>::kBytes : (size_t)TbWin<1>::kBytes; }
-
-/* the 8 rows 8*grp+1 .. 8*grp+8 of column jc (>= 1) of `plane`, whatever the layout: one 16-byte piece where a lane owns >= 8 rows
- * (wavefront-tiled with 8-row sub-tiles, tile layout), otherwise the pieces of 8 / Rr neighbouring lanes (they sit in different chunks) */
-__device__ __forceinline__ u32x4 tb_load_group8(const int16_t *base, const dpx_pair_dev &pr, const int Rr, const int planes, const int plane,
-                                                const int grp, const int jc, const int n) {
-    const int i1 = grp * 8 + 1;
-    if (Rr >= 8) return *reinterpret_cast<const u32x4 *>(base + dpx_cell_index(i1, jc, n, Rr, plane, planes, pr.chunkStride, pr.lanes));
-    if (Rr == 4) {
-        const uint2 lo = *reinterpret_cast<const uint2 *>(base + dpx_cell_index(i1, jc, n, 4, plane, planes, pr.chunkStride, pr.lanes));
-        const uint2 hi = *reinterpret_cast<const uint2 *>(base + dpx_cell_index(i1 + 4, jc, n, 4, plane, planes, pr.chunkStride, pr.lanes));
-        return u32x4{lo.x, lo.y, hi.x, hi.y};
-    }
-    u32x4 v;
-    v.x = *reinterpret_cast<const uint32_t *>(base + dpx_cell_index(i1, jc, n, 2, plane, planes, pr.chunkStride, pr.lanes));
-    v.y = *reinterpret_cast<const uint32_t *>(base + dpx_cell_index(i1 + 2, jc, n, 2, plane, planes, pr.chunkStride, pr.lanes));
-    v.z = *reinterpret_cast<const uint32_t *>(base + dpx_cell_index(i1 + 4, jc, n, 2, plane, planes, pr.chunkStride, pr.lanes));
-    v.w = *reinterpret_cast<const uint32_t *>(base + dpx_cell_index(i1 + 6, jc, n, 2, plane, planes, pr.chunkStride, pr.lanes));
-    return v;
-}
-
-template <int PLANES, bool BAND, int ALGO>
-__global__ void __launch_bounds__(64) k_traceback_wave(const dpx_fill_args a, int numPairs, int R, const int32_t *endRow,
-                                                       const int32_t *endCol, const uint64_t *tbOff, char *tb, int32_t *tbLen) {
-    using W = TbWin<PLANES>;
-    /* BAND: a banded SW matrix (anti-diagonal-major band layout, dpx_band_index) walked by LSW's rule; cells outside the band read 0
-     * (TbView::get, c++/BandedSmithWaterman.cpp's back-tracker sees the zero-initialised matrix there) */
-    constexpr int algo = BAND ? DPX_K_LSW : ALGO; /* (compile-time: the walk of one algorithm carries no branches for the others) */
-    constexpr int G = W::G, WR = W::WR, CS = W::CS;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smemTb[];
-    int16_t *win = reinterpret_cast<int16_t *>(smemTb); /* win[(plane * 64 + (jj - cLo)) * CS + (ii - R0 - 1)] = plane[ii][jj] */
-    const int p = blockIdx.x;
-    const int lane = threadIdx.x;
-    if (p >= numPairs) return;
-    const dpx_pair_dev pr = a.pairs[p];
-    const int n = pr.n, m = pr.m;
-    const int Rr = pr.rows ? (int)pr.rows : R;
-    /* (the host launches this kernel for LSW / LNW / banded SW with one plane and ANW / ASW / ASG with three; rows per lane are
-     * 2, 4, 8 or 16 in every full-matrix layout; empty sequences walk along a border or not at all) */
-    const unsigned char *ref = reinterpret_cast<const unsigned char *>(a.seq + pr.refIdx);
-    const unsigned char *qry = reinterpret_cast<const unsigned char *>(a.seq + pr.qryIdx);
-    const int16_t *base = a.mat + pr.matOff;
-    const int cap = (m + n + 1 + 3) & ~3;
-    char *lr = tb + tbOff[p], *lx = lr + cap, *lq = lx + cap;
-    int pos = cap;
-    const int match = a.match, mismatch = a.mismatch, g = a.gapOpen, ext = a.gapExtend;
-    /* H on row 0 / column 0, `len` cells from the corner (TbView::get): LNW len * gap, ANW open + len * extend (0 in the corner), LSW / ASW 0 */
-    auto bval = [&](const int len) -> int { return algo == DPX_K_LNW ? len * g : ((algo == DPX_K_ANW || algo == DPX_K_ASG) ? (len ? g + len * ext : 0) : 0); };
-    auto bvalRow = [&](const int len) -> int { return algo == DPX_K_ASG ? 0 : bval(len); }; /* ASG: row 0 is free, column 0 is ANW's */
-    /* where the 16-byte piece (8 rows of a row group, one column) lies: shifts only for the two layouts whose lanes own >= 8 rows */
-    const int Q = Rr >> 3, lgQ = Q == 2 ? 1 : 0;
-    const int kind = Rr >= 8 ? (pr.lanes == 64 ? 0 : pr.lanes == 16 ? 1 : 2) : 2;
-    const uint32_t cs = pr.chunkStride; /* (tile layout: the pair's first lane) */
-    const int swBand = a.band, bandSc = BAND ? dpx_log2(dpx_band_cpl(a.band)) : 0; /* banded SW: band width, log2(cells per lane) */
-    /* where the 16-byte piece (rows 8*grp+1 .. +8 of column jc, plane pl) lies, for the two layouts whose lanes own >= 8 rows */
-    auto piece_at = [&](auto kindC, const int pl, const int grp, const int jc) -> const int16_t * {
-        if constexpr (decltype(kindC)::value == 0) { /* wavefront-tiled (dpx_tiled_index + dpx_tile_off) */
-            const int l = (grp >> lgQ) & 63, kk = grp >> (lgQ + 6), sub = grp & (Q - 1);
-            const size_t T = (size_t)kk * (size_t)n + (size_t)(jc - 1) + (size_t)l;
-            return base + T * cs + (size_t)(((((pl << lgQ) + sub) << 6) + l) << 3);
-        } else { /* tile layout of the lane-packed kernels (dpx_wtile_index) */
-            const int l = grp >> lgQ, h = grp & (Q - 1), lam = (int)cs + l, skew = l + ((int)cs & 7), j0 = jc - 1;
-            const size_t t = (size_t)(((j0 >> 3) + 1) * 8 + skew - 1);
-            return base + t * (size_t)(PLANES * Q * 512) + (size_t)((((pl << lgQ) + h) << 9) + ((lam >> 3) << 6) + ((j0 & 7) << 3));
-        }
-    };
-    int i = __builtin_amdgcn_readfirstlane(endRow[p]), j = __builtin_amdgcn_readfirstlane(endCol[p]);
-    int R0 = 1 << 28, cLo = 1 << 28;
-    int diag0 = 0;        /* LSW / LNW: i - j of the cell the window was anchored on */
-    bool banded = false;  /* ... and whether only the band around that diagonal was fetched */
-    bool wantFull = false; /* the walk left the last band sideways (a long gap): fetch whole columns next time */
-    uint32_t chR = 0u, chQ = 0u; /* reference character of this lane's column; query character of window row `lane` */
-    /* window with (ii, jj) in its bottom-right corner region */
-    /* Window with (ii, jj) in its bottom-right corner region.  Only a BAND of it is fetched unless the walk left the last one sideways
-     * -- the three row groups of every column (and plane) around the diagonal through the anchor (rows d-8 .. d+7 at least, d = the
-     * diagonal's row in that column).  The walk follows that diagonal or leaves it by a few gap steps; need_window() re-anchors when it
-     * is more than 7 rows above / 6 below.  In the wavefront-tiled layouts every column's piece lies in its own 64-byte sector, so 3
-     * instead of 8 pieces per column are 3/8 of the traffic and of the requests (the traceback of 10 000 pairs of 1024 x 1024 read
-     * ~5 GB for paths that touch ~0.3 GB).
-     * fill_window<KIND, CNT>: the loads of one layout (0 wavefront-tiled, 1 tile layout, 2 any layout through dpx_cell_index, 3 band
-     * layout) and one group count, straight-line -- round 4 found a window's loads spending ~3000 cycles in the nest of uniform
-     * branches that one loop over "whatever layout, however many groups" compiled to (a taken branch is a fetch bubble).  Cells
-     * without storage (rows past m, columns outside 1..n, outside the band) load the pool's first bytes instead of branching and are
-     * masked to 0 afterwards. */
-    constexpr int GL = 3; /* row groups of a banded column */
-    /* issue<KIND, CNT>: the loads of a window -- CNT row groups from group gBase + gFirst (per lane) of column jc, the query characters of
-     * rows r0 + 1 + lane and the reference character of the column -- into `raw`, nothing else: no value is touched, so every load of the window is
-     * in flight before the wave waits for the first. */
-    auto issue = [&](auto kindC, auto cntC, auto &raw, uint32_t &rawQ, uint32_t &rawR, const int gBase, const int gFirst, const int jc, const int r0) {
-        constexpr int KIND = decltype(kindC)::value, CNT = decltype(cntC)::value;
-        if constexpr (KIND == 3) {
-            /* Band layout (dpx_band_index, its shifts hoisted): the rows of a column lie on consecutive anti-diagonals -- 2-byte loads,
-             * 24 per lane in a banded window (neighbouring columns and rows share 64-byte sectors: ~60 distinct ones for the wave). */
-            const int sg = 3 - bandSc;
-#pragma unroll
-            for (int gi = 0; gi < CNT; gi++) {
-#pragma unroll
-                for (int e = 0; e < 8; e++) {
-                    const int ii2 = (gBase + gFirst + gi) * 8 + 1 + e, dlt = ii2 - jc, A = ii2 + jc - 2, sl = (dlt + swBand - 1) >> 1;
-                    const bool ok = ii2 >= 1 && ii2 <= m && jc >= 1 && jc <= n && dlt < swBand && -dlt < swBand;
-                    const size_t off = (size_t)(A >> sg) * cs + (size_t)(((sl >> bandSc) << 3) + ((A & ((1 << sg) - 1)) << bandSc) + (sl & ((1 << bandSc) - 1)));
-                    const int16_t *at = ok ? base + off : a.mat;
-                    raw[gi * 8 + e] = (uint32_t)*reinterpret_cast<const uint16_t *>(at);
-                }
-            }
-        } else {
-#pragma unroll
-            for (int pl = 0; pl < PLANES; pl++) {
-#pragma unroll
-                for (int gi = 0; gi < CNT; gi++) {
-                    const int grp = gBase + gFirst + gi;
-                    const bool ok = grp >= 0 && grp * 8 < m && jc >= 1 && jc <= n;
-                    u32x4 x;
-                    if constexpr (KIND == 2) {
-                        x = u32x4{0u, 0u, 0u, 0u};
-                        if (ok) x = tb_load_group8(base, pr, Rr, PLANES, pl, grp, jc, n);
-                    } else {
-                        const int16_t *at = ok ? piece_at(kindC, pl, grp, jc) : a.mat;
-                        x = *reinterpret_cast<const u32x4 *>(at);
-                    }
-                    const int k = (pl * CNT + gi) * 4;
-                    raw[k] = x.x; raw[k + 1] = x.y; raw[k + 2] = x.z; raw[k + 3] = x.w;
-                }
-            }
-        }
-        const int qi = r0 + lane;
-        const unsigned char *atQ = (lane < WR && qi >= 0 && qi < m) ? qry + qi : reinterpret_cast<const unsigned char *>(a.seq);
-        const unsigned char *atR = (jc >= 1 && jc <= n) ? ref + (jc - 1) : reinterpret_cast<const unsigned char *>(a.seq);
-        rawQ = *atQ;
-        rawR = *atR;
-    };
-    /* commit<KIND, CNT>: what issue() loaded becomes the window in LDS -- cells without storage masked to 0, the borders of H added as
-     * ordinary cells -- and the lane's two characters */
-    auto commit = [&](auto kindC, auto cntC, const auto &raw, const uint32_t rawQ, const uint32_t rawR, const int gBase, const int gFirst, const int jc, const int r0) {
-        constexpr int KIND = decltype(kindC)::value, CNT = decltype(cntC)::value;
-        u32x4 v[PLANES][CNT];
-        if constexpr (KIND == 3) {
-#pragma unroll
-            for (int gi = 0; gi < CNT; gi++) {
-                uint32_t d[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-                for (int e = 0; e < 8; e++) {
-                    const int ii2 = (gBase + gFirst + gi) * 8 + 1 + e, dlt = ii2 - jc;
-                    const bool ok = ii2 >= 1 && ii2 <= m && jc >= 1 && jc <= n && dlt < swBand && -dlt < swBand;
-                    d[e >> 1] |= (ok ? raw[gi * 8 + e] : 0u) << ((e & 1) * 16);
-                }
-                v[0][gi] = u32x4{d[0], d[1], d[2], d[3]};
-            }
-        } else {
-#pragma unroll
-            for (int pl = 0; pl < PLANES; pl++) {
-#pragma unroll
-                for (int gi = 0; gi < CNT; gi++) {
-                    const int grp = gBase + gFirst + gi, k = (pl * CNT + gi) * 4;
-                    const bool ok = grp >= 0 && grp * 8 < m && jc >= 1 && jc <= n;
-                    v[pl][gi] = ok ? u32x4{raw[k], raw[k + 1], raw[k + 2], raw[k + 3]} : u32x4{0u, 0u, 0u, 0u};
-                }
-            }
-        }
-        { const int qi = r0 + lane; chQ = (lane < WR && qi >= 0 && qi < m) ? rawQ : 0u; } /* query character of row r0 + 1 + lane */
-        chR = (jc >= 1 && jc <= n) ? rawR : 0u;
-        if (algo != DPX_K_LSW && algo != DPX_K_ASW) { /* the borders of H as cells: column 0 and row 0 (LSW / ASW: zeros, as loaded) */
-#pragma unroll
-            for (int gi = 0; gi < CNT; gi++) {
-                const int grp = gBase + gFirst + gi;
-                if (jc == 0 || grp < 0) {
-                    uint32_t d[4];
-#pragma unroll
-                    for (int e = 0; e < 8; e += 2) {
-                        const int r0b = grp * 8 + 1 + e, r1b = r0b + 1;
-                        const int v0 = jc == 0 ? (r0b >= 0 ? bval(r0b) : 0) : (r0b == 0 && jc > 0 ? bvalRow(jc) : 0);
-                        const int v1 = jc == 0 ? (r1b >= 0 ? bval(r1b) : 0) : (r1b == 0 && jc > 0 ? bvalRow(jc) : 0);
-                        d[e >> 1] = ((uint32_t)(uint16_t)v1 << 16) | (uint32_t)(uint16_t)v0;
-                    }
-                    v[0][gi] = u32x4{d[0], d[1], d[2], d[3]};
-                }
-            }
-        }
-#pragma unroll
-        for (int pl = 0; pl < PLANES; pl++)
-#pragma unroll
-            for (int gi = 0; gi < CNT; gi++) *reinterpret_cast<u32x4 *>(win + (pl * 64 + lane) * CS + (gFirst + gi) * 8) = v[pl][gi];
-    };
-    /* first fetched row group (relative to the window's first) of this lane's column in a banded window whose last column holds the
-     * diagonal's row iiDiag */
-    auto band_first = [&](const int iiDiag, const int r0) -> int {
-        const int dl = (iiDiag - r0 - 1) - 63 + lane;
-        return min(max((dl - 8) >> 3, 0), G - GL);
-    };
-    constexpr int kRawFull = BAND ? G * 8 : PLANES * G * 4, kRawBand = BAND ? GL * 8 : PLANES * GL * 4;
-    using std::integral_constant;
-    auto load_window = [&](const int ii, const int jj) {
-        const int gBase = ((ii - 1) >> 3) - (G - 1);
-        R0 = gBase * 8;
-        cLo = jj - 63;
-        const int jc = cLo + lane;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local"); /* the previous window's reads are done before it is overwritten (LDS only: the walk's byte stores are not waited for) */
-        __builtin_amdgcn_wave_barrier();
-        diag0 = ii - jj;
-        banded = !wantFull;
-        const int gFirst = banded ? band_first(ii, R0) : 0;
-        uint32_t rq, rr;
-        auto both = [&](auto kindC, auto cntC, auto &raw) {
-            issue(kindC, cntC, raw, rq, rr, gBase, gFirst, jc, R0);
-            commit(kindC, cntC, raw, rq, rr, gBase, gFirst, jc, R0);
-        };
-        if (banded) {
-            uint32_t raw[kRawBand];
-            if constexpr (BAND) both(integral_constant<int, 3>{}, integral_constant<int, GL>{}, raw);
-            else if (kind == 0) both(integral_constant<int, 0>{}, integral_constant<int, GL>{}, raw);
-            else if (kind == 1) both(integral_constant<int, 1>{}, integral_constant<int, GL>{}, raw);
-            else both(integral_constant<int, 2>{}, integral_constant<int, GL>{}, raw);
-        } else {
-            uint32_t raw[kRawFull];
-            if constexpr (BAND) both(integral_constant<int, 3>{}, integral_constant<int, G>{}, raw);
-            else if (kind == 0) both(integral_constant<int, 0>{}, integral_constant<int, G>{}, raw);
-            else if (kind == 1) both(integral_constant<int, 1>{}, integral_constant<int, G>{}, raw);
-            else both(integral_constant<int, 2>{}, integral_constant<int, G>{}, raw);
-        }
-        /* the two characters are needed HERE: without this the compiler waits for them (s_waitcnt vmcnt(0)) where the walk first uses them --
-         * in every trip of the loop, where the wait also covers the byte stores of the previous trips (3 us per trip, measured) */
-        asm volatile("" : "+v"(chQ), "+v"(chR));
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-    };
-    /* rows i-1, i and columns j-1, j must lie inside the window (borders are cells of it) */
-    auto need_window = [&]() -> bool {
-        if (i - 1 <= R0 || i > R0 + WR || j - 1 < cLo || j > cLo + 63) return true;
-        if (banded) { const int dev = (i - j) - diag0; if (dev < -7 || dev > 6) { wantFull = true; return true; } } /* outside the fetched band */
-        return false;
-    };
-    auto cell = [&](const int pl, const int col, const int row) -> int { return (int)win[(pl * 64 + col) * CS + row]; };
-    /* number of lanes that continue a run which starts at lane `from` and goes DOWN the lanes while `on` holds (lane 0 is never on) */
-    auto run_down = [&](const bool on, const int from) -> int {
-        const unsigned long long inv = ~__builtin_amdgcn_ballot_w64(on) << (63 - from);
-        return inv ? __builtin_clzll(inv) : 64;
-    };
-    /* Decision of window cell (rq, cq) (>= 1 each: callers clamp), rc = the reference character of its column: 0 diagonal, 1 up, 2 left,
-     * 3 stop / other (ANW: the SCORING state's 1 = to INSERTION, 2 = to DELETION).  qcOut = the query character of its row. */
-    auto decide_cell = [&](const int rq, const int cq, const uint32_t rc, int &qcOut) -> uint32_t {
-        const int qc = __builtin_amdgcn_ds_bpermute(rq << 2, (int)chQ);
-        qcOut = qc;
-        const int ii = R0 + 1 + rq, jc = cLo + cq;
-        uint32_t d;
-        if constexpr (PLANES == 1) {
-            const int h = cell(0, cq, rq), up = cell(0, cq, rq - 1), left = cell(0, cq - 1, rq);
-            if (algo == DPX_K_LSW) {
-                d = h <= 0 ? 3u : (up + g == h ? 1u : (left + g == h ? 2u : 0u)); /* UPPER, LEFT, CORNER; stop at 0 (c++/backtrack.cpp:21-97) */
-            } else {
-                const int dg = cell(0, cq - 1, rq - 1);
-                const int mm = dg + ((uint32_t)qc == rc ? match : mismatch);
-                const int del = up + g, ins = left + g;
-                d = ins >= max(del, mm) ? 2u : (del >= mm ? 1u : 0u); /* INSERTION over DELETION over the diagonal */
-                if (ii == 0) d = 2u;       /* row 0: QUERY_INSERTION to the corner */
-                else if (jc == 0) d = 1u;  /* column 0: QUERY_DELETION */
-            }
-        } else {
-            const int dg = cell(0, cq - 1, rq - 1), I = cell(1, cq, rq), D = cell(2, cq, rq);
-            const int mm = dg + ((uint32_t)qc == rc ? match : mismatch);
-            d = I >= max(D, mm) ? 1u : (D >= mm ? 2u : 0u);
-            if (algo == DPX_K_ASW && cell(0, cq, rq) <= 0) d = 3u; /* ASW: H = 0, the local alignment starts here */
-            if (ii <= 0 || jc <= 0) d = 3u;
-        }
-        return d;
-    };
-    /* (r, c) = the walker's window cell; lane l decides the cell of the walker's diagonal in its own column (3 outside the usable part) */
-    auto decide_diag = [&](const int r, const int c, int &qcOut) -> uint32_t {
-        const int rr = r - (c - lane);
-        const bool usable = lane <= c && lane >= 1 && rr >= 1;
-        const uint32_t d = decide_cell(usable ? rr : 1, usable ? lane : 1, chR, qcOut); /* (clamped: every lane reads inside the window) */
-        return usable ? d : 3u;
-    };
-    /* LSW / LNW gaps in runs as well (round 4: the end gaps of a global alignment of short reads are 30 steps along one row): the cells to the
-     * left of the walker on its row (lane l: column l) or above it in its column (lane k: k rows up) that decide like it.  In a banded
-     * window a run ends where it leaves the fetched band (`dev` = the walker's distance from the anchor's diagonal). */
-    auto left_run = [&](const int r, const int c, const int dev) -> int {
-        int qc;
-        const bool usable = lane <= c && lane >= 1 && (!banded || dev + (c - lane) <= 6);
-        const uint32_t d = decide_cell(r, usable ? lane : 1, chR, qc);
-        return run_down(usable && d == 2u, c);
-    };
-    auto up_run = [&](const int r, const int c, const int dev) -> int {
-        int qc;
-        const bool usable = r - lane >= 1 && (!banded || dev - lane >= -7);
-        const uint32_t d = decide_cell(usable ? r - lane : 1, c, (uint32_t)__builtin_amdgcn_readlane((int)chR, c), qc);
-        const unsigned long long ends = __builtin_amdgcn_ballot_w64(!(usable && d == 1u));
-        return ends ? __builtin_ctzll(ends) : 64;
-    };
-    /* the lanes c, c-1, ... c-len+1 store the characters of a diagonal run (their own column's reference character, their row's query character) */
-    auto emit_diag = [&](const int c, const int len, const int qc) {
-        const int k = c - lane;
-        if (k >= 0 && k < len) {
-            const int at = pos - 1 - k;
-            lr[at] = (char)chR; lx[at] = ((uint32_t)qc == chR) ? '*' : '|'; lq[at] = (char)qc;
-        }
-        pos -= len;
-    };
-    /* `len` steps to the left from column c: the lanes store their reference characters against gaps */
-    auto emit_left = [&](const int c, const int len) {
-        const int k = c - lane;
-        if (k >= 0 && k < len) { const int at = pos - 1 - k; lr[at] = (char)chR; lx[at] = ' '; lq[at] = '_'; }
-        pos -= len;
-    };
-    /* `len` steps up from row r: lane k stores the query character of row r - k */
-    auto emit_up = [&](const int r, const int len) {
-        const int qc = __builtin_amdgcn_ds_bpermute(max(r - lane, 0) << 2, (int)chQ);
-        if (lane < len) { const int at = pos - 1 - lane; lr[at] = '_'; lx[at] = ' '; lq[at] = (char)qc; }
-        pos -= len;
-    };
-    int cur = 0; /* ANW: 0 SCORING, 1 INSERTION, 2 DELETION */
-    for (;;) {
-        if ((algo == DPX_K_LSW || algo == DPX_K_ASW) ? !(i > 0 && j > 0) : (algo == DPX_K_ASG ? i == 0 : !(i != 0 || j != 0))) break; /* (ASG: row 0 ends the walk) */
-        if (need_window()) { load_window(max(i, 1), max(j, 1)); wantFull = false; } /* (a window anchored on row 1 / column 1 also serves row 0 / column 0) */
-        const int r = i - R0 - 1, c = j - cLo;
-        if constexpr (PLANES == 1) {
-            if (algo != DPX_K_LSW && (i == 0 || j == 0)) { /* LNW on a border: to the corner in runs (row 0: QUERY_INSERTION, column 0: QUERY_DELETION) */
-                if (i == 0) { const int len = min(j, c); emit_left(c, len); j -= len; }
-                else { const int len = min(i, r); emit_up(r, len); i -= len; }
-                continue;
-            }
-            int qc;
-            const uint32_t d = decide_diag(r, c, qc);
-            const int run = run_down(d == 0u, c);
-            if (run) {
-                /* ... and the step that ends the run with it: the lane below the run has decided that cell already (paths of related
-                 * sequences are diagonal runs separated by single gap steps: half the trips) */
-                emit_diag(c, run, qc); i -= run; j -= run;
-                const int cx = c - run, rx = r - run;
-                if (cx >= 1 && rx >= 1 && i > 0 && j > 0) {
-                    const uint32_t dx = (uint32_t)__builtin_amdgcn_readlane((int)d, cx);
-                    if (dx == 1u) { emit_up(rx, 1); i--; }
-                    else if (dx == 2u) { emit_left(cx, 1); j--; }
-                    else if (algo == DPX_K_LSW) break; /* H = 0: the local alignment starts here */
-                }
-                continue;
-            }
-            const uint32_t dc = (uint32_t)__builtin_amdgcn_readlane((int)d, c);
-            if (algo == DPX_K_LSW && dc == 3u) break;
-            const int dev = (i - j) - diag0;
-            if (dc == 1u) { const int len = max(up_run(r, c, dev), 1); emit_up(r, len); i -= len; }
-            else { const int len = max(left_run(r, c, dev), 1); emit_left(c, len); j -= len; }
-        } else {
-            if (i == 0 || j == 0) { /* along a border to the corner: first up column 0, then left along row 0 (c++/backtrack.cpp:214-356) */
-                if (i > 0) { const int len = min(i, r); emit_up(r, len); i -= len; }   /* (rows r, r-1, ... 1 of the window hold query rows) */
-                else { const int len = min(j, c); emit_left(c, len); j -= len; }
-                continue;
-            }
-            if (cur == 0) {
-                int qc;
-                const uint32_t d = decide_diag(r, c, qc);
-                const int run = run_down(d == 0u, c);
-                if (run) {
-                    emit_diag(c, run, qc); i -= run; j -= run;
-                    const int cx = c - run, rx = r - run; /* the cell that ends the run has been decided with it */
-                    if (cx >= 1 && rx >= 1 && i > 0 && j > 0) {
-                        const int dx = __builtin_amdgcn_readlane((int)d, cx);
-                        if (dx == 1 || dx == 2) cur = dx;
-                        else if (algo == DPX_K_ASW) break; /* H = 0 */
-                    }
-                    continue;
-                }
-                cur = __builtin_amdgcn_readlane((int)d, c); /* 1: to INSERTION, 2: to DELETION */
-                if (algo == DPX_K_ASW && cur == 3) break;    /* (ASW: 3 = H is 0 here) */
-            } else if (cur == 1) {
-                /* INSERTION: steps to the left along row r until (and including) the cell where the gap was opened; lane l decides the cell in column l */
-                const int cq = max(lane, 1), jc = cLo + cq;
-                const bool opened = jc == 1 || cell(0, cq - 1, r) + g + ext >= cell(1, cq - 1, r) + ext;
-                const bool usable = lane <= c && lane >= 1 && jc >= 1 && (!banded || (i - j) - diag0 + (c - lane) <= 6); /* (column l-1, row r inside the band) */
-                const int cont = run_down(usable && !opened, c);          /* cells the gap passes through */
-                const bool stops = c - cont >= 1 && cLo + c - cont >= 1 && (!banded || (i - j) - diag0 + cont <= 6); /* ... and then a usable cell that opened it (else: the window's / band's edge) */
-                const int len = cont + (stops ? 1 : 0);
-                emit_left(c, len); j -= len;
-                if (stops) cur = 0;
-            } else {
-                /* DELETION: steps up along column c; lane k decides the cell k rows above the walker */
-                const int rq = max(r - lane, 1), ii = R0 + 1 + rq;
-                const bool opened = ii == 1 || cell(0, c, rq - 1) + g + ext >= cell(2, c, rq - 1) + ext;
-                const bool usable = r - lane >= 1 && ii >= 1 && (!banded || (i - j) - diag0 - lane >= -7); /* (column c, row r-k-1 inside the band) */
-                const unsigned long long m64 = __builtin_amdgcn_ballot_w64(!(usable && !opened)); /* first lane that ends the run: opened, or not usable */
-                const int cont = m64 ? __builtin_ctzll(m64) : 64;
-                const bool stops = r - cont >= 1 && R0 + 1 + r - cont >= 1 && (!banded || (i - j) - diag0 - cont >= -7);
-                const int len = cont + (stops ? 1 : 0);
-                emit_up(r, len); i -= len;
-                if (stops) cur = 0;
-            }
-        }
-    }
-    if (lane == 0) tbLen[p] = cap - pos;
-}
-
-/* =====================================================================================================
- * Output path: packed, variable-length result text built on the device -- the reference's V15 idea
- * (cuda/LNW/LinearNeedlemanWunschV15.cu:168-172,372-425: per-pair string lengths, prefix offsets, one packed buffer, one
- * D2H of the real bytes) taken one step further: the device writes each pair's block exactly as c++/main.cpp prints it,
- *     "<pair number> | <score>\n<reference line>\n<relation line>\n<query line>\n"
- * (three empty lines for a zero-score local alignment, c++/LinearSmithWaterman.cpp:253-257), so the host's share of the
- * output is one fwrite per batch.  Three small kernels after k_traceback: block lengths, an exclusive scan, the copy.
- * ===================================================================================================== */
-__device__ __forceinline__ int dec_digits(unsigned long long v) {
-    int d = 1;
-    while (v >= 10ull) { v /= 10ull; d++; }
-    return d;
-}
-__device__ __forceinline__ unsigned long long block_len(unsigned long long number, int score, int len) {
-    const unsigned us = score < 0 ? 0u - (unsigned)score : (unsigned)score;
-    return (unsigned long long)(dec_digits(number) + 3 + (score < 0 ? 1 : 0) + dec_digits(us) + 1) + 3ull * (unsigned long long)(len + 1);
-}
-
-constexpr int kScanThreads = 256, kScanPerThread = 8, kScanTile = kScanThreads * kScanPerThread;
-
-/* inclusive scan of one value per thread across the workgroup; returns the exclusive prefix, *total = sum over the group */
-__device__ __forceinline__ unsigned long long group_exclusive(unsigned long long v, unsigned long long *lds, unsigned long long *total) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    unsigned long long x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned long long o = __shfl_up(x, off, 64);
-        if (lane >= off) x += o;
-    }
-    if (lane == 63) lds[wv] = x;
-    __syncthreads();
-    unsigned long long base = 0, all = 0;
-    for (int k = 0; k < kScanThreads / 64; k++) { const unsigned long long w = lds[k]; if (k < wv) base += w; all += w; }
-    __syncthreads();
-    *total = all;
-    return base + x - v;
-}
-
-/* phase 1: per-tile totals of the block lengths; phase 3 (FINAL): per-pair offsets = tile base + exclusive prefix */
-template <bool FINAL>
-__global__ void __launch_bounds__(kScanThreads) k_out_scan(const int32_t *score, const int32_t *tbLen, int numPairs, unsigned long long firstNumber,
-                                                           unsigned long long *tileSums, unsigned long long *outOff) {
-    __shared__ unsigned long long lds[kScanThreads / 64];
-    const size_t base = (size_t)blockIdx.x * kScanTile + (size_t)threadIdx.x * kScanPerThread;
-    unsigned long long v[kScanPerThread], mine = 0;
-#pragma unroll
-    for (int k = 0; k < kScanPerThread; k++) {
-        const size_t p = base + k;
-        v[k] = p < (size_t)numPairs ? block_len(firstNumber + p, score[p], tbLen[p]) : 0ull;
-        mine += v[k];
-    }
-    unsigned long long total;
-    unsigned long long ex = group_exclusive(mine, lds, &total);
-    if constexpr (!FINAL) {
-        if (threadIdx.x == 0) tileSums[blockIdx.x] = total;
-    } else {
-        ex += tileSums[blockIdx.x]; /* exclusive prefix of the tiles, from k_out_scan_tiles */
-#pragma unroll
-        for (int k = 0; k < kScanPerThread; k++) {
-            const size_t p = base + k;
-            if (p < (size_t)numPairs) outOff[p] = ex;
-            ex += v[k];
-        }
-        if (blockIdx.x == gridDim.x - 1 && threadIdx.x == kScanThreads - 1) outOff[numPairs] = ex; /* total bytes */
-    }
-}
-
-/* phase 2: exclusive scan of the tile totals, in place (one workgroup; numTiles is small: pairs / 2048) */
-__global__ void __launch_bounds__(kScanThreads) k_out_scan_tiles(unsigned long long *tileSums, int numTiles) {
-    __shared__ unsigned long long lds[kScanThreads / 64];
-    unsigned long long carry = 0;
-    for (int t0 = 0; t0 < numTiles; t0 += kScanThreads) {
-        const int t = t0 + (int)threadIdx.x;
-        const unsigned long long v = t < numTiles ? tileSums[t] : 0ull;
-        unsigned long long total;
-        const unsigned long long ex = group_exclusive(v, lds, &total);
-        if (t < numTiles) tileSums[t] = carry + ex;
-        carry += total;
-    }
-}
-
-/* one pair's block, written by one wave: header by lane 0, the three right-aligned lines of k_traceback copied 64 bytes per instruction */
-__device__ __forceinline__ void out_write_block(const dpx_pair_dev *pairs, const int32_t *score, const int32_t *tbLen, const uint64_t *tbOff,
-                                                const char *tb, const int p, const int lane, const unsigned long long firstNumber,
-                                                const unsigned long long dstOff, char *out) {
-    const int len = tbLen[p], sc = score[p];
-    const int cap = (pairs[p].m + pairs[p].n + 1 + 3) & ~3; /* line capacity, as in k_traceback */
-    char *dst = out + dstOff;
-    const unsigned long long number = firstNumber + (unsigned long long)p;
-    const unsigned us = sc < 0 ? 0u - (unsigned)sc : (unsigned)sc;
-    const int dn = dec_digits(number), ds = dec_digits(us), neg = sc < 0 ? 1 : 0;
-    const int hdr = dn + 3 + neg + ds + 1;
-    if (lane == 0) {
-        unsigned long long v = number;
-        for (int k = dn - 1; k >= 0; k--) { dst[k] = (char)('0' + (int)(v % 10ull)); v /= 10ull; }
-        dst[dn] = ' '; dst[dn + 1] = '|'; dst[dn + 2] = ' ';
-        if (neg) dst[dn + 3] = '-';
-        unsigned u = us;
-        for (int k = ds - 1; k >= 0; k--) { dst[dn + 3 + neg + k] = (char)('0' + (int)(u % 10u)); u /= 10u; }
-        dst[hdr - 1] = '\n';
-    }
-    const char *src = tb + tbOff[p] + (cap - len);
-#pragma unroll
-    for (int line = 0; line < 3; line++) {
-        const char *s = src + (size_t)line * cap;
-        char *d = dst + hdr + (size_t)line * (len + 1);
-        for (int x = lane; x < len; x += 64) d[x] = s[x];
-        if (lane == 0) d[len] = '\n';
-    }
-}
-
-__global__ void __launch_bounds__(256) k_out_compact(const dpx_pair_dev *pairs, const int32_t *score, const int32_t *tbLen, const uint64_t *tbOff,
-                                                      const char *tb, int numPairs, unsigned long long firstNumber,
-                                                      const unsigned long long *outOff, char *out) {
-    const int lane = threadIdx.x & 63;
-    const int p = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
-    if (p >= numPairs) return;
-    out_write_block(pairs, score, tbLen, tbOff, tb, p, lane, firstNumber, outOff[p], out);
-}
-
-/* Small batches (up to kOutSmallPairs pairs: the class-per-pair drivers send 20 per device round trip): lengths, scan and copy in ONE
- * workgroup -- one launch instead of four in a chain of dependent kernels whose launches are most of the round trip. */
-constexpr int kOutSmallPairs = 256;
-static_assert(kOutSmallPairs <= kScanThreads, "one pair per thread");
-__global__ void __launch_bounds__(kScanThreads) k_out_small(const dpx_pair_dev *pairs, const int32_t *score, const int32_t *tbLen, const uint64_t *tbOff,
-                                                            const char *tb, int numPairs, unsigned long long firstNumber, unsigned long long *outOff,
-                                                            char *out) {
-    __shared__ unsigned long long lds[kScanThreads / 64];
-    __shared__ unsigned long long offs[kOutSmallPairs];
-    const int p = (int)threadIdx.x; /* one pair per thread (kScanThreads >= kOutSmallPairs) */
-    const unsigned long long mine = p < numPairs ? block_len(firstNumber + (unsigned long long)p, score[p], tbLen[p]) : 0ull;
-    unsigned long long total;
-    const unsigned long long ex = group_exclusive(mine, lds, &total);
-    if (p < numPairs) { outOff[p] = ex; offs[p] = ex; }
-    if (p == 0) outOff[numPairs] = total;
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    for (int q = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); q < numPairs; q += kScanThreads / 64)
-        out_write_block(pairs, score, tbLen, tbOff, tb, q, lane, firstNumber, offs[q], out);
-}
-
-/* =====================================================================================================
- * 2-bit packed input (dpx_batch_create_packed2; the input side of c++/parseInput.cpp:78-112): the host sends four bases
- * per byte (base k in bits 2*(k%4) of byte k/4) and a 4-entry alphabet; one thread expands one dword = 16 bases into the 16 bytes
- * of the byte buffer that every fill, traceback and output kernel reads (one aligned 16-byte store).  The fills keep matching
- * plain bytes (the reference's contract: any alphabet), so a packed batch and a byte batch are the same batch after this kernel.
- * ===================================================================================================== */
-__global__ void __launch_bounds__(256) k_unpack2(const uint32_t *packed, const uint32_t alphabet, uint4 *out, const size_t numDwords) {
-    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
-    if (i >= numDwords) return;
-    const uint32_t w = packed[i];
-    uint32_t o[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) { /* eight bits of w = four bases = one output dword: v_perm_b32 picks alphabet bytes by selector */
-        const uint32_t c = (w >> (8 * k)) & 0xFFu;
-        const uint32_t sel = (c & 3u) | (((c >> 2) & 3u) << 8) | (((c >> 4) & 3u) << 16) | ((c >> 6) << 24);
-        o[k] = __builtin_amdgcn_perm(0u, alphabet, sel);
-    }
-    out[i] = make_uint4(o[0], o[1], o[2], o[3]);
-}
-
-/* =====================================================================================================
- * DPX primitive probe (dpx_prim_eval): runs the CDNA4 mappings of dpx_prims.hpp on the device.
- * ===================================================================================================== */
-__global__ void k_prim_eval(const int32_t *op, const uint32_t *a, const uint32_t *b, const uint32_t *c, size_t count,
-                            uint32_t *res, uint32_t *pred) {
-    const size_t x = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (x >= count) return;
-    const uint32_t A = a[x], B = b[x], C = c[x];
-    const int sa = (int)A, sb = (int)B, sc = (int)C;
-    bool p = false, ph = false, pl = false;
-    uint32_t r = 0;
-    switch (op[x]) {
-    case 0: r = (uint32_t)dpx::vimax3_s32(sa, sb, sc); break;
-    case 1: r = dpx::vimax3_s16x2(A, B, C); break;
-    case 2: r = dpx::vimax3_u32(A, B, C); break;
-    case 3: r = dpx::vimax3_u16x2(A, B, C); break;
-    case 4: r = (uint32_t)dpx::vimin3_s32(sa, sb, sc); break;
-    case 5: r = dpx::vimin3_s16x2(A, B, C); break;
-    case 6: r = dpx::vimin3_u32(A, B, C); break;
-    case 7: r = dpx::vimin3_u16x2(A, B, C); break;
-    case 8: r = (uint32_t)dpx::vimax_s32_relu(sa, sb); break;
-    case 9: r = dpx::vimax_s16x2_relu(A, B); break;
-    case 10: r = (uint32_t)dpx::vimin_s32_relu(sa, sb); break;
-    case 11: r = dpx::vimin_s16x2_relu(A, B); break;
-    case 12: r = (uint32_t)dpx::vimax3_s32_relu(sa, sb, sc); break;
-    case 13: r = dpx::vimax3_s16x2_relu(A, B, C); break;
-    case 14: r = (uint32_t)dpx::vimin3_s32_relu(sa, sb, sc); break;
-    case 15: r = dpx::vimin3_s16x2_relu(A, B, C); break;
-    case 16: r = (uint32_t)dpx::vibmax_s32(sa, sb, &p); break;
-    case 17: r = dpx::vibmax_u32(A, B, &p); break;
-    case 18: r = (uint32_t)dpx::vibmin_s32(sa, sb, &p); break;
-    case 19: r = dpx::vibmin_u32(A, B, &p); break;
-    case 20: r = dpx::vibmax_s16x2(A, B, &ph, &pl); break;
-    case 21: r = dpx::vibmax_u16x2(A, B, &ph, &pl); break;
-    case 22: r = dpx::vibmin_s16x2(A, B, &ph, &pl); break;
-    case 23: r = dpx::vibmin_u16x2(A, B, &ph, &pl); break;
-    case 24: r = (uint32_t)dpx::viaddmax_s32(sa, sb, sc); break;
-    case 25: r = dpx::viaddmax_u32(A, B, C); break;
-    case 26: r = dpx::viaddmax_s16x2(A, B, C); break;
-    case 27: r = dpx::viaddmax_u16x2(A, B, C); break;
-    case 28: r = (uint32_t)dpx::viaddmin_s32(sa, sb, sc); break;
-    case 29: r = dpx::viaddmin_u32(A, B, C); break;
-    case 30: r = dpx::viaddmin_s16x2(A, B, C); break;
-    case 31: r = dpx::viaddmin_u16x2(A, B, C); break;
-    case 32: r = (uint32_t)dpx::viaddmax_s32_relu(sa, sb, sc); break;
-    case 33: r = dpx::viaddmax_s16x2_relu(A, B, C); break;
-    case 34: r = (uint32_t)dpx::viaddmin_s32_relu(sa, sb, sc); break;
-    case 35: r = dpx::viaddmin_s16x2_relu(A, B, C); break;
-    default: break;
-    }
-    res[x] = r;
-    const int o = op[x];
-    pred[x] = (o >= 20 && o <= 23) ? (uint32_t)((ph ? 2 : 0) | (pl ? 1 : 0)) : (uint32_t)(p ? 1 : 0);
-}
-
-template <class K>
-hipError_t launch_fill_kernel(K kernel, const dpx_fill_args &a, dim3 grid, size_t lds, hipStream_t s) {
-    if (lds > 64u * 1024u) { /* opt in to more than the default 64 KiB of dynamic LDS (160 KiB per CU on gfx950) */
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    /* workgroups of a.wavesPerBlock independent waves (4, or 1 for small launches: see dpx_fill_waves_per_block); `lds` is the request of a
-     * four-wave workgroup */
-    const unsigned wpb = a.wavesPerBlock;
-    hipLaunchKernelGGL(kernel, grid, dim3(64u * wpb), lds / 4u * wpb, s, a);
-    return hipGetLastError();
-}
-
-template <int R>
-hipError_t launch_linear_R(const dpx_fill_args &a, bool local, bool store, dim3 grid, size_t lds, hipStream_t s) {
-    if (local) return store ? launch_fill_kernel(k_linear_fill<R, true, true>, a, grid, lds, s)
-                            : launch_fill_kernel(k_linear_fill<R, true, false>, a, grid, lds, s);
-    return store ? launch_fill_kernel(k_linear_fill<R, false, true>, a, grid, lds, s)
-                 : launch_fill_kernel(k_linear_fill<R, false, false>, a, grid, lds, s);
-}
-
-template <int R>
-hipError_t launch_linear_pk_R(const dpx_fill_args &a, bool local, dim3 grid, size_t lds, hipStream_t s) {
-    if (!local) return launch_fill_kernel(k_linear_fill_pk<R, false, false>, a, grid, lds, s);
-    return a.rowTags ? launch_fill_kernel(k_linear_fill_pk<R, true, true>, a, grid, lds, s)
-                     : launch_fill_kernel(k_linear_fill_pk<R, true, false>, a, grid, lds, s);
-}
-
-template <int C>
-hipError_t launch_banded_C(const dpx_fill_args &a, bool store, dim3 grid, size_t lds, hipStream_t s) {
-    const bool pb = ((a.band + 1) & 1) != 0; /* parity of step A = 0 */
-    if (pb) return store ? launch_fill_kernel(k_banded_fill<C, true, true>, a, grid, lds, s)
-                         : launch_fill_kernel(k_banded_fill<C, true, false>, a, grid, lds, s);
-    return store ? launch_fill_kernel(k_banded_fill<C, false, true>, a, grid, lds, s)
-                 : launch_fill_kernel(k_banded_fill<C, false, false>, a, grid, lds, s);
-}
-
-template <int R>
-hipError_t launch_affine_R(const dpx_fill_args &a, bool store, dim3 grid, size_t lds, hipStream_t s) {
-    return store ? launch_fill_kernel(k_affine_fill<R, true>, a, grid, lds, s)
-                 : launch_fill_kernel(k_affine_fill<R, false>, a, grid, lds, s);
-}
-
-template <int R>
-hipError_t launch_asw_R(const dpx_fill_args &a, bool store, dim3 grid, size_t lds, hipStream_t s) {
-    return store ? launch_fill_kernel(k_asw_fill<R, true>, a, grid, lds, s)
-                 : launch_fill_kernel(k_asw_fill<R, false>, a, grid, lds, s);
-}
-
-template <int R>
-hipError_t launch_asg_R(const dpx_fill_args &a, bool store, dim3 grid, size_t lds, hipStream_t s) {
-    return store ? launch_fill_kernel(k_asg_fill<R, true>, a, grid, lds, s)
-                 : launch_fill_kernel(k_asg_fill<R, false>, a, grid, lds, s);
-}
-
 } // namespace
 
-/* ---- host-callable launchers (used by dpx_capi.cpp) ---- */
+/* ---- host-callable launchers (used by dpx_capi.cpp); dpx_device.hpp has launch_fill, launch_lds and the dispatchers ---- */
 
 hipError_t dpx_launch_fill(const dpx_fill_args &a, int algo, int R, bool store, size_t ldsBytes, hipStream_t stream) {
     if (a.numPairs <= 0) return hipSuccess;
-    const int wavesPerBlock = (int)a.wavesPerBlock;
-    dim3 grid((unsigned)((a.numPairs + wavesPerBlock - 1) / wavesPerBlock));
-    if (algo == DPX_K_LNW || algo == DPX_K_LSW) {
-        const bool local = algo == DPX_K_LSW;
-        switch (R) {
-        case 2: return launch_linear_R<2>(a, local, store, grid, ldsBytes, stream);
-        case 4: return launch_linear_R<4>(a, local, store, grid, ldsBytes, stream);
-        case 8: return launch_linear_R<8>(a, local, store, grid, ldsBytes, stream);
-        case 16: return launch_linear_R<16>(a, local, store, grid, ldsBytes, stream);
-        default: return hipErrorInvalidValue;
-        }
-    }
-    if (algo == DPX_K_BSW) { /* here R carries the cells-per-lane count C = dpx_band_cpl(band) */
-        switch (R) {
-        case 1: return launch_banded_C<1>(a, store, grid, ldsBytes, stream);
-        case 2: return launch_banded_C<2>(a, store, grid, ldsBytes, stream);
-        case 4: return launch_banded_C<4>(a, store, grid, ldsBytes, stream);
-        case 8: return launch_banded_C<8>(a, store, grid, ldsBytes, stream);
-        default: return hipErrorInvalidValue;
-        }
-    }
-    if (algo == DPX_K_ANW) {
-        switch (R) {
-        case 2: return launch_affine_R<2>(a, store, grid, ldsBytes, stream);
-        case 4: return launch_affine_R<4>(a, store, grid, ldsBytes, stream);
-        case 8: return launch_affine_R<8>(a, store, grid, ldsBytes, stream);
-        default: return hipErrorInvalidValue;
-        }
-    }
-    if (algo == DPX_K_ASW) {
-        switch (R) {
-        case 2: return launch_asw_R<2>(a, store, grid, ldsBytes, stream);
-        case 4: return launch_asw_R<4>(a, store, grid, ldsBytes, stream);
-        case 8: return launch_asw_R<8>(a, store, grid, ldsBytes, stream);
-        default: return hipErrorInvalidValue;
-        }
-    }
-    if (algo == DPX_K_ASG) {
-        switch (R) {
-        case 2: return launch_asg_R<2>(a, store, grid, ldsBytes, stream);
-        case 4: return launch_asg_R<4>(a, store, grid, ldsBytes, stream);
-        case 8: return launch_asg_R<8>(a, store, grid, ldsBytes, stream);
-        default: return hipErrorInvalidValue;
-        }
-    }
-    return hipErrorInvalidValue;
+    if (algo == DPX_K_BSW) return dpx_launch_bsw_fill(a, R, store, ldsBytes, stream); /* here R carries the cells-per-lane count C = dpx_band_cpl(band) */
+    if (algo == DPX_K_ANW || algo == DPX_K_ASW || algo == DPX_K_ASG) return dpx_launch_affine_fill(a, algo, R, store, ldsBytes, stream);
+    if (algo != DPX_K_LNW && algo != DPX_K_LSW) return hipErrorInvalidValue;
+    return dispatch_int<2, 4, 8, 16>(R, [&](auto r) {
+        return dispatch_bool(algo == DPX_K_LSW, [&](auto local) {
+            return dispatch_bool(store, [&](auto st) {
+                return launch_fill(k_linear_fill<decltype(r)::value, decltype(local)::value, decltype(st)::value>, a, a, ldsBytes, stream);
+            });
+        });
+    });
 }
 
 /* lane-packed kernels (short / medium queries): a.waves = one descriptor per wave, a.numPairs = number of waves.
  * ldsBytes is per workgroup: (dpx_lanes_stage_bytes() + reference area) x waves per workgroup (4 for the linear kernels,
  * 1 for the affine one). */
-
-template <class K>
-static hipError_t launch_lanes_kernel(K kernel, const dpx_fill_args &a, dim3 grid, int threads, size_t lds, hipStream_t s) {
-    if (lds > 64u * 1024u) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, s, a);
-    return hipGetLastError();
-}
-
 hipError_t dpx_launch_fill_lanes(const dpx_fill_args &a, int algo, int R, bool store, size_t ldsBytes, hipStream_t stream) {
     if (a.numPairs <= 0) return hipSuccess;
-    const int wpb = (algo == DPX_K_ANW || algo == DPX_K_ASW || algo == DPX_K_ASG) ? DPX_ALANES_THREADS / 64 : (int)a.wavesPerBlock; /* (ldsBytes = per wave x this) */
-    dim3 grid((unsigned)((a.numPairs + wpb - 1) / wpb));
-    if (algo == DPX_K_ANW) {
-        const int th = DPX_ALANES_THREADS;
-        if (R == 8) return store ? launch_lanes_kernel(k_affine_lanes<8, true>, a, grid, th, ldsBytes, stream)
-                                 : launch_lanes_kernel(k_affine_lanes<8, false>, a, grid, th, ldsBytes, stream);
-        return hipErrorInvalidValue;
-    }
-    if (algo == DPX_K_ASW) {
-        const int th = DPX_ALANES_THREADS;
-        if (R == 8) return store ? launch_lanes_kernel(k_asw_lanes<8, true>, a, grid, th, ldsBytes, stream)
-                                 : launch_lanes_kernel(k_asw_lanes<8, false>, a, grid, th, ldsBytes, stream);
-        return hipErrorInvalidValue;
-    }
-    if (algo == DPX_K_ASG) {
-        const int th = DPX_ALANES_THREADS;
-        if (R == 8) return store ? launch_lanes_kernel(k_asg_lanes<8, true>, a, grid, th, ldsBytes, stream)
-                                 : launch_lanes_kernel(k_asg_lanes<8, false>, a, grid, th, ldsBytes, stream);
-        return hipErrorInvalidValue;
-    }
-    const bool local = algo == DPX_K_LSW;
-    const int th = 64 * wpb;
-#define DPX_LANES_CASE(R_)                                                                                              \
-    case R_:                                                                                                           \
-        if (local) return store ? launch_lanes_kernel(k_linear_lanes<R_, true, true>, a, grid, th, ldsBytes, stream)    \
-                                : launch_lanes_kernel(k_linear_lanes<R_, true, false>, a, grid, th, ldsBytes, stream);  \
-        return store ? launch_lanes_kernel(k_linear_lanes<R_, false, true>, a, grid, th, ldsBytes, stream)              \
-                     : launch_lanes_kernel(k_linear_lanes<R_, false, false>, a, grid, th, ldsBytes, stream);
-    switch (R) {
-        DPX_LANES_CASE(8)
-        DPX_LANES_CASE(16)
-    default: return hipErrorInvalidValue;
-    }
-#undef DPX_LANES_CASE
+    if (algo == DPX_K_ANW || algo == DPX_K_ASW || algo == DPX_K_ASG) return dpx_launch_affine_lanes(a, algo, R, store, ldsBytes, stream);
+    const int wpb = (int)a.wavesPerBlock;
+    const dim3 grid((unsigned)((a.numPairs + wpb - 1) / wpb));
+    return dispatch_int<8, 16>(R, [&](auto r) {
+        return dispatch_bool(algo == DPX_K_LSW, [&](auto local) {
+            return dispatch_bool(store, [&](auto st) {
+                return launch_lds(k_linear_lanes<decltype(r)::value, decltype(local)::value, decltype(st)::value>, grid, dim3(64 * wpb), ldsBytes, stream, a);
+            });
+        });
+    });
 }
 
 /* packed lane kernel (16 rows per lane, two row blocks of one pair in the two halves): a.waves / a.numPairs as dpx_launch_fill_lanes */
 hipError_t dpx_launch_fill_lanes_packed(const dpx_fill_args &a, int algo, size_t ldsBytes, hipStream_t stream) {
     if (a.numPairs <= 0) return hipSuccess;
     const int wpb = (int)a.wavesPerBlock;
-    dim3 grid((unsigned)((a.numPairs + wpb - 1) / wpb));
-    return algo == DPX_K_LSW ? launch_lanes_kernel(k_linear_lanes_pk<true>, a, grid, 64 * wpb, ldsBytes, stream)
-                             : launch_lanes_kernel(k_linear_lanes_pk<false>, a, grid, 64 * wpb, ldsBytes, stream);
+    const dim3 grid((unsigned)((a.numPairs + wpb - 1) / wpb));
+    return dispatch_bool(algo == DPX_K_LSW, [&](auto local) {
+        return launch_lds(k_linear_lanes_pk<decltype(local)::value>, grid, dim3(64 * wpb), ldsBytes, stream, a);
+    });
 }
 
 /* split kernel (small batches): one workgroup of `waves` waves per pair, a.numPairs workgroups */
 hipError_t dpx_launch_fill_split(const dpx_fill_args &a, int algo, int R, int waves, size_t ldsBytes, hipStream_t stream) {
     if (a.numPairs <= 0) return hipSuccess;
     if (waves < 1 || waves > DPX_SPLIT_MAX_WAVES) return hipErrorInvalidValue;
-    const bool local = algo == DPX_K_LSW;
-    dim3 grid((unsigned)a.numPairs);
-#define DPX_SPLIT_CASE(R_)                                                                                                   \
-    case R_: return local ? launch_lanes_kernel(k_linear_split<R_, true>, a, grid, 64 * waves, ldsBytes, stream)             \
-                          : launch_lanes_kernel(k_linear_split<R_, false>, a, grid, 64 * waves, ldsBytes, stream);
-    switch (R) {
-        DPX_SPLIT_CASE(2)
-        DPX_SPLIT_CASE(4)
-    default: return hipErrorInvalidValue; /* (8 rows per lane would spill under the 1024-thread launch bound) */
-    }
-#undef DPX_SPLIT_CASE
+    return dispatch_int<2, 4>(R, [&](auto r) { /* (8 rows per lane would spill under the 1024-thread launch bound) */
+        return dispatch_bool(algo == DPX_K_LSW, [&](auto local) {
+            return launch_lds(k_linear_split<decltype(r)::value, decltype(local)::value>, dim3((unsigned)a.numPairs), dim3(64 * waves), ldsBytes, stream, a);
+        });
+    });
 }
 
 /* packed two-pairs-per-wave linear fill: a.order = couples (2 ints each), a.numPairs = number of couples */
 hipError_t dpx_launch_fill_packed(const dpx_fill_args &a, int algo, int R, size_t ldsBytes, hipStream_t stream) {
     if (a.numPairs <= 0) return hipSuccess;
-    const int wavesPerBlock = (int)a.wavesPerBlock;
-    dim3 grid((unsigned)((a.numPairs + wavesPerBlock - 1) / wavesPerBlock));
-    const bool local = algo == DPX_K_LSW;
-    switch (R) {
-    case 2: return launch_linear_pk_R<2>(a, local, grid, ldsBytes, stream);
-    case 4: return launch_linear_pk_R<4>(a, local, grid, ldsBytes, stream);
-    case 8: return launch_linear_pk_R<8>(a, local, grid, ldsBytes, stream);
-    case 16: return launch_linear_pk_R<16>(a, local, grid, ldsBytes, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_int<2, 4, 8, 16>(R, [&](auto r) {
+        constexpr int kR = decltype(r)::value;
+        if (algo != DPX_K_LSW) return launch_fill(k_linear_fill_pk<kR, false, false>, a, a, ldsBytes, stream);
+        return a.rowTags ? launch_fill(k_linear_fill_pk<kR, true, true>, a, a, ldsBytes, stream)
+                         : launch_fill(k_linear_fill_pk<kR, true, false>, a, a, ldsBytes, stream);
+    });
 }
 
-/* packed banded fill: a.order = couples (2 ints each), a.numPairs = number of couples; C = cells per lane */
-template <int C>
-static hipError_t launch_banded_pk_C(const dpx_fill_args &a, dim3 grid, size_t lds, hipStream_t s) {
-    const bool pb = ((a.band + 1) & 1) != 0; /* parity of step A = 0 */
-    return pb ? launch_fill_kernel(k_banded_fill_pk<C, true>, a, grid, lds, s) : launch_fill_kernel(k_banded_fill_pk<C, false>, a, grid, lds, s);
-}
-hipError_t dpx_launch_banded_packed(const dpx_fill_args &a, int C, size_t ldsBytes, hipStream_t stream) {
-    if (a.numPairs <= 0) return hipSuccess;
-    const int wavesPerBlock = (int)a.wavesPerBlock;
-    dim3 grid((unsigned)((a.numPairs + wavesPerBlock - 1) / wavesPerBlock));
-    switch (C) {
-    case 1: return launch_banded_pk_C<1>(a, grid, ldsBytes, stream);
-    case 2: return launch_banded_pk_C<2>(a, grid, ldsBytes, stream);
-    case 4: return launch_banded_pk_C<4>(a, grid, ldsBytes, stream);
-    case 8: return launch_banded_pk_C<8>(a, grid, ldsBytes, stream);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-
-hipError_t dpx_launch_export(const int16_t *mat, const dpx_pair_dev &pr, int algo, int R, int planes, int plane, int gapOpen,
-                             int gapExtend, int band, int16_t *out, hipStream_t stream) {
-    const size_t total = (size_t)(pr.m + 1) * (size_t)(pr.n + 1);
-    unsigned blocks = (unsigned)((total + 255) / 256);
-    if (blocks > 4096u) blocks = 4096u;
-    hipLaunchKernelGGL(k_export_matrix, dim3(blocks), dim3(256), 0, stream, mat, pr, algo, R, planes, plane, gapOpen,
-                       gapExtend, band, out);
-    return hipGetLastError();
-}
-
-hipError_t dpx_launch_traceback(const dpx_fill_args &a, int numPairs, int algo, int R, int planes, int walk,
-                                const uint64_t *tbOff, char *tb, int32_t *tbLen, hipStream_t stream) {
-    if (numPairs <= 0) return hipSuccess;
-    const bool cachedWalk = walk == 1;
-    if (walk == 2) { /* one wave per pair with an LDS window (k_traceback_wave) */
-        const size_t lds = dpx_traceback_wave_lds((algo == DPX_K_ANW || algo == DPX_K_ASW || algo == DPX_K_ASG) ? 3 : 1);
-        if (algo == DPX_K_ANW)
-            hipLaunchKernelGGL((k_traceback_wave<3, false, DPX_K_ANW>), dim3((unsigned)numPairs), dim3(64), lds, stream, a, numPairs, R, a.endRow, a.endCol, tbOff, tb, tbLen);
-        else if (algo == DPX_K_ASW)
-            hipLaunchKernelGGL((k_traceback_wave<3, false, DPX_K_ASW>), dim3((unsigned)numPairs), dim3(64), lds, stream, a, numPairs, R, a.endRow, a.endCol, tbOff, tb, tbLen);
-        else if (algo == DPX_K_ASG)
-            hipLaunchKernelGGL((k_traceback_wave<3, false, DPX_K_ASG>), dim3((unsigned)numPairs), dim3(64), lds, stream, a, numPairs, R, a.endRow, a.endCol, tbOff, tb, tbLen);
-        else if (algo == DPX_K_BSW)
-            hipLaunchKernelGGL((k_traceback_wave<1, true, DPX_K_LSW>), dim3((unsigned)numPairs), dim3(64), lds, stream, a, numPairs, R, a.endRow, a.endCol, tbOff, tb, tbLen);
-        else if (algo == DPX_K_LNW)
-            hipLaunchKernelGGL((k_traceback_wave<1, false, DPX_K_LNW>), dim3((unsigned)numPairs), dim3(64), lds, stream, a, numPairs, R, a.endRow, a.endCol, tbOff, tb, tbLen);
-        else
-            hipLaunchKernelGGL((k_traceback_wave<1, false, DPX_K_LSW>), dim3((unsigned)numPairs), dim3(64), lds, stream, a, numPairs, R, a.endRow, a.endCol, tbOff, tb, tbLen);
-        return hipGetLastError();
-    }
-    if (algo == DPX_K_ASW) /* (walk 1 caches linear-gap columns only: the ASW walk is walk 0's) */
-        hipLaunchKernelGGL(k_asw_traceback, dim3((unsigned)((numPairs + 63) / 64)), dim3(64), 0, stream, a, numPairs, R, planes, a.endRow,
-                           a.endCol, tbOff, tb, tbLen);
-    else if (algo == DPX_K_ASG) /* (likewise; ASG's borders are this walk's own) */
-        hipLaunchKernelGGL(k_asg_traceback, dim3((unsigned)((numPairs + 63) / 64)), dim3(64), 0, stream, a, numPairs, R, planes, a.endRow,
-                           a.endCol, tbOff, tb, tbLen);
-    else
-        hipLaunchKernelGGL(k_traceback, dim3((unsigned)((numPairs + 63) / 64)), dim3(64), 0, stream, a, numPairs, algo, R, planes,
-                           cachedWalk ? 1 : 0, a.endRow, a.endCol, tbOff, tb, tbLen);
-    return hipGetLastError();
-}
-
-/* result text of a batch: lengths -> exclusive scan (tileSums: ceil(numPairs / 2048) + 1 entries of scratch) -> packed copy.
- * outOff[numPairs] receives the total number of bytes. */
-size_t dpx_out_scan_tiles(size_t numPairs) { return (numPairs + kScanTile - 1) / kScanTile; }
-hipError_t dpx_launch_output(const dpx_pair_dev *pairs, const int32_t *score, const int32_t *tbLen, const uint64_t *tbOff, const char *tb,
-                             int numPairs, unsigned long long firstNumber, unsigned long long *tileSums, unsigned long long *outOff, char *out,
-                             bool scanOnly, bool compactOnly, hipStream_t stream) {
-    if (numPairs <= 0) return hipSuccess;
-    const int tiles = (int)dpx_out_scan_tiles((size_t)numPairs);
-    if (!compactOnly && !scanOnly && numPairs <= kOutSmallPairs) {
-        hipLaunchKernelGGL(k_out_small, dim3(1), dim3(kScanThreads), 0, stream, pairs, score, tbLen, tbOff, tb, numPairs, firstNumber, outOff, out);
-        return hipGetLastError();
-    }
-    if (!compactOnly) {
-        hipLaunchKernelGGL(k_out_scan<false>, dim3(tiles), dim3(kScanThreads), 0, stream, score, tbLen, numPairs, firstNumber, tileSums, outOff);
-        hipLaunchKernelGGL(k_out_scan_tiles, dim3(1), dim3(kScanThreads), 0, stream, tileSums, tiles);
-        hipLaunchKernelGGL(k_out_scan<true>, dim3(tiles), dim3(kScanThreads), 0, stream, score, tbLen, numPairs, firstNumber, tileSums, outOff);
-    }
-    if (!scanOnly)
-        hipLaunchKernelGGL(k_out_compact, dim3((unsigned)((numPairs + 3) / 4)), dim3(256), 0, stream, pairs, score, tbLen, tbOff, tb, numPairs, firstNumber,
-                           outOff, out);
-    return hipGetLastError();
-}
-
-/* expand numDwords x 16 bases (2 bits each) into bytes: out must be 16-byte aligned and hold 16 * numDwords bytes */
-hipError_t dpx_launch_unpack2(const uint32_t *packed, uint32_t alphabet, char *out, size_t numDwords, hipStream_t stream) {
-    if (numDwords == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_unpack2, dim3((unsigned)((numDwords + 255) / 256)), dim3(256), 0, stream, packed, alphabet, reinterpret_cast<uint4 *>(out), numDwords);
-    return hipGetLastError();
-}
-
-hipError_t dpx_launch_prim_eval(const int32_t *op, const uint32_t *a, const uint32_t *b, const uint32_t *c, size_t count,
-                                uint32_t *res, uint32_t *pred, hipStream_t stream) {
-    if (count == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_prim_eval, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, op, a, b, c, count, res,
-                       pred);
-    return hipGetLastError();
-}

@@ -2,15 +2,12 @@
 k_traceback_wave<3, false, ASG>) in the gfx950 code object, checked on the CPU: every instantiation exists, none uses scratch or the matrix
 cores, the storing fills move their neighbours with DPP and write 16 bytes per lane as their ANW twins do, and every kernel keeps four
 waves per SIMD (<= 128 VGPRs)."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "dpx_gpu_genomics_project_amd", "csrc")
+import isa_units
+
 
 # .vgpr_count as measured when the kernels were written: (template arguments) -> registers
 FILL_VGPRS = {("2", "1"): 58, ("2", "0"): 48, ("4", "1"): 74, ("4", "0"): 59, ("8", "1"): 101, ("8", "0"): 83}   # k_asg_fill<R, STORE>
@@ -20,29 +17,12 @@ WALK_VGPRS = {"k_asg_traceback": 78, "k_traceback_waveILi3ELb0ELi6E": 107}
 
 
 @pytest.fixture(scope="module")
-def isa(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc on this machine")
-    text = ""
-    for unit in ("dpx_kernels", "dpx_dir_kernels"):
-        out = tmp_path_factory.mktemp("asg_isa") / (unit + ".s")
-        subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-I", CSRC, "-I", os.path.join(ROOT, "include"),
-                        os.path.join(CSRC, unit + ".hip"), "-o", str(out)], check=True, timeout=900)
-        text += open(out).read() + "\n"
-    meta = {m.group(1): m.group(0) for m in re.finditer(r"\.name:\s+(\S+)\n(?:.*\n){0,12}?.*\.vgpr_count:\s+\d+", text)}
-    ks = {}
-    for name in meta:
-        if "k_asg_" not in name and "k_traceback_waveILi3ELb0ELi6E" not in name:
-            continue
-        start = text.find("\n" + name + ":")
-        end = text.find(".Lfunc_end", start)
-        ks[name] = (meta[name], text[start:end] if start >= 0 else "")
-    return ks
+def isa():
+    return {name: v[:2] for name, v in isa_units.kernels("dpx_kernels", "dpx_dir_kernels").items()
+            if "k_asg_" in name or "k_traceback_waveILi3ELb0ELi6E" in name}
 
 
-def _vgprs(meta):
-    return int(re.search(r"\.vgpr_count:\s+(\d+)", meta).group(1))
+_vgprs = isa_units.vgprs
 
 
 def _one(ks, frag):
@@ -77,17 +57,17 @@ def test_storing_fills_use_dpp_and_16_byte_stores(isa):
         meta, body = isa[_one(isa, frag)]
         assert "v_mov_b32_dpp" in body, frag
         assert "v_max3_i32" in body, frag  # the shared recurrence
-        stores = set(re.findall(r"\b(global_store_\w+|buffer_store_\w+|flat_store_\w+)", body))
+        stores = isa_units.stores(body)
         if "ILi8E" in frag:  # 8 rows per lane: one 16-byte piece per plane
             assert "global_store_dwordx4" in stores, (frag, stores)
     for frag in ["k_asg_fillILi%sELb0EE" % r for r in "248"] + ["k_asg_lanesILi8ELb0EE"]:  # score-only: the three result dwords alone
         meta, body = isa[_one(isa, frag)]
         assert "v_mov_b32_dpp" in body, frag
-        assert set(re.findall(r"\b(global_store_\w+|buffer_store_\w+|flat_store_\w+)", body)) <= {"global_store_dword"}, frag
+        assert isa_units.stores(body) <= {"global_store_dword"}, frag
     wide = {"global_store_dword", "global_store_dwordx2", "global_store_dwordx3", "global_store_dwordx4"}
     for key in DIR_VGPRS:
         meta, body = isa[_one(isa, "k_asg_dirILi%sELb%sEE" % key)]
-        stores = set(re.findall(r"\b(global_store_\w+|buffer_store_\w+|flat_store_\w+)", body))
+        stores = isa_units.stores(body)
         assert stores and stores <= wide and "global_store_dwordx4" in stores, (key, stores)
 
 

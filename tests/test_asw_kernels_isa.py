@@ -2,46 +2,25 @@
 k_traceback_wave<3, false, ASW>) in the
 gfx950 code object, checked on the CPU: no scratch, no matrix cores, the instructions of the ANW fill they share their body with, and a
 register count that keeps four waves per SIMD."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "dpx_gpu_genomics_project_amd", "csrc")
+import isa_units
+
 
 
 @pytest.fixture(scope="module")
-def isa(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc on this machine")
-    out = tmp_path_factory.mktemp("asw_isa") / "dpx_kernels.s"
-    subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-I", CSRC, "-I", os.path.join(ROOT, "include"),
-                    os.path.join(CSRC, "dpx_kernels.hip"), "-o", str(out)], check=True, timeout=600)
-    dout = tmp_path_factory.mktemp("asw_isa_dir") / "dpx_dir_kernels.s"
-    subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-I", CSRC, "-I", os.path.join(ROOT, "include"),
-                    os.path.join(CSRC, "dpx_dir_kernels.hip"), "-o", str(dout)], check=True, timeout=600)
-    return open(out).read() + "\n" + open(dout).read()
+def isa():
+    return isa_units.kernels("dpx_kernels", "dpx_dir_kernels")
 
 
 def _asw_kernels(isa):
     """{mangled name: (metadata, body)} of the kernels that run ASW"""
-    meta = {m.group(1): m.group(0) for m in re.finditer(r"\.name:\s+(\S+)\n(?:.*\n){0,12}?.*\.vgpr_count:\s+\d+", isa)}
-    out = {}
-    for name in meta:
-        if "k_asw_" not in name and "k_traceback_waveILi3ELb0ELi4E" not in name:
-            continue
-        start = isa.find("\n" + name + ":")
-        end = isa.find(".Lfunc_end", start)
-        out[name] = (meta[name], isa[start:end] if start >= 0 else "")
-    return out
+    return {name: v[:2] for name, v in isa.items() if "k_asw_" in name or "k_traceback_waveILi3ELb0ELi4E" in name}
 
 
-def _vgprs(meta):
-    return int(re.search(r"\.vgpr_count:\s+(\d+)", meta).group(1))
+_vgprs = isa_units.vgprs
 
 
 def test_asw_kernels_exist_without_scratch_or_mfma(isa):
@@ -74,6 +53,6 @@ def test_asw_direction_stores_are_dword_or_wider(isa):
     for name, (meta, body) in _asw_kernels(isa).items():
         if "k_asw_dir" not in name:
             continue
-        stores = set(re.findall(r"\b(global_store_\w+|buffer_store_\w+|flat_store_\w+)", body))
+        stores = isa_units.stores(body)
         assert stores and stores <= wide, (name, stores)
         assert "global_store_dwordx4" in stores, name

@@ -2,37 +2,19 @@
 metadata on the CPU: the unit holds exactly the 16 instantiations of k_bdir_fill, the walk and the export, none uses scratch, every
 fill stays within 128 VGPRs (four waves per SIMD, the floor k_baxt_fill is held to), and no name contains a substring the other ISA
 tests count their kernels by.  Metadata only: no instruction is looked at."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "dpx_gpu_genomics_project_amd", "csrc")
+import isa_units
+
 BANNED = ("k_banw", "k_baxt", "k_basw", "k_zext_fill", "k_subst", "k_asw_", "k_asg_", "k_banded_fill", "k_cigar", "k_linear_dir", "k_affine_dir")
 
 
-def _metadata(isa):
-    """{mangled name: (vgpr_count, private_segment_fixed_size, group_segment_fixed_size)} from the code object's kernel metadata"""
-    out = {}
-    for m in re.finditer(r"- \.agpr_count:.*?\.wavefront_size:\s+\d+", isa, re.S):
-        block = m.group(0)
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        out[name] = tuple(int(re.search(rf"\.{key}:\s+(\d+)", block).group(1)) for key in ("vgpr_count", "private_segment_fixed_size", "group_segment_fixed_size"))
-    return out
-
-
 @pytest.fixture(scope="module")
-def meta(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc on this machine")
-    out = tmp_path_factory.mktemp("banddir_isa") / "dpx_banddir_kernels.s"
-    subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-I", CSRC, "-I", os.path.join(ROOT, "include"),
-                    os.path.join(CSRC, "dpx_banddir_kernels.hip"), "-o", str(out)], check=True, timeout=900)
-    return _metadata(open(out).read())
+def meta():
+    """{mangled name: (vgpr_count, private_segment_fixed_size, group_segment_fixed_size)} from the code object's kernel metadata"""
+    return isa_units.counts("dpx_banddir_kernels")
 
 
 def test_sixteen_fills_one_walk_one_export_and_no_scratch(meta):

@@ -6,13 +6,10 @@ with the same register count."""
 import json
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "dpx_gpu_genomics_project_amd", "csrc")
+import isa_units
 
 # .vgpr_count as measured when the kernels were written: the largest of the four instantiations of each cells-per-lane count C (every C
 # keeps four waves per SIMD, <= 128 registers), the export and the two walks
@@ -20,39 +17,17 @@ FILL_VGPRS = {1: 51, 2: 59, 4: 75, 8: 124}
 OTHER_VGPRS = {"k_banw_export": 18, "k_banw_tracebackE": 50, "k_banw_traceback_wave": 225}
 
 
-def _start(tmp, name):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc on this machine")
-    out = tmp / (name + ".s")
-    return out, subprocess.Popen([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-I", CSRC, "-I",
-                                  os.path.join(ROOT, "include"), os.path.join(CSRC, name + ".hip"), "-o", str(out)])
-
-
-def _finish(job):
-    out, proc = job
-    assert proc.wait(timeout=900) == 0, out
-    return open(out).read()
-
-
-def _kernels(isa):
+def _kernels(unit):
     """{mangled name: (metadata, body)}"""
-    meta = {m.group(1): m.group(0) for m in re.finditer(r"\.name:\s+(\S+)\n(?:.*\n){0,12}?.*\.vgpr_count:\s+\d+", isa)}
-    out = {}
-    for name in meta:
-        start = isa.find("\n" + name + ":")
-        end = isa.find(".Lfunc_end", start)
-        out[name] = (meta[name], isa[start:end] if start >= 0 else "")
-    return out
+    return {name: v[:2] for name, v in isa_units.kernels(unit).items()}
 
 
-def _vgprs(meta):
-    return int(re.search(r"\.vgpr_count:\s+(\d+)", meta).group(1))
+_vgprs = isa_units.vgprs
 
 
 @pytest.fixture(scope="module")
-def banw_isa(tmp_path_factory):
-    return _kernels(_finish(_start(tmp_path_factory.mktemp("banw_isa"), "dpx_banw_kernels")))
+def banw_isa():
+    return _kernels("dpx_banw_kernels")
 
 
 def test_every_kernel_exists_without_scratch_or_mfma(banw_isa):
@@ -77,7 +52,7 @@ def test_storing_fills_write_16_bytes_per_lane(banw_isa):
     for name, (meta, body) in banw_isa.items():
         if "k_banw_fill" not in name:
             continue
-        stores = set(re.findall(r"\b(global_store_\w+|buffer_store_\w+|flat_store_\w+)", body))
+        stores = isa_units.stores(body)
         if name.endswith("ELb1EEEv13dpx_fill_args"):  # STORE = true: matrix stores are dwordx4 only (+ the three result dwords)
             assert "global_store_dwordx4" in stores, (name, stores)
             assert stores <= {"global_store_dwordx4", "global_store_dword"}, (name, stores)
@@ -100,13 +75,12 @@ def test_register_counts_are_the_recorded_ones(banw_isa):
     assert all(seen[c] <= 128 for c in seen), seen  # four waves per SIMD at every C
 
 
-def test_every_earlier_kernel_is_unchanged(tmp_path_factory):
-    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "kernel_vgprs_before_banw.json")))["kernels"]
+def test_every_earlier_kernel_is_unchanged():
+    golden = json.load(open(os.path.join(isa_units.ROOT, "tests", "golden", "kernel_vgprs_before_banw.json")))["kernels"]
     assert sorted(golden) == ["dpx_basw_kernels.hip", "dpx_dir_kernels.hip", "dpx_kernels.hip"]
-    tmp = tmp_path_factory.mktemp("before_banw")
-    jobs = {unit: _start(tmp, unit[:-4]) for unit in golden}  # the three compile side by side
-    for unit, want in golden.items():
-        got = {k: _vgprs(v[0]) for k, v in _kernels(_finish(jobs[unit])).items()}
+    isa_units.text(*golden)  # they compile side by side
+    for unit, want in golden.items():  # "dpx_kernels.hip": the union of the units it became (isa_units.SUCCESSORS), no name in two of them
+        got = {k: _vgprs(v[0]) for k, v in _kernels(unit).items()}
         assert len(want) >= 19, unit
         assert got == want, (unit, sorted(set(got.items()) ^ set(want.items())))
         assert not [k for k in got if "banw" in k], unit  # the new kernels live in their own translation unit

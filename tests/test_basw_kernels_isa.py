@@ -6,47 +6,27 @@ same register count."""
 import json
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "dpx_gpu_genomics_project_amd", "csrc")
+import isa_units
 
 # .vgpr_count per cells-per-lane count C as measured when the kernel was written (the largest of the four instantiations of that C):
 # C <= 4 keeps more than four waves per SIMD (<= 128 registers), C = 8 exactly four
 VGPR_BOUND = {1: 46, 2: 54, 4: 75, 8: 122}
 
 
-def _compile(tmp, name):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc on this machine")
-    out = tmp / (name + ".s")
-    subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-I", CSRC, "-I", os.path.join(ROOT, "include"),
-                    os.path.join(CSRC, name + ".hip"), "-o", str(out)], check=True, timeout=900)
-    return open(out).read()
-
-
-def _kernels(isa):
+def _kernels(unit):
     """{mangled name: (metadata, body)}"""
-    meta = {m.group(1): m.group(0) for m in re.finditer(r"\.name:\s+(\S+)\n(?:.*\n){0,12}?.*\.vgpr_count:\s+\d+", isa)}
-    out = {}
-    for name in meta:
-        start = isa.find("\n" + name + ":")
-        end = isa.find(".Lfunc_end", start)
-        out[name] = (meta[name], isa[start:end] if start >= 0 else "")
-    return out
+    return {name: v[:2] for name, v in isa_units.kernels(unit).items()}
 
 
-def _vgprs(meta):
-    return int(re.search(r"\.vgpr_count:\s+(\d+)", meta).group(1))
+_vgprs = isa_units.vgprs
 
 
 @pytest.fixture(scope="module")
-def basw_isa(tmp_path_factory):
-    return _kernels(_compile(tmp_path_factory.mktemp("basw_isa"), "dpx_basw_kernels"))
+def basw_isa():
+    return _kernels("dpx_basw_kernels")
 
 
 def test_every_instantiation_exists_without_scratch_or_mfma(basw_isa):
@@ -71,7 +51,7 @@ def test_storing_fills_write_16_bytes_per_lane_and_move_neighbours_with_dpp(basw
         if "k_basw_fill" not in name:
             continue
         assert "v_mov_b32_dpp" in body, name
-        stores = set(re.findall(r"\b(global_store_\w+|buffer_store_\w+|flat_store_\w+)", body))
+        stores = isa_units.stores(body)
         if name.endswith("ELb1EEEv13dpx_fill_args"):  # STORE = true: matrix stores are dwordx4 only (+ the three result dwords)
             assert "global_store_dwordx4" in stores, (name, stores)
             assert stores <= {"global_store_dwordx4", "global_store_dword"}, (name, stores)
@@ -92,10 +72,10 @@ def test_register_counts_are_the_recorded_ones(basw_isa):
     assert all(seen[c] <= 128 for c in seen), seen  # four waves per SIMD at every C
 
 
-def test_every_earlier_kernel_is_unchanged(tmp_path_factory):
-    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "kernel_vgprs_before_basw.json")))["kernels"]
+def test_every_earlier_kernel_is_unchanged():
+    golden = json.load(open(os.path.join(isa_units.ROOT, "tests", "golden", "kernel_vgprs_before_basw.json")))["kernels"]
     for unit, want in golden.items():
-        got = {k: _vgprs(v[0]) for k, v in _kernels(_compile(tmp_path_factory.mktemp("before_basw"), unit[:-4])).items()}
+        got = {k: _vgprs(v[0]) for k, v in _kernels(unit).items()}  # "dpx_kernels.hip": the union of the units it became
         assert len(want) > 20, unit
         for name, vg in want.items():
             assert got.get(name) == vg, (unit, name, vg, got.get(name))

@@ -1,38 +1,23 @@
 """Build-time properties of the direction-matrix kernels (dpx_dir_kernels.hip), checked on the CPU: no scratch memory, no matrix cores,
 fill kernels within 128 VGPRs, and every store of a fill kernel a whole dword or wider (the codes leave as one 16-byte store per lane and
 group of steps: whole 64-byte sectors)."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "dpx_gpu_genomics_project_amd", "csrc")
+import isa_units
+
 WIDE = {"global_store_dword", "global_store_dwordx2", "global_store_dwordx3", "global_store_dwordx4"}
 
 
 @pytest.fixture(scope="module")
-def isa(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc on this machine")
-    out = tmp_path_factory.mktemp("isa") / "dpx_dir_kernels.s"
-    subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-I", CSRC, "-I", os.path.join(ROOT, "include"),
-                    os.path.join(CSRC, "dpx_dir_kernels.hip"), "-o", str(out)], check=True, timeout=600)
-    return open(out).read()
+def isa():
+    return isa_units.text("dpx_dir_kernels")
 
 
 def _kernels(isa):
     """{mangled name: (metadata text, body text)}"""
-    meta = {m.group(1): m.group(0) for m in re.finditer(r"\.name:\s+(\S+)\n(?:.*\n){0,12}?.*\.vgpr_count:\s+\d+", isa)}
-    out = {}
-    for name in meta:
-        start = isa.find("\n" + name + ":")
-        end = isa.find(".Lfunc_end", start)
-        out[name] = (meta[name], isa[start:end] if start >= 0 else "")
-    return out
+    return {name: v[:2] for name, v in isa_units.kernels("dpx_dir_kernels").items()}
 
 
 def _fills(ks):
@@ -50,12 +35,12 @@ def test_no_scratch_no_mfma(isa):
 
 def test_fill_kernels_fit_128_vgprs(isa):
     for name, (meta, _) in _fills(_kernels(isa)).items():
-        assert int(re.search(r"\.vgpr_count:\s+(\d+)", meta).group(1)) <= 128, name
+        assert isa_units.vgprs(meta) <= 128, name
 
 
 def test_fill_stores_are_dword_or_wider(isa):
     for name, (_, body) in _fills(_kernels(isa)).items():
-        stores = set(re.findall(r"\b(global_store_\w+|buffer_store_\w+|flat_store_\w+)", body))
+        stores = isa_units.stores(body)
         assert stores, name
         assert stores <= WIDE, (name, stores - WIDE)
         assert "global_store_dwordx4" in stores, name  # the codes: one 16-byte store per lane and group of steps

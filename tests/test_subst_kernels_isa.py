@@ -2,37 +2,19 @@
 metadata on the CPU: the unit holds exactly the 32 instantiations of k_subst_fill and the two walks, none uses scratch, every fill
 stays within 128 VGPRs (four waves per SIMD, the floor k_baxt_fill is held to), and no name contains a substring the other ISA tests
 count their kernels by."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "dpx_gpu_genomics_project_amd", "csrc")
+import isa_units
+
 BANNED = ("k_banw", "k_baxt", "k_basw", "k_zext_fill", "k_asw_", "k_asg_", "k_banded_fill", "k_cigar")
 
 
-def _metadata(isa):
-    """{mangled name: (vgpr_count, private_segment_fixed_size)} from the code object's kernel metadata"""
-    out = {}
-    for m in re.finditer(r"- \.agpr_count:.*?\.wavefront_size:\s+\d+", isa, re.S):
-        block = m.group(0)
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        out[name] = (int(re.search(r"\.vgpr_count:\s+(\d+)", block).group(1)), int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", block).group(1)))
-    return out
-
-
 @pytest.fixture(scope="module")
-def meta(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc on this machine")
-    out = tmp_path_factory.mktemp("subst_isa") / "dpx_subst_kernels.s"
-    subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-I", CSRC, "-I", os.path.join(ROOT, "include"),
-                    os.path.join(CSRC, "dpx_subst_kernels.hip"), "-o", str(out)], check=True, timeout=900)
-    return _metadata(open(out).read())
+def meta():
+    """{mangled name: (vgpr_count, private_segment_fixed_size)} from the code object's kernel metadata"""
+    return {name: c[:2] for name, c in isa_units.counts("dpx_subst_kernels").items()}
 
 
 def test_thirty_two_fills_two_walks_and_no_scratch(meta):

@@ -1,52 +1,23 @@
 """Build-time properties of BAXT's extension-mode fill (dpx_zext_kernels.hip) in the gfx950 code object, read from the code-object
 metadata on the CPU: all 32 instantiations of k_zext_fill exist and nothing else lives in the unit, none uses scratch, and at every
 cells-per-lane count C the register count allows at least 4 waves per SIMD, the floor the project sets for k_baxt_fill at C = 8."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "dpx_gpu_genomics_project_amd", "csrc")
+import isa_units
 
 
-def _start(tmp, name):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc on this machine")
-    out = tmp / (name + ".s")
-    return out, subprocess.Popen([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-I", CSRC, "-I",
-                                  os.path.join(ROOT, "include"), os.path.join(CSRC, name + ".hip"), "-o", str(out)])
 
-
-def _finish(job):
-    out, proc = job
-    assert proc.wait(timeout=900) == 0, out
-    return open(out).read()
-
-
-def _metadata(isa):
-    """{mangled name: (vgpr_count, private_segment_fixed_size)} from the code object's kernel metadata"""
-    out = {}
-    for m in re.finditer(r"- \.agpr_count:.*?\.wavefront_size:\s+\d+", isa, re.S):
-        block = m.group(0)
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        out[name] = (int(re.search(r"\.vgpr_count:\s+(\d+)", block).group(1)), int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", block).group(1)))
-    return out
-
-
-def _waves_per_simd(vgprs):
-    """gfx950: 512 registers per lane and SIMD, allocated in blocks of 8, at most 8 waves"""
-    return min(8, 512 // ((vgprs + 7) // 8 * 8))
+_waves_per_simd = isa_units.waves_per_simd
 
 
 @pytest.fixture(scope="module")
-def units(tmp_path_factory):
-    tmp = tmp_path_factory.mktemp("zext_isa")
-    jobs = {u: _start(tmp, u) for u in ("dpx_zext_kernels", "dpx_baxt_kernels")}  # the two compile side by side
-    return {u: _metadata(_finish(j)) for u, j in jobs.items()}
+def units():
+    """{unit: {mangled name: (vgpr_count, private_segment_fixed_size)}} from the code object's kernel metadata"""
+    names = ("dpx_zext_kernels", "dpx_baxt_kernels")
+    isa_units.text(*names)  # the two compile side by side
+    return {u: {name: c[:2] for name, c in isa_units.counts(u).items()} for u in names}
 
 
 def test_thirty_two_fills_and_no_scratch(units):
