@@ -35,7 +35,7 @@ ABI_SYMBOLS = (
     "dpx_batch_output_begin", "dpx_batch_output_end", "dpx_batch_output_take", "dpx_text_free",
     "dpx_batch_info", "dpx_batch_describe", "dpx_batch_destroy", "dpx_align_batch", "dpx_prim_eval", "dpx_batch_directions",
     "dpx_batch_cigars_begin", "dpx_batch_cigars_end", "dpx_cigar_text", "dpx_batch_set_extension", "dpx_batch_extensions",
-    "dpx_batch_set_substitution",
+    "dpx_batch_set_substitution", "dpx_batch_set_extension_table",
 )
 # declared entry points a library may lack and still load (an older build): checked when they are called
 OPTIONAL_SYMBOLS = ("dpx_batch_directions",)
@@ -127,6 +127,7 @@ def load() -> C.CDLL:
     lib.dpx_batch_set_extension.argtypes = [vp, C.c_int32, C.c_int32]
     lib.dpx_batch_extensions.argtypes = [vp, vp]
     lib.dpx_batch_set_substitution.argtypes = [vp, vp, C.c_int32, vp]
+    lib.dpx_batch_set_extension_table.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, vp]
     for name in ABI_SYMBOLS:  # every declared entry point must be exported (the optional ones by libraries that have them)
         if name not in OPTIONAL_SYMBOLS:
             getattr(lib, name)
@@ -287,15 +288,18 @@ class Batch:
         if scores is None:
             _check(self._lib.dpx_batch_set_substitution(self._h, None, 0, None), "dpx_batch_set_substitution")
             return
-        tab = np.ascontiguousarray(scores, dtype=np.int8)
-        if tab.ndim != 2 or tab.shape[0] != tab.shape[1] or not np.array_equal(tab, np.asarray(scores)):
-            raise ValueError("scores must be a square matrix of int8 values")
-        if code_of is None:
-            raise ValueError("code_of is required with a table")
-        code = np.ascontiguousarray(code_of, dtype=np.uint8)
-        if code.shape != (256,) or not np.array_equal(code, np.asarray(code_of).reshape(-1)):
-            raise ValueError("code_of must hold 256 values in 0..255")
+        tab, code = _table_arrays(scores, code_of)
         _check(self._lib.dpx_batch_set_substitution(self._h, tab.ctypes.data, tab.shape[0], code.ctypes.data), "dpx_batch_set_substitution")
+
+    def set_extension_table(self, zdrop: int, end_bonus: int, scores, code_of) -> None:
+        """BAXT only: extension mode (set_extension's values, not both -1) and a substitution table (set_substitution's arrays, not
+        None) together, the one way to have both.  Replaces both settings; lines and results of an earlier fill are invalid afterwards.
+        To change a value or the table of such a batch, call this again."""
+        if scores is None:
+            raise ValueError("scores is required: set_extension alone runs extension mode without a table")
+        tab, code = _table_arrays(scores, code_of)
+        _check(self._lib.dpx_batch_set_extension_table(self._h, zdrop, end_bonus, tab.ctypes.data, tab.shape[0], code.ctypes.data),
+               "dpx_batch_set_extension_table")
 
     def extensions(self) -> np.ndarray:
         """One EXTENSION_DTYPE record per pair of the last fill, which must have run in extension mode."""
@@ -333,6 +337,19 @@ class Batch:
             self.close()
         except Exception:
             pass
+
+
+def _table_arrays(scores, code_of):
+    """(int8 (A, A) table, uint8 (256,) map) as contiguous arrays, or ValueError: the argument checking of the two table setters"""
+    tab = np.ascontiguousarray(scores, dtype=np.int8)
+    if tab.ndim != 2 or tab.shape[0] != tab.shape[1] or not np.array_equal(tab, np.asarray(scores)):
+        raise ValueError("scores must be a square matrix of int8 values")
+    if code_of is None:
+        raise ValueError("code_of is required with a table")
+    code = np.ascontiguousarray(code_of, dtype=np.uint8)
+    if code.shape != (256,) or not np.array_equal(code, np.asarray(code_of).reshape(-1)):
+        raise ValueError("code_of must hold 256 values in 0..255")
+    return tab, code
 
 
 def code_table(alphabet: bytes, fold_case: bool = True) -> np.ndarray:

@@ -1,12 +1,13 @@
 /*
  * dpx_band_affine.hpp -- what the banded affine-gap units without a zero floor share: dpx_banw_kernels.hip (BANW), dpx_baxt_kernels.hip
- * (BAXT), dpx_zext_kernels.hip (BAXT in extension mode), dpx_subst_kernels.hip (either, scored by a table) and dpx_banddir_kernels.hip
- * (either, storing direction codes).  dpx_basw_kernels.hip, whose step has a zero floor and a start cell, is a different kernel and does
+ * (BAXT), dpx_zext_kernels.hip (BAXT in extension mode), dpx_subst_kernels.hip (either, scored by a table), dpx_zsub_kernels.hip (BAXT in
+ * extension mode, scored by a table) and dpx_banddir_kernels.hip (either, storing direction codes).  dpx_basw_kernels.hip, whose step has a zero floor and a start cell, is a different kernel and does
  * not include it.  Everything here is a __forceinline__ function or a template: each kernel stays in its own unit under its own name.
  *
  * Shared are end_key, the band geometry and BandView, the step of the two fills that track slot keys (slot_key_step: k_baxt_fill and
- * k_zext_fill) and both walks over the stored planes as templates on a Scorer (band_walk_lane, band_walk_wave: BANW's with the byte
- * compare, the substitution walks with the table).  The helpers of every family (stage_bytes, store8, wave_max_u64, CharWin) and the
+ * k_zext_fill), the step under a table (subst_step: k_subst_fill and k_zsub_fill), the scan of extension mode (wave_max_i32, zdrop_test,
+ * write_results, scan_border_line, DPX_BAND_SCAN_AFTER, scan_finish: k_zext_fill and k_zsub_fill) and both walks over the stored planes
+ * as templates on a Scorer (band_walk_lane, band_walk_wave: BANW's with the byte compare, the substitution walks with the table).  The helpers of every family (stage_bytes, store8, wave_max_u64, CharWin) and the
  * launch helper and dispatcher of every fill (launch_fill, dispatch_fill) come from dpx_device.hpp under their old names.
  *
  * NOT shared is one step for all fills.  band_step<C, P1, INTERIOR, Scorer, Tracker> over shared geometry / slide-and-gather / select
@@ -33,6 +34,7 @@
 #define DPX_BAND_AFFINE_HPP
 
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
 
 #include <type_traits>
@@ -200,6 +202,243 @@ __device__ __forceinline__ void slot_key_step(SlotKeyState<C> &st, const int A, 
         outH[c] = h;
         outI[c] = ii;
         outD[c] = d;
+    }
+}
+
+/* ---- the step of k_subst_fill and k_zsub_fill: slot_key_step / banw_step with the table lookup ---- */
+template <int C, bool EXT>
+struct SubstState {
+    int prevH[C], prev2H[C]; /* H on anti-diagonals a-1 and a-2 */
+    int prevI[C], prevD[C];  /* I and D on anti-diagonal a-1 */
+    int qcd[C], rcd[C];      /* query code / reference code << 5 of each slot's cell */
+    int key[EXT ? C : 1];    /* EXT: running signed max of (H << 16 | 0xFFFF - A): max score, then earliest step */
+    int lim;                 /* B-1 - lane*C: slot c is inside the band on a step of parity p when c + p <= lim */
+    int fin;                 /* !EXT: H[m][n], picked up on the last anti-diagonal by the lane that owns its slot */
+};
+
+/* banw_step / slot_key_step with the table lookup.  INTERIOR: every in-band slot of this anti-diagonal lies inside the matrix, so validity
+ * is one compare against the per-lane constant `lim`; no border slot and (!EXT) not the last anti-diagonal */
+template <int C, bool P1, bool INTERIOR, bool EXT>
+__device__ __forceinline__ void subst_step(SubstState<C, EXT> &st, const int A, int &i0, int &j0, const int lane, const int m, const int n,
+                                           const int B, const int o, const int oe, const int e, const int cEnd, const unsigned char *qL,
+                                           const unsigned char *rL, const signed char *tabL, const unsigned char *codeL, int *outH,
+                                           int *outI, int *outD) {
+    const int p = P1 ? 1 : 0;
+    if constexpr (P1) i0++; else j0++;
+    const int smin = INTERIOR ? 0 : max(max(1 - i0, j0 - n), 0);
+    const int smax = INTERIOR ? 0 : min(min(m - i0, j0 - 1), B - 1 - p);
+    /* the in-band border cells of this anti-diagonal: (0, a) in slot -i0 and (a, 0) in slot j0, both H = o + a * e, while a <= B-1 */
+    const int a = A + 2;
+    const int bord = (INTERIOR || a > B - 1) ? DPX_NEG : o + a * e;
+    const int sTop = (INTERIOR || a > n) ? -1 : -i0, sLeft = (INTERIOR || a > m) ? -1 : j0;
+    const int lo = smin - lane * C, cnt = max(smax - smin + 1, 0), cTop = sTop - lane * C, cLeft = sLeft - lane * C;
+    const bool last = !EXT && !INTERIOR && a == m + n;
+    int upH[C], upD[C], leftH[C], leftI[C];
+    if constexpr (P1) {
+        const int newq = codeL[INTERIOR ? qL[i0 + 64 * C - 2] : qL[min(max(i0 + 64 * C - 2, 0), m - 1)]];
+        const int tq = wave_shl1(st.qcd[0], newq);
+#pragma unroll
+        for (int c = 0; c < C - 1; c++) st.qcd[c] = st.qcd[c + 1];
+        st.qcd[C - 1] = tq;
+        const int nbH = wave_shl1(st.prevH[0], DPX_NEG);
+        const int nbI = wave_shl1(st.prevI[0], DPX_NEG);
+#pragma unroll
+        for (int c = 0; c < C; c++) {
+            upH[c] = st.prevH[c];
+            upD[c] = st.prevD[c];
+            leftH[c] = (c < C - 1) ? st.prevH[c + 1] : nbH;
+            leftI[c] = (c < C - 1) ? st.prevI[c + 1] : nbI;
+        }
+    } else {
+        const int newr = (int)codeL[INTERIOR ? rL[j0 - 1] : rL[min(max(j0 - 1, 0), n - 1)]] << 5;
+        const int tr = wave_shr1(st.rcd[C - 1], newr);
+#pragma unroll
+        for (int c = C - 1; c > 0; c--) st.rcd[c] = st.rcd[c - 1];
+        st.rcd[0] = tr;
+        const int nbH = wave_shr1(st.prevH[C - 1], DPX_NEG);
+        const int nbD = wave_shr1(st.prevD[C - 1], DPX_NEG);
+#pragma unroll
+        for (int c = 0; c < C; c++) {
+            leftH[c] = st.prevH[c];
+            leftI[c] = st.prevI[c];
+            upH[c] = (c > 0) ? st.prevH[c - 1] : nbH;
+            upD[c] = (c > 0) ? st.prevD[c - 1] : nbD;
+        }
+    }
+    int sc[C]; /* all C byte reads are in flight before the first is used (codes are < 32: the address stays inside the 1-KiB table) */
+#pragma unroll
+    for (int c = 0; c < C; c++) sc[c] = (int)tabL[st.rcd[c] + st.qcd[c]];
+    const int negA = 0xFFFF - A;
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+        int d = max(upH[c] + oe, upD[c] + e);
+        int ii = max(leftH[c] + oe, leftI[c] + e);
+        int h = max(max(d, ii), st.prev2H[c] + sc[c]); /* (no floor; the diagonal neighbour of an in-band cell is in band, so h is finite) */
+        if constexpr (INTERIOR) {
+            const bool valid = (c + p) <= st.lim;
+            h = valid ? h : DPX_NEG;
+            d = valid ? d : DPX_NEG;
+            ii = valid ? ii : DPX_NEG;
+        } else {
+            /* slot lane * C + c against the step's window [smin, smax] and its two border slots, as compares of the constant c with
+             * per-lane values: one unsigned range compare (cnt = 0 when the window is empty) */
+            const bool valid = (unsigned)(c - lo) < (unsigned)cnt;
+            h = valid ? h : ((c == cTop || c == cLeft) ? bord : DPX_NEG);
+            d = valid ? d : DPX_NEG;
+            ii = valid ? ii : DPX_NEG;
+            if constexpr (!EXT) st.fin = (last && c == cEnd) ? h : st.fin;
+        }
+        if constexpr (EXT) st.key[c] = max(st.key[c], (int)(((unsigned)h << 16) | (unsigned)negA)); /* (after the border select: border cells take part) */
+        st.prev2H[c] = st.prevH[c];
+        st.prevH[c] = h;
+        st.prevI[c] = ii;
+        st.prevD[c] = d;
+        outH[c] = h;
+        outI[c] = ii;
+        outD[c] = d;
+    }
+}
+
+/* ---- the scan of extension mode, after every step of k_zext_fill and k_zsub_fill ---- */
+/* the signed maximum over the 64 lanes, on the VALU: row_shr 1, 2, 4, 8 bring each row's maximum to its lane 15, row_bcast:15 and
+ * row_bcast:31 carry it on to lane 63.  A lane without a source keeps INT_MIN.  All 64 lanes must be active. */
+template <int CTRL, int ROWS>
+__device__ __forceinline__ int dpp_max(const int v) {
+    return max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, CTRL, ROWS, 0xf, false));
+}
+__device__ __forceinline__ int wave_max_i32(int v) {
+    v = dpp_max<0x111, 0xf>(v);
+    v = dpp_max<0x112, 0xf>(v);
+    v = dpp_max<0x114, 0xf>(v);
+    v = dpp_max<0x118, 0xf>(v);
+    v = dpp_max<0x142, 0xa>(v);
+    v = dpp_max<0x143, 0xc>(v);
+    return __builtin_amdgcn_readlane(v, 63);
+}
+
+/* the scan's update-or-drop rule for one non-empty anti-diagonal whose maximum dm sits at (ia, ja); true = the pair is dropped here */
+__device__ __forceinline__ bool zdrop_test(const int dm, const int ia, const int ja, const int Z, const int pen, int &best, int &bi, int &bj) {
+    if (dm > best) {
+        best = dm;
+        bi = ia;
+        bj = ja;
+        return false;
+    }
+    return ia >= bi && ja >= bj && best - dm > Z + pen * abs((ia - bi) - (ja - bj));
+}
+
+/* the pair's results from lane 0: the record into ext, and the chosen score and end cell where BAXT's go (E: the end bonus) */
+__device__ __forceinline__ void write_results(const dpx_fill_args &f, const int E, int32_t *ext, const int p, const int m, const int maxScore, const int maxRow,
+                                              const int maxCol, const int qeScore, const int qeCol, const int lastDiag, const bool dropped) {
+    const bool reached = E >= 0 && !dropped && qeCol >= 0 && qeScore + E > maxScore;
+    f.score[p] = reached ? qeScore : maxScore;
+    f.endRow[p] = reached ? m : maxRow;
+    f.endCol[p] = reached ? qeCol : maxCol;
+    u32x4 *rec = reinterpret_cast<u32x4 *>(ext + (size_t)p * 8u);
+    const u32x4 w0 = {(unsigned)maxScore, (unsigned)maxRow, (unsigned)maxCol, (unsigned)qeScore};
+    const u32x4 w1 = {(unsigned)qeCol, (unsigned)lastDiag, (dropped ? 1u : 0u) | (reached ? 2u : 0u), 0u};
+    rec[0] = w0;
+    rec[1] = w1;
+}
+
+/* an empty sequence (m <= 0 or n <= 0), on one lane: the in-band cells are one border line, cell k (1 <= k <= L = min(max(m, n), B-1))
+ * on anti-diagonal k with H = o + k*e, and 0 at k = 0.  The scan, the maximum and the row-m rule run over it; no diagonal step, so a
+ * substitution table plays no part. */
+template <bool ZDROP>
+__device__ __forceinline__ void scan_border_line(const dpx_fill_args &f, const int E, int32_t *ext, const int p, const int m, const int n, const int B, const int o, const int e,
+                                                 const int Z, const int pen) {
+    const int len = max(max(m, n), 0), L = min(len, B - 1);
+    int best = 0, kb = 0, last = len, maxScore = 0, kmax = 0;
+    bool dropped = false;
+    for (int k = 1; k <= L; k++) {
+        const int v = o + k * e;
+        if (v > best) {
+            best = v;
+            kb = k;
+        } else if (ZDROP && best - v > Z + pen * (k - kb)) {
+            last = k;
+            dropped = true;
+            break;
+        }
+    }
+    const int seen = min(L, last); /* the computed cells are k = 0 .. seen */
+    for (int k = 1; k <= seen; k++)
+        if (o + k * e > maxScore) { maxScore = o + k * e; kmax = k; }
+    int qeScore = INT_MIN, qeCol = -1;
+    if (m <= 0) { /* row m is row 0: the line itself (or the single cell (0, 0)) */
+        qeScore = 0;
+        qeCol = 0;
+        for (int k = 1; k <= (n > 0 ? seen : 0); k++)
+            if (o + k * e > qeScore) { qeScore = o + k * e; qeCol = k; }
+    } else if (m <= seen) { /* n == 0: row m holds the one cell (m, 0) */
+        qeScore = o + m * e;
+        qeCol = 0;
+    }
+    write_results(f, E, ext, p, max(m, 0), maxScore, m > 0 ? kmax : 0, m > 0 ? 0 : kmax, qeScore, qeCol, last, dropped);
+}
+
+/* after step A_ (h_: its C values of H): the row-m pick-up into qe, then (ZDROP) the anti-diagonal's maximum and the drop test, which
+ * sets lastDiag and stop.  The rules are explained at the top of dpx_zext_kernels.hip.  A macro over the kernel's own names (C, ZDROP, m,
+ * n, B, Z, pen, lane, the step's i0, and the scan state qe, best, bi, bj, lastDiag, stop), not a function: as a function taking the state
+ * by reference the same text compiled k_zext_fill<2, ., true, true> to 83 VGPRs instead of 64, from 8 waves per SIMD to 5. */
+#define DPX_BAND_SCAN_AFTER(A_, h_)                                                                                       \
+    {                                                                                                                     \
+        const int a_ = (A_) + 2;                                                                                          \
+        if (a_ >= m && a_ - m <= n && abs(2 * m - a_) <= B - 1) {                                                         \
+            const int sm_ = m - i0, ln_ = sm_ / C, cc_ = sm_ % C; /* (0 <= sm_ <= B-1: the cell is in the band) */          \
+            int v_ = 0;                                                                                                   \
+            _Pragma("unroll") for (int c = 0; c < C; c++)                                                                 \
+                if (cc_ == c) v_ = __builtin_amdgcn_readlane((h_)[c], ln_);                                               \
+            qe = max(qe, (int)(((unsigned)v_ << 16) | (0xFFFFu - (unsigned)(a_ - 1))));                                   \
+        }                                                                                                                 \
+        if constexpr (ZDROP) {                                                                                            \
+            const int rb_ = 0xFFFF - i0 - lane * C;                                                                       \
+            int k_ = INT_MIN;                                                                                             \
+            _Pragma("unroll") for (int c = 0; c < C; c++) k_ = max(k_, (int)pack_lo16(rb_ - c, max((h_)[c], -32768)));    \
+            k_ = wave_max_i32(k_);                                                                                        \
+            const int dm_ = k_ >> 16;                                                                                     \
+            if (dm_ > -32768) { /* (else: no cell on this anti-diagonal) */                                               \
+                const int ia_ = 0xFFFF - (k_ & 0xFFFF);                                                                   \
+                if (zdrop_test(dm_, ia_, a_ - ia_, Z, pen, best, bi, bj)) {                                               \
+                    lastDiag = a_;                                                                                        \
+                    stop = true;                                                                                          \
+                }                                                                                                         \
+            }                                                                                                             \
+        }                                                                                                                 \
+    }
+
+/* after the loops: the maximum of H over the computed cells and its first cell in row-major order, as k_baxt_fill finds it: every
+ * slot's first maximum (within a slot cells arrive in row-major order); across slots max score, min row, min col.  The border cells of
+ * anti-diagonal 1 need no candidate: they count only when o + e > 0, and then the pair cannot drop at anti-diagonal 1, so (1, 1)
+ * is computed and holds H >= 2 * (o + e) > o + e.  Then the record, from lane 0. */
+template <int C>
+__device__ __forceinline__ void scan_finish(const dpx_fill_args &f, const int E, int32_t *ext, const int p, const int *key, const int lane, const int m, const int B, const int qe,
+                                            const int lastDiag, const bool stop) {
+    unsigned long long mine = 0ull;
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+        const int hv = key[c] >> 16;
+        if (hv > 0) {
+            const int A = 0xFFFF - (key[c] & 0xFFFF);
+            const int aa = A + 2;
+            const int pp = (aa + B - 1) & 1;
+            const int u = 2 * (lane * C + c) + pp;
+            const int i = (aa + u - (B - 1)) >> 1;
+            const int j = aa - i;
+            const unsigned long long k = end_key(hv, i, j);
+            mine = k > mine ? k : mine;
+        }
+    }
+    const unsigned long long top = wave_max_u64(mine);
+    const int qeTop = qe;
+    if (lane == 0) {
+        const int hv = (int)(top >> 40);
+        const int maxRow = hv > 0 ? (int)(0xFFFFFu - (unsigned)((top >> 20) & 0xFFFFFu)) : 0;
+        const int maxCol = hv > 0 ? (int)(0xFFFFFu - (unsigned)(top & 0xFFFFFu)) : 0;
+        const bool none = qeTop == INT_MIN;
+        const int qeScore = none ? INT_MIN : (qeTop >> 16);
+        const int qeCol = none ? -1 : (0xFFFF - (qeTop & 0xFFFF)) + 1 - m;
+        write_results(f, E, ext, p, m, hv, maxRow, maxCol, qeScore, qeCol, lastDiag, stop);
     }
 }
 

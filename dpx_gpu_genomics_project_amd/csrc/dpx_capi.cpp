@@ -504,7 +504,7 @@ struct dpx_batch : dpx_plan {
     uint64_t cigarOps = 0;     /* total number of ops (state 2) */
     /* BAXT's extension mode (dpx_batch_set_extension): the next fill runs k_zext_fill while either value is >= 0 */
     int32_t zdrop = -1, endBonus = -1;
-    bool extFilled = false;    /* the last fill ran k_zext_fill: dExt holds its records and dpx_batch_matrix masks behind lastDiag */
+    bool extFilled = false;    /* the last fill ran k_zext_fill / k_zsub_fill: dExt holds its records and dpx_batch_matrix masks behind lastDiag */
     int32_t *dExt = nullptr;   /* device: dpx_extension[numPairs] */
     size_t dExtCap = 0;
     /* substitution table (dpx_batch_set_substitution): while substAlphabet > 0 the fills run k_subst_fill and the walks k_subst_traceback* */
@@ -1043,7 +1043,11 @@ static size_t subst_lds_bytes(const dpx_batch *b) { return b->ldsBytes + (size_t
 
 static hipError_t launch_main(dpx_batch *b, hipStream_t s) { /* the one-wave-per-pair kernel of the batch's algorithm */
     if (b->bandDirs) return dpx_launch_bdir_fill(b->args, b->R, b->kernelAlgo == DPX_ALGO_BAXT, s);
-    if (b->substAlphabet) /* (set only on batches whose kernel is BANW's or BAXT's, extension mode off) */
+    if (b->substAlphabet && extension_on(b)) { /* (both at once: dpx_batch_set_extension_table, BAXT only) */
+        const dpx_zsub_args za = {subst_args(b), b->zdrop, b->endBonus, b->dExt};
+        return dpx_launch_zsub_fill(za, b->R, b->store, subst_lds_bytes(b), s);
+    }
+    if (b->substAlphabet) /* (set only on batches whose kernel is BANW's or BAXT's) */
         return dpx_launch_subst_fill(subst_args(b), b->R, b->store, b->kernelAlgo == DPX_ALGO_BAXT, subst_lds_bytes(b), s);
     if (b->kernelAlgo == DPX_ALGO_BASW) return dpx_launch_basw_fill(b->args, b->R, b->store, b->ldsBytes, s);
     if (b->kernelAlgo == DPX_ALGO_BANW) return dpx_launch_banw_fill(b->args, b->R, b->store, b->ldsBytes, s);
@@ -1276,7 +1280,7 @@ int dpx_batch_matrix(dpx_batch *b, size_t pair, int which, int16_t *out) {
     if (e == hipSuccess && b->extFilled) e = hipMemcpy(&rec, b->dExt + pair * (sizeof rec / sizeof(int32_t)), sizeof rec, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail(e, "dpx_batch_matrix");
     if (b->extFilled && rec.lastDiag < pd.m + pd.n) {
-        /* a z-dropped pair: k_zext_fill stopped on anti-diagonal lastDiag, and what the pool holds behind it is whatever was there before */
+        /* a z-dropped pair: k_zext_fill / k_zsub_fill stopped on anti-diagonal lastDiag, and what the pool holds behind it is whatever was there before */
         for (int i = 0; i <= pd.m; i++)
             for (int j = std::max(rec.lastDiag - i + 1, 0); j <= pd.n; j++) out[(size_t)i * (size_t)(pd.n + 1) + (size_t)j] = 0;
     }
@@ -1287,7 +1291,7 @@ int dpx_batch_set_extension(dpx_batch *b, int32_t zdrop, int32_t endBonus) {
     if (!b || zdrop < -1 || zdrop > (1 << 30) || endBonus < -1 || endBonus > (1 << 30)) return DPX_ERR_INVALID;
     if (b->prm.algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED;
     if (b->bandDirs) return DPX_ERR_UNSUPPORTED; /* extension mode on a band-direction batch: not built */
-    if ((zdrop >= 0 || endBonus >= 0) && b->substAlphabet) return DPX_ERR_UNSUPPORTED; /* extension mode under a substitution table: not built */
+    if ((zdrop >= 0 || endBonus >= 0) && b->substAlphabet) return DPX_ERR_UNSUPPORTED; /* (the two go together through dpx_batch_set_extension_table only) */
     int rc = bind_device(b->device);
     if (rc != DPX_OK) return rc;
     if ((zdrop >= 0 || endBonus >= 0) && !b->dExt && b->numPairs)
@@ -1297,29 +1301,31 @@ int dpx_batch_set_extension(dpx_batch *b, int32_t zdrop, int32_t endBonus) {
     return DPX_OK;
 }
 
-int dpx_batch_set_substitution(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf) {
-    if (!b) return DPX_ERR_INVALID;
-    auto invalidate = [&]() { /* what a refill does to lines, text and CIGARs; the results go with them until the next fill */
-        b->filled = false; b->extFilled = false; b->tbLinesValid = false; b->outState = 0; b->cigarState = 0;
-    };
-    if (!scores) { /* clear: the batch runs its plain kernel again */
-        if (b->substAlphabet) invalidate();
-        b->substAlphabet = 0;
-        return DPX_OK;
-    }
+/* what a refill does to lines, text and CIGARs; the results go with them until the next fill */
+static void invalidate_fill(dpx_batch *b) {
+    b->filled = false; b->extFilled = false; b->tbLinesValid = false; b->outState = 0; b->cigarState = 0;
+}
+
+/* dpx_batch_set_substitution's checks of a table for this batch, all of them: nothing is changed */
+static int check_substitution(const dpx_batch *b, int32_t alphabet, const uint8_t *codeOf) {
     if (alphabet < 1 || alphabet > 32 || !codeOf) return DPX_ERR_INVALID;
     for (int x = 0; x < 256; x++) if ((int)codeOf[x] >= alphabet) return DPX_ERR_INVALID;
     if (b->prm.algo != DPX_ALGO_BANW && b->prm.algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED;
     if (b->kernelAlgo != b->prm.algo || b->dirs || b->bandDirs) return DPX_ERR_UNSUPPORTED; /* (band directions: not built;) a covering BANW band runs as ANW, which has no table kernel */
-    if (extension_on(b)) return DPX_ERR_UNSUPPORTED;
+    return DPX_OK;
+}
+static int check_substitution_fit(const dpx_batch *b, const int8_t *scores, int32_t alphabet) {
     if (subst_lds_bytes(b) > 160u * 1024u) return DPX_ERR_UNSUPPORTED; /* the table image no longer fits beside the staged strings */
     /* fits_int16's BANW / BAXT bounds with the largest entry in place of match and the smallest in place of mismatch */
     dpx_params q = b->prm;
     q.match = -128; q.mismatch = 127;
     for (int k = 0; k < alphabet * alphabet; k++) { q.match = std::max<int32_t>(q.match, scores[k]); q.mismatch = std::min<int32_t>(q.mismatch, scores[k]); }
     for (const dpx_pair_dev &pd : b->pairs) if (!fits_int16(q, pd.m, pd.n)) return DPX_ERR_RANGE;
-    int rc = bind_device(b->device);
-    if (rc != DPX_OK) return rc;
+    return DPX_OK;
+}
+
+/* the checked table becomes the batch's (the image of dpx_kernels.h: rows of 32, the map behind them) */
+static int upload_substitution(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf) {
     unsigned char image[DPX_SUBST_IMAGE_BYTES];
     memset(image, 0, sizeof image);
     for (int r = 0; r < alphabet; r++) memcpy(image + r * 32, scores + r * alphabet, (size_t)alphabet);
@@ -1330,7 +1336,42 @@ int dpx_batch_set_substitution(dpx_batch *b, const int8_t *scores, int32_t alpha
     HIP_TRY(hipStreamSynchronize(b->stream));
     HIP_TRY(hipMemcpy(b->dSubst, image, sizeof image, hipMemcpyHostToDevice));
     b->substAlphabet = alphabet;
-    invalidate();
+    invalidate_fill(b);
+    return DPX_OK;
+}
+
+int dpx_batch_set_substitution(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf) {
+    if (!b) return DPX_ERR_INVALID;
+    if (!scores) { /* clear: the batch runs its plain kernel again */
+        if (b->substAlphabet) invalidate_fill(b);
+        b->substAlphabet = 0;
+        return DPX_OK;
+    }
+    int rc = check_substitution(b, alphabet, codeOf);
+    if (rc != DPX_OK) return rc;
+    if (extension_on(b)) return DPX_ERR_UNSUPPORTED;
+    rc = check_substitution_fit(b, scores, alphabet);
+    if (rc != DPX_OK) return rc;
+    rc = bind_device(b->device);
+    if (rc != DPX_OK) return rc;
+    return upload_substitution(b, scores, alphabet, codeOf);
+}
+
+/* both settings at once, the one way to have both: every check of either comes before the first change */
+int dpx_batch_set_extension_table(dpx_batch *b, int32_t zdrop, int32_t endBonus, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf) {
+    if (!b || !scores || !codeOf) return DPX_ERR_INVALID;
+    if (zdrop < -1 || zdrop > (1 << 30) || endBonus < -1 || endBonus > (1 << 30) || (zdrop < 0 && endBonus < 0)) return DPX_ERR_INVALID;
+    int rc = check_substitution(b, alphabet, codeOf); /* (refuses band-direction batches, where neither setting is built) */
+    if (rc == DPX_OK && b->prm.algo != DPX_ALGO_BAXT) rc = DPX_ERR_UNSUPPORTED;
+    if (rc == DPX_OK) rc = check_substitution_fit(b, scores, alphabet);
+    if (rc != DPX_OK) return rc;
+    rc = bind_device(b->device);
+    if (rc != DPX_OK) return rc;
+    if (!b->dExt && b->numPairs) HIP_TRY(g_tbDevCache.take((void **)&b->dExt, b->numPairs * sizeof(dpx_extension), &b->dExtCap));
+    rc = upload_substitution(b, scores, alphabet, codeOf);
+    if (rc != DPX_OK) return rc;
+    b->zdrop = zdrop;
+    b->endBonus = endBonus;
     return DPX_OK;
 }
 

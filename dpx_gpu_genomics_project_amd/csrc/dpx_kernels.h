@@ -102,6 +102,15 @@ typedef struct dpx_subst_args {
 hipError_t dpx_launch_subst_fill(const dpx_subst_args &a, int C, bool store, bool ext, size_t ldsBytes, hipStream_t stream);
 hipError_t dpx_launch_subst_traceback(const dpx_subst_args &a, int numPairs, int walk, const uint64_t *tbOff, char *tb, int32_t *tbLen,
                                       hipStream_t stream);
+/* BAXT in extension mode under a substitution table (dpx_zsub_kernels.hip, k_zsub_fill; dpx_batch_set_extension_table): k_subst_fill's
+ * cells with k_zext_fill's scan and results.  `s` is what dpx_launch_subst_fill takes (LDS sizes include the table image), zdrop /
+ * endBonus / ext are dpx_zext_args'.  The walks are dpx_launch_subst_traceback's, the export is dpx_launch_banw_export. */
+typedef struct dpx_zsub_args {
+    dpx_subst_args s;
+    int32_t zdrop, endBonus;
+    int32_t *ext;
+} dpx_zsub_args;
+hipError_t dpx_launch_zsub_fill(const dpx_zsub_args &a, int C, bool store, size_t ldsBytes, hipStream_t stream);
 hipError_t dpx_launch_unpack2(const uint32_t *packed, uint32_t alphabet, char *out, size_t numDwords, hipStream_t stream);
 hipError_t dpx_launch_prim_eval(const int32_t *op, const uint32_t *a, const uint32_t *b, const uint32_t *c, size_t count,
                                 uint32_t *res, uint32_t *pred, hipStream_t stream);

@@ -657,7 +657,7 @@ int dpx_plan_describe(const dpx_plan &b, int tbWalk, int zdrop, int endBonus, in
                          : b.kernelAlgo == DPX_ALGO_ASG ? (b.lanePacked ? "k_asg_lanes" : "k_asg_fill")
                          : b.packed ? "k_linear_fill_pk" : b.lanesPk ? "k_linear_lanes_pk" : b.lanePacked ? "k_linear_lanes" : b.split ? "k_linear_split" : "k_linear_fill";
     if (b.kernelAlgo == DPX_ALGO_BAXT && extension) kernel = "k_zext_fill";
-    if (substAlphabet) kernel = "k_subst_fill";
+    if (substAlphabet) kernel = (b.kernelAlgo == DPX_ALGO_BAXT && extension) ? "k_zsub_fill" : "k_subst_fill";
     if (b.bandDirs) kernel = "k_bdir_fill";
     if (b.dirs) kernel = b.kernelAlgo == DPX_ALGO_ANW ? "k_affine_dir" : b.kernelAlgo == DPX_ALGO_ASW ? "k_asw_dir" : b.kernelAlgo == DPX_ALGO_ASG ? "k_asg_dir" : "k_linear_dir";
     /* dtype = the arithmetic type of the kernel that fills (most of) the batch */

@@ -12,6 +12,7 @@
  * and the window registers hold codes, not bytes: the query code as it is, the reference code as code << 5.  A cell's score is then one
  * address add and one signed-byte LDS read where the plain kernels have a compare and a select.  The text is produced by the walks from
  * the sequence bytes, so nothing downstream sees the codes.
+ * The step itself, subst_step with its SubstState, lives in dpx_band_affine.hpp: k_zsub_fill (dpx_zsub_kernels.hip) runs the same text.
  *
  * The walks are BANW's two (one lane per pair; one wave per pair with an LDS window), the same templates under TableScorer
  * (dpx_band_affine.hpp: band_walk_lane, band_walk_wave), with mm = H_diag + s(r, q); the relation character
@@ -23,99 +24,6 @@
 namespace {
 
 using namespace dpx_band;
-
-template <int C, bool EXT>
-struct SubstState {
-    int prevH[C], prev2H[C]; /* H on anti-diagonals a-1 and a-2 */
-    int prevI[C], prevD[C];  /* I and D on anti-diagonal a-1 */
-    int qcd[C], rcd[C];      /* query code / reference code << 5 of each slot's cell */
-    int key[EXT ? C : 1];    /* EXT: running signed max of (H << 16 | 0xFFFF - A): max score, then earliest step */
-    int lim;                 /* B-1 - lane*C: slot c is inside the band on a step of parity p when c + p <= lim */
-    int fin;                 /* !EXT: H[m][n], picked up on the last anti-diagonal by the lane that owns its slot */
-};
-
-/* banw_step / slot_key_step with the table lookup.  INTERIOR: every in-band slot of this anti-diagonal lies inside the matrix, so validity
- * is one compare against the per-lane constant `lim`; no border slot and (!EXT) not the last anti-diagonal */
-template <int C, bool P1, bool INTERIOR, bool EXT>
-__device__ __forceinline__ void subst_step(SubstState<C, EXT> &st, const int A, int &i0, int &j0, const int lane, const int m, const int n,
-                                           const int B, const int o, const int oe, const int e, const int cEnd, const unsigned char *qL,
-                                           const unsigned char *rL, const signed char *tabL, const unsigned char *codeL, int *outH,
-                                           int *outI, int *outD) {
-    const int p = P1 ? 1 : 0;
-    if constexpr (P1) i0++; else j0++;
-    const int smin = INTERIOR ? 0 : max(max(1 - i0, j0 - n), 0);
-    const int smax = INTERIOR ? 0 : min(min(m - i0, j0 - 1), B - 1 - p);
-    /* the in-band border cells of this anti-diagonal: (0, a) in slot -i0 and (a, 0) in slot j0, both H = o + a * e, while a <= B-1 */
-    const int a = A + 2;
-    const int bord = (INTERIOR || a > B - 1) ? DPX_NEG : o + a * e;
-    const int sTop = (INTERIOR || a > n) ? -1 : -i0, sLeft = (INTERIOR || a > m) ? -1 : j0;
-    const int lo = smin - lane * C, cnt = max(smax - smin + 1, 0), cTop = sTop - lane * C, cLeft = sLeft - lane * C;
-    const bool last = !EXT && !INTERIOR && a == m + n;
-    int upH[C], upD[C], leftH[C], leftI[C];
-    if constexpr (P1) {
-        const int newq = codeL[INTERIOR ? qL[i0 + 64 * C - 2] : qL[min(max(i0 + 64 * C - 2, 0), m - 1)]];
-        const int tq = wave_shl1(st.qcd[0], newq);
-#pragma unroll
-        for (int c = 0; c < C - 1; c++) st.qcd[c] = st.qcd[c + 1];
-        st.qcd[C - 1] = tq;
-        const int nbH = wave_shl1(st.prevH[0], DPX_NEG);
-        const int nbI = wave_shl1(st.prevI[0], DPX_NEG);
-#pragma unroll
-        for (int c = 0; c < C; c++) {
-            upH[c] = st.prevH[c];
-            upD[c] = st.prevD[c];
-            leftH[c] = (c < C - 1) ? st.prevH[c + 1] : nbH;
-            leftI[c] = (c < C - 1) ? st.prevI[c + 1] : nbI;
-        }
-    } else {
-        const int newr = (int)codeL[INTERIOR ? rL[j0 - 1] : rL[min(max(j0 - 1, 0), n - 1)]] << 5;
-        const int tr = wave_shr1(st.rcd[C - 1], newr);
-#pragma unroll
-        for (int c = C - 1; c > 0; c--) st.rcd[c] = st.rcd[c - 1];
-        st.rcd[0] = tr;
-        const int nbH = wave_shr1(st.prevH[C - 1], DPX_NEG);
-        const int nbD = wave_shr1(st.prevD[C - 1], DPX_NEG);
-#pragma unroll
-        for (int c = 0; c < C; c++) {
-            leftH[c] = st.prevH[c];
-            leftI[c] = st.prevI[c];
-            upH[c] = (c > 0) ? st.prevH[c - 1] : nbH;
-            upD[c] = (c > 0) ? st.prevD[c - 1] : nbD;
-        }
-    }
-    int sc[C]; /* all C byte reads are in flight before the first is used (codes are < 32: the address stays inside the 1-KiB table) */
-#pragma unroll
-    for (int c = 0; c < C; c++) sc[c] = (int)tabL[st.rcd[c] + st.qcd[c]];
-    const int negA = 0xFFFF - A;
-#pragma unroll
-    for (int c = 0; c < C; c++) {
-        int d = max(upH[c] + oe, upD[c] + e);
-        int ii = max(leftH[c] + oe, leftI[c] + e);
-        int h = max(max(d, ii), st.prev2H[c] + sc[c]); /* (no floor; the diagonal neighbour of an in-band cell is in band, so h is finite) */
-        if constexpr (INTERIOR) {
-            const bool valid = (c + p) <= st.lim;
-            h = valid ? h : DPX_NEG;
-            d = valid ? d : DPX_NEG;
-            ii = valid ? ii : DPX_NEG;
-        } else {
-            /* slot lane * C + c against the step's window [smin, smax] and its two border slots, as compares of the constant c with
-             * per-lane values: one unsigned range compare (cnt = 0 when the window is empty) */
-            const bool valid = (unsigned)(c - lo) < (unsigned)cnt;
-            h = valid ? h : ((c == cTop || c == cLeft) ? bord : DPX_NEG);
-            d = valid ? d : DPX_NEG;
-            ii = valid ? ii : DPX_NEG;
-            if constexpr (!EXT) st.fin = (last && c == cEnd) ? h : st.fin;
-        }
-        if constexpr (EXT) st.key[c] = max(st.key[c], (int)(((unsigned)h << 16) | (unsigned)negA)); /* (after the border select: border cells take part) */
-        st.prev2H[c] = st.prevH[c];
-        st.prevH[c] = h;
-        st.prevI[c] = ii;
-        st.prevD[c] = d;
-        outH[c] = h;
-        outI[c] = ii;
-        outD[c] = d;
-    }
-}
 
 template <int C, bool PB, bool STORE, bool EXT>
 __global__ void __launch_bounds__(DPX_FILL_THREADS) k_subst_fill(const dpx_subst_args sa) {

@@ -21,56 +21,15 @@
  * On a drop the wave leaves the loop, stores its partial group (the steps of the group it did not run keep the previous group's
  * values, or zeros: they lie behind lastDiag and the host never shows them), writes its results and returns; the waves of a workgroup
  * share no barrier.  Nothing is stored past the pair's last chunk: a dropped pair stores a prefix of what k_baxt_fill stores.
+ *
+ * The scan's pieces (wave_max_i32, zdrop_test, write_results, the border-line scan of an empty sequence, the after-step and the final
+ * reduction) live in dpx_band_affine.hpp: k_zsub_fill (dpx_zsub_kernels.hip) runs the same text under a substitution table.
  */
-#include <limits.h>
-
 #include "dpx_band_affine.hpp"
 
 namespace {
 
 using namespace dpx_band;
-
-/* the signed maximum over the 64 lanes, on the VALU: row_shr 1, 2, 4, 8 bring each row's maximum to its lane 15, row_bcast:15 and
- * row_bcast:31 carry it on to lane 63.  A lane without a source keeps INT_MIN.  All 64 lanes must be active. */
-template <int CTRL, int ROWS>
-__device__ __forceinline__ int dpp_max(const int v) {
-    return max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, CTRL, ROWS, 0xf, false));
-}
-__device__ __forceinline__ int wave_max_i32(int v) {
-    v = dpp_max<0x111, 0xf>(v);
-    v = dpp_max<0x112, 0xf>(v);
-    v = dpp_max<0x114, 0xf>(v);
-    v = dpp_max<0x118, 0xf>(v);
-    v = dpp_max<0x142, 0xa>(v);
-    v = dpp_max<0x143, 0xc>(v);
-    return __builtin_amdgcn_readlane(v, 63);
-}
-
-/* the scan's update-or-drop rule for one non-empty anti-diagonal whose maximum dm sits at (ia, ja); true = the pair is dropped here */
-__device__ __forceinline__ bool zdrop_test(const int dm, const int ia, const int ja, const int Z, const int pen, int &best, int &bi, int &bj) {
-    if (dm > best) {
-        best = dm;
-        bi = ia;
-        bj = ja;
-        return false;
-    }
-    return ia >= bi && ja >= bj && best - dm > Z + pen * abs((ia - bi) - (ja - bj));
-}
-
-/* the pair's results from lane 0: the record, and the chosen score and end cell where BAXT's go */
-__device__ __forceinline__ void write_results(const dpx_zext_args &a, const int p, const int m, const int maxScore, const int maxRow,
-                                              const int maxCol, const int qeScore, const int qeCol, const int lastDiag, const bool dropped) {
-    const int E = a.endBonus;
-    const bool reached = E >= 0 && !dropped && qeCol >= 0 && qeScore + E > maxScore;
-    a.f.score[p] = reached ? qeScore : maxScore;
-    a.f.endRow[p] = reached ? m : maxRow;
-    a.f.endCol[p] = reached ? qeCol : maxCol;
-    u32x4 *rec = reinterpret_cast<u32x4 *>(a.ext + (size_t)p * 8u);
-    const u32x4 w0 = {(unsigned)maxScore, (unsigned)maxRow, (unsigned)maxCol, (unsigned)qeScore};
-    const u32x4 w1 = {(unsigned)qeCol, (unsigned)lastDiag, (dropped ? 1u : 0u) | (reached ? 2u : 0u), 0u};
-    rec[0] = w0;
-    rec[1] = w1;
-}
 
 template <int C, bool PB, bool STORE, bool ZDROP>
 __global__ void __launch_bounds__(DPX_FILL_THREADS) k_zext_fill(const dpx_zext_args a) {
@@ -87,38 +46,7 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_zext_fill(const dpx_zext_a
     const int match = a.f.match, mismatch = a.f.mismatch, o = a.f.gapOpen, e = a.f.gapExtend, oe = a.f.gapOpen + a.f.gapExtend;
     const int Z = a.zdrop, pen = e < 0 ? -e : 0;
     if (m <= 0 || n <= 0) {
-        /* an empty sequence: the in-band cells are one border line, cell k (1 <= k <= L = min(max(m, n), B-1)) on anti-diagonal k with
-         * H = o + k*e, and 0 at k = 0.  The scan, the maximum and the row-m rule run over it on lane 0. */
-        if (lane == 0) {
-            const int len = max(max(m, n), 0), L = min(len, B - 1);
-            int best = 0, kb = 0, last = len, maxScore = 0, kmax = 0;
-            bool dropped = false;
-            for (int k = 1; k <= L; k++) {
-                const int v = o + k * e;
-                if (v > best) {
-                    best = v;
-                    kb = k;
-                } else if (ZDROP && best - v > Z + pen * (k - kb)) {
-                    last = k;
-                    dropped = true;
-                    break;
-                }
-            }
-            const int seen = min(L, last); /* the computed cells are k = 0 .. seen */
-            for (int k = 1; k <= seen; k++)
-                if (o + k * e > maxScore) { maxScore = o + k * e; kmax = k; }
-            int qeScore = INT_MIN, qeCol = -1;
-            if (m <= 0) { /* row m is row 0: the line itself (or the single cell (0, 0)) */
-                qeScore = 0;
-                qeCol = 0;
-                for (int k = 1; k <= (n > 0 ? seen : 0); k++)
-                    if (o + k * e > qeScore) { qeScore = o + k * e; qeCol = k; }
-            } else if (m <= seen) { /* n == 0: row m holds the one cell (m, 0) */
-                qeScore = o + m * e;
-                qeCol = 0;
-            }
-            write_results(a, p, max(m, 0), maxScore, m > 0 ? kmax : 0, m > 0 ? 0 : kmax, qeScore, qeCol, last, dropped);
-        }
+        if (lane == 0) scan_border_line<ZDROP>(a.f, a.endBonus, a.ext, p, m, n, B, o, e, Z, pen); /* an empty sequence: one border line */
         return;
     }
     const unsigned char *ref = reinterpret_cast<const unsigned char *>(a.f.seq + pr.refIdx);
@@ -179,31 +107,7 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_zext_fill(const dpx_zext_a
         store8(at_ + 2 * DPX_BAND_PLANE_ELEMS, accD);                                                                     \
     }
     /* after step A_ (i0, j0 are the step's): the row-m pick-up, then the anti-diagonal's maximum and the drop test */
-#define DPX_ZEXT_AFTER(A_, h_)                                                                                            \
-    {                                                                                                                     \
-        const int a_ = (A_) + 2;                                                                                          \
-        if (a_ >= m && a_ - m <= n && abs(2 * m - a_) <= B - 1) {                                                         \
-            const int sm_ = m - i0, ln_ = sm_ / C, cc_ = sm_ % C; /* (0 <= sm_ <= B-1: the cell is in the band) */          \
-            int v_ = 0;                                                                                                   \
-            _Pragma("unroll") for (int c = 0; c < C; c++)                                                                 \
-                if (cc_ == c) v_ = __builtin_amdgcn_readlane((h_)[c], ln_);                                               \
-            qe = max(qe, (int)(((unsigned)v_ << 16) | (0xFFFFu - (unsigned)(a_ - 1))));                                   \
-        }                                                                                                                 \
-        if constexpr (ZDROP) {                                                                                            \
-            const int rb_ = 0xFFFF - i0 - lane * C;                                                                       \
-            int k_ = INT_MIN;                                                                                             \
-            _Pragma("unroll") for (int c = 0; c < C; c++) k_ = max(k_, (int)pack_lo16(rb_ - c, max((h_)[c], -32768)));    \
-            k_ = wave_max_i32(k_);                                                                                        \
-            const int dm_ = k_ >> 16;                                                                                     \
-            if (dm_ > -32768) { /* (else: no cell on this anti-diagonal) */                                               \
-                const int ia_ = 0xFFFF - (k_ & 0xFFFF);                                                                   \
-                if (zdrop_test(dm_, ia_, a_ - ia_, Z, pen, best, bi, bj)) {                                               \
-                    lastDiag = a_;                                                                                        \
-                    stop = true;                                                                                          \
-                }                                                                                                         \
-            }                                                                                                             \
-        }                                                                                                                 \
-    }
+#define DPX_ZEXT_AFTER(A_, h_) DPX_BAND_SCAN_AFTER(A_, h_)
 #define DPX_ZEXT_BODY(INTERIOR_)                                                                                          \
     _Pragma("unroll") for (int g = 0; g < GG; g += 2) {                                                                  \
         slot_key_step<C, PB, INTERIOR_>(st, A0 + g, i0, j0, lane, m, n, B, match, mismatch, o, oe, e, qL, rL,             \
@@ -240,36 +144,7 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_zext_fill(const dpx_zext_a
 #undef DPX_ZEXT_BODY
 #undef DPX_ZEXT_AFTER
 #undef DPX_ZEXT_STORE
-    /* the maximum of H over the computed cells and its first cell in row-major order, as k_baxt_fill finds it: every slot's first
-     * maximum (within a slot cells arrive in row-major order); across slots max score, min row, min col.  The border cells of
-     * anti-diagonal 1 need no candidate: they count only when o + e > 0, and then the pair cannot drop at anti-diagonal 1, so (1, 1)
-     * is computed and holds H >= 2 * (o + e) > o + e. */
-    unsigned long long mine = 0ull;
-#pragma unroll
-    for (int c = 0; c < C; c++) {
-        const int hv = st.key[c] >> 16;
-        if (hv > 0) {
-            const int A = 0xFFFF - (st.key[c] & 0xFFFF);
-            const int aa = A + 2;
-            const int pp = (aa + B - 1) & 1;
-            const int u = 2 * (lane * C + c) + pp;
-            const int i = (aa + u - (B - 1)) >> 1;
-            const int j = aa - i;
-            const unsigned long long k = end_key(hv, i, j);
-            mine = k > mine ? k : mine;
-        }
-    }
-    const unsigned long long top = wave_max_u64(mine);
-    const int qeTop = qe;
-    if (lane == 0) {
-        const int hv = (int)(top >> 40);
-        const int maxRow = hv > 0 ? (int)(0xFFFFFu - (unsigned)((top >> 20) & 0xFFFFFu)) : 0;
-        const int maxCol = hv > 0 ? (int)(0xFFFFFu - (unsigned)(top & 0xFFFFFu)) : 0;
-        const bool none = qeTop == INT_MIN;
-        const int qeScore = none ? INT_MIN : (qeTop >> 16);
-        const int qeCol = none ? -1 : (0xFFFF - (qeTop & 0xFFFF)) + 1 - m;
-        write_results(a, p, m, hv, maxRow, maxCol, qeScore, qeCol, lastDiag, stop);
-    }
+    scan_finish<C>(a.f, a.endBonus, a.ext, p, st.key, lane, m, B, qe, lastDiag, stop);
 }
 
 } // namespace

@@ -464,14 +464,50 @@ int dpx_batch_extensions(dpx_batch *b, dpx_extension *out);
  * arrays are copied at the call.  A refused call leaves the previous setting in force.
  *   DPX_ERR_INVALID      b == NULL, alphabet outside 1..32, codeOf == NULL, or a codeOf[x] >= alphabet
  *   DPX_ERR_UNSUPPORTED  an algorithm other than BANW / BAXT; a BANW batch whose band covers its matrices (it runs as ANW); a batch with
- *                        extension mode on (and dpx_batch_set_extension switching a mode on while a table is set); a batch whose staged
- *                        sequences leave no room in LDS for the table
+ *                        extension mode on (and dpx_batch_set_extension switching a mode on while a table is set: the two go together
+ *                        through dpx_batch_set_extension_table below); a batch whose staged sequences leave no room in LDS for the table
  *   DPX_ERR_RANGE        the create-time range check of BANW / BAXT fails for a pair with the largest of the alphabet^2 entries in place
  *                        of match and the smallest in place of mismatch
  * While a table is set dpx_batch_describe reports kernel=k_subst_fill, traceback=k_subst_traceback_wave / k_subst_traceback and adds
  * ` subst=<alphabet>`.  Matrix and DPX_SCORE_ONLY batches, packed2 input, dpx_batch_create_on and a caller's stream as for BAXT.  A
  * DPX_KEEP_BAND_DIRECTIONS batch: DPX_ERR_UNSUPPORTED (a follow-up), the batch is left as it was. */
 int dpx_batch_set_substitution(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf /* 256 entries */);
+
+/* ---- BAXT extension mode under a substitution table: both of the above at once ----
+ * What ksw2's extz2 takes in one call: (m, mat) with a negative N score together with zdrop and end_bonus.  The two setters above refuse
+ * each other's setting (extension mode under a table, a table in extension mode), and keep doing so; this function switches both on
+ * together.  A new exported symbol, no ABI bump and no new flag: detect it by the symbol, as the other two.  BAXT only.
+ *
+ * The definition is the conjunction of the two blocks above, nothing new:
+ *     Cells, band, borders    BAXT's under the table: the diagonal term is H[i-1][j-1] + scores[codeOf[r] * alphabet + codeOf[q]] for the
+ *                             reference byte r and the query byte q (the row is the reference code; the table need not be symmetric).
+ *                             params.match / params.mismatch are ignored.
+ *     Scan and results        extension mode's, word for word, over those cells: the scan over anti-diagonals with its update-or-drop
+ *                             rule, lastDiag, the computed cells, maxScore / (maxRow, maxCol), qryEndScore / qryEndCol, the end-bonus
+ *                             choice and the dpx_extension record.
+ *     Text                    byte equality, as under a table.
+ * zdrop, endBonus: dpx_batch_set_extension's values; scores, alphabet, codeOf: dpx_batch_set_substitution's (copied at the call).
+ *   DPX_ERR_INVALID      b == NULL; scores == NULL or codeOf == NULL; alphabet outside 1..32; a codeOf[x] >= alphabet; zdrop or endBonus
+ *                        below -1 or above 1 << 30; both zdrop and endBonus -1 (nothing to combine: dpx_batch_set_substitution does that)
+ *   DPX_ERR_UNSUPPORTED  an algorithm other than BAXT; a DPX_KEEP_BAND_DIRECTIONS batch (a follow-up); a batch whose staged sequences
+ *                        leave no room in LDS for the table
+ *   DPX_ERR_RANGE        dpx_batch_set_substitution's range check fails
+ * A refused call leaves both settings of the batch as they were.  Legal in any state; it replaces both settings, applies to every
+ * following fill and, as dpx_batch_set_substitution, invalidates lines, text, CIGARs and results of an earlier fill
+ * (DPX_ERR_NOT_FILLED until the next one, dpx_batch_extensions included).
+ * While both are on: the fill runs k_zsub_fill, the walks are k_subst_traceback_wave / k_subst_traceback from the chosen end cell,
+ * dpx_batch_describe reports kernel=k_zsub_fill with ` zdrop=`, ` end_bonus=` and ` subst=`, dpx_batch_extensions returns the records,
+ * dpx_batch_matrix is BAXT's export with every plane 0 where i + j > lastDiag, and dpx_batch_results, the text pipeline and
+ * dpx_batch_cigars_* see the chosen score and end.  Matrix and DPX_SCORE_ONLY batches, packed2 input, dpx_batch_create_on, a caller's
+ * stream, DPX_TIME_FILLS and repeated fills as for BAXT.
+ * The two setters keep every behaviour they have, on such a batch too:
+ *     dpx_batch_set_extension(b, -1, -1)        switches the mode off and keeps the table: the next fill runs k_subst_fill
+ *     dpx_batch_set_substitution(b, NULL, ...)  clears the table and keeps the mode: the next fill runs k_zext_fill
+ *     dpx_batch_set_extension with a value >= 0 while a table is set, dpx_batch_set_substitution with a table while the mode is on:
+ *                                               DPX_ERR_UNSUPPORTED, as ever
+ * To change Z, E or the table of a combined batch, call this function again. */
+int dpx_batch_set_extension_table(dpx_batch *b, int32_t zdrop, int32_t endBonus,
+                                  const int8_t *scores, int32_t alphabet, const uint8_t *codeOf /* 256 entries */);
 
 /* Sizes: numPairs, total cells (sum refLen*queryLen, the reference's numCells, c++/parseInput.cpp:100),
  * bytes of HBM the matrices occupy, algorithmic bytes of one fill. */
