@@ -684,7 +684,8 @@ static float time_memset(void *p, size_t bytes, hipStream_t s) {
     return best;
 }
 
-static hipError_t launch_all(dpx_batch *b, hipStream_t s);
+static dpx_route route_of(const dpx_batch *b);
+static hipError_t launch_all(dpx_batch *b, const dpx_route &r, hipStream_t s);
 
 /* DPX_TUNE_PLACEMENT (callers that fill a resident batch many times: bench.py, iterative drivers).  The same fill runs up to
  * 27 % apart on two pools of the same construction (ANW 1000 x 1024^2: 1.05 vs 1.20 ms, alternating from one allocation to the
@@ -709,11 +710,12 @@ static void shop_pool_by_fill(dpx_batch *b, PoolRecord &rec, PhaseTrace &trace) 
             b->dirArgs.scratch = b->dirScratch ? reinterpret_cast<unsigned char *>(p) + b->matElems * sizeof(int16_t) : nullptr;
         }
     };
+    const dpx_route route = route_of(b);
     auto time_fill = [&]() -> float {
         float ms = -1.f;
-        hipError_t e = launch_all(b, b->stream);
+        hipError_t e = launch_all(b, route, b->stream);
         if (e == hipSuccess) e = hipEventRecord(e0, b->stream);
-        for (int i = 0; i < 3 && e == hipSuccess; i++) e = launch_all(b, b->stream);
+        for (int i = 0; i < 3 && e == hipSuccess; i++) e = launch_all(b, route, b->stream);
         if (e == hipSuccess) e = hipEventRecord(e1, b->stream);
         if (e == hipSuccess) e = hipEventSynchronize(e1);
         if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
@@ -1033,6 +1035,19 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
  * looks like one operation (events recorded on `s` around it time all of it). */
 static bool extension_on(const dpx_batch *b) { return b->zdrop >= 0 || b->endBonus >= 0; }
 
+/* which kernels the batch runs under its present settings (dpx_plan.h: computed at every use, never kept) */
+static dpx_route route_of(const dpx_batch *b) { return dpx_plan_route(*b, knobs().tbWalk, b->zdrop, b->endBonus, b->substAlphabet); }
+
+/* what a refill does to lines, text and CIGARs; the results go with them until the next fill */
+static void invalidate_fill(dpx_batch *b) {
+    b->filled = false; b->extFilled = false; b->tbLinesValid = false; b->outState = 0; b->cigarState = 0;
+}
+/* ... and that next fill, queued on `s` along route `r` */
+static void mark_filled(dpx_batch *b, const dpx_route &r, hipStream_t s) {
+    invalidate_fill(b);
+    b->filled = true; b->extFilled = r.extRecords; b->lastStream = s;
+}
+
 /* the batch's launch arguments under its substitution table: every wave's LDS slice grows by the table image */
 static dpx_subst_args subst_args(const dpx_batch *b) {
     dpx_subst_args sa = {b->args, reinterpret_cast<const int8_t *>(b->dSubst), b->dSubst + DPX_SUBST_TABLE_BYTES};
@@ -1041,54 +1056,47 @@ static dpx_subst_args subst_args(const dpx_batch *b) {
 }
 static size_t subst_lds_bytes(const dpx_batch *b) { return b->ldsBytes + (size_t)DPX_SUBST_IMAGE_BYTES * (DPX_FILL_THREADS / 64); }
 
-static hipError_t launch_main(dpx_batch *b, hipStream_t s) { /* the one-wave-per-pair kernel of the batch's algorithm */
-    if (b->bandDirs) return dpx_launch_bdir_fill(b->args, b->R, b->kernelAlgo == DPX_ALGO_BAXT, s);
-    if (b->substAlphabet && extension_on(b)) { /* (both at once: dpx_batch_set_extension_table, BAXT only) */
-        const dpx_zsub_args za = {subst_args(b), b->zdrop, b->endBonus, b->dExt};
-        return dpx_launch_zsub_fill(za, b->R, b->store, subst_lds_bytes(b), s);
-    }
-    if (b->substAlphabet) /* (set only on batches whose kernel is BANW's or BAXT's) */
-        return dpx_launch_subst_fill(subst_args(b), b->R, b->store, b->kernelAlgo == DPX_ALGO_BAXT, subst_lds_bytes(b), s);
-    if (b->kernelAlgo == DPX_ALGO_BASW) return dpx_launch_basw_fill(b->args, b->R, b->store, b->ldsBytes, s);
-    if (b->kernelAlgo == DPX_ALGO_BANW) return dpx_launch_banw_fill(b->args, b->R, b->store, b->ldsBytes, s);
-    if (b->kernelAlgo == DPX_ALGO_BAXT && extension_on(b)) {
+static hipError_t launch_main(dpx_batch *b, const dpx_route &r, hipStream_t s) { /* the one-wave-per-pair kernel of the batch's algorithm */
+    switch (r.main) {
+    case DPX_MAIN_NONE: return hipSuccess;
+    case DPX_MAIN_FILL: return dpx_launch_fill(b->args, b->kernelAlgo, b->R, b->store, b->ldsBytes, s);
+    case DPX_MAIN_BASW: return dpx_launch_basw_fill(b->args, b->R, b->store, b->ldsBytes, s);
+    case DPX_MAIN_BANW: return dpx_launch_banw_fill(b->args, b->R, b->store, b->ldsBytes, s);
+    case DPX_MAIN_BAXT: return dpx_launch_baxt_fill(b->args, b->R, b->store, b->ldsBytes, s);
+    case DPX_MAIN_ZEXT: {
         const dpx_zext_args za = {b->args, b->zdrop, b->endBonus, b->dExt};
         return dpx_launch_zext_fill(za, b->R, b->store, b->ldsBytes, s);
     }
-    if (b->kernelAlgo == DPX_ALGO_BAXT) return dpx_launch_baxt_fill(b->args, b->R, b->store, b->ldsBytes, s);
-    return dpx_launch_fill(b->args, b->kernelAlgo, b->R, b->store, b->ldsBytes, s);
+    case DPX_MAIN_SUBST: return dpx_launch_subst_fill(subst_args(b), b->R, b->store, r.ext, subst_lds_bytes(b), s);
+    case DPX_MAIN_ZSUB: {
+        const dpx_zsub_args za = {subst_args(b), b->zdrop, b->endBonus, b->dExt};
+        return dpx_launch_zsub_fill(za, b->R, b->store, subst_lds_bytes(b), s);
+    }
+    case DPX_MAIN_BDIR: return dpx_launch_bdir_fill(b->args, b->R, r.ext, s);
+    }
+    return hipErrorInvalidValue;
 }
 
-static hipError_t launch_all(dpx_batch *b, hipStream_t s) {
-    if (b->dirs) return dpx_launch_fill_dir(b->dirArgs, b->kernelAlgo, b->R, s);
-    const bool hasMain = b->args.numPairs > 0;
-    int kernels = 0;
-    if (b->packed) kernels++;
-    if (b->lanePacked) kernels++;
-    if (hasMain) kernels++;
+static hipError_t launch_all(dpx_batch *b, const dpx_route &r, hipStream_t s) {
+    if (r.dirs) return dpx_launch_fill_dir(b->dirArgs, b->kernelAlgo, b->R, s);
+    if (r.split) return dpx_launch_fill_split(b->args, b->kernelAlgo, b->R, b->splitWaves, b->splitLds, s);
     hipStream_t side = s;
     bool forked = false;
-    if (kernels > 1 && b->sideStream && b->evFork && b->evJoin) {
+    if (r.second != DPX_SECOND_NONE && r.main != DPX_MAIN_NONE && b->sideStream && b->evFork && b->evJoin) {
         hipError_t e = hipEventRecord(b->evFork, s);
         if (e == hipSuccess) e = hipStreamWaitEvent(b->sideStream, b->evFork, 0);
         if (e != hipSuccess) return e;
         side = b->sideStream;
         forked = true;
     }
-    hipError_t e = hipSuccess;
-    /* secondary kernel first (it is the short one; the main kernel then fills the chip around it) */
-    if (b->lanePacked) {
-        if (e == hipSuccess && hasMain) e = launch_main(b, side); /* empty pairs */
-        if (e == hipSuccess) e = b->lanesPk ? dpx_launch_fill_lanes_packed(b->pkArgs, b->kernelAlgo, b->pkLdsBytes, s)
-                                            : dpx_launch_fill_lanes(b->pkArgs, b->kernelAlgo, b->R, b->store, b->pkLdsBytes, s);
-    } else if (b->packed) {
-        if (e == hipSuccess && hasMain) e = launch_main(b, side);
-        if (e == hipSuccess) e = b->kernelAlgo == DPX_ALGO_BSW ? dpx_launch_banded_packed(b->pkArgs, b->R, b->pkLdsBytes, s)
-                                                               : dpx_launch_fill_packed(b->pkArgs, b->kernelAlgo, b->R, b->pkLdsBytes, s);
-    } else if (b->split) {
-        e = dpx_launch_fill_split(b->args, b->kernelAlgo, b->R, b->splitWaves, b->splitLds, s);
-    } else {
-        e = launch_main(b, s);
+    /* the leftover pairs first (theirs is the short kernel; the packed or lane-packed one then fills the chip around it) */
+    hipError_t e = launch_main(b, r, side); /* (beside the lane-packed kernels: the empty pairs) */
+    switch (e == hipSuccess ? r.second : DPX_SECOND_NONE) {
+    case DPX_SECOND_NONE: break;
+    case DPX_SECOND_PACKED: e = dpx_launch_fill_packed(b->pkArgs, b->kernelAlgo, b->R, b->pkLdsBytes, s); break;
+    case DPX_SECOND_BANDED_PACKED: e = dpx_launch_banded_packed(b->pkArgs, b->R, b->pkLdsBytes, s); break;
+    case DPX_SECOND_LANES: e = dpx_launch_fill_lanes(b->pkArgs, b->kernelAlgo, b->R, b->store, b->pkLdsBytes, s); break;
+    case DPX_SECOND_LANES_PK: e = dpx_launch_fill_lanes_packed(b->pkArgs, b->kernelAlgo, b->pkLdsBytes, s); break;
     }
     if (forked) {
         hipError_t j = hipEventRecord(b->evJoin, side);
@@ -1113,14 +1121,10 @@ int dpx_batch_fill(dpx_batch *b, void *stream) {
         if (!b->evT1) HIP_TRY(hipEventCreate(&b->evT1));
         HIP_TRY(hipEventRecord(b->evT0, s));
     }
-    HIP_TRY(launch_all(b, s));
+    const dpx_route r = route_of(b);
+    HIP_TRY(launch_all(b, r, s));
     if (timed) { HIP_TRY(hipEventRecord(b->evT1, s)); b->fillTimed = true; }
-    b->lastStream = s;
-    b->filled = true;
-    b->extFilled = extension_on(b);
-    b->tbLinesValid = false;
-    b->outState = 0;
-    b->cigarState = 0;
+    mark_filled(b, r, s);
     return DPX_OK;
 }
 
@@ -1157,7 +1161,8 @@ int dpx_batch_fill_timed(dpx_batch *b, int repeats, double *usecPerFill) {
     hipError_t e = hipEventCreate(&e0);
     if (e == hipSuccess) e = hipEventCreate(&e1);
     if (e == hipSuccess) e = hipEventRecord(e0, b->stream);
-    for (int i = 0; i < repeats && e == hipSuccess; i++) e = launch_all(b, b->stream);
+    const dpx_route r = route_of(b);
+    for (int i = 0; i < repeats && e == hipSuccess; i++) e = launch_all(b, r, b->stream);
     if (e == hipSuccess) e = hipEventRecord(e1, b->stream);
     if (e == hipSuccess) e = hipEventSynchronize(e1);
     if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
@@ -1165,12 +1170,7 @@ int dpx_batch_fill_timed(dpx_batch *b, int repeats, double *usecPerFill) {
     if (e1) (void)hipEventDestroy(e1);
     if (e != hipSuccess) return hip_fail(e, "dpx_batch_fill_timed");
     *usecPerFill = (double)ms * 1000.0 / repeats;
-    b->lastStream = b->stream;
-    b->filled = true;
-    b->extFilled = extension_on(b);
-    b->tbLinesValid = false;
-    b->outState = 0;
-    b->cigarState = 0;
+    mark_filled(b, r, b->stream);
     return DPX_OK;
 }
 
@@ -1267,12 +1267,12 @@ int dpx_batch_matrix(dpx_batch *b, size_t pair, int which, int16_t *out) {
     size_t dOutCap = 0;
     if (b->lastStream && b->lastStream != b->stream) HIP_TRY(hipStreamSynchronize(b->lastStream));
     HIP_TRY(g_tbDevCache.take((void **)&dOut, total * sizeof(int16_t), &dOutCap)); /* row-major scratch */
-    hipError_t e = is_banw_layout(b->kernelAlgo) /* (BAXT stores what BANW stores) */
-                       ? dpx_launch_banw_export(b->dMat, pd, which, b->prm.band, b->prm.gapOpen, b->prm.gapExtend, dOut, b->stream)
-                   : b->kernelAlgo == DPX_ALGO_BASW
-                       ? dpx_launch_basw_export(b->dMat, pd, which, b->prm.band, dOut, b->stream)
-                       : dpx_launch_export(b->dMat, pd, b->kernelAlgo, b->R, b->planes, which, b->prm.gapOpen, b->prm.gapExtend,
-                                           b->prm.band, dOut, b->stream);
+    hipError_t e = hipErrorInvalidValue;
+    switch (route_of(b).exportKind) {
+    case DPX_EXPORT_PLAIN: e = dpx_launch_export(b->dMat, pd, b->kernelAlgo, b->R, b->planes, which, b->prm.gapOpen, b->prm.gapExtend, b->prm.band, dOut, b->stream); break;
+    case DPX_EXPORT_BASW: e = dpx_launch_basw_export(b->dMat, pd, which, b->prm.band, dOut, b->stream); break;
+    case DPX_EXPORT_BANW: e = dpx_launch_banw_export(b->dMat, pd, which, b->prm.band, b->prm.gapOpen, b->prm.gapExtend, dOut, b->stream); break;
+    }
     if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
     if (e == hipSuccess) e = hipMemcpy(out, dOut, total * sizeof(int16_t), hipMemcpyDeviceToHost);
     g_tbDevCache.park(dOut, dOutCap);
@@ -1299,11 +1299,6 @@ int dpx_batch_set_extension(dpx_batch *b, int32_t zdrop, int32_t endBonus) {
     b->zdrop = zdrop;
     b->endBonus = endBonus;
     return DPX_OK;
-}
-
-/* what a refill does to lines, text and CIGARs; the results go with them until the next fill */
-static void invalidate_fill(dpx_batch *b) {
-    b->filled = false; b->extFilled = false; b->tbLinesValid = false; b->outState = 0; b->cigarState = 0;
 }
 
 /* dpx_batch_set_substitution's checks of a table for this batch, all of them: nothing is changed */
@@ -1392,29 +1387,19 @@ int dpx_batch_extensions(dpx_batch *b, dpx_extension *out) {
  * already formatted as c++/main.cpp prints them, so a driver writes a batch with one fwrite) */
 
 /* The device traceback of every pair into the line buffers (b->dTb must exist), on the batch's stream, unless the lines of this fill
- * are there already: the one place that chooses the walk, for the text pipeline and the CIGAR path alike. */
+ * are there already: the one place that launches the walk, for the text pipeline and the CIGAR path alike. */
 static int traceback_lines(dpx_batch *b) {
     if (b->tbLinesValid) return DPX_OK;
-    /* How to walk (round 4, tools/tb_kernel.sh, kernel time alone; profiles/r04/traceback_walks.txt).  Walk 2 = one WAVE per pair
-     * (k_traceback_wave: runs of path steps decided by all lanes at once from an LDS window): LSW / LNW always -- 1000 x 512^2 0.13 vs
-     * 0.60 ms for one lane per pair, 16 000 x 512^2 0.50 vs 0.76, 20 000 x 300^2 0.36 vs 0.54, 100 000 short reads 0.33 vs 0.57 (LSW) /
-     * 0.71 vs 0.69 (LNW); ANW (three planes per window, 48-row banded windows) up to 20 000 pairs -- 1000 x 512^2 0.17 vs 1.16,
-     * 5000 x 1024^2 0.86 vs 2.51, 20 000 x 300^2 0.92 vs 0.98, but 100 000 short reads 1.48 vs 0.98.  Walks 0 / 1 = one lane
-     * per pair, cell by cell / through register-cached column vectors (the latter from 64k pairs on: enough lanes in flight to thrash
-     * L1 / L2 between two steps of a lane).  Banded matrices: walk 2 as well (its band-layout window loads; numbers in the same file).
-     * DPX_TB_WALK=0/1/2 forces one (tests). */
-    int walk = b->numPairs >= 65536 ? 1 : 0;
-    if (b->kernelAlgo == DPX_ALGO_LSW || b->kernelAlgo == DPX_ALGO_LNW || b->kernelAlgo == DPX_ALGO_BSW) walk = 2;
-    else if (is_affine(b->kernelAlgo) && b->numPairs <= 20000) walk = 2; /* (ASW: as ANW; its walk 1 is walk 0) */
-    { const int w = knobs().tbWalk; if (w >= 0) walk = std::min(2, w); }
-    /* banded affine SW: as ASW -- one wave per pair up to 20 000 pairs (k_basw_traceback_wave, band-layout window loads for the three
-     * planes), one lane per pair beyond that or under DPX_TB_WALK=0 / 1 (k_basw_traceback) */
-    if (b->bandDirs) HIP_TRY(dpx_launch_bdir_traceback(b->args, (int)b->numPairs, b->dTbOff, b->dTb, b->dTbLen, b->stream)); /* (one walk: DPX_TB_WALK has no effect) */
-    else if (b->substAlphabet) HIP_TRY(dpx_launch_subst_traceback(subst_args(b), (int)b->numPairs, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream));
-    else if (b->kernelAlgo == DPX_ALGO_BASW) HIP_TRY(dpx_launch_basw_traceback(b->args, (int)b->numPairs, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream));
-    else if (is_banw_layout(b->kernelAlgo)) HIP_TRY(dpx_launch_banw_traceback(b->args, (int)b->numPairs, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream)); /* (banded affine NW, and the extension, which walks from its end cell to the anchor: the same choice) */
-    else if (b->dirs) HIP_TRY(dpx_launch_traceback_dir(b->dirArgs, (int)b->numPairs, b->kernelAlgo, b->R, b->dTbOff, b->dTb, b->dTbLen, b->stream));
-    else HIP_TRY(dpx_launch_traceback(b->args, (int)b->numPairs, b->kernelAlgo, b->R, b->planes, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream));
+    const dpx_route r = route_of(b); /* (which walk, and why: dpx_plan.cpp) */
+    const int n = (int)b->numPairs, walk = r.walkMode;
+    switch (r.walk) {
+    case DPX_WALK_PLAIN: HIP_TRY(dpx_launch_traceback(b->args, n, b->kernelAlgo, b->R, b->planes, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream)); break;
+    case DPX_WALK_DIR: HIP_TRY(dpx_launch_traceback_dir(b->dirArgs, n, b->kernelAlgo, b->R, b->dTbOff, b->dTb, b->dTbLen, b->stream)); break;
+    case DPX_WALK_BASW: HIP_TRY(dpx_launch_basw_traceback(b->args, n, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream)); break;
+    case DPX_WALK_BANW: HIP_TRY(dpx_launch_banw_traceback(b->args, n, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream)); break;
+    case DPX_WALK_SUBST: HIP_TRY(dpx_launch_subst_traceback(subst_args(b), n, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream)); break;
+    case DPX_WALK_BDIR: HIP_TRY(dpx_launch_bdir_traceback(b->args, n, b->dTbOff, b->dTb, b->dTbLen, b->stream)); break;
+    }
     b->tbLinesValid = true;
     return DPX_OK;
 }

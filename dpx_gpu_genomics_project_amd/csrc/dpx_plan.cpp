@@ -646,34 +646,98 @@ int dpx_plan_batch(const dpx_params &params, const dpx_seq_pair *pairs, size_t f
     return launch_scalars(kn, sh.banded, lanesRefArea, p);
 }
 
+/* How to walk (round 4, tools/tb_kernel.sh, kernel time alone; profiles/r04/traceback_walks.txt).  Walk 2 = one WAVE per pair
+ * (k_traceback_wave: runs of path steps decided by all lanes at once from an LDS window): LSW / LNW always -- 1000 x 512^2 0.13 vs
+ * 0.60 ms for one lane per pair, 16 000 x 512^2 0.50 vs 0.76, 20 000 x 300^2 0.36 vs 0.54, 100 000 short reads 0.33 vs 0.57 (LSW) /
+ * 0.71 vs 0.69 (LNW); ANW (three planes per window, 48-row banded windows) up to 20 000 pairs -- 1000 x 512^2 0.17 vs 1.16,
+ * 5000 x 1024^2 0.86 vs 2.51, 20 000 x 300^2 0.92 vs 0.98, but 100 000 short reads 1.48 vs 0.98.  Walks 0 / 1 = one lane
+ * per pair, cell by cell / through register-cached column vectors (the latter from 64k pairs on: enough lanes in flight to thrash
+ * L1 / L2 between two steps of a lane).  Banded matrices: walk 2 as well (its band-layout window loads; numbers in the same file).
+ * Banded affine SW: as ASW -- one wave per pair up to 20 000 pairs (k_basw_traceback_wave, band-layout window loads for the three
+ * planes), one lane per pair beyond that or under DPX_TB_WALK=0 / 1 (k_basw_traceback); banded affine NW and the extension, which walks
+ * from its end cell to the anchor: the same choice.  DPX_TB_WALK=0/1/2 forces one (tests). */
+static int walk_mode(const dpx_plan &p, int tbWalk) {
+    if (tbWalk >= 0) return std::min(2, tbWalk);
+    if (!is_affine(p.kernelAlgo)) return 2; /* LSW, LNW, BSW */
+    return p.numPairs <= 20000 ? 2 : p.numPairs >= 65536 ? 1 : 0; /* (ASW: as ANW; its walk 1 is walk 0) */
+}
+
+dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus, int substAlphabet) {
+    const int algo = p.kernelAlgo;
+    dpx_route r{};
+    r.ext = algo == DPX_ALGO_BAXT;
+    const bool extension = r.ext && (zdrop >= 0 || endBonus >= 0);
+    const dpx_fill_kernel lanes[] = {DPX_K_LINEAR_LANES, DPX_K_AFFINE_LANES, DPX_K_ASW_LANES, DPX_K_ASG_LANES};
+    const dpx_fill_kernel fill[] = {DPX_K_LINEAR_FILL, DPX_K_AFFINE_FILL, DPX_K_ASW_FILL, DPX_K_ASG_FILL};
+    const dpx_fill_kernel dir[] = {DPX_K_LINEAR_DIR, DPX_K_AFFINE_DIR, DPX_K_ASW_DIR, DPX_K_ASG_DIR};
+    const int family = algo == DPX_ALGO_ANW ? 1 : algo == DPX_ALGO_ASW ? 2 : algo == DPX_ALGO_ASG ? 3 : 0;
+    if (p.dirs) {
+        r.dirs = true; r.kernel = dir[family];
+    } else if (p.bandDirs) {
+        r.main = DPX_MAIN_BDIR; r.kernel = DPX_K_BDIR_FILL;
+    } else if (substAlphabet) { /* (set only on batches whose kernel is BANW's or BAXT's; with extension mode: dpx_batch_set_extension_table) */
+        r.main = extension ? DPX_MAIN_ZSUB : DPX_MAIN_SUBST; r.kernel = extension ? DPX_K_ZSUB_FILL : DPX_K_SUBST_FILL;
+    } else if (algo == DPX_ALGO_BAXT) {
+        r.main = extension ? DPX_MAIN_ZEXT : DPX_MAIN_BAXT; r.kernel = extension ? DPX_K_ZEXT_FILL : DPX_K_BAXT_FILL;
+    } else if (algo == DPX_ALGO_BANW) {
+        r.main = DPX_MAIN_BANW; r.kernel = DPX_K_BANW_FILL;
+    } else if (algo == DPX_ALGO_BASW) {
+        r.main = DPX_MAIN_BASW; r.kernel = DPX_K_BASW_FILL;
+    } else { /* dpx_launch_fill's algorithms, with or without a secondary kernel that takes most of the pairs */
+        const bool bsw = algo == DPX_ALGO_BSW;
+        r.second = p.packed ? (bsw ? DPX_SECOND_BANDED_PACKED : DPX_SECOND_PACKED) : p.lanesPk ? DPX_SECOND_LANES_PK : p.lanePacked ? DPX_SECOND_LANES : DPX_SECOND_NONE;
+        r.split = !r.second && p.split;
+        if (r.second ? p.args.numPairs > 0 : !r.split) r.main = DPX_MAIN_FILL;
+        r.kernel = bsw ? (p.packed ? DPX_K_BANDED_FILL_PK : DPX_K_BANDED_FILL)
+                   : family ? (p.lanePacked ? lanes[family] : fill[family])
+                   : p.packed ? DPX_K_LINEAR_FILL_PK : p.lanesPk ? DPX_K_LINEAR_LANES_PK : p.lanePacked ? DPX_K_LINEAR_LANES : p.split ? DPX_K_LINEAR_SPLIT : DPX_K_LINEAR_FILL;
+    }
+    r.extRecords = r.main == DPX_MAIN_ZEXT || r.main == DPX_MAIN_ZSUB;
+    r.walk = p.bandDirs ? DPX_WALK_BDIR : substAlphabet ? DPX_WALK_SUBST : algo == DPX_ALGO_BASW ? DPX_WALK_BASW : is_banw_layout(algo) ? DPX_WALK_BANW
+             : p.dirs ? DPX_WALK_DIR : DPX_WALK_PLAIN;
+    r.walkMode = (r.walk == DPX_WALK_BDIR || r.walk == DPX_WALK_DIR) ? 0 : walk_mode(p, tbWalk); /* (one walk: DPX_TB_WALK has no effect) */
+    r.exportKind = is_banw_layout(algo) /* (BAXT stores what BANW stores) */ ? DPX_EXPORT_BANW : algo == DPX_ALGO_BASW ? DPX_EXPORT_BASW : DPX_EXPORT_PLAIN;
+    return r;
+}
+
+const char *dpx_route_kernel_name(dpx_fill_kernel k) {
+    static const char *const names[DPX_K_COUNT] = {
+        "k_linear_fill", "k_linear_fill_pk", "k_linear_lanes", "k_linear_lanes_pk", "k_linear_split",
+        "k_affine_fill", "k_asw_fill", "k_asg_fill", "k_affine_lanes", "k_asw_lanes", "k_asg_lanes",
+        "k_banded_fill", "k_banded_fill_pk", "k_basw_fill", "k_banw_fill", "k_baxt_fill",
+        "k_zext_fill", "k_subst_fill", "k_zsub_fill", "k_bdir_fill",
+        "k_linear_dir", "k_affine_dir", "k_asw_dir", "k_asg_dir"};
+    return k >= 0 && k < DPX_K_COUNT ? names[k] : "?";
+}
+
+const char *dpx_route_walk_name(dpx_walk_family walk, int walkMode) {
+    const bool wave = walkMode == 2;
+    switch (walk) {
+    case DPX_WALK_PLAIN: return wave ? "k_traceback_wave" : "k_traceback";
+    case DPX_WALK_DIR: return "k_traceback_dir";
+    case DPX_WALK_BASW: return wave ? "k_basw_traceback_wave" : "k_basw_traceback";
+    case DPX_WALK_BANW: return wave ? "k_banw_traceback_wave" : "k_banw_traceback";
+    case DPX_WALK_SUBST: return wave ? "k_subst_traceback_wave" : "k_subst_traceback";
+    case DPX_WALK_BDIR: return "k_bdir_traceback";
+    }
+    return "?";
+}
+
 int dpx_plan_describe(const dpx_plan &b, int tbWalk, int zdrop, int endBonus, int substAlphabet, char *buf, size_t cap) {
-    const bool extension = zdrop >= 0 || endBonus >= 0;
+    const dpx_route r = dpx_plan_route(b, tbWalk, zdrop, endBonus, substAlphabet);
+    const bool extension = r.ext && (zdrop >= 0 || endBonus >= 0);
     auto name = [](int algo) -> const char * { /* (sparse: 8 and 9 are unassigned) */
         static const char *names[] = {"LNW", "LSW", "ANW", "BSW", "ASW", "BASW", "ASG", "BANW"};
         return algo == DPX_ALGO_BAXT ? "BAXT" : (algo >= 0 && algo <= DPX_ALGO_BANW) ? names[algo] : "?";
     };
-    const char *kernel = b.kernelAlgo == DPX_ALGO_BAXT ? "k_baxt_fill" : b.kernelAlgo == DPX_ALGO_BANW ? "k_banw_fill" : b.kernelAlgo == DPX_ALGO_BASW ? "k_basw_fill" : b.kernelAlgo == DPX_ALGO_BSW ? (b.packed ? "k_banded_fill_pk" : "k_banded_fill") : b.kernelAlgo == DPX_ALGO_ANW ? (b.lanePacked ? "k_affine_lanes" : "k_affine_fill")
-                         : b.kernelAlgo == DPX_ALGO_ASW ? (b.lanePacked ? "k_asw_lanes" : "k_asw_fill")
-                         : b.kernelAlgo == DPX_ALGO_ASG ? (b.lanePacked ? "k_asg_lanes" : "k_asg_fill")
-                         : b.packed ? "k_linear_fill_pk" : b.lanesPk ? "k_linear_lanes_pk" : b.lanePacked ? "k_linear_lanes" : b.split ? "k_linear_split" : "k_linear_fill";
-    if (b.kernelAlgo == DPX_ALGO_BAXT && extension) kernel = "k_zext_fill";
-    if (substAlphabet) kernel = (b.kernelAlgo == DPX_ALGO_BAXT && extension) ? "k_zsub_fill" : "k_subst_fill";
-    if (b.bandDirs) kernel = "k_bdir_fill";
-    if (b.dirs) kernel = b.kernelAlgo == DPX_ALGO_ANW ? "k_affine_dir" : b.kernelAlgo == DPX_ALGO_ASW ? "k_asw_dir" : b.kernelAlgo == DPX_ALGO_ASG ? "k_asg_dir" : "k_linear_dir";
     /* dtype = the arithmetic type of the kernel that fills (most of) the batch */
     int len = snprintf(buf, cap, "algo=%s kernel_algo=%s kernel=%s dtype=%s rows_per_lane=%d store=%d couples=%zu lane_pairs=%zu waves=%zu singles=%zu row_tags=%d seq_input=%s waves_per_workgroup=%u",
-                       name(b.prm.algo), name(b.kernelAlgo), kernel, (b.packed || b.lanesPk) ? "int16" : "int32", b.R, b.store ? 1 : 0, b.nCouples, b.nLanePairs,
+                       name(b.prm.algo), name(b.kernelAlgo), dpx_route_kernel_name(r.kernel), (b.packed || b.lanesPk) ? "int16" : "int32", b.R, b.store ? 1 : 0, b.nCouples, b.nLanePairs,
                        b.nWaves, b.nSingles, (int)b.pkArgs.rowTags, b.packed2 ? "packed2" : "bytes",
                        b.dirs ? b.dirArgs.wavesPerBlock : (b.packed || b.lanePacked) ? b.pkArgs.wavesPerBlock : b.split ? (unsigned)b.splitWaves : b.args.wavesPerBlock);
-    if (is_banded_affine(b.kernelAlgo) && len > 0 && (size_t)len < cap) { /* which walk the batch's traceback takes */
-        const bool wave = tbWalk >= 0 ? tbWalk >= 2 : b.numPairs <= 20000;
-        len += snprintf(buf + len, cap - (size_t)len, " traceback=%s",
-                        b.bandDirs ? "k_bdir_traceback"
-                        : substAlphabet ? (wave ? "k_subst_traceback_wave" : "k_subst_traceback")
-                        : is_banw_layout(b.kernelAlgo) ? (wave ? "k_banw_traceback_wave" : "k_banw_traceback")
-                                                       : (wave ? "k_basw_traceback_wave" : "k_basw_traceback"));
-    }
-    if (b.kernelAlgo == DPX_ALGO_BAXT && extension && len > 0 && (size_t)len < cap)
+    if (is_banded_affine(b.kernelAlgo) && len > 0 && (size_t)len < cap) /* which walk the batch's traceback takes */
+        len += snprintf(buf + len, cap - (size_t)len, " traceback=%s", dpx_route_walk_name(r.walk, r.walkMode));
+    if (extension && len > 0 && (size_t)len < cap)
         len += snprintf(buf + len, cap - (size_t)len, " zdrop=%d end_bonus=%d", (int)zdrop, (int)endBonus);
     if (substAlphabet && len > 0 && (size_t)len < cap) len += snprintf(buf + len, cap - (size_t)len, " subst=%d", substAlphabet);
     if (b.bandDirs && len > 0 && (size_t)len < cap) len += snprintf(buf + len, cap - (size_t)len, " matrix=banddir4");

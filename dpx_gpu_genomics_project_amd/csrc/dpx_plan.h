@@ -79,8 +79,39 @@ bool packed_safe(const dpx_params &p, long long m, long long n);
 int dpx_plan_batch(const dpx_params &params, const dpx_seq_pair *pairs, size_t firstPair, size_t numPairs, size_t numBytes, bool packed2Input,
                    unsigned flags, const Knobs &knobs, dpx_plan &out, std::string &err);
 
-/* dpx_batch_describe()'s text up to the pool fields.  What a batch can change after its creation comes as arguments: the traceback walk
- * knob, BAXT's extension mode (-1, -1: off) and the substitution alphabet (0: none).  Returns the length written (snprintf's rules). */
+/* Which kernels a batch runs: the one place that decides it.  A fill, a traceback, a matrix export and dpx_batch_describe() each compute
+ * the route again and read their part of it (plain data, no allocation; nothing is cached, so a setter has nothing to invalidate). */
+enum dpx_fill_kernel { /* the kernel that fills (most of) the batch: describe's kernel= */
+    DPX_K_LINEAR_FILL, DPX_K_LINEAR_FILL_PK, DPX_K_LINEAR_LANES, DPX_K_LINEAR_LANES_PK, DPX_K_LINEAR_SPLIT,
+    DPX_K_AFFINE_FILL, DPX_K_ASW_FILL, DPX_K_ASG_FILL, DPX_K_AFFINE_LANES, DPX_K_ASW_LANES, DPX_K_ASG_LANES,
+    DPX_K_BANDED_FILL, DPX_K_BANDED_FILL_PK, DPX_K_BASW_FILL, DPX_K_BANW_FILL, DPX_K_BAXT_FILL,
+    DPX_K_ZEXT_FILL, DPX_K_SUBST_FILL, DPX_K_ZSUB_FILL, DPX_K_BDIR_FILL,
+    DPX_K_LINEAR_DIR, DPX_K_AFFINE_DIR, DPX_K_ASW_DIR, DPX_K_ASG_DIR, DPX_K_COUNT
+};
+enum dpx_main_launch { DPX_MAIN_NONE, DPX_MAIN_FILL, DPX_MAIN_BASW, DPX_MAIN_BANW, DPX_MAIN_BAXT, DPX_MAIN_ZEXT, DPX_MAIN_SUBST, DPX_MAIN_ZSUB, DPX_MAIN_BDIR };
+enum dpx_second_launch { DPX_SECOND_NONE, DPX_SECOND_PACKED, DPX_SECOND_BANDED_PACKED, DPX_SECOND_LANES, DPX_SECOND_LANES_PK };
+enum dpx_walk_family { DPX_WALK_PLAIN, DPX_WALK_DIR, DPX_WALK_BASW, DPX_WALK_BANW, DPX_WALK_SUBST, DPX_WALK_BDIR };
+enum dpx_export_kind { DPX_EXPORT_PLAIN, DPX_EXPORT_BASW, DPX_EXPORT_BANW };
+struct dpx_route {
+    dpx_fill_kernel kernel;
+    /* the launches of one fill: a direction batch, or the split kernel, or the secondary kernel (if any) beside the one-wave-per-pair
+     * kernel of the pairs it leaves over (if any) */
+    bool dirs, split;
+    dpx_second_launch second;
+    dpx_main_launch main;
+    bool ext;        /* the band kernel (BDIR, SUBST) runs BAXT's end-cell rule, not BANW's */
+    bool extRecords; /* the fill writes a dpx_extension record per pair (k_zext_fill, k_zsub_fill) */
+    dpx_walk_family walk;
+    int walkMode;    /* 0 / 1: one lane per pair, cell by cell / through cached column vectors; 2: one wave per pair (DIR and BDIR have one walk: 0) */
+    dpx_export_kind exportKind;
+};
+/* What a batch can change after its creation comes as arguments: the traceback walk knob, BAXT's extension mode (-1, -1: off) and the
+ * substitution alphabet (0: none). */
+dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus, int substAlphabet);
+const char *dpx_route_kernel_name(dpx_fill_kernel k);
+const char *dpx_route_walk_name(dpx_walk_family walk, int walkMode);
+
+/* dpx_batch_describe()'s text up to the pool fields, with dpx_plan_route's arguments.  Returns the length written (snprintf's rules). */
 int dpx_plan_describe(const dpx_plan &p, int tbWalk, int zdrop, int endBonus, int substAlphabet, char *buf, size_t cap);
 
 #pragma GCC visibility pop

@@ -7,10 +7,15 @@
  *     knobs <DPX_R> <DPX_PACKED> <DPX_LANES> <DPX_LANES_PK> <DPX_SPLIT> <DPX_ROW_TAGS> <DPX_RAMP_LINES> <DPX_WPB> <DPX_GROUP> <DPX_TB_WALK>
  *           (the values refresh_knobs() would read: 0 for an unset DPX_R / DPX_WPB / DPX_GROUP, -1 for the others)
  *     input <packed2: 0|1> <numBytes> <firstPair> <numPairs>
+ *     mode <zdrop> <endBonus> <substAlphabet>                      (optional: what a batch can change after its creation, as
+ *           dpx_batch_set_extension / _set_substitution / _set_extension_table leave it; absent: -1 -1 0.  The setters' own
+ *           refusals are not applied: the planner is asked what such a batch would run)
  *     <referenceIdx> <referenceSize> <queryIdx> <querySize>        (firstPair + numPairs lines)
  *
  * Output, one line: "status=<n>", then for a refusal " err=<text>" when there is one, else dpx_batch_describe()'s text up to the pool
- * fields, " info=<numPairs>,<cells>,<matrixBytes>,<algorithmicBytes>" (dpx_batch_info) and " state=<16 hex digits>".
+ * fields, " info=<numPairs>,<cells>,<matrixBytes>,<algorithmicBytes>" (dpx_batch_info), " state=<16 hex digits>" and, only when a mode
+ * line was given, " walk=<family>:<mode>": the traceback's family (plain, dir, basw, banw, subst, bdir) and walk (0, 1 or 2) of
+ * dpx_plan_route, which describe's traceback= shows for the banded affine kernels only.
  *
  * state is FNV-1a 64 over, in this order (integers as 8 little-endian bytes, sign-extended):
  *   1. the number of pairs, then of every dpx_pair_dev: refIdx, n, qryIdx, m, matOff, chunkStride, lanes, rows
@@ -71,6 +76,9 @@ int main() {
         fprintf(stderr, "plan_tool: malformed case header\n");
         return 2;
     }
+    int zdrop = -1, endBonus = -1, substAlphabet = 0;
+    const bool mode = scanf(" mode %d %d %d", &zdrop, &endBonus, &substAlphabet) == 3; /* (a pair line stops the match at its first character) */
+    if (!mode) { zdrop = endBonus = -1; substAlphabet = 0; }
     std::vector<dpx_seq_pair> pairs(firstPair + numPairs);
     for (dpx_seq_pair &sp : pairs)
         if (scanf("%d %d %d %d", &sp.referenceIdx, &sp.referenceSize, &sp.queryIdx, &sp.querySize) != 4) {
@@ -86,8 +94,14 @@ int main() {
         return 0;
     }
     char text[4096];
-    dpx_plan_describe(plan, kn.tbWalk, -1, -1, 0, text, sizeof text);
-    printf("status=0 %s info=%zu,%llu,%llu,%llu state=%016llx\n", text, plan.numPairs, (unsigned long long)plan.cells,
+    dpx_plan_describe(plan, kn.tbWalk, zdrop, endBonus, substAlphabet, text, sizeof text);
+    printf("status=0 %s info=%zu,%llu,%llu,%llu state=%016llx", text, plan.numPairs, (unsigned long long)plan.cells,
            (unsigned long long)(plan.matElems * sizeof(int16_t)), (unsigned long long)plan.algBytes, (unsigned long long)plan_state(plan));
+    if (mode) {
+        static const char *const family[] = {"plain", "dir", "basw", "banw", "subst", "bdir"}; /* dpx_walk_family */
+        const dpx_route r = dpx_plan_route(plan, kn.tbWalk, zdrop, endBonus, substAlphabet);
+        printf(" walk=%s:%d", family[r.walk], r.walkMode);
+    }
+    printf("\n");
     return 0;
 }

@@ -2,8 +2,9 @@
 
 A case is a dict: name; algo (name), weights [match, mismatch, gapOpen, gapExtend], band, flags; env (the DPX_* knobs set for it); gen, a
 call of synth.make_batch / make_ragged_batch / from_strings as [function name, arguments...]; optionally tweak, a list of
-[pair, field, value] applied to the generated pair table (an empty or an invalid pair inside a regular batch), first_pair, and packed2
-(the sequences go in as 2-bit codes).  expect is the line plan_tool must print, recorded from the commit before the planner existed
+[pair, field, value] applied to the generated pair table (an empty or an invalid pair inside a regular batch), first_pair, packed2
+(the sequences go in as 2-bit codes), and mode, [zdrop, endBonus, substAlphabet] as the setters of a live batch would leave them
+(plan_tool then prints the walk as well; no golden case has one).  expect is the line plan_tool must print, recorded from the commit before the planner existed
 (profiles/plan_split.md)."""
 import json
 import os
@@ -50,6 +51,8 @@ def tool_input(case, sb) -> str:
     head = ["params %d %d %d %d %d %d" % (ALGOS[case["algo"]], *case["weights"], case["band"]), "flags %d" % case["flags"],
             "knobs " + " ".join(str(int(env.get(k, unset))) for k, unset in KNOBS),
             "input %d %d %d %d" % (1 if case.get("packed2") else 0, sb.sequences.size, first, len(sb.pairs) - first)]
+    if "mode" in case:
+        head.append("mode %d %d %d" % tuple(case["mode"]))
     p = sb.pairs
     table = np.stack([p["referenceIdx"], p["referenceSize"], p["queryIdx"], p["querySize"]], axis=1).astype(np.int64)
     return "\n".join(head) + "\n" + "\n".join(" ".join(map(str, row)) for row in table.tolist()) + "\n"
