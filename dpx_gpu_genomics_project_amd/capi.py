@@ -35,7 +35,7 @@ ABI_SYMBOLS = (
     "dpx_batch_output_begin", "dpx_batch_output_end", "dpx_batch_output_take", "dpx_text_free",
     "dpx_batch_info", "dpx_batch_describe", "dpx_batch_destroy", "dpx_align_batch", "dpx_prim_eval", "dpx_batch_directions",
     "dpx_batch_cigars_begin", "dpx_batch_cigars_end", "dpx_cigar_text", "dpx_batch_set_extension", "dpx_batch_extensions",
-    "dpx_batch_set_substitution", "dpx_batch_set_extension_table",
+    "dpx_batch_set_substitution", "dpx_batch_set_extension_table", "dpx_batch_set_direction_scoring",
 )
 # declared entry points a library may lack and still load (an older build): checked when they are called
 OPTIONAL_SYMBOLS = ("dpx_batch_directions",)
@@ -128,6 +128,7 @@ def load() -> C.CDLL:
     lib.dpx_batch_extensions.argtypes = [vp, vp]
     lib.dpx_batch_set_substitution.argtypes = [vp, vp, C.c_int32, vp]
     lib.dpx_batch_set_extension_table.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, vp]
+    lib.dpx_batch_set_direction_scoring.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, vp]
     for name in ABI_SYMBOLS:  # every declared entry point must be exported (the optional ones by libraries that have them)
         if name not in OPTIONAL_SYMBOLS:
             getattr(lib, name)
@@ -300,6 +301,17 @@ class Batch:
         tab, code = _table_arrays(scores, code_of)
         _check(self._lib.dpx_batch_set_extension_table(self._h, zdrop, end_bonus, tab.ctypes.data, tab.shape[0], code.ctypes.data),
                "dpx_batch_set_extension_table")
+
+    def set_direction_scoring(self, zdrop: int = -1, end_bonus: int = -1, scores=None, code_of=None) -> None:
+        """KEEP_BAND_DIRECTIONS batches only: all scoring at once -- z-drop and end bonus (BAXT; -1 = off) and a substitution table
+        (set_substitution's arrays; None = no table).  Replaces all three settings; everything off returns the batch to k_bdir_fill.
+        Lines and results of an earlier fill are invalid afterwards when a setting changed."""
+        if scores is None:
+            _check(self._lib.dpx_batch_set_direction_scoring(self._h, zdrop, end_bonus, None, 0, None), "dpx_batch_set_direction_scoring")
+            return
+        tab, code = _table_arrays(scores, code_of)
+        _check(self._lib.dpx_batch_set_direction_scoring(self._h, zdrop, end_bonus, tab.ctypes.data, tab.shape[0], code.ctypes.data),
+               "dpx_batch_set_direction_scoring")
 
     def extensions(self) -> np.ndarray:
         """One EXTENSION_DTYPE record per pair of the last fill, which must have run in extension mode."""

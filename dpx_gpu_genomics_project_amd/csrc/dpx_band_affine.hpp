@@ -1,7 +1,8 @@
 /*
  * dpx_band_affine.hpp -- what the banded affine-gap units without a zero floor share: dpx_banw_kernels.hip (BANW), dpx_baxt_kernels.hip
  * (BAXT), dpx_zext_kernels.hip (BAXT in extension mode), dpx_subst_kernels.hip (either, scored by a table), dpx_zsub_kernels.hip (BAXT in
- * extension mode, scored by a table) and dpx_banddir_kernels.hip (either, storing direction codes).  dpx_basw_kernels.hip, whose step has a zero floor and a start cell, is a different kernel and does
+ * extension mode, scored by a table), dpx_banddir_kernels.hip (either, storing direction codes) and dpx_bdx_kernels.hip (the same under a table
+ * and / or BAXT's extension mode).  dpx_basw_kernels.hip, whose step has a zero floor and a start cell, is a different kernel and does
  * not include it.  Everything here is a __forceinline__ function or a template: each kernel stays in its own unit under its own name.
  *
  * Shared are end_key, the band geometry and BandView, the step of the two fills that track slot keys (slot_key_step: k_baxt_fill and

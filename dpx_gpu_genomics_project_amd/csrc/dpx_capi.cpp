@@ -504,13 +504,15 @@ struct dpx_batch : dpx_plan {
     uint64_t cigarOps = 0;     /* total number of ops (state 2) */
     /* BAXT's extension mode (dpx_batch_set_extension): the next fill runs k_zext_fill while either value is >= 0 */
     int32_t zdrop = -1, endBonus = -1;
-    bool extFilled = false;    /* the last fill ran k_zext_fill / k_zsub_fill: dExt holds its records and dpx_batch_matrix masks behind lastDiag */
+    bool extFilled = false;    /* the last fill ran the extension scan (k_zext_fill, k_zsub_fill, k_bdx_fill with zdrop or endBonus on): dExt holds its
+                                  records, and dpx_batch_matrix / dpx_batch_directions mask behind lastDiag */
     int32_t *dExt = nullptr;   /* device: dpx_extension[numPairs] */
     size_t dExtCap = 0;
     /* substitution table (dpx_batch_set_substitution): while substAlphabet > 0 the fills run k_subst_fill and the walks k_subst_traceback* */
     int substAlphabet = 0;
     unsigned char *dSubst = nullptr; /* device: the table at row stride 32 (DPX_SUBST_TABLE_BYTES), then codeOf[256] */
     size_t dSubstCap = 0;
+    std::vector<unsigned char> bdxImage; /* dpx_batch_set_direction_scoring: the image dSubst holds, to tell a changed table from the same one */
     PoolRecord poolRec;    /* how the matrix pool behind dMat was built / timed */
     bool tunePool = false, tuneShop = false; /* DPX_TUNE_PLACEMENT: the pool is timed / shopped for at the end of dpx_batch_create */
 };
@@ -1073,6 +1075,14 @@ static hipError_t launch_main(dpx_batch *b, const dpx_route &r, hipStream_t s) {
         return dpx_launch_zsub_fill(za, b->R, b->store, subst_lds_bytes(b), s);
     }
     case DPX_MAIN_BDIR: return dpx_launch_bdir_fill(b->args, b->R, r.ext, s);
+    case DPX_MAIN_BDX: { /* (dpx_batch_set_direction_scoring: with a table every wave's LDS slice grows by the image, and the workgroup may shrink to one wave) */
+        dpx_bdx_args xa = {b->args, nullptr, nullptr, r.ext ? b->zdrop : -1, r.ext ? b->endBonus : -1, b->dExt};
+        if (b->substAlphabet) {
+            xa.table = reinterpret_cast<const int8_t *>(b->dSubst); xa.codeOf = b->dSubst + DPX_SUBST_TABLE_BYTES;
+            xa.f.ldsPerWave += DPX_SUBST_IMAGE_BYTES; xa.f.wavesPerBlock = dpx_plan_bdx_waves(*b, true);
+        }
+        return dpx_launch_bdx_fill(xa, b->R, r.ext, s);
+    }
     }
     return hipErrorInvalidValue;
 }
@@ -1251,7 +1261,14 @@ int dpx_batch_directions(dpx_batch *b, size_t pair, int which, uint8_t *out) {
     if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
     if (e == hipSuccess) e = hipMemcpy(out, dOut, total, hipMemcpyDeviceToHost);
     g_tbDevCache.park(dOut, dOutCap);
+    dpx_extension rec{};
+    if (e == hipSuccess && b->bandDirs && b->extFilled) e = hipMemcpy(&rec, b->dExt + pair * (sizeof rec / sizeof(int32_t)), sizeof rec, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail(e, "dpx_batch_directions");
+    if (b->bandDirs && b->extFilled && rec.lastDiag < pd.m + pd.n) {
+        /* a z-dropped pair: k_bdx_fill stopped on anti-diagonal lastDiag, and the codes behind it are whatever the pool held before */
+        for (int i = 0; i <= pd.m; i++)
+            for (int j = std::max(rec.lastDiag - i + 1, 0); j <= pd.n; j++) out[(size_t)i * (size_t)(pd.n + 1) + (size_t)j] = 0;
+    }
     return DPX_OK;
 }
 
@@ -1290,7 +1307,7 @@ int dpx_batch_matrix(dpx_batch *b, size_t pair, int which, int16_t *out) {
 int dpx_batch_set_extension(dpx_batch *b, int32_t zdrop, int32_t endBonus) {
     if (!b || zdrop < -1 || zdrop > (1 << 30) || endBonus < -1 || endBonus > (1 << 30)) return DPX_ERR_INVALID;
     if (b->prm.algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED;
-    if (b->bandDirs) return DPX_ERR_UNSUPPORTED; /* extension mode on a band-direction batch: not built */
+    if (b->bandDirs) return DPX_ERR_UNSUPPORTED; /* refused by design (tests pin it): dpx_batch_set_direction_scoring is a band-direction batch's setter */
     if ((zdrop >= 0 || endBonus >= 0) && b->substAlphabet) return DPX_ERR_UNSUPPORTED; /* (the two go together through dpx_batch_set_extension_table only) */
     int rc = bind_device(b->device);
     if (rc != DPX_OK) return rc;
@@ -1306,7 +1323,7 @@ static int check_substitution(const dpx_batch *b, int32_t alphabet, const uint8_
     if (alphabet < 1 || alphabet > 32 || !codeOf) return DPX_ERR_INVALID;
     for (int x = 0; x < 256; x++) if ((int)codeOf[x] >= alphabet) return DPX_ERR_INVALID;
     if (b->prm.algo != DPX_ALGO_BANW && b->prm.algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED;
-    if (b->kernelAlgo != b->prm.algo || b->dirs || b->bandDirs) return DPX_ERR_UNSUPPORTED; /* (band directions: not built;) a covering BANW band runs as ANW, which has no table kernel */
+    if (b->kernelAlgo != b->prm.algo || b->dirs || b->bandDirs) return DPX_ERR_UNSUPPORTED; /* band directions: refused by design, dpx_batch_set_direction_scoring is their setter; a covering BANW band runs as ANW, which has no table kernel */
     return DPX_OK;
 }
 static int check_substitution_fit(const dpx_batch *b, const int8_t *scores, int32_t alphabet) {
@@ -1365,6 +1382,50 @@ int dpx_batch_set_extension_table(dpx_batch *b, int32_t zdrop, int32_t endBonus,
     if (!b->dExt && b->numPairs) HIP_TRY(g_tbDevCache.take((void **)&b->dExt, b->numPairs * sizeof(dpx_extension), &b->dExtCap));
     rc = upload_substitution(b, scores, alphabet, codeOf);
     if (rc != DPX_OK) return rc;
+    b->zdrop = zdrop;
+    b->endBonus = endBonus;
+    return DPX_OK;
+}
+
+/* all scoring of a band-direction batch, the three settings at once; every check comes before the first change */
+int dpx_batch_set_direction_scoring(dpx_batch *b, int32_t zdrop, int32_t endBonus, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf) {
+    if (!b || zdrop < -1 || zdrop > (1 << 30) || endBonus < -1 || endBonus > (1 << 30)) return DPX_ERR_INVALID;
+    if (scores) {
+        if (alphabet < 1 || alphabet > 32 || !codeOf) return DPX_ERR_INVALID;
+        for (int x = 0; x < 256; x++) if ((int)codeOf[x] >= alphabet) return DPX_ERR_INVALID;
+    }
+    if (!b->bandDirs) return DPX_ERR_UNSUPPORTED; /* matrix and score-only batches, the other algorithms, a covering BANW band (k_affine_dir) */
+    const bool scan = zdrop >= 0 || endBonus >= 0;
+    if (scan && b->prm.algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED;
+    unsigned char image[DPX_SUBST_IMAGE_BYTES];
+    if (scores) {
+        if (!dpx_plan_bdx_waves(*b, true)) return DPX_ERR_UNSUPPORTED; /* one wave's staged strings leave no room in LDS for the table image */
+        /* fits_dir with the largest entry in place of match and the smallest in place of mismatch.  (With int8 entries and strings that
+         * fit LDS this can only refuse a batch that its creation's own check admitted at its very limit.) */
+        dpx_params q = b->prm;
+        q.match = -128; q.mismatch = 127;
+        for (int k = 0; k < alphabet * alphabet; k++) { q.match = std::max<int32_t>(q.match, scores[k]); q.mismatch = std::min<int32_t>(q.mismatch, scores[k]); }
+        for (const dpx_pair_dev &pd : b->pairs) if (!fits_dir(q, pd.m, pd.n)) return DPX_ERR_RANGE;
+        memset(image, 0, sizeof image);
+        for (int r = 0; r < alphabet; r++) memcpy(image + r * 32, scores + r * alphabet, (size_t)alphabet);
+        memcpy(image + DPX_SUBST_TABLE_BYTES, codeOf, 256);
+    }
+    int rc = bind_device(b->device);
+    if (rc != DPX_OK) return rc;
+    const bool sameTable = scores ? (b->substAlphabet == alphabet && b->bdxImage.size() == sizeof image && !memcmp(b->bdxImage.data(), image, sizeof image))
+                                  : b->substAlphabet == 0;
+    if (scan && !b->dExt && b->numPairs) HIP_TRY(g_tbDevCache.take((void **)&b->dExt, b->numPairs * sizeof(dpx_extension), &b->dExtCap));
+    if (scores && !sameTable) {
+        if (!b->dSubst) HIP_TRY(g_tbDevCache.take((void **)&b->dSubst, sizeof image, &b->dSubstCap));
+        /* a fill in flight may still read the previous table */
+        if (b->lastStream && b->lastStream != b->stream) HIP_TRY(hipStreamSynchronize(b->lastStream));
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        HIP_TRY(hipMemcpy(b->dSubst, image, sizeof image, hipMemcpyHostToDevice));
+        b->bdxImage.assign(image, image + sizeof image);
+    }
+    if (!sameTable || zdrop != b->zdrop || endBonus != b->endBonus) invalidate_fill(b);
+    b->substAlphabet = scores ? alphabet : 0;
+    if (!scores) b->bdxImage.clear();
     b->zdrop = zdrop;
     b->endBonus = endBonus;
     return DPX_OK;

@@ -111,6 +111,19 @@ typedef struct dpx_zsub_args {
     int32_t *ext;
 } dpx_zsub_args;
 hipError_t dpx_launch_zsub_fill(const dpx_zsub_args &a, int C, bool store, size_t ldsBytes, hipStream_t stream);
+/* A band-direction batch (dpx_banddir.h) under dpx_batch_set_direction_scoring (dpx_bdx_kernels.hip, k_bdx_fill): k_bdir_fill's cells,
+ * codes and stores with the diagonal term from a table (`table` / `codeOf` as in dpx_subst_args, both NULL: byte compare) and, `ext`
+ * only, BAXT's extension mode (zdrop / endBonus / ext as in dpx_zext_args; both -1: off).  At least one of the two is on; BANW takes a
+ * table only.  With a table f.ldsPerWave includes DPX_SUBST_IMAGE_BYTES behind the staged strings; the launch asks for f.ldsPerWave *
+ * f.wavesPerBlock bytes of LDS, as dpx_launch_bdir_fill does.  Walk and export are dpx_launch_bdir_traceback / _export. */
+typedef struct dpx_bdx_args {
+    dpx_fill_args f;
+    const int8_t *table;
+    const uint8_t *codeOf;
+    int32_t zdrop, endBonus;
+    int32_t *ext;
+} dpx_bdx_args;
+hipError_t dpx_launch_bdx_fill(const dpx_bdx_args &a, int C, bool ext, hipStream_t stream);
 hipError_t dpx_launch_unpack2(const uint32_t *packed, uint32_t alphabet, char *out, size_t numDwords, hipStream_t stream);
 hipError_t dpx_launch_prim_eval(const int32_t *op, const uint32_t *a, const uint32_t *b, const uint32_t *c, size_t count,
                                 uint32_t *res, uint32_t *pred, hipStream_t stream);

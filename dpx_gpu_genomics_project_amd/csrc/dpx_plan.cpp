@@ -673,8 +673,9 @@ dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus,
     const int family = algo == DPX_ALGO_ANW ? 1 : algo == DPX_ALGO_ASW ? 2 : algo == DPX_ALGO_ASG ? 3 : 0;
     if (p.dirs) {
         r.dirs = true; r.kernel = dir[family];
-    } else if (p.bandDirs) {
-        r.main = DPX_MAIN_BDIR; r.kernel = DPX_K_BDIR_FILL;
+    } else if (p.bandDirs) { /* (a mode comes through dpx_batch_set_direction_scoring only; extension mode is BAXT's) */
+        const bool bdx = extension || substAlphabet;
+        r.main = bdx ? DPX_MAIN_BDX : DPX_MAIN_BDIR; r.kernel = bdx ? DPX_K_BDX_FILL : DPX_K_BDIR_FILL;
     } else if (substAlphabet) { /* (set only on batches whose kernel is BANW's or BAXT's; with extension mode: dpx_batch_set_extension_table) */
         r.main = extension ? DPX_MAIN_ZSUB : DPX_MAIN_SUBST; r.kernel = extension ? DPX_K_ZSUB_FILL : DPX_K_SUBST_FILL;
     } else if (algo == DPX_ALGO_BAXT) {
@@ -692,7 +693,7 @@ dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus,
                    : family ? (p.lanePacked ? lanes[family] : fill[family])
                    : p.packed ? DPX_K_LINEAR_FILL_PK : p.lanesPk ? DPX_K_LINEAR_LANES_PK : p.lanePacked ? DPX_K_LINEAR_LANES : p.split ? DPX_K_LINEAR_SPLIT : DPX_K_LINEAR_FILL;
     }
-    r.extRecords = r.main == DPX_MAIN_ZEXT || r.main == DPX_MAIN_ZSUB;
+    r.extRecords = r.main == DPX_MAIN_ZEXT || r.main == DPX_MAIN_ZSUB || (r.main == DPX_MAIN_BDX && extension);
     r.walk = p.bandDirs ? DPX_WALK_BDIR : substAlphabet ? DPX_WALK_SUBST : algo == DPX_ALGO_BASW ? DPX_WALK_BASW : is_banw_layout(algo) ? DPX_WALK_BANW
              : p.dirs ? DPX_WALK_DIR : DPX_WALK_PLAIN;
     r.walkMode = (r.walk == DPX_WALK_BDIR || r.walk == DPX_WALK_DIR) ? 0 : walk_mode(p, tbWalk); /* (one walk: DPX_TB_WALK has no effect) */
@@ -700,12 +701,19 @@ dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus,
     return r;
 }
 
+unsigned dpx_plan_bdx_waves(const dpx_plan &p, bool table) {
+    if (!table) return p.args.wavesPerBlock;
+    const size_t perWave = (size_t)p.args.ldsPerWave + DPX_SUBST_IMAGE_BYTES;
+    if (perWave > kLdsMax) return 0u;
+    return perWave * (DPX_FILL_THREADS / 64) > kLdsMax ? 1u : p.args.wavesPerBlock;
+}
+
 const char *dpx_route_kernel_name(dpx_fill_kernel k) {
     static const char *const names[DPX_K_COUNT] = {
         "k_linear_fill", "k_linear_fill_pk", "k_linear_lanes", "k_linear_lanes_pk", "k_linear_split",
         "k_affine_fill", "k_asw_fill", "k_asg_fill", "k_affine_lanes", "k_asw_lanes", "k_asg_lanes",
         "k_banded_fill", "k_banded_fill_pk", "k_basw_fill", "k_banw_fill", "k_baxt_fill",
-        "k_zext_fill", "k_subst_fill", "k_zsub_fill", "k_bdir_fill",
+        "k_zext_fill", "k_subst_fill", "k_zsub_fill", "k_bdir_fill", "k_bdx_fill",
         "k_linear_dir", "k_affine_dir", "k_asw_dir", "k_asg_dir"};
     return k >= 0 && k < DPX_K_COUNT ? names[k] : "?";
 }
@@ -734,7 +742,7 @@ int dpx_plan_describe(const dpx_plan &b, int tbWalk, int zdrop, int endBonus, in
     int len = snprintf(buf, cap, "algo=%s kernel_algo=%s kernel=%s dtype=%s rows_per_lane=%d store=%d couples=%zu lane_pairs=%zu waves=%zu singles=%zu row_tags=%d seq_input=%s waves_per_workgroup=%u",
                        name(b.prm.algo), name(b.kernelAlgo), dpx_route_kernel_name(r.kernel), (b.packed || b.lanesPk) ? "int16" : "int32", b.R, b.store ? 1 : 0, b.nCouples, b.nLanePairs,
                        b.nWaves, b.nSingles, (int)b.pkArgs.rowTags, b.packed2 ? "packed2" : "bytes",
-                       b.dirs ? b.dirArgs.wavesPerBlock : (b.packed || b.lanePacked) ? b.pkArgs.wavesPerBlock : b.split ? (unsigned)b.splitWaves : b.args.wavesPerBlock);
+                       b.dirs ? b.dirArgs.wavesPerBlock : (b.packed || b.lanePacked) ? b.pkArgs.wavesPerBlock : b.split ? (unsigned)b.splitWaves : b.bandDirs ? dpx_plan_bdx_waves(b, substAlphabet != 0) : b.args.wavesPerBlock);
     if (is_banded_affine(b.kernelAlgo) && len > 0 && (size_t)len < cap) /* which walk the batch's traceback takes */
         len += snprintf(buf + len, cap - (size_t)len, " traceback=%s", dpx_route_walk_name(r.walk, r.walkMode));
     if (extension && len > 0 && (size_t)len < cap)

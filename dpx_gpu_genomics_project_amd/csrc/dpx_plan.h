@@ -85,10 +85,10 @@ enum dpx_fill_kernel { /* the kernel that fills (most of) the batch: describe's 
     DPX_K_LINEAR_FILL, DPX_K_LINEAR_FILL_PK, DPX_K_LINEAR_LANES, DPX_K_LINEAR_LANES_PK, DPX_K_LINEAR_SPLIT,
     DPX_K_AFFINE_FILL, DPX_K_ASW_FILL, DPX_K_ASG_FILL, DPX_K_AFFINE_LANES, DPX_K_ASW_LANES, DPX_K_ASG_LANES,
     DPX_K_BANDED_FILL, DPX_K_BANDED_FILL_PK, DPX_K_BASW_FILL, DPX_K_BANW_FILL, DPX_K_BAXT_FILL,
-    DPX_K_ZEXT_FILL, DPX_K_SUBST_FILL, DPX_K_ZSUB_FILL, DPX_K_BDIR_FILL,
+    DPX_K_ZEXT_FILL, DPX_K_SUBST_FILL, DPX_K_ZSUB_FILL, DPX_K_BDIR_FILL, DPX_K_BDX_FILL,
     DPX_K_LINEAR_DIR, DPX_K_AFFINE_DIR, DPX_K_ASW_DIR, DPX_K_ASG_DIR, DPX_K_COUNT
 };
-enum dpx_main_launch { DPX_MAIN_NONE, DPX_MAIN_FILL, DPX_MAIN_BASW, DPX_MAIN_BANW, DPX_MAIN_BAXT, DPX_MAIN_ZEXT, DPX_MAIN_SUBST, DPX_MAIN_ZSUB, DPX_MAIN_BDIR };
+enum dpx_main_launch { DPX_MAIN_NONE, DPX_MAIN_FILL, DPX_MAIN_BASW, DPX_MAIN_BANW, DPX_MAIN_BAXT, DPX_MAIN_ZEXT, DPX_MAIN_SUBST, DPX_MAIN_ZSUB, DPX_MAIN_BDIR, DPX_MAIN_BDX };
 enum dpx_second_launch { DPX_SECOND_NONE, DPX_SECOND_PACKED, DPX_SECOND_BANDED_PACKED, DPX_SECOND_LANES, DPX_SECOND_LANES_PK };
 enum dpx_walk_family { DPX_WALK_PLAIN, DPX_WALK_DIR, DPX_WALK_BASW, DPX_WALK_BANW, DPX_WALK_SUBST, DPX_WALK_BDIR };
 enum dpx_export_kind { DPX_EXPORT_PLAIN, DPX_EXPORT_BASW, DPX_EXPORT_BANW };
@@ -100,14 +100,20 @@ struct dpx_route {
     dpx_second_launch second;
     dpx_main_launch main;
     bool ext;        /* the band kernel (BDIR, SUBST) runs BAXT's end-cell rule, not BANW's */
-    bool extRecords; /* the fill writes a dpx_extension record per pair (k_zext_fill, k_zsub_fill) */
+    bool extRecords; /* the fill writes a dpx_extension record per pair (k_zext_fill, k_zsub_fill, k_bdx_fill with its scan on) */
     dpx_walk_family walk;
     int walkMode;    /* 0 / 1: one lane per pair, cell by cell / through cached column vectors; 2: one wave per pair (DIR and BDIR have one walk: 0) */
     dpx_export_kind exportKind;
 };
 /* What a batch can change after its creation comes as arguments: the traceback walk knob, BAXT's extension mode (-1, -1: off) and the
- * substitution alphabet (0: none). */
+ * substitution alphabet (0: none).  On a bandDirs plan either of the two (dpx_batch_set_direction_scoring) turns k_bdir_fill into
+ * k_bdx_fill; the walk stays k_bdir_traceback. */
 dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus, int substAlphabet);
+/* Waves per workgroup of a bandDirs plan's fill: the plan's own without a table; with one (DPX_SUBST_IMAGE_BYTES more per wave) the
+ * plan's own when four waves' strings and images fit one workgroup's LDS, else 1, and 0 when not even one wave's fit (the setter
+ * refuses).  The plan's own is 1 or 4 (fill_waves_per_block: DPX_WPB takes no other value), so "four do not fit" and "the plan's own do
+ * not fit" are the same test wherever it matters.  A pure function of the plan, which is not changed. */
+unsigned dpx_plan_bdx_waves(const dpx_plan &p, bool table);
 const char *dpx_route_kernel_name(dpx_fill_kernel k);
 const char *dpx_route_walk_name(dpx_walk_family walk, int walkMode);
 

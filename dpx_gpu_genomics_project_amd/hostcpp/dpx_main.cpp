@@ -17,6 +17,8 @@
 // -match / -mismatch.  NCBI text format: '#' lines are comments; one header row of 1..32 single-character column letters; then one row
 // per letter: the letter, then that many integers in -128..127.  The row letter is the REFERENCE's.  A lower-case byte takes its
 // upper-case letter's code, every other unlisted byte the last letter's ('*' in NCBI files, 'N' in a DNA file).
+// -directions with -algo BANW|BAXT keeps band direction codes (DPX_KEEP_BAND_DIRECTIONS); -zdrop / -endbonus / -matrix then go through
+// dpx_batch_set_direction_scoring (k_bdx_fill) and print what the run without -directions prints.
 //
 // Batch size: by default from a matrix-pool BUDGET (-pool-gb, 4 GiB): as many pairs as fit the budget, at most 20000 (the
 // reference sizes its buffers once for BATCH_SIZE = 10000 reads of 150 bases, cuda/LNW/LinearNeedlemanWunschV9.cu:26-46,
@@ -120,7 +122,8 @@ bool read_matrix(const char *path, std::vector<int8_t> &scores, int &alphabet, u
 static void usage() {
     fprintf(stderr, "usage: dpx_main -pairs <InSeqFile> -match <matchWeight> -mismatch <mismatchWeight> -open <gapWeight> "
                     "[-extend <gapExtend>] [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band <B>] [-batch <N>] [-device <D>] [-noprint] [-cigar [M]] "
-                    "[-zdrop <Z>] [-endbonus <E>] (BAXT only) [-matrix <file>] (BANW / BAXT, not with -zdrop / -endbonus)\n");
+                    "[-zdrop <Z>] [-endbonus <E>] (BAXT only) [-matrix <file>] (BANW / BAXT, not with -zdrop / -endbonus) "
+                    "[-directions] (direction codes instead of score matrices; BANW / BAXT: with -zdrop / -endbonus / -matrix too)\n");
     exit(EXIT_FAILURE);
 }
 
@@ -355,8 +358,14 @@ int main(int argc, char *argv[]) {
                         : dpx_batch_create(&prm, sequences, fileInfo.numBytes, reinterpret_cast<const dpx_seq_pair *>(sequenceIdxs), first, next.count,
                                            flags, &next.b);
         if (prc != DPX_OK) die("FAILED TO CREATE DEVICE BATCH", prc);
-        if ((zdrop != -1 || endBonus != -1) && (prc = dpx_batch_set_extension(next.b, zdrop, endBonus)) != DPX_OK) die("FAILED TO SET THE EXTENSION MODE", prc);
-        if (matrixFile && (prc = dpx_batch_set_substitution(next.b, substScores.data(), substAlphabet, substCode)) != DPX_OK) die("FAILED TO SET THE SUBSTITUTION MATRIX", prc);
+        if (bandDirections) { // the one setter of a band-direction batch: the two below refuse it
+            if ((zdrop != -1 || endBonus != -1 || matrixFile) &&
+                (prc = dpx_batch_set_direction_scoring(next.b, zdrop, endBonus, matrixFile ? substScores.data() : nullptr, substAlphabet, substCode)) != DPX_OK)
+                die(matrixFile ? "FAILED TO SET THE SUBSTITUTION MATRIX" : "FAILED TO SET THE EXTENSION MODE", prc);
+        } else {
+            if ((zdrop != -1 || endBonus != -1) && (prc = dpx_batch_set_extension(next.b, zdrop, endBonus)) != DPX_OK) die("FAILED TO SET THE EXTENSION MODE", prc);
+            if (matrixFile && (prc = dpx_batch_set_substitution(next.b, substScores.data(), substAlphabet, substCode)) != DPX_OK) die("FAILED TO SET THE SUBSTITUTION MATRIX", prc);
+        }
         create_time += get_time() - t0;
         if ((prc = dpx_batch_fill(next.b, nullptr)) != DPX_OK) die("KERNEL LAUNCH FAILED", prc);
         // global pair numbers: shardFirst + index inside the shard

@@ -209,7 +209,7 @@ typedef struct dpx_params {
                                     |m - n| < B unchanged, as for matrix batches.  A BANW band that covers the matrix (B >= max(m, n) + 1)
                                     runs as an ANW DPX_KEEP_DIRECTIONS batch (kernel_algo=ANW), the fall-back the matrix batch takes.
                                     dpx_batch_set_extension and dpx_batch_set_substitution on such a batch: DPX_ERR_UNSUPPORTED, the batch is
-                                    left as it was (both are follow-ups).  DPX_TIME_FILLS, dpx_batch_fill_timed, repeated fills, a caller's
+                                    left as it was (both keep refusing: dpx_batch_set_direction_scoring is the way in).  DPX_TIME_FILLS, dpx_batch_fill_timed, repeated fills, a caller's
                                     stream, dpx_batch_create_on, packed2 input, the output pipeline and dpx_batch_cigars_* as for a BANW
                                     matrix batch; DPX_TB_WALK has no effect (one walk, k_bdir_traceback).  Strings are staged in LDS as for
                                     BANW; where four waves' strings do not fit a workgroup the fill runs one-wave workgroups, and a pair
@@ -444,7 +444,7 @@ typedef struct dpx_extension {      /* 32 bytes */
  * DPX_ERR_UNSUPPORTED; a value below -1 or above 1 << 30: DPX_ERR_INVALID.  (-1, -1) returns the batch to plain BAXT (k_baxt_fill).
  * While either value is >= 0 the fill runs k_zext_fill and dpx_batch_describe adds `zdrop=` and `end_bonus=`.  Matrix and
  * DPX_SCORE_ONLY batches, packed2 input, dpx_batch_create_on and a caller's stream as for BAXT.  A DPX_KEEP_BAND_DIRECTIONS batch:
- * DPX_ERR_UNSUPPORTED (a follow-up), the batch is left as it was. */
+ * DPX_ERR_UNSUPPORTED, the batch is left as it was (this setter keeps refusing: dpx_batch_set_direction_scoring is the way in). */
 int dpx_batch_set_extension(dpx_batch *b, int32_t zdrop, int32_t endBonus);
 /* numPairs records into host memory.  DPX_ERR_NOT_FILLED before a fill; DPX_ERR_UNSUPPORTED when the last fill ran without
  * extension mode. */
@@ -470,7 +470,8 @@ int dpx_batch_extensions(dpx_batch *b, dpx_extension *out);
  *                        of match and the smallest in place of mismatch
  * While a table is set dpx_batch_describe reports kernel=k_subst_fill, traceback=k_subst_traceback_wave / k_subst_traceback and adds
  * ` subst=<alphabet>`.  Matrix and DPX_SCORE_ONLY batches, packed2 input, dpx_batch_create_on and a caller's stream as for BAXT.  A
- * DPX_KEEP_BAND_DIRECTIONS batch: DPX_ERR_UNSUPPORTED (a follow-up), the batch is left as it was. */
+ * DPX_KEEP_BAND_DIRECTIONS batch: DPX_ERR_UNSUPPORTED, the batch is left as it was (this setter keeps refusing:
+ * dpx_batch_set_direction_scoring is the way in). */
 int dpx_batch_set_substitution(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf /* 256 entries */);
 
 /* ---- BAXT extension mode under a substitution table: both of the above at once ----
@@ -489,8 +490,8 @@ int dpx_batch_set_substitution(dpx_batch *b, const int8_t *scores, int32_t alpha
  * zdrop, endBonus: dpx_batch_set_extension's values; scores, alphabet, codeOf: dpx_batch_set_substitution's (copied at the call).
  *   DPX_ERR_INVALID      b == NULL; scores == NULL or codeOf == NULL; alphabet outside 1..32; a codeOf[x] >= alphabet; zdrop or endBonus
  *                        below -1 or above 1 << 30; both zdrop and endBonus -1 (nothing to combine: dpx_batch_set_substitution does that)
- *   DPX_ERR_UNSUPPORTED  an algorithm other than BAXT; a DPX_KEEP_BAND_DIRECTIONS batch (a follow-up); a batch whose staged sequences
- *                        leave no room in LDS for the table
+ *   DPX_ERR_UNSUPPORTED  an algorithm other than BAXT; a DPX_KEEP_BAND_DIRECTIONS batch (this setter keeps refusing:
+ *                        dpx_batch_set_direction_scoring is the way in); a batch whose staged sequences leave no room in LDS for the table
  *   DPX_ERR_RANGE        dpx_batch_set_substitution's range check fails
  * A refused call leaves both settings of the batch as they were.  Legal in any state; it replaces both settings, applies to every
  * following fill and, as dpx_batch_set_substitution, invalidates lines, text, CIGARs and results of an earlier fill
@@ -508,6 +509,38 @@ int dpx_batch_set_substitution(dpx_batch *b, const int8_t *scores, int32_t alpha
  * To change Z, E or the table of a combined batch, call this function again. */
 int dpx_batch_set_extension_table(dpx_batch *b, int32_t zdrop, int32_t endBonus,
                                   const int8_t *scores, int32_t alphabet, const uint8_t *codeOf /* 256 entries */);
+
+/* ---- scoring of a DPX_KEEP_BAND_DIRECTIONS batch: substitution table, z-drop and end bonus ----
+ * Band-direction batches are the storage mode of BANW / BAXT that runs long reads (int32 cells, no m + n limit); this function gives
+ * them the other half of a mapper's extension step.  The three setters above refuse such a batch with DPX_ERR_UNSUPPORTED and keep
+ * doing so; this is ONE setter for all scoring of a band-direction batch.  A new exported symbol, no ABI bump and no new flag: detect
+ * it by the symbol.  It accepts a batch only when dpx_batch_describe says kernel=k_bdir_fill (or, after an earlier call, k_bdx_fill).
+ *     scores == NULL           no table; alphabet and codeOf are ignored.  Otherwise dpx_batch_set_substitution's arrays, copied at the call.
+ *     zdrop, endBonus          dpx_batch_set_extension's values, -1 = off (BAXT only).
+ *     everything off           the batch runs plain k_bdir_fill again.
+ * The call replaces all three settings at once and applies to every following fill.  If any setting changed it invalidates lines,
+ * text, CIGARs and results of an earlier fill as dpx_batch_set_substitution does (DPX_ERR_NOT_FILLED until the next fill,
+ * dpx_batch_extensions included).  A refused call changes nothing: dpx_batch_describe is byte-identical before and after.
+ * The definitions are the blocks above, word for word, over the same cells: substitution-matrix scoring, BAXT extension mode, and
+ * their conjunction.  Nothing about the scan, the record, the end-bonus choice or the text changes.
+ *   DPX_ERR_INVALID      b == NULL; zdrop or endBonus below -1 or above 1 << 30; with scores != NULL: alphabet outside 1..32,
+ *                        codeOf == NULL, or a codeOf[x] >= alphabet
+ *   DPX_ERR_UNSUPPORTED  a batch that is not a band-direction batch (matrix and score-only batches, every other algorithm, a covering
+ *                        BANW band that runs as k_affine_dir); zdrop >= 0 or endBonus >= 0 on BANW; one wave's staged strings plus the
+ *                        table image exceed one workgroup's LDS
+ *   DPX_ERR_RANGE        the create-time range check of a band-direction batch (bounds against 2^28) fails for a pair with the table's
+ *                        largest entry in place of match and its smallest in place of mismatch.  With int8 entries and strings that
+ *                        fit LDS this can only happen where the creation's own check was already at its limit.
+ * While a mode is on: the fill runs k_bdx_fill (dpx_batch_describe: kernel=k_bdx_fill traceback=k_bdir_traceback matrix=banddir4,
+ * with ` zdrop=` / ` end_bonus=` / ` subst=` exactly as a matrix batch prints them); with a table, where four waves' strings plus
+ * table images do not fit a workgroup the fill runs one-wave workgroups (waves_per_workgroup says what will launch).
+ * dpx_batch_extensions returns the records after a fill that ran the scan (zdrop or endBonus on) and DPX_ERR_UNSUPPORTED after one
+ * that did not.  dpx_batch_results, dpx_batch_device_results, dpx_batch_traceback, the text pipeline and dpx_batch_cigars_* see the
+ * chosen score and end cell.  dpx_batch_directions gives the enum export with every plane 0 where i + j > lastDiag; under a table the
+ * H plane's MATCH / MISMATCH stays byte equality.  Repeated fills, DPX_TIME_FILLS, dpx_batch_fill_timed, a caller's stream,
+ * dpx_batch_create_on and packed2 input as for a BANW band-direction batch. */
+int dpx_batch_set_direction_scoring(dpx_batch *b, int32_t zdrop, int32_t endBonus,
+                                    const int8_t *scores, int32_t alphabet, const uint8_t *codeOf /* 256 entries */);
 
 /* Sizes: numPairs, total cells (sum refLen*queryLen, the reference's numCells, c++/parseInput.cpp:100),
  * bytes of HBM the matrices occupy, algorithmic bytes of one fill. */
