@@ -17,7 +17,9 @@ ALGO_NAMES = {ALGO_LNW: "LNW", ALGO_LSW: "LSW", ALGO_ANW: "ANW", ALGO_BSW: "BSW"
               ALGO_BANW: "BANW", ALGO_BAXT: "BAXT"}
 KEEP_MATRICES, SCORE_ONLY, TIME_FILLS, TUNE_PLACEMENT, KEEP_DIRECTIONS = 0x0, 0x1, 0x2, 0x4, 0x8
 KEEP_BAND_DIRECTIONS = 0x10  # BANW / BAXT: 4-bit direction codes per in-band cell, int32 scores (0x8 stays refused on banded algorithms)
+TWO_PIECE_GAPS = 0x20  # with KEEP_BAND_DIRECTIONS: a second gap piece (Batch.set_second_gap), 8-bit codes, bands up to 256
 MAT_H, MAT_I, MAT_D = 0, 1, 2
+MAT_I2, MAT_D2, MAT_H_PIECE = 3, 4, 5  # Batch.directions on a TWO_PIECE_GAPS batch: piece 2's planes, and the piece of H's gap move
 # CIGARs (dpx_batch_cigars_begin / _end): an op is (length << 4) | code with BAM's code numbers
 CIGAR_OP_M, CIGAR_OP_I, CIGAR_OP_D, CIGAR_OP_EQ, CIGAR_OP_X = 0, 1, 2, 7, 8
 CIGAR_EXTENDED, CIGAR_M = 0x0, 0x1
@@ -36,6 +38,7 @@ ABI_SYMBOLS = (
     "dpx_batch_info", "dpx_batch_describe", "dpx_batch_destroy", "dpx_align_batch", "dpx_prim_eval", "dpx_batch_directions",
     "dpx_batch_cigars_begin", "dpx_batch_cigars_end", "dpx_cigar_text", "dpx_batch_set_extension", "dpx_batch_extensions",
     "dpx_batch_set_substitution", "dpx_batch_set_extension_table", "dpx_batch_set_direction_scoring",
+    "dpx_batch_set_second_gap",
 )
 # declared entry points a library may lack and still load (an older build): checked when they are called
 OPTIONAL_SYMBOLS = ("dpx_batch_directions",)
@@ -129,6 +132,7 @@ def load() -> C.CDLL:
     lib.dpx_batch_set_substitution.argtypes = [vp, vp, C.c_int32, vp]
     lib.dpx_batch_set_extension_table.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, vp]
     lib.dpx_batch_set_direction_scoring.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, vp]
+    lib.dpx_batch_set_second_gap.argtypes = [vp, C.c_int32, C.c_int32]
     for name in ABI_SYMBOLS:  # every declared entry point must be exported (the optional ones by libraries that have them)
         if name not in OPTIONAL_SYMBOLS:
             getattr(lib, name)
@@ -312,6 +316,12 @@ class Batch:
         tab, code = _table_arrays(scores, code_of)
         _check(self._lib.dpx_batch_set_direction_scoring(self._h, zdrop, end_bonus, tab.ctypes.data, tab.shape[0], code.ctypes.data),
                "dpx_batch_set_direction_scoring")
+
+    def set_second_gap(self, gap_open2: int, gap_extend2: int) -> None:
+        """TWO_PIECE_GAPS batches only: the second gap piece of the following fills; a gap of length k then scores
+        max(gap_open + k * gap_extend, gap_open2 + k * gap_extend2).  Lines and results of an earlier fill are invalid afterwards when a
+        value changed."""
+        _check(self._lib.dpx_batch_set_second_gap(self._h, gap_open2, gap_extend2), "dpx_batch_set_second_gap")
 
     def extensions(self) -> np.ndarray:
         """One EXTENSION_DTYPE record per pair of the last fill, which must have run in extension mode."""

@@ -871,6 +871,7 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
     const bool dirFlag = (flags & DPX_KEEP_DIRECTIONS) != 0, bandDirFlag = (flags & DPX_KEEP_BAND_DIRECTIONS) != 0;
     if ((dirFlag || bandDirFlag) && (flags & DPX_SCORE_ONLY)) return DPX_ERR_INVALID;
     if (dirFlag && is_banded(params->algo)) return DPX_ERR_UNSUPPORTED; /* 0x8 on a banded algorithm stays refused, with or without 0x10 */
+    if ((flags & DPX_TWO_PIECE_GAPS) && !bandDirFlag) return DPX_ERR_INVALID; /* the second gap piece exists on band-direction batches only */
     if (bandDirFlag && params->algo != DPX_ALGO_BANW && params->algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED; /* (BSW / BASW: not built) */
     rc = bind_device(device);
     if (rc != DPX_OK) return rc;
@@ -1083,6 +1084,14 @@ static hipError_t launch_main(dpx_batch *b, const dpx_route &r, hipStream_t s) {
         }
         return dpx_launch_bdx_fill(xa, b->R, r.ext, s);
     }
+    case DPX_MAIN_BD2: { /* (a two-piece batch: every mode, "nothing on" included, is k_bd2_fill's; the table's LDS as for k_bdx_fill) */
+        dpx_bd2_args xa = {b->args, nullptr, nullptr, r.ext ? b->zdrop : -1, r.ext ? b->endBonus : -1, b->dExt, b->gapOpen2, b->gapExtend2};
+        if (b->substAlphabet) {
+            xa.table = reinterpret_cast<const int8_t *>(b->dSubst); xa.codeOf = b->dSubst + DPX_SUBST_TABLE_BYTES;
+            xa.f.ldsPerWave += DPX_SUBST_IMAGE_BYTES; xa.f.wavesPerBlock = dpx_plan_bdx_waves(*b, true);
+        }
+        return dpx_launch_bd2_fill(xa, b->R, r.ext, s);
+    }
     }
     return hipErrorInvalidValue;
 }
@@ -1245,7 +1254,7 @@ int dpx_batch_results(dpx_batch *b, int32_t *scores, int32_t *endRow, int32_t *e
 }
 
 int dpx_batch_directions(dpx_batch *b, size_t pair, int which, uint8_t *out) {
-    if (!b || !out || pair >= b->numPairs || which < 0 || which >= b->planes) return DPX_ERR_INVALID;
+    if (!b || !out || pair >= b->numPairs || which < 0 || which >= (b->twoPiece ? DPX_MAT_H_PIECE + 1 : b->planes)) return DPX_ERR_INVALID;
     if (!b->dirs && !b->bandDirs) return DPX_ERR_NO_MATRIX;
     if (!b->filled) return DPX_ERR_NOT_FILLED;
     int rc = bind_device(b->device);
@@ -1256,8 +1265,9 @@ int dpx_batch_directions(dpx_batch *b, size_t pair, int which, uint8_t *out) {
     size_t dOutCap = 0;
     if (b->lastStream && b->lastStream != b->stream) HIP_TRY(hipStreamSynchronize(b->lastStream));
     HIP_TRY(g_tbDevCache.take((void **)&dOut, std::max<size_t>(total, 16), &dOutCap)); /* row-major scratch */
-    hipError_t e = b->bandDirs ? dpx_launch_bdir_export(reinterpret_cast<const uint8_t *>(b->dMat), pd, b->dSeq, b->prm.band, which, dOut, b->stream)
-                               : dpx_launch_export_dir(reinterpret_cast<const uint8_t *>(b->dMat), pd, b->dSeq, b->kernelAlgo, b->R, which, dOut, b->stream);
+    hipError_t e = b->twoPiece ? dpx_launch_bd2_export(reinterpret_cast<const uint8_t *>(b->dMat), pd, b->dSeq, b->prm.band, which, dOut, b->stream)
+                   : b->bandDirs ? dpx_launch_bdir_export(reinterpret_cast<const uint8_t *>(b->dMat), pd, b->dSeq, b->prm.band, which, dOut, b->stream)
+                                 : dpx_launch_export_dir(reinterpret_cast<const uint8_t *>(b->dMat), pd, b->dSeq, b->kernelAlgo, b->R, which, dOut, b->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
     if (e == hipSuccess) e = hipMemcpy(out, dOut, total, hipMemcpyDeviceToHost);
     g_tbDevCache.park(dOut, dOutCap);
@@ -1387,6 +1397,38 @@ int dpx_batch_set_extension_table(dpx_batch *b, int32_t zdrop, int32_t endBonus,
     return DPX_OK;
 }
 
+/* fits_dir for a band-direction batch under two gap pieces: on their componentwise minimum and again on their componentwise maximum,
+ * valid lower and upper bounds of every cell (equal pieces: fits_dir itself) */
+static bool fits_dir_pieces(dpx_params q, int32_t o2, int32_t e2, long long m, long long n) {
+    const int32_t o1 = q.gapOpen, e1 = q.gapExtend;
+    q.gapOpen = std::min(o1, o2); q.gapExtend = std::min(e1, e2);
+    if (!fits_dir(q, m, n)) return false;
+    q.gapOpen = std::max(o1, o2); q.gapExtend = std::max(e1, e2);
+    return fits_dir(q, m, n);
+}
+
+/* the second gap piece of a two-piece batch; every check comes before the first change */
+int dpx_batch_set_second_gap(dpx_batch *b, int32_t gapOpen2, int32_t gapExtend2) {
+    if (!b) return DPX_ERR_INVALID;
+    if (!b->twoPiece) return DPX_ERR_UNSUPPORTED;
+    const int32_t lim = 1 << 20; /* validate_params' rule */
+    if (gapOpen2 > lim || gapOpen2 < -lim || gapExtend2 > lim || gapExtend2 < -lim) return DPX_ERR_RANGE;
+    dpx_params q = b->prm;
+    if (b->substAlphabet && b->bdxImage.size() == DPX_SUBST_IMAGE_BYTES) { /* under a table: its largest and smallest entries, as its setter checks */
+        q.match = -128; q.mismatch = 127;
+        for (int r = 0; r < b->substAlphabet; r++)
+            for (int c = 0; c < b->substAlphabet; c++) {
+                const int32_t v = (int8_t)b->bdxImage[(size_t)r * 32 + (size_t)c];
+                q.match = std::max(q.match, v); q.mismatch = std::min(q.mismatch, v);
+            }
+    }
+    for (const dpx_pair_dev &pd : b->pairs) if (!fits_dir_pieces(q, gapOpen2, gapExtend2, pd.m, pd.n)) return DPX_ERR_RANGE;
+    if (gapOpen2 != b->gapOpen2 || gapExtend2 != b->gapExtend2) invalidate_fill(b);
+    b->gapOpen2 = gapOpen2;
+    b->gapExtend2 = gapExtend2;
+    return DPX_OK;
+}
+
 /* all scoring of a band-direction batch, the three settings at once; every check comes before the first change */
 int dpx_batch_set_direction_scoring(dpx_batch *b, int32_t zdrop, int32_t endBonus, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf) {
     if (!b || zdrop < -1 || zdrop > (1 << 30) || endBonus < -1 || endBonus > (1 << 30)) return DPX_ERR_INVALID;
@@ -1405,7 +1447,7 @@ int dpx_batch_set_direction_scoring(dpx_batch *b, int32_t zdrop, int32_t endBonu
         dpx_params q = b->prm;
         q.match = -128; q.mismatch = 127;
         for (int k = 0; k < alphabet * alphabet; k++) { q.match = std::max<int32_t>(q.match, scores[k]); q.mismatch = std::min<int32_t>(q.mismatch, scores[k]); }
-        for (const dpx_pair_dev &pd : b->pairs) if (!fits_dir(q, pd.m, pd.n)) return DPX_ERR_RANGE;
+        for (const dpx_pair_dev &pd : b->pairs) if (!fits_dir_pieces(q, b->twoPiece ? b->gapOpen2 : q.gapOpen, b->twoPiece ? b->gapExtend2 : q.gapExtend, pd.m, pd.n)) return DPX_ERR_RANGE;
         memset(image, 0, sizeof image);
         for (int r = 0; r < alphabet; r++) memcpy(image + r * 32, scores + r * alphabet, (size_t)alphabet);
         memcpy(image + DPX_SUBST_TABLE_BYTES, codeOf, 256);
@@ -1460,6 +1502,7 @@ static int traceback_lines(dpx_batch *b) {
     case DPX_WALK_BANW: HIP_TRY(dpx_launch_banw_traceback(b->args, n, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream)); break;
     case DPX_WALK_SUBST: HIP_TRY(dpx_launch_subst_traceback(subst_args(b), n, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream)); break;
     case DPX_WALK_BDIR: HIP_TRY(dpx_launch_bdir_traceback(b->args, n, b->dTbOff, b->dTb, b->dTbLen, b->stream)); break;
+    case DPX_WALK_BD2: HIP_TRY(dpx_launch_bd2_traceback(b->args, n, b->dTbOff, b->dTb, b->dTbLen, b->stream)); break;
     }
     b->tbLinesValid = true;
     return DPX_OK;

@@ -328,7 +328,9 @@ int choose_kernel(const Knobs &kn, dpx_plan &p, int &R) {
     /* DPX_KEEP_BAND_DIRECTIONS: a covering BANW band takes the matrix batch's fall-back to ANW, as an ANW direction batch; every other band
      * runs k_bdir_fill */
     const bool bandDirFlag = (p.flags & DPX_KEEP_BAND_DIRECTIONS) != 0;
-    const bool bandDirCovering = bandDirFlag && prm.algo == DPX_ALGO_BANW && (long long)prm.band >= longest + 1;
+    p.twoPiece = bandDirFlag && (p.flags & DPX_TWO_PIECE_GAPS) != 0; /* (no ANW fall-back: ANW has no second piece) */
+    p.gapOpen2 = prm.gapOpen; p.gapExtend2 = prm.gapExtend;
+    const bool bandDirCovering = bandDirFlag && !p.twoPiece && prm.algo == DPX_ALGO_BANW && (long long)prm.band >= longest + 1;
     p.dirs = (p.flags & DPX_KEEP_DIRECTIONS) != 0 || bandDirCovering; p.bandDirs = bandDirFlag && !bandDirCovering; p.kernelAlgo = prm.algo;
     /* rows per lane: smallest tile that keeps short queries in one stripe, 8 (or DPX_R) otherwise */
     /* linear gaps: 16 rows per lane once a query is longer than 512 (one stripe up to 1024 rows, two 1-KiB sub-tiles per
@@ -338,6 +340,11 @@ int choose_kernel(const Knobs &kn, dpx_plan &p, int &R) {
     const int v = kn.rowsPerLane;
     R = (v == 2 || v == 4 || v == 8 || (v == 16 && wide)) ? v : p.maxM <= 128 ? 2 : p.maxM <= 256 ? 4 : (p.maxM <= 512 || !wide) ? 8 : 16;
     if (!is_banded(prm.algo)) return DPX_OK;
+    if (p.twoPiece) { /* k_bd2_fill holds <= 4 cells per lane, covering band or not */
+        if (prm.band > DPX_BANDDIR2_MAX_BAND) return DPX_ERR_UNSUPPORTED;
+        R = dpx_band_cpl(prm.band);
+        return DPX_OK;
+    }
     /* (BANW: + 1, its band applies to the border cells too -- at B = max(m, n) the border cell (m, 0) or (0, n) is outside it) */
     /* (BAXT: no covering fall-back -- no unbanded extension kernel exists; a band <= 512 that covers the matrix runs k_baxt_fill) */
     if (prm.algo != DPX_ALGO_BAXT && (long long)prm.band >= longest + (prm.algo == DPX_ALGO_BANW ? 1 : 0)) {
@@ -513,7 +520,7 @@ void place_matrices(const Knobs &kn, bool banded, dpx_plan &p) {
         const uint64_t inband = (p.bandDirs || (banded && p.store && !p.dirs)) ? band_cells(pd.m, pd.n, p.prm.band) : 0;
         p.bandCells += inband;
         if (p.dirs) p.algBytes += ((uint64_t)(pd.m + 1) * (uint64_t)(pd.n + 1) + 1) / 2; /* half a byte per cell */
-        else if (p.bandDirs) p.algBytes += (inband + 1) / 2;                              /* half a byte per in-band cell */
+        else if (p.bandDirs) p.algBytes += p.twoPiece ? inband : (inband + 1) / 2;        /* half a byte per in-band cell, two-piece: a byte */
         else if (p.store && banded) p.algBytes += 2ull * (uint64_t)bandPlanes * inband;   /* 2 B per in-band cell and plane */
         else if (p.store) p.algBytes += 2ull * (uint64_t)p.planes * (uint64_t)(pd.m + 1) * (uint64_t)(pd.n + 1);
     }
@@ -522,7 +529,7 @@ void place_matrices(const Knobs &kn, bool banded, dpx_plan &p) {
     const uint32_t chunkElems = p.bandDirs ? 512u : banded ? dpx_band_chunk_elems(bandPlanes) : (p.split || p.dirs) ? 512u : dpx_tiled_chunk_elems(p.R, p.planes); /* (dirs: 1-KiB code chunks) */
     auto chunksOf = [&](const dpx_pair_dev &pd) -> uint64_t {
         if (p.dirs) return dpx_dir_chunks(pd.m, pd.n, p.R);
-        if (p.bandDirs) return dpx_banddir_chunks(pd.m, pd.n, p.prm.band);
+        if (p.bandDirs) return p.twoPiece ? dpx_banddir2_chunks(pd.m, pd.n, p.prm.band) : dpx_banddir_chunks(pd.m, pd.n, p.prm.band);
         if (pd.lanes == 32) return dpx_split_chunks(pd.m, pd.n, p.R);
         return banded ? dpx_band_chunks(pd.m, pd.n, p.prm.band) : dpx_tiled_chunks(pd.m, pd.n, p.R);
     };
@@ -632,6 +639,10 @@ int launch_scalars(const Knobs &kn, bool banded, size_t lanesRefArea, dpx_plan &
 int dpx_plan_batch(const dpx_params &params, const dpx_seq_pair *pairs, size_t firstPair, size_t numPairs, size_t numBytes, bool packed2Input,
                    unsigned flags, const Knobs &kn, dpx_plan &p, std::string &err) {
     p = dpx_plan();
+    if (flags & DPX_TWO_PIECE_GAPS) { /* legal only together with DPX_KEEP_BAND_DIRECTIONS, on the algorithms that flag serves */
+        if (!(flags & DPX_KEEP_BAND_DIRECTIONS)) return DPX_ERR_INVALID;
+        if (params.algo != DPX_ALGO_BANW && params.algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED;
+    }
     p.prm = params; p.flags = flags; p.numPairs = numPairs; p.packed2 = packed2Input;
     p.store = !(flags & DPX_SCORE_ONLY); p.planes = is_affine(params.algo) ? 3 : 1;
     Shape sh; int baseR = 0;
@@ -675,7 +686,7 @@ dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus,
         r.dirs = true; r.kernel = dir[family];
     } else if (p.bandDirs) { /* (a mode comes through dpx_batch_set_direction_scoring only; extension mode is BAXT's) */
         const bool bdx = extension || substAlphabet;
-        r.main = bdx ? DPX_MAIN_BDX : DPX_MAIN_BDIR; r.kernel = bdx ? DPX_K_BDX_FILL : DPX_K_BDIR_FILL;
+        r.main = p.twoPiece ? DPX_MAIN_BD2 : bdx ? DPX_MAIN_BDX : DPX_MAIN_BDIR; r.kernel = p.twoPiece ? DPX_K_BD2_FILL : bdx ? DPX_K_BDX_FILL : DPX_K_BDIR_FILL;
     } else if (substAlphabet) { /* (set only on batches whose kernel is BANW's or BAXT's; with extension mode: dpx_batch_set_extension_table) */
         r.main = extension ? DPX_MAIN_ZSUB : DPX_MAIN_SUBST; r.kernel = extension ? DPX_K_ZSUB_FILL : DPX_K_SUBST_FILL;
     } else if (algo == DPX_ALGO_BAXT) {
@@ -693,10 +704,10 @@ dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus,
                    : family ? (p.lanePacked ? lanes[family] : fill[family])
                    : p.packed ? DPX_K_LINEAR_FILL_PK : p.lanesPk ? DPX_K_LINEAR_LANES_PK : p.lanePacked ? DPX_K_LINEAR_LANES : p.split ? DPX_K_LINEAR_SPLIT : DPX_K_LINEAR_FILL;
     }
-    r.extRecords = r.main == DPX_MAIN_ZEXT || r.main == DPX_MAIN_ZSUB || (r.main == DPX_MAIN_BDX && extension);
-    r.walk = p.bandDirs ? DPX_WALK_BDIR : substAlphabet ? DPX_WALK_SUBST : algo == DPX_ALGO_BASW ? DPX_WALK_BASW : is_banw_layout(algo) ? DPX_WALK_BANW
+    r.extRecords = r.main == DPX_MAIN_ZEXT || r.main == DPX_MAIN_ZSUB || ((r.main == DPX_MAIN_BDX || r.main == DPX_MAIN_BD2) && extension);
+    r.walk = p.twoPiece ? DPX_WALK_BD2 : p.bandDirs ? DPX_WALK_BDIR : substAlphabet ? DPX_WALK_SUBST : algo == DPX_ALGO_BASW ? DPX_WALK_BASW : is_banw_layout(algo) ? DPX_WALK_BANW
              : p.dirs ? DPX_WALK_DIR : DPX_WALK_PLAIN;
-    r.walkMode = (r.walk == DPX_WALK_BDIR || r.walk == DPX_WALK_DIR) ? 0 : walk_mode(p, tbWalk); /* (one walk: DPX_TB_WALK has no effect) */
+    r.walkMode = (r.walk == DPX_WALK_BD2 || r.walk == DPX_WALK_BDIR || r.walk == DPX_WALK_DIR) ? 0 : walk_mode(p, tbWalk); /* (one walk: DPX_TB_WALK has no effect) */
     r.exportKind = is_banw_layout(algo) /* (BAXT stores what BANW stores) */ ? DPX_EXPORT_BANW : algo == DPX_ALGO_BASW ? DPX_EXPORT_BASW : DPX_EXPORT_PLAIN;
     return r;
 }
@@ -713,7 +724,7 @@ const char *dpx_route_kernel_name(dpx_fill_kernel k) {
         "k_linear_fill", "k_linear_fill_pk", "k_linear_lanes", "k_linear_lanes_pk", "k_linear_split",
         "k_affine_fill", "k_asw_fill", "k_asg_fill", "k_affine_lanes", "k_asw_lanes", "k_asg_lanes",
         "k_banded_fill", "k_banded_fill_pk", "k_basw_fill", "k_banw_fill", "k_baxt_fill",
-        "k_zext_fill", "k_subst_fill", "k_zsub_fill", "k_bdir_fill", "k_bdx_fill",
+        "k_zext_fill", "k_subst_fill", "k_zsub_fill", "k_bdir_fill", "k_bdx_fill", "k_bd2_fill",
         "k_linear_dir", "k_affine_dir", "k_asw_dir", "k_asg_dir"};
     return k >= 0 && k < DPX_K_COUNT ? names[k] : "?";
 }
@@ -727,6 +738,7 @@ const char *dpx_route_walk_name(dpx_walk_family walk, int walkMode) {
     case DPX_WALK_BANW: return wave ? "k_banw_traceback_wave" : "k_banw_traceback";
     case DPX_WALK_SUBST: return wave ? "k_subst_traceback_wave" : "k_subst_traceback";
     case DPX_WALK_BDIR: return "k_bdir_traceback";
+    case DPX_WALK_BD2: return "k_bd2_traceback";
     }
     return "?";
 }
@@ -748,7 +760,8 @@ int dpx_plan_describe(const dpx_plan &b, int tbWalk, int zdrop, int endBonus, in
     if (extension && len > 0 && (size_t)len < cap)
         len += snprintf(buf + len, cap - (size_t)len, " zdrop=%d end_bonus=%d", (int)zdrop, (int)endBonus);
     if (substAlphabet && len > 0 && (size_t)len < cap) len += snprintf(buf + len, cap - (size_t)len, " subst=%d", substAlphabet);
-    if (b.bandDirs && len > 0 && (size_t)len < cap) len += snprintf(buf + len, cap - (size_t)len, " matrix=banddir4");
+    if (b.bandDirs && len > 0 && (size_t)len < cap) len += snprintf(buf + len, cap - (size_t)len, b.twoPiece ? " matrix=banddir8" : " matrix=banddir4");
+    if (b.twoPiece && len > 0 && (size_t)len < cap) len += snprintf(buf + len, cap - (size_t)len, " gap2=%d,%d", (int)b.gapOpen2, (int)b.gapExtend2);
     if (b.dirs && len > 0 && (size_t)len < cap) /* the code layout, and where the edge rows live */
         len += snprintf(buf + len, cap - (size_t)len, " matrix=dir4 dir_edges=%s dir_scratch_bytes=%zu", b.dirScratch ? "global" : "lds", b.dirScratch);
     return len;

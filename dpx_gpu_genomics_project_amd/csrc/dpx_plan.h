@@ -10,6 +10,7 @@
 #include "../../include/dpx_align.h"
 #include "dpx_dir.h" /* (first: it brings dpx_kernels.h, whose hip_runtime.h the layout headers need under hipcc) */
 #include "dpx_banddir.h"
+#include "dpx_banddir2.h"
 
 #pragma GCC visibility push(hidden) /* (internal to libdpxalign.so: not part of its ABI) */
 
@@ -46,6 +47,8 @@ struct dpx_plan {
     bool dirs = false;     /* DPX_KEEP_DIRECTIONS: 4-bit codes in the pool (matElems counts them in int16 units, dpx_dir.h), k_linear_dir / k_affine_dir */
     bool bandDirs = false; /* DPX_KEEP_BAND_DIRECTIONS on a BANW / BAXT band kernel: codes in dpx_banddir.h's layout, k_bdir_fill through `args`
                               (a covering BANW band is a `dirs` batch of ANW instead) */
+    bool twoPiece = false; /* ... with DPX_TWO_PIECE_GAPS: 8-bit codes in dpx_banddir2.h's layout, k_bd2_fill; every band <= 256 runs the band kernel */
+    int32_t gapOpen2 = 0, gapExtend2 = 0; /* twoPiece: the second gap piece (dpx_batch_set_second_gap; piece 1 until then) */
     bool packed = false;     /* LNW / LSW / BSW with matrices: couples of equal-shaped pairs, two per wave + leftover singles */
     bool split = false;      /* small batch: one workgroup per pair, one wave per stripe (k_linear_split) */
     bool lanePacked = false; /* short queries: several pairs per wave (k_linear_lanes / k_affine_lanes, 8 x 8 tile layout) */
@@ -85,12 +88,12 @@ enum dpx_fill_kernel { /* the kernel that fills (most of) the batch: describe's 
     DPX_K_LINEAR_FILL, DPX_K_LINEAR_FILL_PK, DPX_K_LINEAR_LANES, DPX_K_LINEAR_LANES_PK, DPX_K_LINEAR_SPLIT,
     DPX_K_AFFINE_FILL, DPX_K_ASW_FILL, DPX_K_ASG_FILL, DPX_K_AFFINE_LANES, DPX_K_ASW_LANES, DPX_K_ASG_LANES,
     DPX_K_BANDED_FILL, DPX_K_BANDED_FILL_PK, DPX_K_BASW_FILL, DPX_K_BANW_FILL, DPX_K_BAXT_FILL,
-    DPX_K_ZEXT_FILL, DPX_K_SUBST_FILL, DPX_K_ZSUB_FILL, DPX_K_BDIR_FILL, DPX_K_BDX_FILL,
+    DPX_K_ZEXT_FILL, DPX_K_SUBST_FILL, DPX_K_ZSUB_FILL, DPX_K_BDIR_FILL, DPX_K_BDX_FILL, DPX_K_BD2_FILL,
     DPX_K_LINEAR_DIR, DPX_K_AFFINE_DIR, DPX_K_ASW_DIR, DPX_K_ASG_DIR, DPX_K_COUNT
 };
-enum dpx_main_launch { DPX_MAIN_NONE, DPX_MAIN_FILL, DPX_MAIN_BASW, DPX_MAIN_BANW, DPX_MAIN_BAXT, DPX_MAIN_ZEXT, DPX_MAIN_SUBST, DPX_MAIN_ZSUB, DPX_MAIN_BDIR, DPX_MAIN_BDX };
+enum dpx_main_launch { DPX_MAIN_NONE, DPX_MAIN_FILL, DPX_MAIN_BASW, DPX_MAIN_BANW, DPX_MAIN_BAXT, DPX_MAIN_ZEXT, DPX_MAIN_SUBST, DPX_MAIN_ZSUB, DPX_MAIN_BDIR, DPX_MAIN_BDX, DPX_MAIN_BD2 };
 enum dpx_second_launch { DPX_SECOND_NONE, DPX_SECOND_PACKED, DPX_SECOND_BANDED_PACKED, DPX_SECOND_LANES, DPX_SECOND_LANES_PK };
-enum dpx_walk_family { DPX_WALK_PLAIN, DPX_WALK_DIR, DPX_WALK_BASW, DPX_WALK_BANW, DPX_WALK_SUBST, DPX_WALK_BDIR };
+enum dpx_walk_family { DPX_WALK_PLAIN, DPX_WALK_DIR, DPX_WALK_BASW, DPX_WALK_BANW, DPX_WALK_SUBST, DPX_WALK_BDIR, DPX_WALK_BD2 };
 enum dpx_export_kind { DPX_EXPORT_PLAIN, DPX_EXPORT_BASW, DPX_EXPORT_BANW };
 struct dpx_route {
     dpx_fill_kernel kernel;
@@ -107,7 +110,8 @@ struct dpx_route {
 };
 /* What a batch can change after its creation comes as arguments: the traceback walk knob, BAXT's extension mode (-1, -1: off) and the
  * substitution alphabet (0: none).  On a bandDirs plan either of the two (dpx_batch_set_direction_scoring) turns k_bdir_fill into
- * k_bdx_fill; the walk stays k_bdir_traceback. */
+ * k_bdx_fill; the walk stays k_bdir_traceback.  A twoPiece plan runs k_bd2_fill and k_bd2_traceback in every mode; its second piece is
+ * the plan's own (the batch IS the plan), so the signatures here do not know it. */
 dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus, int substAlphabet);
 /* Waves per workgroup of a bandDirs plan's fill: the plan's own without a table; with one (DPX_SUBST_IMAGE_BYTES more per wave) the
  * plan's own when four waves' strings and images fit one workgroup's LDS, else 1, and 0 when not even one wave's fit (the setter

@@ -11,7 +11,7 @@
 // coordinates and the SAM CIGAR ('=' / 'X' ops; "-cigar M" merges them into 'M').  The lines are formatted on the host.
 //
 //   dpx_main -pairs <file> [-match 3] [-mismatch -1] [-open -2 | -gap -2] [-extend -1]
-//            [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band 128] [-batch N | -pool-gb 4] [-inflight K] [-tune 0|1] [-device 0] [-noprint] [-pack2] [-directions] [-cigar [M]] [-zdrop Z] [-endbonus E] [-matrix FILE] [-producer P] [-rank r -world w]
+//            [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band 128] [-batch N | -pool-gb 4] [-inflight K] [-tune 0|1] [-device 0] [-noprint] [-pack2] [-directions] [-cigar [M]] [-zdrop Z] [-endbonus E] [-matrix FILE] [-open2 O2 -extend2 E2] [-producer P] [-rank r -world w]
 //
 // -matrix FILE (BANW / BAXT, not with -zdrop / -endbonus): score columns by a substitution matrix (dpx_batch_set_substitution) instead of
 // -match / -mismatch.  NCBI text format: '#' lines are comments; one header row of 1..32 single-character column letters; then one row
@@ -19,6 +19,9 @@
 // upper-case letter's code, every other unlisted byte the last letter's ('*' in NCBI files, 'N' in a DNA file).
 // -directions with -algo BANW|BAXT keeps band direction codes (DPX_KEEP_BAND_DIRECTIONS); -zdrop / -endbonus / -matrix then go through
 // dpx_batch_set_direction_scoring (k_bdx_fill) and print what the run without -directions prints.
+// -open2 O2 -extend2 E2 (both or neither; only with -directions and -algo BANW|BAXT): two-piece affine gaps, a gap of length k scores
+// max(open + k * extend, O2 + k * E2) (DPX_TWO_PIECE_GAPS and dpx_batch_set_second_gap, k_bd2_fill; bands up to 256).  They combine with
+// -zdrop / -endbonus / -matrix through dpx_batch_set_direction_scoring.
 //
 // Batch size: by default from a matrix-pool BUDGET (-pool-gb, 4 GiB): as many pairs as fit the budget, at most 20000 (the
 // reference sizes its buffers once for BATCH_SIZE = 10000 reads of 150 bases, cuda/LNW/LinearNeedlemanWunschV9.cu:26-46,
@@ -123,7 +126,8 @@ static void usage() {
     fprintf(stderr, "usage: dpx_main -pairs <InSeqFile> -match <matchWeight> -mismatch <mismatchWeight> -open <gapWeight> "
                     "[-extend <gapExtend>] [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band <B>] [-batch <N>] [-device <D>] [-noprint] [-cigar [M]] "
                     "[-zdrop <Z>] [-endbonus <E>] (BAXT only) [-matrix <file>] (BANW / BAXT, not with -zdrop / -endbonus) "
-                    "[-directions] (direction codes instead of score matrices; BANW / BAXT: with -zdrop / -endbonus / -matrix too)\n");
+                    "[-directions] (direction codes instead of score matrices; BANW / BAXT: with -zdrop / -endbonus / -matrix too) "
+                    "[-open2 <O2> -extend2 <E2>] (two-piece gaps: both together, only with -directions and -algo BANW|BAXT)\n");
     exit(EXIT_FAILURE);
 }
 
@@ -140,6 +144,8 @@ int main(int argc, char *argv[]) {
     bool directions = false; // -directions: batches keep 4-bit direction codes (DPX_KEEP_DIRECTIONS): int32 scores, a quarter of the pool per pair
                              // (-algo BANW | BAXT: DPX_KEEP_BAND_DIRECTIONS, one code per in-band cell)
     int zdrop = -1, endBonus = -1; // -zdrop / -endbonus: BAXT's extension mode (dpx_batch_set_extension) on every batch; -1 = off
+    bool haveOpen2 = false, haveExtend2 = false; // -open2 / -extend2: the second gap piece (dpx_batch_set_second_gap) on every batch
+    int gapOpen2 = 0, gapExtend2 = 0;
     const char *matrixFile = nullptr; // -matrix: a substitution table (dpx_batch_set_substitution) on every batch
     int inflight = 3;      // batches on the device at a time (= matrix pools reserved)
     int tuneFlag = -1;     // -1: by the length of the job
@@ -169,6 +175,8 @@ int main(int argc, char *argv[]) {
         else if (!strcmp(argv[i], "-zdrop")) zdrop = atoi(next("-zdrop"));
         else if (!strcmp(argv[i], "-endbonus")) endBonus = atoi(next("-endbonus"));
         else if (!strcmp(argv[i], "-matrix")) matrixFile = next("-matrix");
+        else if (!strcmp(argv[i], "-open2")) { gapOpen2 = atoi(next("-open2")); haveOpen2 = true; }
+        else if (!strcmp(argv[i], "-extend2")) { gapExtend2 = atoi(next("-extend2")); haveExtend2 = true; }
         else if (!strcmp(argv[i], "-producer")) producerFlag = atoi(next("-producer"));
         else if (!strcmp(argv[i], "-inflight")) inflight = atoi(next("-inflight"));
         else if (!strcmp(argv[i], "-tune")) tuneFlag = atoi(next("-tune"));
@@ -184,6 +192,8 @@ int main(int argc, char *argv[]) {
                      : algoName == "BSW" ? DPX_ALGO_BSW : algoName == "ASW" ? DPX_ALGO_ASW : algoName == "BASW" ? DPX_ALGO_BASW : algoName == "ASG" ? DPX_ALGO_ASG : algoName == "BANW" ? DPX_ALGO_BANW : algoName == "BAXT" ? DPX_ALGO_BAXT : -1;
     if (algo < 0) { fprintf(stderr, "unknown -algo %s\n", algoName.c_str()); exit(EXIT_FAILURE); }
     if ((zdrop != -1 || endBonus != -1) && algo != DPX_ALGO_BAXT) usage();
+    const bool twoPiece = haveOpen2 || haveExtend2;
+    if (twoPiece && (!(haveOpen2 && haveExtend2) || !directions || (algo != DPX_ALGO_BANW && algo != DPX_ALGO_BAXT))) usage();
     std::vector<int8_t> substScores;
     int substAlphabet = 0;
     uint8_t substCode[256];
@@ -242,7 +252,7 @@ int main(int argc, char *argv[]) {
         // (-directions on BANW / BAXT: ceil((m + n - 1) / Gd) chunks of 1 KiB, Gd = 32 / C steps per chunk, C = cells per lane of the
         // band -- the layout of csrc/dpx_banddir.h)
         const bool bandDirections = directions && (algo == DPX_ALGO_BANW || algo == DPX_ALGO_BAXT);
-        const long long bC0 = ((long long)band + 63) / 64, bC = bC0 <= 1 ? 1 : bC0 <= 2 ? 2 : bC0 <= 4 ? 4 : 8, bGd = 32 / bC;
+        const long long bC0 = ((long long)band + 63) / 64, bC = bC0 <= 1 ? 1 : bC0 <= 2 ? 2 : bC0 <= 4 ? 4 : 8, bGd = (twoPiece ? 16 : 32) / bC; // (two-piece: a byte per cell, csrc/dpx_banddir2.h)
         const double bandDirChunks = (double)((mq + (long long)fileInfo.maxReferenceLength - 1 + bGd - 1) / bGd);
         const double perPair = bandDirections ? 1024.0 * bandDirChunks + 1024.0
                              : directions ? 0.5 * dirRows * dirCols + 1024.0
@@ -352,12 +362,13 @@ int main(int argc, char *argv[]) {
         next.count = std::min(batchSize, shardHi - first);
         const uint64_t t0 = get_time();
         const bool bandDirections = directions && (algo == DPX_ALGO_BANW || algo == DPX_ALGO_BAXT);
-        const unsigned flags = (bandDirections ? DPX_KEEP_BAND_DIRECTIONS : directions ? DPX_KEEP_DIRECTIONS : DPX_KEEP_MATRICES) | DPX_TIME_FILLS | ((tunePools && tuned.fetch_add(1) < inflight) ? DPX_TUNE_PLACEMENT : 0u);
+        const unsigned flags = (twoPiece ? DPX_TWO_PIECE_GAPS : 0u) | (bandDirections ? DPX_KEEP_BAND_DIRECTIONS : directions ? DPX_KEEP_DIRECTIONS : DPX_KEEP_MATRICES) | DPX_TIME_FILLS | ((tunePools && tuned.fetch_add(1) < inflight) ? DPX_TUNE_PLACEMENT : 0u);
         int prc = pack2 ? dpx_batch_create_packed2(-1, &prm, packed.data(), fileInfo.numBytes, alphabet, reinterpret_cast<const dpx_seq_pair *>(sequenceIdxs),
                                                    first, next.count, flags, &next.b)
                         : dpx_batch_create(&prm, sequences, fileInfo.numBytes, reinterpret_cast<const dpx_seq_pair *>(sequenceIdxs), first, next.count,
                                            flags, &next.b);
         if (prc != DPX_OK) die("FAILED TO CREATE DEVICE BATCH", prc);
+        if (twoPiece && (prc = dpx_batch_set_second_gap(next.b, gapOpen2, gapExtend2)) != DPX_OK) die("FAILED TO SET THE SECOND GAP PIECE", prc);
         if (bandDirections) { // the one setter of a band-direction batch: the two below refuse it
             if ((zdrop != -1 || endBonus != -1 || matrixFile) &&
                 (prc = dpx_batch_set_direction_scoring(next.b, zdrop, endBonus, matrixFile ? substScores.data() : nullptr, substAlphabet, substCode)) != DPX_OK)

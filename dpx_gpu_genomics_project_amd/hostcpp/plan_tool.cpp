@@ -10,6 +10,8 @@
  *     mode <zdrop> <endBonus> <substAlphabet>                      (optional: what a batch can change after its creation, as
  *           dpx_batch_set_extension / _set_substitution / _set_extension_table leave it; absent: -1 -1 0.  The setters' own
  *           refusals are not applied: the planner is asked what such a batch would run)
+ *     gap2 <gapOpen2> <gapExtend2>                                 (optional, after the mode line if there is one: the second gap piece
+ *           of a DPX_TWO_PIECE_GAPS plan as dpx_batch_set_second_gap leaves it; absent: piece 1)
  *     <referenceIdx> <referenceSize> <queryIdx> <querySize>        (firstPair + numPairs lines)
  *
  * Output, one line: "status=<n>", then for a refusal " err=<text>" when there is one, else dpx_batch_describe()'s text up to the pool
@@ -79,6 +81,8 @@ int main() {
     int zdrop = -1, endBonus = -1, substAlphabet = 0;
     const bool mode = scanf(" mode %d %d %d", &zdrop, &endBonus, &substAlphabet) == 3; /* (a pair line stops the match at its first character) */
     if (!mode) { zdrop = endBonus = -1; substAlphabet = 0; }
+    int gapOpen2 = 0, gapExtend2 = 0;
+    const bool gap2 = scanf(" gap2 %d %d", &gapOpen2, &gapExtend2) == 2; /* (as dpx_batch_set_second_gap leaves a two-piece plan) */
     std::vector<dpx_seq_pair> pairs(firstPair + numPairs);
     for (dpx_seq_pair &sp : pairs)
         if (scanf("%d %d %d %d", &sp.referenceIdx, &sp.referenceSize, &sp.queryIdx, &sp.querySize) != 4) {
@@ -93,12 +97,13 @@ int main() {
         printf("status=%d%s%s\n", rc, err.empty() ? "" : " err=", err.c_str());
         return 0;
     }
+    if (gap2 && plan.twoPiece) { plan.gapOpen2 = gapOpen2; plan.gapExtend2 = gapExtend2; }
     char text[4096];
     dpx_plan_describe(plan, kn.tbWalk, zdrop, endBonus, substAlphabet, text, sizeof text);
     printf("status=0 %s info=%zu,%llu,%llu,%llu state=%016llx", text, plan.numPairs, (unsigned long long)plan.cells,
            (unsigned long long)(plan.matElems * sizeof(int16_t)), (unsigned long long)plan.algBytes, (unsigned long long)plan_state(plan));
     if (mode) {
-        static const char *const family[] = {"plain", "dir", "basw", "banw", "subst", "bdir"}; /* dpx_walk_family */
+        static const char *const family[] = {"plain", "dir", "basw", "banw", "subst", "bdir", "bd2"}; /* dpx_walk_family */
         const dpx_route r = dpx_plan_route(plan, kn.tbWalk, zdrop, endBonus, substAlphabet);
         printf(" walk=%s:%d", family[r.walk], r.walkMode);
     }

@@ -542,6 +542,56 @@ int dpx_batch_set_extension_table(dpx_batch *b, int32_t zdrop, int32_t endBonus,
 int dpx_batch_set_direction_scoring(dpx_batch *b, int32_t zdrop, int32_t endBonus,
                                     const int8_t *scores, int32_t alphabet, const uint8_t *codeOf /* 256 entries */);
 
+/* ---- Two-piece affine gaps for DPX_KEEP_BAND_DIRECTIONS batches of BANW and BAXT ----
+ * Long-read mappers score a gap of length k as the cheaper of two affine pieces: g(k) = max(o1 + k*e1, o2 + k*e2).  Piece 1,
+ * (o1, e1) = params.gapOpen / params.gapExtend, prices sequencing errors; piece 2, (o2, e2) with |e2| < |e1|, prices real indels
+ * (minimap2's ksw_extd2 / ksw_gg2).  A two-piece batch is created with DPX_KEEP_BAND_DIRECTIONS | DPX_TWO_PIECE_GAPS on BANW or BAXT;
+ * until dpx_batch_set_second_gap is called piece 2 equals piece 1 and the batch reports exactly what the unflagged band-direction
+ * batch reports.  No ABI bump: detect the feature by the symbol dpx_batch_set_second_gap.
+ * Everything not named here is BANW's / BAXT's definition, unchanged: the band |i - j| <= B - 1, the anchoring, the end-cell rules,
+ * the admission rule, the tails and the text.
+ *   Borders.  H[0][0] = 0; in-band H[i][0] = g(i) and H[0][j] = g(j).  The four gap planes D1, D2, I1, I2 are minus infinity on every
+ *     border and outside the band.
+ *   Cells.  Dk = max(H_up + ok + ek, Dk_up + ek), Ik = max(H_left + ok + ek, Ik_left + ek); GAP_OPEN wins a tie in each of the four.
+ *     best = H_diag + s; then, in this order, D1, D2, I1, I2: a candidate that is >= the winner so far takes the cell.  H is the final
+ *     winner; there is no floor.  With (o2, e2) == (o1, e1) the geometry of every choice is the one-piece definition's: insertion holds
+ *     iff max(I) >= max(D, diag), otherwise deletion holds iff max(D) >= diag.
+ *   Walk.  Five states.  In SCORING the cell's winner names the move and, for a gap, the piece.  In state Dk / Ik the walk emits the gap
+ *     column, stays in that state while the cell's own extend bit of that plane is set, and returns to SCORING where that plane opened.
+ *     Then ANW's two tails.  The lines, the `_` convention, the relation line and the CIGAR are unchanged; a CIGAR does not say which
+ *     piece paid for a gap.
+ *   Empty sequences.  The one border line carries g(k), which is convex in k.  BANW's score is g(max(m, n)).  BAXT's first maximum is at
+ *     k = 1 when g(1) >= g(L), else at k = L, with L = min(max(m, n), B - 1); it counts only when above 0.
+ *   Extension mode on such a batch.  The scan, the record, the drop rule and the end-bonus choice stay word for word; the only change is
+ *     pen = max(0, -max(e1, e2)), the flatter piece (what ksw_extd2 passes), which equals the present pen when the pieces are equal.  The
+ *     value on anti-diagonal 1 is g(1).
+ * The batch stores one BYTE per in-band cell (csrc/dpx_banddir2.h) and runs k_bd2_fill / k_bd2_traceback: dpx_batch_describe reports
+ * kernel=k_bd2_fill traceback=k_bd2_traceback matrix=banddir8 and ` gap2=<o2>,<e2>`.  The band limit is B <= 256, covering or not
+ * (DPX_ERR_UNSUPPORTED above it: eight cells per lane do not fit the register file); a BANW band that covers the matrix runs the band
+ * kernel like any other band, because ANW has no second piece.  The range check is the band-direction batch's, on the componentwise
+ * minimum of the two pieces and again on their componentwise maximum.
+ * DPX_TWO_PIECE_GAPS without DPX_KEEP_BAND_DIRECTIONS: DPX_ERR_INVALID; with another algorithm than BANW / BAXT: DPX_ERR_UNSUPPORTED.
+ * dpx_batch_set_direction_scoring accepts a two-piece batch with its present arguments, checks and semantics; the three older setters
+ * keep refusing.  dpx_batch_extensions, the masking of exported planes behind lastDiag, repeated fills, DPX_TIME_FILLS,
+ * dpx_batch_fill_timed, a caller's stream, dpx_batch_create_on, packed2 input, the text pipeline and dpx_batch_cigars_* work as for a
+ * band-direction batch.
+ * dpx_batch_directions on a two-piece batch: DPX_MAT_H is directionMain (either piece exports QUERY_INSERTION / QUERY_DELETION),
+ * DPX_MAT_I / DPX_MAT_D are piece 1's planes, DPX_MAT_I2 / DPX_MAT_D2 piece 2's (GAP_OPEN / GAP_EXTEND, the same edge and border
+ * conventions), DPX_MAT_H_PIECE is 0 where H took the diagonal or the cell has no code and 1 / 2 for the piece of a gap move.  On any
+ * other batch selectors 3..5 answer what an out-of-range `which` answers.
+ * dpx_batch_set_second_gap: legal any time after create, applies to every following fill; if a value changed it invalidates the
+ * earlier fill's results, lines, text, CIGARs and records (DPX_ERR_NOT_FILLED), as dpx_batch_set_substitution does.
+ *   DPX_ERR_INVALID      b == NULL
+ *   DPX_ERR_UNSUPPORTED  a batch created without DPX_TWO_PIECE_GAPS
+ *   DPX_ERR_RANGE        a weight beyond +-2^20, or the range check fails for a pair
+ * A refused call changes nothing: dpx_batch_describe is byte-identical before and after.
+ * The class surface (dpx_class_main) and dpx_align_batch stay one-piece. */
+#define DPX_TWO_PIECE_GAPS 0x20u /* dpx_batch_create flag, only together with DPX_KEEP_BAND_DIRECTIONS */
+#define DPX_MAT_I2 3      /* dpx_batch_directions on a two-piece batch: piece 2's horizontal-gap plane */
+#define DPX_MAT_D2 4      /* ... piece 2's vertical-gap plane */
+#define DPX_MAT_H_PIECE 5 /* ... which piece H's gap move took (0 none, 1, 2) */
+int dpx_batch_set_second_gap(dpx_batch *b, int32_t gapOpen2, int32_t gapExtend2);
+
 /* Sizes: numPairs, total cells (sum refLen*queryLen, the reference's numCells, c++/parseInput.cpp:100),
  * bytes of HBM the matrices occupy, algorithmic bytes of one fill. */
 int dpx_batch_info(dpx_batch *b, size_t *numPairs, uint64_t *cells, uint64_t *matrixBytes, uint64_t *algorithmicBytes);
