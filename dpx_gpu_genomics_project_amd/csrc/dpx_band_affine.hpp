@@ -1,8 +1,9 @@
 /*
  * dpx_band_affine.hpp -- what the banded affine-gap units without a zero floor share: dpx_banw_kernels.hip (BANW), dpx_baxt_kernels.hip
  * (BAXT), dpx_zext_kernels.hip (BAXT in extension mode), dpx_subst_kernels.hip (either, scored by a table), dpx_zsub_kernels.hip (BAXT in
- * extension mode, scored by a table), dpx_banddir_kernels.hip (either, storing direction codes) and dpx_bdx_kernels.hip (the same under a table
- * and / or BAXT's extension mode).  dpx_basw_kernels.hip, whose step has a zero floor and a start cell, is a different kernel and does
+ * extension mode, scored by a table) and, through dpx_banddir_dev.hpp, the three band-direction units (dpx_banddir_kernels.hip,
+ * dpx_bdx_kernels.hip, dpx_bd2_kernels.hip: either algorithm, storing direction codes; what those three share among themselves is in
+ * dpx_banddir_dev.hpp and dpx_banddir_fill.inc).  dpx_basw_kernels.hip, whose step has a zero floor and a start cell, is a different kernel and does
  * not include it.  Everything here is a __forceinline__ function or a template: each kernel stays in its own unit under its own name.
  *
  * Shared are end_key, the band geometry and BandView, the step of the two fills that track slot keys (slot_key_step: k_baxt_fill and
@@ -19,7 +20,9 @@
  * band 128, k_bdir_fill<EXT> +1.1 % at band 64 and +0.7 % at band 256 (k_banw_fill +3.6 % at band 128, inside a 5 % spread); with the
  * phase loops as a function template over step and trip callables, 7 to 9 % at band 128.  (In the interior loop the wait for the
  * character read from LDS came 6 instructions behind the read instead of 12.)  So every fill keeps the step, prologue and loops it
- * had, and with them the code it compiled to before; profiles/band_sharing_ab.md has the table.
+ * had, and with them the code it compiled to before; profiles/band_sharing_ab.md has the table.  What does not move a fill is text
+ * included inside the kernel itself: the band-direction fills share their frame that way (dpx_banddir_fill.inc,
+ * profiles/banddir_sharing_ab.md) and keep three steps.
  *
  * The recurrence is ANW's Gotoh recurrence restricted to the band |i-j| <= B-1, border cells included: H[0][0] = 0, the in-band border
  * cells carry H = gapOpen + k * gapExtend (k <= B-1), everything outside the band is -infinity (DPX_NEG) in H, I and D; no zero floor.
@@ -343,16 +346,16 @@ __device__ __forceinline__ void write_results(const dpx_fill_args &f, const int 
 }
 
 /* an empty sequence (m <= 0 or n <= 0), on one lane: the in-band cells are one border line, cell k (1 <= k <= L = min(max(m, n), B-1))
- * on anti-diagonal k with H = o + k*e, and 0 at k = 0.  The scan, the maximum and the row-m rule run over it; no diagonal step, so a
- * substitution table plays no part. */
-template <bool ZDROP>
-__device__ __forceinline__ void scan_border_line(const dpx_fill_args &f, const int E, int32_t *ext, const int p, const int m, const int n, const int B, const int o, const int e,
+ * on anti-diagonal k with H = bord(k) (o + k*e; two-piece gaps: the better piece), and 0 at k = 0.  The scan, the maximum and the row-m
+ * rule run over it; no diagonal step, so a substitution table plays no part. */
+template <bool ZDROP, class Bord>
+__device__ __forceinline__ void scan_border_line(const dpx_fill_args &f, const int E, int32_t *ext, const int p, const int m, const int n, const int B, const Bord &bord,
                                                  const int Z, const int pen) {
     const int len = max(max(m, n), 0), L = min(len, B - 1);
     int best = 0, kb = 0, last = len, maxScore = 0, kmax = 0;
     bool dropped = false;
     for (int k = 1; k <= L; k++) {
-        const int v = o + k * e;
+        const int v = bord(k);
         if (v > best) {
             best = v;
             kb = k;
@@ -364,15 +367,15 @@ __device__ __forceinline__ void scan_border_line(const dpx_fill_args &f, const i
     }
     const int seen = min(L, last); /* the computed cells are k = 0 .. seen */
     for (int k = 1; k <= seen; k++)
-        if (o + k * e > maxScore) { maxScore = o + k * e; kmax = k; }
+        if (bord(k) > maxScore) { maxScore = bord(k); kmax = k; }
     int qeScore = INT_MIN, qeCol = -1;
     if (m <= 0) { /* row m is row 0: the line itself (or the single cell (0, 0)) */
         qeScore = 0;
         qeCol = 0;
         for (int k = 1; k <= (n > 0 ? seen : 0); k++)
-            if (o + k * e > qeScore) { qeScore = o + k * e; qeCol = k; }
+            if (bord(k) > qeScore) { qeScore = bord(k); qeCol = k; }
     } else if (m <= seen) { /* n == 0: row m holds the one cell (m, 0) */
-        qeScore = o + m * e;
+        qeScore = bord(m);
         qeCol = 0;
     }
     write_results(f, E, ext, p, max(m, 0), maxScore, m > 0 ? kmax : 0, m > 0 ? 0 : kmax, qeScore, qeCol, last, dropped);

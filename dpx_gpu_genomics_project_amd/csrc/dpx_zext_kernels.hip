@@ -46,7 +46,7 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_zext_fill(const dpx_zext_a
     const int match = a.f.match, mismatch = a.f.mismatch, o = a.f.gapOpen, e = a.f.gapExtend, oe = a.f.gapOpen + a.f.gapExtend;
     const int Z = a.zdrop, pen = e < 0 ? -e : 0;
     if (m <= 0 || n <= 0) {
-        if (lane == 0) scan_border_line<ZDROP>(a.f, a.endBonus, a.ext, p, m, n, B, o, e, Z, pen); /* an empty sequence: one border line */
+        if (lane == 0) scan_border_line<ZDROP>(a.f, a.endBonus, a.ext, p, m, n, B, [&](const int k) { return o + k * e; }, Z, pen); /* an empty sequence: one border line */
         return;
     }
     const unsigned char *ref = reinterpret_cast<const unsigned char *>(a.f.seq + pr.refIdx);

@@ -39,7 +39,7 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_zsub_fill(const dpx_zsub_a
     const int o = a.gapOpen, e = a.gapExtend, oe = a.gapOpen + a.gapExtend;
     const int Z = za.zdrop, pen = e < 0 ? -e : 0;
     if (m <= 0 || n <= 0) {
-        if (lane == 0) scan_border_line<ZDROP>(a, za.endBonus, za.ext, p, m, n, B, o, e, Z, pen); /* an empty sequence: one border line */
+        if (lane == 0) scan_border_line<ZDROP>(a, za.endBonus, za.ext, p, m, n, B, [&](const int k) { return o + k * e; }, Z, pen); /* an empty sequence: one border line */
         return;
     }
     const unsigned char *ref = reinterpret_cast<const unsigned char *>(a.seq + pr.refIdx);

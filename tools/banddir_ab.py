@@ -10,7 +10,13 @@ measurement in a FRESH process (its own pool), the two kinds of process alternat
 
 A process runs one discarded warm-up fill, then one timed pass of --fills back-to-back fills (dpx_batch_fill_timed); its figure is the
 mean of those fills.  --passes processes per case; the report gives their median, minimum and maximum.  One JSON line per process, then
-a summary.  No ratio is promised: the tool measures.  Needs a GPU."""
+a summary.  No ratio is promised: the tool measures.  Needs a GPU.
+
+--ab OLD.so NEW.so compares two builds of the library instead (DPX_LIB), by the method and rule of profiles/band_sharing_ab.md: direction
+batches only, 4096 x 4096 pairs, weights 2 / -3 / -5 / -1, --passes fresh processes per library and case, strictly alternating; the new
+median must be at most the old median plus the old max - min.  Cases: the fills of BANW and BAXT at bands 64, 128, 256 and 512 (600
+pairs, 512 at band 512), then traceback + text of --tb-pairs pairs at band 128 for BANW and BAXT, one-piece and two-piece (DPX_TWO_PIECE_GAPS:
+weights 2 / -4 / -4 / -2 and a second piece -24 / -1).  --ab-only fills | walks runs one half."""
 import argparse
 import ctypes as C
 import json
@@ -23,6 +29,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 W = (3, -1, -3, -1)
+AB_W = (2, -3, -5, -1)
+TWO_W, TWO_SECOND = (2, -4, -4, -2), (-24, -1)
 MAPPER = (2, -4, -4, -2)
 HBM_BYTES_PER_S = 8e12
 ALGOS = {"BANW": 7, "BAXT": 10}
@@ -34,8 +42,10 @@ def child(args):
 
     dpx.init(0)
     sb = make_batch(args.pairs, args.m, args.n, seed=args.seed)
-    w = MAPPER if args.mapper else W
+    w = MAPPER if args.mapper else TWO_W if args.two_piece else AB_W if args.ab_weights else W
     keep = dpx.KEEP_BAND_DIRECTIONS if args.kind == "directions" else dpx.KEEP_MATRICES
+    if args.two_piece:
+        keep |= dpx.TWO_PIECE_GAPS
     rec = {"algo": args.child, "kind": args.kind, "pairs": args.pairs, "m": args.m, "n": args.n, "band": args.band, "weights": w}
     try:
         b = dpx.Batch(ALGOS[args.child], sb.sequences, sb.pairs, *w, band=args.band, flags=keep | dpx.TIME_FILLS)
@@ -44,6 +54,8 @@ def child(args):
         print(json.dumps(rec), flush=True)
         return
     with b:
+        if args.two_piece:
+            b.set_second_gap(*TWO_SECOND)
         b.fill_timed(1)  # warm-up (first touch of the pool, code load): discarded
         us = b.fill_timed(args.fills)
         info, d = b.info(), b.describe()
@@ -62,11 +74,13 @@ def child(args):
     print(json.dumps(rec), flush=True)
 
 
-def run(algo, kind, pairs, m, n, args, tb=False, mapper=False):
+def run(algo, kind, pairs, m, n, args, tb=False, mapper=False, lib=None, band=None, extra=()):
     env = dict(os.environ)
     env.pop("DPX_TB_WALK", None)
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", algo, "--kind", kind, "--pairs", str(pairs), "--band", str(args.band), "--m", str(m),
-           "--n", str(n), "--fills", str(args.fills), "--seed", str(args.seed)] + (["--tb"] if tb else []) + (["--mapper"] if mapper else [])
+    if lib:
+        env["DPX_LIB"] = os.path.abspath(lib)
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", algo, "--kind", kind, "--pairs", str(pairs), "--band", str(band or args.band), "--m", str(m),
+           "--n", str(n), "--fills", str(args.fills), "--seed", str(args.seed)] + (["--tb"] if tb else []) + (["--mapper"] if mapper else []) + list(extra)
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=args.timeout)
     if r.returncode != 0:
         raise SystemExit(f"{' '.join(cmd)} failed ({r.returncode}): {r.stderr[-800:]!r}")
@@ -83,6 +97,30 @@ def spread(recs, key="fill_us"):
 def fmt(t):
     md, lo, hi = t
     return f"{md / 1e3:9.3f} ms [{lo / 1e3:.3f} .. {hi / 1e3:.3f}]"
+
+
+def ab(args):
+    """two builds of the library, direction batches only; a table in the format of profiles/band_sharing_ab.md"""
+    old_lib, new_lib = args.ab
+    cases = []
+    if args.ab_only in ("", "fills"):
+        cases += [(f"{algo} fill, `k_bdir_fill<EXT = {'true' if algo == 'BAXT' else 'false'}>`, band {band}", algo, 512 if band == 512 else 600, band, False, ["--ab-weights"], "fill_us")
+                  for algo in ("BANW", "BAXT") for band in (64, 128, 256, 512)]
+    if args.ab_only in ("", "walks"):
+        cases += [(f"{algo} traceback + text, {'two-piece' if two else 'one-piece'}, band 128", algo, args.tb_pairs, 128, True, ["--two-piece"] if two else ["--ab-weights"], "output_us")
+                  for two in (False, True) for algo in ("BANW", "BAXT")]
+    rows = []
+    for name, algo, pairs, band, tb, extra, key in cases:
+        got = {old_lib: [], new_lib: []}
+        for _ in range(args.passes):  # strictly alternating fresh processes
+            for lib in (old_lib, new_lib):
+                got[lib].append(run(algo, "directions", pairs, args.m, args.n, args, tb=tb, lib=lib, band=band, extra=extra)[key])
+        (om, olo, ohi), nm = (statistics.median(got[old_lib]), min(got[old_lib]), max(got[old_lib])), statistics.median(got[new_lib])
+        rows.append(f"| {name} | {pairs} | {om:.1f} | {ohi - olo:.1f} | {nm:.1f} | {(nm / om - 1) * 100:+.1f} % | {'met' if nm <= om + (ohi - olo) else 'MISSED'} |"
+                    f"{' (old spread above 3 % of its median)' if ohi - olo > 0.03 * om else ''}")
+        print(rows[-1], flush=True)
+    print("| case | pairs | before: median us | before: max - min us | after: median us | change | rule |\n|---|---|---|---|---|---|---|")
+    print("\n".join(rows))
 
 
 def main():
@@ -104,9 +142,15 @@ def main():
     ap.add_argument("--long-pairs", type=int, default=2000)
     ap.add_argument("--long-m", type=int, default=20000)
     ap.add_argument("--long-n", type=int, default=20000)
+    ap.add_argument("--two-piece", action="store_true", help="child: a DPX_TWO_PIECE_GAPS batch")
+    ap.add_argument("--ab-weights", action="store_true", help="child: weights 2 / -3 / -5 / -1")
+    ap.add_argument("--ab", nargs=2, metavar=("OLD.so", "NEW.so"), default=None)
+    ap.add_argument("--ab-only", default="", choices=["", "fills", "walks"])
     args = ap.parse_args()
     if args.child:
         return child(args)
+    if args.ab:
+        return ab(args)
     lines = []
     for algo in [a for a in args.algos.split(",") if a]:
         got = {"directions": [], "matrices": []}
