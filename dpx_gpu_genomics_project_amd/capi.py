@@ -38,7 +38,7 @@ ABI_SYMBOLS = (
     "dpx_batch_info", "dpx_batch_describe", "dpx_batch_destroy", "dpx_align_batch", "dpx_prim_eval", "dpx_batch_directions",
     "dpx_batch_cigars_begin", "dpx_batch_cigars_end", "dpx_cigar_text", "dpx_batch_set_extension", "dpx_batch_extensions",
     "dpx_batch_set_substitution", "dpx_batch_set_extension_table", "dpx_batch_set_direction_scoring",
-    "dpx_batch_set_second_gap",
+    "dpx_batch_set_second_gap", "dpx_batch_set_reversed",
 )
 # declared entry points a library may lack and still load (an older build): checked when they are called
 OPTIONAL_SYMBOLS = ("dpx_batch_directions",)
@@ -133,6 +133,7 @@ def load() -> C.CDLL:
     lib.dpx_batch_set_extension_table.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, vp]
     lib.dpx_batch_set_direction_scoring.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, vp]
     lib.dpx_batch_set_second_gap.argtypes = [vp, C.c_int32, C.c_int32]
+    lib.dpx_batch_set_reversed.argtypes = [vp, vp]
     for name in ABI_SYMBOLS:  # every declared entry point must be exported (the optional ones by libraries that have them)
         if name not in OPTIONAL_SYMBOLS:
             getattr(lib, name)
@@ -322,6 +323,19 @@ class Batch:
         max(gap_open + k * gap_extend, gap_open2 + k * gap_extend2).  Lines and results of an earlier fill are invalid afterwards when a
         value changed."""
         _check(self._lib.dpx_batch_set_second_gap(self._h, gap_open2, gap_extend2), "dpx_batch_set_second_gap")
+
+    def set_reversed(self, mask) -> None:
+        """BANW / BAXT only: the pairs whose mask entry is nonzero are aligned as (reverse(ref), reverse(qry)) in the following fills,
+        on the device.  Results, extension records and exported planes stay in that reversed frame; lines, text, CIGAR ops and alignment
+        coordinates come back in the original orientation.  `mask` holds num_pairs values; None or all zeros clears it.  Lines and
+        results of an earlier fill are invalid afterwards."""
+        if mask is None:
+            _check(self._lib.dpx_batch_set_reversed(self._h, None), "dpx_batch_set_reversed")
+            return
+        arr = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
+        if arr.size != self.num_pairs:
+            raise ValueError(f"mask must hold one value per pair ({self.num_pairs}), got {arr.size}")
+        _check(self._lib.dpx_batch_set_reversed(self._h, arr.ctypes.data if arr.size else None), "dpx_batch_set_reversed")
 
     def extensions(self) -> np.ndarray:
         """One EXTENSION_DTYPE record per pair of the last fill, which must have run in extension mode."""

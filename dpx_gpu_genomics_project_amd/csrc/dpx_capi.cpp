@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "dpx_cigar.h"
+#include "dpx_reverse.h"
 #include "dpx_plan.h" /* (brings dpx_kernels.h, dpx_dir.h, dpx_banddir.h and dpx_layout.h) */
 
 namespace {
@@ -513,6 +514,17 @@ struct dpx_batch : dpx_plan {
     unsigned char *dSubst = nullptr; /* device: the table at row stride 32 (DPX_SUBST_TABLE_BYTES), then codeOf[256] */
     size_t dSubstCap = 0;
     std::vector<unsigned char> bdxImage; /* dpx_batch_set_direction_scoring: the image dSubst holds, to tell a changed table from the same one */
+    /* orientation (dpx_batch_set_reversed): while revCount > 0 dSeq points at dRev, the setter's own allocation -- [the arena's sequence
+     * bytes][reversed copies of the flagged pairs' strings][the kernel's job list][the flagged pairs' numbers] -- and the flagged pairs'
+     * indices in `pairs` / dPairs at the copies.  The fills, walks and exports know nothing of it. */
+    char *dSeqOwn = nullptr;     /* the arena's sequence bytes (== dSeq while no mask is set) */
+    size_t seqBytes = 0;         /* ... and their padded size */
+    char *dRev = nullptr;
+    size_t dRevCap = 0;
+    const int32_t *dFlagged = nullptr; /* inside dRev: revCount pair numbers, ascending */
+    size_t revCount = 0;
+    struct RevSaved { int32_t pair, refIdx, qryIdx; };
+    std::vector<RevSaved> revSaved;    /* the flagged pairs' own indices, for the next call of the setter */
     PoolRecord poolRec;    /* how the matrix pool behind dMat was built / timed */
     bool tunePool = false, tuneShop = false; /* DPX_TUNE_PLACEMENT: the pool is timed / shopped for at the end of dpx_batch_create */
 };
@@ -790,6 +802,7 @@ int dpx_batch_destroy(dpx_batch *b) {
     g_tbHostCache.park(b->hCigarOps, b->hCigarOpsCap);
     g_tbDevCache.park(b->dExt, b->dExtCap);
     g_tbDevCache.park(b->dSubst, b->dSubstCap);
+    g_arenaCache.park(b->dRev, b->dRevCap);
     g_stageCache.park(b->hStage, b->hStageCap);
     delete b;
     trace.mark("destroy");
@@ -909,6 +922,7 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
         CREATE_TRY(g_arenaCache.take((void **)&b->arena, need, &b->arenaCap));
         char *q = b->arena;
         b->dSeq = q;                  q += szSeq;
+        b->dSeqOwn = b->dSeq; b->seqBytes = szSeq;
         b->dPairs = (dpx_pair_dev *)q; q += szPairs;
         b->dScore = (int32_t *)q;     q += szI32;
         b->dEndRow = (int32_t *)q;    q += szI32;
@@ -1473,6 +1487,97 @@ int dpx_batch_set_direction_scoring(dpx_batch *b, int32_t zdrop, int32_t endBonu
     return DPX_OK;
 }
 
+/* ---- orientation: dpx_batch_set_reversed ----
+ * The kernels find a pair's strings through the pair table, so the setter builds reversed copies of the flagged pairs' strings on the
+ * device (k_reverse_strings) behind a device copy of the batch's bytes, points the flagged pairs at them and the launch arguments'
+ * `seq` at the new allocation.  Nothing is reversed in place (pairs share bytes), no sequence byte crosses PCIe and the host reads
+ * none.  The plan is a function of sizes and stays. */
+static void set_seq_pointer(dpx_batch *b, char *seq) {
+    b->dSeq = seq;
+    b->args.seq = seq;
+    if (b->pkArgs.seq) b->pkArgs.seq = seq;
+    if (b->dirs) b->dirArgs.seq = seq;
+}
+
+int dpx_batch_set_reversed(dpx_batch *b, const uint8_t *reversed) {
+    if (!b) return DPX_ERR_INVALID;
+    if (b->prm.algo != DPX_ALGO_BANW && b->prm.algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED;
+    const size_t np = b->numPairs;
+    std::vector<int32_t> flagged;
+    for (size_t i = 0; reversed && i < np; i++) if (reversed[i]) flagged.push_back((int32_t)i);
+    if (flagged.empty() && !b->revCount) return DPX_OK; /* no mask before, none now */
+    PhaseTrace trace;
+    /* the layout, from the pairs' own indices (a flagged pair's are in revSaved); every check comes before the first change */
+    std::vector<dpx_pair_dev> table = b->pairs;
+    for (const dpx_batch::RevSaved &sv : b->revSaved) { table[(size_t)sv.pair].refIdx = sv.refIdx; table[(size_t)sv.pair].qryIdx = sv.qryIdx; }
+    std::vector<dpx_rev_job> jobs;
+    std::vector<dpx_batch::RevSaved> saved;
+    jobs.reserve(2 * flagged.size());
+    saved.reserve(flagged.size());
+    /* (index, length) -> the job that copies it: a string that many pairs share is copied once.  Open addressing, at most half full. */
+    size_t slots = 16;
+    while (slots < 4 * flagged.size()) slots <<= 1;
+    std::vector<int32_t> jobOf(slots, -1);
+    size_t off = b->seqBytes;
+    for (const int32_t p : flagged) {
+        dpx_pair_dev &pd = table[(size_t)p];
+        saved.push_back({p, pd.refIdx, pd.qryIdx});
+        for (int side = 0; side < 2; side++) {
+            int32_t &idx = side ? pd.qryIdx : pd.refIdx;
+            const int32_t len = side ? pd.m : pd.n;
+            if (len <= 0) continue; /* (an empty string is never read: its index stays) */
+            size_t h = (size_t)((((uint64_t)(uint32_t)idx << 32) | (uint32_t)len) * 0x9E3779B97F4A7C15ull >> 32) & (slots - 1);
+            while (jobOf[h] >= 0 && (jobs[(size_t)jobOf[h]].src != idx || jobs[(size_t)jobOf[h]].len != len)) h = (h + 1) & (slots - 1);
+            if (jobOf[h] < 0) {
+                if (off + dpx_rev_slot_bytes((size_t)len) > (size_t)0x7fffffff) {
+                    t_err = "dpx_batch_set_reversed: the reversed copies end beyond byte 2^31 of the sequence buffer (pair " + std::to_string(p) + "), int32 offsets cannot reach them";
+                    return DPX_ERR_RANGE;
+                }
+                jobOf[h] = (int32_t)jobs.size();
+                jobs.push_back({idx, (int32_t)off, len, 0});
+                off += dpx_rev_slot_bytes((size_t)len);
+            }
+            idx = jobs[(size_t)jobOf[h]].dst;
+        }
+    }
+    trace.mark("set_reversed: layout");
+    const size_t jobsAt = align_up(off, 256), flaggedAt = jobsAt + align_up(jobs.size() * sizeof(dpx_rev_job), 256);
+    const size_t need = flaggedAt + align_up(flagged.size() * sizeof(int32_t), 256);
+    int rc = bind_device(b->device);
+    if (rc != DPX_OK) return rc;
+    /* a fill, a walk or an export in flight may still read the present strings and table */
+    if (b->lastStream && b->lastStream != b->stream) HIP_TRY(hipStreamSynchronize(b->lastStream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    char *fresh = nullptr;
+    size_t freshCap = 0;
+    if (!flagged.empty()) {
+        HIP_TRY(g_arenaCache.take((void **)&fresh, need, &freshCap));
+        trace.mark("set_reversed: allocation");
+        hipError_t e = hipMemcpyAsync(fresh, b->dSeqOwn, b->seqBytes, hipMemcpyDeviceToDevice, b->stream);
+        if (e == hipSuccess && !jobs.empty()) e = hipMemcpy(fresh + jobsAt, jobs.data(), jobs.size() * sizeof(dpx_rev_job), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(fresh + flaggedAt, flagged.data(), flagged.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = dpx_launch_reverse_strings(fresh, reinterpret_cast<const dpx_rev_job *>(fresh + jobsAt), (int)jobs.size(), b->stream);
+        if (e == hipSuccess && np) e = hipMemcpy(b->dPairs, table.data(), np * sizeof(dpx_pair_dev), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { /* (the batch keeps its present mask) */
+            (void)hipStreamSynchronize(b->stream);
+            if (np) (void)hipMemcpy(b->dPairs, b->pairs.data(), np * sizeof(dpx_pair_dev), hipMemcpyHostToDevice);
+            g_arenaCache.park(fresh, freshCap);
+            return hip_fail(e, "dpx_batch_set_reversed");
+        }
+    } else if (np) HIP_TRY(hipMemcpy(b->dPairs, table.data(), np * sizeof(dpx_pair_dev), hipMemcpyHostToDevice));
+    g_arenaCache.park(b->dRev, b->dRevCap); /* (idle: both streams were waited for) */
+    b->dRev = fresh; b->dRevCap = freshCap;
+    b->dFlagged = fresh ? reinterpret_cast<const int32_t *>(fresh + flaggedAt) : nullptr;
+    b->revCount = flagged.size();
+    b->revSaved = std::move(saved);
+    b->pairs = std::move(table);
+    set_seq_pointer(b, fresh ? fresh : b->dSeqOwn);
+    if (fresh) b->uploadPending = true; /* the copies are being written on b->stream: a fill on a caller's stream waits for it once */
+    invalidate_fill(b);
+    trace.mark("set_reversed: uploads+launch");
+    return DPX_OK;
+}
+
 int dpx_batch_extensions(dpx_batch *b, dpx_extension *out) {
     if (!b || !out) return DPX_ERR_INVALID;
     if (!b->filled) return DPX_ERR_NOT_FILLED;
@@ -1504,6 +1609,8 @@ static int traceback_lines(dpx_batch *b) {
     case DPX_WALK_BDIR: HIP_TRY(dpx_launch_bdir_traceback(b->args, n, b->dTbOff, b->dTb, b->dTbLen, b->stream)); break;
     case DPX_WALK_BD2: HIP_TRY(dpx_launch_bd2_traceback(b->args, n, b->dTbOff, b->dTb, b->dTbLen, b->stream)); break;
     }
+    /* reversed pairs (dpx_batch_set_reversed): their lines come out of the walk in the reversed frame and are turned round here, once */
+    if (b->revCount) HIP_TRY(dpx_launch_flip_lines(b->dPairs, b->dFlagged, (int)b->revCount, b->dTbLen, b->dTbOff, b->dTb, b->stream));
     b->tbLinesValid = true;
     return DPX_OK;
 }
@@ -1717,6 +1824,7 @@ int dpx_batch_cigars_begin(dpx_batch *b, unsigned flags) {
         if (rc != DPX_OK) return rc;
         HIP_TRY(dpx_launch_cigars(b->dPairs, b->dEndRow, b->dEndCol, b->dTbLen, b->dTbOff, b->dTb, (int)np, flags,
                                   reinterpret_cast<dpx_alignment *>(b->dCigar), dTotal + 1, dTotal, b->dCigarOps, b->stream));
+        if (b->revCount) HIP_TRY(dpx_launch_map_records(b->dPairs, b->dFlagged, (int)b->revCount, reinterpret_cast<dpx_alignment *>(b->dCigar), b->stream));
         HIP_TRY(hipMemcpyAsync(b->hCigar, b->dCigar, recBytes + sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
     } else {
         memset(b->hCigar, 0, sizeof(uint64_t)); /* a batch without pairs: no records, no ops */
@@ -1784,6 +1892,9 @@ int dpx_cigar_text(const uint32_t *ops, size_t numOps, char *out, size_t cap, si
 int dpx_batch_describe(dpx_batch *b, char *buf, size_t cap) {
     if (!b || !buf || !cap) return DPX_ERR_INVALID;
     int len = dpx_plan_describe(*b, knobs().tbWalk, b->zdrop, b->endBonus, b->substAlphabet, buf, cap);
+    if (b->revCount && len > 0 && (size_t)len < cap) /* (the two blocks are diagnostics like pool_addr: the tests overwrite them between calls) */
+        len += snprintf(buf + len, cap - (size_t)len, " reversed=%zu rev_addr=0x%llx rev_bytes=%zu lines_addr=0x%llx lines_bytes=%zu", b->revCount,
+                        (unsigned long long)(uintptr_t)b->dRev, b->dRevCap, (unsigned long long)(uintptr_t)b->dTb, b->dTbCap);
     if (b->dMat && len > 0 && (size_t)len < cap) { /* the matrix pool: how it was built, and the memset time of every candidate that was timed */
         const PoolRecord &r = b->poolRec;
         len += snprintf(buf + len, cap - (size_t)len, " pool=%s pool_bytes=%zu pool_addr=0x%llx pool_chunk_mb=%zu pool_kept=%d pool_memset_ms=", r.mode.c_str(), b->matPoolBytes,

@@ -11,7 +11,7 @@
 // coordinates and the SAM CIGAR ('=' / 'X' ops; "-cigar M" merges them into 'M').  The lines are formatted on the host.
 //
 //   dpx_main -pairs <file> [-match 3] [-mismatch -1] [-open -2 | -gap -2] [-extend -1]
-//            [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band 128] [-batch N | -pool-gb 4] [-inflight K] [-tune 0|1] [-device 0] [-noprint] [-pack2] [-directions] [-cigar [M]] [-zdrop Z] [-endbonus E] [-matrix FILE] [-open2 O2 -extend2 E2] [-producer P] [-rank r -world w]
+//            [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band 128] [-batch N | -pool-gb 4] [-inflight K] [-tune 0|1] [-device 0] [-noprint] [-pack2] [-directions] [-cigar [M]] [-zdrop Z] [-endbonus E] [-matrix FILE] [-open2 O2 -extend2 E2] [-reverse] [-producer P] [-rank r -world w]
 //
 // -matrix FILE (BANW / BAXT, not with -zdrop / -endbonus): score columns by a substitution matrix (dpx_batch_set_substitution) instead of
 // -match / -mismatch.  NCBI text format: '#' lines are comments; one header row of 1..32 single-character column letters; then one row
@@ -22,6 +22,10 @@
 // -open2 O2 -extend2 E2 (both or neither; only with -directions and -algo BANW|BAXT): two-piece affine gaps, a gap of length k scores
 // max(open + k * extend, O2 + k * E2) (DPX_TWO_PIECE_GAPS and dpx_batch_set_second_gap, k_bd2_fill; bands up to 256).  They combine with
 // -zdrop / -endbonus / -matrix through dpx_batch_set_direction_scoring.
+// -reverse (only with -algo BANW|BAXT, and with every flag those take): every pair is aligned as (reverse(ref), reverse(qry)) on the
+// device (dpx_batch_set_reversed) -- a leftward extension, or a global alignment with its gaps at the right end of every ambiguous run.
+// Score and, for BAXT, the end cell behind it are the reversed frame's; lines, CIGARs and coordinates are printed along the strings as
+// they stand in the file.
 //
 // Batch size: by default from a matrix-pool BUDGET (-pool-gb, 4 GiB): as many pairs as fit the budget, at most 20000 (the
 // reference sizes its buffers once for BATCH_SIZE = 10000 reads of 150 bases, cuda/LNW/LinearNeedlemanWunschV9.cu:26-46,
@@ -127,7 +131,8 @@ static void usage() {
                     "[-extend <gapExtend>] [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band <B>] [-batch <N>] [-device <D>] [-noprint] [-cigar [M]] "
                     "[-zdrop <Z>] [-endbonus <E>] (BAXT only) [-matrix <file>] (BANW / BAXT, not with -zdrop / -endbonus) "
                     "[-directions] (direction codes instead of score matrices; BANW / BAXT: with -zdrop / -endbonus / -matrix too) "
-                    "[-open2 <O2> -extend2 <E2>] (two-piece gaps: both together, only with -directions and -algo BANW|BAXT)\n");
+                    "[-open2 <O2> -extend2 <E2>] (two-piece gaps: both together, only with -directions and -algo BANW|BAXT) "
+                    "[-reverse] (align every pair right to left on the device, output in the file's orientation; only with -algo BANW|BAXT)\n");
     exit(EXIT_FAILURE);
 }
 
@@ -146,6 +151,7 @@ int main(int argc, char *argv[]) {
     int zdrop = -1, endBonus = -1; // -zdrop / -endbonus: BAXT's extension mode (dpx_batch_set_extension) on every batch; -1 = off
     bool haveOpen2 = false, haveExtend2 = false; // -open2 / -extend2: the second gap piece (dpx_batch_set_second_gap) on every batch
     int gapOpen2 = 0, gapExtend2 = 0;
+    bool reverse = false;    // -reverse: every pair of every batch is reversed on the device (dpx_batch_set_reversed)
     const char *matrixFile = nullptr; // -matrix: a substitution table (dpx_batch_set_substitution) on every batch
     int inflight = 3;      // batches on the device at a time (= matrix pools reserved)
     int tuneFlag = -1;     // -1: by the length of the job
@@ -177,6 +183,7 @@ int main(int argc, char *argv[]) {
         else if (!strcmp(argv[i], "-matrix")) matrixFile = next("-matrix");
         else if (!strcmp(argv[i], "-open2")) { gapOpen2 = atoi(next("-open2")); haveOpen2 = true; }
         else if (!strcmp(argv[i], "-extend2")) { gapExtend2 = atoi(next("-extend2")); haveExtend2 = true; }
+        else if (!strcmp(argv[i], "-reverse")) reverse = true;
         else if (!strcmp(argv[i], "-producer")) producerFlag = atoi(next("-producer"));
         else if (!strcmp(argv[i], "-inflight")) inflight = atoi(next("-inflight"));
         else if (!strcmp(argv[i], "-tune")) tuneFlag = atoi(next("-tune"));
@@ -194,6 +201,7 @@ int main(int argc, char *argv[]) {
     if ((zdrop != -1 || endBonus != -1) && algo != DPX_ALGO_BAXT) usage();
     const bool twoPiece = haveOpen2 || haveExtend2;
     if (twoPiece && (!(haveOpen2 && haveExtend2) || !directions || (algo != DPX_ALGO_BANW && algo != DPX_ALGO_BAXT))) usage();
+    if (reverse && algo != DPX_ALGO_BANW && algo != DPX_ALGO_BAXT) usage();
     std::vector<int8_t> substScores;
     int substAlphabet = 0;
     uint8_t substCode[256];
@@ -376,6 +384,10 @@ int main(int argc, char *argv[]) {
         } else {
             if ((zdrop != -1 || endBonus != -1) && (prc = dpx_batch_set_extension(next.b, zdrop, endBonus)) != DPX_OK) die("FAILED TO SET THE EXTENSION MODE", prc);
             if (matrixFile && (prc = dpx_batch_set_substitution(next.b, substScores.data(), substAlphabet, substCode)) != DPX_OK) die("FAILED TO SET THE SUBSTITUTION MATRIX", prc);
+        }
+        if (reverse) {
+            const std::vector<uint8_t> all(next.count, 1);
+            if ((prc = dpx_batch_set_reversed(next.b, all.data())) != DPX_OK) die("FAILED TO SET THE ORIENTATION", prc);
         }
         create_time += get_time() - t0;
         if ((prc = dpx_batch_fill(next.b, nullptr)) != DPX_OK) die("KERNEL LAUNCH FAILED", prc);

@@ -592,6 +592,49 @@ int dpx_batch_set_direction_scoring(dpx_batch *b, int32_t zdrop, int32_t endBonu
 #define DPX_MAT_H_PIECE 5 /* ... which piece H's gap move took (0 none, 1, 2) */
 int dpx_batch_set_second_gap(dpx_batch *b, int32_t gapOpen2, int32_t gapExtend2);
 
+/* ---- Per-pair orientation for BANW and BAXT batches: leftward extension and right-aligned gaps ----
+ * A mapper extends leftward from its first anchor as often as rightward from its last, and on reverse-strand hits it wants the gaps of
+ * an ambiguous run at the other end of the run (ksw2's KSW_EZ_RIGHT with KSW_EZ_REV_CIGAR).  Both are the alignment of the reversed
+ * strings.  dpx_batch_set_reversed marks pairs of a batch as reversed; the reversing is done on the device, the caller keeps uploading
+ * its strings once, left to right, and reads lines, CIGARs and coordinates in its own orientation.  No ABI bump: detect the feature by
+ * the symbol dpx_batch_set_reversed.
+ *   Definition.  With n / m the pair's reference / query length, a reversed pair is aligned exactly as the pair (reverse(ref),
+ *     reverse(qry)) would be by the same batch: cells, band, borders, tie order, end-cell rule, z-drop scan, the table lookup s(r, q) and
+ *     the second gap piece are unchanged.  This is the pair's REVERSED FRAME.  A pair that is not reversed reports what it reports in a
+ *     batch without a mask, bit for bit.
+ *   Reversed frame, unchanged: dpx_batch_results, dpx_batch_device_results, dpx_batch_extensions (every field), dpx_batch_matrix and
+ *     dpx_batch_directions (row i / column j are the i-th / j-th character from the RIGHT end of the query / reference).  endRow /
+ *     endCol count characters consumed from the right end of the original strings: a BAXT alignment covers ref[n - endCol, n) and
+ *     qry[m - endRow, m).
+ *   Original orientation: dpx_batch_traceback, the text pipeline (dpx_batch_output_*) and dpx_batch_cigars_*.  The three lines are the
+ *     reversed frame's lines read back to front, so they read left to right along the original strings; the ops are in left-to-right
+ *     order of the original strings (the reversed frame's ops in reverse order; under DPX_CIGAR_M merging and reversing commute);
+ *     refStart = n - refEnd', refEnd = n - refStart', qryStart = m - qryEnd', qryEnd = m - qryStart' with ' the reversed frame's value,
+ *     so that the alignment covers ref[refStart, refEnd) and qry[qryStart, qryEnd) of the original strings and a leftward BAXT extension
+ *     ends at refEnd = n, qryEnd = m; numOps and the four counters are unchanged.  The header line of a text block (pair number,
+ *     score) is unchanged.
+ *   `reversed`: numPairs bytes, nonzero = reversed; NULL = no pair.  Legal any time after create, takes effect at the next fill and
+ *     invalidates the earlier fill's results, lines, text, CIGARs and records (DPX_ERR_NOT_FILLED) unless there was no mask before and
+ *     there is none now.  Calling it again replaces the mask; NULL or all zeros returns the batch to exactly what it reports without
+ *     this call.  Admitted on matrix, DPX_SCORE_ONLY, DPX_KEEP_BAND_DIRECTIONS and DPX_TWO_PIECE_GAPS batches, on a BANW batch whose
+ *     band covers the matrix, and together with dpx_batch_set_extension, _set_substitution, _set_extension_table,
+ *     _set_direction_scoring and _set_second_gap in either call order; packed2 input, dpx_batch_create_on, a caller's stream, repeated
+ *     fills, DPX_TIME_FILLS and dpx_batch_fill_timed work as before.
+ *   Cost.  One device allocation of the batch's sequence bytes plus the reversed copies (a string that several reversed pairs share is
+ *     copied once), one device-to-device copy and one kernel over the copies per call; per fill one pass over the reversed pairs' lines
+ *     behind the walk.  No sequence byte crosses the bus again and the host reads none.
+ *   dpx_batch_describe gains ` reversed=<count>` behind the plan's fields while count > 0, followed by `rev_addr=0x<hex> rev_bytes=<n>`
+ *     (the setter's allocation) and `lines_addr=0x<hex> lines_bytes=<n>` (the traceback line buffer, 0x0 before the first walk):
+ *     diagnostics like pool_addr, for tests that overwrite the blocks to show that no result depends on what they held.  With no
+ *     reversed pair the text is byte for byte what it was.
+ *   DPX_ERR_INVALID      b == NULL
+ *   DPX_ERR_UNSUPPORTED  an algorithm other than BANW / BAXT
+ *   DPX_ERR_RANGE        the copies would end beyond byte 2^31 of the device sequence buffer, where the pair table's int32 indices do not
+ *                        reach (text in dpx_last_error())
+ *   DPX_ERR_NOMEM / DPX_ERR_HIP  the allocation or a device call failed
+ * A refused or failed call changes nothing: dpx_batch_describe is byte-identical before and after, and the batch fills as before. */
+int dpx_batch_set_reversed(dpx_batch *b, const uint8_t *reversed /* numPairs bytes; nonzero = reversed; NULL = none */);
+
 /* Sizes: numPairs, total cells (sum refLen*queryLen, the reference's numCells, c++/parseInput.cpp:100),
  * bytes of HBM the matrices occupy, algorithmic bytes of one fill. */
 int dpx_batch_info(dpx_batch *b, size_t *numPairs, uint64_t *cells, uint64_t *matrixBytes, uint64_t *algorithmicBytes);
