@@ -17,6 +17,7 @@ ALGO_NAMES = {ALGO_LNW: "LNW", ALGO_LSW: "LSW", ALGO_ANW: "ANW", ALGO_BSW: "BSW"
               ALGO_BANW: "BANW", ALGO_BAXT: "BAXT"}
 KEEP_MATRICES, SCORE_ONLY, TIME_FILLS, TUNE_PLACEMENT, KEEP_DIRECTIONS = 0x0, 0x1, 0x2, 0x4, 0x8
 KEEP_BAND_DIRECTIONS = 0x10  # BANW / BAXT: 4-bit direction codes per in-band cell, int32 scores (0x8 stays refused on banded algorithms)
+KEEP_LOCAL_BAND_DIRECTIONS = 0x40  # BSW / BASW: 4-bit direction codes per in-band cell, int32 scores (0x8 and 0x10 stay refused on them)
 TWO_PIECE_GAPS = 0x20  # with KEEP_BAND_DIRECTIONS: a second gap piece (Batch.set_second_gap), 8-bit codes, bands up to 256
 MAT_H, MAT_I, MAT_D = 0, 1, 2
 MAT_I2, MAT_D2, MAT_H_PIECE = 3, 4, 5  # Batch.directions on a TWO_PIECE_GAPS batch: piece 2's planes, and the piece of H's gap move

@@ -1,11 +1,12 @@
 /*
- * dpx_banddir.h -- banded direction batches (DPX_KEEP_BAND_DIRECTIONS on BANW / BAXT): the 4-bit code layout and the launchers of
- * dpx_banddir_kernels.hip.  Shared by host and device code.
+ * dpx_banddir.h -- banded direction batches (DPX_KEEP_BAND_DIRECTIONS on BANW / BAXT, DPX_KEEP_LOCAL_BAND_DIRECTIONS on BSW / BASW): the
+ * 4-bit code layout and the launchers of dpx_banddir_kernels.hip and dpx_bdl_kernels.hip.  Shared by host and device code.
  *
  * Code of one cell (one nibble) -- dpx_dir.h's ANW code:
  *   bits 0-1  the move: 1 diagonal, 2 up (QUERY_DELETION), 3 left (QUERY_INSERTION); MATCH versus MISMATCH is rebuilt from the two bases
  *   bit 2     the I (horizontal gap) cell extends rather than opens
  *   bit 3     the D (vertical gap) cell extends rather than opens
+ * BASW stores dpx_dir.h's ASW code (the same, with move 0 where H == 0), BSW its LSW code (move 0-3, bit 2: H == 0).
  *
  * Layout.  The fill runs k_banw_fill's schedule (dpx_layout.h, "Banded SW"): step A = i + j - 2, slot s = (i - j + B-1) >> 1, lane
  * l = s / C, c = s % C with C = dpx_band_cpl(B) slots per lane.  A lane collects its C codes of Gd = 32 / C consecutive steps in four
@@ -58,6 +59,15 @@ hipError_t dpx_launch_bdir_traceback(const dpx_fill_args &a, int numPairs, const
 /* one pair's direction matrix `which` (0 H, 1 I, 2 D) as the row-major (m+1) x (n+1) uint8 enums of c++/backtrack.h */
 hipError_t dpx_launch_bdir_export(const uint8_t *codes, const dpx_pair_dev &pr, const char *seq, int band, int which, uint8_t *out,
                                   hipStream_t stream);
+
+/* dpx_bdl_kernels.hip -- the same three for DPX_KEEP_LOCAL_BAND_DIRECTIONS batches of BSW (`affine` false: LSW's code, bit 2 = "H is 0") and
+ * BASW (true: ASW's code, move 0 = "H is 0") in the same layout: zero floor, neighbours without a cell read H = 0, the end cell is the first
+ * maximum in row-major order, the walk stops where H == 0 and has no tails, the export is 0 on the borders */
+hipError_t dpx_launch_bdl_fill(const dpx_fill_args &a, int C, bool affine, hipStream_t stream);
+hipError_t dpx_launch_bdl_traceback(const dpx_fill_args &a, int numPairs, bool affine, const uint64_t *tbOff, char *tb, int32_t *tbLen,
+                                    hipStream_t stream);
+hipError_t dpx_launch_bdl_export(const uint8_t *codes, const dpx_pair_dev &pr, const char *seq, int band, int which, uint8_t *out,
+                                 hipStream_t stream);
 #endif
 
 #endif

@@ -1,11 +1,12 @@
 /*
- * dpx_banddir_dev.hpp -- device code shared by the three band-direction units: dpx_banddir_kernels.hip (4-bit codes), dpx_bdx_kernels.hip
- * (the same under a table and / or BAXT's extension mode) and dpx_bd2_kernels.hip (two-piece gaps, 8-bit codes).
+ * dpx_banddir_dev.hpp -- device code shared by the band-direction units: dpx_banddir_kernels.hip (4-bit codes), dpx_bdx_kernels.hip
+ * (the same under a table and / or BAXT's extension mode), dpx_bd2_kernels.hip (two-piece gaps, 8-bit codes) and dpx_bdl_kernels.hip
+ * (BSW / BASW: the local forms of walk and export, LOCAL below).
  *
  * Shared as templates (outside the fills' hot loops): window_push, the launch helper of the fills, the two codecs over dpx_banddir.h /
  * dpx_banddir2.h, the walk (banddir_walk) and the export loop (banddir_export).  Shared as text: the fills' frame, dpx_banddir_fill.inc,
- * included inside each fill kernel, and the scan after a step, DPX_BANDDIR_SCAN_AFTER below.  NOT shared, on purpose: bdir_step, bdx_step
- * and bd2_step.  How the same operations are grouped into functions moves the compiler's schedule of these fills
+ * included inside each fill kernel, and the scan after a step, DPX_BANDDIR_SCAN_AFTER below.  NOT shared, on purpose: bdir_step, bdx_step,
+ * bd2_step and bdl_step.  How the same operations are grouped into functions moves the compiler's schedule of these fills
  * (profiles/band_sharing_ab.md); text included inside the kernel does not (profiles/banddir_sharing_ab.md).
  */
 #ifndef DPX_BANDDIR_DEV_HPP
@@ -102,13 +103,16 @@ struct ByteCodec { /* dpx_banddir2.h: moves 1-5 in bits 0-2, I1 / D1 / I2 / D2 e
  * SCORING, its row in an I plane, its column in a D plane) and a ballot gives the number of cells the path really follows; a cell below
  * the ring ends the run early, and the next trip slides the ring.  In SCORING the cell's move names the plane; in a gap state the walk
  * follows that plane's own extend bit.  Then ANW's two tails.  `ring` is the kernel's own kRingBytes of LDS.
+ * LOCAL (k_bdl_traceback, BSW / BASW): the walk stops in SCORING on the first cell whose H is 0 -- BSW (`linear`): bit 2 of its code,
+ * BASW: move 0; a cell without a code (border, outside the band) has H = 0 too -- and there are no tails.  BSW has no gap states: a gap
+ * move is a single step and the next cell is read in SCORING.
  * ----------------------------------------------------------------------------------------------------- */
 constexpr int kRing = 16; /* chunks in LDS */
 constexpr int kRingBytes = kRing * (int)DPX_BANDDIR_CHUNK_BYTES;
 
-template <class Codec>
+template <class Codec, bool LOCAL = false>
 __device__ __forceinline__ void banddir_walk(unsigned char *ring, const dpx_fill_args &a, const int numPairs, const uint64_t *tbOff, char *tb,
-                                             int32_t *tbLen) {
+                                             int32_t *tbLen, [[maybe_unused]] const bool linear = false) {
     const int p = blockIdx.x, lane = threadIdx.x;
     if (p >= numPairs) return;
     const dpx_pair_dev pr = a.pairs[p];
@@ -161,9 +165,24 @@ __device__ __forceinline__ void banddir_walk(unsigned char *ring, const dpx_fill
             __syncthreads();
         }
         const int c0 = code(i, j); /* the walker's own cell: the same byte for every lane */
-        if (c0 < 0) break;         /* (cannot happen: the walker stands on a stored cell of the ring's upper half) */
+        if (c0 < 0) break;         /* (global: cannot happen, the walker stands on a stored cell of the ring's upper half; LOCAL: a border cell or one outside the band, H = 0) */
+        if constexpr (LOCAL) { /* H == 0 ends the walk where it stands in SCORING: BSW's bit 2, BASW's move 0 */
+            if (cur == 0 && (linear ? (c0 & 4) != 0 : (c0 & 3) == 0)) break;
+        }
         const int kind = cur != 0 ? cur : Codec::move(c0);
         if (!Codec::is_move(kind)) break; /* (cannot happen: a stored cell has a move) */
+        if constexpr (LOCAL) {
+            if (kind != 1 && linear) { /* BSW: a gap move is one step, the next cell says its own move (there is no extend bit) */
+                const bool left = kind == 3;
+                if (lane == 0) {
+                    if (left) put(pos - 1, ref[j - 1], ' ', '_');
+                    else put(pos - 1, '_', ' ', qry[i - 1]);
+                }
+                pos--;
+                if (left) j--; else i--;
+                continue;
+            }
+        }
         if (kind != 1) { /* a gap: step l is taken while the cells before it extend in this plane; the cell that opens ends it */
             const bool left = (kind & 1) != 0; /* an I plane: along the row */
             const int bit = Codec::extend_bit(kind);
@@ -187,7 +206,9 @@ __device__ __forceinline__ void banddir_walk(unsigned char *ring, const dpx_fill
         }
         /* the diagonal: step l leaves cell l of the walker's diagonal, which must itself say "diagonal" (lane 0 has said so) */
         const int c = lane == 0 ? c0 : code(i - lane, j - lane);
-        const int steps = run_of(c >= 0 && (lane == 0 || (c & Codec::kMoveMask) == 1));
+        /* (LOCAL: a run ends on the first cell that is zero or not diagonal; BSW's zero cells carry a move, so bit 2 counts) */
+        const int runMask = (LOCAL && linear) ? 7 : Codec::kMoveMask;
+        const int steps = run_of(c >= 0 && (lane == 0 || (c & runMask) == 1));
         if (steps == 0) break; /* (cannot happen) */
         if (lane < steps) {
             const int qd = (int)qry[i - lane - 1], rd = (int)ref[j - lane - 1];
@@ -197,18 +218,21 @@ __device__ __forceinline__ void banddir_walk(unsigned char *ring, const dpx_fill
         i -= steps;
         j -= steps;
     }
-    /* ANW's tails: the rest of column 0 as deletions, then the rest of row 0 as insertions (at most one of the two is left) */
-    for (int x = lane; x < i; x += 64) put(pos - 1 - x, '_', ' ', qry[i - 1 - x]);
-    pos -= max(i, 0);
-    for (int x = lane; x < j; x += 64) put(pos - 1 - x, ref[j - 1 - x], ' ', '_');
-    pos -= max(j, 0);
+    if constexpr (!LOCAL) { /* ANW's tails: the rest of column 0 as deletions, then the rest of row 0 as insertions (at most one of the two is left) */
+        for (int x = lane; x < i; x += 64) put(pos - 1 - x, '_', ' ', qry[i - 1 - x]);
+        pos -= max(i, 0);
+        for (int x = lane; x < j; x += 64) put(pos - 1 - x, ref[j - 1 - x], ' ', '_');
+        pos -= max(j, 0);
+    }
     if (lane == 0) tbLen[p] = cap - pos;
 }
 
 /* One pair's plane `which` as the oracles write it (c++/backtrack.h enums: directionMain NONE 0, MATCH 1, MISMATCH 2, QUERY_INSERTION 3,
  * QUERY_DELETION 4; directionIndel NONE 0, GAP_OPEN 1, GAP_EXTEND 2): 0 outside the band; the in-band border cells of H as ANW exports
- * them; I on the band's lower edge and D on its upper edge are GAP_OPEN by the geometry (-inf >= -inf); else the codec's decode. */
-template <class Codec>
+ * them; I on the band's lower edge and D on its upper edge are GAP_OPEN by the geometry (-inf >= -inf); else the codec's decode.
+ * LOCAL (BSW / BASW): every plane is 0 on the borders, and the edge planes are decoded like every other cell (the neighbour outside the
+ * band read H = 0, D = -inf, so the stored bit says GAP_OPEN). */
+template <class Codec, bool LOCAL = false>
 __device__ __forceinline__ void banddir_export(const unsigned char *codes, const dpx_pair_dev &pr, const char *seq, const int band, const int which,
                                                uint8_t *out) {
     const int n = pr.n, m = pr.m;
@@ -218,9 +242,11 @@ __device__ __forceinline__ void banddir_export(const unsigned char *codes, const
         const int i = (int)(idx / (uint64_t)(n + 1)), j = (int)(idx % (uint64_t)(n + 1));
         uint8_t v = 0;
         if (in_band(i, j, band)) {
-            if (i == 0 || j == 0) {
+            if (LOCAL && (i == 0 || j == 0)) {
+                v = 0;
+            } else if (i == 0 || j == 0) {
                 v = (which != 0 || (i | j) == 0) ? 0 : (j == 0 ? 4 : 3); /* column 0: QUERY_DELETION, row 0: QUERY_INSERTION */
-            } else if ((iPlane && i - j == band - 1) || (dPlane && j - i == band - 1)) {
+            } else if (!LOCAL && ((iPlane && i - j == band - 1) || (dPlane && j - i == band - 1))) {
                 v = 1;
             } else {
                 const int d = Codec::decode(Codec::code_at(codes + (size_t)pr.matOff * 2u, ~0ull, i, j, band, (uint64_t)pr.chunkStride * 2u), which);

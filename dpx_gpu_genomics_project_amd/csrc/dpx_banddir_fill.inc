@@ -18,6 +18,8 @@
  *       line_first_max(L)         an empty sequence: the k in 0 .. L of the first maximum of the border line's cells 1 .. L (0 when L = 0)
  *                             and whatever else the step's arguments need.  The two callables capture BY VALUE: a capture by reference
  *                             takes the address of a weight, and that reordered the registers of every C = 1 instantiation
+ *   DPX_BANDDIR_NO_CELL_H     H of a slot that holds no cell on anti-diagonals 0 and 1: DPX_NEG for the global and extension fills, 0 for the
+ *                             local ones (k_bdl_fill), whose neighbours without a cell read H = 0
  *   DPX_BANDDIR_STEP(P1_, INTERIOR_, A_)   the unit's own step on anti-diagonal A_, with the unit's own arguments; it may name st, i0, j0,
  *                             lane, m, n, B, cEnd, qL, rL, tabL, codeL of this text
  *
@@ -100,8 +102,8 @@
                 st.rch[c] = rb;
             }
             const int bi0 = vi0 + s; /* the slot's cell on a = 1 is (bi0, 1 - bi0) */
-            st.prevH[c] = (B >= 2 && (bi0 == 0 || bi0 == 1)) ? bord1 : DPX_NEG;
-            st.prev2H[c] = (s == ((B - 1) >> 1)) ? 0 : DPX_NEG;
+            st.prevH[c] = (B >= 2 && (bi0 == 0 || bi0 == 1)) ? bord1 : DPX_BANDDIR_NO_CELL_H;
+            st.prev2H[c] = (s == ((B - 1) >> 1)) ? 0 : DPX_BANDDIR_NO_CELL_H;
             st.clear_gaps(c);
         }
         st.bestKey = 0xFFFFFFFFll; /* score 0 at row 0: only H > 0 displaces it */

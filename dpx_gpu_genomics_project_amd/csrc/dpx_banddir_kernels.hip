@@ -159,10 +159,12 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_bdir_fill(const dpx_fill_a
     const int bord1 = oe;                                                                                                \
     auto bord = [o, e](const int k) -> int { return o + k * e; };                                                        \
     auto line_first_max = [e](const int L) -> int { return e > 0 ? L : min(L, 1); };
+#define DPX_BANDDIR_NO_CELL_H DPX_NEG
 #define DPX_BANDDIR_STEP(P1_, INTERIOR_, A_) \
     bdir_step<C, EXT, P1_, INTERIOR_>(st, A_, i0, j0, lane, m, n, B, match, mismatch, o, oe, e, cEnd, qL, rL)
 #include "dpx_banddir_fill.inc"
 #undef DPX_BANDDIR_STEP
+#undef DPX_BANDDIR_NO_CELL_H
 #undef DPX_BANDDIR_WEIGHTS
 }
 

@@ -175,10 +175,12 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_bd2_fill(const dpx_bd2_arg
     const int bord1 = gap_of(g, 1);                                                                                                  \
     auto bord = [g](const int k) -> int { return gap_of(g, k); };                                                                    \
     auto line_first_max = [g, bord1](const int L) -> int { return (L >= 1 && bord1 >= gap_of(g, L)) ? 1 : L; };
+#define DPX_BANDDIR_NO_CELL_H DPX_NEG
 #define DPX_BANDDIR_STEP(P1_, INTERIOR_, A_) \
     bd2_step<C, EXT, TABLE, P1_, INTERIOR_>(st, A_, i0, j0, lane, m, n, B, match, mismatch, g, cEnd, qL, rL, tabL, codeL)
 #include "dpx_banddir_fill.inc"
 #undef DPX_BANDDIR_STEP
+#undef DPX_BANDDIR_NO_CELL_H
 #undef DPX_BANDDIR_WEIGHTS
 }
 

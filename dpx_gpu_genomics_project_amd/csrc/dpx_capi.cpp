@@ -882,10 +882,12 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
         if (device >= n) return DPX_ERR_INVALID;
     } else if (device != -1) return DPX_ERR_INVALID;
     const bool dirFlag = (flags & DPX_KEEP_DIRECTIONS) != 0, bandDirFlag = (flags & DPX_KEEP_BAND_DIRECTIONS) != 0;
-    if ((dirFlag || bandDirFlag) && (flags & DPX_SCORE_ONLY)) return DPX_ERR_INVALID;
+    const bool localFlag = (flags & DPX_KEEP_LOCAL_BAND_DIRECTIONS) != 0; /* (its algorithm rule is the planner's) */
+    if ((dirFlag || bandDirFlag || localFlag) && (flags & DPX_SCORE_ONLY)) return DPX_ERR_INVALID;
+    if (localFlag && (flags & (DPX_KEEP_BAND_DIRECTIONS | DPX_TWO_PIECE_GAPS))) return DPX_ERR_INVALID;
     if (dirFlag && is_banded(params->algo)) return DPX_ERR_UNSUPPORTED; /* 0x8 on a banded algorithm stays refused, with or without 0x10 */
     if ((flags & DPX_TWO_PIECE_GAPS) && !bandDirFlag) return DPX_ERR_INVALID; /* the second gap piece exists on band-direction batches only */
-    if (bandDirFlag && params->algo != DPX_ALGO_BANW && params->algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED; /* (BSW / BASW: not built) */
+    if (bandDirFlag && params->algo != DPX_ALGO_BANW && params->algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED; /* (BSW / BASW: DPX_KEEP_LOCAL_BAND_DIRECTIONS is their flag) */
     rc = bind_device(device);
     if (rc != DPX_OK) return rc;
 
@@ -1090,6 +1092,7 @@ static hipError_t launch_main(dpx_batch *b, const dpx_route &r, hipStream_t s) {
         return dpx_launch_zsub_fill(za, b->R, b->store, subst_lds_bytes(b), s);
     }
     case DPX_MAIN_BDIR: return dpx_launch_bdir_fill(b->args, b->R, r.ext, s);
+    case DPX_MAIN_BDL: return dpx_launch_bdl_fill(b->args, b->R, b->prm.algo == DPX_ALGO_BASW, s);
     case DPX_MAIN_BDX: { /* (dpx_batch_set_direction_scoring: with a table every wave's LDS slice grows by the image, and the workgroup may shrink to one wave) */
         dpx_bdx_args xa = {b->args, nullptr, nullptr, r.ext ? b->zdrop : -1, r.ext ? b->endBonus : -1, b->dExt};
         if (b->substAlphabet) {
@@ -1280,6 +1283,7 @@ int dpx_batch_directions(dpx_batch *b, size_t pair, int which, uint8_t *out) {
     if (b->lastStream && b->lastStream != b->stream) HIP_TRY(hipStreamSynchronize(b->lastStream));
     HIP_TRY(g_tbDevCache.take((void **)&dOut, std::max<size_t>(total, 16), &dOutCap)); /* row-major scratch */
     hipError_t e = b->twoPiece ? dpx_launch_bd2_export(reinterpret_cast<const uint8_t *>(b->dMat), pd, b->dSeq, b->prm.band, which, dOut, b->stream)
+                   : b->bandLocal ? dpx_launch_bdl_export(reinterpret_cast<const uint8_t *>(b->dMat), pd, b->dSeq, b->prm.band, which, dOut, b->stream)
                    : b->bandDirs ? dpx_launch_bdir_export(reinterpret_cast<const uint8_t *>(b->dMat), pd, b->dSeq, b->prm.band, which, dOut, b->stream)
                                  : dpx_launch_export_dir(reinterpret_cast<const uint8_t *>(b->dMat), pd, b->dSeq, b->kernelAlgo, b->R, which, dOut, b->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
@@ -1450,7 +1454,7 @@ int dpx_batch_set_direction_scoring(dpx_batch *b, int32_t zdrop, int32_t endBonu
         if (alphabet < 1 || alphabet > 32 || !codeOf) return DPX_ERR_INVALID;
         for (int x = 0; x < 256; x++) if ((int)codeOf[x] >= alphabet) return DPX_ERR_INVALID;
     }
-    if (!b->bandDirs) return DPX_ERR_UNSUPPORTED; /* matrix and score-only batches, the other algorithms, a covering BANW band (k_affine_dir) */
+    if (!b->bandDirs || b->bandLocal) return DPX_ERR_UNSUPPORTED; /* matrix and score-only batches, the other algorithms (BSW / BASW direction batches included), a covering BANW band (k_affine_dir) */
     const bool scan = zdrop >= 0 || endBonus >= 0;
     if (scan && b->prm.algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED;
     unsigned char image[DPX_SUBST_IMAGE_BYTES];
@@ -1608,6 +1612,7 @@ static int traceback_lines(dpx_batch *b) {
     case DPX_WALK_SUBST: HIP_TRY(dpx_launch_subst_traceback(subst_args(b), n, walk, b->dTbOff, b->dTb, b->dTbLen, b->stream)); break;
     case DPX_WALK_BDIR: HIP_TRY(dpx_launch_bdir_traceback(b->args, n, b->dTbOff, b->dTb, b->dTbLen, b->stream)); break;
     case DPX_WALK_BD2: HIP_TRY(dpx_launch_bd2_traceback(b->args, n, b->dTbOff, b->dTb, b->dTbLen, b->stream)); break;
+    case DPX_WALK_BDL: HIP_TRY(dpx_launch_bdl_traceback(b->args, n, b->prm.algo == DPX_ALGO_BASW, b->dTbOff, b->dTb, b->dTbLen, b->stream)); break;
     }
     /* reversed pairs (dpx_batch_set_reversed): their lines come out of the walk in the reversed frame and are turned round here, once */
     if (b->revCount) HIP_TRY(dpx_launch_flip_lines(b->dPairs, b->dFlagged, (int)b->revCount, b->dTbLen, b->dTbOff, b->dTb, b->stream));

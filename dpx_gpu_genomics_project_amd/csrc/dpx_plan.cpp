@@ -109,8 +109,10 @@ bool fits_dir(const dpx_params &p, long long m, long long n) {
     auto pos = [](long long v) { return v > 0 ? v : 0; };
     auto neg = [](long long v) { return v < 0 ? v : 0; };
     const long long lim = 1ll << 28, diag = pos(std::max<long long>(p.match, p.mismatch)) * std::min(m, n);
-    if (p.algo == DPX_ALGO_LSW) return diag + pos(p.gapOpen) * (m + n) <= lim;
-    if (p.algo == DPX_ALGO_ASW) { /* fits_int16's ASW bounds without the column keys (the direction fill keeps an int32 column per row) */
+    /* (BSW / BASW, DPX_KEEP_LOCAL_BAND_DIRECTIONS: LSW's and ASW's bounds -- a band only removes paths -- and no m + n limit: k_bdl_fill keeps
+     * the value and the position of its running maximum in separate registers) */
+    if (p.algo == DPX_ALGO_LSW || p.algo == DPX_ALGO_BSW) return diag + pos(p.gapOpen) * (m + n) <= lim;
+    if (p.algo == DPX_ALGO_ASW || p.algo == DPX_ALGO_BASW) { /* fits_int16's ASW bounds without the column keys (the direction fill keeps an int32 column per row) */
         const long long o = p.gapOpen, e = p.gapExtend;
         const long long hiH = diag + (pos(o) + pos(e)) * (m + n);
         return neg(o + e) >= -lim && hiH + pos(o) + pos(e) * std::max(m, n) <= lim;
@@ -281,7 +283,7 @@ bool kernel_packed_safe(const dpx_plan &p) { dpx_params kp = p.prm; kp.algo = p.
 
 /* step 1: pairs and geometry */
 int validate_pairs(const dpx_seq_pair *pairs, size_t numBytes, dpx_plan &p, Shape &sh, std::string &err) {
-    const bool dirRange = (p.flags & (DPX_KEEP_DIRECTIONS | DPX_KEEP_BAND_DIRECTIONS)) != 0;
+    const bool dirRange = (p.flags & (DPX_KEEP_DIRECTIONS | DPX_KEEP_BAND_DIRECTIONS | DPX_KEEP_LOCAL_BAND_DIRECTIONS)) != 0;
     p.pairs.resize(p.numPairs);
     for (size_t i = 0; i < p.numPairs; i++) {
         const dpx_seq_pair &sp = pairs[i];
@@ -331,7 +333,11 @@ int choose_kernel(const Knobs &kn, dpx_plan &p, int &R) {
     p.twoPiece = bandDirFlag && (p.flags & DPX_TWO_PIECE_GAPS) != 0; /* (no ANW fall-back: ANW has no second piece) */
     p.gapOpen2 = prm.gapOpen; p.gapExtend2 = prm.gapExtend;
     const bool bandDirCovering = bandDirFlag && !p.twoPiece && prm.algo == DPX_ALGO_BANW && (long long)prm.band >= longest + 1;
-    p.dirs = (p.flags & DPX_KEEP_DIRECTIONS) != 0 || bandDirCovering; p.bandDirs = bandDirFlag && !bandDirCovering; p.kernelAlgo = prm.algo;
+    /* DPX_KEEP_LOCAL_BAND_DIRECTIONS (BSW / BASW; dpx_plan_batch has refused every other algorithm): a covering band takes the matrix batch's
+     * fall-back to LSW / ASW, as a direction batch of that algorithm; every other band runs k_bdl_fill */
+    const bool localFlag = (p.flags & DPX_KEEP_LOCAL_BAND_DIRECTIONS) != 0, localCovering = localFlag && (long long)prm.band >= longest;
+    p.bandLocal = localFlag && !localCovering;
+    p.dirs = (p.flags & DPX_KEEP_DIRECTIONS) != 0 || bandDirCovering || localCovering; p.bandDirs = (bandDirFlag && !bandDirCovering) || p.bandLocal; p.kernelAlgo = prm.algo;
     /* rows per lane: smallest tile that keeps short queries in one stripe, 8 (or DPX_R) otherwise */
     /* linear gaps: 16 rows per lane once a query is longer than 512 (one stripe up to 1024 rows, two 1-KiB sub-tiles per
      * step: measured 4 % faster than 8 rows x 2 rolling stripes); the affine kernel carries three chains and stays at 8 */
@@ -425,7 +431,7 @@ bool want_packed(const dpx_plan &p, const Knobs &kn, const Shape &sh, int R) {
     const size_t pkMinPairs = (sh.linear && R == 16) ? 1400 : 4096;
     bool use = p.store && ((sh.linear && dpx_tiled_stripes(p.maxM, R) == 1) || bandedLinear) && p.numPairs >= pkMinPairs;
     if (kn.packed >= 0) use = kn.packed != 0 && p.store && (sh.linear || bandedLinear);
-    if (!use || p.dirs) return false;
+    if (!use || p.dirs || p.bandDirs) return false; /* (band directions of BSW: every pair on k_bdl_fill) */
     /* 16-bit wrapping arithmetic: only when weights and every intermediate provably fit (also under DPX_PACKED=1) */
     if (!(kernel_packed_safe(p) && (!sh.banded || p.prm.gapOpen <= 0))) return false; /* (the packed band kernel's gap term saturates at 0) */
     return packed_lds(sh.banded, p.maxM, p.maxN).perWave * (DPX_FILL_THREADS / 64) <= kLdsMax; /* very long references do not fit the LDS twice over */
@@ -639,6 +645,11 @@ int launch_scalars(const Knobs &kn, bool banded, size_t lanesRefArea, dpx_plan &
 int dpx_plan_batch(const dpx_params &params, const dpx_seq_pair *pairs, size_t firstPair, size_t numPairs, size_t numBytes, bool packed2Input,
                    unsigned flags, const Knobs &kn, dpx_plan &p, std::string &err) {
     p = dpx_plan();
+    if (flags & DPX_KEEP_LOCAL_BAND_DIRECTIONS) { /* BSW / BASW only, and with none of the flags that choose another storage */
+        if (flags & (DPX_SCORE_ONLY | DPX_KEEP_BAND_DIRECTIONS | DPX_TWO_PIECE_GAPS)) return DPX_ERR_INVALID;
+        if (params.algo != DPX_ALGO_BSW && params.algo != DPX_ALGO_BASW) return DPX_ERR_UNSUPPORTED;
+        if (flags & DPX_KEEP_DIRECTIONS) return DPX_ERR_UNSUPPORTED; /* 0x8 on a banded algorithm stays refused */
+    }
     if (flags & DPX_TWO_PIECE_GAPS) { /* legal only together with DPX_KEEP_BAND_DIRECTIONS, on the algorithms that flag serves */
         if (!(flags & DPX_KEEP_BAND_DIRECTIONS)) return DPX_ERR_INVALID;
         if (params.algo != DPX_ALGO_BANW && params.algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED;
@@ -684,6 +695,8 @@ dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus,
     const int family = algo == DPX_ALGO_ANW ? 1 : algo == DPX_ALGO_ASW ? 2 : algo == DPX_ALGO_ASG ? 3 : 0;
     if (p.dirs) {
         r.dirs = true; r.kernel = dir[family];
+    } else if (p.bandLocal) { /* (no mode: every setter refuses these batches) */
+        r.main = DPX_MAIN_BDL; r.kernel = DPX_K_BDL_FILL;
     } else if (p.bandDirs) { /* (a mode comes through dpx_batch_set_direction_scoring only; extension mode is BAXT's) */
         const bool bdx = extension || substAlphabet;
         r.main = p.twoPiece ? DPX_MAIN_BD2 : bdx ? DPX_MAIN_BDX : DPX_MAIN_BDIR; r.kernel = p.twoPiece ? DPX_K_BD2_FILL : bdx ? DPX_K_BDX_FILL : DPX_K_BDIR_FILL;
@@ -705,9 +718,9 @@ dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus,
                    : p.packed ? DPX_K_LINEAR_FILL_PK : p.lanesPk ? DPX_K_LINEAR_LANES_PK : p.lanePacked ? DPX_K_LINEAR_LANES : p.split ? DPX_K_LINEAR_SPLIT : DPX_K_LINEAR_FILL;
     }
     r.extRecords = r.main == DPX_MAIN_ZEXT || r.main == DPX_MAIN_ZSUB || ((r.main == DPX_MAIN_BDX || r.main == DPX_MAIN_BD2) && extension);
-    r.walk = p.twoPiece ? DPX_WALK_BD2 : p.bandDirs ? DPX_WALK_BDIR : substAlphabet ? DPX_WALK_SUBST : algo == DPX_ALGO_BASW ? DPX_WALK_BASW : is_banw_layout(algo) ? DPX_WALK_BANW
+    r.walk = p.bandLocal ? DPX_WALK_BDL : p.twoPiece ? DPX_WALK_BD2 : p.bandDirs ? DPX_WALK_BDIR : substAlphabet ? DPX_WALK_SUBST : algo == DPX_ALGO_BASW ? DPX_WALK_BASW : is_banw_layout(algo) ? DPX_WALK_BANW
              : p.dirs ? DPX_WALK_DIR : DPX_WALK_PLAIN;
-    r.walkMode = (r.walk == DPX_WALK_BD2 || r.walk == DPX_WALK_BDIR || r.walk == DPX_WALK_DIR) ? 0 : walk_mode(p, tbWalk); /* (one walk: DPX_TB_WALK has no effect) */
+    r.walkMode = (r.walk == DPX_WALK_BDL || r.walk == DPX_WALK_BD2 || r.walk == DPX_WALK_BDIR || r.walk == DPX_WALK_DIR) ? 0 : walk_mode(p, tbWalk); /* (one walk: DPX_TB_WALK has no effect) */
     r.exportKind = is_banw_layout(algo) /* (BAXT stores what BANW stores) */ ? DPX_EXPORT_BANW : algo == DPX_ALGO_BASW ? DPX_EXPORT_BASW : DPX_EXPORT_PLAIN;
     return r;
 }
@@ -725,7 +738,7 @@ const char *dpx_route_kernel_name(dpx_fill_kernel k) {
         "k_affine_fill", "k_asw_fill", "k_asg_fill", "k_affine_lanes", "k_asw_lanes", "k_asg_lanes",
         "k_banded_fill", "k_banded_fill_pk", "k_basw_fill", "k_banw_fill", "k_baxt_fill",
         "k_zext_fill", "k_subst_fill", "k_zsub_fill", "k_bdir_fill", "k_bdx_fill", "k_bd2_fill",
-        "k_linear_dir", "k_affine_dir", "k_asw_dir", "k_asg_dir"};
+        "k_linear_dir", "k_affine_dir", "k_asw_dir", "k_asg_dir", "k_bdl_fill"};
     return k >= 0 && k < DPX_K_COUNT ? names[k] : "?";
 }
 
@@ -739,6 +752,7 @@ const char *dpx_route_walk_name(dpx_walk_family walk, int walkMode) {
     case DPX_WALK_SUBST: return wave ? "k_subst_traceback_wave" : "k_subst_traceback";
     case DPX_WALK_BDIR: return "k_bdir_traceback";
     case DPX_WALK_BD2: return "k_bd2_traceback";
+    case DPX_WALK_BDL: return "k_bdl_traceback";
     }
     return "?";
 }
@@ -755,7 +769,7 @@ int dpx_plan_describe(const dpx_plan &b, int tbWalk, int zdrop, int endBonus, in
                        name(b.prm.algo), name(b.kernelAlgo), dpx_route_kernel_name(r.kernel), (b.packed || b.lanesPk) ? "int16" : "int32", b.R, b.store ? 1 : 0, b.nCouples, b.nLanePairs,
                        b.nWaves, b.nSingles, (int)b.pkArgs.rowTags, b.packed2 ? "packed2" : "bytes",
                        b.dirs ? b.dirArgs.wavesPerBlock : (b.packed || b.lanePacked) ? b.pkArgs.wavesPerBlock : b.split ? (unsigned)b.splitWaves : b.bandDirs ? dpx_plan_bdx_waves(b, substAlphabet != 0) : b.args.wavesPerBlock);
-    if (is_banded_affine(b.kernelAlgo) && len > 0 && (size_t)len < cap) /* which walk the batch's traceback takes */
+    if ((is_banded_affine(b.kernelAlgo) || b.bandLocal) && len > 0 && (size_t)len < cap) /* which walk the batch's traceback takes */
         len += snprintf(buf + len, cap - (size_t)len, " traceback=%s", dpx_route_walk_name(r.walk, r.walkMode));
     if (extension && len > 0 && (size_t)len < cap)
         len += snprintf(buf + len, cap - (size_t)len, " zdrop=%d end_bonus=%d", (int)zdrop, (int)endBonus);

@@ -17,6 +17,8 @@
 // -match / -mismatch.  NCBI text format: '#' lines are comments; one header row of 1..32 single-character column letters; then one row
 // per letter: the letter, then that many integers in -128..127.  The row letter is the REFERENCE's.  A lower-case byte takes its
 // upper-case letter's code, every other unlisted byte the last letter's ('*' in NCBI files, 'N' in a DNA file).
+// -directions with -algo BSW|BASW keeps band direction codes too (DPX_KEEP_LOCAL_BAND_DIRECTIONS, k_bdl_fill): int32 scores, so pairs run that
+// the int16 matrices refuse, and the output is what the run without -directions prints.
 // -directions with -algo BANW|BAXT keeps band direction codes (DPX_KEEP_BAND_DIRECTIONS); -zdrop / -endbonus / -matrix then go through
 // dpx_batch_set_direction_scoring (k_bdx_fill) and print what the run without -directions prints.
 // -open2 O2 -extend2 E2 (both or neither; only with -directions and -algo BANW|BAXT): two-piece affine gaps, a gap of length k scores
@@ -130,7 +132,7 @@ static void usage() {
     fprintf(stderr, "usage: dpx_main -pairs <InSeqFile> -match <matchWeight> -mismatch <mismatchWeight> -open <gapWeight> "
                     "[-extend <gapExtend>] [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band <B>] [-batch <N>] [-device <D>] [-noprint] [-cigar [M]] "
                     "[-zdrop <Z>] [-endbonus <E>] (BAXT only) [-matrix <file>] (BANW / BAXT, not with -zdrop / -endbonus) "
-                    "[-directions] (direction codes instead of score matrices; BANW / BAXT: with -zdrop / -endbonus / -matrix too) "
+                    "[-directions] (direction codes instead of score matrices; -algo BSW|BASW -directions: one code per in-band cell, long pairs run; BANW / BAXT: with -zdrop / -endbonus / -matrix too) "
                     "[-open2 <O2> -extend2 <E2>] (two-piece gaps: both together, only with -directions and -algo BANW|BAXT) "
                     "[-reverse] (align every pair right to left on the device, output in the file's orientation; only with -algo BANW|BAXT)\n");
     exit(EXIT_FAILURE);
@@ -147,7 +149,7 @@ int main(int argc, char *argv[]) {
     bool cigar = false;      // -cigar: records + CIGAR ops instead of the text pipeline
     unsigned cigarFlags = DPX_CIGAR_EXTENDED;
     bool directions = false; // -directions: batches keep 4-bit direction codes (DPX_KEEP_DIRECTIONS): int32 scores, a quarter of the pool per pair
-                             // (-algo BANW | BAXT: DPX_KEEP_BAND_DIRECTIONS, one code per in-band cell)
+                             // (-algo BANW | BAXT: DPX_KEEP_BAND_DIRECTIONS, -algo BSW | BASW: DPX_KEEP_LOCAL_BAND_DIRECTIONS, one code per in-band cell)
     int zdrop = -1, endBonus = -1; // -zdrop / -endbonus: BAXT's extension mode (dpx_batch_set_extension) on every batch; -1 = off
     bool haveOpen2 = false, haveExtend2 = false; // -open2 / -extend2: the second gap piece (dpx_batch_set_second_gap) on every batch
     int gapOpen2 = 0, gapExtend2 = 0;
@@ -257,9 +259,11 @@ int main(int argc, char *argv[]) {
         const long long mq = fileInfo.maxQueryLength, dR = mq <= 128 ? 2 : mq <= 256 ? 4 : (mq <= 512 || algo != DPX_ALGO_LNW) ? 8 : 16;
         const double dirRows = (double)((mq + 64 * dR - 1) / (64 * dR) * 64 * dR);
         const double dirCols = (double)(((long long)fileInfo.maxReferenceLength + 63 + 32 / dR - 1) / (32 / dR) * (32 / dR));
-        // (-directions on BANW / BAXT: ceil((m + n - 1) / Gd) chunks of 1 KiB, Gd = 32 / C steps per chunk, C = cells per lane of the
+        // (-directions on a banded algorithm: ceil((m + n - 1) / Gd) chunks of 1 KiB, Gd = 32 / C steps per chunk, C = cells per lane of the
         // band -- the layout of csrc/dpx_banddir.h)
-        const bool bandDirections = directions && (algo == DPX_ALGO_BANW || algo == DPX_ALGO_BAXT);
+        // (BSW / BASW under a covering band run as LSW / ASW direction batches: the estimate above)
+        const bool localAlgo = algo == DPX_ALGO_BSW || algo == DPX_ALGO_BASW;
+        const bool bandDirections = directions && bandAlgo && (!localAlgo || (long long)band < std::max<long long>(mq, fileInfo.maxReferenceLength));
         const long long bC0 = ((long long)band + 63) / 64, bC = bC0 <= 1 ? 1 : bC0 <= 2 ? 2 : bC0 <= 4 ? 4 : 8, bGd = (twoPiece ? 16 : 32) / bC; // (two-piece: a byte per cell, csrc/dpx_banddir2.h)
         const double bandDirChunks = (double)((mq + (long long)fileInfo.maxReferenceLength - 1 + bGd - 1) / bGd);
         const double perPair = bandDirections ? 1024.0 * bandDirChunks + 1024.0
@@ -370,7 +374,8 @@ int main(int argc, char *argv[]) {
         next.count = std::min(batchSize, shardHi - first);
         const uint64_t t0 = get_time();
         const bool bandDirections = directions && (algo == DPX_ALGO_BANW || algo == DPX_ALGO_BAXT);
-        const unsigned flags = (twoPiece ? DPX_TWO_PIECE_GAPS : 0u) | (bandDirections ? DPX_KEEP_BAND_DIRECTIONS : directions ? DPX_KEEP_DIRECTIONS : DPX_KEEP_MATRICES) | DPX_TIME_FILLS | ((tunePools && tuned.fetch_add(1) < inflight) ? DPX_TUNE_PLACEMENT : 0u);
+        const bool localDirections = directions && (algo == DPX_ALGO_BSW || algo == DPX_ALGO_BASW);
+        const unsigned flags = (twoPiece ? DPX_TWO_PIECE_GAPS : 0u) | (bandDirections ? DPX_KEEP_BAND_DIRECTIONS : localDirections ? DPX_KEEP_LOCAL_BAND_DIRECTIONS : directions ? DPX_KEEP_DIRECTIONS : DPX_KEEP_MATRICES) | DPX_TIME_FILLS | ((tunePools && tuned.fetch_add(1) < inflight) ? DPX_TUNE_PLACEMENT : 0u);
         int prc = pack2 ? dpx_batch_create_packed2(-1, &prm, packed.data(), fileInfo.numBytes, alphabet, reinterpret_cast<const dpx_seq_pair *>(sequenceIdxs),
                                                    first, next.count, flags, &next.b)
                         : dpx_batch_create(&prm, sequences, fileInfo.numBytes, reinterpret_cast<const dpx_seq_pair *>(sequenceIdxs), first, next.count,

@@ -16,7 +16,7 @@
  *
  * Output, one line: "status=<n>", then for a refusal " err=<text>" when there is one, else dpx_batch_describe()'s text up to the pool
  * fields, " info=<numPairs>,<cells>,<matrixBytes>,<algorithmicBytes>" (dpx_batch_info), " state=<16 hex digits>" and, only when a mode
- * line was given, " walk=<family>:<mode>": the traceback's family (plain, dir, basw, banw, subst, bdir) and walk (0, 1 or 2) of
+ * line was given, " walk=<family>:<mode>": the traceback's family (plain, dir, basw, banw, subst, bdir, bd2, bdl) and walk (0, 1 or 2) of
  * dpx_plan_route, which describe's traceback= shows for the banded affine kernels only.
  *
  * state is FNV-1a 64 over, in this order (integers as 8 little-endian bytes, sign-extended):
@@ -103,7 +103,7 @@ int main() {
     printf("status=0 %s info=%zu,%llu,%llu,%llu state=%016llx", text, plan.numPairs, (unsigned long long)plan.cells,
            (unsigned long long)(plan.matElems * sizeof(int16_t)), (unsigned long long)plan.algBytes, (unsigned long long)plan_state(plan));
     if (mode) {
-        static const char *const family[] = {"plain", "dir", "basw", "banw", "subst", "bdir", "bd2"}; /* dpx_walk_family */
+        static const char *const family[] = {"plain", "dir", "basw", "banw", "subst", "bdir", "bd2", "bdl"}; /* dpx_walk_family */
         const dpx_route r = dpx_plan_route(plan, kn.tbWalk, zdrop, endBonus, substAlphabet);
         printf(" walk=%s:%d", family[r.walk], r.walkMode);
     }

@@ -25,7 +25,7 @@ extern "C" {
 /* 1: round 1.  2: + dpx_batch_create_on, dpx_batch_fill_timed, dpx_batch_last_fill_usec, dpx_batch_output_begin/_end/_take,
  * dpx_text_free, DPX_TUNE_PLACEMENT (round 2).  3: + dpx_pool_reserve, dpx_text_reserve, dpx_batch_last_output_usec, dpx_pack2, dpx_batch_create_packed2; dpx_batch_describe reports the
  * matrix pool (round 3); + DPX_KEEP_DIRECTIONS, dpx_batch_directions (detect them by the exported symbol: the number stays 3); + DPX_ALGO_ASW
- * (detect it by creating a batch: an older library returns DPX_ERR_INVALID for algo 4); + DPX_ALGO_BASW (likewise: DPX_ERR_INVALID for algo 5); + DPX_ALGO_ASG (likewise: DPX_ERR_INVALID for algo 6); + DPX_ALGO_BANW (likewise: DPX_ERR_INVALID for algo 7); + DPX_ALGO_BAXT (likewise: DPX_ERR_INVALID for algo 10); + dpx_batch_cigars_begin / _end, dpx_cigar_text (detect them by the exported symbol).  Additions only: a caller built against an older version keeps working; dpx_abi_version() >= the version
+ * (detect it by creating a batch: an older library returns DPX_ERR_INVALID for algo 4); + DPX_ALGO_BASW (likewise: DPX_ERR_INVALID for algo 5); + DPX_ALGO_ASG (likewise: DPX_ERR_INVALID for algo 6); + DPX_ALGO_BANW (likewise: DPX_ERR_INVALID for algo 7); + DPX_ALGO_BAXT (likewise: DPX_ERR_INVALID for algo 10); + dpx_batch_cigars_begin / _end, dpx_cigar_text (detect them by the exported symbol); + DPX_KEEP_LOCAL_BAND_DIRECTIONS (an older library ignores the bit: dpx_batch_describe then shows kernel=k_banded_fill / k_basw_fill).  Additions only: a caller built against an older version keeps working; dpx_abi_version() >= the version
  * a caller needs is the check. */
 #define DPX_ABI_VERSION 3
 
@@ -64,7 +64,8 @@ typedef enum dpx_algo {
                          cannot leave the band (an extension out of a cell outside the band costs -infinity + e, so GAP_OPEN wins there).
                          LSW's / ASW's text block.  B >= max(m, n) of the batch runs as ASW (same results); otherwise B <= 512, a wider
                          band that does not cover the matrix is DPX_ERR_UNSUPPORTED.  gapOpen = 0 gives BSW's H matrix with linear gap
-                         gapExtend.  Matrices and DPX_SCORE_ONLY; DPX_KEEP_DIRECTIONS is DPX_ERR_UNSUPPORTED, as for BSW.
+                         gapExtend.  Matrices and DPX_SCORE_ONLY; DPX_KEEP_DIRECTIONS is DPX_ERR_UNSUPPORTED, as for BSW (4-bit codes per
+                         in-band cell: DPX_KEEP_LOCAL_BAND_DIRECTIONS).
                          Added without an ABI bump or a new symbol: a library that predates it returns DPX_ERR_INVALID for algo 5. */
     DPX_ALGO_ASG = 6, /* affine-gap semi-global alignment ("fitting", "glocal", ends-free in the reference), no reference counterpart: the
                          whole query is aligned end to end against the stretch of the reference that fits it best; the reference before
@@ -192,7 +193,7 @@ typedef struct dpx_params {
                                     a few hundred rows on; short reads keep a larger fraction); scores may exceed int16 (bounds checked against 2^28) and references 65 000 columns.
                                     dpx_batch_matrix() returns DPX_ERR_NO_MATRIX, dpx_batch_directions() exports the codes.  With
                                     DPX_SCORE_ONLY: DPX_ERR_INVALID; with BSW / BASW / BANW / BAXT: DPX_ERR_UNSUPPORTED, with or without 0x10
-                                    (BANW and BAXT keep directions under DPX_KEEP_BAND_DIRECTIONS below; BSW / BASW directions are not implemented). */
+                                    (BANW and BAXT keep directions under DPX_KEEP_BAND_DIRECTIONS below, BSW and BASW under DPX_KEEP_LOCAL_BAND_DIRECTIONS). */
 #define DPX_KEEP_BAND_DIRECTIONS 0x10u /* BANW / BAXT: keep one 4-bit direction code per IN-BAND cell instead of the three int16 planes, compute in int32
                                     (k_bdir_fill; half a byte per in-band cell in whole 1-KiB chunks, a twelfth of the matrix batch's bytes).
                                     The definitions of BANW and BAXT do not change: same scores, end cells, traceback lines, text blocks and
@@ -205,7 +206,7 @@ typedef struct dpx_params {
                                     along row 0, NONE_MAIN at (0, 0)), borders of I and D are 0; every plane is 0 outside the band.
                                     A separate bit because 0x8 on a banded algorithm is pinned to DPX_ERR_UNSUPPORTED, and stays so.
                                     With DPX_SCORE_ONLY: DPX_ERR_INVALID.  With another algorithm than BANW / BAXT: DPX_ERR_UNSUPPORTED (BSW /
-                                    BASW are follow-ups).  Band > 512 (BANW: not covering): DPX_ERR_UNSUPPORTED, BANW's admission rule
+                                    BASW: DPX_KEEP_LOCAL_BAND_DIRECTIONS).  Band > 512 (BANW: not covering): DPX_ERR_UNSUPPORTED, BANW's admission rule
                                     |m - n| < B unchanged, as for matrix batches.  A BANW band that covers the matrix (B >= max(m, n) + 1)
                                     runs as an ANW DPX_KEEP_DIRECTIONS batch (kernel_algo=ANW), the fall-back the matrix batch takes.
                                     dpx_batch_set_extension and dpx_batch_set_substitution on such a batch: DPX_ERR_UNSUPPORTED, the batch is
@@ -218,6 +219,34 @@ typedef struct dpx_params {
                                     bit and builds an int16 matrix batch -- dpx_batch_describe then shows kernel=k_banw_fill / k_baxt_fill
                                     (this library: kernel=k_bdir_fill, or k_affine_dir under a covering BANW band) and dpx_batch_directions
                                     returns DPX_ERR_NO_MATRIX. */
+#define DPX_KEEP_LOCAL_BAND_DIRECTIONS 0x40u /* BSW / BASW: keep one 4-bit direction code per IN-BAND cell (i, j >= 1) instead of the int16 planes, compute in
+                                    int32 (k_bdl_fill; dpx_banddir.h's layout unchanged: half a byte per in-band cell in whole 1-KiB chunks, a quarter
+                                    of BSW's bytes and a twelfth of BASW's).  The definitions of BSW and BASW do not change: same scores, end
+                                    cells, traceback lines, text blocks, dpx_alignment records and CIGAR ops as a DPX_KEEP_MATRICES batch wherever
+                                    that batch is admitted -- and batches it refuses with DPX_ERR_RANGE run: the bounds are LSW's (BSW) and ASW's
+                                    (BASW; a band only removes paths), checked against 2^28, with no n or m + n limit.
+                                    dpx_batch_matrix() returns DPX_ERR_NO_MATRIX.  dpx_batch_directions() exports c++/backtrack.h enums, row-major
+                                    (m+1) x (n+1); every plane is 0 on the borders and outside the band.  BSW, DPX_MAT_H only: NONE_MAIN iff
+                                    t = max(up, left, corner) < 0, else QUERY_DELETION when up == H, else QUERY_INSERTION when left == H, else
+                                    MATCH / MISMATCH -- a cell with t == 0 has H == 0 and still carries a move (the walk stops there all the
+                                    same); the other selectors answer what an LSW direction batch answers.  BASW: DPX_MAT_H is NONE_MAIN where
+                                    H == 0; DPX_MAT_I / DPX_MAT_D are GAP_OPEN / GAP_EXTEND for every in-band cell (on the band's edges the
+                                    neighbour outside it reads H = 0, I = D = -infinity, so the cell opens).
+                                    A separate bit because 0x10 on BSW / BASW is pinned to DPX_ERR_UNSUPPORTED, as 0x8 is, and both stay so.
+                                    With DPX_SCORE_ONLY, 0x10 or 0x20: DPX_ERR_INVALID.  With 0x8 on BSW / BASW: DPX_ERR_UNSUPPORTED (the rule
+                                    above wins).  With another algorithm than BSW / BASW: DPX_ERR_UNSUPPORTED.  Band > 512 and not covering:
+                                    DPX_ERR_UNSUPPORTED.  A band that covers the matrix (B >= max(m, n) over the batch) runs as an LSW / ASW
+                                    DPX_KEEP_DIRECTIONS batch (kernel_algo=LSW / ASW, k_linear_dir / k_asw_dir), the fall-back the matrix batch
+                                    takes.  Strings are staged in LDS as for 0x10: one-wave workgroups where four waves' strings do not fit, and
+                                    DPX_ERR_UNSUPPORTED where one wave's do not.  DPX_TIME_FILLS, dpx_batch_fill_timed, repeated fills, a caller's
+                                    stream, dpx_batch_create_on, packed2 input, the output pipeline and dpx_batch_cigars_* as for a BSW / BASW
+                                    matrix batch; DPX_TB_WALK has no effect (one walk, k_bdl_traceback).  Every setter refuses as it does for
+                                    a BSW / BASW matrix batch (substitution tables, z-drop, end bonus, two-piece gaps and reversed pairs are
+                                    not built for these batches), and leaves the batch as it was.
+                                    Added without an ABI bump or a new symbol.  Detecting it: a library that predates the flag ignores the
+                                    bit and builds an int16 matrix batch -- dpx_batch_describe then shows kernel=k_banded_fill /
+                                    k_banded_fill_pk / k_basw_fill (this library: kernel=k_bdl_fill, or k_linear_dir / k_asw_dir under a
+                                    covering band) and dpx_batch_directions returns DPX_ERR_NO_MATRIX. */
 
 /* matrix selectors for dpx_batch_matrix / dpx_batch_directions */
 #define DPX_MAT_H 0 /* scoring matrix   (reference: memo / scoringMemo)            */
