@@ -98,8 +98,9 @@ def _want(orc, algo, sb, w, band, ext):
     return _WANT[key]
 
 
-def _read_and_compare(gpu, b, want, dirs, ext, what):
-    """everything the filled batch `b` can give against `want`"""
+def _read_and_compare(gpu, b, want, dirs, ext, what, picks=None):
+    """everything the filled batch `b` can give against `want`.  `picks`: the pairs whose planes are read (all of them by default).  A
+    pair of `want` may carry "cigar_end", the cell its alignment coordinates count from where that is not its end cell (a reversed pair)"""
     scores, rows, cols = b.results()
     for p, r in enumerate(want):
         assert (int(scores[p]), (int(rows[p]), int(cols[p]))) == (r["score"], r["end"]), (what, p, "score / end cell")
@@ -108,6 +109,8 @@ def _read_and_compare(gpu, b, want, dirs, ext, what):
         for p, r in enumerate(want):
             assert {k: int(recs[k][p]) for k in zext_ref.FIELDS} == r["rec"], (what, p, "extension record")
     for p, r in enumerate(want):
+        if picks is not None and p not in picks:
+            continue
         for which in range(len(r["planes"])):
             got = b.directions(p, which) if dirs else b.matrix(p, which).astype(np.int32)
             ref = r["dirs"][which] if dirs else r["planes"][which]
@@ -122,7 +125,8 @@ def _read_and_compare(gpu, b, want, dirs, ext, what):
     for flags in (R.FLAG_EXTENDED, R.FLAG_M):
         b.cigars_begin(flags)
         recs, ops = b.cigars_end()
-        wrecs, wops = R.batch([r["lines"] for r in want], [r["end"][0] for r in want], [r["end"][1] for r in want], flags)
+        ends = [r.get("cigar_end", r["end"]) for r in want]
+        wrecs, wops = R.batch([r["lines"] for r in want], [e[0] for e in ends], [e[1] for e in ends], flags)
         assert ops.tolist() == wops, (what, "CIGAR ops", flags)
         for p, wr in enumerate(wrecs):
             assert {k: int(recs[k][p]) for k in wr} == wr, (what, p, "CIGAR record", flags)

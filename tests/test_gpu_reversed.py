@@ -73,8 +73,9 @@ def _texts(seed=5):
 
 def _flat(texts, residues=True):
     """The flat buffer by hand: pair p's reference starts at p mod 16 (mod 16), its query at p + 8 (mod 16), so 16 pairs put a string
-    of each kind on every residue; pair 0's reference is at byte 0, so the device copy keeps the residues.  residues=False: no padding
-    at all, every string directly behind the one before."""
+    of each kind on every residue; pair 0's reference is at byte 0, so the device copy keeps the residues (tests/layouts.py has the
+    window that does not start at byte 0, where host and device residues differ; tests/test_gpu_layouts.py runs the setter on it).
+    residues=False: no padding at all, every string directly behind the one before."""
     buf, pairs = bytearray(), np.zeros(len(texts), PAIR_DTYPE)
     for p, (ref, qry) in enumerate(texts):
         at = []

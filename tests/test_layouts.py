@@ -1,0 +1,204 @@
+"""tests/layouts.py and tests/layout_cases.py without a GPU: the builders keep every byte of the texts and have the properties the GPU
+tests rely on (residues, order, shared bytes, the window), the planner decides the same for every layout of every case, firstPair
+selects the right slice of the table, and the `embedded` layout is not vacuous: on the oracle alone, reading the flanks changes the
+answer of every case."""
+import subprocess
+
+import numpy as np
+import pytest
+
+import layout_cases as L
+import layouts
+import plan_cases
+from layouts import LAYOUTS, lay
+
+TEXT_SETS = {
+    "standard": L.standard_texts(),
+    "coupled": L.coupled_texts(),
+    "one_pair": [(b"ACGTTGCA", b"ACGTGCA")],
+    "all_empty": [(b"", b"")] * 3,
+    "empties_first": [(b"", b"ACG"), (b"TTGACA", b""), (b"", b""), (b"GATTACA", b"GATACA")],
+    "other_bytes": [(b"0123", b"0123"), (b"\xff\x01ab", b"ab"), (b"n", b"")],
+}
+
+
+@pytest.mark.parametrize("layout", LAYOUTS)
+@pytest.mark.parametrize("name", list(TEXT_SETS))
+def test_builders_keep_the_texts(name, layout):
+    texts = TEXT_SETS[name]
+    laid = lay(layout, texts)
+    sb = laid.sb
+    assert sb.num_pairs == laid.num_pairs == len(texts)
+    assert [(sb.ref(p), sb.qry(p)) for p in range(len(texts))] == texts
+    whole = laid.pairs
+    assert ((whole["referenceIdx"] >= 0) & (whole["queryIdx"] >= 0)).all()
+    assert (whole["referenceIdx"] + whole["referenceSize"] <= laid.sequences.size).all() and (whole["queryIdx"] + whole["querySize"] <= laid.sequences.size).all()
+    if layout != "canonical":   # filler, flanks and junk come from the texts' own bytes (ACGT where all are empty) and are never NUL
+        assert set(laid.sequences.tolist()) <= (set(b"".join(r + q for r, q in texts)) or set(b"ACGT")) and laid.sequences.all()
+
+
+def test_residues_and_windowed_reach_every_residue():
+    texts = L.standard_texts()
+    assert len(texts) >= 16
+    everything = {(kind, r) for kind in ("ref", "qry") for r in range(16)}
+    for layout, smallest in (("residues", 5), ("windowed", 4101)):
+        laid = lay(layout, texts)
+        assert laid.coverage == everything, (layout, everything - laid.coverage)
+        assert laid.smallest_offset == smallest and smallest % 16 == 5
+        own = laid.sb.pairs   # host residues are the device's plus 5: the rebasing shows
+        assert [int(x) % 16 for x in own["referenceIdx"]] == [(p + 5) % 16 for p in range(len(texts))]
+        assert [int(x) % 16 for x in own["queryIdx"]] == [(p + 13) % 16 for p in range(len(texts))]
+    for case in L.CASES:   # the other text sets: every residue too, but for the three long pairs of the global-edge cases
+        if "global-edges" not in case.id:
+            assert lay("residues", L.texts_of(case)).coverage == everything, case.id
+    w = lay("windowed", texts)
+    assert (w.first_pair, w.num_pairs, len(w.pairs)) == (2, len(texts), len(texts) + 4)
+    decoys = [tuple(int(x) for x in w.pairs[k]) for k in (0, 1, -2, -1)]
+    real = {tuple(int(x) for x in r) for r in w.sb.pairs}
+    assert not set(decoys) & real and all(max(d[0] + d[1], d[2] + d[3]) <= layouts.JUNK for d in decoys)
+    shapes = {(len(r), len(q)) for r, q in texts}
+    assert all((d[1], d[3]) not in shapes for d in decoys)
+    assert w.sequences[:layouts.JUNK].all() and w.sequences.all()
+
+
+def test_tight_reversed_descends_and_ends_on_the_last_byte():
+    for name in ("standard", "coupled", "one_pair", "empties_first"):
+        texts = TEXT_SETS[name]
+        laid = lay("tight_reversed", texts)
+        own = laid.sb.pairs
+        offs, sizes = [], []
+        for r in own:
+            offs += [int(r["referenceIdx"]), int(r["queryIdx"])]
+            sizes += [int(r["referenceSize"]), int(r["querySize"])]
+        assert offs[0] + sizes[0] == laid.sequences.size                          # pair 0's reference ends on the last byte
+        assert all(offs[k] == offs[k + 1] + sizes[k + 1] for k in range(len(offs) - 1))   # nothing between two strings
+        assert offs[-1] == 0 and sum(sizes) == laid.sequences.size
+    texts = [t for t in TEXT_SETS["standard"] if t[0] and t[1]]
+    own = lay("tight_reversed", texts).sb.pairs
+    flat = [int(x) for r in own for x in (r["referenceIdx"], r["queryIdx"])]
+    assert all(a > b for a, b in zip(flat, flat[1:])) and (own["queryIdx"] < own["referenceIdx"]).all()
+
+
+def test_shared_shares():
+    for name in ("standard", "coupled"):
+        texts = TEXT_SETS[name]
+        own = lay("shared", texts).sb.pairs
+        records = [tuple(int(x) for x in r) for r in own]
+        assert any(r[0] == r[2] and r[1] == r[3] > 0 for r in records), name                                  # queryIdx == referenceIdx
+        assert any(r[0] < r[2] and r[2] + r[3] < r[0] + r[1] and r[3] > 0 for r in records), name             # a query inside its reference
+        at = {}
+        for (ref, _), r in zip(texts, records):
+            assert at.setdefault(ref, r[0]) == r[0], name                                                     # equal references: one copy
+    records = [tuple(int(x) for x in r) for r in lay("shared", TEXT_SETS["standard"]).sb.pairs]
+    assert len(set(records)) < len(records)                                                                   # an exact duplicate record
+    assert sum(r[0] == records[0][0] and r[1] == 131 for r in records) == 3                                   # three pairs on one reference
+    total = sum(len(r) + len(q) for r, q in TEXT_SETS["standard"])
+    assert lay("shared", TEXT_SETS["standard"]).sequences.size < total - 2 * 131 - 120
+
+
+def test_embedded_flanks_are_the_same_bytes():
+    texts = TEXT_SETS["empties_first"] + TEXT_SETS["standard"]
+    laid = lay("embedded", texts)
+    F = layouts.FLANK
+    for p, (ref, qry) in enumerate(texts):
+        r = laid.sb.pairs[p]
+        oref, oqry = laid.outer(p)
+        assert laid.sequences[r["referenceIdx"] - F:r["referenceIdx"] + len(ref) + F].tobytes() == oref
+        assert laid.sequences[r["queryIdx"] - F:r["queryIdx"] + len(qry) + F].tobytes() == oqry
+        assert oref[:F] == oqry[:F] and oref[len(oref) - F:] == oqry[len(oqry) - F:] and oref[F:len(oref) - F] == ref and oqry[F:len(oqry) - F] == qry
+        assert 0 not in oref + oqry
+
+
+# ------------------------------------------------------------------------------------------------------------------- the case table
+
+def test_the_case_table_names_every_fill_kernel():
+    """27 names in dpx_route_kernel_name; each has a case, each case of a walk family with a choice runs under both walks, and every case
+    runs under non-canonical layouts"""
+    with open(plan_cases.ROOT + "/dpx_gpu_genomics_project_amd/csrc/dpx_plan.cpp") as f:
+        src = f.read()
+    body = src[src.index("dpx_route_kernel_name(dpx_fill_kernel k) {"):]
+    body = body[body.index("{", body.index("names[DPX_K_COUNT]")):body.index("};")]
+    names = {x.strip().strip('"') for x in body.strip("{").split(",") if x.strip()}
+    assert len(names) == 27 and names == L.KERNELS
+    assert {c.kernel for c in L.CASES} == names
+    assert len({c.id for c in L.CASES}) == len(L.CASES)
+    for c in L.CASES:
+        assert set(c.layouts) - {"canonical"} and c.layouts[0] == "canonical", c.id
+        assert c.walks == (L.BOTH if c.storage == "mat" else ("default",)), c.id
+        assert 16 <= len(L.texts_of(c)) <= 20 or c.texts in (L.ragged40_texts, L.ragged_couples_texts, L.global_edge_texts), c.id
+    assert {c.band for c in L.CASES if c.band} == set(L.BANDS)
+
+
+@pytest.fixture(scope="module")
+def tool():
+    return plan_cases.build_tool()
+
+
+def _plan(tool, text):
+    r = subprocess.run([tool], input=text, capture_output=True, text=True)
+    assert r.returncode == 0 and not r.stderr, r.stderr[-2000:]
+    out = r.stdout.rstrip("\n")
+    fields = dict(kv.split("=", 1) for kv in out.split() if "=" in kv)
+    return " ".join(x for x in out.split(" ") if not x.startswith("state=")), fields
+
+
+@pytest.mark.parametrize("case", L.CASES, ids=lambda c: c.id)
+def test_the_plan_does_not_depend_on_the_layout(tool, case):
+    """status, describe text and info= byte for byte (state= hashes refIdx, qryIdx and seqLo and differs, as it should)"""
+    texts = L.texts_of(case)
+    for walk in case.walks:
+        control, fields = _plan(tool, L.plan_tool_input(case, lay("canonical", texts), walk=walk))
+        assert control.startswith("status=0 ") and fields["kernel"] == case.kernel and fields["algo"] == case.algo, control
+        assert all(fields.get(k) == v for k, v in case.describe.items()), control
+        if "traceback" in fields and case.walks == L.BOTH:
+            assert fields["traceback"].endswith("_wave") == (walk == "default"), control
+        states = {fields["state"]}
+        for layout in case.layouts[1:]:
+            got, f = _plan(tool, L.plan_tool_input(case, lay(layout, texts), walk=walk))
+            assert got == control, (case.id, layout, walk)
+            states.add(f["state"])
+        assert len(states) > 1, case.id   # (the offsets did reach the planner)
+
+
+def test_first_pair_selects_the_slice(tool):
+    """an invalid decoy in front of the batch (an offset beyond numBytes) is never looked at under first_pair=2; from pair 0 it refuses"""
+    case = next(c for c in L.CASES if c.id == "BAXT-k_baxt_fill-B17")
+    laid = lay("windowed", L.texts_of(case))
+    control, _ = _plan(tool, L.plan_tool_input(case, laid))
+    laid.pairs[0]["referenceIdx"] = laid.sequences.size + 1
+    got, fields = _plan(tool, L.plan_tool_input(case, laid))
+    assert got == control and fields["status"] == "0" and fields["info"].split(",")[0] == str(laid.num_pairs)
+    refused, fields = _plan(tool, L.plan_tool_input(case, laid, first_pair=0))
+    assert fields["status"] == "-1", refused
+
+
+# ------------------------------------------------------------------------------------------------------------------- not vacuous
+
+@pytest.fixture(scope="module")
+def oracles(tmp_path_factory):
+    return L.build_oracles(tmp_path_factory.mktemp("layout_oracles"))
+
+
+@pytest.mark.parametrize("case", L.CASES, ids=lambda c: c.id)
+def test_embedded_flanks_change_the_answer(oracles, case):
+    """had a kernel read the flanks as part of the strings it would report the outer strings' result: on the oracle, at least one pair's
+    score differs between the strings with and without their flanks, and for local and extension algorithms the end cell (counted from
+    the inner strings' first characters) differs too"""
+    texts = L.texts_of(case)
+    laid = lay("embedded", texts)
+    inner = L.want(oracles, case)
+    outer = [L.expect(oracles, case, *laid.outer(p)) for p in range(len(texts))]
+    F = layouts.FLANK
+    assert any(a["score"] != b["score"] for a, b in zip(inner, outer)), case.id
+    if case.algo in L.LOCAL_OR_EXTENSION:
+        assert any(a["end"] != (b["end"][0] - F, b["end"][1] - F) for a, b in zip(inner, outer)), case.id
+
+
+def test_expectations_are_the_texts_alone(oracles):
+    """want() is keyed by the case: every layout's ref(p) / qry(p) are the bytes it was computed from"""
+    case = L.CASES[0]
+    texts = L.texts_of(case)
+    for layout in LAYOUTS:
+        sb = lay(layout, texts).sb
+        assert [(sb.ref(p), sb.qry(p)) for p in range(sb.num_pairs)] == texts
+    assert len(L.want(oracles, case)) == len(texts) and np.isscalar(L.want(oracles, case)[0]["score"])
