@@ -1,6 +1,8 @@
 /* dpx_affine_dir.inc -- body of the affine-gap direction fills, included by dpx_dir_kernels.hip inside k_affine_dir (ANW, LOCAL = false)
- * k_asw_dir (ASW, LOCAL = true) and k_asg_dir (ASG, SEMI = true), for the reason given in dpx_affine_fill.inc.  In scope: `a`, R, GLOBAL,
- * LOCAL and SEMI. */
+ * k_asw_dir (ASW, LOCAL = true) and k_asg_dir (ASG, SEMI = true), for the reason given in dpx_affine_fill.inc, and by
+ * dpx_dirtab_kernels.hip inside k_dirtab_fill (TABLE = true: the diagonal term is tableG[codeOfG[reference byte] * 32 + codeOfG[query
+ * byte]], dpx_batch_set_direction_table).  In scope: `a`, R, GLOBAL, LOCAL, SEMI, TABLE and the two global pointers tableG / codeOfG
+ * (null constants where TABLE is false: nothing of the table survives in those kernels). */
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int G = 32 / R;
     const int lane = threadIdx.x & 63;
@@ -10,7 +12,7 @@
     const int p = a.order ? a.order[a.firstSlot + slot] : a.firstSlot + slot;
     const dpx_pair_dev pr = a.pairs[p];
     const int n = pr.n, m = pr.m;
-    const int match = a.match, mismatch = a.mismatch;
+    [[maybe_unused]] const int match = a.match, mismatch = a.mismatch;
     const int o = a.gapOpen, e = a.gapExtend, oe = o + e;
 
     if (m <= 0 || n <= 0) {
@@ -27,11 +29,33 @@
     const unsigned char *qry = reinterpret_cast<const unsigned char *>(a.seq + pr.qryIdx);
     unsigned char *my;
     if constexpr (GLOBAL) my = a.scratch + (size_t)slot * a.ldsPerWave;
-    else my = smem + (size_t)wv * a.ldsPerWave;
+    else my = smem + (size_t)wv * a.ldsPerWave; /* (TABLE: a.ldsPerWave counts the image behind the staged reference) */
     int32_t *edgeH = reinterpret_cast<int32_t *>(my);
     int32_t *edgeD = reinterpret_cast<int32_t *>(my + a.ldsEdge2Off);
     const unsigned char *refl = stage_bytes(my + a.ldsRefOff + 64, ref, n, lane, 64) - 64;
     for (int x = lane; x <= n + 1; x += 64) { edgeH[x] = (LOCAL || SEMI) ? 0 : o + x * e; edgeD[x] = DPX_NEG; } /* H[0][j] (:50-53; ASW / ASG 0), virtual D[0][j] */
+    [[maybe_unused]] const signed char *tabL = nullptr;
+    [[maybe_unused]] const unsigned char *codeL = nullptr;
+    if constexpr (TABLE) { /* the wave's own table image (dpx_kernels.h: rows of 32, the map behind them; both arrays 16-byte aligned in one
+                            * device allocation) behind its LDS slice, or -- GLOBAL -- the only thing it keeps in LDS */
+        unsigned char *img = GLOBAL ? smem + (size_t)wv * DPX_SUBST_IMAGE_BYTES : my + (a.ldsPerWave - (uint32_t)DPX_SUBST_IMAGE_BYTES);
+        reinterpret_cast<u32x4 *>(img)[lane] = reinterpret_cast<const u32x4 *>(tableG)[lane];
+        if (lane < 16) reinterpret_cast<u32x4 *>(img + DPX_SUBST_TABLE_BYTES)[lane] = reinterpret_cast<const u32x4 *>(codeOfG)[lane];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+        tabL = reinterpret_cast<const signed char *>(img);
+        codeL = img + DPX_SUBST_TABLE_BYTES;
+        /* the staged reference becomes codes, once (the walk and the export read the caller's bytes from a.seq, never the stage) */
+        unsigned char *sref = const_cast<unsigned char *>(refl) + 64;
+        if constexpr (GLOBAL) __threadfence_block(); /* (a lane translates bytes that other lanes staged) */
+        for (int x = lane; x < n; x += 64) sref[x] = codeL[sref[x]];
+        if constexpr (!GLOBAL) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+        }
+    }
     if constexpr (GLOBAL) __threadfence_block();
 
     const int S = dpx_tiled_stripes(m, R);
@@ -49,7 +73,8 @@
         const bool hasRows = nrows > 0, hasNext = k + 1 < S;
 #pragma unroll
         for (int r = 0; r < R; r++) {
-            qc[r] = r < nrows ? (int)qry[row0 + r] : 0x100;
+            if constexpr (TABLE) qc[r] = r < nrows ? (int)codeL[qry[row0 + r]] : 0; /* the lane's query codes, once per stripe (rows past m: any code, never read back) */
+            else qc[r] = r < nrows ? (int)qry[row0 + r] : 0x100;
             Hl[r] = LOCAL ? 0 : o + (row0 + 1 + r) * e; /* H[i][0] = o + i*e (:43-46); ASW: 0 */
             Il[r] = DPX_NEG;                /* virtual I[i][0] */
             if constexpr (LOCAL) { bv[r] = 0; bc[r] = 0; }
@@ -76,10 +101,14 @@
                 uint32_t w[2] = {0u, 0u};
                 if (hasRows && j >= 1 && j <= n) {
                     int uH = upH, uD = upD, d = dtop;
+                    [[maybe_unused]] const signed char *trow = nullptr;
+                    if constexpr (TABLE) trow = tabL + (rc << 5); /* the table's row is the reference code */
 #pragma unroll
                     for (int r = 0; r < R; r++) {
                         const int lH = Hl[r];
-                        const int s = (qc[r] == rc) ? match : mismatch;
+                        int s;
+                        if constexpr (TABLE) s = trow[qc[r]]; /* one signed byte from LDS */
+                        else s = (qc[r] == rc) ? match : mismatch;
                         const int dOpen = uH + oe, dExt = uD + e; /* :185-197 */
                         const int Dn = max(dOpen, dExt);
                         const int iOpen = lH + oe, iExt = Il[r] + e; /* :201-213 */

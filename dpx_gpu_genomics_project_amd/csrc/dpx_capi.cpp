@@ -509,11 +509,12 @@ struct dpx_batch : dpx_plan {
                                   records, and dpx_batch_matrix / dpx_batch_directions mask behind lastDiag */
     int32_t *dExt = nullptr;   /* device: dpx_extension[numPairs] */
     size_t dExtCap = 0;
-    /* substitution table (dpx_batch_set_substitution): while substAlphabet > 0 the fills run k_subst_fill and the walks k_subst_traceback* */
+    /* substitution table (dpx_batch_set_substitution): while substAlphabet > 0 the fills run k_subst_fill and the walks k_subst_traceback*
+     * (band-direction batches: k_bdx_fill; ANW / ASW / ASG direction batches, dpx_batch_set_direction_table: k_dirtab_fill, the walk stays) */
     int substAlphabet = 0;
     unsigned char *dSubst = nullptr; /* device: the table at row stride 32 (DPX_SUBST_TABLE_BYTES), then codeOf[256] */
     size_t dSubstCap = 0;
-    std::vector<unsigned char> bdxImage; /* dpx_batch_set_direction_scoring: the image dSubst holds, to tell a changed table from the same one */
+    std::vector<unsigned char> bdxImage; /* dpx_batch_set_direction_scoring / _set_direction_table: the image dSubst holds, to tell a changed table from the same one */
     /* orientation (dpx_batch_set_reversed): while revCount > 0 dSeq points at dRev, the setter's own allocation -- [the arena's sequence
      * bytes][reversed copies of the flagged pairs' strings][the kernel's job list][the flagged pairs' numbers] -- and the flagged pairs'
      * indices in `pairs` / dPairs at the copies.  The fills, walks and exports know nothing of it. */
@@ -1114,6 +1115,12 @@ static hipError_t launch_main(dpx_batch *b, const dpx_route &r, hipStream_t s) {
 }
 
 static hipError_t launch_all(dpx_batch *b, const dpx_route &r, hipStream_t s) {
+    if (r.dirTable) { /* (dpx_batch_set_direction_table: edge rows in LDS, every wave's slice grows by the image; the workgroup may shrink to one wave) */
+        dpx_dirtab_args ta = {b->dirArgs, reinterpret_cast<const int8_t *>(b->dSubst), b->dSubst + DPX_SUBST_TABLE_BYTES};
+        if (!ta.d.scratch) ta.d.ldsPerWave += DPX_SUBST_IMAGE_BYTES;
+        ta.d.wavesPerBlock = dpx_plan_dirtab_waves(*b);
+        return dpx_launch_dirtab_fill(ta, b->kernelAlgo, b->R, s);
+    }
     if (r.dirs) return dpx_launch_fill_dir(b->dirArgs, b->kernelAlgo, b->R, s);
     if (r.split) return dpx_launch_fill_split(b->args, b->kernelAlgo, b->R, b->splitWaves, b->splitLds, s);
     hipStream_t side = s;
@@ -1488,6 +1495,43 @@ int dpx_batch_set_direction_scoring(dpx_batch *b, int32_t zdrop, int32_t endBonu
     if (!scores) b->bdxImage.clear();
     b->zdrop = zdrop;
     b->endBonus = endBonus;
+    return DPX_OK;
+}
+
+/* the table of an ANW / ASW / ASG direction batch (k_dirtab_fill); every check comes before the first change */
+int dpx_batch_set_direction_table(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf) {
+    if (!b) return DPX_ERR_INVALID;
+    if (!scores) { /* clear: legal on every batch; the batch runs its plain kernel again */
+        if (b->substAlphabet) invalidate_fill(b);
+        b->substAlphabet = 0;
+        b->bdxImage.clear();
+        return DPX_OK;
+    }
+    if (alphabet < 1 || alphabet > 32 || !codeOf) return DPX_ERR_INVALID;
+    for (int x = 0; x < 256; x++) if ((int)codeOf[x] >= alphabet) return DPX_ERR_INVALID;
+    /* the batch's own algorithm, not the kernel's: a covering BANW / BASW band that runs k_affine_dir / k_asw_dir is not admitted */
+    const bool three = b->prm.algo == DPX_ALGO_ANW || b->prm.algo == DPX_ALGO_ASW || b->prm.algo == DPX_ALGO_ASG;
+    if (!three || !b->dirs || !(b->flags & DPX_KEEP_DIRECTIONS)) return DPX_ERR_UNSUPPORTED;
+    /* fits_dir with the largest entry in place of match and the smallest in place of mismatch, over every pair */
+    dpx_params q = b->prm;
+    q.match = -128; q.mismatch = 127;
+    for (int k = 0; k < alphabet * alphabet; k++) { q.match = std::max<int32_t>(q.match, scores[k]); q.mismatch = std::min<int32_t>(q.mismatch, scores[k]); }
+    for (const dpx_pair_dev &pd : b->pairs) if (!fits_dir(q, pd.m, pd.n)) return DPX_ERR_RANGE;
+    unsigned char image[DPX_SUBST_IMAGE_BYTES];
+    memset(image, 0, sizeof image);
+    for (int r = 0; r < alphabet; r++) memcpy(image + r * 32, scores + r * alphabet, (size_t)alphabet);
+    memcpy(image + DPX_SUBST_TABLE_BYTES, codeOf, 256);
+    if (b->substAlphabet == alphabet && b->bdxImage.size() == sizeof image && !memcmp(b->bdxImage.data(), image, sizeof image)) return DPX_OK; /* the same table: nothing to invalidate */
+    int rc = bind_device(b->device);
+    if (rc != DPX_OK) return rc;
+    if (!b->dSubst) HIP_TRY(g_tbDevCache.take((void **)&b->dSubst, sizeof image, &b->dSubstCap));
+    /* a fill in flight may still read the previous table */
+    if (b->lastStream && b->lastStream != b->stream) HIP_TRY(hipStreamSynchronize(b->lastStream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipMemcpy(b->dSubst, image, sizeof image, hipMemcpyHostToDevice));
+    b->bdxImage.assign(image, image + sizeof image);
+    b->substAlphabet = alphabet;
+    invalidate_fill(b);
     return DPX_OK;
 }
 

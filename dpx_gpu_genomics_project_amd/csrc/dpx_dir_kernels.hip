@@ -22,34 +22,17 @@
 
 #include "dpx_device.hpp"
 #include "dpx_dir.h"
+#include "dpx_dir_dev.hpp"
 #include "dpx_prims.hpp"
 
 namespace {
 
 using dpx::wave_shr1;
+using dpx_dir_dev::dir_put;
+using dpx_dir_dev::dir_store;
 using dpx_dev::stage_bytes;
 using dpx_dev::u32x4;
 using dpx_dev::wave_max_u64;
-
-/* the R codes of one lane and step (4 bits each, row r in bits 4r) into the lane's 32-nibble store word: step q of the group */
-template <int R>
-__device__ __forceinline__ void dir_put(uint32_t (&acc)[4], const int q, const uint32_t w0, const uint32_t w1) {
-    if constexpr (R == 16) {
-        acc[2 * q] = w0;
-        acc[2 * q + 1] = w1;
-    } else if constexpr (R == 8) {
-        acc[q] = w0;
-    } else if constexpr (R == 4) {
-        acc[q >> 1] = (q & 1) ? (acc[q >> 1] | (w0 << 16)) : w0;
-    } else {
-        acc[q >> 2] = (q & 3) ? (acc[q >> 2] | (w0 << (8 * (q & 3)))) : w0;
-    }
-}
-
-__device__ __forceinline__ void dir_store(unsigned char *dst, const uint32_t (&acc)[4]) {
-    const u32x4 v = {acc[0], acc[1], acc[2], acc[3]};
-    *reinterpret_cast<u32x4 *>(dst) = v; /* global_store_dwordx4: the wave writes one whole KiB */
-}
 
 /* =====================================================================================================
  * LNW (LOCAL = false) / LSW (LOCAL = true).
@@ -190,14 +173,16 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_linear_dir(const dpx_dir_a
  * ===================================================================================================== */
 template <int R, bool GLOBAL>
 __global__ void __launch_bounds__(DPX_FILL_THREADS) k_affine_dir(const dpx_dir_args a) {
-    constexpr bool LOCAL = false, SEMI = false;
+    constexpr bool LOCAL = false, SEMI = false, TABLE = false;
+    constexpr const int8_t *tableG = nullptr; constexpr const unsigned char *codeOfG = nullptr;
 #include "dpx_affine_dir.inc"
 }
 
 /* ASW (affine-gap Smith-Waterman, include/dpx_align.h): the same fill with the zero floor; code move 0 where H == 0, bits 2 / 3 as ANW */
 template <int R, bool GLOBAL>
 __global__ void __launch_bounds__(DPX_FILL_THREADS) k_asw_dir(const dpx_dir_args a) {
-    constexpr bool LOCAL = true, SEMI = false;
+    constexpr bool LOCAL = true, SEMI = false, TABLE = false;
+    constexpr const int8_t *tableG = nullptr; constexpr const unsigned char *codeOfG = nullptr;
 #include "dpx_affine_dir.inc"
 }
 
@@ -205,7 +190,8 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_asw_dir(const dpx_dir_args
  * maximum of row m, its column-0 border included */
 template <int R, bool GLOBAL>
 __global__ void __launch_bounds__(DPX_FILL_THREADS) k_asg_dir(const dpx_dir_args a) {
-    constexpr bool LOCAL = false, SEMI = true;
+    constexpr bool LOCAL = false, SEMI = true, TABLE = false;
+    constexpr const int8_t *tableG = nullptr; constexpr const unsigned char *codeOfG = nullptr;
 #include "dpx_affine_dir.inc"
 }
 

@@ -695,6 +695,7 @@ dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus,
     const int family = algo == DPX_ALGO_ANW ? 1 : algo == DPX_ALGO_ASW ? 2 : algo == DPX_ALGO_ASG ? 3 : 0;
     if (p.dirs) {
         r.dirs = true; r.kernel = dir[family];
+        r.dirTable = substAlphabet != 0 && family != 0; /* (set only by dpx_batch_set_direction_table, on a DPX_KEEP_DIRECTIONS batch of the three) */
     } else if (p.bandLocal) { /* (no mode: every setter refuses these batches) */
         r.main = DPX_MAIN_BDL; r.kernel = DPX_K_BDL_FILL;
     } else if (p.bandDirs) { /* (a mode comes through dpx_batch_set_direction_scoring only; extension mode is BAXT's) */
@@ -718,7 +719,7 @@ dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus,
                    : p.packed ? DPX_K_LINEAR_FILL_PK : p.lanesPk ? DPX_K_LINEAR_LANES_PK : p.lanePacked ? DPX_K_LINEAR_LANES : p.split ? DPX_K_LINEAR_SPLIT : DPX_K_LINEAR_FILL;
     }
     r.extRecords = r.main == DPX_MAIN_ZEXT || r.main == DPX_MAIN_ZSUB || ((r.main == DPX_MAIN_BDX || r.main == DPX_MAIN_BD2) && extension);
-    r.walk = p.bandLocal ? DPX_WALK_BDL : p.twoPiece ? DPX_WALK_BD2 : p.bandDirs ? DPX_WALK_BDIR : substAlphabet ? DPX_WALK_SUBST : algo == DPX_ALGO_BASW ? DPX_WALK_BASW : is_banw_layout(algo) ? DPX_WALK_BANW
+    r.walk = p.bandLocal ? DPX_WALK_BDL : p.twoPiece ? DPX_WALK_BD2 : p.bandDirs ? DPX_WALK_BDIR : (substAlphabet && !p.dirs) ? DPX_WALK_SUBST : algo == DPX_ALGO_BASW ? DPX_WALK_BASW : is_banw_layout(algo) ? DPX_WALK_BANW
              : p.dirs ? DPX_WALK_DIR : DPX_WALK_PLAIN;
     r.walkMode = (r.walk == DPX_WALK_BDL || r.walk == DPX_WALK_BD2 || r.walk == DPX_WALK_BDIR || r.walk == DPX_WALK_DIR) ? 0 : walk_mode(p, tbWalk); /* (one walk: DPX_TB_WALK has no effect) */
     r.exportKind = is_banw_layout(algo) /* (BAXT stores what BANW stores) */ ? DPX_EXPORT_BANW : algo == DPX_ALGO_BASW ? DPX_EXPORT_BASW : DPX_EXPORT_PLAIN;
@@ -730,6 +731,11 @@ unsigned dpx_plan_bdx_waves(const dpx_plan &p, bool table) {
     const size_t perWave = (size_t)p.args.ldsPerWave + DPX_SUBST_IMAGE_BYTES;
     if (perWave > kLdsMax) return 0u;
     return perWave * (DPX_FILL_THREADS / 64) > kLdsMax ? 1u : p.args.wavesPerBlock;
+}
+
+unsigned dpx_plan_dirtab_waves(const dpx_plan &p) {
+    const size_t perWave = (p.dirScratch ? 0 : (size_t)p.dirArgs.ldsPerWave) + DPX_SUBST_IMAGE_BYTES;
+    return perWave * p.dirArgs.wavesPerBlock <= kLdsMax ? p.dirArgs.wavesPerBlock : 1u;
 }
 
 const char *dpx_route_kernel_name(dpx_fill_kernel k) {
@@ -768,7 +774,7 @@ int dpx_plan_describe(const dpx_plan &b, int tbWalk, int zdrop, int endBonus, in
     int len = snprintf(buf, cap, "algo=%s kernel_algo=%s kernel=%s dtype=%s rows_per_lane=%d store=%d couples=%zu lane_pairs=%zu waves=%zu singles=%zu row_tags=%d seq_input=%s waves_per_workgroup=%u",
                        name(b.prm.algo), name(b.kernelAlgo), dpx_route_kernel_name(r.kernel), (b.packed || b.lanesPk) ? "int16" : "int32", b.R, b.store ? 1 : 0, b.nCouples, b.nLanePairs,
                        b.nWaves, b.nSingles, (int)b.pkArgs.rowTags, b.packed2 ? "packed2" : "bytes",
-                       b.dirs ? b.dirArgs.wavesPerBlock : (b.packed || b.lanePacked) ? b.pkArgs.wavesPerBlock : b.split ? (unsigned)b.splitWaves : b.bandDirs ? dpx_plan_bdx_waves(b, substAlphabet != 0) : b.args.wavesPerBlock);
+                       b.dirs ? (r.dirTable ? dpx_plan_dirtab_waves(b) : b.dirArgs.wavesPerBlock) : (b.packed || b.lanePacked) ? b.pkArgs.wavesPerBlock : b.split ? (unsigned)b.splitWaves : b.bandDirs ? dpx_plan_bdx_waves(b, substAlphabet != 0) : b.args.wavesPerBlock);
     if ((is_banded_affine(b.kernelAlgo) || b.bandLocal) && len > 0 && (size_t)len < cap) /* which walk the batch's traceback takes */
         len += snprintf(buf + len, cap - (size_t)len, " traceback=%s", dpx_route_walk_name(r.walk, r.walkMode));
     if (extension && len > 0 && (size_t)len < cap)

@@ -102,6 +102,7 @@ struct dpx_route {
     /* the launches of one fill: a direction batch, or the split kernel, or the secondary kernel (if any) beside the one-wave-per-pair
      * kernel of the pairs it leaves over (if any) */
     bool dirs, split;
+    bool dirTable;   /* ... a direction batch of ANW / ASW / ASG under a table (dpx_batch_set_direction_table): k_dirtab_fill, a mode of the same three kernel= names */
     dpx_second_launch second;
     dpx_main_launch main;
     bool ext;        /* the band kernel (BDIR, SUBST) runs BAXT's end-cell rule, not BANW's */
@@ -112,7 +113,8 @@ struct dpx_route {
 };
 /* What a batch can change after its creation comes as arguments: the traceback walk knob, BAXT's extension mode (-1, -1: off) and the
  * substitution alphabet (0: none).  On a bandDirs plan either of the two (dpx_batch_set_direction_scoring) turns k_bdir_fill into
- * k_bdx_fill; the walk stays k_bdir_traceback.  A twoPiece plan runs k_bd2_fill and k_bd2_traceback in every mode; its second piece is
+ * k_bdx_fill; the walk stays k_bdir_traceback.  On a dirs plan of ANW / ASW / ASG the alphabet
+ * (dpx_batch_set_direction_table) sets dirTable and nothing else.  A twoPiece plan runs k_bd2_fill and k_bd2_traceback in every mode; its second piece is
  * the plan's own (the batch IS the plan), so the signatures here do not know it. */
 dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus, int substAlphabet);
 /* Waves per workgroup of a bandDirs plan's fill: the plan's own without a table; with one (DPX_SUBST_IMAGE_BYTES more per wave) the
@@ -120,6 +122,11 @@ dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus,
  * refuses).  The plan's own is 1 or 4 (fill_waves_per_block: DPX_WPB takes no other value), so "four do not fit" and "the plan's own do
  * not fit" are the same test wherever it matters.  A pure function of the plan, which is not changed. */
 unsigned dpx_plan_bdx_waves(const dpx_plan &p, bool table);
+/* Waves per workgroup of a dirs plan's fill under a table (dpx_batch_set_direction_table): the plan's own when that many waves' edge
+ * rows, staged references and images fit one workgroup's LDS, else 1.  One wave always fits (edge rows in LDS: dirArgs.ldsPerWave <= 64
+ * KiB; edge rows in the scratch: the image alone, and the plan's own is 1), so this setter has no "no room in LDS" refusal.  A pure
+ * function of the plan, which is not changed. */
+unsigned dpx_plan_dirtab_waves(const dpx_plan &p);
 const char *dpx_route_kernel_name(dpx_fill_kernel k);
 const char *dpx_route_walk_name(dpx_walk_family walk, int walkMode);
 

@@ -21,6 +21,8 @@
 // the int16 matrices refuse, and the output is what the run without -directions prints.
 // -directions with -algo BANW|BAXT keeps band direction codes (DPX_KEEP_BAND_DIRECTIONS); -zdrop / -endbonus / -matrix then go through
 // dpx_batch_set_direction_scoring (k_bdx_fill) and print what the run without -directions prints.
+// -directions with -algo ANW|ASW|ASG takes -matrix too: the table goes through dpx_batch_set_direction_table (k_dirtab_fill: int32 scores
+// against 2^28, so a protein matrix with entries up to 127 runs on long pairs), and the text and CIGARs stay byte equality.
 // -open2 O2 -extend2 E2 (both or neither; only with -directions and -algo BANW|BAXT): two-piece affine gaps, a gap of length k scores
 // max(open + k * extend, O2 + k * E2) (DPX_TWO_PIECE_GAPS and dpx_batch_set_second_gap, k_bd2_fill; bands up to 256).  They combine with
 // -zdrop / -endbonus / -matrix through dpx_batch_set_direction_scoring.
@@ -131,8 +133,8 @@ bool read_matrix(const char *path, std::vector<int8_t> &scores, int &alphabet, u
 static void usage() {
     fprintf(stderr, "usage: dpx_main -pairs <InSeqFile> -match <matchWeight> -mismatch <mismatchWeight> -open <gapWeight> "
                     "[-extend <gapExtend>] [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band <B>] [-batch <N>] [-device <D>] [-noprint] [-cigar [M]] "
-                    "[-zdrop <Z>] [-endbonus <E>] (BAXT only) [-matrix <file>] (BANW / BAXT, not with -zdrop / -endbonus) "
-                    "[-directions] (direction codes instead of score matrices; -algo BSW|BASW -directions: one code per in-band cell, long pairs run; BANW / BAXT: with -zdrop / -endbonus / -matrix too) "
+                    "[-zdrop <Z>] [-endbonus <E>] (BAXT only) [-matrix <file>] (BANW / BAXT, not with -zdrop / -endbonus; ANW / ASW / ASG only with -directions) "
+                    "[-directions] (direction codes instead of score matrices; -algo BSW|BASW -directions: one code per in-band cell, long pairs run; BANW / BAXT: with -zdrop / -endbonus / -matrix too; -algo ANW|ASW|ASG -directions -matrix <file>: full-matrix affine alignment under a substitution matrix) "
                     "[-open2 <O2> -extend2 <E2>] (two-piece gaps: both together, only with -directions and -algo BANW|BAXT) "
                     "[-reverse] (align every pair right to left on the device, output in the file's orientation; only with -algo BANW|BAXT)\n");
     exit(EXIT_FAILURE);
@@ -207,8 +209,10 @@ int main(int argc, char *argv[]) {
     std::vector<int8_t> substScores;
     int substAlphabet = 0;
     uint8_t substCode[256];
+    // -matrix on a direction batch of the three full-matrix affine algorithms (dpx_batch_set_direction_table)
+    const bool directionTable = matrixFile && directions && (algo == DPX_ALGO_ANW || algo == DPX_ALGO_ASW || algo == DPX_ALGO_ASG);
     if (matrixFile) {
-        if ((algo != DPX_ALGO_BANW && algo != DPX_ALGO_BAXT) || zdrop != -1 || endBonus != -1) usage();
+        if (((algo != DPX_ALGO_BANW && algo != DPX_ALGO_BAXT) && !directionTable) || zdrop != -1 || endBonus != -1) usage();
         std::string why;
         if (!read_matrix(matrixFile, substScores, substAlphabet, substCode, why)) {
             fprintf(stderr, "-matrix %s: %s\n", matrixFile, why.c_str());
@@ -386,6 +390,8 @@ int main(int argc, char *argv[]) {
             if ((zdrop != -1 || endBonus != -1 || matrixFile) &&
                 (prc = dpx_batch_set_direction_scoring(next.b, zdrop, endBonus, matrixFile ? substScores.data() : nullptr, substAlphabet, substCode)) != DPX_OK)
                 die(matrixFile ? "FAILED TO SET THE SUBSTITUTION MATRIX" : "FAILED TO SET THE EXTENSION MODE", prc);
+        } else if (directionTable) {
+            if ((prc = dpx_batch_set_direction_table(next.b, substScores.data(), substAlphabet, substCode)) != DPX_OK) die("FAILED TO SET THE SUBSTITUTION MATRIX", prc);
         } else {
             if ((zdrop != -1 || endBonus != -1) && (prc = dpx_batch_set_extension(next.b, zdrop, endBonus)) != DPX_OK) die("FAILED TO SET THE EXTENSION MODE", prc);
             if (matrixFile && (prc = dpx_batch_set_substitution(next.b, substScores.data(), substAlphabet, substCode)) != DPX_OK) die("FAILED TO SET THE SUBSTITUTION MATRIX", prc);

@@ -664,6 +664,39 @@ int dpx_batch_set_second_gap(dpx_batch *b, int32_t gapOpen2, int32_t gapExtend2)
  * A refused or failed call changes nothing: dpx_batch_describe is byte-identical before and after, and the batch fills as before. */
 int dpx_batch_set_reversed(dpx_batch *b, const uint8_t *reversed /* numPairs bytes; nonzero = reversed; NULL = none */);
 
+/* ---- substitution-matrix scoring of ANW, ASW and ASG direction batches ----
+ * Protein local alignment under a 20-24 letter matrix, DNA with a negative N and folded lower case, transition / transversion weights, a
+ * read fitted into a reference window under a 5 x 5 matrix: none of them is a banded problem.  This setter gives the three full-matrix
+ * affine algorithms a table in the storage mode that carries it: a DPX_KEEP_DIRECTIONS batch computes in int32 against a 2^28 bound and
+ * its walk and export read only the 4-bit codes and the two bytes of a cell.  A new exported symbol, no ABI bump and no new flag: detect
+ * it by the symbol.
+ *   Definition.  ANW's / ASW's / ASG's block above, word for word, with one change: the diagonal term is
+ *         H[i-1][j-1] + scores[codeOf[r] * alphabet + codeOf[q]]
+ *     for the reference byte r and the query byte q (the row is the reference code; the table need not be symmetric).  params.match /
+ *     params.mismatch are ignored.  Borders, tie order and end-cell rules, ASW's zero floor and "move 0 where H == 0", ASG's first
+ *     maximum of row m with its column-0 border, the empty-sequence results and the walk do not change.
+ *   Text.  The relation line, the CIGAR's '=' / 'X' and the MATCH / MISMATCH enum of dpx_batch_directions stay byte equality, as under
+ *     dpx_batch_set_substitution.
+ *   Arguments.  dpx_batch_set_substitution's: both arrays are copied at the call; scores == NULL clears the table (the other arguments
+ *     are ignored), is legal on every batch and changes nothing where nothing was set.
+ *   Lifecycle.  dpx_batch_set_substitution's: the setting applies to every following fill; a call that changes it invalidates results,
+ *     lines, text and CIGARs of an earlier fill (DPX_ERR_NOT_FILLED until the next fill); setting the same table again invalidates
+ *     nothing; a refused call leaves the previous setting in force and dpx_batch_describe byte-identical.
+ *   DPX_ERR_INVALID      b == NULL; with scores != NULL: alphabet outside 1..32, codeOf == NULL, or a codeOf[x] >= alphabet
+ *   DPX_ERR_UNSUPPORTED  anything but a DPX_ALGO_ANW / DPX_ALGO_ASW / DPX_ALGO_ASG batch created with DPX_KEEP_DIRECTIONS: their matrix
+ *                        and DPX_SCORE_ONLY batches, LNW / LSW direction batches, every banded algorithm in every storage mode (a BANW
+ *                        band-direction batch whose covering band runs k_affine_dir and a BSW / BASW local band-direction batch whose
+ *                        covering band runs k_linear_dir / k_asw_dir included)
+ *   DPX_ERR_RANGE        the create-time range check of a direction batch (bounds against 2^28) fails for a pair with the table's largest
+ *                        entry in place of match and its smallest in place of mismatch
+ * While a table is set dpx_batch_describe keeps kernel=k_affine_dir / k_asw_dir / k_asg_dir and matrix=dir4 (the table is a mode of the
+ * same fill, k_dirtab_fill in the library) and adds ` subst=<alphabet>`.  Every wave keeps the 1280-byte table image in LDS; where the
+ * plan's waves per workgroup no longer fit with it the fill runs one-wave workgroups (waves_per_workgroup says what will launch), and
+ * a one-wave workgroup always fits, so there is no "no room in LDS" refusal.  dpx_batch_set_extension, dpx_batch_set_substitution (with
+ * a table), dpx_batch_set_extension_table and dpx_batch_set_direction_scoring keep refusing these batches.  Repeated fills,
+ * DPX_TIME_FILLS, dpx_batch_fill_timed, a caller's stream, dpx_batch_create_on and packed2 input as for any direction batch. */
+int dpx_batch_set_direction_table(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf /* 256 entries */);
+
 /* Sizes: numPairs, total cells (sum refLen*queryLen, the reference's numCells, c++/parseInput.cpp:100),
  * bytes of HBM the matrices occupy, algorithmic bytes of one fill. */
 int dpx_batch_info(dpx_batch *b, size_t *numPairs, uint64_t *cells, uint64_t *matrixBytes, uint64_t *algorithmicBytes);
