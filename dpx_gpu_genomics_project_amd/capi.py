@@ -40,6 +40,7 @@ ABI_SYMBOLS = (
     "dpx_batch_cigars_begin", "dpx_batch_cigars_end", "dpx_cigar_text", "dpx_batch_set_extension", "dpx_batch_extensions",
     "dpx_batch_set_substitution", "dpx_batch_set_extension_table", "dpx_batch_set_direction_scoring",
     "dpx_batch_set_second_gap", "dpx_batch_set_reversed", "dpx_batch_set_direction_table",
+    "dpx_batch_set_score_table",
 )
 # declared entry points a library may lack and still load (an older build): checked when they are called
 OPTIONAL_SYMBOLS = ("dpx_batch_directions",)
@@ -136,6 +137,7 @@ def load() -> C.CDLL:
     lib.dpx_batch_set_second_gap.argtypes = [vp, C.c_int32, C.c_int32]
     lib.dpx_batch_set_reversed.argtypes = [vp, vp]
     lib.dpx_batch_set_direction_table.argtypes = [vp, vp, C.c_int32, vp]
+    lib.dpx_batch_set_score_table.argtypes = [vp, vp, C.c_int32, vp]
     for name in ABI_SYMBOLS:  # every declared entry point must be exported (the optional ones by libraries that have them)
         if name not in OPTIONAL_SYMBOLS:
             getattr(lib, name)
@@ -329,6 +331,16 @@ class Batch:
             return
         tab, code = _table_arrays(scores, code_of)
         _check(self._lib.dpx_batch_set_direction_table(self._h, tab.ctypes.data, tab.shape[0], code.ctypes.data), "dpx_batch_set_direction_table")
+
+    def set_score_table(self, scores, code_of=None) -> None:
+        """ANW / ASW / ASG batches created with SCORE_ONLY only: score columns by scores[code_of[ref byte], code_of[qry byte]] in the
+        following fills (set_substitution's arrays; the table need not be symmetric).  None clears the table.  Results of an earlier
+        fill are invalid afterwards when the table changed."""
+        if scores is None:
+            _check(self._lib.dpx_batch_set_score_table(self._h, None, 0, None), "dpx_batch_set_score_table")
+            return
+        tab, code = _table_arrays(scores, code_of)
+        _check(self._lib.dpx_batch_set_score_table(self._h, tab.ctypes.data, tab.shape[0], code.ctypes.data), "dpx_batch_set_score_table")
 
     def set_second_gap(self, gap_open2: int, gap_extend2: int) -> None:
         """TWO_PIECE_GAPS batches only: the second gap piece of the following fills; a gap of length k then scores

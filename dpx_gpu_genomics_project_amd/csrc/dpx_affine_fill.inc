@@ -3,7 +3,10 @@
  * the first maximum of row m, column 0 included).  The body sits in each kernel itself rather than in a shared __device__ function:
  * passing the kernel argument block to a function changed the scheduling of the ANW kernel (its gfx950 code differed, and 4000 x 512^2
  * filled 3-8 % slower); included this way the ANW kernels compile to the code they compiled to before ASW existed.
- * In scope: `a` (the kernel's dpx_fill_args), R, STORE, LOCAL and SEMI. */
+ * dpx_scoretab_kernels.hip includes it inside k_scoretab_fill with TABLE = true (score-only batches under dpx_batch_set_score_table): the
+ * diagonal term is tableG[codeOfG[reference byte] * 32 + codeOfG[query byte]], read from the wave's own LDS image.
+ * In scope: `a` (the kernel's dpx_fill_args), R, STORE, LOCAL, SEMI, TABLE and the two global pointers tableG / codeOfG (null constants
+ * where TABLE is false: nothing of the table survives in those kernels). */
     constexpr int MODE = LOCAL ? 1 : (SEMI ? 2 : 0); /* aff_cells: ANW, ASW, ASG */
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
@@ -34,6 +37,13 @@
     const unsigned char *refl = stage_bytes(my + a.ldsRefOff + 64, ref, n, lane, 64) - 64;
     /* row-0 border H[0][j] = o + j*e (AffineNeedlemanWunsch.cpp:50-53); D[0][j] is the virtual DPX_NEG (k == 0 below) */
     for (int x = lane; x <= n + 1; x += 64) { edgeH[x] = (int16_t)((LOCAL || SEMI) ? 0 : o + x * e); edgeD[x] = 0; } /* (ASW / ASG: H[0][j] = 0) */
+    [[maybe_unused]] unsigned char *img = nullptr;
+    [[maybe_unused]] const unsigned char *codeL = nullptr;
+    if constexpr (TABLE) { /* the wave's own table image behind its LDS slice (a.ldsPerWave counts it); the staged reference becomes codes, once */
+        img = my + (a.ldsPerWave - (uint32_t)DPX_SUBST_IMAGE_BYTES);
+        codeL = table_stage(img, tableG, codeOfG, lane);
+        table_translate(const_cast<unsigned char *>(refl) + 64, n, lane, 64, codeL);
+    }
 
     int16_t *Mp = a.mat + pr.matOff;
     const int W = n + 63;
@@ -122,6 +132,10 @@
             const bool laneHasRows = nrows > 0;
             const bool hasNext = (k + 1 < S);
             load_query_rows<R>(st.qc, qry, row0, nrows);
+            if constexpr (TABLE) { /* the LDS addresses of the lane's query codes' columns of the transposed image (table_column), once per stripe (rows past m: some code, their cells are never read back) */
+    #pragma unroll
+                for (int r = 0; r < R; r++) st.qc[r] = table_column(img, codeL, st.qc[r]);
+            }
     #pragma unroll
             for (int r = 0; r < R; r++) {
                 st.Hl[r] = LOCAL ? 0 : o + (row0 + 1 + r) * e; /* H[i][0] = o + i*e (:43-46); ASW: 0 */
@@ -143,7 +157,7 @@
                 rcN = rp[t + 1];                                                                                          \
                 eHN = edgeH[min(t + 2, n + 1)];                                                                           \
                 eDN = k == 0 ? DPX_NEG : (int)edgeD[min(t + 2, n + 1)];                                                   \
-                aff_step<R, MODE, STORE, MASKED_, WHOLE_>(st, t, lane, n, HASROWS_, match, mismatch, oe, e, eH, eD, rc, edgeH, edgeD, \
+                aff_step<R, MODE, STORE, MASKED_, WHOLE_, TABLE>(st, t, lane, n, HASROWS_, match, mismatch, oe, e, eH, eD, rc, edgeH, edgeD, \
                                             hasNext, tile + (size_t)t * cs, storeLanes, a.rampLines, rsel);               \
             }
             const bool fast = (base + 64 * R <= m) && (n >= 64);

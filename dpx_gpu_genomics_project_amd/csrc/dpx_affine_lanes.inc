@@ -1,6 +1,8 @@
 /* dpx_affine_lanes.inc -- body of the lane-packed affine-gap kernels, included by dpx_affine_kernels.hip inside k_affine_lanes (ANW, LOCAL = false)
- * k_asw_lanes (ASW, LOCAL = true) and k_asg_lanes (ASG, SEMI = true), for the reason given in dpx_affine_fill.inc.  In scope: `a`, R, STORE,
- * LOCAL and SEMI. */
+ * k_asw_lanes (ASW, LOCAL = true) and k_asg_lanes (ASG, SEMI = true), for the reason given in dpx_affine_fill.inc, and by
+ * dpx_scoretab_kernels.hip inside k_scoretab_lanes (TABLE = true: the diagonal term from the wave's LDS table image, as in
+ * dpx_affine_fill.inc; the image sits behind the wave's reference area, a.ldsPerWave counts it).  In scope: `a`, R, STORE, LOCAL, SEMI,
+ * TABLE and the global pointers tableG / codeOfG (null constants where TABLE is false). */
     constexpr int MODE = LOCAL ? 1 : (SEMI ? 2 : 0); /* aff_cells_g: ANW, ASW, ASG */
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     static_assert(R == 8, "one 8-row block per lane");
@@ -17,18 +19,30 @@
     const dpx_pair_dev pr = a.pairs[p];
     const int n = has ? pr.n : 0, m = has ? pr.m : 0;
     const int o = a.gapOpen, e = a.gapExtend, oe = o + e;
-    const int matchG = a.match - oe, mismatchG = a.mismatch - oe;
+    const int matchG = (TABLE ? 0 : a.match) - oe, mismatchG = a.mismatch - oe; /* (TABLE: matchG is the frame's -(o+e) alone, aff_cells_g) */
     const unsigned char *ref = reinterpret_cast<const unsigned char *>(a.seq + pr.refIdx);
     const unsigned char *qry = reinterpret_cast<const unsigned char *>(a.seq + pr.qryIdx);
 
     unsigned char *tileL = smem + (size_t)wv * a.ldsPerWave;
     unsigned char *refl = tileL + (STORE ? kStageBytes : kLaneScratch) + sl.refOff;
     const unsigned char *refs = stage_bytes(refl, ref, n, l, max(sl.num, 1));
+    [[maybe_unused]] unsigned char *img = nullptr;
+    [[maybe_unused]] const unsigned char *codeL = nullptr;
+    if constexpr (TABLE) { /* the wave's table image behind its reference area (a.ldsPerWave counts it); every slot's staged reference becomes
+                            * codes, once, by the slot's own lanes */
+        img = tileL + (a.ldsPerWave - (uint32_t)DPX_SUBST_IMAGE_BYTES);
+        codeL = table_stage(img, tableG, codeOfG, lane);
+        table_translate(const_cast<unsigned char *>(refs), n, l, max(sl.num, 1), codeL);
+    }
 
     const int row0 = l * R;
     const int nrows = min(max(m - row0, 0), R);
     AffStateG<R> st;
     load_query_rows<R>(st.qc, qry, row0, nrows);
+    if constexpr (TABLE) { /* the LDS addresses of the lane's query codes' columns of the transposed image (table_column), once (rows past m: some code, their cells are never read back) */
+#pragma unroll
+        for (int r = 0; r < R; r++) st.qc[r] = table_column(img, codeL, st.qc[r]);
+    }
 #pragma unroll
     for (int r = 0; r < R; r++) {
         st.Hoe[r] = (LOCAL ? 0 : o + (row0 + 1 + r) * e) + oe; /* H[i][0] = o + i*e (AffineNeedlemanWunsch.cpp:43-46); ASW: 0 */
@@ -91,7 +105,7 @@
         if constexpr (!LOCAL && !SEMI) bordOe += e;
         if ((unsigned)tms < nEff) {
             int Hv[R], Iv[R], Dv[R];
-            aff_cells_g<R, MODE>(st, upHoe, upDe, rc, matchG, mismatchG, oe, e, Hv, Iv, Dv, 0xFFFEu - (unsigned)tms, rsel);
+            aff_cells_g<R, MODE, TABLE>(st, upHoe, upDe, rc, matchG, mismatchG, oe, e, Hv, Iv, Dv, 0xFFFEu - (unsigned)tms, rsel);
             if constexpr (STORE) {
                 *reinterpret_cast<u32x4 *>(putPtr + 0 * kPlane + (K << 4)) = pack8(Hv);
                 *reinterpret_cast<u32x4 *>(putPtr + 1 * kPlane + (K << 4)) = pack8(Iv);

@@ -510,11 +510,12 @@ struct dpx_batch : dpx_plan {
     int32_t *dExt = nullptr;   /* device: dpx_extension[numPairs] */
     size_t dExtCap = 0;
     /* substitution table (dpx_batch_set_substitution): while substAlphabet > 0 the fills run k_subst_fill and the walks k_subst_traceback*
-     * (band-direction batches: k_bdx_fill; ANW / ASW / ASG direction batches, dpx_batch_set_direction_table: k_dirtab_fill, the walk stays) */
+     * (band-direction batches: k_bdx_fill; ANW / ASW / ASG direction batches, dpx_batch_set_direction_table: k_dirtab_fill, the walk stays;
+     * their score-only batches, dpx_batch_set_score_table: k_scoretab_fill / k_scoretab_lanes) */
     int substAlphabet = 0;
     unsigned char *dSubst = nullptr; /* device: the table at row stride 32 (DPX_SUBST_TABLE_BYTES), then codeOf[256] */
     size_t dSubstCap = 0;
-    std::vector<unsigned char> bdxImage; /* dpx_batch_set_direction_scoring / _set_direction_table: the image dSubst holds, to tell a changed table from the same one */
+    std::vector<unsigned char> bdxImage; /* dpx_batch_set_direction_scoring / _set_direction_table / _set_score_table: the image dSubst holds, to tell a changed table from the same one */
     /* orientation (dpx_batch_set_reversed): while revCount > 0 dSeq points at dRev, the setter's own allocation -- [the arena's sequence
      * bytes][reversed copies of the flagged pairs' strings][the kernel's job list][the flagged pairs' numbers] -- and the flagged pairs'
      * indices in `pairs` / dPairs at the copies.  The fills, walks and exports know nothing of it. */
@@ -1079,7 +1080,13 @@ static size_t subst_lds_bytes(const dpx_batch *b) { return b->ldsBytes + (size_t
 static hipError_t launch_main(dpx_batch *b, const dpx_route &r, hipStream_t s) { /* the one-wave-per-pair kernel of the batch's algorithm */
     switch (r.main) {
     case DPX_MAIN_NONE: return hipSuccess;
-    case DPX_MAIN_FILL: return dpx_launch_fill(b->args, b->kernelAlgo, b->R, b->store, b->ldsBytes, s);
+    case DPX_MAIN_FILL:
+        if (r.scoreTable) { /* (dpx_batch_set_score_table: every wave's LDS slice grows by the image; the workgroup may shrink to one wave) */
+            dpx_scoretab_args ta = {b->args, reinterpret_cast<const int8_t *>(b->dSubst), b->dSubst + DPX_SUBST_TABLE_BYTES};
+            ta.f.ldsPerWave = (uint32_t)dpx_plan_scoretab_lds(*b); ta.f.wavesPerBlock = dpx_plan_scoretab_waves(*b);
+            return dpx_launch_scoretab_fill(ta, b->kernelAlgo, b->R, s);
+        }
+        return dpx_launch_fill(b->args, b->kernelAlgo, b->R, b->store, b->ldsBytes, s);
     case DPX_MAIN_BASW: return dpx_launch_basw_fill(b->args, b->R, b->store, b->ldsBytes, s);
     case DPX_MAIN_BANW: return dpx_launch_banw_fill(b->args, b->R, b->store, b->ldsBytes, s);
     case DPX_MAIN_BAXT: return dpx_launch_baxt_fill(b->args, b->R, b->store, b->ldsBytes, s);
@@ -1138,7 +1145,15 @@ static hipError_t launch_all(dpx_batch *b, const dpx_route &r, hipStream_t s) {
     case DPX_SECOND_NONE: break;
     case DPX_SECOND_PACKED: e = dpx_launch_fill_packed(b->pkArgs, b->kernelAlgo, b->R, b->pkLdsBytes, s); break;
     case DPX_SECOND_BANDED_PACKED: e = dpx_launch_banded_packed(b->pkArgs, b->R, b->pkLdsBytes, s); break;
-    case DPX_SECOND_LANES: e = dpx_launch_fill_lanes(b->pkArgs, b->kernelAlgo, b->R, b->store, b->pkLdsBytes, s); break;
+    case DPX_SECOND_LANES:
+        if (r.scoreTable) { /* (the image behind the wave's reference area) */
+            dpx_scoretab_args ta = {b->pkArgs, reinterpret_cast<const int8_t *>(b->dSubst), b->dSubst + DPX_SUBST_TABLE_BYTES};
+            ta.f.ldsPerWave = (uint32_t)dpx_plan_scoretab_lanes_lds(*b);
+            e = dpx_launch_scoretab_lanes(ta, b->kernelAlgo, b->R, s);
+            break;
+        }
+        e = dpx_launch_fill_lanes(b->pkArgs, b->kernelAlgo, b->R, b->store, b->pkLdsBytes, s);
+        break;
     case DPX_SECOND_LANES_PK: e = dpx_launch_fill_lanes_packed(b->pkArgs, b->kernelAlgo, b->pkLdsBytes, s); break;
     }
     if (forked) {
@@ -1498,25 +1513,26 @@ int dpx_batch_set_direction_scoring(dpx_batch *b, int32_t zdrop, int32_t endBonu
     return DPX_OK;
 }
 
-/* the table of an ANW / ASW / ASG direction batch (k_dirtab_fill); every check comes before the first change */
-int dpx_batch_set_direction_table(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf) {
-    if (!b) return DPX_ERR_INVALID;
-    if (!scores) { /* clear: legal on every batch; the batch runs its plain kernel again */
-        if (b->substAlphabet) invalidate_fill(b);
-        b->substAlphabet = 0;
-        b->bdxImage.clear();
-        return DPX_OK;
-    }
-    if (alphabet < 1 || alphabet > 32 || !codeOf) return DPX_ERR_INVALID;
-    for (int x = 0; x < 256; x++) if ((int)codeOf[x] >= alphabet) return DPX_ERR_INVALID;
-    /* the batch's own algorithm, not the kernel's: a covering BANW / BASW band that runs k_affine_dir / k_asw_dir is not admitted */
-    const bool three = b->prm.algo == DPX_ALGO_ANW || b->prm.algo == DPX_ALGO_ASW || b->prm.algo == DPX_ALGO_ASG;
-    if (!three || !b->dirs || !(b->flags & DPX_KEEP_DIRECTIONS)) return DPX_ERR_UNSUPPORTED;
-    /* fits_dir with the largest entry in place of match and the smallest in place of mismatch, over every pair */
+/* ---- what dpx_batch_set_direction_table and dpx_batch_set_score_table share ----
+ * the range check of the batch's storage mode (`fits`: fits_dir or fits_int16) with the table's largest entry in place of match and its
+ * smallest in place of mismatch, over every pair */
+static bool table_in_range(const dpx_batch *b, const int8_t *scores, int32_t alphabet, bool (*fits)(const dpx_params &, long long, long long)) {
     dpx_params q = b->prm;
     q.match = -128; q.mismatch = 127;
     for (int k = 0; k < alphabet * alphabet; k++) { q.match = std::max<int32_t>(q.match, scores[k]); q.mismatch = std::min<int32_t>(q.mismatch, scores[k]); }
-    for (const dpx_pair_dev &pd : b->pairs) if (!fits_dir(q, pd.m, pd.n)) return DPX_ERR_RANGE;
+    for (const dpx_pair_dev &pd : b->pairs) if (!fits(q, pd.m, pd.n)) return false;
+    return true;
+}
+/* scores == NULL: whatever table the batch holds goes, through whichever setter it came (legal on every batch) */
+static int clear_table_image(dpx_batch *b) {
+    if (b->substAlphabet) invalidate_fill(b);
+    b->substAlphabet = 0;
+    b->bdxImage.clear();
+    return DPX_OK;
+}
+/* the checked table becomes the batch's: the image of dpx_kernels.h (rows of 32, the map behind them), kept on the host too, to tell a
+ * changed table from the same one (which invalidates nothing) */
+static int set_table_image(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf) {
     unsigned char image[DPX_SUBST_IMAGE_BYTES];
     memset(image, 0, sizeof image);
     for (int r = 0; r < alphabet; r++) memcpy(image + r * 32, scores + r * alphabet, (size_t)alphabet);
@@ -1533,6 +1549,39 @@ int dpx_batch_set_direction_table(dpx_batch *b, const int8_t *scores, int32_t al
     b->substAlphabet = alphabet;
     invalidate_fill(b);
     return DPX_OK;
+}
+
+/* the table of an ANW / ASW / ASG direction batch (k_dirtab_fill); every check comes before the first change */
+int dpx_batch_set_direction_table(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf) {
+    if (!b) return DPX_ERR_INVALID;
+    if (!scores) { /* clear: legal on every batch; the batch runs its plain kernel again */
+        return clear_table_image(b);
+    }
+    if (alphabet < 1 || alphabet > 32 || !codeOf) return DPX_ERR_INVALID;
+    for (int x = 0; x < 256; x++) if ((int)codeOf[x] >= alphabet) return DPX_ERR_INVALID;
+    /* the batch's own algorithm, not the kernel's: a covering BANW / BASW band that runs k_affine_dir / k_asw_dir is not admitted */
+    const bool three = b->prm.algo == DPX_ALGO_ANW || b->prm.algo == DPX_ALGO_ASW || b->prm.algo == DPX_ALGO_ASG;
+    if (!three || !b->dirs || !(b->flags & DPX_KEEP_DIRECTIONS)) return DPX_ERR_UNSUPPORTED;
+    /* fits_dir with the largest entry in place of match and the smallest in place of mismatch, over every pair */
+    if (!table_in_range(b, scores, alphabet, fits_dir)) return DPX_ERR_RANGE;
+    return set_table_image(b, scores, alphabet, codeOf);
+}
+
+/* the table of an ANW / ASW / ASG score-only batch (k_scoretab_fill / k_scoretab_lanes); every check comes before the first change */
+int dpx_batch_set_score_table(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf) {
+    if (!b) return DPX_ERR_INVALID;
+    if (!scores) { /* clear: legal on every batch; the batch runs its plain kernels again */
+        return clear_table_image(b);
+    }
+    if (alphabet < 1 || alphabet > 32 || !codeOf) return DPX_ERR_INVALID;
+    for (int x = 0; x < 256; x++) if ((int)codeOf[x] >= alphabet) return DPX_ERR_INVALID;
+    /* the batch's own algorithm, not the kernel's: a covering BANW / BASW band that runs the ANW / ASW kernels is not admitted */
+    const bool three = b->prm.algo == DPX_ALGO_ANW || b->prm.algo == DPX_ALGO_ASW || b->prm.algo == DPX_ALGO_ASG;
+    if (!three || b->store || b->dirs || !(b->flags & DPX_SCORE_ONLY)) return DPX_ERR_UNSUPPORTED;
+    if (!dpx_plan_scoretab_fits(*b, t_err)) return DPX_ERR_UNSUPPORTED;
+    /* fits_int16 with the largest entry in place of match and the smallest in place of mismatch, over every pair */
+    if (!table_in_range(b, scores, alphabet, fits_int16)) return DPX_ERR_RANGE;
+    return set_table_image(b, scores, alphabet, codeOf);
 }
 
 /* ---- orientation: dpx_batch_set_reversed ----

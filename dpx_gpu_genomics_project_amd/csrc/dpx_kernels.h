@@ -124,6 +124,18 @@ typedef struct dpx_bdx_args {
     int32_t *ext;
 } dpx_bdx_args;
 hipError_t dpx_launch_bdx_fill(const dpx_bdx_args &a, int C, bool ext, hipStream_t stream);
+/* ANW / ASW / ASG score-only batches under a substitution table (dpx_scoretab_kernels.hip, dpx_batch_set_score_table): k_affine_fill's /
+ * k_asw_fill's / k_asg_fill's cells and results without stores (k_scoretab_fill) and the lane-packed kernels' (k_scoretab_lanes, R = 8)
+ * with the diagonal term H + table[(codeOf[ref byte] << 5) + codeOf[qry byte]] (`table` / `codeOf` as in dpx_subst_args); f.match /
+ * f.mismatch are not read.  f.ldsPerWave includes DPX_SUBST_IMAGE_BYTES behind the wave's slice (the one-wave kernel) or behind its
+ * reference area (the lane-packed one), and each launch asks for f.ldsPerWave * f.wavesPerBlock bytes of LDS. */
+typedef struct dpx_scoretab_args {
+    dpx_fill_args f;
+    const int8_t *table;
+    const uint8_t *codeOf;
+} dpx_scoretab_args;
+hipError_t dpx_launch_scoretab_fill(const dpx_scoretab_args &a, int algo, int R, hipStream_t stream);
+hipError_t dpx_launch_scoretab_lanes(const dpx_scoretab_args &a, int algo, int R, hipStream_t stream);
 hipError_t dpx_launch_unpack2(const uint32_t *packed, uint32_t alphabet, char *out, size_t numDwords, hipStream_t stream);
 hipError_t dpx_launch_prim_eval(const int32_t *op, const uint32_t *a, const uint32_t *b, const uint32_t *c, size_t count,
                                 uint32_t *res, uint32_t *pred, hipStream_t stream);

@@ -701,6 +701,12 @@ dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus,
     } else if (p.bandDirs) { /* (a mode comes through dpx_batch_set_direction_scoring only; extension mode is BAXT's) */
         const bool bdx = extension || substAlphabet;
         r.main = p.twoPiece ? DPX_MAIN_BD2 : bdx ? DPX_MAIN_BDX : DPX_MAIN_BDIR; r.kernel = p.twoPiece ? DPX_K_BD2_FILL : bdx ? DPX_K_BDX_FILL : DPX_K_BDIR_FILL;
+    } else if (substAlphabet && family != 0) { /* (set only by dpx_batch_set_score_table, on a DPX_SCORE_ONLY batch of the three: the launches of the plain
+                                                * batch, each through its k_scoretab twin; the kernel= names stay) */
+        r.scoreTable = true;
+        r.second = p.lanePacked ? DPX_SECOND_LANES : DPX_SECOND_NONE;
+        if (!r.second || p.args.numPairs > 0) r.main = DPX_MAIN_FILL;
+        r.kernel = p.lanePacked ? lanes[family] : fill[family];
     } else if (substAlphabet) { /* (set only on batches whose kernel is BANW's or BAXT's; with extension mode: dpx_batch_set_extension_table) */
         r.main = extension ? DPX_MAIN_ZSUB : DPX_MAIN_SUBST; r.kernel = extension ? DPX_K_ZSUB_FILL : DPX_K_SUBST_FILL;
     } else if (algo == DPX_ALGO_BAXT) {
@@ -719,7 +725,7 @@ dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus,
                    : p.packed ? DPX_K_LINEAR_FILL_PK : p.lanesPk ? DPX_K_LINEAR_LANES_PK : p.lanePacked ? DPX_K_LINEAR_LANES : p.split ? DPX_K_LINEAR_SPLIT : DPX_K_LINEAR_FILL;
     }
     r.extRecords = r.main == DPX_MAIN_ZEXT || r.main == DPX_MAIN_ZSUB || ((r.main == DPX_MAIN_BDX || r.main == DPX_MAIN_BD2) && extension);
-    r.walk = p.bandLocal ? DPX_WALK_BDL : p.twoPiece ? DPX_WALK_BD2 : p.bandDirs ? DPX_WALK_BDIR : (substAlphabet && !p.dirs) ? DPX_WALK_SUBST : algo == DPX_ALGO_BASW ? DPX_WALK_BASW : is_banw_layout(algo) ? DPX_WALK_BANW
+    r.walk = p.bandLocal ? DPX_WALK_BDL : p.twoPiece ? DPX_WALK_BD2 : p.bandDirs ? DPX_WALK_BDIR : (substAlphabet && !p.dirs && !r.scoreTable) ? DPX_WALK_SUBST : algo == DPX_ALGO_BASW ? DPX_WALK_BASW : is_banw_layout(algo) ? DPX_WALK_BANW
              : p.dirs ? DPX_WALK_DIR : DPX_WALK_PLAIN;
     r.walkMode = (r.walk == DPX_WALK_BDL || r.walk == DPX_WALK_BD2 || r.walk == DPX_WALK_BDIR || r.walk == DPX_WALK_DIR) ? 0 : walk_mode(p, tbWalk); /* (one walk: DPX_TB_WALK has no effect) */
     r.exportKind = is_banw_layout(algo) /* (BAXT stores what BANW stores) */ ? DPX_EXPORT_BANW : algo == DPX_ALGO_BASW ? DPX_EXPORT_BASW : DPX_EXPORT_PLAIN;
@@ -736,6 +742,28 @@ unsigned dpx_plan_bdx_waves(const dpx_plan &p, bool table) {
 unsigned dpx_plan_dirtab_waves(const dpx_plan &p) {
     const size_t perWave = (p.dirScratch ? 0 : (size_t)p.dirArgs.ldsPerWave) + DPX_SUBST_IMAGE_BYTES;
     return perWave * p.dirArgs.wavesPerBlock <= kLdsMax ? p.dirArgs.wavesPerBlock : 1u;
+}
+
+unsigned dpx_plan_scoretab_waves(const dpx_plan &p) {
+    const size_t perWave = dpx_plan_scoretab_lds(p);
+    if (perWave > kLdsMax) return 0u;
+    return perWave * p.args.wavesPerBlock <= kLdsMax ? p.args.wavesPerBlock : 1u;
+}
+size_t dpx_plan_scoretab_lds(const dpx_plan &p) { return (size_t)p.args.ldsPerWave + DPX_SUBST_IMAGE_BYTES; }
+size_t dpx_plan_scoretab_lanes_lds(const dpx_plan &p) { return p.lanePacked ? (size_t)p.pkArgs.ldsPerWave + DPX_SUBST_IMAGE_BYTES : 0; }
+bool dpx_plan_scoretab_fits(const dpx_plan &p, std::string &err) {
+    char text[160];
+    if ((!p.lanePacked || p.args.numPairs > 0) && dpx_plan_scoretab_waves(p) == 0u) {
+        snprintf(text, sizeof text, "score table: one wave's LDS slice with the table image (%zu bytes) exceeds a workgroup's %zu", dpx_plan_scoretab_lds(p), kLdsMax);
+        err = text;
+        return false;
+    }
+    if (dpx_plan_scoretab_lanes_lds(p) * (DPX_ALANES_THREADS / 64) > kLdsMax) {
+        snprintf(text, sizeof text, "score table: a lane-packed wave's LDS with the table image (%zu bytes) exceeds a workgroup's %zu", dpx_plan_scoretab_lanes_lds(p), kLdsMax);
+        err = text;
+        return false;
+    }
+    return true;
 }
 
 const char *dpx_route_kernel_name(dpx_fill_kernel k) {
@@ -774,7 +802,7 @@ int dpx_plan_describe(const dpx_plan &b, int tbWalk, int zdrop, int endBonus, in
     int len = snprintf(buf, cap, "algo=%s kernel_algo=%s kernel=%s dtype=%s rows_per_lane=%d store=%d couples=%zu lane_pairs=%zu waves=%zu singles=%zu row_tags=%d seq_input=%s waves_per_workgroup=%u",
                        name(b.prm.algo), name(b.kernelAlgo), dpx_route_kernel_name(r.kernel), (b.packed || b.lanesPk) ? "int16" : "int32", b.R, b.store ? 1 : 0, b.nCouples, b.nLanePairs,
                        b.nWaves, b.nSingles, (int)b.pkArgs.rowTags, b.packed2 ? "packed2" : "bytes",
-                       b.dirs ? (r.dirTable ? dpx_plan_dirtab_waves(b) : b.dirArgs.wavesPerBlock) : (b.packed || b.lanePacked) ? b.pkArgs.wavesPerBlock : b.split ? (unsigned)b.splitWaves : b.bandDirs ? dpx_plan_bdx_waves(b, substAlphabet != 0) : b.args.wavesPerBlock);
+                       b.dirs ? (r.dirTable ? dpx_plan_dirtab_waves(b) : b.dirArgs.wavesPerBlock) : (b.packed || b.lanePacked) ? b.pkArgs.wavesPerBlock : b.split ? (unsigned)b.splitWaves : b.bandDirs ? dpx_plan_bdx_waves(b, substAlphabet != 0) : r.scoreTable ? dpx_plan_scoretab_waves(b) : b.args.wavesPerBlock);
     if ((is_banded_affine(b.kernelAlgo) || b.bandLocal) && len > 0 && (size_t)len < cap) /* which walk the batch's traceback takes */
         len += snprintf(buf + len, cap - (size_t)len, " traceback=%s", dpx_route_walk_name(r.walk, r.walkMode));
     if (extension && len > 0 && (size_t)len < cap)

@@ -103,6 +103,8 @@ struct dpx_route {
      * kernel of the pairs it leaves over (if any) */
     bool dirs, split;
     bool dirTable;   /* ... a direction batch of ANW / ASW / ASG under a table (dpx_batch_set_direction_table): k_dirtab_fill, a mode of the same three kernel= names */
+    bool scoreTable; /* ... a DPX_SCORE_ONLY batch of ANW / ASW / ASG under a table (dpx_batch_set_score_table): main and second are the plain batch's, each launched
+                        through its table twin (k_scoretab_fill / k_scoretab_lanes); a mode of the same six kernel= names */
     dpx_second_launch second;
     dpx_main_launch main;
     bool ext;        /* the band kernel (BDIR, SUBST) runs BAXT's end-cell rule, not BANW's */
@@ -114,7 +116,8 @@ struct dpx_route {
 /* What a batch can change after its creation comes as arguments: the traceback walk knob, BAXT's extension mode (-1, -1: off) and the
  * substitution alphabet (0: none).  On a bandDirs plan either of the two (dpx_batch_set_direction_scoring) turns k_bdir_fill into
  * k_bdx_fill; the walk stays k_bdir_traceback.  On a dirs plan of ANW / ASW / ASG the alphabet
- * (dpx_batch_set_direction_table) sets dirTable and nothing else.  A twoPiece plan runs k_bd2_fill and k_bd2_traceback in every mode; its second piece is
+ * (dpx_batch_set_direction_table) sets dirTable and nothing else; on a score-only plan of the three (dpx_batch_set_score_table) it sets
+ * scoreTable and nothing else.  A twoPiece plan runs k_bd2_fill and k_bd2_traceback in every mode; its second piece is
  * the plan's own (the batch IS the plan), so the signatures here do not know it. */
 dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus, int substAlphabet);
 /* Waves per workgroup of a bandDirs plan's fill: the plan's own without a table; with one (DPX_SUBST_IMAGE_BYTES more per wave) the
@@ -127,6 +130,16 @@ unsigned dpx_plan_bdx_waves(const dpx_plan &p, bool table);
  * KiB; edge rows in the scratch: the image alone, and the plan's own is 1), so this setter has no "no room in LDS" refusal.  A pure
  * function of the plan, which is not changed. */
 unsigned dpx_plan_dirtab_waves(const dpx_plan &p);
+/* A score-only plan of ANW / ASW / ASG under a table (dpx_batch_set_score_table).  _lds: one wave's slice of the one-wave-per-pair kernel
+ * with the image behind it; _lanes_lds: the lane-packed kernel's per wave (its workgroups are one wave), 0 when the plan is not
+ * lane-packed.  _waves: waves per workgroup of the one-wave-per-pair fill -- the plan's own when that many slices with their images fit
+ * one workgroup's LDS, else 1, and 0 when not even one fits.  _fits: every launch of the plan finds room (the setter refuses otherwise,
+ * with `err` for dpx_last_error()).  Pure functions of the plan, which is not changed.  launch_scalars admits a plan only when four plain
+ * slices of its longest reference fit one workgroup (lane-packed plans included), so a plan that dpx_plan_batch made always fits: the
+ * 0 and the refusal guard against a planner that one day admits longer references (tests/scoretab_fits_main.cpp drives them directly). */
+size_t dpx_plan_scoretab_lds(const dpx_plan &p), dpx_plan_scoretab_lanes_lds(const dpx_plan &p);
+unsigned dpx_plan_scoretab_waves(const dpx_plan &p);
+bool dpx_plan_scoretab_fits(const dpx_plan &p, std::string &err);
 const char *dpx_route_kernel_name(dpx_fill_kernel k);
 const char *dpx_route_walk_name(dpx_walk_family walk, int walkMode);
 

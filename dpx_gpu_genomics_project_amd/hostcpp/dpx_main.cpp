@@ -23,6 +23,11 @@
 // dpx_batch_set_direction_scoring (k_bdx_fill) and print what the run without -directions prints.
 // -directions with -algo ANW|ASW|ASG takes -matrix too: the table goes through dpx_batch_set_direction_table (k_dirtab_fill: int32 scores
 // against 2^28, so a protein matrix with entries up to 127 runs on long pairs), and the text and CIGARs stay byte equality.
+// -scores (any -algo): score-only batches (DPX_SCORE_ONLY: no matrix pool, no traceback); one line per pair, "<number> | <score> | <endRow>
+// <endCol>", formatted on the host from dpx_batch_results.  With -algo ANW|ASW|ASG it takes -matrix FILE: the table goes through
+// dpx_batch_set_score_table (k_scoretab_fill / k_scoretab_lanes) -- the scoring pass of a database search.  Not with -directions, -cigar,
+// -zdrop, -endbonus, -open2 / -extend2 or -reverse, and for the other algorithms not with -matrix.  Without -batch N a -scores run takes
+// batches of 20000 pairs, the cap of the budgeted batches (there is no matrix pool to size them by).
 // -open2 O2 -extend2 E2 (both or neither; only with -directions and -algo BANW|BAXT): two-piece affine gaps, a gap of length k scores
 // max(open + k * extend, O2 + k * E2) (DPX_TWO_PIECE_GAPS and dpx_batch_set_second_gap, k_bd2_fill; bands up to 256).  They combine with
 // -zdrop / -endbonus / -matrix through dpx_batch_set_direction_scoring.
@@ -136,6 +141,7 @@ static void usage() {
                     "[-zdrop <Z>] [-endbonus <E>] (BAXT only) [-matrix <file>] (BANW / BAXT, not with -zdrop / -endbonus; ANW / ASW / ASG only with -directions) "
                     "[-directions] (direction codes instead of score matrices; -algo BSW|BASW -directions: one code per in-band cell, long pairs run; BANW / BAXT: with -zdrop / -endbonus / -matrix too; -algo ANW|ASW|ASG -directions -matrix <file>: full-matrix affine alignment under a substitution matrix) "
                     "[-open2 <O2> -extend2 <E2>] (two-piece gaps: both together, only with -directions and -algo BANW|BAXT) "
+                    "[-scores] (score-only batches: one line '<number> | <score> | <endRow> <endCol>' per pair; not with -directions / -cigar / -zdrop / -endbonus / -open2 / -extend2 / -reverse; -matrix <file> with it only for -algo ANW|ASW|ASG; batches of 20000 pairs unless -batch says otherwise) "
                     "[-reverse] (align every pair right to left on the device, output in the file's orientation; only with -algo BANW|BAXT)\n");
     exit(EXIT_FAILURE);
 }
@@ -155,6 +161,7 @@ int main(int argc, char *argv[]) {
     int zdrop = -1, endBonus = -1; // -zdrop / -endbonus: BAXT's extension mode (dpx_batch_set_extension) on every batch; -1 = off
     bool haveOpen2 = false, haveExtend2 = false; // -open2 / -extend2: the second gap piece (dpx_batch_set_second_gap) on every batch
     int gapOpen2 = 0, gapExtend2 = 0;
+    bool scoresOnly = false; // -scores: score-only batches (DPX_SCORE_ONLY), one "<number> | <score> | <endRow> <endCol>" line per pair from dpx_batch_results
     bool reverse = false;    // -reverse: every pair of every batch is reversed on the device (dpx_batch_set_reversed)
     const char *matrixFile = nullptr; // -matrix: a substitution table (dpx_batch_set_substitution) on every batch
     int inflight = 3;      // batches on the device at a time (= matrix pools reserved)
@@ -188,6 +195,7 @@ int main(int argc, char *argv[]) {
         else if (!strcmp(argv[i], "-open2")) { gapOpen2 = atoi(next("-open2")); haveOpen2 = true; }
         else if (!strcmp(argv[i], "-extend2")) { gapExtend2 = atoi(next("-extend2")); haveExtend2 = true; }
         else if (!strcmp(argv[i], "-reverse")) reverse = true;
+        else if (!strcmp(argv[i], "-scores")) scoresOnly = true;
         else if (!strcmp(argv[i], "-producer")) producerFlag = atoi(next("-producer"));
         else if (!strcmp(argv[i], "-inflight")) inflight = atoi(next("-inflight"));
         else if (!strcmp(argv[i], "-tune")) tuneFlag = atoi(next("-tune"));
@@ -206,13 +214,17 @@ int main(int argc, char *argv[]) {
     const bool twoPiece = haveOpen2 || haveExtend2;
     if (twoPiece && (!(haveOpen2 && haveExtend2) || !directions || (algo != DPX_ALGO_BANW && algo != DPX_ALGO_BAXT))) usage();
     if (reverse && algo != DPX_ALGO_BANW && algo != DPX_ALGO_BAXT) usage();
+    if (scoresOnly && (directions || cigar || zdrop != -1 || endBonus != -1 || twoPiece || reverse)) usage();
     std::vector<int8_t> substScores;
     int substAlphabet = 0;
     uint8_t substCode[256];
     // -matrix on a direction batch of the three full-matrix affine algorithms (dpx_batch_set_direction_table)
     const bool directionTable = matrixFile && directions && (algo == DPX_ALGO_ANW || algo == DPX_ALGO_ASW || algo == DPX_ALGO_ASG);
+    // -matrix on a score-only batch of the same three (dpx_batch_set_score_table); the other algorithms have no score-only table kernel
+    const bool scoreTable = matrixFile && scoresOnly && (algo == DPX_ALGO_ANW || algo == DPX_ALGO_ASW || algo == DPX_ALGO_ASG);
     if (matrixFile) {
-        if (((algo != DPX_ALGO_BANW && algo != DPX_ALGO_BAXT) && !directionTable) || zdrop != -1 || endBonus != -1) usage();
+        if (scoresOnly && !scoreTable) usage();
+        if (((algo != DPX_ALGO_BANW && algo != DPX_ALGO_BAXT) && !directionTable && !scoreTable) || zdrop != -1 || endBonus != -1) usage();
         std::string why;
         if (!read_matrix(matrixFile, substScores, substAlphabet, substCode, why)) {
             fprintf(stderr, "-matrix %s: %s\n", matrixFile, why.c_str());
@@ -241,7 +253,8 @@ int main(int argc, char *argv[]) {
     const size_t poolBudget = (size_t)(poolGb * (double)(1ull << 30)) * (threePlanes && !directions ? 3 : 1);
     std::thread reserve;
     // (and pinned text buffers: one being printed, one per batch in flight, two spare)
-    const bool budgetedBatches = batchSize == 0;
+    const bool budgetedBatches = batchSize == 0 && !scoresOnly; // (-scores: the batches have no pool and no text)
+    if (batchSize == 0 && scoresOnly) batchSize = 20000; // no pool to budget against: the cap the budgeted batches have below (enough waves for the chip, small enough to pipeline)
     if (budgetedBatches) reserve = std::thread([poolBudget, print, inflight]() { (void)dpx_pool_reserve(poolBudget, inflight); if (print) (void)dpx_text_reserve((size_t)16 << 20, inflight + 3); });
 
     printf("Parsing input file: %s\n", pairFileName);
@@ -318,7 +331,13 @@ int main(int argc, char *argv[]) {
         char *text = nullptr;
         size_t bytes = 0;
         std::string lines; // -cigar: the batch's lines, formatted here while the batch (which owns the records and ops) is alive
-        if (print && cigar) {
+        if (print && scoresOnly) { // no device text: the three result arrays, formatted here
+            std::vector<int32_t> scores(f.count), endRow(f.count), endCol(f.count);
+            if ((rc = dpx_batch_results(f.b, scores.data(), endRow.data(), endCol.data())) != DPX_OK) die("RESULTS FAILED", rc);
+            char line[96];
+            for (size_t k = 0; k < f.count; k++)
+                lines.append(line, (size_t)snprintf(line, sizeof line, "%zu | %d | %d %d\n", shardFirst + f.first + k, scores[k], endRow[k], endCol[k]));
+        } else if (print && cigar) {
             const dpx_alignment *recs = nullptr;
             const uint32_t *ops = nullptr;
             uint64_t numOps = 0;
@@ -346,7 +365,7 @@ int main(int argc, char *argv[]) {
         double usec = 0;
         if ((rc = dpx_batch_last_fill_usec(f.b, &usec)) != DPX_OK) die("KERNEL TIMING FAILED", rc);
         kernel_time += (uint64_t)usec;
-        if (print && dpx_batch_last_output_usec(f.b, &usec) == DPX_OK) traceback_kernel_time += (uint64_t)usec;
+        if (print && !scoresOnly && dpx_batch_last_output_usec(f.b, &usec) == DPX_OK) traceback_kernel_time += (uint64_t)usec;
         backtracking_time += get_time() - t0;
         t0 = get_time();
         dpx_batch_destroy(f.b);
@@ -354,7 +373,7 @@ int main(int argc, char *argv[]) {
         memalloc_time += get_time() - t0;
         retire_printed();
         printingText = text;
-        if (print && cigar) printer = std::thread([s = std::move(lines)]() { fwrite(s.data(), 1, s.size(), stdout); });
+        if (print && (cigar || scoresOnly)) printer = std::thread([s = std::move(lines)]() { fwrite(s.data(), 1, s.size(), stdout); });
         else if (print) printer = std::thread([text, bytes]() { fwrite(text, 1, bytes, stdout); });
     };
     size_t shardCells = 0;
@@ -379,7 +398,7 @@ int main(int argc, char *argv[]) {
         const uint64_t t0 = get_time();
         const bool bandDirections = directions && (algo == DPX_ALGO_BANW || algo == DPX_ALGO_BAXT);
         const bool localDirections = directions && (algo == DPX_ALGO_BSW || algo == DPX_ALGO_BASW);
-        const unsigned flags = (twoPiece ? DPX_TWO_PIECE_GAPS : 0u) | (bandDirections ? DPX_KEEP_BAND_DIRECTIONS : localDirections ? DPX_KEEP_LOCAL_BAND_DIRECTIONS : directions ? DPX_KEEP_DIRECTIONS : DPX_KEEP_MATRICES) | DPX_TIME_FILLS | ((tunePools && tuned.fetch_add(1) < inflight) ? DPX_TUNE_PLACEMENT : 0u);
+        const unsigned flags = (twoPiece ? DPX_TWO_PIECE_GAPS : 0u) | (bandDirections ? DPX_KEEP_BAND_DIRECTIONS : localDirections ? DPX_KEEP_LOCAL_BAND_DIRECTIONS : directions ? DPX_KEEP_DIRECTIONS : scoresOnly ? DPX_SCORE_ONLY : DPX_KEEP_MATRICES) | DPX_TIME_FILLS | ((tunePools && !scoresOnly && tuned.fetch_add(1) < inflight) ? DPX_TUNE_PLACEMENT : 0u);
         int prc = pack2 ? dpx_batch_create_packed2(-1, &prm, packed.data(), fileInfo.numBytes, alphabet, reinterpret_cast<const dpx_seq_pair *>(sequenceIdxs),
                                                    first, next.count, flags, &next.b)
                         : dpx_batch_create(&prm, sequences, fileInfo.numBytes, reinterpret_cast<const dpx_seq_pair *>(sequenceIdxs), first, next.count,
@@ -392,6 +411,8 @@ int main(int argc, char *argv[]) {
                 die(matrixFile ? "FAILED TO SET THE SUBSTITUTION MATRIX" : "FAILED TO SET THE EXTENSION MODE", prc);
         } else if (directionTable) {
             if ((prc = dpx_batch_set_direction_table(next.b, substScores.data(), substAlphabet, substCode)) != DPX_OK) die("FAILED TO SET THE SUBSTITUTION MATRIX", prc);
+        } else if (scoreTable) {
+            if ((prc = dpx_batch_set_score_table(next.b, substScores.data(), substAlphabet, substCode)) != DPX_OK) die("FAILED TO SET THE SUBSTITUTION MATRIX", prc);
         } else {
             if ((zdrop != -1 || endBonus != -1) && (prc = dpx_batch_set_extension(next.b, zdrop, endBonus)) != DPX_OK) die("FAILED TO SET THE EXTENSION MODE", prc);
             if (matrixFile && (prc = dpx_batch_set_substitution(next.b, substScores.data(), substAlphabet, substCode)) != DPX_OK) die("FAILED TO SET THE SUBSTITUTION MATRIX", prc);
@@ -403,7 +424,8 @@ int main(int argc, char *argv[]) {
         create_time += get_time() - t0;
         if ((prc = dpx_batch_fill(next.b, nullptr)) != DPX_OK) die("KERNEL LAUNCH FAILED", prc);
         // global pair numbers: shardFirst + index inside the shard
-        if (print && cigar) { if ((prc = dpx_batch_cigars_begin(next.b, cigarFlags)) != DPX_OK) die("TRACEBACK LAUNCH FAILED", prc); }
+        if (print && scoresOnly) { /* (nothing to start: finish reads the results) */ }
+        else if (print && cigar) { if ((prc = dpx_batch_cigars_begin(next.b, cigarFlags)) != DPX_OK) die("TRACEBACK LAUNCH FAILED", prc); }
         else if (print && (prc = dpx_batch_output_begin(next.b, shardFirst + first)) != DPX_OK) die("TRACEBACK LAUNCH FAILED", prc);
         return next;
     };

@@ -697,6 +697,45 @@ int dpx_batch_set_reversed(dpx_batch *b, const uint8_t *reversed /* numPairs byt
  * DPX_TIME_FILLS, dpx_batch_fill_timed, a caller's stream, dpx_batch_create_on and packed2 input as for any direction batch. */
 int dpx_batch_set_direction_table(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf /* 256 entries */);
 
+/* ---- substitution-matrix scoring of ANW, ASW and ASG score-only batches ----
+ * A database search -- one query scored against many sequences under BLOSUM62 -- or a read scored against many candidate windows under a
+ * 5 x 5 matrix with a negative N needs scores and end cells, no traceback: score everything, keep the hits, realign those on a direction
+ * batch (dpx_batch_set_direction_table).  This setter gives DPX_SCORE_ONLY batches of the three full-matrix affine algorithms a table: no
+ * pool, no stores, the kernels of any score-only batch with one term changed.  A new exported symbol, no ABI bump and no new flag:
+ * detect it by the symbol.
+ *   Definition.  ANW's / ASW's / ASG's block above, word for word, with one change: the diagonal term is
+ *         H[i-1][j-1] + scores[codeOf[r] * alphabet + codeOf[q]]
+ *     for the reference byte r and the query byte q (the row is the reference code; the table need not be symmetric).  params.match /
+ *     params.mismatch are ignored.  Borders, tie order, ASW's zero floor and first strict maximum in row-major order, ASG's first
+ *     maximum of row m with column 0 winning a tie, and the empty-sequence results do not change.
+ *   Arguments.  dpx_batch_set_substitution's: both arrays are copied at the call; scores == NULL clears the table (the other arguments
+ *     are ignored), is legal on every batch and changes nothing where nothing was set.  Where a table was set through another setter
+ *     (dpx_batch_set_substitution on a BANW batch, say) the NULL call clears that one, as dpx_batch_set_direction_table's NULL call
+ *     does: a batch holds one table, and NULL through any of the three clears it.
+ *   Lifecycle.  dpx_batch_set_substitution's: the setting applies to every following fill; a call that changes it invalidates the
+ *     results of an earlier fill (DPX_ERR_NOT_FILLED until the next fill); setting the same table again invalidates nothing; a refused
+ *     or failed call leaves the previous setting in force, dpx_batch_describe byte-identical and the batch filling as before.
+ *   DPX_ERR_INVALID      b == NULL; with scores != NULL: alphabet outside 1..32, codeOf == NULL, or a codeOf[x] >= alphabet
+ *   DPX_ERR_UNSUPPORTED  anything but a DPX_ALGO_ANW / DPX_ALGO_ASW / DPX_ALGO_ASG batch (the batch's own algorithm) created with
+ *                        DPX_SCORE_ONLY: their matrix batches (a traceback under a table is the direction batch's, at a twelfth of the
+ *                        bytes), their direction batches (which keep their own setter), LNW / LSW, every banded algorithm in every
+ *                        storage mode (a covering BANW / BASW band that runs the ANW / ASW kernels included); and a batch where one
+ *                        wave's LDS slice plus the table image does not fit a workgroup (dpx_last_error() says which; today creation
+ *                        admits a batch only when FOUR plain slices fit one workgroup, so no batch that exists reaches this refusal)
+ *   DPX_ERR_RANGE        the create-time range check of an int16 batch (fits_int16) fails for a pair with the table's largest entry in
+ *                        place of match and its smallest in place of mismatch.  Score-only batches stay on the int16 bound because
+ *                        these kernels keep their stripe edge rows as int16 in LDS and their ASW / ASG running maxima as 16-bit
+ *                        (score, column) keys; the bounds carry over by the argument given for dpx_batch_set_substitution (a diagonal
+ *                        step scores at least the smallest entry and at most the largest).  Longer pairs belong on a direction batch.
+ * While a table is set dpx_batch_describe keeps kernel= (k_affine_fill, k_asw_lanes, ...: the table is a mode of the same fills,
+ * k_scoretab_fill / k_scoretab_lanes in the library) and store=0, and adds ` subst=<alphabet>`.  Every wave keeps the 1280-byte table
+ * image in LDS; where the plan's waves per workgroup no longer fit with it the one-wave-per-pair fill runs one-wave workgroups
+ * (waves_per_workgroup says what will launch; the lane-packed kernels are one-wave workgroups already).  dpx_batch_set_extension,
+ * dpx_batch_set_substitution (with a table), dpx_batch_set_extension_table, dpx_batch_set_direction_scoring and
+ * dpx_batch_set_direction_table keep refusing these batches; matrix requests stay DPX_ERR_NO_MATRIX.  Repeated fills, DPX_TIME_FILLS,
+ * dpx_batch_fill_timed, a caller's stream, dpx_batch_create_on, packed2 input and pairs that share bytes as for any score-only batch. */
+int dpx_batch_set_score_table(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf /* 256 entries */);
+
 /* Sizes: numPairs, total cells (sum refLen*queryLen, the reference's numCells, c++/parseInput.cpp:100),
  * bytes of HBM the matrices occupy, algorithmic bytes of one fill. */
 int dpx_batch_info(dpx_batch *b, size_t *numPairs, uint64_t *cells, uint64_t *matrixBytes, uint64_t *algorithmicBytes);
