@@ -24,6 +24,8 @@ MAT_I2, MAT_D2, MAT_H_PIECE = 3, 4, 5  # Batch.directions on a TWO_PIECE_GAPS ba
 # CIGARs (dpx_batch_cigars_begin / _end): an op is (length << 4) | code with BAM's code numbers
 CIGAR_OP_M, CIGAR_OP_I, CIGAR_OP_D, CIGAR_OP_EQ, CIGAR_OP_X = 0, 1, 2, 7, 8
 CIGAR_EXTENDED, CIGAR_M = 0x0, 0x1
+# difference strings (dpx_batch_diffs_begin / _end): SAM's MD tag, minimap2's short cs tag
+DIFF_MD, DIFF_CS = 0x1, 0x2
 # BAXT's extension mode (dpx_batch_set_extension / dpx_batch_extensions)
 EXT_ZDROPPED, EXT_REACHED_END = 0x1, 0x2
 EXT_NO_QUERY_END = -2**31
@@ -40,7 +42,7 @@ ABI_SYMBOLS = (
     "dpx_batch_cigars_begin", "dpx_batch_cigars_end", "dpx_cigar_text", "dpx_batch_set_extension", "dpx_batch_extensions",
     "dpx_batch_set_substitution", "dpx_batch_set_extension_table", "dpx_batch_set_direction_scoring",
     "dpx_batch_set_second_gap", "dpx_batch_set_reversed", "dpx_batch_set_direction_table",
-    "dpx_batch_set_score_table",
+    "dpx_batch_set_score_table", "dpx_batch_diffs_begin", "dpx_batch_diffs_end",
 )
 # declared entry points a library may lack and still load (an older build): checked when they are called
 OPTIONAL_SYMBOLS = ("dpx_batch_directions",)
@@ -138,6 +140,8 @@ def load() -> C.CDLL:
     lib.dpx_batch_set_reversed.argtypes = [vp, vp]
     lib.dpx_batch_set_direction_table.argtypes = [vp, vp, C.c_int32, vp]
     lib.dpx_batch_set_score_table.argtypes = [vp, vp, C.c_int32, vp]
+    lib.dpx_batch_diffs_begin.argtypes = [vp, C.c_uint]
+    lib.dpx_batch_diffs_end.argtypes = [vp, C.c_uint, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.POINTER(C.c_uint64))]
     for name in ABI_SYMBOLS:  # every declared entry point must be exported (the optional ones by libraries that have them)
         if name not in OPTIONAL_SYMBOLS:
             getattr(lib, name)
@@ -285,6 +289,23 @@ class Batch:
             if self.num_pairs else np.zeros(0, ALIGNMENT_DTYPE)
         out = np.frombuffer(C.string_at(ops, n.value * 4), dtype=np.uint32).copy() if n.value else np.zeros(0, np.uint32)
         return records, out
+
+    def diffs_begin(self, kinds: int = DIFF_MD | DIFF_CS) -> None:
+        """Start building the batch's MD and / or cs strings on the device (asynchronous); `kinds`: DIFF_MD, DIFF_CS or both."""
+        _check(self._lib.dpx_batch_diffs_begin(self._h, kinds), "dpx_batch_diffs_begin")
+
+    def diffs_end(self, kind: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(text, offsets) of one kind: the pairs' strings back to back as a uint8 array and numPairs + 1 uint64 byte offsets, as copies."""
+        text, nbytes, offs = C.c_void_p(), C.c_size_t(0), C.POINTER(C.c_uint64)()
+        _check(self._lib.dpx_batch_diffs_end(self._h, kind, C.byref(text), C.byref(nbytes), C.byref(offs)), "dpx_batch_diffs_end")
+        raw = np.frombuffer(C.string_at(text, nbytes.value), dtype=np.uint8).copy() if nbytes.value else np.zeros(0, np.uint8)
+        return raw, np.ctypeslib.as_array(offs, shape=(self.num_pairs + 1,)).copy()
+
+    def diff_strings(self, kind: int) -> list:
+        """The strings of diffs_end(kind), one bytes object per pair (cut at the offsets: a string may hold any byte)."""
+        raw, offs = self.diffs_end(kind)
+        data = raw.tobytes()
+        return [data[int(offs[p]):int(offs[p + 1])] for p in range(self.num_pairs)]
 
     def set_extension(self, zdrop: int = -1, end_bonus: int = -1) -> None:
         """BAXT only: z-drop threshold and end bonus of the following fills (-1 = off; both off = plain BAXT)."""

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "dpx_cigar.h"
+#include "dpx_diff.h"
 #include "dpx_reverse.h"
 #include "dpx_plan.h" /* (brings dpx_kernels.h, dpx_dir.h, dpx_banddir.h and dpx_layout.h) */
 
@@ -503,6 +504,13 @@ struct dpx_batch : dpx_plan {
     uint32_t *hCigarOps = nullptr; /* pinned: exactly the ops */
     size_t dCigarCap = 0, dCigarOpsCap = 0, hCigarCap = 0, hCigarOpsCap = 0;
     uint64_t cigarOps = 0;     /* total number of ops (state 2) */
+    /* difference strings (dpx_batch_diffs_begin / _end), index 0: MD, 1: cs -- from the same lines again, with buffers of their own per kind */
+    int diffState[2] = {0, 0};             /* 0 none, 1 dpx_batch_diffs_begin() in flight, 2 text on the host */
+    char *dDiffOff[2] = {nullptr, nullptr};  /* device: uint64 offsets[numPairs + 1], uint64 tile sums of the scan */
+    char *dDiffText[2] = {nullptr, nullptr}; /* device: the size of the line buffer (three times the line capacity per pair at worst) */
+    char *hDiffOff[2] = {nullptr, nullptr};  /* pinned: uint64 offsets[numPairs + 1] */
+    char *hDiffText[2] = {nullptr, nullptr}; /* pinned: exactly the strings and one NUL */
+    size_t dDiffOffCap[2] = {0, 0}, dDiffTextCap[2] = {0, 0}, hDiffOffCap[2] = {0, 0}, hDiffTextCap[2] = {0, 0};
     /* BAXT's extension mode (dpx_batch_set_extension): the next fill runs k_zext_fill while either value is >= 0 */
     int32_t zdrop = -1, endBonus = -1;
     bool extFilled = false;    /* the last fill ran the extension scan (k_zext_fill, k_zsub_fill, k_bdx_fill with zdrop or endBonus on): dExt holds its
@@ -802,6 +810,12 @@ int dpx_batch_destroy(dpx_batch *b) {
     g_tbDevCache.park(b->dCigarOps, b->dCigarOpsCap);
     g_tbHostCache.park(b->hCigar, b->hCigarCap);
     g_tbHostCache.park(b->hCigarOps, b->hCigarOpsCap);
+    for (int k = 0; k < 2; k++) {
+        g_tbDevCache.park(b->dDiffOff[k], b->dDiffOffCap[k]);
+        g_tbDevCache.park(b->dDiffText[k], b->dDiffTextCap[k]);
+        g_tbHostCache.park(b->hDiffOff[k], b->hDiffOffCap[k]);
+        g_tbHostCache.park(b->hDiffText[k], b->hDiffTextCap[k]);
+    }
     g_tbDevCache.park(b->dExt, b->dExtCap);
     g_tbDevCache.park(b->dSubst, b->dSubstCap);
     g_arenaCache.park(b->dRev, b->dRevCap);
@@ -1061,7 +1075,7 @@ static dpx_route route_of(const dpx_batch *b) { return dpx_plan_route(*b, knobs(
 
 /* what a refill does to lines, text and CIGARs; the results go with them until the next fill */
 static void invalidate_fill(dpx_batch *b) {
-    b->filled = false; b->extFilled = false; b->tbLinesValid = false; b->outState = 0; b->cigarState = 0;
+    b->filled = false; b->extFilled = false; b->tbLinesValid = false; b->outState = 0; b->cigarState = 0; b->diffState[0] = b->diffState[1] = 0;
 }
 /* ... and that next fill, queued on `s` along route `r` */
 static void mark_filled(dpx_batch *b, const dpx_route &r, hipStream_t s) {
@@ -1957,6 +1971,71 @@ int dpx_batch_cigars_end(dpx_batch *b, const dpx_alignment **records, const uint
     if (records) *records = reinterpret_cast<const dpx_alignment *>(b->hCigar);
     if (ops) *ops = b->hCigarOps;
     if (numOps) *numOps = b->cigarOps;
+    return DPX_OK;
+}
+
+/* ---- difference strings: the same traceback lines once more, as MD or cs text per pair (dpx_diff_kernels.hip) -> D2H of the
+ * numPairs + 1 offsets, then of exactly the bytes.  Buffers of their own per kind, so text, CIGARs and these may follow the same fill
+ * in any order. */
+
+int dpx_batch_diffs_begin(dpx_batch *b, unsigned kinds) {
+    if (!b || kinds == 0 || (kinds & ~(DPX_DIFF_MD | DPX_DIFF_CS)) != 0) return DPX_ERR_INVALID;
+    if (!b->store) return DPX_ERR_NO_MATRIX;
+    if (!b->filled) return DPX_ERR_NOT_FILLED;
+    int rc = bind_device(b->device);
+    if (rc != DPX_OK) return rc;
+    const size_t np = b->numPairs, offBytes = (np + 1) * sizeof(uint64_t);
+    const uint64_t lines = b->tbOff[np];
+    if (!b->dTb) HIP_TRY(g_tbDevCache.take((void **)&b->dTb, (size_t)std::max<uint64_t>(lines, 16), &b->dTbCap));
+    if (np) {
+        rc = order_behind_fill(b);
+        if (rc == DPX_OK) rc = traceback_lines(b);
+        if (rc != DPX_OK) return rc;
+    }
+    for (int k = 0; k < 2; k++) {
+        const unsigned kind = k == 0 ? DPX_DIFF_MD : DPX_DIFF_CS;
+        if (!(kinds & kind)) continue;
+        /* buffers, on first use (a failed attempt is simply repeated); text, worst case: three bytes per column of every line capacity */
+        if (!b->dDiffOff[k]) HIP_TRY(g_tbDevCache.take((void **)&b->dDiffOff[k], offBytes + dpx_diff_scan_tiles(np) * sizeof(uint64_t) + 16, &b->dDiffOffCap[k]));
+        if (!b->dDiffText[k]) HIP_TRY(g_tbDevCache.take((void **)&b->dDiffText[k], (size_t)lines + 16, &b->dDiffTextCap[k]));
+        if (!b->hDiffOff[k]) HIP_TRY(g_tbHostCache.take((void **)&b->hDiffOff[k], offBytes + 16, &b->hDiffOffCap[k]));
+        if (np) {
+            unsigned long long *dOff = reinterpret_cast<unsigned long long *>(b->dDiffOff[k]);
+            HIP_TRY(dpx_launch_diffs(kind, b->dPairs, b->dTbLen, b->dTbOff, b->dTb, (int)np, dOff, dOff + np + 1, b->dDiffText[k], b->stream));
+            HIP_TRY(hipMemcpyAsync(b->hDiffOff[k], b->dDiffOff[k], offBytes, hipMemcpyDeviceToHost, b->stream));
+        } else {
+            memset(b->hDiffOff[k], 0, sizeof(uint64_t)); /* a batch without pairs: one offset of 0, no bytes */
+        }
+        b->diffState[k] = 1;
+    }
+    return DPX_OK;
+}
+
+int dpx_batch_diffs_end(dpx_batch *b, unsigned kind, const char **text, size_t *bytes, const uint64_t **offsets) {
+    if (!b || (kind != DPX_DIFF_MD && kind != DPX_DIFF_CS)) return DPX_ERR_INVALID;
+    const int k = kind == DPX_DIFF_MD ? 0 : 1;
+    if (b->diffState[k] == 0) return DPX_ERR_NOT_FILLED; /* no dpx_batch_diffs_begin() of this kind since the last fill */
+    int rc = bind_device(b->device);
+    if (rc != DPX_OK) return rc;
+    const uint64_t *hOff = reinterpret_cast<const uint64_t *>(b->hDiffOff[k]);
+    if (b->diffState[k] == 1) {
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        const size_t total = (size_t)hOff[b->numPairs];
+        if (!b->hDiffText[k] || b->hDiffTextCap[k] < total + 1 + 16) {
+            g_tbHostCache.park(b->hDiffText[k], b->hDiffTextCap[k]);
+            b->hDiffText[k] = nullptr;
+            HIP_TRY(g_tbHostCache.take((void **)&b->hDiffText[k], total + 1 + 16, &b->hDiffTextCap[k]));
+        }
+        if (total) {
+            HIP_TRY(hipMemcpyAsync(b->hDiffText[k], b->dDiffText[k], total, hipMemcpyDeviceToHost, b->stream));
+            HIP_TRY(hipStreamSynchronize(b->stream));
+        }
+        b->hDiffText[k][total] = 0;
+        b->diffState[k] = 2;
+    }
+    if (text) *text = b->hDiffText[k];
+    if (bytes) *bytes = (size_t)hOff[b->numPairs];
+    if (offsets) *offsets = hOff;
     return DPX_OK;
 }
 

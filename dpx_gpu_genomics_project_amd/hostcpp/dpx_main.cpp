@@ -9,9 +9,11 @@
 // -cigar [M]: instead of the four-line block, one tab-separated line per pair from the engine's alignment records and CIGAR ops
 // (dpx_batch_cigars_begin / _end): pair, score, qryLen, qryStart, qryEnd, refLen, refStart, refEnd, matches, alnLen, cigar -- PAF's
 // coordinates and the SAM CIGAR ('=' / 'X' ops; "-cigar M" merges them into 'M').  The lines are formatted on the host.
+// -md / -cs (only with -cigar): every line gains the fields NM:i:<mismatches + insertions + deletions>, then MD:Z:<text> under -md and
+// cs:Z:<text> under -cs, the strings built on the device (dpx_batch_diffs_begin / _end).
 //
 //   dpx_main -pairs <file> [-match 3] [-mismatch -1] [-open -2 | -gap -2] [-extend -1]
-//            [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band 128] [-batch N | -pool-gb 4] [-inflight K] [-tune 0|1] [-device 0] [-noprint] [-pack2] [-directions] [-cigar [M]] [-zdrop Z] [-endbonus E] [-matrix FILE] [-open2 O2 -extend2 E2] [-reverse] [-producer P] [-rank r -world w]
+//            [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band 128] [-batch N | -pool-gb 4] [-inflight K] [-tune 0|1] [-device 0] [-noprint] [-pack2] [-directions] [-cigar [M] [-md] [-cs]] [-zdrop Z] [-endbonus E] [-matrix FILE] [-open2 O2 -extend2 E2] [-reverse] [-producer P] [-rank r -world w]
 //
 // -matrix FILE (BANW / BAXT, not with -zdrop / -endbonus): score columns by a substitution matrix (dpx_batch_set_substitution) instead of
 // -match / -mismatch.  NCBI text format: '#' lines are comments; one header row of 1..32 single-character column letters; then one row
@@ -137,7 +139,7 @@ bool read_matrix(const char *path, std::vector<int8_t> &scores, int &alphabet, u
 
 static void usage() {
     fprintf(stderr, "usage: dpx_main -pairs <InSeqFile> -match <matchWeight> -mismatch <mismatchWeight> -open <gapWeight> "
-                    "[-extend <gapExtend>] [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band <B>] [-batch <N>] [-device <D>] [-noprint] [-cigar [M]] "
+                    "[-extend <gapExtend>] [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band <B>] [-batch <N>] [-device <D>] [-noprint] [-cigar [M]] [-md] [-cs] (only with -cigar: NM:i:, MD:Z: and cs:Z: fields behind the CIGAR) "
                     "[-zdrop <Z>] [-endbonus <E>] (BAXT only) [-matrix <file>] (BANW / BAXT, not with -zdrop / -endbonus; ANW / ASW / ASG only with -directions) "
                     "[-directions] (direction codes instead of score matrices; -algo BSW|BASW -directions: one code per in-band cell, long pairs run; BANW / BAXT: with -zdrop / -endbonus / -matrix too; -algo ANW|ASW|ASG -directions -matrix <file>: full-matrix affine alignment under a substitution matrix) "
                     "[-open2 <O2> -extend2 <E2>] (two-piece gaps: both together, only with -directions and -algo BANW|BAXT) "
@@ -156,6 +158,7 @@ int main(int argc, char *argv[]) {
     int producerFlag = -1; // producer threads; -1: by batch size (2 for batches of many short pairs, none for few long ones)
     bool cigar = false;      // -cigar: records + CIGAR ops instead of the text pipeline
     unsigned cigarFlags = DPX_CIGAR_EXTENDED;
+    unsigned diffKinds = 0;  // -md / -cs (only with -cigar): every line gains NM:i:, then MD:Z: and / or cs:Z: from dpx_batch_diffs_begin / _end
     bool directions = false; // -directions: batches keep 4-bit direction codes (DPX_KEEP_DIRECTIONS): int32 scores, a quarter of the pool per pair
                              // (-algo BANW | BAXT: DPX_KEEP_BAND_DIRECTIONS, -algo BSW | BASW: DPX_KEEP_LOCAL_BAND_DIRECTIONS, one code per in-band cell)
     int zdrop = -1, endBonus = -1; // -zdrop / -endbonus: BAXT's extension mode (dpx_batch_set_extension) on every batch; -1 = off
@@ -189,6 +192,8 @@ int main(int argc, char *argv[]) {
             cigar = true;
             if (i + 1 < argc && !strcmp(argv[i + 1], "M")) { cigarFlags = DPX_CIGAR_M; i++; }
         }
+        else if (!strcmp(argv[i], "-md")) diffKinds |= DPX_DIFF_MD;
+        else if (!strcmp(argv[i], "-cs")) diffKinds |= DPX_DIFF_CS;
         else if (!strcmp(argv[i], "-zdrop")) zdrop = atoi(next("-zdrop"));
         else if (!strcmp(argv[i], "-endbonus")) endBonus = atoi(next("-endbonus"));
         else if (!strcmp(argv[i], "-matrix")) matrixFile = next("-matrix");
@@ -214,6 +219,7 @@ int main(int argc, char *argv[]) {
     const bool twoPiece = haveOpen2 || haveExtend2;
     if (twoPiece && (!(haveOpen2 && haveExtend2) || !directions || (algo != DPX_ALGO_BANW && algo != DPX_ALGO_BAXT))) usage();
     if (reverse && algo != DPX_ALGO_BANW && algo != DPX_ALGO_BAXT) usage();
+    if (diffKinds && !cigar) usage();
     if (scoresOnly && (directions || cigar || zdrop != -1 || endBonus != -1 || twoPiece || reverse)) usage();
     std::vector<int8_t> substScores;
     int substAlphabet = 0;
@@ -344,6 +350,10 @@ int main(int argc, char *argv[]) {
             if ((rc = dpx_batch_cigars_end(f.b, &recs, &ops, &numOps)) != DPX_OK) die("TRACEBACK FAILED", rc);
             std::vector<int32_t> scores(f.count);
             if ((rc = dpx_batch_results(f.b, scores.data(), nullptr, nullptr)) != DPX_OK) die("RESULTS FAILED", rc);
+            const char *diffText[2] = {nullptr, nullptr}; // MD, cs: the batch's strings back to back, cut at the offsets
+            const uint64_t *diffOff[2] = {nullptr, nullptr};
+            if ((diffKinds & DPX_DIFF_MD) && (rc = dpx_batch_diffs_end(f.b, DPX_DIFF_MD, &diffText[0], nullptr, &diffOff[0])) != DPX_OK) die("MD FAILED", rc);
+            if ((diffKinds & DPX_DIFF_CS) && (rc = dpx_batch_diffs_end(f.b, DPX_DIFF_CS, &diffText[1], nullptr, &diffOff[1])) != DPX_OK) die("CS FAILED", rc);
             std::vector<char> cg;
             for (size_t k = 0; k < f.count; k++) {
                 const dpx_alignment &r = recs[k];
@@ -357,6 +367,14 @@ int main(int argc, char *argv[]) {
                                        r.matches + r.mismatches + r.insertions + r.deletions);
                 lines.append(head, (size_t)h);
                 lines.append(cg.data(), need);
+                if (diffKinds) {
+                    lines.append(head, (size_t)snprintf(head, sizeof head, "\tNM:i:%d", r.mismatches + r.insertions + r.deletions));
+                    for (int d = 0; d < 2; d++)
+                        if (diffText[d]) {
+                            lines.append(d == 0 ? "\tMD:Z:" : "\tcs:Z:");
+                            lines.append(diffText[d] + diffOff[d][k], (size_t)(diffOff[d][k + 1] - diffOff[d][k]));
+                        }
+                }
                 lines.push_back('\n');
             }
         } else if (print) {
@@ -425,7 +443,8 @@ int main(int argc, char *argv[]) {
         if ((prc = dpx_batch_fill(next.b, nullptr)) != DPX_OK) die("KERNEL LAUNCH FAILED", prc);
         // global pair numbers: shardFirst + index inside the shard
         if (print && scoresOnly) { /* (nothing to start: finish reads the results) */ }
-        else if (print && cigar) { if ((prc = dpx_batch_cigars_begin(next.b, cigarFlags)) != DPX_OK) die("TRACEBACK LAUNCH FAILED", prc); }
+        else if (print && cigar) { if ((prc = dpx_batch_cigars_begin(next.b, cigarFlags)) != DPX_OK) die("TRACEBACK LAUNCH FAILED", prc);
+            if (diffKinds && (prc = dpx_batch_diffs_begin(next.b, diffKinds)) != DPX_OK) die("MD / CS LAUNCH FAILED", prc); }
         else if (print && (prc = dpx_batch_output_begin(next.b, shardFirst + first)) != DPX_OK) die("TRACEBACK LAUNCH FAILED", prc);
         return next;
     };

@@ -424,6 +424,66 @@ int dpx_batch_cigars_end(dpx_batch *b, const dpx_alignment **records, const uint
  * an op code outside {0, 1, 2, 7, 8} returns DPX_ERR_INVALID. */
 int dpx_cigar_text(const uint32_t *ops, size_t numOps, char *out, size_t cap, size_t *len);
 
+/* ---- Difference strings of the whole batch: SAM's MD tag and minimap2's short cs tag ----------------------------------------
+ * What a SAM or PAF record needs beyond the CIGAR, built on the device from the same traceback lines: one packed text buffer per
+ * kind and numPairs + 1 byte offsets, instead of three (m + n)-byte lines per pair tokenised on the host.  Every algorithm and
+ * storage mode the CIGAR path serves; a DPX_SCORE_ONLY batch is DPX_ERR_NO_MATRIX.  No reference counterpart.  Added without an ABI
+ * bump: detect the two functions by the exported symbol.
+ *
+ * NM, the edit distance, has no entry point of its own: NM = mismatches + insertions + deletions of the pair's dpx_alignment record.
+ *
+ * Columns of a pair's three lines are classified exactly as the CIGAR section classifies them:
+ *     relation '*',           any query-line byte        '='
+ *     relation '|',           any query-line byte        'X'
+ *     anything else,          query-line byte '_'        'D'
+ *     anything else,          anything else              'I'
+ * ref[c] and qry[c] are the bytes of the reference line and the query line at column c.  Columns run from the start of the alignment
+ * to its end cell.  Under dpx_batch_set_reversed the lines are already in the caller's orientation when these kernels see them, so
+ * the strings come out in the caller's orientation.
+ *
+ * MD is what `samtools calmd` writes:
+ *     n = 0; prev = none
+ *     for each column c:
+ *         '=' : n += 1
+ *         'X' : emit decimal(n), emit ref[c]; n = 0
+ *         'D' : if prev != 'D': emit decimal(n), emit '^'; n = 0
+ *               emit ref[c]
+ *         'I' : nothing          (an insertion does not break a match run, but it does end a deletion run)
+ *         prev = class of c
+ *     emit decimal(n)
+ * decimal(n) has no leading zeros; decimal(0) is "0".  An empty alignment gives "0".  Reference bytes are emitted as they are: there
+ * is no case folding, and a reference byte that is a digit or '^' makes the string ambiguous (it is emitted all the same).
+ *
+ * cs is minimap2's short form.  Take the maximal runs of equal class, which are the ops of DPX_CIGAR_EXTENDED:
+ *     an '=' run of length L emits ':' then decimal(L)
+ *     every 'X' column emits '*', lc(ref[c]), lc(qry[c])
+ *     an 'I' run emits '+' then lc(qry[c]) for each column
+ *     a 'D' run emits '-' then lc(ref[c]) for each column
+ * lc adds 32 to the bytes 'A'..'Z' and leaves every other byte alone.  An empty alignment gives the empty string.  The long form
+ * (matched bases spelled out) is not built.
+ *
+ * Length bound.  A pair's MD or cs never exceeds 3 * cap bytes, where cap = (m + n + 1 + 3) & ~3 is the capacity of one of its lines
+ * and len <= m + n its alignment length, so cap >= len + 1.  cs: an 'X' column emits 3 bytes, an 'I' or 'D' column 2 at the start of
+ * its run and 1 inside it, and an '=' run of L >= 1 columns 1 + digits(L) <= 3 * L bytes: at most 3 bytes per column, 3 * len in
+ * all.  MD: a number of d digits in front of a breaker stands for at least d '=' columns that emit nothing else, except that a "0"
+ * costs one byte without any; so the densest pattern is D X D X ..., "0^" + base for a D and "0" + base for an X, 2.5 bytes per
+ * column, and with the closing number MD <= (5 * len + 1) / 2 + 1 <= 3 * (len + 1) <= 3 * cap.  Hence one device text buffer of the
+ * size of the batch's line buffer holds every kind's worst case, and count, scan and write run without a host round trip. */
+#define DPX_DIFF_MD 0x1u
+#define DPX_DIFF_CS 0x2u
+
+/* _begin (`kinds`: one or both bits) is asynchronous on the batch's stream (behind a fill on a caller's stream it orders itself with an
+ * event): the device traceback if the lines of this fill do not exist yet, so the walk runs once whichever of text, CIGARs and diffs
+ * comes first; then per requested kind count, scan and write kernels and the D2H of the numPairs + 1 offsets.  _end (`kind`: exactly
+ * one bit that a _begin since the last fill was given) waits and copies exactly offsets[numPairs] bytes to pinned host memory: *text
+ * holds the pairs' strings back to back with no separators and one NUL after the last byte, *offsets are numPairs + 1 byte offsets,
+ * *bytes is offsets[numPairs].  The pointers stay valid until the batch is filled again, the next _begin of that kind, or destroy.
+ * The text pipeline, the CIGAR path and this one may follow the same fill in any order.  `kinds` 0 or with unknown bits, `kind` not
+ * exactly one known bit: DPX_ERR_INVALID; not filled, or _end for a kind not begun since the last fill: DPX_ERR_NOT_FILLED.  A batch
+ * of zero pairs gives *bytes = 0 and one offset of 0. */
+int dpx_batch_diffs_begin(dpx_batch *b, unsigned kinds);
+int dpx_batch_diffs_end(dpx_batch *b, unsigned kind, const char **text, size_t *bytes, const uint64_t **offsets);
+
 /* ---- BAXT extension mode: z-drop termination, the query-end score and an end bonus -----------------------------------------
  * What a read mapper's extension step needs beyond DPX_ALGO_BAXT: stop once the score has fallen far enough below its best (ksw2's
  * zdrop, BWA-MEM's Z-dropoff), report the best score that reaches the END OF THE QUERY (ksw2's mqe / mqe_t, BWA's gscore / gtle),
