@@ -3,14 +3,16 @@ fill kernel under every layout of tests/layouts.py).  TEST INFRASTRUCTURE ONLY -
 
 One small batch per fill kernel of dpx_route_kernel_name, forced the way the kernel's own GPU test forces it, and for each the CPU oracle
 of its algorithm -- the ones those tests use.  An expectation depends on the texts only: want() computes it once per case and every
-layout, walk and test shares it.
+layout, walk and test shares it.  Behind the storing cases come the DPX_SCORE_ONLY cases -- every route such a batch can take, each on
+the texts, the oracle and the want() of its storing sibling -- and the table twins of ANW / ASW / ASG (dpx_batch_set_score_table on the
+score-only cases, dpx_batch_set_direction_table on the direction cases, tests/dirtab_ref.py), which launch under unchanged kernel= names.
 
 TEXTS (standard_texts): 18 ACGT pairs, lengths 0, 1, 15, 16, 17, 63, 64, 65 and 131 among them, |m - n| < 17 so that BANW admits them at
 band 17, longest string 131 so that no band of 129 covers the batch.  Pairs 0..2 share one reference of 131 (a mutated query, a query
 that is a slice of that reference, a query equal to it), pair 13 repeats pair 12, pairs 16 and 17 have the empty reference and the empty
 query -- on residues that pairs 0 and 1 cover as well, so the 16 non-empty references and 16 non-empty queries in front of them put a
 string of each kind on every residue."""
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import numpy as np
 
@@ -22,6 +24,7 @@ import baxt_ref
 import bd2_ref
 import bdl_ref
 import bdx_ref
+import dirtab_ref
 import layouts
 import subst_ref
 import zext_ref
@@ -40,7 +43,7 @@ P1, P2 = (-4, -2), (-24, -1)             # the two gap pieces (tests/test_gpu_bd
 Z, E = 20, 5
 CODE_OF = {"LNW": 0, "LSW": 1, "ANW": 2, "BSW": 3, "ASW": 4, "BASW": 5, "ASG": 6, "BANW": 7, "BAXT": 10}
 FLAGS = {"mat": capi.KEEP_MATRICES, "dirs": capi.KEEP_DIRECTIONS, "bdirs": capi.KEEP_BAND_DIRECTIONS,
-         "two": capi.KEEP_BAND_DIRECTIONS | capi.TWO_PIECE_GAPS, "local": capi.KEEP_LOCAL_BAND_DIRECTIONS}
+         "two": capi.KEEP_BAND_DIRECTIONS | capi.TWO_PIECE_GAPS, "local": capi.KEEP_LOCAL_BAND_DIRECTIONS, "score": capi.SCORE_ONLY}
 BANDS = (17, 129)                        # 1 and 4 cells per lane
 LOCAL_OR_EXTENSION = ("LSW", "BSW", "ASW", "BASW", "ASG", "BAXT")   # (ASG: free reference ends)
 KERNELS = {"k_linear_fill", "k_linear_fill_pk", "k_linear_lanes", "k_linear_lanes_pk", "k_linear_split", "k_affine_fill", "k_asw_fill",
@@ -129,6 +132,12 @@ def ragged40_texts():
     return layouts.texts_of(make_ragged_batch(40, 1, 256, 1, 260, seed=40))
 
 
+def ragged40_acgt_texts():
+    """the same 40 pairs in the letters ACGT: under the five-letter table the digits would all be N"""
+    digits = bytes.maketrans(b"0123", b"ACGT")
+    return [(ref.translate(digits), qry.translate(digits)) for ref, qry in ragged40_texts()]
+
+
 def global_edge_texts(nedges):
     return layouts.texts_of(_dir_global(nedges))
 
@@ -154,17 +163,23 @@ class Case:
     band: int = 0
     env: dict = field(default_factory=dict)
     storage: str = "mat"                # a key of FLAGS
-    mode: tuple = ()                    # ("zext" | "subst" | "zsub" | "bdx" | "bd2", ...): the setters behind the creation
+    mode: tuple = ()                    # ("zext" | "subst" | "zsub" | "bdx" | "bd2" | "table", ...): the setters behind the creation
     walks: tuple = ("default",)
     texts: object = standard_texts
     texts_args: tuple = ()
     every: int = 1                      # planes are read of every `every`-th pair
     layouts: tuple = layouts.LAYOUTS
     describe: dict = field(default_factory=dict)
+    sibling: str = ""                   # a score-only case: the storing case whose texts, oracle and want() it shares
 
     @property
     def dirs(self):
-        return self.storage != "mat"
+        return self.storage not in ("mat", "score")
+
+    @property
+    def table(self):
+        """ANW / ASW / ASG under dpx_batch_set_score_table (score-only) or dpx_batch_set_direction_table (directions)"""
+        return bool(self.mode) and self.mode[0] == "table"
 
     @property
     def scan(self):
@@ -218,10 +233,38 @@ def _cases():
         add(f"BAXT-k_bd2_fill-B{band}", "BAXT", "k_bd2_fill", (2, -4) + P1, band=band, storage="two", mode=("bd2", Z, E, True))
         for algo in ("BSW", "BASW"):
             add(f"{algo}-k_bdl_fill-B{band}", algo, "k_bdl_fill", bdl_ref.weights(CODE_OF[algo], AFF), band=band, storage="local")
+    # DPX_SCORE_ONLY: every route such a batch can take (the planner never packs or splits it), on the texts and the oracle of its storing
+    # sibling; the STORE = false instantiations stage, step and fold differently (tests/test_gpu_score_only.py)
+    by_id = {c.id: c for c in out}
+    score = lambda sib, R: out.append(replace(by_id[sib], id=sib + "-score-only", storage="score", walks=("default",), sibling=sib,
+                                              describe={"store": 0, "rows_per_lane": R}))
+    for algo in ("LSW", "LNW"):
+        score(f"{algo}-k_linear_fill-R2", 2)
+        score(f"{algo}-k_linear_lanes-ragged40", 8)
+    for algo, kernel in (("ANW", "k_affine"), ("ASW", "k_asw"), ("ASG", "k_asg")):
+        score(f"{algo}-{kernel}_fill-R2", 2)
+        score(f"{algo}-{kernel}_lanes-ragged40", 8)
+    for band, cpl in zip(BANDS, (1, 4)):
+        for sib in ("BSW-k_banded_fill", "BASW-k_basw_fill", "BANW-k_banw_fill", "BAXT-k_baxt_fill", "BAXT-k_zext_fill",
+                    ("BANW" if band == 17 else "BAXT") + "-k_subst_fill", "BAXT-k_zsub_fill"):
+            score(f"{sib}-B{band}", cpl)
+    # the table twins of ANW / ASW / ASG (k_dirtab_* and k_scoretab_*): they launch under the kernel= names of the plain batches.  The table
+    # is asymmetric and its map folds every byte outside ACGT onto N, so the fillers and flanks of the layouts are legal and score like
+    # sequence.  A score-only case shares the want() of the direction case over the same texts
+    tab = dict(mode=("table",))
+    for algo, kernel in (("ANW", "k_affine"), ("ASW", "k_asw"), ("ASG", "k_asg")):
+        add(f"{algo}-{kernel}_dir-table", algo, f"{kernel}_dir", (1, -1) + GAPS, storage="dirs", describe={"dir_edges": "lds", "subst": 5}, **tab)
+        add(f"{algo}-{kernel}_dir-global-edges-table", algo, f"{kernel}_dir", (1, -1) + GAPS, storage="dirs", describe={"dir_edges": "global", "subst": 5},
+            texts=global_edge_texts, texts_args=(2,), layouts=("canonical", "residues", "embedded"), **tab)
+        add(f"{algo}-{kernel}_fill-R2-score-table", algo, f"{kernel}_fill", (1, -1) + GAPS, env={"DPX_LANES": "0", "DPX_R": "2"}, storage="score",
+            describe={"store": 0, "rows_per_lane": 2, "subst": 5}, sibling=f"{algo}-{kernel}_dir-table", **tab)
+        add(f"{algo}-{kernel}_lanes-ragged40-score-table", algo, f"{kernel}_lanes", (1, -1) + GAPS, env={"DPX_LANES": "1"}, storage="score",
+            describe={"store": 0, "rows_per_lane": 8, "subst": 5}, texts=ragged40_acgt_texts, every=5, **tab)
     return out
 
 
 CASES = _cases()
+BY_ID = {c.id: c for c in CASES}
 
 
 def plan_case(case):
@@ -230,7 +273,7 @@ def plan_case(case):
     kind = case.mode[0] if case.mode else None
     if kind == "zext":
         out["mode"] = [case.mode[1], case.mode[2], 0]
-    elif kind == "subst":
+    elif kind in ("subst", "table"):
         out["mode"] = [-1, -1, 5]
     elif kind == "zsub":
         out["mode"] = [case.mode[1], case.mode[2], 5]
@@ -259,7 +302,8 @@ def plan_tool_input(case, laid, first_pair=None, walk="default"):
 
 def build_oracles(d):
     return {"ASW": asw_ref.build(d), "ASG": asg_ref.build(d), "BASW": basw_ref.build(d), "BANW": banw_ref.build(d), "BAXT": baxt_ref.build(d),
-            "ZEXT": zext_ref.build(d), "SUBST": subst_ref.build(d), "ZSUB": zsub_ref.build(d), "BD2": bd2_ref.build(d), "BDL": bdl_ref.build(d)}
+            "ZEXT": zext_ref.build(d), "SUBST": subst_ref.build(d), "ZSUB": zsub_ref.build(d), "BD2": bd2_ref.build(d), "BDL": bdl_ref.build(d),
+            "DIRTAB": dirtab_ref.build(d)}
 
 
 def expect(orc, case, ref, qry):
@@ -267,6 +311,12 @@ def expect(orc, case, ref, qry):
     batches: int32 arrays) or dirs (direction batches: uint8 arrays; `planes` then only counts them), lines, rec"""
     kind = case.mode[0] if case.mode else None
     ext = case.algo == "BAXT"
+    if kind == "table":   # score-only and direction batches alike: the comparators take what their storage reports
+        r = orc["DIRTAB"].align(case.algo, ref, qry, TABLE, CODE, *case.w[2:])
+        dirs = [r["dirH"], r["dirI"], r["dirD"]]
+        return {"score": r["score"], "end": tuple(r["end"]), "planes": dirs, "dirs": dirs, "lines": tuple(r["lines"])}
+    if case.storage == "score":   # the oracle of the storing sibling: same algorithm, weights, band and mode
+        return expect(orc, BY_ID[case.sibling], ref, qry)
     if case.storage in ("mat", "dirs") and kind in (None, "zext"):
         return _expect(orc, case.algo, ref, qry, case.w, case.band, tuple(case.mode[1:]) if kind else None)
     if kind == "subst":
@@ -295,10 +345,16 @@ _WANT = {}
 
 
 def want(orc, case):
-    """the oracle's results of a case's texts, computed once and shared by every layout and walk; nothing modifies them"""
-    if case.id not in _WANT:
-        _WANT[case.id] = [expect(orc, case, ref, qry) for ref, qry in texts_of(case)]
-    return _WANT[case.id]
+    """the oracle's results of a case's texts, computed once and shared by every layout and walk, and by a score-only case and its
+    sibling; nothing modifies them"""
+    key = want_key(case)
+    if key not in _WANT:
+        _WANT[key] = [expect(orc, case, ref, qry) for ref, qry in texts_of(case)]
+    return _WANT[key]
+
+
+def want_key(case):
+    return case.sibling or case.id
 
 
 def configure(case, b):
@@ -312,5 +368,7 @@ def configure(case, b):
         b.set_extension_table(case.mode[1], case.mode[2], TABLE, CODE)
     elif kind == "bd2":
         b.set_second_gap(*P2)
+    elif kind == "table":
+        (b.set_score_table if case.storage == "score" else b.set_direction_table)(TABLE, CODE)
     if kind in ("bdx", "bd2") and (case.mode[1] >= 0 or case.mode[2] >= 0 or case.mode[3]):
         b.set_direction_scoring(case.mode[1], case.mode[2], *((TABLE, CODE) if case.mode[3] else (None, None)))

@@ -130,7 +130,10 @@ def test_score_only_matches(gpu):
             with pytest.raises(gpu.DpxError):
                 b.matrix(0)
         for p in range(sb.num_pairs):
-            assert sc[p] == _oracle(algo, sb.ref(p), sb.qry(p), w).score
+            o = _oracle(algo, sb.ref(p), sb.qry(p), w)
+            assert sc[p] == o.score
+            end = (o.end_row, o.end_col) if algo == "LSW" else (len(sb.qry(p)), len(sb.ref(p)))
+            assert (er[p], ec[p]) == end, (algo, p)
 
 
 def test_int16_range_is_enforced(gpu):

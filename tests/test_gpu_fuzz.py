@@ -1,6 +1,7 @@
 """GPU parity fuzz: random shapes (incl. empty, 1-long, ragged), random byte alphabets (any byte value, matching is plain
 byte equality as in the reference), and unusual weights (zero, positive gaps, mismatch > match) -- every cell of every
-matrix, scores, start cells and traceback lines against the oracle, for all four algorithms."""
+matrix, scores, start cells and traceback lines against the oracle, for all four algorithms; then a DPX_SCORE_ONLY batch of the
+same inputs under every weight set: scores and end cells against the same oracle results."""
 import numpy as np
 import pytest
 
@@ -56,6 +57,7 @@ def test_fuzz(gpu, algo, seed, max_lens=(70, 140, 300)):
         sb = random_batch(rng, 24, max_lens[(wi + seed) % 3], alphabet)
         band = int(rng.integers(1, 80))
         code = {"LNW": gpu.ALGO_LNW, "LSW": gpu.ALGO_LSW, "ANW": gpu.ALGO_ANW, "BSW": gpu.ALGO_BSW}[algo]
+        want = []   # the oracle's (score, end row, end column) of every pair, for the score-only batch below
         with gpu.Batch(code, sb.sequences, sb.pairs, w[0], w[1], w[2], w[3], band=band if algo == "BSW" else 0) as b:
             b.fill()
             sc, er, ec = b.results()
@@ -66,15 +68,27 @@ def test_fuzz(gpu, algo, seed, max_lens=(70, 140, 300)):
                     o = O.lsw(refs, qry, w[0], w[1], w[2], band=band if algo == "BSW" else 0)
                     assert (sc[p], er[p], ec[p]) == (o.score, o.end_row, o.end_col), tag
                     lines = ("", "", "") if o.score == 0 else O.lsw_traceback(refs, qry, o)
+                    want.append((o.score, o.end_row, o.end_col))
                 elif algo == "LNW":
                     o = O.lnw(refs, qry, w[0], w[1], w[2])
                     assert sc[p] == o.score, tag
                     lines = O.lnw_traceback(refs, qry, o)
+                    want.append((o.score, len(qry), len(refs)))
                 else:
                     o = O.anw(refs, qry, *w)
                     assert sc[p] == o.score, tag
                     lines = O.anw_traceback(refs, qry, o)
+                    want.append((o.score, len(qry), len(refs)))
                     assert np.array_equal(b.matrix(p, gpu.MAT_I).astype(np.int32), o.I), tag
                     assert np.array_equal(b.matrix(p, gpu.MAT_D).astype(np.int32), o.D), tag
                 assert np.array_equal(b.matrix(p).astype(np.int32), o.H), tag
                 assert b.traceback(p) == lines, tag
+        # the STORE = false instantiation of the same kernels over the same inputs (under DPX_LANES=1: the lane kernels), against the oracle
+        # results above: masked rows under a positive gap, mismatch above match, all 256 byte values
+        with gpu.Batch(code, sb.sequences, sb.pairs, w[0], w[1], w[2], w[3], band=band if algo == "BSW" else 0, flags=gpu.SCORE_ONLY) as b:
+            assert b.describe()["store"] == 0
+            b.fill()
+            sc, er, ec = b.results()
+            got = list(zip(sc.tolist(), er.tolist(), ec.tolist()))
+            bad = [(p, got[p], want[p]) for p in range(sb.num_pairs) if got[p] != want[p]]
+            assert not bad, (algo, seed, w, "score-only: pair, got, want", bad[:6], len(bad))

@@ -11,7 +11,9 @@ asserted from dpx_batch_describe; each runs under all six layouts (the direction
 both walks where DPX_TB_WALK chooses one, and everything the batch reports -- results, extension records, every plane of every pair (of
 every fifth pair in the 40-pair batches of the kernels that pack several pairs into a wave), every traceback, the text and its offsets,
 the CIGAR records and ops under both flags -- must equal the oracle bit for bit.  The oracle's answer depends on the texts alone and is
-computed once per case; no GPU batch is compared with another.  tests/test_layouts.py shows on the oracle alone that the `embedded`
+computed once per case; no GPU batch is compared with another.  The DPX_SCORE_ONLY cases (every route such a batch can take) share the
+want() of their storing siblings and go through tests/test_gpu_score_only.py's comparator; the table twins of ANW / ASW / ASG run an
+asymmetric five-letter table whose map folds the layouts' fillers and flanks onto N.  tests/test_layouts.py shows on the oracle alone that the `embedded`
 layout is not vacuous (the flanks change every case's answer) and that the planner decides the same for every layout.
 
 Then dpx_batch_set_reversed on a rebased window and on pairs that share bytes (BANW and BAXT as matrix, band-direction and two-piece
@@ -23,6 +25,7 @@ import pytest
 import layout_cases as L
 from layouts import lay
 from test_gpu_poison import _read_and_compare
+from test_gpu_score_only import _score_only
 
 pytestmark = pytest.mark.gpu
 
@@ -48,7 +51,9 @@ def _environment(monkeypatch, case, walk="default"):
 
 def _ran(case, d, walk="default"):
     assert d["algo"] == case.algo and d["kernel"] == case.kernel, d
-    assert all(d[k] == v for k, v in case.describe.items()), d
+    assert all(d.get(k) == v for k, v in case.describe.items()), d
+    if case.storage == "score":
+        assert d["store"] == 0 and (d["waves"] > 0) == case.kernel.endswith("_lanes"), d
     if "traceback" in d and case.walks == L.BOTH:
         assert d["traceback"].endswith("_wave") == (walk == "default"), d
 
@@ -65,16 +70,35 @@ def test_every_kernel_under_every_layout(gpu, oracles, monkeypatch, case, layout
         _ran(case, d, walk)
         assert d["seq_input"] == "bytes" and b.num_pairs == len(texts)
         b.fill()
-        _read_and_compare(gpu, b, want, case.dirs, True if case.scan else None, (case.id, layout, walk), picks=range(0, len(texts), case.every))
+        if case.storage == "score":
+            _score_only(b, want, (case.id, layout))
+        else:
+            _read_and_compare(gpu, b, want, case.dirs, True if case.scan else None, (case.id, layout, walk), picks=range(0, len(texts), case.every))
+
+
+SCORE_ONLY_ROUTES = {"k_linear_fill", "k_linear_lanes", "k_affine_fill", "k_asw_fill", "k_asg_fill", "k_affine_lanes", "k_asw_lanes", "k_asg_lanes",
+                     "k_banded_fill", "k_basw_fill", "k_banw_fill", "k_baxt_fill", "k_zext_fill", "k_subst_fill", "k_zsub_fill"}
+SCORE_TABLE_ROUTES = {"k_affine_fill", "k_asw_fill", "k_asg_fill", "k_affine_lanes", "k_asw_lanes", "k_asg_lanes"}
+DIRECTION_TABLE_ROUTES = {"k_affine_dir", "k_asw_dir", "k_asg_dir"}
 
 
 def test_what_the_table_above_exercised():
     """all 27 fill kernels, both walks where there is a choice, the reversed setter in three storage modes and packed2 on three routes,
-    each under layouts other than the canonical one"""
-    ran = {}
+    each under layouts other than the canonical one; every (kernel, storage, table or not) combination -- the score-only routes and the
+    table twins launch under the storing kernels' names -- under at least `residues` and `embedded`"""
+    ran, combos = {}, {}
     for p in PARAMS:
         case, layout, walk = p.values
         ran.setdefault(case.kernel, set()).add((layout, walk))
+        combos.setdefault((case.kernel, case.storage, case.table), set()).add(layout)
+    for combo, seen in combos.items():
+        assert {"residues", "embedded"} <= seen, combo
+    assert {k for k, storage, table in combos if storage == "score" and not table} == SCORE_ONLY_ROUTES
+    assert {k for k, storage, table in combos if storage == "score" and table} == SCORE_TABLE_ROUTES
+    assert {k for k, storage, table in combos if storage == "dirs" and table} == DIRECTION_TABLE_ROUTES
+    assert {c.band for c in L.CASES if c.storage == "score" and c.band} == set(L.BANDS)
+    for kernel in DIRECTION_TABLE_ROUTES:   # the global edge rows under the table too, under the three layouts of the plain ones
+        assert any(c.kernel == kernel and c.table and c.describe["dir_edges"] == "global" and c.layouts == ("canonical", "residues", "embedded") for c in L.CASES)
     assert set(ran) == L.KERNELS and len(ran) == 27
     for kernel, seen in ran.items():
         assert {"residues", "embedded"} <= {layout for layout, _ in seen}, kernel

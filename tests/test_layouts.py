@@ -125,8 +125,18 @@ def test_the_case_table_names_every_fill_kernel():
     for c in L.CASES:
         assert set(c.layouts) - {"canonical"} and c.layouts[0] == "canonical", c.id
         assert c.walks == (L.BOTH if c.storage == "mat" else ("default",)), c.id
-        assert 16 <= len(L.texts_of(c)) <= 20 or c.texts in (L.ragged40_texts, L.ragged_couples_texts, L.global_edge_texts), c.id
+        assert 16 <= len(L.texts_of(c)) <= 20 or c.texts in (L.ragged40_texts, L.ragged40_acgt_texts, L.ragged_couples_texts, L.global_edge_texts), c.id
     assert {c.band for c in L.CASES if c.band} == set(L.BANDS)
+    for c in L.CASES:   # a score-only case runs its sibling's algorithm, weights, band, mode and texts: want() is shared
+        if c.storage == "score" and not c.table:
+            s = L.BY_ID[c.sibling]
+            assert s.storage == "mat" and (c.algo, c.kernel, c.w, c.band, c.mode, c.texts, c.texts_args) == (s.algo, s.kernel, s.w, s.band, s.mode, s.texts, s.texts_args), c.id
+        if c.table:
+            assert c.algo in ("ANW", "ASW", "ASG") and c.storage in ("score", "dirs") and c.describe["subst"] == 5, c.id
+            if c.sibling:
+                s = L.BY_ID[c.sibling]
+                assert s.table and (c.algo, c.w, c.texts, c.texts_args) == (s.algo, s.w, s.texts, s.texts_args), c.id
+    assert not np.array_equal(L.TABLE, L.TABLE.T) and set(L.CODE[k] for k in range(256) if k not in b"ACGTacgt") == {4}   # asymmetric; every other byte is N
 
 
 @pytest.fixture(scope="module")
@@ -149,7 +159,8 @@ def test_the_plan_does_not_depend_on_the_layout(tool, case):
     for walk in case.walks:
         control, fields = _plan(tool, L.plan_tool_input(case, lay("canonical", texts), walk=walk))
         assert control.startswith("status=0 ") and fields["kernel"] == case.kernel and fields["algo"] == case.algo, control
-        assert all(fields.get(k) == v for k, v in case.describe.items()), control
+        assert all(fields.get(k) == str(v) for k, v in case.describe.items()), control
+        assert fields["store"] == ("0" if case.storage == "score" else "1"), control
         if "traceback" in fields and case.walks == L.BOTH:
             assert fields["traceback"].endswith("_wave") == (walk == "default"), control
         states = {fields["state"]}
@@ -179,6 +190,9 @@ def oracles(tmp_path_factory):
     return L.build_oracles(tmp_path_factory.mktemp("layout_oracles"))
 
 
+_OUTER = {}
+
+
 @pytest.mark.parametrize("case", L.CASES, ids=lambda c: c.id)
 def test_embedded_flanks_change_the_answer(oracles, case):
     """had a kernel read the flanks as part of the strings it would report the outer strings' result: on the oracle, at least one pair's
@@ -187,7 +201,10 @@ def test_embedded_flanks_change_the_answer(oracles, case):
     texts = L.texts_of(case)
     laid = lay("embedded", texts)
     inner = L.want(oracles, case)
-    outer = [L.expect(oracles, case, *laid.outer(p)) for p in range(len(texts))]
+    key = L.want_key(case)   # (a score-only case and its sibling: one oracle, one answer)
+    if key not in _OUTER:
+        _OUTER[key] = [L.expect(oracles, case, *laid.outer(p)) for p in range(len(texts))]
+    outer = _OUTER[key]
     F = layouts.FLANK
     assert any(a["score"] != b["score"] for a, b in zip(inner, outer)), case.id
     if case.algo in L.LOCAL_OR_EXTENSION:
