@@ -13,6 +13,7 @@
 #include "dpx_fill_common.hpp"
 #include "dpx_kernels.h"
 #include "dpx_prims.hpp"
+#include "dpx_table_dev.hpp"
 
 namespace dpx_affine {
 
@@ -20,6 +21,8 @@ using dpx::wave_shr1;
 using dpx_dev::wave_max_u64;
 using dpx_fill::ramp_stores;
 using dpx_fill::store_tile;
+using dpx_table::table_stage;
+using dpx_table::table_translate;
 
 /* =====================================================================================================
  * Affine-gap (Gotoh) global fill: AffineNeedlemanWunsch (c++/AffineNeedlemanWunsch.cpp:167-240).
@@ -32,31 +35,10 @@ using dpx_fill::store_tile;
  * as in k_linear_fill (per-row (H << 16 | 0xFFFF - j) keys folded per stripe, one wave reduction at the end).
  * ===================================================================================================== */
 /* ---- the substitution table in LDS (TABLE kernels) ----
- * The image of dpx_kernels.h (1 KiB of int8 at row stride 32, row = reference code, then the 256-byte map; both 16-byte aligned in one
- * device allocation) goes into `img`, DPX_SUBST_IMAGE_BYTES of the calling wave's LDS, by all 64 lanes: the table TRANSPOSED, the map
- * behind it as it is.  A lane's row bases are then formed once per stripe and a cell's address is one add of the staged reference code,
- * no shift per step.  Returns the map.  Pointers into LDS are kept in the LDS address space, where they are 32-bit offsets. */
+ * table_stage() and table_translate() are dpx_table_dev.hpp's.  Pointers into LDS are kept in the LDS address space, where they are
+ * 32-bit offsets. */
 typedef __attribute__((address_space(3))) signed char lds_i8;
 
-__device__ __forceinline__ const unsigned char *table_stage(unsigned char *img, const int8_t *tableG, const unsigned char *codeOfG, const int lane) {
-    const dpx_dev::u32x4 v = reinterpret_cast<const dpx_dev::u32x4 *>(tableG)[lane]; /* row lane / 2, columns 16 * (lane & 1) ... */
-    unsigned char *col = img + (lane >> 1) + ((lane & 1) << 9);
-#pragma unroll
-    for (int k = 0; k < 16; k++) col[k << 5] = (unsigned char)(v[k >> 2] >> (8 * (k & 3)));
-    if (lane < 16) reinterpret_cast<dpx_dev::u32x4 *>(img + DPX_SUBST_TABLE_BYTES)[lane] = reinterpret_cast<const dpx_dev::u32x4 *>(codeOfG)[lane];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-    return img + DPX_SUBST_TABLE_BYTES;
-}
-/* a staged string of n bytes becomes codes in place, by the G lanes that share it (l = the calling lane's index among them): a lane
- * translates bytes that other lanes staged */
-__device__ __forceinline__ void table_translate(unsigned char *s, const int n, const int l, const int G, const unsigned char *codeL) {
-    for (int x = l; x < n; x += G) s[x] = codeL[s[x]];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-}
 /* the LDS address of query byte q's column of the transposed table (rows past the query's end arrive as 0x100: some code, never read back) */
 __device__ __forceinline__ int table_column(unsigned char *img, const unsigned char *codeL, const int q) {
     return (int)reinterpret_cast<uintptr_t>((lds_i8 *)img) + ((int)codeL[q & 0xFF] << 5);

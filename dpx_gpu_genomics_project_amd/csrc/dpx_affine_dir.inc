@@ -1,8 +1,8 @@
 /* dpx_affine_dir.inc -- body of the affine-gap direction fills, included by dpx_dir_kernels.hip inside k_affine_dir (ANW, LOCAL = false)
  * k_asw_dir (ASW, LOCAL = true) and k_asg_dir (ASG, SEMI = true), for the reason given in dpx_affine_fill.inc, and by
- * dpx_dirtab_kernels.hip inside k_dirtab_fill (TABLE = true: the diagonal term is tableG[codeOfG[reference byte] * 32 + codeOfG[query
- * byte]], dpx_batch_set_direction_table).  In scope: `a`, R, GLOBAL, LOCAL, SEMI, TABLE and the two global pointers tableG / codeOfG
- * (null constants where TABLE is false: nothing of the table survives in those kernels). */
+ * dpx_dirtab_kernels.hip inside k_dirtab_fill (TABLE = true: the diagonal term is table[codeOf[reference byte] * 32 + codeOf[query
+ * byte]], dpx_batch_set_direction_table).  In scope: `a`, R, GLOBAL, LOCAL, SEMI, TABLE and the table's dpx_table_ref `tref` (null constants
+ * where TABLE is false: nothing of the table survives in those kernels). */
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int G = 32 / R;
     const int lane = threadIdx.x & 63;
@@ -36,25 +36,17 @@
     for (int x = lane; x <= n + 1; x += 64) { edgeH[x] = (LOCAL || SEMI) ? 0 : o + x * e; edgeD[x] = DPX_NEG; } /* H[0][j] (:50-53; ASW / ASG 0), virtual D[0][j] */
     [[maybe_unused]] const signed char *tabL = nullptr;
     [[maybe_unused]] const unsigned char *codeL = nullptr;
-    if constexpr (TABLE) { /* the wave's own table image (dpx_kernels.h: rows of 32, the map behind them; both arrays 16-byte aligned in one
-                            * device allocation) behind its LDS slice, or -- GLOBAL -- the only thing it keeps in LDS */
+    if constexpr (TABLE) { /* the wave's own table image (dpx_table_dev.hpp) behind its LDS slice, or -- GLOBAL -- the only thing it keeps in LDS */
         unsigned char *img = GLOBAL ? smem + (size_t)wv * DPX_SUBST_IMAGE_BYTES : my + (a.ldsPerWave - (uint32_t)DPX_SUBST_IMAGE_BYTES);
-        reinterpret_cast<u32x4 *>(img)[lane] = reinterpret_cast<const u32x4 *>(tableG)[lane];
-        if (lane < 16) reinterpret_cast<u32x4 *>(img + DPX_SUBST_TABLE_BYTES)[lane] = reinterpret_cast<const u32x4 *>(codeOfG)[lane];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
         tabL = reinterpret_cast<const signed char *>(img);
-        codeL = img + DPX_SUBST_TABLE_BYTES;
+        codeL = table_stage_rows(img, tref, lane);
         /* the staged reference becomes codes, once (the walk and the export read the caller's bytes from a.seq, never the stage) */
         unsigned char *sref = const_cast<unsigned char *>(refl) + 64;
+        /* table_translate's loop, written out: the stage is in global memory when GLOBAL, and through the call the nine LDS instantiations
+         * compile to other operand orders in their cell loop */
         if constexpr (GLOBAL) __threadfence_block(); /* (a lane translates bytes that other lanes staged) */
         for (int x = lane; x < n; x += 64) sref[x] = codeL[sref[x]];
-        if constexpr (!GLOBAL) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-        }
+        if constexpr (!GLOBAL) dpx_table::wave_publish_lds();
     }
     if constexpr (GLOBAL) __threadfence_block();
 

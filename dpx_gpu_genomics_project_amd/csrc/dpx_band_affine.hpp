@@ -47,6 +47,7 @@
 #include "dpx_kernels.h"
 #include "dpx_layout.h"
 #include "dpx_prims.hpp"
+#include "dpx_table_dev.hpp"
 
 namespace dpx_band {
 
@@ -63,6 +64,7 @@ using dpx_dev::stage_bytes;
 using dpx_dev::store8;
 using dpx_dev::u32x4;
 using dpx_dev::wave_max_u64;
+using dpx_table::table_stage_rows;
 
 /* (score, min row, min column) as one unsigned key; score > 0 */
 __device__ __forceinline__ unsigned long long end_key(const int hv, const int i, const int j) {
@@ -547,7 +549,8 @@ __device__ __forceinline__ void band_walk_wave(const dpx_fill_args &a, Scorer sc
     const int p = blockIdx.x;
     const int lane = threadIdx.x;
     if (p >= numPairs) return;
-    if constexpr (Scorer::kTable) /* 64 x 16 B = the 1-KiB table, behind the window; load_window's fences order it before the first read */
+    if constexpr (Scorer::kTable) /* 64 x 16 B = the 1-KiB table, behind the window; load_window's fences order it before the first read.
+                                   * Not table_stage_rows: that copies the map too, and the walk's LDS holds kBytes + the table alone */
         reinterpret_cast<u32x4 *>(smemTb + BandWin::kBytes)[lane] = reinterpret_cast<const u32x4 *>(tableSrc)[lane];
     const dpx_pair_dev pr = a.pairs[p];
     const int n = pr.n, m = pr.m, B = a.band;

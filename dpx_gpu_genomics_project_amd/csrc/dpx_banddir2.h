@@ -45,14 +45,12 @@ DPX_HD uint64_t dpx_banddir2_byte(int i, int j, int band, uint64_t chunkStrideBy
 #if defined(__HIPCC__) /* the launchers (the layout above is plain C) */
 #include "dpx_kernels.h"
 
-/* k_bd2_fill: dpx_bdx_args' fields and meaning (table / codeOf both NULL: byte compare; zdrop / endBonus both -1: no scan, `ext` batches
- * only) plus the second gap piece; piece 1 is f.gapOpen / f.gapExtend.  Every mode is legal, "nothing on" included. */
+/* k_bd2_fill: dpx_bdx_args' fields and meaning (`tab`, both pointers NULL: byte compare; `scan`, zdrop / endBonus both -1: no scan, `ext`
+ * batches only) plus the second gap piece; piece 1 is f.gapOpen / f.gapExtend.  Every mode is legal, "nothing on" included. */
 typedef struct dpx_bd2_args {
     dpx_fill_args f;
-    const int8_t *table;
-    const uint8_t *codeOf;
-    int32_t zdrop, endBonus;
-    int32_t *ext;
+    dpx_table_ref tab;
+    dpx_ext_ref scan;
     int32_t gapOpen2, gapExtend2;
 } dpx_bd2_args;
 hipError_t dpx_launch_bd2_fill(const dpx_bd2_args &a, int C, bool ext, hipStream_t stream);

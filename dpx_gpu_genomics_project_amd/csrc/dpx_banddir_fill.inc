@@ -45,7 +45,7 @@
     if (m <= 0 || n <= 0) { /* an empty sequence: no cell has a code and no diagonal step runs, so a table plays no part */
         if (lane == 0) {
             if constexpr (SCAN > 0) {
-                scan_border_line<SCAN == 2>(a, x.endBonus, x.ext, p, m, n, B, bord, Z, pen);
+                scan_border_line<SCAN == 2>(a, x.scan.endBonus, x.scan.ext, p, m, n, B, bord, Z, pen);
             } else if constexpr (EXT) { /* the first maximum of the one border line, when it is above the 0 of (0, 0) */
                 const int L = min(max(max(m, n), 0), B - 1);
                 const int k = line_first_max(L);
@@ -70,15 +70,10 @@
     const unsigned char *rL = stage_bytes(my + a.ldsRefOff, ref, n, lane, 64);
     [[maybe_unused]] const signed char *tabL = nullptr;
     [[maybe_unused]] const unsigned char *codeL = nullptr;
-    if constexpr (TABLE) { /* (both arrays are 16-byte aligned: the host keeps them in one device allocation, the map behind the table) */
+    if constexpr (TABLE) {
         unsigned char *img = my + (a.ldsPerWave - (uint32_t)DPX_SUBST_IMAGE_BYTES);
-        reinterpret_cast<u32x4 *>(img)[lane] = reinterpret_cast<const u32x4 *>(x.table)[lane];
-        if (lane < 16) reinterpret_cast<u32x4 *>(img + DPX_SUBST_TABLE_BYTES)[lane] = reinterpret_cast<const u32x4 *>(x.codeOf)[lane];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+        codeL = table_stage_rows(img, x.tab, lane);
         tabL = reinterpret_cast<const signed char *>(img);
-        codeL = img + DPX_SUBST_TABLE_BYTES;
     }
 
     State st;
@@ -193,7 +188,7 @@
         if (lane == 0) {
             const int maxRow = hv > 0 ? (int)(at >> 32) : 0, maxCol = hv > 0 ? (int)(at & 0xFFFFFFFFull) : 0;
             if constexpr (SCAN > 0) {
-                write_results(a, x.endBonus, x.ext, p, m, max(hv, 0), maxRow, maxCol, qeCol >= 0 ? qeScore : INT_MIN, qeCol, lastDiag, stop);
+                write_results(a, x.scan.endBonus, x.scan.ext, p, m, max(hv, 0), maxRow, maxCol, qeCol >= 0 ? qeScore : INT_MIN, qeCol, lastDiag, stop);
             } else {
                 a.score[p] = hv;
                 a.endRow[p] = maxRow;

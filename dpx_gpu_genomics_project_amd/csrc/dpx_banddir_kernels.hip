@@ -147,7 +147,7 @@ template <int C, bool PB, bool EXT>
 __global__ void __launch_bounds__(DPX_FILL_THREADS) k_bdir_fill(const dpx_fill_args f) {
     constexpr bool TABLE = false;
     constexpr int SCAN = 0;
-    const dpx_bdx_args x = {f, nullptr, nullptr, -1, -1, nullptr}; /* (the frame's names; nothing of it but x.f is read) */
+    const dpx_bdx_args x = {f, {nullptr, nullptr}, {-1, -1, nullptr}}; /* (the frame's names; nothing of it but x.f is read) */
     const dpx_fill_args &a = x.f;
     using State = BdirState<C, EXT>;
     constexpr int Gd = 32 / C, kStepBits = 4 * C; /* steps per 16-byte store (a multiple of 4); a nibble per cell */

@@ -171,7 +171,7 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_bd2_fill(const dpx_bd2_arg
 #define DPX_BANDDIR_WEIGHTS                                                                                                          \
     const int match = a.match, mismatch = a.mismatch;                                                                                \
     const Bd2Gaps g = {a.gapOpen + a.gapExtend, a.gapExtend, x.gapOpen2 + x.gapExtend2, x.gapExtend2, a.gapOpen, x.gapOpen2};        \
-    const int Z = x.zdrop, pen = max(0, -max(g.e1, g.e2));                                                                           \
+    const int Z = x.scan.zdrop, pen = max(0, -max(g.e1, g.e2));                                                                           \
     const int bord1 = gap_of(g, 1);                                                                                                  \
     auto bord = [g](const int k) -> int { return gap_of(g, k); };                                                                    \
     auto line_first_max = [g, bord1](const int L) -> int { return (L >= 1 && bord1 >= gap_of(g, L)) ? 1 : L; };
@@ -199,9 +199,9 @@ __global__ void __launch_bounds__(256) k_bd2_export(const unsigned char *codes, 
 
 hipError_t dpx_launch_bd2_fill(const dpx_bd2_args &x, int C, bool ext, hipStream_t stream) {
     if (x.f.numPairs <= 0) return hipSuccess;
-    const bool table = x.table != nullptr;
-    const int scan = !ext ? 0 : x.zdrop >= 0 ? 2 : x.endBonus >= 0 ? 1 : 0;
-    if ((table && !x.codeOf) || (scan && !x.ext) || x.f.band > DPX_BANDDIR2_MAX_BAND || C != dpx_band_cpl(x.f.band)) return hipErrorInvalidValue;
+    const bool table = x.tab.table != nullptr;
+    const int scan = !ext ? 0 : x.scan.zdrop >= 0 ? 2 : x.scan.endBonus >= 0 ? 1 : 0;
+    if ((table && !x.tab.codeOf) || (scan && !x.scan.ext) || x.f.band > DPX_BANDDIR2_MAX_BAND || C != dpx_band_cpl(x.f.band)) return hipErrorInvalidValue;
     const bool pb = ((x.f.band + 1) & 1) != 0; /* parity of step A = 0 */
     return dpx_dev::dispatch_int<1, 2, 4>(C, [&](auto c) {
         return dpx_dev::dispatch_bool(pb, [&](auto pbc) {

@@ -160,7 +160,7 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_bdx_fill(const dpx_bdx_arg
     /* (the border line is linear in k: its first maximum is at k = L when e > 0 and at k = 1 otherwise) */
 #define DPX_BANDDIR_WEIGHTS                                                                                              \
     const int match = a.match, mismatch = a.mismatch, o = a.gapOpen, e = a.gapExtend, oe = a.gapOpen + a.gapExtend;      \
-    const int Z = x.zdrop, pen = e < 0 ? -e : 0;                                                                         \
+    const int Z = x.scan.zdrop, pen = e < 0 ? -e : 0;                                                                         \
     const int bord1 = oe;                                                                                                \
     auto bord = [o, e](const int k) -> int { return o + k * e; };                                                        \
     auto line_first_max = [e](const int L) -> int { return e > 0 ? L : min(L, 1); };
@@ -177,9 +177,9 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_bdx_fill(const dpx_bdx_arg
 
 hipError_t dpx_launch_bdx_fill(const dpx_bdx_args &x, int C, bool ext, hipStream_t stream) {
     if (x.f.numPairs <= 0) return hipSuccess;
-    const bool table = x.table != nullptr;
-    const int scan = !ext ? 0 : x.zdrop >= 0 ? 2 : x.endBonus >= 0 ? 1 : 0;
-    if ((table && !x.codeOf) || (scan && !x.ext) || (!table && !scan)) return hipErrorInvalidValue;
+    const bool table = x.tab.table != nullptr;
+    const int scan = !ext ? 0 : x.scan.zdrop >= 0 ? 2 : x.scan.endBonus >= 0 ? 1 : 0;
+    if ((table && !x.tab.codeOf) || (scan && !x.scan.ext) || (!table && !scan)) return hipErrorInvalidValue;
     return dispatch_fill(C, x.f.band, table, [&](auto c, auto pb, auto tb) {
         constexpr int kC = decltype(c)::value;
         constexpr bool kPB = decltype(pb)::value, kTable = decltype(tb)::value;

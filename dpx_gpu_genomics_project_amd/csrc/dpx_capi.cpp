@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -523,7 +524,7 @@ struct dpx_batch : dpx_plan {
     int substAlphabet = 0;
     unsigned char *dSubst = nullptr; /* device: the table at row stride 32 (DPX_SUBST_TABLE_BYTES), then codeOf[256] */
     size_t dSubstCap = 0;
-    std::vector<unsigned char> bdxImage; /* dpx_batch_set_direction_scoring / _set_direction_table / _set_score_table: the image dSubst holds, to tell a changed table from the same one */
+    std::vector<unsigned char> tableImage; /* the image dSubst holds while substAlphabet != 0 (every table setter keeps it, every clear drops it) */
     /* orientation (dpx_batch_set_reversed): while revCount > 0 dSeq points at dRev, the setter's own allocation -- [the arena's sequence
      * bytes][reversed copies of the flagged pairs' strings][the kernel's job list][the flagged pairs' numbers] -- and the flagged pairs'
      * indices in `pairs` / dPairs at the copies.  The fills, walks and exports know nothing of it. */
@@ -1083,9 +1084,12 @@ static void mark_filled(dpx_batch *b, const dpx_route &r, hipStream_t s) {
     b->filled = true; b->extFilled = r.extRecords; b->lastStream = s;
 }
 
+/* the batch's table on the device (dpx_kernels.h: the map behind the table, one allocation) */
+static dpx_table_ref table_ref(const dpx_batch *b) { return {reinterpret_cast<const int8_t *>(b->dSubst), b->dSubst + DPX_SUBST_TABLE_BYTES}; }
+
 /* the batch's launch arguments under its substitution table: every wave's LDS slice grows by the table image */
 static dpx_subst_args subst_args(const dpx_batch *b) {
-    dpx_subst_args sa = {b->args, reinterpret_cast<const int8_t *>(b->dSubst), b->dSubst + DPX_SUBST_TABLE_BYTES};
+    dpx_subst_args sa = {b->args, table_ref(b)};
     sa.f.ldsPerWave += DPX_SUBST_IMAGE_BYTES;
     return sa;
 }
@@ -1096,7 +1100,7 @@ static hipError_t launch_main(dpx_batch *b, const dpx_route &r, hipStream_t s) {
     case DPX_MAIN_NONE: return hipSuccess;
     case DPX_MAIN_FILL:
         if (r.scoreTable) { /* (dpx_batch_set_score_table: every wave's LDS slice grows by the image; the workgroup may shrink to one wave) */
-            dpx_scoretab_args ta = {b->args, reinterpret_cast<const int8_t *>(b->dSubst), b->dSubst + DPX_SUBST_TABLE_BYTES};
+            dpx_subst_args ta = {b->args, table_ref(b)};
             ta.f.ldsPerWave = (uint32_t)dpx_plan_scoretab_lds(*b); ta.f.wavesPerBlock = dpx_plan_scoretab_waves(*b);
             return dpx_launch_scoretab_fill(ta, b->kernelAlgo, b->R, s);
         }
@@ -1105,28 +1109,28 @@ static hipError_t launch_main(dpx_batch *b, const dpx_route &r, hipStream_t s) {
     case DPX_MAIN_BANW: return dpx_launch_banw_fill(b->args, b->R, b->store, b->ldsBytes, s);
     case DPX_MAIN_BAXT: return dpx_launch_baxt_fill(b->args, b->R, b->store, b->ldsBytes, s);
     case DPX_MAIN_ZEXT: {
-        const dpx_zext_args za = {b->args, b->zdrop, b->endBonus, b->dExt};
+        const dpx_zext_args za = {b->args, {b->zdrop, b->endBonus, b->dExt}};
         return dpx_launch_zext_fill(za, b->R, b->store, b->ldsBytes, s);
     }
     case DPX_MAIN_SUBST: return dpx_launch_subst_fill(subst_args(b), b->R, b->store, r.ext, subst_lds_bytes(b), s);
     case DPX_MAIN_ZSUB: {
-        const dpx_zsub_args za = {subst_args(b), b->zdrop, b->endBonus, b->dExt};
+        const dpx_zsub_args za = {subst_args(b), {b->zdrop, b->endBonus, b->dExt}};
         return dpx_launch_zsub_fill(za, b->R, b->store, subst_lds_bytes(b), s);
     }
     case DPX_MAIN_BDIR: return dpx_launch_bdir_fill(b->args, b->R, r.ext, s);
     case DPX_MAIN_BDL: return dpx_launch_bdl_fill(b->args, b->R, b->prm.algo == DPX_ALGO_BASW, s);
     case DPX_MAIN_BDX: { /* (dpx_batch_set_direction_scoring: with a table every wave's LDS slice grows by the image, and the workgroup may shrink to one wave) */
-        dpx_bdx_args xa = {b->args, nullptr, nullptr, r.ext ? b->zdrop : -1, r.ext ? b->endBonus : -1, b->dExt};
+        dpx_bdx_args xa = {b->args, {nullptr, nullptr}, {r.ext ? b->zdrop : -1, r.ext ? b->endBonus : -1, b->dExt}};
         if (b->substAlphabet) {
-            xa.table = reinterpret_cast<const int8_t *>(b->dSubst); xa.codeOf = b->dSubst + DPX_SUBST_TABLE_BYTES;
+            xa.tab = table_ref(b);
             xa.f.ldsPerWave += DPX_SUBST_IMAGE_BYTES; xa.f.wavesPerBlock = dpx_plan_bdx_waves(*b, true);
         }
         return dpx_launch_bdx_fill(xa, b->R, r.ext, s);
     }
     case DPX_MAIN_BD2: { /* (a two-piece batch: every mode, "nothing on" included, is k_bd2_fill's; the table's LDS as for k_bdx_fill) */
-        dpx_bd2_args xa = {b->args, nullptr, nullptr, r.ext ? b->zdrop : -1, r.ext ? b->endBonus : -1, b->dExt, b->gapOpen2, b->gapExtend2};
+        dpx_bd2_args xa = {b->args, {nullptr, nullptr}, {r.ext ? b->zdrop : -1, r.ext ? b->endBonus : -1, b->dExt}, b->gapOpen2, b->gapExtend2};
         if (b->substAlphabet) {
-            xa.table = reinterpret_cast<const int8_t *>(b->dSubst); xa.codeOf = b->dSubst + DPX_SUBST_TABLE_BYTES;
+            xa.tab = table_ref(b);
             xa.f.ldsPerWave += DPX_SUBST_IMAGE_BYTES; xa.f.wavesPerBlock = dpx_plan_bdx_waves(*b, true);
         }
         return dpx_launch_bd2_fill(xa, b->R, r.ext, s);
@@ -1137,7 +1141,7 @@ static hipError_t launch_main(dpx_batch *b, const dpx_route &r, hipStream_t s) {
 
 static hipError_t launch_all(dpx_batch *b, const dpx_route &r, hipStream_t s) {
     if (r.dirTable) { /* (dpx_batch_set_direction_table: edge rows in LDS, every wave's slice grows by the image; the workgroup may shrink to one wave) */
-        dpx_dirtab_args ta = {b->dirArgs, reinterpret_cast<const int8_t *>(b->dSubst), b->dSubst + DPX_SUBST_TABLE_BYTES};
+        dpx_dirtab_args ta = {b->dirArgs, table_ref(b)};
         if (!ta.d.scratch) ta.d.ldsPerWave += DPX_SUBST_IMAGE_BYTES;
         ta.d.wavesPerBlock = dpx_plan_dirtab_waves(*b);
         return dpx_launch_dirtab_fill(ta, b->kernelAlgo, b->R, s);
@@ -1161,7 +1165,7 @@ static hipError_t launch_all(dpx_batch *b, const dpx_route &r, hipStream_t s) {
     case DPX_SECOND_BANDED_PACKED: e = dpx_launch_banded_packed(b->pkArgs, b->R, b->pkLdsBytes, s); break;
     case DPX_SECOND_LANES:
         if (r.scoreTable) { /* (the image behind the wave's reference area) */
-            dpx_scoretab_args ta = {b->pkArgs, reinterpret_cast<const int8_t *>(b->dSubst), b->dSubst + DPX_SUBST_TABLE_BYTES};
+            dpx_subst_args ta = {b->pkArgs, table_ref(b)};
             ta.f.ldsPerWave = (uint32_t)dpx_plan_scoretab_lanes_lds(*b);
             e = dpx_launch_scoretab_lanes(ta, b->kernelAlgo, b->R, s);
             break;
@@ -1368,89 +1372,32 @@ int dpx_batch_matrix(dpx_batch *b, size_t pair, int which, int16_t *out) {
     return DPX_OK;
 }
 
-int dpx_batch_set_extension(dpx_batch *b, int32_t zdrop, int32_t endBonus) {
-    if (!b || zdrop < -1 || zdrop > (1 << 30) || endBonus < -1 || endBonus > (1 << 30)) return DPX_ERR_INVALID;
-    if (b->prm.algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED;
-    if (b->bandDirs) return DPX_ERR_UNSUPPORTED; /* refused by design (tests pin it): dpx_batch_set_direction_scoring is a band-direction batch's setter */
-    if ((zdrop >= 0 || endBonus >= 0) && b->substAlphabet) return DPX_ERR_UNSUPPORTED; /* (the two go together through dpx_batch_set_extension_table only) */
-    int rc = bind_device(b->device);
-    if (rc != DPX_OK) return rc;
-    if ((zdrop >= 0 || endBonus >= 0) && !b->dExt && b->numPairs)
-        HIP_TRY(g_tbDevCache.take((void **)&b->dExt, b->numPairs * sizeof(dpx_extension), &b->dExtCap));
-    b->zdrop = zdrop;
-    b->endBonus = endBonus;
-    return DPX_OK;
+/* ---- substitution tables and BAXT's extension mode: what the setters below share ----
+ * One copy of every check and of every step that changes the batch.  A setter is its own admission rule, the shared checks in its
+ * documented order, then ensure_ext_records / install_table / clear_table: every check comes before the first change. */
+static bool ext_bounds_ok(int32_t zdrop, int32_t endBonus) { return zdrop >= -1 && zdrop <= (1 << 30) && endBonus >= -1 && endBonus <= (1 << 30); }
+static bool table_args_ok(int32_t alphabet, const uint8_t *codeOf) {
+    if (alphabet < 1 || alphabet > 32 || !codeOf) return false;
+    for (int x = 0; x < 256; x++) if ((int)codeOf[x] >= alphabet) return false;
+    return true;
 }
-
-/* dpx_batch_set_substitution's checks of a table for this batch, all of them: nothing is changed */
-static int check_substitution(const dpx_batch *b, int32_t alphabet, const uint8_t *codeOf) {
-    if (alphabet < 1 || alphabet > 32 || !codeOf) return DPX_ERR_INVALID;
-    for (int x = 0; x < 256; x++) if ((int)codeOf[x] >= alphabet) return DPX_ERR_INVALID;
-    if (b->prm.algo != DPX_ALGO_BANW && b->prm.algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED;
-    if (b->kernelAlgo != b->prm.algo || b->dirs || b->bandDirs) return DPX_ERR_UNSUPPORTED; /* band directions: refused by design, dpx_batch_set_direction_scoring is their setter; a covering BANW band runs as ANW, which has no table kernel */
-    return DPX_OK;
-}
-static int check_substitution_fit(const dpx_batch *b, const int8_t *scores, int32_t alphabet) {
-    if (subst_lds_bytes(b) > 160u * 1024u) return DPX_ERR_UNSUPPORTED; /* the table image no longer fits beside the staged strings */
-    /* fits_int16's BANW / BAXT bounds with the largest entry in place of match and the smallest in place of mismatch */
+/* the batch's parameters with the table's largest entry in place of match and its smallest in place of mismatch; `entries` is the
+ * caller's array (stride = alphabet) or the host image (stride 32) */
+static dpx_params table_extremes(const dpx_batch *b, const void *entries, int32_t alphabet, int32_t stride) {
     dpx_params q = b->prm;
     q.match = -128; q.mismatch = 127;
-    for (int k = 0; k < alphabet * alphabet; k++) { q.match = std::max<int32_t>(q.match, scores[k]); q.mismatch = std::min<int32_t>(q.mismatch, scores[k]); }
-    for (const dpx_pair_dev &pd : b->pairs) if (!fits_int16(q, pd.m, pd.n)) return DPX_ERR_RANGE;
-    return DPX_OK;
+    for (int r = 0; r < alphabet; r++)
+        for (int c = 0; c < alphabet; c++) {
+            const int32_t v = static_cast<const int8_t *>(entries)[r * stride + c];
+            q.match = std::max(q.match, v); q.mismatch = std::min(q.mismatch, v);
+        }
+    return q;
 }
-
-/* the checked table becomes the batch's (the image of dpx_kernels.h: rows of 32, the map behind them) */
-static int upload_substitution(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf) {
-    unsigned char image[DPX_SUBST_IMAGE_BYTES];
-    memset(image, 0, sizeof image);
-    for (int r = 0; r < alphabet; r++) memcpy(image + r * 32, scores + r * alphabet, (size_t)alphabet);
-    memcpy(image + DPX_SUBST_TABLE_BYTES, codeOf, 256);
-    if (!b->dSubst) HIP_TRY(g_tbDevCache.take((void **)&b->dSubst, sizeof image, &b->dSubstCap));
-    /* a fill or a walk in flight may still read the previous table */
-    if (b->lastStream && b->lastStream != b->stream) HIP_TRY(hipStreamSynchronize(b->lastStream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    HIP_TRY(hipMemcpy(b->dSubst, image, sizeof image, hipMemcpyHostToDevice));
-    b->substAlphabet = alphabet;
-    invalidate_fill(b);
-    return DPX_OK;
+/* the range check of the batch's storage mode (`fits`: fits_int16, fits_dir or a two-piece wrapper of it) over every pair */
+static bool pairs_in_range(const dpx_batch *b, const dpx_params &q, const std::function<bool(const dpx_params &, long long, long long)> &fits) {
+    for (const dpx_pair_dev &pd : b->pairs) if (!fits(q, pd.m, pd.n)) return false;
+    return true;
 }
-
-int dpx_batch_set_substitution(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf) {
-    if (!b) return DPX_ERR_INVALID;
-    if (!scores) { /* clear: the batch runs its plain kernel again */
-        if (b->substAlphabet) invalidate_fill(b);
-        b->substAlphabet = 0;
-        return DPX_OK;
-    }
-    int rc = check_substitution(b, alphabet, codeOf);
-    if (rc != DPX_OK) return rc;
-    if (extension_on(b)) return DPX_ERR_UNSUPPORTED;
-    rc = check_substitution_fit(b, scores, alphabet);
-    if (rc != DPX_OK) return rc;
-    rc = bind_device(b->device);
-    if (rc != DPX_OK) return rc;
-    return upload_substitution(b, scores, alphabet, codeOf);
-}
-
-/* both settings at once, the one way to have both: every check of either comes before the first change */
-int dpx_batch_set_extension_table(dpx_batch *b, int32_t zdrop, int32_t endBonus, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf) {
-    if (!b || !scores || !codeOf) return DPX_ERR_INVALID;
-    if (zdrop < -1 || zdrop > (1 << 30) || endBonus < -1 || endBonus > (1 << 30) || (zdrop < 0 && endBonus < 0)) return DPX_ERR_INVALID;
-    int rc = check_substitution(b, alphabet, codeOf); /* (refuses band-direction batches, where neither setting is built) */
-    if (rc == DPX_OK && b->prm.algo != DPX_ALGO_BAXT) rc = DPX_ERR_UNSUPPORTED;
-    if (rc == DPX_OK) rc = check_substitution_fit(b, scores, alphabet);
-    if (rc != DPX_OK) return rc;
-    rc = bind_device(b->device);
-    if (rc != DPX_OK) return rc;
-    if (!b->dExt && b->numPairs) HIP_TRY(g_tbDevCache.take((void **)&b->dExt, b->numPairs * sizeof(dpx_extension), &b->dExtCap));
-    rc = upload_substitution(b, scores, alphabet, codeOf);
-    if (rc != DPX_OK) return rc;
-    b->zdrop = zdrop;
-    b->endBonus = endBonus;
-    return DPX_OK;
-}
-
 /* fits_dir for a band-direction batch under two gap pieces: on their componentwise minimum and again on their componentwise maximum,
  * valid lower and upper bounds of every cell (equal pieces: fits_dir itself) */
 static bool fits_dir_pieces(dpx_params q, int32_t o2, int32_t e2, long long m, long long n) {
@@ -1460,142 +1407,165 @@ static bool fits_dir_pieces(dpx_params q, int32_t o2, int32_t e2, long long m, l
     q.gapOpen = std::max(o1, o2); q.gapExtend = std::max(e1, e2);
     return fits_dir(q, m, n);
 }
+/* the image of dpx_kernels.h: rows of 32, the 256-byte map behind them */
+static void build_table_image(unsigned char (&image)[DPX_SUBST_IMAGE_BYTES], const int8_t *scores, int32_t alphabet, const uint8_t *codeOf) {
+    memset(image, 0, sizeof image);
+    for (int r = 0; r < alphabet; r++) memcpy(image + r * 32, scores + r * alphabet, (size_t)alphabet);
+    memcpy(image + DPX_SUBST_TABLE_BYTES, codeOf, 256);
+}
+/* the batch's device is bound and, with the scan on, its per-pair records exist */
+static int ensure_ext_records(dpx_batch *b, bool scan) {
+    int rc = bind_device(b->device);
+    if (rc != DPX_OK) return rc;
+    if (scan && !b->dExt && b->numPairs) HIP_TRY(g_tbDevCache.take((void **)&b->dExt, b->numPairs * sizeof(dpx_extension), &b->dExtCap));
+    return DPX_OK;
+}
+/* the checked table becomes the batch's, on the device and -- to tell a changed table from the same one, and for
+ * dpx_batch_set_second_gap's range check -- on the host.  keepIfSame: the same table again invalidates nothing. */
+static int install_table(dpx_batch *b, const unsigned char (&image)[DPX_SUBST_IMAGE_BYTES], int32_t alphabet, bool keepIfSame) {
+    if (keepIfSame && b->substAlphabet == alphabet && !memcmp(b->tableImage.data(), image, sizeof image)) return DPX_OK;
+    int rc = bind_device(b->device);
+    if (rc != DPX_OK) return rc;
+    if (!b->dSubst) HIP_TRY(g_tbDevCache.take((void **)&b->dSubst, sizeof image, &b->dSubstCap));
+    /* a fill or a walk in flight may still read the previous table */
+    if (b->lastStream && b->lastStream != b->stream) HIP_TRY(hipStreamSynchronize(b->lastStream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipMemcpy(b->dSubst, image, sizeof image, hipMemcpyHostToDevice));
+    b->tableImage.assign(image, image + sizeof image);
+    b->substAlphabet = alphabet;
+    invalidate_fill(b);
+    return DPX_OK;
+}
+/* scores == NULL: whatever table the batch holds goes, through whichever setter it came (legal on every batch); the batch runs its
+ * plain kernels again */
+static int clear_table(dpx_batch *b) {
+    if (b->substAlphabet) invalidate_fill(b);
+    b->substAlphabet = 0;
+    b->tableImage.clear();
+    return DPX_OK;
+}
 
-/* the second gap piece of a two-piece batch; every check comes before the first change */
+int dpx_batch_set_extension(dpx_batch *b, int32_t zdrop, int32_t endBonus) {
+    if (!b || !ext_bounds_ok(zdrop, endBonus)) return DPX_ERR_INVALID;
+    if (b->prm.algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED;
+    if (b->bandDirs) return DPX_ERR_UNSUPPORTED; /* refused by design (tests pin it): dpx_batch_set_direction_scoring is a band-direction batch's setter */
+    if ((zdrop >= 0 || endBonus >= 0) && b->substAlphabet) return DPX_ERR_UNSUPPORTED; /* (the two go together through dpx_batch_set_extension_table only) */
+    int rc = ensure_ext_records(b, zdrop >= 0 || endBonus >= 0);
+    if (rc != DPX_OK) return rc;
+    b->zdrop = zdrop;
+    b->endBonus = endBonus;
+    return DPX_OK;
+}
+
+/* dpx_batch_set_substitution's and dpx_batch_set_extension_table's batches: BANW / BAXT with matrices or score-only.  Band directions are
+ * refused by design (dpx_batch_set_direction_scoring is their setter); a covering BANW band runs as ANW, which has no table kernel */
+static bool admits_band_table(const dpx_batch *b) {
+    return (b->prm.algo == DPX_ALGO_BANW || b->prm.algo == DPX_ALGO_BAXT) && b->kernelAlgo == b->prm.algo && !b->dirs && !b->bandDirs;
+}
+/* ... and what both check behind it: the image fits beside the staged strings, and fits_int16's BANW / BAXT bounds hold under the table */
+static int check_band_table_fit(const dpx_batch *b, const int8_t *scores, int32_t alphabet) {
+    if (subst_lds_bytes(b) > 160u * 1024u) return DPX_ERR_UNSUPPORTED;
+    return pairs_in_range(b, table_extremes(b, scores, alphabet, alphabet), fits_int16) ? DPX_OK : DPX_ERR_RANGE;
+}
+
+int dpx_batch_set_substitution(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf) {
+    if (!b) return DPX_ERR_INVALID;
+    if (!scores) return clear_table(b);
+    if (!table_args_ok(alphabet, codeOf)) return DPX_ERR_INVALID;
+    if (!admits_band_table(b) || extension_on(b)) return DPX_ERR_UNSUPPORTED;
+    int rc = check_band_table_fit(b, scores, alphabet);
+    if (rc != DPX_OK) return rc;
+    unsigned char image[DPX_SUBST_IMAGE_BYTES];
+    build_table_image(image, scores, alphabet, codeOf);
+    return install_table(b, image, alphabet, false);
+}
+
+/* both settings at once, the one way to have both */
+int dpx_batch_set_extension_table(dpx_batch *b, int32_t zdrop, int32_t endBonus, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf) {
+    if (!b || !scores || !codeOf) return DPX_ERR_INVALID;
+    if (!ext_bounds_ok(zdrop, endBonus) || (zdrop < 0 && endBonus < 0)) return DPX_ERR_INVALID;
+    if (!table_args_ok(alphabet, codeOf)) return DPX_ERR_INVALID;
+    if (!admits_band_table(b) || b->prm.algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED;
+    int rc = check_band_table_fit(b, scores, alphabet);
+    if (rc != DPX_OK) return rc;
+    unsigned char image[DPX_SUBST_IMAGE_BYTES];
+    build_table_image(image, scores, alphabet, codeOf);
+    rc = ensure_ext_records(b, true);
+    if (rc == DPX_OK) rc = install_table(b, image, alphabet, false);
+    if (rc != DPX_OK) return rc;
+    b->zdrop = zdrop;
+    b->endBonus = endBonus;
+    return DPX_OK;
+}
+
+/* the second gap piece of a two-piece batch */
 int dpx_batch_set_second_gap(dpx_batch *b, int32_t gapOpen2, int32_t gapExtend2) {
     if (!b) return DPX_ERR_INVALID;
     if (!b->twoPiece) return DPX_ERR_UNSUPPORTED;
     const int32_t lim = 1 << 20; /* validate_params' rule */
     if (gapOpen2 > lim || gapOpen2 < -lim || gapExtend2 > lim || gapExtend2 < -lim) return DPX_ERR_RANGE;
-    dpx_params q = b->prm;
-    if (b->substAlphabet && b->bdxImage.size() == DPX_SUBST_IMAGE_BYTES) { /* under a table: its largest and smallest entries, as its setter checks */
-        q.match = -128; q.mismatch = 127;
-        for (int r = 0; r < b->substAlphabet; r++)
-            for (int c = 0; c < b->substAlphabet; c++) {
-                const int32_t v = (int8_t)b->bdxImage[(size_t)r * 32 + (size_t)c];
-                q.match = std::max(q.match, v); q.mismatch = std::min(q.mismatch, v);
-            }
-    }
-    for (const dpx_pair_dev &pd : b->pairs) if (!fits_dir_pieces(q, gapOpen2, gapExtend2, pd.m, pd.n)) return DPX_ERR_RANGE;
+    /* under a table: its largest and smallest entries, as its setter checks */
+    const dpx_params q = b->substAlphabet ? table_extremes(b, b->tableImage.data(), b->substAlphabet, 32) : b->prm;
+    if (!pairs_in_range(b, q, [&](const dpx_params &qq, long long m, long long n) { return fits_dir_pieces(qq, gapOpen2, gapExtend2, m, n); })) return DPX_ERR_RANGE;
     if (gapOpen2 != b->gapOpen2 || gapExtend2 != b->gapExtend2) invalidate_fill(b);
     b->gapOpen2 = gapOpen2;
     b->gapExtend2 = gapExtend2;
     return DPX_OK;
 }
 
-/* all scoring of a band-direction batch, the three settings at once; every check comes before the first change */
+/* all scoring of a band-direction batch, the three settings at once */
 int dpx_batch_set_direction_scoring(dpx_batch *b, int32_t zdrop, int32_t endBonus, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf) {
-    if (!b || zdrop < -1 || zdrop > (1 << 30) || endBonus < -1 || endBonus > (1 << 30)) return DPX_ERR_INVALID;
-    if (scores) {
-        if (alphabet < 1 || alphabet > 32 || !codeOf) return DPX_ERR_INVALID;
-        for (int x = 0; x < 256; x++) if ((int)codeOf[x] >= alphabet) return DPX_ERR_INVALID;
-    }
+    if (!b || !ext_bounds_ok(zdrop, endBonus)) return DPX_ERR_INVALID;
+    if (scores && !table_args_ok(alphabet, codeOf)) return DPX_ERR_INVALID;
     if (!b->bandDirs || b->bandLocal) return DPX_ERR_UNSUPPORTED; /* matrix and score-only batches, the other algorithms (BSW / BASW direction batches included), a covering BANW band (k_affine_dir) */
     const bool scan = zdrop >= 0 || endBonus >= 0;
     if (scan && b->prm.algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED;
     unsigned char image[DPX_SUBST_IMAGE_BYTES];
     if (scores) {
         if (!dpx_plan_bdx_waves(*b, true)) return DPX_ERR_UNSUPPORTED; /* one wave's staged strings leave no room in LDS for the table image */
-        /* fits_dir with the largest entry in place of match and the smallest in place of mismatch.  (With int8 entries and strings that
-         * fit LDS this can only refuse a batch that its creation's own check admitted at its very limit.) */
-        dpx_params q = b->prm;
-        q.match = -128; q.mismatch = 127;
-        for (int k = 0; k < alphabet * alphabet; k++) { q.match = std::max<int32_t>(q.match, scores[k]); q.mismatch = std::min<int32_t>(q.mismatch, scores[k]); }
-        for (const dpx_pair_dev &pd : b->pairs) if (!fits_dir_pieces(q, b->twoPiece ? b->gapOpen2 : q.gapOpen, b->twoPiece ? b->gapExtend2 : q.gapExtend, pd.m, pd.n)) return DPX_ERR_RANGE;
-        memset(image, 0, sizeof image);
-        for (int r = 0; r < alphabet; r++) memcpy(image + r * 32, scores + r * alphabet, (size_t)alphabet);
-        memcpy(image + DPX_SUBST_TABLE_BYTES, codeOf, 256);
+        /* fits_dir under the table and the batch's gap pieces.  (With int8 entries and strings that fit LDS this can only refuse a batch
+         * that its creation's own check admitted at its very limit.) */
+        const int32_t o2 = b->twoPiece ? b->gapOpen2 : b->prm.gapOpen, e2 = b->twoPiece ? b->gapExtend2 : b->prm.gapExtend;
+        if (!pairs_in_range(b, table_extremes(b, scores, alphabet, alphabet),
+                            [&](const dpx_params &q, long long m, long long n) { return fits_dir_pieces(q, o2, e2, m, n); })) return DPX_ERR_RANGE;
+        build_table_image(image, scores, alphabet, codeOf);
     }
-    int rc = bind_device(b->device);
+    int rc = ensure_ext_records(b, scan);
+    if (rc == DPX_OK) rc = scores ? install_table(b, image, alphabet, true) : clear_table(b);
     if (rc != DPX_OK) return rc;
-    const bool sameTable = scores ? (b->substAlphabet == alphabet && b->bdxImage.size() == sizeof image && !memcmp(b->bdxImage.data(), image, sizeof image))
-                                  : b->substAlphabet == 0;
-    if (scan && !b->dExt && b->numPairs) HIP_TRY(g_tbDevCache.take((void **)&b->dExt, b->numPairs * sizeof(dpx_extension), &b->dExtCap));
-    if (scores && !sameTable) {
-        if (!b->dSubst) HIP_TRY(g_tbDevCache.take((void **)&b->dSubst, sizeof image, &b->dSubstCap));
-        /* a fill in flight may still read the previous table */
-        if (b->lastStream && b->lastStream != b->stream) HIP_TRY(hipStreamSynchronize(b->lastStream));
-        HIP_TRY(hipStreamSynchronize(b->stream));
-        HIP_TRY(hipMemcpy(b->dSubst, image, sizeof image, hipMemcpyHostToDevice));
-        b->bdxImage.assign(image, image + sizeof image);
-    }
-    if (!sameTable || zdrop != b->zdrop || endBonus != b->endBonus) invalidate_fill(b);
-    b->substAlphabet = scores ? alphabet : 0;
-    if (!scores) b->bdxImage.clear();
+    if (zdrop != b->zdrop || endBonus != b->endBonus) invalidate_fill(b);
     b->zdrop = zdrop;
     b->endBonus = endBonus;
     return DPX_OK;
 }
 
-/* ---- what dpx_batch_set_direction_table and dpx_batch_set_score_table share ----
- * the range check of the batch's storage mode (`fits`: fits_dir or fits_int16) with the table's largest entry in place of match and its
- * smallest in place of mismatch, over every pair */
-static bool table_in_range(const dpx_batch *b, const int8_t *scores, int32_t alphabet, bool (*fits)(const dpx_params &, long long, long long)) {
-    dpx_params q = b->prm;
-    q.match = -128; q.mismatch = 127;
-    for (int k = 0; k < alphabet * alphabet; k++) { q.match = std::max<int32_t>(q.match, scores[k]); q.mismatch = std::min<int32_t>(q.mismatch, scores[k]); }
-    for (const dpx_pair_dev &pd : b->pairs) if (!fits(q, pd.m, pd.n)) return false;
-    return true;
-}
-/* scores == NULL: whatever table the batch holds goes, through whichever setter it came (legal on every batch) */
-static int clear_table_image(dpx_batch *b) {
-    if (b->substAlphabet) invalidate_fill(b);
-    b->substAlphabet = 0;
-    b->bdxImage.clear();
-    return DPX_OK;
-}
-/* the checked table becomes the batch's: the image of dpx_kernels.h (rows of 32, the map behind them), kept on the host too, to tell a
- * changed table from the same one (which invalidates nothing) */
-static int set_table_image(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf) {
-    unsigned char image[DPX_SUBST_IMAGE_BYTES];
-    memset(image, 0, sizeof image);
-    for (int r = 0; r < alphabet; r++) memcpy(image + r * 32, scores + r * alphabet, (size_t)alphabet);
-    memcpy(image + DPX_SUBST_TABLE_BYTES, codeOf, 256);
-    if (b->substAlphabet == alphabet && b->bdxImage.size() == sizeof image && !memcmp(b->bdxImage.data(), image, sizeof image)) return DPX_OK; /* the same table: nothing to invalidate */
-    int rc = bind_device(b->device);
-    if (rc != DPX_OK) return rc;
-    if (!b->dSubst) HIP_TRY(g_tbDevCache.take((void **)&b->dSubst, sizeof image, &b->dSubstCap));
-    /* a fill in flight may still read the previous table */
-    if (b->lastStream && b->lastStream != b->stream) HIP_TRY(hipStreamSynchronize(b->lastStream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    HIP_TRY(hipMemcpy(b->dSubst, image, sizeof image, hipMemcpyHostToDevice));
-    b->bdxImage.assign(image, image + sizeof image);
-    b->substAlphabet = alphabet;
-    invalidate_fill(b);
-    return DPX_OK;
-}
+/* dpx_batch_set_direction_table's and dpx_batch_set_score_table's algorithms: the batch's own, not the kernel's -- a covering BANW / BASW
+ * band that runs the ANW / ASW kernels is not admitted */
+static bool one_of_anw_asw_asg(const dpx_batch *b) { return b->prm.algo == DPX_ALGO_ANW || b->prm.algo == DPX_ALGO_ASW || b->prm.algo == DPX_ALGO_ASG; }
 
-/* the table of an ANW / ASW / ASG direction batch (k_dirtab_fill); every check comes before the first change */
+/* the table of an ANW / ASW / ASG direction batch (k_dirtab_fill) */
 int dpx_batch_set_direction_table(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf) {
     if (!b) return DPX_ERR_INVALID;
-    if (!scores) { /* clear: legal on every batch; the batch runs its plain kernel again */
-        return clear_table_image(b);
-    }
-    if (alphabet < 1 || alphabet > 32 || !codeOf) return DPX_ERR_INVALID;
-    for (int x = 0; x < 256; x++) if ((int)codeOf[x] >= alphabet) return DPX_ERR_INVALID;
-    /* the batch's own algorithm, not the kernel's: a covering BANW / BASW band that runs k_affine_dir / k_asw_dir is not admitted */
-    const bool three = b->prm.algo == DPX_ALGO_ANW || b->prm.algo == DPX_ALGO_ASW || b->prm.algo == DPX_ALGO_ASG;
-    if (!three || !b->dirs || !(b->flags & DPX_KEEP_DIRECTIONS)) return DPX_ERR_UNSUPPORTED;
-    /* fits_dir with the largest entry in place of match and the smallest in place of mismatch, over every pair */
-    if (!table_in_range(b, scores, alphabet, fits_dir)) return DPX_ERR_RANGE;
-    return set_table_image(b, scores, alphabet, codeOf);
+    if (!scores) return clear_table(b);
+    if (!table_args_ok(alphabet, codeOf)) return DPX_ERR_INVALID;
+    if (!one_of_anw_asw_asg(b) || !b->dirs || !(b->flags & DPX_KEEP_DIRECTIONS)) return DPX_ERR_UNSUPPORTED;
+    if (!pairs_in_range(b, table_extremes(b, scores, alphabet, alphabet), fits_dir)) return DPX_ERR_RANGE;
+    unsigned char image[DPX_SUBST_IMAGE_BYTES];
+    build_table_image(image, scores, alphabet, codeOf);
+    return install_table(b, image, alphabet, true);
 }
 
-/* the table of an ANW / ASW / ASG score-only batch (k_scoretab_fill / k_scoretab_lanes); every check comes before the first change */
+/* the table of an ANW / ASW / ASG score-only batch (k_scoretab_fill / k_scoretab_lanes) */
 int dpx_batch_set_score_table(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf) {
     if (!b) return DPX_ERR_INVALID;
-    if (!scores) { /* clear: legal on every batch; the batch runs its plain kernels again */
-        return clear_table_image(b);
-    }
-    if (alphabet < 1 || alphabet > 32 || !codeOf) return DPX_ERR_INVALID;
-    for (int x = 0; x < 256; x++) if ((int)codeOf[x] >= alphabet) return DPX_ERR_INVALID;
-    /* the batch's own algorithm, not the kernel's: a covering BANW / BASW band that runs the ANW / ASW kernels is not admitted */
-    const bool three = b->prm.algo == DPX_ALGO_ANW || b->prm.algo == DPX_ALGO_ASW || b->prm.algo == DPX_ALGO_ASG;
-    if (!three || b->store || b->dirs || !(b->flags & DPX_SCORE_ONLY)) return DPX_ERR_UNSUPPORTED;
+    if (!scores) return clear_table(b);
+    if (!table_args_ok(alphabet, codeOf)) return DPX_ERR_INVALID;
+    if (!one_of_anw_asw_asg(b) || b->store || b->dirs || !(b->flags & DPX_SCORE_ONLY)) return DPX_ERR_UNSUPPORTED;
     if (!dpx_plan_scoretab_fits(*b, t_err)) return DPX_ERR_UNSUPPORTED;
-    /* fits_int16 with the largest entry in place of match and the smallest in place of mismatch, over every pair */
-    if (!table_in_range(b, scores, alphabet, fits_int16)) return DPX_ERR_RANGE;
-    return set_table_image(b, scores, alphabet, codeOf);
+    if (!pairs_in_range(b, table_extremes(b, scores, alphabet, alphabet), fits_int16)) return DPX_ERR_RANGE;
+    unsigned char image[DPX_SUBST_IMAGE_BYTES];
+    build_table_image(image, scores, alphabet, codeOf);
+    return install_table(b, image, alphabet, true);
 }
 
 /* ---- orientation: dpx_batch_set_reversed ----

@@ -74,15 +74,14 @@ typedef struct dpx_dir_args {
 hipError_t dpx_launch_fill_dir(const dpx_dir_args &a, int algo, int R, hipStream_t stream);
 
 /* ANW / ASW / ASG direction batches under a substitution table (dpx_batch_set_direction_table; dpx_dirtab_kernels.hip): the same fill,
- * codes and stores with the diagonal term table[codeOf[reference byte] * 32 + codeOf[query byte]] (`table` / `codeOf` as in
- * dpx_subst_args: the device image of dpx_kernels.h, the map behind the table); d.match / d.mismatch are not read.  Every wave keeps the
+ * codes and stores with the diagonal term table[codeOf[reference byte] * 32 + codeOf[query byte]] (`tab`: dpx_kernels.h's
+ * dpx_table_ref, the device image with the map behind the table); d.match / d.mismatch are not read.  Every wave keeps the
  * image in LDS: with the edge rows in LDS d.ldsPerWave includes DPX_SUBST_IMAGE_BYTES behind the staged reference and the launch asks
  * for d.ldsPerWave * d.wavesPerBlock; with the edge rows in d.scratch d.ldsPerWave is the scratch area's as before and the launch asks
  * for DPX_SUBST_IMAGE_BYTES * d.wavesPerBlock. */
 typedef struct dpx_dirtab_args {
     dpx_dir_args d;
-    const int8_t *table;
-    const uint8_t *codeOf;
+    dpx_table_ref tab;
 } dpx_dirtab_args;
 hipError_t dpx_launch_dirtab_fill(const dpx_dirtab_args &a, int algo, int R, hipStream_t stream);
 /* one wave per pair walks the codes in runs and writes the three right-aligned lines at tbOff[p] (capacity (m+n+1+3)&~3) and tbLen[p],

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "dpx_device.hpp"
+#include "dpx_table_dev.hpp"
 
 namespace dpx_dir_dev {
 

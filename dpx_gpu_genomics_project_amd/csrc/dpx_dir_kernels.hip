@@ -33,6 +33,7 @@ using dpx_dir_dev::dir_store;
 using dpx_dev::stage_bytes;
 using dpx_dev::u32x4;
 using dpx_dev::wave_max_u64;
+using dpx_table::table_stage_rows;
 
 /* =====================================================================================================
  * LNW (LOCAL = false) / LSW (LOCAL = true).
@@ -174,7 +175,7 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_linear_dir(const dpx_dir_a
 template <int R, bool GLOBAL>
 __global__ void __launch_bounds__(DPX_FILL_THREADS) k_affine_dir(const dpx_dir_args a) {
     constexpr bool LOCAL = false, SEMI = false, TABLE = false;
-    constexpr const int8_t *tableG = nullptr; constexpr const unsigned char *codeOfG = nullptr;
+    constexpr dpx_table_ref tref = {nullptr, nullptr};
 #include "dpx_affine_dir.inc"
 }
 
@@ -182,7 +183,7 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_affine_dir(const dpx_dir_a
 template <int R, bool GLOBAL>
 __global__ void __launch_bounds__(DPX_FILL_THREADS) k_asw_dir(const dpx_dir_args a) {
     constexpr bool LOCAL = true, SEMI = false, TABLE = false;
-    constexpr const int8_t *tableG = nullptr; constexpr const unsigned char *codeOfG = nullptr;
+    constexpr dpx_table_ref tref = {nullptr, nullptr};
 #include "dpx_affine_dir.inc"
 }
 
@@ -191,7 +192,7 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_asw_dir(const dpx_dir_args
 template <int R, bool GLOBAL>
 __global__ void __launch_bounds__(DPX_FILL_THREADS) k_asg_dir(const dpx_dir_args a) {
     constexpr bool LOCAL = false, SEMI = true, TABLE = false;
-    constexpr const int8_t *tableG = nullptr; constexpr const unsigned char *codeOfG = nullptr;
+    constexpr dpx_table_ref tref = {nullptr, nullptr};
 #include "dpx_affine_dir.inc"
 }
 

@@ -27,13 +27,13 @@ using dpx_dir_dev::dir_store;
 using dpx_dev::stage_bytes;
 using dpx_dev::u32x4;
 using dpx_dev::wave_max_u64;
+using dpx_table::table_stage_rows;
 
 template <int R, bool GLOBAL, int KIND>
 __global__ void __launch_bounds__(DPX_FILL_THREADS) k_dirtab_fill(const dpx_dirtab_args t) {
     constexpr bool LOCAL = KIND == DPX_K_ASW, SEMI = KIND == DPX_K_ASG, TABLE = true;
     const dpx_dir_args &a = t.d;
-    const int8_t *const tableG = t.table;
-    const unsigned char *const codeOfG = t.codeOf;
+    const dpx_table_ref &tref = t.tab;
 #include "dpx_affine_dir.inc"
 }
 
@@ -65,7 +65,7 @@ hipError_t launch_dirtab_kind(const dpx_dirtab_args &t, int R, hipStream_t s) {
 
 hipError_t dpx_launch_dirtab_fill(const dpx_dirtab_args &t, int algo, int R, hipStream_t stream) {
     if (t.d.numPairs <= 0) return hipSuccess;
-    if (!t.table || !t.codeOf) return hipErrorInvalidValue;
+    if (!t.tab.table || !t.tab.codeOf) return hipErrorInvalidValue;
     switch (algo) {
     case DPX_K_ANW: return launch_dirtab_kind<DPX_K_ANW>(t, R, stream);
     case DPX_K_ASW: return launch_dirtab_kind<DPX_K_ASW>(t, R, stream);

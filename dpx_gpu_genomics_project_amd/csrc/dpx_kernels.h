@@ -78,64 +78,66 @@ hipError_t dpx_launch_banw_traceback(const dpx_fill_args &a, int numPairs, int w
 /* banded affine extension (dpx_baxt_kernels.hip): the fill only -- the stored layout, the edge rule and the border rule are BANW's, so
  * dpx_launch_banw_export and dpx_launch_banw_traceback serve it (both walks start from endRow / endCol) */
 hipError_t dpx_launch_baxt_fill(const dpx_fill_args &a, int C, bool store, size_t ldsBytes, hipStream_t stream);
-/* BAXT in extension mode (dpx_zext_kernels.hip, k_zext_fill): k_baxt_fill's cells and stores with z-drop termination (zdrop >= 0), the
- * best score of row m and the end-bonus choice (endBonus >= 0; -1 = off for either, not both).  `ext` is the device array of per-pair
- * records, eight int32 each in dpx_extension's field order.  Export and walks are BANW's, as for dpx_launch_baxt_fill. */
-typedef struct dpx_zext_args {
-    dpx_fill_args f;
+/* BAXT's extension mode, as every kernel that runs it takes it (dpx_zext_args, dpx_zsub_args, dpx_bdx_args, dpx_bd2_args): z-drop
+ * termination (zdrop >= 0), the best score of row m and the end-bonus choice (endBonus >= 0; -1 = off for either).  `ext` is the device
+ * array of per-pair records, eight int32 each in dpx_extension's field order. */
+typedef struct dpx_ext_ref {
     int32_t zdrop, endBonus;
     int32_t *ext;
+} dpx_ext_ref;
+/* BAXT in extension mode (dpx_zext_kernels.hip, k_zext_fill): k_baxt_fill's cells and stores with the scan of dpx_ext_ref (zdrop /
+ * endBonus: not both off).  Export and walks are BANW's, as for dpx_launch_baxt_fill. */
+typedef struct dpx_zext_args {
+    dpx_fill_args f;
+    dpx_ext_ref scan;
 } dpx_zext_args;
 hipError_t dpx_launch_zext_fill(const dpx_zext_args &a, int C, bool store, size_t ldsBytes, hipStream_t stream);
-/* BANW / BAXT under a substitution table (dpx_subst_kernels.hip, dpx_batch_set_substitution): k_banw_fill's / k_baxt_fill's cells, stores
- * and results (`ext`: BAXT's end cell) with the diagonal term H + table[(codeOf[ref byte] << 5) + codeOf[qry byte]].  `table` is 1 KiB of
- * int8 with a row stride of 32 (row = reference code), `codeOf` 256 bytes, both 16-byte aligned in device memory.  f.ldsPerWave and
- * `ldsBytes` include DPX_SUBST_IMAGE_BYTES per wave behind the staged strings.  The walks are BANW's with the same diagonal term; the
- * export is dpx_launch_banw_export. */
+/* A batch's substitution table on the device, as every table kernel takes it: `table` is 1 KiB of int8 with a row stride of 32 (row =
+ * reference code, column = query code, unused entries 0), `codeOf` the 256-byte map from sequence byte to code, both 16-byte aligned in
+ * device memory: one allocation of DPX_SUBST_IMAGE_BYTES, the map behind the table.  A cell's diagonal term is
+ * H + table[(codeOf[ref byte] << 5) + codeOf[qry byte]]. */
 #define DPX_SUBST_TABLE_BYTES 1024
 #define DPX_SUBST_IMAGE_BYTES 1280
-typedef struct dpx_subst_args {
-    dpx_fill_args f;
+typedef struct dpx_table_ref {
     const int8_t *table;
     const uint8_t *codeOf;
+} dpx_table_ref;
+/* A fill's arguments under a table, two families' worth.
+ * BANW / BAXT (dpx_subst_kernels.hip, dpx_batch_set_substitution): k_banw_fill's / k_baxt_fill's cells, stores and results (`ext`: BAXT's
+ * end cell) with the diagonal term of dpx_table_ref.  f.ldsPerWave and `ldsBytes` include DPX_SUBST_IMAGE_BYTES per wave behind the
+ * staged strings.  The walks are BANW's with the same diagonal term; the export is dpx_launch_banw_export.
+ * ANW / ASW / ASG score-only batches (dpx_scoretab_kernels.hip, dpx_batch_set_score_table): k_affine_fill's / k_asw_fill's / k_asg_fill's
+ * cells and results without stores (k_scoretab_fill) and the lane-packed kernels' (k_scoretab_lanes, R = 8) with the same diagonal term;
+ * f.match / f.mismatch are not read.  f.ldsPerWave includes DPX_SUBST_IMAGE_BYTES behind the wave's slice (the one-wave kernel) or behind
+ * its reference area (the lane-packed one), and each launch asks for f.ldsPerWave * f.wavesPerBlock bytes of LDS. */
+typedef struct dpx_subst_args {
+    dpx_fill_args f;
+    dpx_table_ref tab;
 } dpx_subst_args;
 hipError_t dpx_launch_subst_fill(const dpx_subst_args &a, int C, bool store, bool ext, size_t ldsBytes, hipStream_t stream);
 hipError_t dpx_launch_subst_traceback(const dpx_subst_args &a, int numPairs, int walk, const uint64_t *tbOff, char *tb, int32_t *tbLen,
                                       hipStream_t stream);
+hipError_t dpx_launch_scoretab_fill(const dpx_subst_args &a, int algo, int R, hipStream_t stream);
+hipError_t dpx_launch_scoretab_lanes(const dpx_subst_args &a, int algo, int R, hipStream_t stream);
 /* BAXT in extension mode under a substitution table (dpx_zsub_kernels.hip, k_zsub_fill; dpx_batch_set_extension_table): k_subst_fill's
- * cells with k_zext_fill's scan and results.  `s` is what dpx_launch_subst_fill takes (LDS sizes include the table image), zdrop /
- * endBonus / ext are dpx_zext_args'.  The walks are dpx_launch_subst_traceback's, the export is dpx_launch_banw_export. */
+ * cells with k_zext_fill's scan and results.  `s` is what dpx_launch_subst_fill takes (LDS sizes include the table image), `scan` is
+ * dpx_zext_args'.  The walks are dpx_launch_subst_traceback's, the export is dpx_launch_banw_export. */
 typedef struct dpx_zsub_args {
     dpx_subst_args s;
-    int32_t zdrop, endBonus;
-    int32_t *ext;
+    dpx_ext_ref scan;
 } dpx_zsub_args;
 hipError_t dpx_launch_zsub_fill(const dpx_zsub_args &a, int C, bool store, size_t ldsBytes, hipStream_t stream);
 /* A band-direction batch (dpx_banddir.h) under dpx_batch_set_direction_scoring (dpx_bdx_kernels.hip, k_bdx_fill): k_bdir_fill's cells,
- * codes and stores with the diagonal term from a table (`table` / `codeOf` as in dpx_subst_args, both NULL: byte compare) and, `ext`
- * only, BAXT's extension mode (zdrop / endBonus / ext as in dpx_zext_args; both -1: off).  At least one of the two is on; BANW takes a
- * table only.  With a table f.ldsPerWave includes DPX_SUBST_IMAGE_BYTES behind the staged strings; the launch asks for f.ldsPerWave *
- * f.wavesPerBlock bytes of LDS, as dpx_launch_bdir_fill does.  Walk and export are dpx_launch_bdir_traceback / _export. */
+ * codes and stores with the diagonal term from a table (`tab`, both pointers NULL: byte compare) and, `ext` only, BAXT's extension mode
+ * (`scan`; zdrop and endBonus both -1: off).  At least one of the two is on; BANW takes a table only.  With a table f.ldsPerWave includes
+ * DPX_SUBST_IMAGE_BYTES behind the staged strings; the launch asks for f.ldsPerWave * f.wavesPerBlock bytes of LDS, as
+ * dpx_launch_bdir_fill does.  Walk and export are dpx_launch_bdir_traceback / _export. */
 typedef struct dpx_bdx_args {
     dpx_fill_args f;
-    const int8_t *table;
-    const uint8_t *codeOf;
-    int32_t zdrop, endBonus;
-    int32_t *ext;
+    dpx_table_ref tab;
+    dpx_ext_ref scan;
 } dpx_bdx_args;
 hipError_t dpx_launch_bdx_fill(const dpx_bdx_args &a, int C, bool ext, hipStream_t stream);
-/* ANW / ASW / ASG score-only batches under a substitution table (dpx_scoretab_kernels.hip, dpx_batch_set_score_table): k_affine_fill's /
- * k_asw_fill's / k_asg_fill's cells and results without stores (k_scoretab_fill) and the lane-packed kernels' (k_scoretab_lanes, R = 8)
- * with the diagonal term H + table[(codeOf[ref byte] << 5) + codeOf[qry byte]] (`table` / `codeOf` as in dpx_subst_args); f.match /
- * f.mismatch are not read.  f.ldsPerWave includes DPX_SUBST_IMAGE_BYTES behind the wave's slice (the one-wave kernel) or behind its
- * reference area (the lane-packed one), and each launch asks for f.ldsPerWave * f.wavesPerBlock bytes of LDS. */
-typedef struct dpx_scoretab_args {
-    dpx_fill_args f;
-    const int8_t *table;
-    const uint8_t *codeOf;
-} dpx_scoretab_args;
-hipError_t dpx_launch_scoretab_fill(const dpx_scoretab_args &a, int algo, int R, hipStream_t stream);
-hipError_t dpx_launch_scoretab_lanes(const dpx_scoretab_args &a, int algo, int R, hipStream_t stream);
 hipError_t dpx_launch_unpack2(const uint32_t *packed, uint32_t alphabet, char *out, size_t numDwords, hipStream_t stream);
 hipError_t dpx_launch_prim_eval(const int32_t *op, const uint32_t *a, const uint32_t *b, const uint32_t *c, size_t count,
                                 uint32_t *res, uint32_t *pred, hipStream_t stream);

@@ -39,41 +39,41 @@ constexpr int scoretab_waves(int R, int KIND) { return R < 8 ? 8 : (KIND == DPX_
 
 template <int R, int KIND>
 __global__ void __launch_bounds__(DPX_FILL_THREADS) __attribute__((amdgpu_waves_per_eu(scoretab_waves(R, KIND))))
-k_scoretab_fill(const dpx_scoretab_args t) {
+k_scoretab_fill(const dpx_subst_args t) {
     constexpr bool LOCAL = KIND == DPX_K_ASW, SEMI = KIND == DPX_K_ASG, STORE = false, TABLE = true;
     const dpx_fill_args &a = t.f;
-    const int8_t *const tableG = t.table;
-    const unsigned char *const codeOfG = t.codeOf;
+    const int8_t *const tableG = t.tab.table;
+    const unsigned char *const codeOfG = t.tab.codeOf;
 #include "dpx_affine_fill.inc"
 }
 
 template <int KIND>
-__global__ void __launch_bounds__(DPX_ALANES_THREADS) k_scoretab_lanes(const dpx_scoretab_args t) {
+__global__ void __launch_bounds__(DPX_ALANES_THREADS) k_scoretab_lanes(const dpx_subst_args t) {
     constexpr int R = 8;
     constexpr bool LOCAL = KIND == DPX_K_ASW, SEMI = KIND == DPX_K_ASG, STORE = false, TABLE = true;
     const dpx_fill_args &a = t.f;
-    const int8_t *const tableG = t.table;
-    const unsigned char *const codeOfG = t.codeOf;
+    const int8_t *const tableG = t.tab.table;
+    const unsigned char *const codeOfG = t.tab.codeOf;
 #include "dpx_affine_lanes.inc"
 }
 
 /* f.wavesPerBlock waves per workgroup, f.ldsPerWave (image included) bytes of LDS each */
 template <class K>
-hipError_t scoretab_launch(K kernel, const dpx_scoretab_args &t, hipStream_t s) {
+hipError_t scoretab_launch(K kernel, const dpx_subst_args &t, hipStream_t s) {
     const unsigned wpb = t.f.wavesPerBlock ? t.f.wavesPerBlock : 1u;
     return launch_lds(kernel, dim3(((unsigned)t.f.numPairs + wpb - 1) / wpb), dim3(64u * wpb), (size_t)t.f.ldsPerWave * wpb, s, t);
 }
 
 template <int KIND>
-hipError_t launch_scoretab_kind(const dpx_scoretab_args &t, int R, hipStream_t s) {
+hipError_t launch_scoretab_kind(const dpx_subst_args &t, int R, hipStream_t s) {
     return dispatch_int<2, 4, 8>(R, [&](auto r) { return scoretab_launch(k_scoretab_fill<decltype(r)::value, KIND>, t, s); });
 }
 
 } // namespace
 
-hipError_t dpx_launch_scoretab_fill(const dpx_scoretab_args &t, int algo, int R, hipStream_t stream) {
+hipError_t dpx_launch_scoretab_fill(const dpx_subst_args &t, int algo, int R, hipStream_t stream) {
     if (t.f.numPairs <= 0) return hipSuccess;
-    if (!t.table || !t.codeOf || t.f.ldsPerWave < DPX_SUBST_IMAGE_BYTES) return hipErrorInvalidValue;
+    if (!t.tab.table || !t.tab.codeOf || t.f.ldsPerWave < DPX_SUBST_IMAGE_BYTES) return hipErrorInvalidValue;
     switch (algo) {
     case DPX_K_ANW: return launch_scoretab_kind<DPX_K_ANW>(t, R, stream);
     case DPX_K_ASW: return launch_scoretab_kind<DPX_K_ASW>(t, R, stream);
@@ -82,9 +82,9 @@ hipError_t dpx_launch_scoretab_fill(const dpx_scoretab_args &t, int algo, int R,
     }
 }
 
-hipError_t dpx_launch_scoretab_lanes(const dpx_scoretab_args &t, int algo, int R, hipStream_t stream) {
+hipError_t dpx_launch_scoretab_lanes(const dpx_subst_args &t, int algo, int R, hipStream_t stream) {
     if (t.f.numPairs <= 0) return hipSuccess;
-    if (!t.table || !t.codeOf || R != 8 || t.f.wavesPerBlock != DPX_ALANES_THREADS / 64 || t.f.ldsPerWave < DPX_SUBST_IMAGE_BYTES) return hipErrorInvalidValue;
+    if (!t.tab.table || !t.tab.codeOf || R != 8 || t.f.wavesPerBlock != DPX_ALANES_THREADS / 64 || t.f.ldsPerWave < DPX_SUBST_IMAGE_BYTES) return hipErrorInvalidValue;
     switch (algo) {
     case DPX_K_ANW: return scoretab_launch(k_scoretab_lanes<DPX_K_ANW>, t, stream);
     case DPX_K_ASW: return scoretab_launch(k_scoretab_lanes<DPX_K_ASW>, t, stream);

@@ -62,10 +62,7 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_subst_fill(const dpx_subst
     const unsigned char *qL = stage_bytes(my, qry, m, lane, 64);
     const unsigned char *rL = stage_bytes(my + a.ldsRefOff, ref, n, lane, 64);
     unsigned char *img = my + (a.ldsPerWave - (uint32_t)DPX_SUBST_IMAGE_BYTES);
-    { /* (both arrays are 16-byte aligned: the host keeps them in one device allocation, the map behind the table) */
-        reinterpret_cast<u32x4 *>(img)[lane] = reinterpret_cast<const u32x4 *>(sa.table)[lane];
-        if (lane < 16) reinterpret_cast<u32x4 *>(img + DPX_SUBST_TABLE_BYTES)[lane] = reinterpret_cast<const u32x4 *>(sa.codeOf)[lane];
-    }
+    DPX_TABLE_COPY_ROWS(img, sa.tab, lane)
     const signed char *tabL = reinterpret_cast<const signed char *>(img);
     const unsigned char *codeL = img + DPX_SUBST_TABLE_BYTES;
 
@@ -172,14 +169,14 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_subst_fill(const dpx_subst
 /* the one-lane walk reads table and map from global memory (1280 bytes, resident in L1 after the first steps) */
 __global__ void k_subst_traceback(const dpx_subst_args sa, int numPairs, const int32_t *endRow, const int32_t *endCol,
                                   const uint64_t *tbOff, char *tb, int32_t *tbLen) {
-    band_walk_lane(sa.f, TableScorer{reinterpret_cast<const signed char *>(sa.table), sa.codeOf}, numPairs, endRow, endCol, tbOff, tb, tbLen);
+    band_walk_lane(sa.f, TableScorer{reinterpret_cast<const signed char *>(sa.tab.table), sa.tab.codeOf}, numPairs, endRow, endCol, tbOff, tb, tbLen);
 }
 
 /* the wave walk keeps the table in LDS behind its window and reads the map from global memory */
 __global__ void __launch_bounds__(64) k_subst_traceback_wave(const dpx_subst_args sa, int numPairs, const int32_t *endRow, const int32_t *endCol,
                                                              const uint64_t *tbOff, char *tb, int32_t *tbLen) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smemTb[];
-    band_walk_wave(sa.f, TableScorer{reinterpret_cast<const signed char *>(smemTb + BandWin::kBytes), sa.codeOf}, sa.table, smemTb, numPairs,
+    band_walk_wave(sa.f, TableScorer{reinterpret_cast<const signed char *>(smemTb + BandWin::kBytes), sa.tab.codeOf}, sa.tab.table, smemTb, numPairs,
                    endRow, endCol, tbOff, tb, tbLen);
 }
 

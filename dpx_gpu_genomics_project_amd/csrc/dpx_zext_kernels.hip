@@ -44,9 +44,9 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_zext_fill(const dpx_zext_a
     const dpx_pair_dev pr = a.f.pairs[p];
     const int n = pr.n, m = pr.m, B = a.f.band;
     const int match = a.f.match, mismatch = a.f.mismatch, o = a.f.gapOpen, e = a.f.gapExtend, oe = a.f.gapOpen + a.f.gapExtend;
-    const int Z = a.zdrop, pen = e < 0 ? -e : 0;
+    const int Z = a.scan.zdrop, pen = e < 0 ? -e : 0;
     if (m <= 0 || n <= 0) {
-        if (lane == 0) scan_border_line<ZDROP>(a.f, a.endBonus, a.ext, p, m, n, B, [&](const int k) { return o + k * e; }, Z, pen); /* an empty sequence: one border line */
+        if (lane == 0) scan_border_line<ZDROP>(a.f, a.scan.endBonus, a.scan.ext, p, m, n, B, [&](const int k) { return o + k * e; }, Z, pen); /* an empty sequence: one border line */
         return;
     }
     const unsigned char *ref = reinterpret_cast<const unsigned char *>(a.f.seq + pr.refIdx);
@@ -144,18 +144,18 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_zext_fill(const dpx_zext_a
 #undef DPX_ZEXT_BODY
 #undef DPX_ZEXT_AFTER
 #undef DPX_ZEXT_STORE
-    scan_finish<C>(a.f, a.endBonus, a.ext, p, st.key, lane, m, B, qe, lastDiag, stop);
+    scan_finish<C>(a.f, a.scan.endBonus, a.scan.ext, p, st.key, lane, m, B, qe, lastDiag, stop);
 }
 
 } // namespace
 
 hipError_t dpx_launch_zext_fill(const dpx_zext_args &a, int C, bool store, size_t ldsBytes, hipStream_t stream) {
     if (a.f.numPairs <= 0) return hipSuccess;
-    if (!a.ext) return hipErrorInvalidValue;
+    if (!a.scan.ext) return hipErrorInvalidValue;
     return dispatch_fill(C, a.f.band, store, [&](auto c, auto pb, auto st) {
         constexpr int kC = decltype(c)::value;
         constexpr bool kPB = decltype(pb)::value, kStore = decltype(st)::value;
-        return a.zdrop >= 0 ? launch_fill(k_zext_fill<kC, kPB, kStore, true>, a, a.f, ldsBytes, stream)
+        return a.scan.zdrop >= 0 ? launch_fill(k_zext_fill<kC, kPB, kStore, true>, a, a.f, ldsBytes, stream)
                             : launch_fill(k_zext_fill<kC, kPB, kStore, false>, a, a.f, ldsBytes, stream);
     });
 }

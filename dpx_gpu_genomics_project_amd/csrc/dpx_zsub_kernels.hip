@@ -37,9 +37,9 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_zsub_fill(const dpx_zsub_a
     const dpx_pair_dev pr = a.pairs[p];
     const int n = pr.n, m = pr.m, B = a.band;
     const int o = a.gapOpen, e = a.gapExtend, oe = a.gapOpen + a.gapExtend;
-    const int Z = za.zdrop, pen = e < 0 ? -e : 0;
+    const int Z = za.scan.zdrop, pen = e < 0 ? -e : 0;
     if (m <= 0 || n <= 0) {
-        if (lane == 0) scan_border_line<ZDROP>(a, za.endBonus, za.ext, p, m, n, B, [&](const int k) { return o + k * e; }, Z, pen); /* an empty sequence: one border line */
+        if (lane == 0) scan_border_line<ZDROP>(a, za.scan.endBonus, za.scan.ext, p, m, n, B, [&](const int k) { return o + k * e; }, Z, pen); /* an empty sequence: one border line */
         return;
     }
     const unsigned char *ref = reinterpret_cast<const unsigned char *>(a.seq + pr.refIdx);
@@ -49,10 +49,7 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_zsub_fill(const dpx_zsub_a
     const unsigned char *qL = stage_bytes(my, qry, m, lane, 64);
     const unsigned char *rL = stage_bytes(my + a.ldsRefOff, ref, n, lane, 64);
     unsigned char *img = my + (a.ldsPerWave - (uint32_t)DPX_SUBST_IMAGE_BYTES);
-    { /* (both arrays are 16-byte aligned: the host keeps them in one device allocation, the map behind the table) */
-        reinterpret_cast<u32x4 *>(img)[lane] = reinterpret_cast<const u32x4 *>(za.s.table)[lane];
-        if (lane < 16) reinterpret_cast<u32x4 *>(img + DPX_SUBST_TABLE_BYTES)[lane] = reinterpret_cast<const u32x4 *>(za.s.codeOf)[lane];
-    }
+    DPX_TABLE_COPY_ROWS(img, za.s.tab, lane)
     const signed char *tabL = reinterpret_cast<const signed char *>(img);
     const unsigned char *codeL = img + DPX_SUBST_TABLE_BYTES;
 
@@ -143,18 +140,18 @@ __global__ void __launch_bounds__(DPX_FILL_THREADS) k_zsub_fill(const dpx_zsub_a
     }
 #undef DPX_ZSUB_BODY
 #undef DPX_ZSUB_STORE
-    scan_finish<C>(a, za.endBonus, za.ext, p, st.key, lane, m, B, qe, lastDiag, stop);
+    scan_finish<C>(a, za.scan.endBonus, za.scan.ext, p, st.key, lane, m, B, qe, lastDiag, stop);
 }
 
 } // namespace
 
 hipError_t dpx_launch_zsub_fill(const dpx_zsub_args &a, int C, bool store, size_t ldsBytes, hipStream_t stream) {
     if (a.s.f.numPairs <= 0) return hipSuccess;
-    if (!a.ext || !a.s.table || !a.s.codeOf) return hipErrorInvalidValue;
+    if (!a.scan.ext || !a.s.tab.table || !a.s.tab.codeOf) return hipErrorInvalidValue;
     return dispatch_fill(C, a.s.f.band, store, [&](auto c, auto pb, auto st) {
         constexpr int kC = decltype(c)::value;
         constexpr bool kPB = decltype(pb)::value, kStore = decltype(st)::value;
-        return a.zdrop >= 0 ? launch_fill(k_zsub_fill<kC, kPB, kStore, true>, a, a.s.f, ldsBytes, stream)
+        return a.scan.zdrop >= 0 ? launch_fill(k_zsub_fill<kC, kPB, kStore, true>, a, a.s.f, ldsBytes, stream)
                             : launch_fill(k_zsub_fill<kC, kPB, kStore, false>, a, a.s.f, ldsBytes, stream);
     });
 }

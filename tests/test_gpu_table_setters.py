@@ -1,0 +1,160 @@
+"""The five setters that hand a batch a substitution table, each on a batch kind it admits, through the steps they share in
+dpx_capi.cpp: the argument check, the install and the clear.  Three pairs of about 33 x 47 (band 16 where banded), results bit-exact
+against the CPU oracles of the setters' own test files (subst_ref, zsub_ref, bdx_ref, dirtab_ref; dirtab_oracle.c is the score-table
+oracle too).  "Plain" results are the same oracles under the table that scores as byte equality with the batch's match / mismatch.
+
+dpx_batch_set_direction_scoring's batch is BAXT with DPX_KEEP_BAND_DIRECTIONS, the flag that makes a band-direction batch
+(DPX_KEEP_DIRECTIONS is refused on banded algorithms)."""
+import numpy as np
+import pytest
+
+import bdx_ref
+import dirtab_ref
+import subst_ref
+import zsub_ref
+from dpx_gpu_genomics_project_amd.synth import from_strings
+
+pytestmark = pytest.mark.gpu
+
+INVALID, NOT_FILLED = -1, -6
+BANW, BAXT, ASW, ASG = 7, 10, 4, 6
+MM, GAPS, BAND = (2, -3), zsub_ref.GAPS, 16
+Z, E = 30, 5  # the extension setters' z-drop and end bonus; they stay when another setter's NULL call clears the table
+SHAPES = ((33, 47), (47, 33), (40, 41))  # (m, n); |m - n| <= BAND - 1, so BANW admits them
+TABLE, CODE = zsub_ref.acgtn_table()  # asymmetric: a transposed lookup gives other scores
+TABLE[1, 1], TABLE[3, 1] = 3, -2  # ... and apart from byte equality on every pair: C under C scores 3, a reference T under a query C -2
+PLAIN, PLAIN_CODE = subst_ref.identity_table(*MM, b"ACGT")
+
+
+@pytest.fixture(scope="module")
+def oracles(tmp_path_factory):
+    d = tmp_path_factory.mktemp("table_setters")
+    return {"subst": subst_ref.build(d), "zsub": zsub_ref.build(d), "dirtab": dirtab_ref.build(d)}
+
+
+@pytest.fixture(scope="module")
+def sb():
+    rng = np.random.default_rng(4733)
+    texts = []
+    for m, n in SHAPES:
+        ref = rng.integers(0, 4, n)
+        qry = np.resize(ref, m).copy()
+        hit = rng.random(m) < 0.2
+        qry[hit] = rng.integers(0, 4, int(hit.sum()))
+        texts.append((np.frombuffer(b"ACGT", np.uint8)[ref].tobytes(), np.frombuffer(b"ACGT", np.uint8)[qry].tobytes()))
+    return from_strings(texts)
+
+
+class Setter:
+    """one setter: its batch, its typed call, its raw call (scores, alphabet, codeOf as the C function takes them), the setter whose
+    NULL call clears its table, and the oracle's (score, end row, end column) of one pair under a table"""
+
+    def __init__(self, name, algo, flags, banded, always_invalidates, clear_with, set_table, raw, want):
+        self.name, self.algo, self.flags, self.banded, self.always_invalidates = name, algo, flags, banded, always_invalidates
+        self.clear_with, self.set_table, self.raw, self.want = clear_with, set_table, raw, want
+
+    def batch(self, gpu, sb):
+        return gpu.Batch(self.algo, sb.sequences, sb.pairs, *MM, *GAPS, band=BAND if self.banded else 0, flags=getattr(gpu, self.flags))
+
+
+def _tuple(r):
+    return (r["score"], *r["end"])
+
+
+SETTERS = [
+    Setter("set_substitution", BANW, "KEEP_MATRICES", True, True, "dpx_batch_set_score_table",
+           lambda b, t, c: b.set_substitution(t, c),
+           lambda lib, b, s, a, c: lib.dpx_batch_set_substitution(b._h, s, a, c),
+           lambda o, ref, qry, t, c: o["subst"].result(ref, qry, t, c, *GAPS, BAND, False)),
+    Setter("set_extension_table", BAXT, "KEEP_MATRICES", True, True, "dpx_batch_set_substitution",
+           lambda b, t, c: b.set_extension_table(Z, E, t, c),
+           lambda lib, b, s, a, c: lib.dpx_batch_set_extension_table(b._h, Z, E, s, a, c),
+           lambda o, ref, qry, t, c: _tuple(o["zsub"].align(ref, qry, t, c, *GAPS, BAND, Z, E, walk=False))),
+    Setter("set_direction_scoring", BAXT, "KEEP_BAND_DIRECTIONS", True, False, "dpx_batch_set_direction_table",
+           lambda b, t, c: b.set_direction_scoring(Z, E, t, c),
+           lambda lib, b, s, a, c: lib.dpx_batch_set_direction_scoring(b._h, Z, E, s, a, c),
+           lambda o, ref, qry, t, c: _tuple(bdx_ref.expect(o["zsub"], ref, qry, t, c, *GAPS, BAND, True, Z, E))),
+    Setter("set_direction_table", ASW, "KEEP_DIRECTIONS", False, False, "dpx_batch_set_substitution",
+           lambda b, t, c: b.set_direction_table(t, c),
+           lambda lib, b, s, a, c: lib.dpx_batch_set_direction_table(b._h, s, a, c),
+           lambda o, ref, qry, t, c: _tuple(o["dirtab"].align("ASW", ref, qry, t, c, *GAPS))),
+    Setter("set_score_table", ASG, "SCORE_ONLY", False, False, "dpx_batch_set_direction_table",
+           lambda b, t, c: b.set_score_table(t, c),
+           lambda lib, b, s, a, c: lib.dpx_batch_set_score_table(b._h, s, a, c),
+           lambda o, ref, qry, t, c: _tuple(o["dirtab"].align("ASG", ref, qry, t, c, *GAPS))),
+]
+BY_NAME = pytest.mark.parametrize("setter", SETTERS, ids=[s.name for s in SETTERS])
+
+
+def _results(b):
+    s, r, c = b.results()
+    return list(zip(s.tolist(), r.tolist(), c.tolist()))
+
+
+def _want(setter, oracles, sb, table, code):
+    return [tuple(int(v) for v in setter.want(oracles, sb.ref(p), sb.qry(p), table, code)) for p in range(sb.num_pairs)]
+
+
+def _status(gpu, call):
+    try:
+        call()
+    except gpu.DpxError as e:
+        return e.status
+    return 0
+
+
+@BY_NAME
+def test_refused_calls_change_nothing(gpu, oracles, sb, setter):
+    """codeOf NULL, alphabet 0, alphabet 33 and a map entry equal to the alphabet: DPX_ERR_INVALID each, and results and describe() stay"""
+    lib = gpu.load()
+    tab = np.ascontiguousarray(TABLE, np.int8)
+    big = np.zeros((33, 33), np.int8)
+    bad_code = CODE.copy()
+    bad_code[ord("T")] = tab.shape[0]
+    with setter.batch(gpu, sb) as b:
+        setter.set_table(b, TABLE, CODE)
+        b.fill()
+        before, described = _results(b), b.describe()
+        assert before == _want(setter, oracles, sb, TABLE, CODE)
+        refused = {"codeOf NULL": (tab.ctypes.data, tab.shape[0], None), "alphabet 0": (tab.ctypes.data, 0, CODE.ctypes.data),
+                   "alphabet 33": (big.ctypes.data, 33, CODE.ctypes.data), "entry == alphabet": (tab.ctypes.data, tab.shape[0], bad_code.ctypes.data)}
+        for what, (s, a, c) in refused.items():
+            assert setter.raw(lib, b, s, a, c) == INVALID, what
+            assert _results(b) == before, what
+            assert b.describe() == described, what
+
+
+@BY_NAME
+def test_set_fill_clear_refill(gpu, oracles, sb, setter):
+    """the table, then none (cleared through ANOTHER setter's NULL call, legal on every batch), then the table again: bit for bit"""
+    lib = gpu.load()
+    under_table, plain = _want(setter, oracles, sb, TABLE, CODE), _want(setter, oracles, sb, PLAIN, PLAIN_CODE)
+    assert under_table != plain  # the table is seen
+    with setter.batch(gpu, sb) as b:
+        setter.set_table(b, TABLE, CODE)
+        assert b.describe().get("subst") == TABLE.shape[0]
+        b.fill()
+        first = _results(b)
+        assert first == under_table
+        assert getattr(lib, setter.clear_with)(b._h, None, 0, None) == 0
+        assert b.describe().get("subst") is None
+        assert _status(gpu, b.results) == NOT_FILLED
+        b.fill()
+        assert _results(b) == plain
+        setter.set_table(b, TABLE, CODE)
+        b.fill()
+        assert _results(b) == first
+
+
+@BY_NAME
+def test_same_table_again(gpu, sb, setter):
+    """after a fill: dpx_batch_set_substitution and dpx_batch_set_extension_table always invalidate, the other three keep the results"""
+    with setter.batch(gpu, sb) as b:
+        setter.set_table(b, TABLE, CODE)
+        b.fill()
+        before = _results(b)
+        setter.set_table(b, TABLE.copy(), CODE.copy())
+        if setter.always_invalidates:
+            assert _status(gpu, b.results) == NOT_FILLED
+        else:
+            assert _results(b) == before

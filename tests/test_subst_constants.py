@@ -20,7 +20,9 @@ def test_header_symbol_and_abi_version():
     assert re.search(r"\bDPX_ALGO_BAXT\s*=\s*10\b", header) and "DPX_ALGO_SUBST" not in header  # a setting of BANW / BAXT, not a new dpx_algo
     kernels = open(os.path.join(CSRC, "dpx_kernels.h")).read()
     assert "dpx_launch_subst_fill" in kernels and "dpx_launch_subst_traceback" in kernels
-    assert re.search(r"typedef struct dpx_subst_args \{\s*dpx_fill_args f;\s*const int8_t \*table;\s*const uint8_t \*codeOf;\s*\} dpx_subst_args;", kernels)
+    # (the two pointers moved into dpx_table_ref, which dpx_subst_args holds at their place)
+    assert re.search(r"typedef struct dpx_table_ref \{\s*const int8_t \*table;\s*const uint8_t \*codeOf;\s*\} dpx_table_ref;", kernels)
+    assert re.search(r"typedef struct dpx_subst_args \{\s*dpx_fill_args f;\s*dpx_table_ref tab;\s*\} dpx_subst_args;", kernels)
     assert "dpx_subst_kernels.hip" in open(os.path.join(CSRC, "Makefile")).read()
 
 
