@@ -1,4 +1,4 @@
-/* dpx_cigar.h -- interface between the C-ABI layer (dpx_capi.cpp) and the CIGAR kernels (dpx_cigar_kernels.hip). */
+/* dpx_cigar.h -- interface between the C-ABI layer (dpx_output.cpp) and the CIGAR kernels (dpx_cigar_kernels.hip). */
 #ifndef DPX_CIGAR_H
 #define DPX_CIGAR_H
 

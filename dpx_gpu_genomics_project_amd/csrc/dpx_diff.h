@@ -1,4 +1,4 @@
-/* dpx_diff.h -- interface between the C-ABI layer (dpx_capi.cpp) and the difference-string kernels (dpx_diff_kernels.hip). */
+/* dpx_diff.h -- interface between the C-ABI layer (dpx_output.cpp) and the difference-string kernels (dpx_diff_kernels.hip). */
 #ifndef DPX_DIFF_H
 #define DPX_DIFF_H
 

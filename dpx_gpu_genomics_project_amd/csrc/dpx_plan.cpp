@@ -8,7 +8,6 @@
 #include <numeric>
 #include <utility>
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 /* LDS request that caps residency at 16 fill waves per CU (9 KiB per wave of the workgroup) */
 constexpr size_t kLdsFloor = 36u * 1024u * (DPX_FILL_THREADS / 64) / 4;

@@ -1,6 +1,7 @@
 /* dpx_plan.h -- the host-only half of dpx_batch_create: what a batch decides before it touches the device, as a pure function of the
  * parameters, the pairs' sizes and indices, the flags and a Knobs snapshot.  No sequence byte is read and no HIP function called
- * (dpx_kernels.h: the argument structs only), so hostcpp/plan_tool runs it without a GPU.  dpx_capi.cpp does the device work. */
+ * (dpx_kernels.h: the argument structs only), so hostcpp/plan_tool runs it without a GPU.  dpx_capi.cpp, dpx_settings.cpp and
+ * dpx_output.cpp do the device work. */
 #ifndef DPX_PLAN_H
 #define DPX_PLAN_H
 
@@ -14,7 +15,7 @@
 
 #pragma GCC visibility push(hidden) /* (internal to libdpxalign.so: not part of its ABI) */
 
-/* Development and test knobs.  The environment is read in ONE place (dpx_capi.cpp: refresh_knobs), when dpx_init() binds a device and
+/* Development and test knobs.  The environment is read in ONE place (dpx_host.cpp: refresh_knobs), when dpx_init() binds a device and
  * again at the start of every dpx_batch_create*() (the tests flip a knob between two batches of one process); everything else reads this
  * snapshot.  -1 / 0 = not set.  None of them changes a result: they force or forbid a kernel family, change the launch shape or trace
  * the runtime. */
@@ -36,7 +37,7 @@ struct Knobs {
     bool trace = false, traceVmm = false; /* DPX_TRACE / DPX_TRACE_VMM: phase timings / pool mapping calls on stderr */
 };
 
-/* What dpx_plan_batch decides.  dpx_batch (dpx_capi.cpp) takes it over by move and fills in the device pointers. */
+/* What dpx_plan_batch decides.  dpx_batch (dpx_batch.h) takes it over by move and fills in the device pointers. */
 struct dpx_plan {
     dpx_params prm{}; unsigned flags = 0; size_t numPairs = 0;
     bool packed2 = false;  /* the sequences arrive as 2-bit codes (dpx_batch_create_packed2) */
@@ -74,7 +75,7 @@ struct dpx_plan {
 };
 
 bool is_affine(int algo), is_banded(int algo), is_banded_affine(int algo), is_banw_layout(int algo);
-size_t align_up(size_t v, size_t a);
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 int validate_params(const dpx_params *p);
 bool fits_int16(const dpx_params &p, long long m, long long n), fits_dir(const dpx_params &p, long long m, long long n);
 bool packed_safe(const dpx_params &p, long long m, long long n);

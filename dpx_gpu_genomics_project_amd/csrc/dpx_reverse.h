@@ -1,4 +1,4 @@
-/* dpx_reverse.h -- interface between the C-ABI layer (dpx_capi.cpp) and the orientation kernels (dpx_reverse_kernels.hip):
+/* dpx_reverse.h -- interface between the C-ABI layer (dpx_settings.cpp, dpx_output.cpp) and the orientation kernels (dpx_reverse_kernels.hip):
  * dpx_batch_set_reversed's device work. */
 #ifndef DPX_REVERSE_H
 #define DPX_REVERSE_H

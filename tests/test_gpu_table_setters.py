@@ -1,5 +1,5 @@
 """The five setters that hand a batch a substitution table, each on a batch kind it admits, through the steps they share in
-dpx_capi.cpp: the argument check, the install and the clear.  Three pairs of about 33 x 47 (band 16 where banded), results bit-exact
+dpx_settings.cpp: the argument check, the install and the clear.  Three pairs of about 33 x 47 (band 16 where banded), results bit-exact
 against the CPU oracles of the setters' own test files (subst_ref, zsub_ref, bdx_ref, dirtab_ref; dirtab_oracle.c is the score-table
 oracle too).  "Plain" results are the same oracles under the table that scores as byte equality with the batch's match / mismatch.
 

@@ -2,7 +2,7 @@
 kernel and the traceback that dpx_batch_describe() names, and the walk family and mode that the traceback launches.
 
 The expectations below were written by hand from the if-chains of the commit before the route existed -- launch_main and launch_all
-(fill), traceback_lines (walk family; walk mode with its 20 000- and 65 536-pair thresholds and DPX_TB_WALK) in csrc/dpx_capi.cpp -- and
+(fill), traceback_lines (walk family; walk mode with its 20 000- and 65 536-pair thresholds and DPX_TB_WALK) in csrc/dpx_capi.cpp (today: dpx_capi.cpp and dpx_output.cpp's lines_behind_fill) -- and
 from the planner's own rules for lanes, couples and the split kernel.  None of them was produced by running the code under test.
 A direction or band-direction batch has one walk and takes no mode: the route says 0 whatever the knob says.
 

@@ -37,13 +37,16 @@ def test_library_exports_the_symbol_and_the_binding_has_the_method():
 
 
 def test_the_unit_is_built_into_the_library():
-    assert "dpx_reverse_kernels.hip" in open(os.path.join(CSRC, "Makefile")).read()
+    makefile = open(os.path.join(CSRC, "Makefile")).read()
+    assert "dpx_reverse_kernels.hip" in makefile
     unit = open(os.path.join(CSRC, "dpx_reverse_kernels.hip")).read()
     for kernel in ("k_reverse_strings", "k_flip_lines", "k_map_records"):
         assert f"{kernel}(" in unit, kernel
-    capi = open(os.path.join(CSRC, "dpx_capi.cpp")).read()
+    host_units = sorted(set(re.findall(r"\bdpx_\w+\.cpp\b", makefile)))  # the host side of the library: every .cpp unit it is built from
+    assert "dpx_capi.cpp" in host_units and "dpx_settings.cpp" in host_units and "dpx_output.cpp" in host_units
+    host = "".join(open(os.path.join(CSRC, name)).read() for name in host_units)
     for launch in ("dpx_launch_reverse_strings", "dpx_launch_flip_lines", "dpx_launch_map_records"):
-        assert launch in capi, launch
+        assert f"{launch}(" in host, launch
 
 
 def test_dpx_main_usage_names_reverse_and_refuses_it_elsewhere(tmp_path):

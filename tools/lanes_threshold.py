@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """tools/lanes_threshold.py -- where do the lane-packed kernels beat the engine's other choices?  Ragged short reads at several batch
-sizes and a few mid-size shapes, DPX_LANES=0 / 1 (development aid; sets the thresholds in dpx_capi.cpp)."""
+sizes and a few mid-size shapes, DPX_LANES=0 / 1 (development aid; sets the thresholds in dpx_plan.cpp)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import dpx_gpu_genomics_project_amd as dpx
