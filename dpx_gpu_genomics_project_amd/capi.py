@@ -42,7 +42,7 @@ ABI_SYMBOLS = (
     "dpx_batch_cigars_begin", "dpx_batch_cigars_end", "dpx_cigar_text", "dpx_batch_set_extension", "dpx_batch_extensions",
     "dpx_batch_set_substitution", "dpx_batch_set_extension_table", "dpx_batch_set_direction_scoring",
     "dpx_batch_set_second_gap", "dpx_batch_set_reversed", "dpx_batch_set_direction_table",
-    "dpx_batch_set_score_table", "dpx_batch_diffs_begin", "dpx_batch_diffs_end",
+    "dpx_batch_set_score_table", "dpx_batch_diffs_begin", "dpx_batch_diffs_end", "dpx_batch_set_local_direction_table",
 )
 # declared entry points a library may lack and still load (an older build): checked when they are called
 OPTIONAL_SYMBOLS = ("dpx_batch_directions",)
@@ -140,6 +140,7 @@ def load() -> C.CDLL:
     lib.dpx_batch_set_reversed.argtypes = [vp, vp]
     lib.dpx_batch_set_direction_table.argtypes = [vp, vp, C.c_int32, vp]
     lib.dpx_batch_set_score_table.argtypes = [vp, vp, C.c_int32, vp]
+    lib.dpx_batch_set_local_direction_table.argtypes = [vp, vp, C.c_int32, vp]
     lib.dpx_batch_diffs_begin.argtypes = [vp, C.c_uint]
     lib.dpx_batch_diffs_end.argtypes = [vp, C.c_uint, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.POINTER(C.c_uint64))]
     for name in ABI_SYMBOLS:  # every declared entry point must be exported (the optional ones by libraries that have them)
@@ -362,6 +363,17 @@ class Batch:
             return
         tab, code = _table_arrays(scores, code_of)
         _check(self._lib.dpx_batch_set_score_table(self._h, tab.ctypes.data, tab.shape[0], code.ctypes.data), "dpx_batch_set_score_table")
+
+    def set_local_direction_table(self, scores, code_of=None) -> None:
+        """BSW / BASW batches created with KEEP_LOCAL_BAND_DIRECTIONS (band not covering) only: score columns by
+        scores[code_of[ref byte], code_of[qry byte]] in the following fills (set_substitution's arrays; the table need not be symmetric).
+        None clears the table.  Lines and results of an earlier fill are invalid afterwards when the table changed."""
+        if scores is None:
+            _check(self._lib.dpx_batch_set_local_direction_table(self._h, None, 0, None), "dpx_batch_set_local_direction_table")
+            return
+        tab, code = _table_arrays(scores, code_of)
+        _check(self._lib.dpx_batch_set_local_direction_table(self._h, tab.ctypes.data, tab.shape[0], code.ctypes.data),
+               "dpx_batch_set_local_direction_table")
 
     def set_second_gap(self, gap_open2: int, gap_extend2: int) -> None:
         """TWO_PIECE_GAPS batches only: the second gap piece of the following fills; a gap of length k then scores

@@ -68,6 +68,10 @@ hipError_t dpx_launch_bdl_traceback(const dpx_fill_args &a, int numPairs, bool a
                                     hipStream_t stream);
 hipError_t dpx_launch_bdl_export(const uint8_t *codes, const dpx_pair_dev &pr, const char *seq, int band, int which, uint8_t *out,
                                  hipStream_t stream);
+/* dpx_bdlt_kernels.hip -- dpx_launch_bdl_fill's cells, codes, stores and results with the diagonal term of t.tab (k_bdlt_fill;
+ * dpx_batch_set_local_direction_table).  t.f.ldsPerWave includes DPX_SUBST_IMAGE_BYTES behind the staged strings, and the launch asks for
+ * t.f.ldsPerWave * t.f.wavesPerBlock bytes of LDS; t.f.match / mismatch are not read.  Walk and export are the two above. */
+hipError_t dpx_launch_bdlt_fill(const dpx_subst_args &t, int C, bool affine, hipStream_t stream);
 #endif
 
 #endif

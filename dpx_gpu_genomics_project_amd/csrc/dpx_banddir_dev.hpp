@@ -6,8 +6,9 @@
  * Shared as templates (outside the fills' hot loops): window_push, the launch helper of the fills, the two codecs over dpx_banddir.h /
  * dpx_banddir2.h, the walk (banddir_walk) and the export loop (banddir_export).  Shared as text: the fills' frame, dpx_banddir_fill.inc,
  * included inside each fill kernel, and the scan after a step, DPX_BANDDIR_SCAN_AFTER below.  NOT shared, on purpose: bdir_step, bdx_step,
- * bd2_step and bdl_step.  How the same operations are grouped into functions moves the compiler's schedule of these fills
- * (profiles/band_sharing_ab.md); text included inside the kernel does not (profiles/banddir_sharing_ab.md).
+ * bd2_step and bdl_step (the last is dpx_bdl_dev.hpp's, one text for the two local units, dpx_bdl_kernels.hip and dpx_bdlt_kernels.hip).
+ * How the same operations are grouped into functions moves the compiler's schedule of these fills (profiles/band_sharing_ab.md); text
+ * included inside the kernel does not (profiles/banddir_sharing_ab.md).
  */
 #ifndef DPX_BANDDIR_DEV_HPP
 #define DPX_BANDDIR_DEV_HPP

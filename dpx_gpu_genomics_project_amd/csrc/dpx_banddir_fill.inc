@@ -19,7 +19,7 @@
  *                             and whatever else the step's arguments need.  The two callables capture BY VALUE: a capture by reference
  *                             takes the address of a weight, and that reordered the registers of every C = 1 instantiation
  *   DPX_BANDDIR_NO_CELL_H     H of a slot that holds no cell on anti-diagonals 0 and 1: DPX_NEG for the global and extension fills, 0 for the
- *                             local ones (k_bdl_fill), whose neighbours without a cell read H = 0
+ *                             local ones (k_bdl_fill, k_bdlt_fill), whose neighbours without a cell read H = 0
  *   DPX_BANDDIR_STEP(P1_, INTERIOR_, A_)   the unit's own step on anti-diagonal A_, with the unit's own arguments; it may name st, i0, j0,
  *                             lane, m, n, B, cEnd, qL, rL, tabL, codeL of this text
  *

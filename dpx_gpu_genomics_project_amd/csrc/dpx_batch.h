@@ -74,7 +74,7 @@ struct dpx_batch : dpx_plan {
                                   records, and dpx_batch_matrix / dpx_batch_directions mask behind lastDiag */
     Buf<int32_t> dExt{g_tbDevCache};   /* device: dpx_extension[numPairs] */
     /* substitution table (dpx_batch_set_substitution): while substAlphabet > 0 the fills run k_subst_fill and the walks k_subst_traceback*
-     * (band-direction batches: k_bdx_fill; ANW / ASW / ASG direction batches, dpx_batch_set_direction_table: k_dirtab_fill, the walk stays;
+     * (band-direction batches: k_bdx_fill; local band-direction batches, dpx_batch_set_local_direction_table: k_bdlt_fill, the walk stays; ANW / ASW / ASG direction batches, dpx_batch_set_direction_table: k_dirtab_fill, the walk stays;
      * their score-only batches, dpx_batch_set_score_table: k_scoretab_fill / k_scoretab_lanes) */
     int substAlphabet = 0;
     Buf<unsigned char> dSubst{g_tbDevCache}; /* device: the table at row stride 32 (DPX_SUBST_TABLE_BYTES), then codeOf[256] */

@@ -577,6 +577,11 @@ static hipError_t launch_main(dpx_batch *b, const dpx_route &r, hipStream_t s) {
     }
     case DPX_MAIN_BDIR: return dpx_launch_bdir_fill(b->args, b->R, r.ext, s);
     case DPX_MAIN_BDL: return dpx_launch_bdl_fill(b->args, b->R, b->prm.algo == DPX_ALGO_BASW, s);
+    case DPX_MAIN_BDLT: { /* (dpx_batch_set_local_direction_table: every wave's LDS slice grows by the image, and the workgroup may shrink to one wave) */
+        dpx_subst_args ta = subst_args(b);
+        ta.f.wavesPerBlock = dpx_plan_bdx_waves(*b, true);
+        return dpx_launch_bdlt_fill(ta, b->R, b->prm.algo == DPX_ALGO_BASW, s);
+    }
     case DPX_MAIN_BDX: { /* (dpx_batch_set_direction_scoring: with a table every wave's LDS slice grows by the image, and the workgroup may shrink to one wave) */
         dpx_bdx_args xa = {b->args, {nullptr, nullptr}, {r.ext ? b->zdrop : -1, r.ext ? b->endBonus : -1, b->dExt.get()}};
         if (b->substAlphabet) {

@@ -695,8 +695,8 @@ dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus,
     if (p.dirs) {
         r.dirs = true; r.kernel = dir[family];
         r.dirTable = substAlphabet != 0 && family != 0; /* (set only by dpx_batch_set_direction_table, on a DPX_KEEP_DIRECTIONS batch of the three) */
-    } else if (p.bandLocal) { /* (no mode: every setter refuses these batches) */
-        r.main = DPX_MAIN_BDL; r.kernel = DPX_K_BDL_FILL;
+    } else if (p.bandLocal) { /* (a table comes through dpx_batch_set_local_direction_table only; every other setter refuses these batches) */
+        r.main = substAlphabet ? DPX_MAIN_BDLT : DPX_MAIN_BDL; r.kernel = substAlphabet ? DPX_K_BDLT_FILL : DPX_K_BDL_FILL;
     } else if (p.bandDirs) { /* (a mode comes through dpx_batch_set_direction_scoring only; extension mode is BAXT's) */
         const bool bdx = extension || substAlphabet;
         r.main = p.twoPiece ? DPX_MAIN_BD2 : bdx ? DPX_MAIN_BDX : DPX_MAIN_BDIR; r.kernel = p.twoPiece ? DPX_K_BD2_FILL : bdx ? DPX_K_BDX_FILL : DPX_K_BDIR_FILL;
@@ -766,6 +766,9 @@ bool dpx_plan_scoretab_fits(const dpx_plan &p, std::string &err) {
 }
 
 const char *dpx_route_kernel_name(dpx_fill_kernel k) {
+    /* (the table below names the kernels a created batch can run, each with a case in tests/layout_cases.py; the one that only
+     * dpx_batch_set_local_direction_table brings is named here, its layout case is in tests/test_gpu_bdlt.py) */
+    if (k == DPX_K_BDLT_FILL) return "k_bdlt_fill";
     static const char *const names[DPX_K_COUNT] = {
         "k_linear_fill", "k_linear_fill_pk", "k_linear_lanes", "k_linear_lanes_pk", "k_linear_split",
         "k_affine_fill", "k_asw_fill", "k_asg_fill", "k_affine_lanes", "k_asw_lanes", "k_asg_lanes",

@@ -49,7 +49,8 @@ struct dpx_plan {
     bool bandDirs = false; /* DPX_KEEP_BAND_DIRECTIONS on a BANW / BAXT band kernel: codes in dpx_banddir.h's layout, k_bdir_fill through `args`
                               (a covering BANW band is a `dirs` batch of ANW instead) */
     bool bandLocal = false; /* DPX_KEEP_LOCAL_BAND_DIRECTIONS on a BSW / BASW band kernel: a bandDirs plan in the same layout whose kernels are k_bdl_fill,
-                              k_bdl_traceback and k_bdl_export (a covering band is a `dirs` batch of LSW / ASW instead) */
+                              k_bdl_traceback and k_bdl_export (a covering band is a `dirs` batch of LSW / ASW instead); under a table
+                              (dpx_batch_set_local_direction_table) the fill is k_bdlt_fill, walk and export stay */
     bool twoPiece = false; /* ... with DPX_TWO_PIECE_GAPS: 8-bit codes in dpx_banddir2.h's layout, k_bd2_fill; every band <= 256 runs the band kernel */
     int32_t gapOpen2 = 0, gapExtend2 = 0; /* twoPiece: the second gap piece (dpx_batch_set_second_gap; piece 1 until then) */
     bool packed = false;     /* LNW / LSW / BSW with matrices: couples of equal-shaped pairs, two per wave + leftover singles */
@@ -92,9 +93,9 @@ enum dpx_fill_kernel { /* the kernel that fills (most of) the batch: describe's 
     DPX_K_AFFINE_FILL, DPX_K_ASW_FILL, DPX_K_ASG_FILL, DPX_K_AFFINE_LANES, DPX_K_ASW_LANES, DPX_K_ASG_LANES,
     DPX_K_BANDED_FILL, DPX_K_BANDED_FILL_PK, DPX_K_BASW_FILL, DPX_K_BANW_FILL, DPX_K_BAXT_FILL,
     DPX_K_ZEXT_FILL, DPX_K_SUBST_FILL, DPX_K_ZSUB_FILL, DPX_K_BDIR_FILL, DPX_K_BDX_FILL, DPX_K_BD2_FILL,
-    DPX_K_LINEAR_DIR, DPX_K_AFFINE_DIR, DPX_K_ASW_DIR, DPX_K_ASG_DIR, DPX_K_BDL_FILL, DPX_K_COUNT
+    DPX_K_LINEAR_DIR, DPX_K_AFFINE_DIR, DPX_K_ASW_DIR, DPX_K_ASG_DIR, DPX_K_BDL_FILL, DPX_K_BDLT_FILL, DPX_K_COUNT
 };
-enum dpx_main_launch { DPX_MAIN_NONE, DPX_MAIN_FILL, DPX_MAIN_BASW, DPX_MAIN_BANW, DPX_MAIN_BAXT, DPX_MAIN_ZEXT, DPX_MAIN_SUBST, DPX_MAIN_ZSUB, DPX_MAIN_BDIR, DPX_MAIN_BDX, DPX_MAIN_BD2, DPX_MAIN_BDL };
+enum dpx_main_launch { DPX_MAIN_NONE, DPX_MAIN_FILL, DPX_MAIN_BASW, DPX_MAIN_BANW, DPX_MAIN_BAXT, DPX_MAIN_ZEXT, DPX_MAIN_SUBST, DPX_MAIN_ZSUB, DPX_MAIN_BDIR, DPX_MAIN_BDX, DPX_MAIN_BD2, DPX_MAIN_BDL, DPX_MAIN_BDLT };
 enum dpx_second_launch { DPX_SECOND_NONE, DPX_SECOND_PACKED, DPX_SECOND_BANDED_PACKED, DPX_SECOND_LANES, DPX_SECOND_LANES_PK };
 enum dpx_walk_family { DPX_WALK_PLAIN, DPX_WALK_DIR, DPX_WALK_BASW, DPX_WALK_BANW, DPX_WALK_SUBST, DPX_WALK_BDIR, DPX_WALK_BD2, DPX_WALK_BDL };
 enum dpx_export_kind { DPX_EXPORT_PLAIN, DPX_EXPORT_BASW, DPX_EXPORT_BANW };
@@ -116,7 +117,8 @@ struct dpx_route {
 };
 /* What a batch can change after its creation comes as arguments: the traceback walk knob, BAXT's extension mode (-1, -1: off) and the
  * substitution alphabet (0: none).  On a bandDirs plan either of the two (dpx_batch_set_direction_scoring) turns k_bdir_fill into
- * k_bdx_fill; the walk stays k_bdir_traceback.  On a dirs plan of ANW / ASW / ASG the alphabet
+ * k_bdx_fill; the walk stays k_bdir_traceback.  On a bandLocal plan the alphabet (dpx_batch_set_local_direction_table) turns k_bdl_fill
+ * into k_bdlt_fill; the walk stays k_bdl_traceback.  On a dirs plan of ANW / ASW / ASG the alphabet
  * (dpx_batch_set_direction_table) sets dirTable and nothing else; on a score-only plan of the three (dpx_batch_set_score_table) it sets
  * scoreTable and nothing else.  A twoPiece plan runs k_bd2_fill and k_bd2_traceback in every mode; its second piece is
  * the plan's own (the batch IS the plan), so the signatures here do not know it. */

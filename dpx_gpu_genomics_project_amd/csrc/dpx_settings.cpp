@@ -208,6 +208,19 @@ int dpx_batch_set_score_table(dpx_batch *b, const int8_t *scores, int32_t alphab
     return install_table(b, image, alphabet, true);
 }
 
+/* the table of a BSW / BASW local band-direction batch (k_bdlt_fill); a covering band runs k_linear_dir / k_asw_dir and is not admitted */
+int dpx_batch_set_local_direction_table(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf) {
+    if (!b) return DPX_ERR_INVALID;
+    if (!scores) return clear_table(b);
+    if (!table_args_ok(alphabet, codeOf)) return DPX_ERR_INVALID;
+    if (!b->bandLocal) return DPX_ERR_UNSUPPORTED;
+    if (!dpx_plan_bdx_waves(*b, true)) return DPX_ERR_UNSUPPORTED; /* one wave's staged strings leave no room in LDS for the table image */
+    if (!pairs_in_range(b, table_extremes(b, scores, alphabet, alphabet), fits_dir)) return DPX_ERR_RANGE;
+    unsigned char image[DPX_SUBST_IMAGE_BYTES];
+    build_table_image(image, scores, alphabet, codeOf);
+    return install_table(b, image, alphabet, true);
+}
+
 /* ---- orientation: dpx_batch_set_reversed ----
  * The kernels find a pair's strings through the pair table, so the setter builds reversed copies of the flagged pairs' strings on the
  * device (k_reverse_strings) behind a device copy of the batch's bytes, points the flagged pairs at them and the launch arguments'

@@ -13,7 +13,7 @@
 // cs:Z:<text> under -cs, the strings built on the device (dpx_batch_diffs_begin / _end).
 //
 //   dpx_main -pairs <file> [-match 3] [-mismatch -1] [-open -2 | -gap -2] [-extend -1]
-//            [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band 128] [-batch N | -pool-gb 4] [-inflight K] [-tune 0|1] [-device 0] [-noprint] [-pack2] [-directions] [-cigar [M] [-md] [-cs]] [-zdrop Z] [-endbonus E] [-matrix FILE] [-open2 O2 -extend2 E2] [-reverse] [-producer P] [-rank r -world w]
+//            [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band 128] [-batch N | -pool-gb 4] [-inflight K] [-tune 0|1] [-device 0] [-noprint] [-pack2] [-directions] [-cigar [M] [-md] [-cs]] [-zdrop Z] [-endbonus E] [-matrix FILE] [-localmatrix FILE] [-open2 O2 -extend2 E2] [-reverse] [-producer P] [-rank r -world w]
 //
 // -matrix FILE (BANW / BAXT, not with -zdrop / -endbonus): score columns by a substitution matrix (dpx_batch_set_substitution) instead of
 // -match / -mismatch.  NCBI text format: '#' lines are comments; one header row of 1..32 single-character column letters; then one row
@@ -21,6 +21,8 @@
 // upper-case letter's code, every other unlisted byte the last letter's ('*' in NCBI files, 'N' in a DNA file).
 // -directions with -algo BSW|BASW keeps band direction codes too (DPX_KEEP_LOCAL_BAND_DIRECTIONS, k_bdl_fill): int32 scores, so pairs run that
 // the int16 matrices refuse, and the output is what the run without -directions prints.
+// -localmatrix FILE (only with -algo BSW|BASW -directions): a -matrix file for those batches, through dpx_batch_set_local_direction_table
+// (k_bdlt_fill); composes with -cigar [M] -md -cs.  -matrix itself stays a usage error there.
 // -directions with -algo BANW|BAXT keeps band direction codes (DPX_KEEP_BAND_DIRECTIONS); -zdrop / -endbonus / -matrix then go through
 // dpx_batch_set_direction_scoring (k_bdx_fill) and print what the run without -directions prints.
 // -directions with -algo ANW|ASW|ASG takes -matrix too: the table goes through dpx_batch_set_direction_table (k_dirtab_fill: int32 scores
@@ -142,6 +144,7 @@ static void usage() {
                     "[-extend <gapExtend>] [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band <B>] [-batch <N>] [-device <D>] [-noprint] [-cigar [M]] [-md] [-cs] (only with -cigar: NM:i:, MD:Z: and cs:Z: fields behind the CIGAR) "
                     "[-zdrop <Z>] [-endbonus <E>] (BAXT only) [-matrix <file>] (BANW / BAXT, not with -zdrop / -endbonus; ANW / ASW / ASG only with -directions) "
                     "[-directions] (direction codes instead of score matrices; -algo BSW|BASW -directions: one code per in-band cell, long pairs run; BANW / BAXT: with -zdrop / -endbonus / -matrix too; -algo ANW|ASW|ASG -directions -matrix <file>: full-matrix affine alignment under a substitution matrix) "
+                    "[-localmatrix <file>] (a -matrix file for the local band-direction batches: only with -algo BSW|BASW -directions, not with -matrix) "
                     "[-open2 <O2> -extend2 <E2>] (two-piece gaps: both together, only with -directions and -algo BANW|BAXT) "
                     "[-scores] (score-only batches: one line '<number> | <score> | <endRow> <endCol>' per pair; not with -directions / -cigar / -zdrop / -endbonus / -open2 / -extend2 / -reverse; -matrix <file> with it only for -algo ANW|ASW|ASG; batches of 20000 pairs unless -batch says otherwise) "
                     "[-reverse] (align every pair right to left on the device, output in the file's orientation; only with -algo BANW|BAXT)\n");
@@ -167,6 +170,7 @@ int main(int argc, char *argv[]) {
     bool scoresOnly = false; // -scores: score-only batches (DPX_SCORE_ONLY), one "<number> | <score> | <endRow> <endCol>" line per pair from dpx_batch_results
     bool reverse = false;    // -reverse: every pair of every batch is reversed on the device (dpx_batch_set_reversed)
     const char *matrixFile = nullptr; // -matrix: a substitution table (dpx_batch_set_substitution) on every batch
+    const char *localMatrixFile = nullptr; // -localmatrix: a substitution table (dpx_batch_set_local_direction_table) on every BSW / BASW band-direction batch
     int inflight = 3;      // batches on the device at a time (= matrix pools reserved)
     int tuneFlag = -1;     // -1: by the length of the job
     std::string algoName = "LSW";
@@ -197,6 +201,7 @@ int main(int argc, char *argv[]) {
         else if (!strcmp(argv[i], "-zdrop")) zdrop = atoi(next("-zdrop"));
         else if (!strcmp(argv[i], "-endbonus")) endBonus = atoi(next("-endbonus"));
         else if (!strcmp(argv[i], "-matrix")) matrixFile = next("-matrix");
+        else if (!strcmp(argv[i], "-localmatrix")) localMatrixFile = next("-localmatrix");
         else if (!strcmp(argv[i], "-open2")) { gapOpen2 = atoi(next("-open2")); haveOpen2 = true; }
         else if (!strcmp(argv[i], "-extend2")) { gapExtend2 = atoi(next("-extend2")); haveExtend2 = true; }
         else if (!strcmp(argv[i], "-reverse")) reverse = true;
@@ -234,6 +239,14 @@ int main(int argc, char *argv[]) {
         std::string why;
         if (!read_matrix(matrixFile, substScores, substAlphabet, substCode, why)) {
             fprintf(stderr, "-matrix %s: %s\n", matrixFile, why.c_str());
+            usage();
+        }
+    }
+    if (localMatrixFile) {
+        if (matrixFile || !directions || (algo != DPX_ALGO_BSW && algo != DPX_ALGO_BASW)) usage();
+        std::string why;
+        if (!read_matrix(localMatrixFile, substScores, substAlphabet, substCode, why)) {
+            fprintf(stderr, "-localmatrix %s: %s\n", localMatrixFile, why.c_str());
             usage();
         }
     }
@@ -427,6 +440,8 @@ int main(int argc, char *argv[]) {
             if ((zdrop != -1 || endBonus != -1 || matrixFile) &&
                 (prc = dpx_batch_set_direction_scoring(next.b, zdrop, endBonus, matrixFile ? substScores.data() : nullptr, substAlphabet, substCode)) != DPX_OK)
                 die(matrixFile ? "FAILED TO SET THE SUBSTITUTION MATRIX" : "FAILED TO SET THE EXTENSION MODE", prc);
+        } else if (localMatrixFile) { // (a covering band is refused here: it runs k_linear_dir / k_asw_dir, which take no table)
+            if ((prc = dpx_batch_set_local_direction_table(next.b, substScores.data(), substAlphabet, substCode)) != DPX_OK) die("FAILED TO SET THE SUBSTITUTION MATRIX", prc);
         } else if (directionTable) {
             if ((prc = dpx_batch_set_direction_table(next.b, substScores.data(), substAlphabet, substCode)) != DPX_OK) die("FAILED TO SET THE SUBSTITUTION MATRIX", prc);
         } else if (scoreTable) {

@@ -241,8 +241,9 @@ typedef struct dpx_params {
                                     DPX_ERR_UNSUPPORTED where one wave's do not.  DPX_TIME_FILLS, dpx_batch_fill_timed, repeated fills, a caller's
                                     stream, dpx_batch_create_on, packed2 input, the output pipeline and dpx_batch_cigars_* as for a BSW / BASW
                                     matrix batch; DPX_TB_WALK has no effect (one walk, k_bdl_traceback).  Every setter refuses as it does for
-                                    a BSW / BASW matrix batch (substitution tables, z-drop, end bonus, two-piece gaps and reversed pairs are
-                                    not built for these batches), and leaves the batch as it was.
+                                    a BSW / BASW matrix batch (z-drop, end bonus, two-piece gaps and reversed pairs are not built for these
+                                    batches), and leaves the batch as it was; a substitution table comes through the batches' own setter,
+                                    dpx_batch_set_local_direction_table (k_bdlt_fill).
                                     Added without an ABI bump or a new symbol.  Detecting it: a library that predates the flag ignores the
                                     bit and builds an int16 matrix batch -- dpx_batch_describe then shows kernel=k_banded_fill /
                                     k_banded_fill_pk / k_basw_fill (this library: kernel=k_bdl_fill, or k_linear_dir / k_asw_dir under a
@@ -795,6 +796,44 @@ int dpx_batch_set_direction_table(dpx_batch *b, const int8_t *scores, int32_t al
  * dpx_batch_set_direction_table keep refusing these batches; matrix requests stay DPX_ERR_NO_MATRIX.  Repeated fills, DPX_TIME_FILLS,
  * dpx_batch_fill_timed, a caller's stream, dpx_batch_create_on, packed2 input and pairs that share bytes as for any score-only batch. */
 int dpx_batch_set_score_table(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf /* 256 entries */);
+
+/* ---- substitution-matrix scoring of BSW and BASW local band-direction batches ----
+ * A DPX_KEEP_LOCAL_BAND_DIRECTIONS batch is the only local alignment that runs past ~10-16 kb: a long noisy read aligned locally against
+ * a window, where N must not match N and soft-masked lower case must fold; transition / transversion weights; a banded local protein
+ * alignment under a 20-24 letter matrix that realigns the hits a score-only table batch found.  This setter gives those batches a table.
+ * A new exported symbol, no ABI bump and no new flag: detect it by the symbol.
+ *   Definition.  BSW's / BASW's block above as a DPX_KEEP_LOCAL_BAND_DIRECTIONS batch computes it, word for word, with one change: the
+ *     diagonal term of every in-band cell is
+ *         H[i-1][j-1] + scores[codeOf[r] * alphabet + codeOf[q]]
+ *     for the reference byte r and the query byte q (the row is the reference code; the table need not be symmetric).  params.match /
+ *     params.mismatch are ignored.  The zero floor, the H = 0 read from every neighbour without a cell, the tie orders, the codes, the
+ *     end-cell rule (first maximum in row-major order, (0, 0) when every H is 0) and the walk that stops where H == 0 do not change.
+ *   Text.  The relation line, the CIGAR's '=' / 'X', MD / cs and the MATCH / MISMATCH enum of dpx_batch_directions stay byte equality,
+ *     as under dpx_batch_set_substitution.
+ *   Arguments.  dpx_batch_set_substitution's: entries are int8, 1 <= alphabet <= 32, codeOf has 256 entries, each < alphabet; both arrays
+ *     are copied at the call; scores == NULL clears the table (the other arguments are ignored), is legal on every batch and changes
+ *     nothing where nothing was set.  A batch holds one table, and NULL through any table setter clears it.
+ *   Lifecycle.  dpx_batch_set_substitution's: the setting applies to every following fill; a call that changes it invalidates results,
+ *     lines, text, CIGARs and difference strings of an earlier fill (DPX_ERR_NOT_FILLED until the next fill);
+ *     setting the same table again invalidates nothing; a refused call leaves the previous setting in force and dpx_batch_describe
+ *     byte-identical.
+ *   Statuses, in this order, every check before the first change:
+ *   DPX_ERR_INVALID      b == NULL; with scores != NULL: alphabet outside 1..32, codeOf == NULL, or a codeOf[x] >= alphabet
+ *   DPX_ERR_UNSUPPORTED  anything but a DPX_ALGO_BSW / DPX_ALGO_BASW batch created with DPX_KEEP_LOCAL_BAND_DIRECTIONS whose band does not
+ *                        cover the matrix: matrix and DPX_SCORE_ONLY batches, every other algorithm, BANW / BAXT band-direction batches
+ *                        (dpx_batch_set_direction_scoring is theirs), and a covering BSW / BASW band, which runs k_linear_dir / k_asw_dir
+ *   DPX_ERR_UNSUPPORTED  one wave's staged strings leave no room in LDS for the 1280-byte table image
+ *   DPX_ERR_RANGE        the create-time range check of the batch (LSW's / ASW's bounds against 2^28) fails for a pair with the table's
+ *                        largest entry in place of match and its smallest in place of mismatch
+ * While a table is set dpx_batch_describe says kernel=k_bdlt_fill, keeps traceback=k_bdl_traceback and matrix=banddir4 and adds
+ * ` subst=<alphabet>` between them.  Every wave keeps the table image in LDS behind its staged strings; where four waves' strings and
+ * images no longer fit a workgroup the fill runs one-wave workgroups (waves_per_workgroup says what will launch).  The seven other
+ * setters (dpx_batch_set_extension, dpx_batch_set_substitution with a table, dpx_batch_set_extension_table, dpx_batch_set_second_gap,
+ * dpx_batch_set_direction_scoring, dpx_batch_set_direction_table, dpx_batch_set_score_table with a table; dpx_batch_set_reversed too)
+ * keep refusing these batches, table set or not.  Not built: covering bands, reversed pairs, two-piece gaps and extension settings on
+ * local batches, a table through dpx_align_batch.  Repeated fills, DPX_TIME_FILLS, dpx_batch_fill_timed, a caller's stream,
+ * dpx_batch_create_on, packed2 input, the output pipeline, dpx_batch_cigars_* and dpx_batch_diffs_* as for any local band-direction batch. */
+int dpx_batch_set_local_direction_table(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf /* 256 entries */);
 
 /* Sizes: numPairs, total cells (sum refLen*queryLen, the reference's numCells, c++/parseInput.cpp:100),
  * bytes of HBM the matrices occupy, algorithmic bytes of one fill. */
