@@ -19,6 +19,7 @@ KEEP_MATRICES, SCORE_ONLY, TIME_FILLS, TUNE_PLACEMENT, KEEP_DIRECTIONS = 0x0, 0x
 KEEP_BAND_DIRECTIONS = 0x10  # BANW / BAXT: 4-bit direction codes per in-band cell, int32 scores (0x8 stays refused on banded algorithms)
 KEEP_LOCAL_BAND_DIRECTIONS = 0x40  # BSW / BASW: 4-bit direction codes per in-band cell, int32 scores (0x8 and 0x10 stay refused on them)
 TWO_PIECE_GAPS = 0x20  # with KEEP_BAND_DIRECTIONS: a second gap piece (Batch.set_second_gap), 8-bit codes, bands up to 256
+LOCAL_TWO_PIECE_GAPS = 0x80  # with KEEP_LOCAL_BAND_DIRECTIONS on BASW: a second gap piece (Batch.set_second_gap), 8-bit codes, bands up to 256
 MAT_H, MAT_I, MAT_D = 0, 1, 2
 MAT_I2, MAT_D2, MAT_H_PIECE = 3, 4, 5  # Batch.directions on a TWO_PIECE_GAPS batch: piece 2's planes, and the piece of H's gap move
 # CIGARs (dpx_batch_cigars_begin / _end): an op is (length << 4) | code with BAM's code numbers
@@ -367,7 +368,8 @@ class Batch:
     def set_local_direction_table(self, scores, code_of=None) -> None:
         """BSW / BASW batches created with KEEP_LOCAL_BAND_DIRECTIONS (band not covering) only: score columns by
         scores[code_of[ref byte], code_of[qry byte]] in the following fills (set_substitution's arrays; the table need not be symmetric).
-        None clears the table.  Lines and results of an earlier fill are invalid afterwards when the table changed."""
+        None clears the table.  Lines and results of an earlier fill are invalid afterwards when the table changed.  A
+        LOCAL_TWO_PIECE_GAPS batch takes the same setter."""
         if scores is None:
             _check(self._lib.dpx_batch_set_local_direction_table(self._h, None, 0, None), "dpx_batch_set_local_direction_table")
             return
@@ -376,7 +378,7 @@ class Batch:
                "dpx_batch_set_local_direction_table")
 
     def set_second_gap(self, gap_open2: int, gap_extend2: int) -> None:
-        """TWO_PIECE_GAPS batches only: the second gap piece of the following fills; a gap of length k then scores
+        """TWO_PIECE_GAPS and LOCAL_TWO_PIECE_GAPS batches only: the second gap piece of the following fills; a gap of length k then scores
         max(gap_open + k * gap_extend, gap_open2 + k * gap_extend2).  Lines and results of an earlier fill are invalid afterwards when a
         value changed."""
         _check(self._lib.dpx_batch_set_second_gap(self._h, gap_open2, gap_extend2), "dpx_batch_set_second_gap")

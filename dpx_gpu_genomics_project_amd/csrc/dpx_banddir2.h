@@ -59,6 +59,20 @@ hipError_t dpx_launch_bd2_traceback(const dpx_fill_args &a, int numPairs, const 
 /* one pair's plane `which`: 0 H, 1 I (piece 1), 2 D (piece 1), 3 I2, 4 D2 as c++/backtrack.h's enums, 5 the piece of H's gap move */
 hipError_t dpx_launch_bd2_export(const uint8_t *codes, const dpx_pair_dev &pr, const char *seq, int band, int which, uint8_t *out,
                                  hipStream_t stream);
+
+/* dpx_lb2_kernels.hip: the local twin (DPX_KEEP_LOCAL_BAND_DIRECTIONS | DPX_LOCAL_TWO_PIECE_GAPS on BASW), the same byte code and layout;
+ * move 0 is a cell with H == 0.  k_lb2_fill: `tab` as above, no scan; piece 1 is f.gapOpen / f.gapExtend. */
+typedef struct dpx_lb2_args {
+    dpx_fill_args f;
+    dpx_table_ref tab;
+    int32_t gapOpen2, gapExtend2;
+} dpx_lb2_args;
+hipError_t dpx_launch_lb2_fill(const dpx_lb2_args &a, int C, hipStream_t stream);
+/* dpx_launch_bdl_traceback's contract over the byte codes (five states, the walk ends on H == 0, no tails) */
+hipError_t dpx_launch_lb2_traceback(const dpx_fill_args &a, int numPairs, const uint64_t *tbOff, char *tb, int32_t *tbLen, hipStream_t stream);
+/* dpx_launch_bd2_export's six selectors under the local export's rule: every plane 0 on the borders and outside the band */
+hipError_t dpx_launch_lb2_export(const uint8_t *codes, const dpx_pair_dev &pr, const char *seq, int band, int which, uint8_t *out,
+                                 hipStream_t stream);
 #endif
 
 #endif

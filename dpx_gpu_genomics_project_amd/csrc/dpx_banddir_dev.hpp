@@ -1,12 +1,13 @@
 /*
  * dpx_banddir_dev.hpp -- device code shared by the band-direction units: dpx_banddir_kernels.hip (4-bit codes), dpx_bdx_kernels.hip
- * (the same under a table and / or BAXT's extension mode), dpx_bd2_kernels.hip (two-piece gaps, 8-bit codes) and dpx_bdl_kernels.hip
- * (BSW / BASW: the local forms of walk and export, LOCAL below).
+ * (the same under a table and / or BAXT's extension mode), dpx_bd2_kernels.hip (two-piece gaps, 8-bit codes), dpx_bdl_kernels.hip
+ * (BSW / BASW: the local forms of walk and export, LOCAL below) and dpx_lb2_kernels.hip (BASW under two gap pieces: LOCAL over the
+ * 8-bit codes).
  *
  * Shared as templates (outside the fills' hot loops): window_push, the launch helper of the fills, the two codecs over dpx_banddir.h /
  * dpx_banddir2.h, the walk (banddir_walk) and the export loop (banddir_export).  Shared as text: the fills' frame, dpx_banddir_fill.inc,
  * included inside each fill kernel, and the scan after a step, DPX_BANDDIR_SCAN_AFTER below.  NOT shared, on purpose: bdir_step, bdx_step,
- * bd2_step and bdl_step (the last is dpx_bdl_dev.hpp's, one text for the two local units, dpx_bdl_kernels.hip and dpx_bdlt_kernels.hip).
+ * bd2_step, lb2_step and bdl_step (the last is dpx_bdl_dev.hpp's, one text for the two local units, dpx_bdl_kernels.hip and dpx_bdlt_kernels.hip).
  * How the same operations are grouped into functions moves the compiler's schedule of these fills (profiles/band_sharing_ab.md); text
  * included inside the kernel does not (profiles/banddir_sharing_ab.md).
  */
@@ -104,9 +105,9 @@ struct ByteCodec { /* dpx_banddir2.h: moves 1-5 in bits 0-2, I1 / D1 / I2 / D2 e
  * SCORING, its row in an I plane, its column in a D plane) and a ballot gives the number of cells the path really follows; a cell below
  * the ring ends the run early, and the next trip slides the ring.  In SCORING the cell's move names the plane; in a gap state the walk
  * follows that plane's own extend bit.  Then ANW's two tails.  `ring` is the kernel's own kRingBytes of LDS.
- * LOCAL (k_bdl_traceback, BSW / BASW): the walk stops in SCORING on the first cell whose H is 0 -- BSW (`linear`): bit 2 of its code,
- * BASW: move 0; a cell without a code (border, outside the band) has H = 0 too -- and there are no tails.  BSW has no gap states: a gap
- * move is a single step and the next cell is read in SCORING.
+ * LOCAL (k_bdl_traceback, BSW / BASW; k_lb2_traceback, BASW under two gap pieces): the walk stops in SCORING on the first cell whose H
+ * is 0 -- BSW (`linear`): bit 2 of its code, BASW: move 0 under the codec's move mask; a cell without a code (border, outside the band)
+ * has H = 0 too -- and there are no tails.  BSW has no gap states: a gap move is a single step and the next cell is read in SCORING.
  * ----------------------------------------------------------------------------------------------------- */
 constexpr int kRing = 16; /* chunks in LDS */
 constexpr int kRingBytes = kRing * (int)DPX_BANDDIR_CHUNK_BYTES;
@@ -168,7 +169,7 @@ __device__ __forceinline__ void banddir_walk(unsigned char *ring, const dpx_fill
         const int c0 = code(i, j); /* the walker's own cell: the same byte for every lane */
         if (c0 < 0) break;         /* (global: cannot happen, the walker stands on a stored cell of the ring's upper half; LOCAL: a border cell or one outside the band, H = 0) */
         if constexpr (LOCAL) { /* H == 0 ends the walk where it stands in SCORING: BSW's bit 2, BASW's move 0 */
-            if (cur == 0 && (linear ? (c0 & 4) != 0 : (c0 & 3) == 0)) break;
+            if (cur == 0 && (linear ? (c0 & 4) != 0 : (c0 & Codec::kMoveMask) == 0)) break;
         }
         const int kind = cur != 0 ? cur : Codec::move(c0);
         if (!Codec::is_move(kind)) break; /* (cannot happen: a stored cell has a move) */

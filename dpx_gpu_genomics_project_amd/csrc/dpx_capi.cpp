@@ -554,6 +554,15 @@ static int create_impl(int device, const dpx_params *params, const char *sequenc
  * looks like one operation (events recorded on `s` around it time all of it). */
 
 static hipError_t launch_main(dpx_batch *b, const dpx_route &r, hipStream_t s) { /* the one-wave-per-pair kernel of the batch's algorithm */
+    if (r.main == DPX_MAIN_LB2) { /* (DPX_LOCAL_TWO_PIECE_GAPS: k_lb2_fill with and without a table; the table's LDS as for k_bdlt_fill.  In front of
+                                   * the switch: the value is declared behind dpx_main_launch's enumerator list, dpx_plan.h) */
+        dpx_lb2_args xa = {b->args, {nullptr, nullptr}, b->gapOpen2, b->gapExtend2};
+        if (b->substAlphabet) {
+            xa.tab = table_ref(b);
+            xa.f.ldsPerWave += DPX_SUBST_IMAGE_BYTES; xa.f.wavesPerBlock = dpx_plan_bdx_waves(*b, true);
+        }
+        return dpx_launch_lb2_fill(xa, b->R, s);
+    }
     switch (r.main) {
     case DPX_MAIN_NONE: return hipSuccess;
     case DPX_MAIN_FILL:
@@ -777,7 +786,8 @@ int dpx_batch_directions(dpx_batch *b, size_t pair, int which, uint8_t *out) {
     Buf<uint8_t> dOut(g_tbDevCache); /* row-major scratch */
     HIP_TRY(wait_for_fill(b));
     HIP_TRY(dOut.ensure(std::max<size_t>(total, 16)));
-    hipError_t e = b->twoPiece ? dpx_launch_bd2_export(reinterpret_cast<const uint8_t *>(b->dMat.get()), pd, b->dSeq, b->prm.band, which, dOut.get(), b->stream)
+    hipError_t e = (b->twoPiece && b->bandLocal) ? dpx_launch_lb2_export(reinterpret_cast<const uint8_t *>(b->dMat.get()), pd, b->dSeq, b->prm.band, which, dOut.get(), b->stream)
+                   : b->twoPiece ? dpx_launch_bd2_export(reinterpret_cast<const uint8_t *>(b->dMat.get()), pd, b->dSeq, b->prm.band, which, dOut.get(), b->stream)
                    : b->bandLocal ? dpx_launch_bdl_export(reinterpret_cast<const uint8_t *>(b->dMat.get()), pd, b->dSeq, b->prm.band, which, dOut.get(), b->stream)
                    : b->bandDirs ? dpx_launch_bdir_export(reinterpret_cast<const uint8_t *>(b->dMat.get()), pd, b->dSeq, b->prm.band, which, dOut.get(), b->stream)
                                  : dpx_launch_export_dir(reinterpret_cast<const uint8_t *>(b->dMat.get()), pd, b->dSeq, b->kernelAlgo, b->R, which, dOut.get(), b->stream);

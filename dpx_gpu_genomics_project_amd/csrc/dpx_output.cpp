@@ -38,6 +38,7 @@ static int lines_behind_fill(dpx_batch *b, hipEvent_t started = nullptr) {
     case DPX_WALK_BDIR: HIP_TRY(dpx_launch_bdir_traceback(b->args, n, b->dTbOff, b->dTb.get(), b->dTbLen, b->stream)); break;
     case DPX_WALK_BD2: HIP_TRY(dpx_launch_bd2_traceback(b->args, n, b->dTbOff, b->dTb.get(), b->dTbLen, b->stream)); break;
     case DPX_WALK_BDL: HIP_TRY(dpx_launch_bdl_traceback(b->args, n, b->prm.algo == DPX_ALGO_BASW, b->dTbOff, b->dTb.get(), b->dTbLen, b->stream)); break;
+    case DPX_WALK_LB2: HIP_TRY(dpx_launch_lb2_traceback(b->args, n, b->dTbOff, b->dTb.get(), b->dTbLen, b->stream)); break;
     }
     /* reversed pairs (dpx_batch_set_reversed): their lines come out of the walk in the reversed frame and are turned round here, once */
     if (b->revCount) HIP_TRY(dpx_launch_flip_lines(b->dPairs, b->dFlagged, (int)b->revCount, b->dTbLen, b->dTbOff, b->dTb.get(), b->stream));

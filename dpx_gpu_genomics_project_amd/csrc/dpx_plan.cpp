@@ -329,12 +329,15 @@ int choose_kernel(const Knobs &kn, dpx_plan &p, int &R) {
     /* DPX_KEEP_BAND_DIRECTIONS: a covering BANW band takes the matrix batch's fall-back to ANW, as an ANW direction batch; every other band
      * runs k_bdir_fill */
     const bool bandDirFlag = (p.flags & DPX_KEEP_BAND_DIRECTIONS) != 0;
-    p.twoPiece = bandDirFlag && (p.flags & DPX_TWO_PIECE_GAPS) != 0; /* (no ANW fall-back: ANW has no second piece) */
+    const bool localFlag = (p.flags & DPX_KEEP_LOCAL_BAND_DIRECTIONS) != 0;
+    /* (no ANW / ASW fall-back: neither has a second piece; dpx_plan_batch has paired each two-piece flag with its storage flag) */
+    p.twoPiece = (bandDirFlag && (p.flags & DPX_TWO_PIECE_GAPS) != 0) || (localFlag && (p.flags & DPX_LOCAL_TWO_PIECE_GAPS) != 0);
     p.gapOpen2 = prm.gapOpen; p.gapExtend2 = prm.gapExtend;
     const bool bandDirCovering = bandDirFlag && !p.twoPiece && prm.algo == DPX_ALGO_BANW && (long long)prm.band >= longest + 1;
     /* DPX_KEEP_LOCAL_BAND_DIRECTIONS (BSW / BASW; dpx_plan_batch has refused every other algorithm): a covering band takes the matrix batch's
-     * fall-back to LSW / ASW, as a direction batch of that algorithm; every other band runs k_bdl_fill */
-    const bool localFlag = (p.flags & DPX_KEEP_LOCAL_BAND_DIRECTIONS) != 0, localCovering = localFlag && (long long)prm.band >= longest;
+     * fall-back to LSW / ASW, as a direction batch of that algorithm; every other band runs k_bdl_fill (two pieces: k_lb2_fill, covering
+     * or not) */
+    const bool localCovering = localFlag && !p.twoPiece && (long long)prm.band >= longest;
     p.bandLocal = localFlag && !localCovering;
     p.dirs = (p.flags & DPX_KEEP_DIRECTIONS) != 0 || bandDirCovering || localCovering; p.bandDirs = (bandDirFlag && !bandDirCovering) || p.bandLocal; p.kernelAlgo = prm.algo;
     /* rows per lane: smallest tile that keeps short queries in one stripe, 8 (or DPX_R) otherwise */
@@ -345,7 +348,7 @@ int choose_kernel(const Knobs &kn, dpx_plan &p, int &R) {
     const int v = kn.rowsPerLane;
     R = (v == 2 || v == 4 || v == 8 || (v == 16 && wide)) ? v : p.maxM <= 128 ? 2 : p.maxM <= 256 ? 4 : (p.maxM <= 512 || !wide) ? 8 : 16;
     if (!is_banded(prm.algo)) return DPX_OK;
-    if (p.twoPiece) { /* k_bd2_fill holds <= 4 cells per lane, covering band or not */
+    if (p.twoPiece) { /* k_bd2_fill and k_lb2_fill hold <= 4 cells per lane, covering band or not */
         if (prm.band > DPX_BANDDIR2_MAX_BAND) return DPX_ERR_UNSUPPORTED;
         R = dpx_band_cpl(prm.band);
         return DPX_OK;
@@ -649,6 +652,10 @@ int dpx_plan_batch(const dpx_params &params, const dpx_seq_pair *pairs, size_t f
         if (params.algo != DPX_ALGO_BSW && params.algo != DPX_ALGO_BASW) return DPX_ERR_UNSUPPORTED;
         if (flags & DPX_KEEP_DIRECTIONS) return DPX_ERR_UNSUPPORTED; /* 0x8 on a banded algorithm stays refused */
     }
+    if (flags & DPX_LOCAL_TWO_PIECE_GAPS) { /* legal only together with DPX_KEEP_LOCAL_BAND_DIRECTIONS (whose own checks came first), on BASW: BSW has one linear gap weight */
+        if (!(flags & DPX_KEEP_LOCAL_BAND_DIRECTIONS) || (flags & (DPX_SCORE_ONLY | DPX_KEEP_BAND_DIRECTIONS | DPX_TWO_PIECE_GAPS))) return DPX_ERR_INVALID;
+        if (params.algo != DPX_ALGO_BASW) return DPX_ERR_UNSUPPORTED;
+    }
     if (flags & DPX_TWO_PIECE_GAPS) { /* legal only together with DPX_KEEP_BAND_DIRECTIONS, on the algorithms that flag serves */
         if (!(flags & DPX_KEEP_BAND_DIRECTIONS)) return DPX_ERR_INVALID;
         if (params.algo != DPX_ALGO_BANW && params.algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED;
@@ -696,7 +703,8 @@ dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus,
         r.dirs = true; r.kernel = dir[family];
         r.dirTable = substAlphabet != 0 && family != 0; /* (set only by dpx_batch_set_direction_table, on a DPX_KEEP_DIRECTIONS batch of the three) */
     } else if (p.bandLocal) { /* (a table comes through dpx_batch_set_local_direction_table only; every other setter refuses these batches) */
-        r.main = substAlphabet ? DPX_MAIN_BDLT : DPX_MAIN_BDL; r.kernel = substAlphabet ? DPX_K_BDLT_FILL : DPX_K_BDL_FILL;
+        if (p.twoPiece) { r.main = DPX_MAIN_LB2; r.kernel = DPX_K_LB2_FILL; } /* (DPX_LOCAL_TWO_PIECE_GAPS: one kernel with and without a table) */
+        else { r.main = substAlphabet ? DPX_MAIN_BDLT : DPX_MAIN_BDL; r.kernel = substAlphabet ? DPX_K_BDLT_FILL : DPX_K_BDL_FILL; }
     } else if (p.bandDirs) { /* (a mode comes through dpx_batch_set_direction_scoring only; extension mode is BAXT's) */
         const bool bdx = extension || substAlphabet;
         r.main = p.twoPiece ? DPX_MAIN_BD2 : bdx ? DPX_MAIN_BDX : DPX_MAIN_BDIR; r.kernel = p.twoPiece ? DPX_K_BD2_FILL : bdx ? DPX_K_BDX_FILL : DPX_K_BDIR_FILL;
@@ -724,9 +732,9 @@ dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus,
                    : p.packed ? DPX_K_LINEAR_FILL_PK : p.lanesPk ? DPX_K_LINEAR_LANES_PK : p.lanePacked ? DPX_K_LINEAR_LANES : p.split ? DPX_K_LINEAR_SPLIT : DPX_K_LINEAR_FILL;
     }
     r.extRecords = r.main == DPX_MAIN_ZEXT || r.main == DPX_MAIN_ZSUB || ((r.main == DPX_MAIN_BDX || r.main == DPX_MAIN_BD2) && extension);
-    r.walk = p.bandLocal ? DPX_WALK_BDL : p.twoPiece ? DPX_WALK_BD2 : p.bandDirs ? DPX_WALK_BDIR : (substAlphabet && !p.dirs && !r.scoreTable) ? DPX_WALK_SUBST : algo == DPX_ALGO_BASW ? DPX_WALK_BASW : is_banw_layout(algo) ? DPX_WALK_BANW
+    r.walk = p.bandLocal ? (p.twoPiece ? DPX_WALK_LB2 : DPX_WALK_BDL) : p.twoPiece ? DPX_WALK_BD2 : p.bandDirs ? DPX_WALK_BDIR : (substAlphabet && !p.dirs && !r.scoreTable) ? DPX_WALK_SUBST : algo == DPX_ALGO_BASW ? DPX_WALK_BASW : is_banw_layout(algo) ? DPX_WALK_BANW
              : p.dirs ? DPX_WALK_DIR : DPX_WALK_PLAIN;
-    r.walkMode = (r.walk == DPX_WALK_BDL || r.walk == DPX_WALK_BD2 || r.walk == DPX_WALK_BDIR || r.walk == DPX_WALK_DIR) ? 0 : walk_mode(p, tbWalk); /* (one walk: DPX_TB_WALK has no effect) */
+    r.walkMode = (r.walk == DPX_WALK_BDL || r.walk == DPX_WALK_LB2 || r.walk == DPX_WALK_BD2 || r.walk == DPX_WALK_BDIR || r.walk == DPX_WALK_DIR) ? 0 : walk_mode(p, tbWalk); /* (one walk: DPX_TB_WALK has no effect) */
     r.exportKind = is_banw_layout(algo) /* (BAXT stores what BANW stores) */ ? DPX_EXPORT_BANW : algo == DPX_ALGO_BASW ? DPX_EXPORT_BASW : DPX_EXPORT_PLAIN;
     return r;
 }
@@ -769,6 +777,7 @@ const char *dpx_route_kernel_name(dpx_fill_kernel k) {
     /* (the table below names the kernels a created batch can run, each with a case in tests/layout_cases.py; the one that only
      * dpx_batch_set_local_direction_table brings is named here, its layout case is in tests/test_gpu_bdlt.py) */
     if (k == DPX_K_BDLT_FILL) return "k_bdlt_fill";
+    if (k == DPX_K_LB2_FILL) return "k_lb2_fill"; /* (DPX_LOCAL_TWO_PIECE_GAPS; its layout cases are in tests/test_gpu_lb2.py) */
     static const char *const names[DPX_K_COUNT] = {
         "k_linear_fill", "k_linear_fill_pk", "k_linear_lanes", "k_linear_lanes_pk", "k_linear_split",
         "k_affine_fill", "k_asw_fill", "k_asg_fill", "k_affine_lanes", "k_asw_lanes", "k_asg_lanes",
@@ -789,6 +798,7 @@ const char *dpx_route_walk_name(dpx_walk_family walk, int walkMode) {
     case DPX_WALK_BDIR: return "k_bdir_traceback";
     case DPX_WALK_BD2: return "k_bd2_traceback";
     case DPX_WALK_BDL: return "k_bdl_traceback";
+    case DPX_WALK_LB2: return "k_lb2_traceback";
     }
     return "?";
 }

@@ -51,7 +51,8 @@ struct dpx_plan {
     bool bandLocal = false; /* DPX_KEEP_LOCAL_BAND_DIRECTIONS on a BSW / BASW band kernel: a bandDirs plan in the same layout whose kernels are k_bdl_fill,
                               k_bdl_traceback and k_bdl_export (a covering band is a `dirs` batch of LSW / ASW instead); under a table
                               (dpx_batch_set_local_direction_table) the fill is k_bdlt_fill, walk and export stay */
-    bool twoPiece = false; /* ... with DPX_TWO_PIECE_GAPS: 8-bit codes in dpx_banddir2.h's layout, k_bd2_fill; every band <= 256 runs the band kernel */
+    bool twoPiece = false; /* ... with DPX_TWO_PIECE_GAPS: 8-bit codes in dpx_banddir2.h's layout, k_bd2_fill; every band <= 256 runs the band kernel.
+                              On a bandLocal plan (DPX_LOCAL_TWO_PIECE_GAPS, BASW): the same codes and layout, k_lb2_fill / k_lb2_traceback / k_lb2_export */
     int32_t gapOpen2 = 0, gapExtend2 = 0; /* twoPiece: the second gap piece (dpx_batch_set_second_gap; piece 1 until then) */
     bool packed = false;     /* LNW / LSW / BSW with matrices: couples of equal-shaped pairs, two per wave + leftover singles */
     bool split = false;      /* small batch: one workgroup per pair, one wave per stripe (k_linear_split) */
@@ -96,8 +97,13 @@ enum dpx_fill_kernel { /* the kernel that fills (most of) the batch: describe's 
     DPX_K_LINEAR_DIR, DPX_K_AFFINE_DIR, DPX_K_ASW_DIR, DPX_K_ASG_DIR, DPX_K_BDL_FILL, DPX_K_BDLT_FILL, DPX_K_COUNT
 };
 enum dpx_main_launch { DPX_MAIN_NONE, DPX_MAIN_FILL, DPX_MAIN_BASW, DPX_MAIN_BANW, DPX_MAIN_BAXT, DPX_MAIN_ZEXT, DPX_MAIN_SUBST, DPX_MAIN_ZSUB, DPX_MAIN_BDIR, DPX_MAIN_BDX, DPX_MAIN_BD2, DPX_MAIN_BDL, DPX_MAIN_BDLT };
+/* The two-piece local band-direction batches (DPX_LOCAL_TWO_PIECE_GAPS, dpx_lb2_kernels.hip).  Values of the two enums above, declared
+ * behind them: tests/test_bdlt_constants.py holds both enumerator lists to the last name they had, and DPX_K_COUNT stays the size of
+ * dpx_route_kernel_name's table of create-time kernels.  Both values lie inside the enums' ranges (5 and 4 bits). */
+constexpr dpx_fill_kernel DPX_K_LB2_FILL = static_cast<dpx_fill_kernel>(DPX_K_COUNT + 1);
+constexpr dpx_main_launch DPX_MAIN_LB2 = static_cast<dpx_main_launch>(DPX_MAIN_BDLT + 1);
 enum dpx_second_launch { DPX_SECOND_NONE, DPX_SECOND_PACKED, DPX_SECOND_BANDED_PACKED, DPX_SECOND_LANES, DPX_SECOND_LANES_PK };
-enum dpx_walk_family { DPX_WALK_PLAIN, DPX_WALK_DIR, DPX_WALK_BASW, DPX_WALK_BANW, DPX_WALK_SUBST, DPX_WALK_BDIR, DPX_WALK_BD2, DPX_WALK_BDL };
+enum dpx_walk_family { DPX_WALK_PLAIN, DPX_WALK_DIR, DPX_WALK_BASW, DPX_WALK_BANW, DPX_WALK_SUBST, DPX_WALK_BDIR, DPX_WALK_BD2, DPX_WALK_BDL, DPX_WALK_LB2 };
 enum dpx_export_kind { DPX_EXPORT_PLAIN, DPX_EXPORT_BASW, DPX_EXPORT_BANW };
 struct dpx_route {
     dpx_fill_kernel kernel;
@@ -120,7 +126,8 @@ struct dpx_route {
  * k_bdx_fill; the walk stays k_bdir_traceback.  On a bandLocal plan the alphabet (dpx_batch_set_local_direction_table) turns k_bdl_fill
  * into k_bdlt_fill; the walk stays k_bdl_traceback.  On a dirs plan of ANW / ASW / ASG the alphabet
  * (dpx_batch_set_direction_table) sets dirTable and nothing else; on a score-only plan of the three (dpx_batch_set_score_table) it sets
- * scoreTable and nothing else.  A twoPiece plan runs k_bd2_fill and k_bd2_traceback in every mode; its second piece is
+ * scoreTable and nothing else.  A twoPiece plan runs k_bd2_fill and k_bd2_traceback in every mode (bandLocal as well: k_lb2_fill and
+ * k_lb2_traceback, with or without the alphabet); its second piece is
  * the plan's own (the batch IS the plan), so the signatures here do not know it. */
 dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus, int substAlphabet);
 /* Waves per workgroup of a bandDirs plan's fill: the plan's own without a table; with one (DPX_SUBST_IMAGE_BYTES more per wave) the

@@ -138,10 +138,10 @@ int dpx_batch_set_extension_table(dpx_batch *b, int32_t zdrop, int32_t endBonus,
     return DPX_OK;
 }
 
-/* the second gap piece of a two-piece batch */
+/* the second gap piece of a two-piece batch (DPX_TWO_PIECE_GAPS on BANW / BAXT, DPX_LOCAL_TWO_PIECE_GAPS on BASW) */
 int dpx_batch_set_second_gap(dpx_batch *b, int32_t gapOpen2, int32_t gapExtend2) {
     if (!b) return DPX_ERR_INVALID;
-    if (!b->twoPiece) return DPX_ERR_UNSUPPORTED;
+    if (!b->twoPiece) return DPX_ERR_UNSUPPORTED; /* (a batch created without a two-piece flag) */
     const int32_t lim = 1 << 20; /* validate_params' rule */
     if (gapOpen2 > lim || gapOpen2 < -lim || gapExtend2 > lim || gapExtend2 < -lim) return DPX_ERR_RANGE;
     /* under a table: its largest and smallest entries, as its setter checks */
@@ -208,14 +208,17 @@ int dpx_batch_set_score_table(dpx_batch *b, const int8_t *scores, int32_t alphab
     return install_table(b, image, alphabet, true);
 }
 
-/* the table of a BSW / BASW local band-direction batch (k_bdlt_fill); a covering band runs k_linear_dir / k_asw_dir and is not admitted */
+/* the table of a BSW / BASW local band-direction batch (k_bdlt_fill; two pieces: k_lb2_fill, whose band never falls back); a covering band runs k_linear_dir / k_asw_dir and is not admitted */
 int dpx_batch_set_local_direction_table(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf) {
     if (!b) return DPX_ERR_INVALID;
     if (!scores) return clear_table(b);
     if (!table_args_ok(alphabet, codeOf)) return DPX_ERR_INVALID;
     if (!b->bandLocal) return DPX_ERR_UNSUPPORTED;
     if (!dpx_plan_bdx_waves(*b, true)) return DPX_ERR_UNSUPPORTED; /* one wave's staged strings leave no room in LDS for the table image */
-    if (!pairs_in_range(b, table_extremes(b, scores, alphabet, alphabet), fits_dir)) return DPX_ERR_RANGE;
+    /* fits_dir under the table and the batch's gap pieces (DPX_LOCAL_TWO_PIECE_GAPS; one piece: fits_dir itself) */
+    const int32_t o2 = b->twoPiece ? b->gapOpen2 : b->prm.gapOpen, e2 = b->twoPiece ? b->gapExtend2 : b->prm.gapExtend;
+    if (!pairs_in_range(b, table_extremes(b, scores, alphabet, alphabet),
+                        [&](const dpx_params &q, long long m, long long n) { return fits_dir_pieces(q, o2, e2, m, n); })) return DPX_ERR_RANGE;
     unsigned char image[DPX_SUBST_IMAGE_BYTES];
     build_table_image(image, scores, alphabet, codeOf);
     return install_table(b, image, alphabet, true);

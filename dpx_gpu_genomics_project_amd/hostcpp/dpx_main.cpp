@@ -13,7 +13,7 @@
 // cs:Z:<text> under -cs, the strings built on the device (dpx_batch_diffs_begin / _end).
 //
 //   dpx_main -pairs <file> [-match 3] [-mismatch -1] [-open -2 | -gap -2] [-extend -1]
-//            [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band 128] [-batch N | -pool-gb 4] [-inflight K] [-tune 0|1] [-device 0] [-noprint] [-pack2] [-directions] [-cigar [M] [-md] [-cs]] [-zdrop Z] [-endbonus E] [-matrix FILE] [-localmatrix FILE] [-open2 O2 -extend2 E2] [-reverse] [-producer P] [-rank r -world w]
+//            [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band 128] [-batch N | -pool-gb 4] [-inflight K] [-tune 0|1] [-device 0] [-noprint] [-pack2] [-directions] [-cigar [M] [-md] [-cs]] [-zdrop Z] [-endbonus E] [-matrix FILE] [-localmatrix FILE] [-open2 O2 -extend2 E2] [-localopen2 O2 -localextend2 E2] [-reverse] [-producer P] [-rank r -world w]
 //
 // -matrix FILE (BANW / BAXT, not with -zdrop / -endbonus): score columns by a substitution matrix (dpx_batch_set_substitution) instead of
 // -match / -mismatch.  NCBI text format: '#' lines are comments; one header row of 1..32 single-character column letters; then one row
@@ -35,6 +35,9 @@
 // -open2 O2 -extend2 E2 (both or neither; only with -directions and -algo BANW|BAXT): two-piece affine gaps, a gap of length k scores
 // max(open + k * extend, O2 + k * E2) (DPX_TWO_PIECE_GAPS and dpx_batch_set_second_gap, k_bd2_fill; bands up to 256).  They combine with
 // -zdrop / -endbonus / -matrix through dpx_batch_set_direction_scoring.
+// -localopen2 O2 -localextend2 E2 (both or neither; only with -directions and -algo BASW): the same two-piece gaps on the local band-direction
+// batches (DPX_LOCAL_TWO_PIECE_GAPS and dpx_batch_set_second_gap, k_lb2_fill; bands up to 256, covering or not).  They combine with
+// -localmatrix, -cigar [M] -md -cs, -pack2 and -band.
 // -reverse (only with -algo BANW|BAXT, and with every flag those take): every pair is aligned as (reverse(ref), reverse(qry)) on the
 // device (dpx_batch_set_reversed) -- a leftward extension, or a global alignment with its gaps at the right end of every ambiguous run.
 // Score and, for BAXT, the end cell behind it are the reversed frame's; lines, CIGARs and coordinates are printed along the strings as
@@ -146,6 +149,7 @@ static void usage() {
                     "[-directions] (direction codes instead of score matrices; -algo BSW|BASW -directions: one code per in-band cell, long pairs run; BANW / BAXT: with -zdrop / -endbonus / -matrix too; -algo ANW|ASW|ASG -directions -matrix <file>: full-matrix affine alignment under a substitution matrix) "
                     "[-localmatrix <file>] (a -matrix file for the local band-direction batches: only with -algo BSW|BASW -directions, not with -matrix) "
                     "[-open2 <O2> -extend2 <E2>] (two-piece gaps: both together, only with -directions and -algo BANW|BAXT) "
+                    "[-localopen2 <O2> -localextend2 <E2>] (two-piece gaps on local band-direction batches: both together, only with -directions and -algo BASW) "
                     "[-scores] (score-only batches: one line '<number> | <score> | <endRow> <endCol>' per pair; not with -directions / -cigar / -zdrop / -endbonus / -open2 / -extend2 / -reverse; -matrix <file> with it only for -algo ANW|ASW|ASG; batches of 20000 pairs unless -batch says otherwise) "
                     "[-reverse] (align every pair right to left on the device, output in the file's orientation; only with -algo BANW|BAXT)\n");
     exit(EXIT_FAILURE);
@@ -167,6 +171,7 @@ int main(int argc, char *argv[]) {
     int zdrop = -1, endBonus = -1; // -zdrop / -endbonus: BAXT's extension mode (dpx_batch_set_extension) on every batch; -1 = off
     bool haveOpen2 = false, haveExtend2 = false; // -open2 / -extend2: the second gap piece (dpx_batch_set_second_gap) on every batch
     int gapOpen2 = 0, gapExtend2 = 0;
+    bool haveLocalOpen2 = false, haveLocalExtend2 = false; // -localopen2 / -localextend2: the same on BASW's local band-direction batches (DPX_LOCAL_TWO_PIECE_GAPS)
     bool scoresOnly = false; // -scores: score-only batches (DPX_SCORE_ONLY), one "<number> | <score> | <endRow> <endCol>" line per pair from dpx_batch_results
     bool reverse = false;    // -reverse: every pair of every batch is reversed on the device (dpx_batch_set_reversed)
     const char *matrixFile = nullptr; // -matrix: a substitution table (dpx_batch_set_substitution) on every batch
@@ -204,6 +209,8 @@ int main(int argc, char *argv[]) {
         else if (!strcmp(argv[i], "-localmatrix")) localMatrixFile = next("-localmatrix");
         else if (!strcmp(argv[i], "-open2")) { gapOpen2 = atoi(next("-open2")); haveOpen2 = true; }
         else if (!strcmp(argv[i], "-extend2")) { gapExtend2 = atoi(next("-extend2")); haveExtend2 = true; }
+        else if (!strcmp(argv[i], "-localopen2")) { gapOpen2 = atoi(next("-localopen2")); haveLocalOpen2 = true; }
+        else if (!strcmp(argv[i], "-localextend2")) { gapExtend2 = atoi(next("-localextend2")); haveLocalExtend2 = true; }
         else if (!strcmp(argv[i], "-reverse")) reverse = true;
         else if (!strcmp(argv[i], "-scores")) scoresOnly = true;
         else if (!strcmp(argv[i], "-producer")) producerFlag = atoi(next("-producer"));
@@ -223,9 +230,11 @@ int main(int argc, char *argv[]) {
     if ((zdrop != -1 || endBonus != -1) && algo != DPX_ALGO_BAXT) usage();
     const bool twoPiece = haveOpen2 || haveExtend2;
     if (twoPiece && (!(haveOpen2 && haveExtend2) || !directions || (algo != DPX_ALGO_BANW && algo != DPX_ALGO_BAXT))) usage();
+    const bool localTwoPiece = haveLocalOpen2 || haveLocalExtend2;
+    if (localTwoPiece && (!(haveLocalOpen2 && haveLocalExtend2) || twoPiece || !directions || algo != DPX_ALGO_BASW)) usage();
     if (reverse && algo != DPX_ALGO_BANW && algo != DPX_ALGO_BAXT) usage();
     if (diffKinds && !cigar) usage();
-    if (scoresOnly && (directions || cigar || zdrop != -1 || endBonus != -1 || twoPiece || reverse)) usage();
+    if (scoresOnly && (directions || cigar || zdrop != -1 || endBonus != -1 || twoPiece || localTwoPiece || reverse)) usage();
     std::vector<int8_t> substScores;
     int substAlphabet = 0;
     uint8_t substCode[256];
@@ -299,8 +308,8 @@ int main(int argc, char *argv[]) {
         // band -- the layout of csrc/dpx_banddir.h)
         // (BSW / BASW under a covering band run as LSW / ASW direction batches: the estimate above)
         const bool localAlgo = algo == DPX_ALGO_BSW || algo == DPX_ALGO_BASW;
-        const bool bandDirections = directions && bandAlgo && (!localAlgo || (long long)band < std::max<long long>(mq, fileInfo.maxReferenceLength));
-        const long long bC0 = ((long long)band + 63) / 64, bC = bC0 <= 1 ? 1 : bC0 <= 2 ? 2 : bC0 <= 4 ? 4 : 8, bGd = (twoPiece ? 16 : 32) / bC; // (two-piece: a byte per cell, csrc/dpx_banddir2.h)
+        const bool bandDirections = directions && bandAlgo && (!localAlgo || localTwoPiece || (long long)band < std::max<long long>(mq, fileInfo.maxReferenceLength)); // (two local pieces: the band kernel, covering or not)
+        const long long bC0 = ((long long)band + 63) / 64, bC = bC0 <= 1 ? 1 : bC0 <= 2 ? 2 : bC0 <= 4 ? 4 : 8, bGd = ((twoPiece || localTwoPiece) ? 16 : 32) / bC; // (two-piece: a byte per cell, csrc/dpx_banddir2.h)
         const double bandDirChunks = (double)((mq + (long long)fileInfo.maxReferenceLength - 1 + bGd - 1) / bGd);
         const double perPair = bandDirections ? 1024.0 * bandDirChunks + 1024.0
                              : directions ? 0.5 * dirRows * dirCols + 1024.0
@@ -429,13 +438,13 @@ int main(int argc, char *argv[]) {
         const uint64_t t0 = get_time();
         const bool bandDirections = directions && (algo == DPX_ALGO_BANW || algo == DPX_ALGO_BAXT);
         const bool localDirections = directions && (algo == DPX_ALGO_BSW || algo == DPX_ALGO_BASW);
-        const unsigned flags = (twoPiece ? DPX_TWO_PIECE_GAPS : 0u) | (bandDirections ? DPX_KEEP_BAND_DIRECTIONS : localDirections ? DPX_KEEP_LOCAL_BAND_DIRECTIONS : directions ? DPX_KEEP_DIRECTIONS : scoresOnly ? DPX_SCORE_ONLY : DPX_KEEP_MATRICES) | DPX_TIME_FILLS | ((tunePools && !scoresOnly && tuned.fetch_add(1) < inflight) ? DPX_TUNE_PLACEMENT : 0u);
+        const unsigned flags = (twoPiece ? DPX_TWO_PIECE_GAPS : localTwoPiece ? DPX_LOCAL_TWO_PIECE_GAPS : 0u) | (bandDirections ? DPX_KEEP_BAND_DIRECTIONS : localDirections ? DPX_KEEP_LOCAL_BAND_DIRECTIONS : directions ? DPX_KEEP_DIRECTIONS : scoresOnly ? DPX_SCORE_ONLY : DPX_KEEP_MATRICES) | DPX_TIME_FILLS | ((tunePools && !scoresOnly && tuned.fetch_add(1) < inflight) ? DPX_TUNE_PLACEMENT : 0u);
         int prc = pack2 ? dpx_batch_create_packed2(-1, &prm, packed.data(), fileInfo.numBytes, alphabet, reinterpret_cast<const dpx_seq_pair *>(sequenceIdxs),
                                                    first, next.count, flags, &next.b)
                         : dpx_batch_create(&prm, sequences, fileInfo.numBytes, reinterpret_cast<const dpx_seq_pair *>(sequenceIdxs), first, next.count,
                                            flags, &next.b);
         if (prc != DPX_OK) die("FAILED TO CREATE DEVICE BATCH", prc);
-        if (twoPiece && (prc = dpx_batch_set_second_gap(next.b, gapOpen2, gapExtend2)) != DPX_OK) die("FAILED TO SET THE SECOND GAP PIECE", prc);
+        if ((twoPiece || localTwoPiece) && (prc = dpx_batch_set_second_gap(next.b, gapOpen2, gapExtend2)) != DPX_OK) die("FAILED TO SET THE SECOND GAP PIECE", prc);
         if (bandDirections) { // the one setter of a band-direction batch: the two below refuse it
             if ((zdrop != -1 || endBonus != -1 || matrixFile) &&
                 (prc = dpx_batch_set_direction_scoring(next.b, zdrop, endBonus, matrixFile ? substScores.data() : nullptr, substAlphabet, substCode)) != DPX_OK)

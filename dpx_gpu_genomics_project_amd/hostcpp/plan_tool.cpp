@@ -11,12 +11,12 @@
  *           dpx_batch_set_extension / _set_substitution / _set_extension_table leave it; absent: -1 -1 0.  The setters' own
  *           refusals are not applied: the planner is asked what such a batch would run)
  *     gap2 <gapOpen2> <gapExtend2>                                 (optional, after the mode line if there is one: the second gap piece
- *           of a DPX_TWO_PIECE_GAPS plan as dpx_batch_set_second_gap leaves it; absent: piece 1)
+ *           of a DPX_TWO_PIECE_GAPS / DPX_LOCAL_TWO_PIECE_GAPS plan as dpx_batch_set_second_gap leaves it; absent: piece 1)
  *     <referenceIdx> <referenceSize> <queryIdx> <querySize>        (firstPair + numPairs lines)
  *
  * Output, one line: "status=<n>", then for a refusal " err=<text>" when there is one, else dpx_batch_describe()'s text up to the pool
  * fields, " info=<numPairs>,<cells>,<matrixBytes>,<algorithmicBytes>" (dpx_batch_info), " state=<16 hex digits>" and, only when a mode
- * line was given, " walk=<family>:<mode>": the traceback's family (plain, dir, basw, banw, subst, bdir, bd2, bdl) and walk (0, 1 or 2) of
+ * line was given, " walk=<family>:<mode>": the traceback's family (plain, dir, basw, banw, subst, bdir, bd2, bdl, lb2) and walk (0, 1 or 2) of
  * dpx_plan_route, which describe's traceback= shows for the banded affine kernels only.
  *
  * state is FNV-1a 64 over, in this order (integers as 8 little-endian bytes, sign-extended):
@@ -103,7 +103,7 @@ int main() {
     printf("status=0 %s info=%zu,%llu,%llu,%llu state=%016llx", text, plan.numPairs, (unsigned long long)plan.cells,
            (unsigned long long)(plan.matElems * sizeof(int16_t)), (unsigned long long)plan.algBytes, (unsigned long long)plan_state(plan));
     if (mode) {
-        static const char *const family[] = {"plain", "dir", "basw", "banw", "subst", "bdir", "bd2", "bdl"}; /* dpx_walk_family */
+        static const char *const family[] = {"plain", "dir", "basw", "banw", "subst", "bdir", "bd2", "bdl", "lb2"}; /* dpx_walk_family */
         const dpx_route r = dpx_plan_route(plan, kn.tbWalk, zdrop, endBonus, substAlphabet);
         printf(" walk=%s:%d", family[r.walk], r.walkMode);
     }

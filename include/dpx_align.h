@@ -672,7 +672,7 @@ int dpx_batch_set_direction_scoring(dpx_batch *b, int32_t zdrop, int32_t endBonu
  * dpx_batch_set_second_gap: legal any time after create, applies to every following fill; if a value changed it invalidates the
  * earlier fill's results, lines, text, CIGARs and records (DPX_ERR_NOT_FILLED), as dpx_batch_set_substitution does.
  *   DPX_ERR_INVALID      b == NULL
- *   DPX_ERR_UNSUPPORTED  a batch created without DPX_TWO_PIECE_GAPS
+ *   DPX_ERR_UNSUPPORTED  a batch created without a two-piece flag (DPX_TWO_PIECE_GAPS, or DPX_LOCAL_TWO_PIECE_GAPS below)
  *   DPX_ERR_RANGE        a weight beyond +-2^20, or the range check fails for a pair
  * A refused call changes nothing: dpx_batch_describe is byte-identical before and after.
  * The class surface (dpx_class_main) and dpx_align_batch stay one-piece. */
@@ -830,10 +830,55 @@ int dpx_batch_set_score_table(dpx_batch *b, const int8_t *scores, int32_t alphab
  * images no longer fit a workgroup the fill runs one-wave workgroups (waves_per_workgroup says what will launch).  The seven other
  * setters (dpx_batch_set_extension, dpx_batch_set_substitution with a table, dpx_batch_set_extension_table, dpx_batch_set_second_gap,
  * dpx_batch_set_direction_scoring, dpx_batch_set_direction_table, dpx_batch_set_score_table with a table; dpx_batch_set_reversed too)
- * keep refusing these batches, table set or not.  Not built: covering bands, reversed pairs, two-piece gaps and extension settings on
- * local batches, a table through dpx_align_batch.  Repeated fills, DPX_TIME_FILLS, dpx_batch_fill_timed, a caller's stream,
+ * keep refusing these batches, table set or not (dpx_batch_set_second_gap admits the DPX_LOCAL_TWO_PIECE_GAPS batches of BASW, below).
+ * Not built: covering bands, reversed pairs and extension settings on local batches, a table through dpx_align_batch.  Repeated fills, DPX_TIME_FILLS, dpx_batch_fill_timed, a caller's stream,
  * dpx_batch_create_on, packed2 input, the output pipeline, dpx_batch_cigars_* and dpx_batch_diffs_* as for any local band-direction batch. */
 int dpx_batch_set_local_direction_table(dpx_batch *b, const int8_t *scores, int32_t alphabet, const uint8_t *codeOf /* 256 entries */);
+
+/* ---- A second gap piece for BASW local band-direction batches ----
+ * The pairs that need a DPX_KEEP_LOCAL_BAND_DIRECTIONS batch are long noisy reads against a window, and every long-read scoring scheme
+ * prices them with two gap pieces: a gap of length k scores max(o1 + k*e1, o2 + k*e2), so a 100-base deletion does not cost a hundred
+ * sequencing errors.  New create flag DPX_LOCAL_TWO_PIECE_GAPS, legal only together with DPX_KEEP_LOCAL_BAND_DIRECTIONS, on
+ * DPX_ALGO_BASW (BSW has one linear gap weight and no second piece).  Piece 1 is params.gapOpen / gapExtend.  Piece 2 starts equal to
+ * piece 1 and is set with dpx_batch_set_second_gap(b, o2, e2), whose rule "a batch created without DPX_TWO_PIECE_GAPS ->
+ * DPX_ERR_UNSUPPORTED" reads "without a two-piece flag".  There is no new symbol and no ABI bump.
+ * Everything not named below is BASW's definition under DPX_KEEP_LOCAL_BAND_DIRECTIONS, unchanged: the band |i - j| <= B - 1 over cells
+ * with i, j >= 1, the end-cell rule, the text block, and "no tails".
+ *   Neighbours.  A neighbour that is a border cell, lies outside the band or lies outside the matrix reads H = 0 and D1 = D2 = I1 = I2 =
+ *     minus infinity: BASW's rule with four gap planes.
+ *   Cells.  Dk = max(H_up + ok + ek, Dk_up + ek) and Ik = max(H_left + ok + ek, Ik_left + ek); GAP_OPEN wins a tie in each of the four.
+ *     best = H_diag + s; then, in this order, D1, D2, I1, I2: a candidate that is >= the winner so far takes the cell (k_bd2_fill's
+ *     order).  H = max(0, winner); the move is NONE where H == 0.  With (o2, e2) == (o1, e1), every score, end cell, line, CIGAR and the
+ *     H / I / D planes equal the one-piece local batch's; piece 2's planes equal piece 1's.
+ *   Score / end cell.  BASW's rule: the first maximum in row-major order, or 0 at (0, 0) when every H is 0.  Empty sequences give 0 at
+ *     (0, 0).
+ *   Walk.  Five states, from the end cell in SCORING.  In SCORING the walk stops on the first cell whose H is 0: move 0, or a cell
+ *     without a code (a border cell or a cell outside the band).  In state Dk / Ik the walk emits the gap column, stays in that state
+ *     while the cell's own extend bit of that plane is set, and returns to SCORING where that plane opened.  An edge cell always opens,
+ *     so the walk cannot extend out of the band.  The lines, the `_` convention, the relation line, the CIGAR, MD / cs and the
+ *     dpx_alignment records are as for the one-piece batch; a CIGAR does not say which piece paid.
+ *   dpx_batch_directions takes the six selectors of a two-piece batch.  DPX_MAT_H is NONE_MAIN where H == 0; either piece exports
+ *     QUERY_INSERTION / QUERY_DELETION.  DPX_MAT_I / _D / _I2 / _D2 are GAP_OPEN / GAP_EXTEND for every in-band cell.  DPX_MAT_H_PIECE is
+ *     0 / 1 / 2.  Every plane is 0 on the borders and outside the band (the local export's rule).
+ *   Storage.  One byte per in-band cell in csrc/dpx_banddir2.h's layout, unchanged.  dpx_batch_describe shows kernel=k_lb2_fill
+ *     traceback=k_lb2_traceback matrix=banddir8 gap2=<o2>,<e2>.
+ *   Band.  B <= 256, covering or not; 257 and above is DPX_ERR_UNSUPPORTED.  A covering band runs the band kernel, because ASW has no
+ *     second piece (as for DPX_TWO_PIECE_GAPS).
+ *   Range.  The local batch's check (ASW's bounds against 2^28, no m + n limit) on the componentwise minimum of the two pieces and again
+ *     on their maximum; under a table, with the table's extremes.
+ *   Flags.  DPX_LOCAL_TWO_PIECE_GAPS without DPX_KEEP_LOCAL_BAND_DIRECTIONS: DPX_ERR_INVALID; with DPX_SCORE_ONLY,
+ *     DPX_KEEP_BAND_DIRECTIONS or DPX_TWO_PIECE_GAPS: DPX_ERR_INVALID; on any algorithm but BASW: DPX_ERR_UNSUPPORTED, BSW included; with
+ *     DPX_KEEP_DIRECTIONS: DPX_ERR_UNSUPPORTED.
+ *   Setters.  dpx_batch_set_second_gap has its present argument checks and invalidates the earlier fill only when a value changed.
+ *     dpx_batch_set_local_direction_table is admitted, with its lifecycle, its LDS-fit refusal and its one-wave workgroups where four
+ *     waves' strings plus images pass 160 KiB; describe then adds ` subst=<alphabet>` and keeps kernel=k_lb2_fill.  Every other setter
+ *     refuses as on a one-piece local batch (extension, substitution, extension_table, direction_scoring, direction_table, score_table,
+ *     reversed).  A refused call leaves dpx_batch_describe byte-identical.
+ *   Detecting it.  An older library ignores the bit and builds the one-piece batch: describe then says kernel=k_bdl_fill
+ *     matrix=banddir4, and dpx_batch_set_second_gap returns DPX_ERR_UNSUPPORTED.
+ * Not built: bands 257..512 under two pieces, z-drop / end bonus and reversed pairs on local batches, the class surface and
+ * dpx_align_batch, BSW. */
+#define DPX_LOCAL_TWO_PIECE_GAPS 0x80u /* dpx_batch_create flag, only together with DPX_KEEP_LOCAL_BAND_DIRECTIONS, on DPX_ALGO_BASW */
 
 /* Sizes: numPairs, total cells (sum refLen*queryLen, the reference's numCells, c++/parseInput.cpp:100),
  * bytes of HBM the matrices occupy, algorithmic bytes of one fill. */
