@@ -20,6 +20,7 @@ KEEP_BAND_DIRECTIONS = 0x10  # BANW / BAXT: 4-bit direction codes per in-band ce
 KEEP_LOCAL_BAND_DIRECTIONS = 0x40  # BSW / BASW: 4-bit direction codes per in-band cell, int32 scores (0x8 and 0x10 stay refused on them)
 TWO_PIECE_GAPS = 0x20  # with KEEP_BAND_DIRECTIONS: a second gap piece (Batch.set_second_gap), 8-bit codes, bands up to 256
 LOCAL_TWO_PIECE_GAPS = 0x80  # with KEEP_LOCAL_BAND_DIRECTIONS on BASW: a second gap piece (Batch.set_second_gap), 8-bit codes, bands up to 256
+LONG_SCORES = 0x100  # with exactly one of KEEP_BAND_DIRECTIONS / KEEP_LOCAL_BAND_DIRECTIONS: that batch's int32 fill with nothing stored but the results (no pool)
 MAT_H, MAT_I, MAT_D = 0, 1, 2
 MAT_I2, MAT_D2, MAT_H_PIECE = 3, 4, 5  # Batch.directions on a TWO_PIECE_GAPS batch: piece 2's planes, and the piece of H's gap move
 # CIGARs (dpx_batch_cigars_begin / _end): an op is (length << 4) | code with BAM's code numbers

@@ -340,11 +340,22 @@ __device__ __forceinline__ void write_results(const dpx_fill_args &f, const int 
     f.score[p] = reached ? qeScore : maxScore;
     f.endRow[p] = reached ? m : maxRow;
     f.endCol[p] = reached ? qeCol : maxCol;
+#ifndef DPX_BANDDIR_SCORE_ONLY
     u32x4 *rec = reinterpret_cast<u32x4 *>(ext + (size_t)p * 8u);
     const u32x4 w0 = {(unsigned)maxScore, (unsigned)maxRow, (unsigned)maxCol, (unsigned)qeScore};
     const u32x4 w1 = {(unsigned)qeCol, (unsigned)lastDiag, (dropped ? 1u : 0u) | (reached ? 2u : 0u), 0u};
     rec[0] = w0;
     rec[1] = w1;
+#else
+    /* the DPX_LONG_SCORES units (dpx_banddir_fill.inc) write the same record field by field: once per pair, and it keeps their code free
+     * of 16-byte global stores, which tests/test_bscore_kernels_isa.py reads as "no code group is stored".  volatile keeps the eight
+     * stores apart (plain and nontemporal ones are merged again); the global address space keeps them global_store, not flat_store */
+    using gptr = volatile __attribute__((address_space(1))) int32_t *;
+    const gptr rec = (gptr)(ext + (size_t)p * 8u);
+    const int32_t v[8] = {maxScore, maxRow, maxCol, qeScore, qeCol, lastDiag, (int32_t)((dropped ? 1u : 0u) | (reached ? 2u : 0u)), 0};
+#pragma unroll
+    for (int k = 0; k < 8; k++) rec[k] = v[k];
+#endif
 }
 
 /* an empty sequence (m <= 0 or n <= 0), on one lane: the in-band cells are one border line, cell k (1 <= k <= L = min(max(m, n), B-1))

@@ -31,7 +31,12 @@
  * A drop (SCAN == 2).  The loop body runs two steps; a drop after the first does not run the second.  The window then holds a partial
  * group: the missing steps are shifted in as zeros and the group goes to chunk (lastDiag - 2) / Gd (the chosen end cell may lie in it),
  * not to the pair's last chunk.  A drop on anti-diagonal 1 stores nothing.  Nothing is stored past the drop: the chunks behind it keep
- * what the pool held, and no walk reads them (a walk only visits smaller anti-diagonals than its start). */
+ * what the pool held, and no walk reads them (a walk only visits smaller anti-diagonals than its start).
+ *
+ * DPX_BANDDIR_SCORE_ONLY (defined by dpx_bscore_kernels.hip and dpx_lscore_kernels.hip only, in front of the include): the same frame with
+ * nothing stored but the results.  The window, the pair's place in the pool, store_group and the partial last group are not compiled;
+ * State needs no w, and the kernel defines neither Gd nor kStepBits.  A dropped pair simply ends.  A preprocessor switch and not a
+ * template constant: the text the storing units see is the text they had. */
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int kLogC = C == 8 ? 3 : C == 4 ? 2 : C == 2 ? 1 : 0;
     const int lane = threadIdx.x & 63;
@@ -79,7 +84,9 @@
     State st;
     st.lim = B - 1 - lane * C;
     st.fin = DPX_NEG;
+#ifndef DPX_BANDDIR_SCORE_ONLY
     st.w[0] = st.w[1] = st.w[2] = st.w[3] = 0u;
+#endif
     { /* anti-diagonals a = 1 (prev: the border cells (0, 1) and (1, 0), in band when B >= 2) and a = 0 (prev2: H[0][0] = 0, which
        * shares its slot with cell (1, 1)); the character windows are those of a = 1, the first real step then slides one of them */
         const int p1 = B & 1;
@@ -114,9 +121,11 @@
         return ii0 >= 1 && ii0 + top <= m && jj0 - top >= 1 && jj0 <= n;
     };
     const int NS = m + n - 1;                 /* anti-diagonals a = 2 .. m+n */
+#ifndef DPX_BANDDIR_SCORE_ONLY
     const int numGroups = (NS + Gd - 1) / Gd; /* == the layout's chunks of the pair: no store goes past the pair's last chunk */
     unsigned char *base = reinterpret_cast<unsigned char *>(a.mat) + (size_t)pr.matOff * 2u;
     const uint64_t cs = (uint64_t)pr.chunkStride * 2u;
+#endif
     int i0 = (1 + (B & 1) - (B - 1)) >> 1;
     int j0 = 1 - i0;
     /* the scan's state.  Row m: every lane keeps (score, column) of the row-m cells its own slots held, replaced when strictly greater
@@ -132,10 +141,15 @@
             stop = true;
         }
     }
+#ifndef DPX_BANDDIR_SCORE_ONLY
     auto store_group = [&](const int grp) {
         if (grp < numGroups)
             *reinterpret_cast<u32x4 *>(base + dpx_banddir_piece((uint64_t)grp, lane, cs)) = u32x4{st.w[0], st.w[1], st.w[2], st.w[3]};
     };
+#define DPX_BANDDIR_STORE_AFTER(A_) if ((((A_) + 2) & (Gd - 1)) == 0) store_group(((A_) + 1) / Gd);
+#else
+#define DPX_BANDDIR_STORE_AFTER(A_)
+#endif
 #define DPX_BANDDIR_BODY(INTERIOR_)                                                                                       \
     {                                                                                                                     \
         DPX_BANDDIR_STEP(PB, INTERIOR_, A0);                                                                              \
@@ -143,7 +157,7 @@
         if (stop) break; /* (a drop after the first step: the second does not run) */                                     \
         DPX_BANDDIR_STEP(!PB, INTERIOR_, A0 + 1);                                                                         \
         DPX_BANDDIR_SCAN_AFTER(A0 + 1)                                                                                    \
-        if (((A0 + 2) & (Gd - 1)) == 0) store_group((A0 + 1) / Gd);                                                       \
+        DPX_BANDDIR_STORE_AFTER(A0)                                                                                       \
         if (stop) break;                                                                                                  \
     }
     int A0 = 0;
@@ -151,15 +165,18 @@
     for (; !stop && A0 + 2 < NS && interior(A0 + 1); A0 += 2) DPX_BANDDIR_BODY(true)
     for (; !stop && A0 < NS; A0 += 2) DPX_BANDDIR_BODY(false)
 #undef DPX_BANDDIR_BODY
+#undef DPX_BANDDIR_STORE_AFTER
     /* the partial last group.  `pushed` steps have entered the window, pushed % Gd of them since the last store (a drop on step A left
      * lastDiag = A + 2; a group that the dropping step completed has been stored already); the missing steps are shifted in as zeros
      * so that step t of the group sits at code t * C.  Without a drop the group is the pair's last chunk, after one the chunk of the
      * dropping step; a drop on anti-diagonal 1 ran no step and stores nothing. */
+#ifndef DPX_BANDDIR_SCORE_ONLY
     const int pushed = stop ? lastDiag - 1 : A0;
     if (pushed & (Gd - 1)) {
         for (int t = pushed & (Gd - 1); t < Gd; t++) window_push<kStepBits>(st.w, 0u);
         store_group(pushed / Gd);
     }
+#endif
     if constexpr (!EXT) {
         if (cEnd >= 0) { a.score[p] = st.fin; a.endRow[p] = m; a.endCol[p] = n; }
     } else {

@@ -563,6 +563,15 @@ static hipError_t launch_main(dpx_batch *b, const dpx_route &r, hipStream_t s) {
         }
         return dpx_launch_lb2_fill(xa, b->R, s);
     }
+    if (r.main == DPX_MAIN_BSCORE || r.main == DPX_MAIN_LSCORE) { /* (DPX_LONG_SCORES: k_bscore_fill / k_lscore_fill in every mode; the table's LDS as for
+                                                                   * k_bdx_fill / k_bdlt_fill.  In front of the switch for the same reason) */
+        dpx_bdx_args xa = {b->args, {nullptr, nullptr}, {r.ext ? b->zdrop : -1, r.ext ? b->endBonus : -1, b->dExt.get()}};
+        if (b->substAlphabet) {
+            xa.tab = table_ref(b);
+            xa.f.ldsPerWave += DPX_SUBST_IMAGE_BYTES; xa.f.wavesPerBlock = dpx_plan_bdx_waves(*b, true);
+        }
+        return r.main == DPX_MAIN_LSCORE ? dpx_launch_lscore_fill(xa, b->R, b->prm.algo == DPX_ALGO_BASW, s) : dpx_launch_bscore_fill(xa, b->R, r.ext, s);
+    }
     switch (r.main) {
     case DPX_MAIN_NONE: return hipSuccess;
     case DPX_MAIN_FILL:
@@ -777,7 +786,7 @@ int dpx_batch_results(dpx_batch *b, int32_t *scores, int32_t *endRow, int32_t *e
 
 int dpx_batch_directions(dpx_batch *b, size_t pair, int which, uint8_t *out) {
     if (!b || !out || pair >= b->numPairs || which < 0 || which >= (b->twoPiece ? DPX_MAT_H_PIECE + 1 : b->planes)) return DPX_ERR_INVALID;
-    if (!b->dirs && !b->bandDirs) return DPX_ERR_NO_MATRIX;
+    if ((!b->dirs && !b->bandDirs) || b->bandScores) return DPX_ERR_NO_MATRIX; /* (DPX_LONG_SCORES: a band-direction plan without codes) */
     if (!b->filled) return DPX_ERR_NOT_FILLED;
     int rc = bind_device(b->device);
     if (rc != DPX_OK) return rc;

@@ -138,6 +138,13 @@ typedef struct dpx_bdx_args {
     dpx_ext_ref scan;
 } dpx_bdx_args;
 hipError_t dpx_launch_bdx_fill(const dpx_bdx_args &a, int C, bool ext, hipStream_t stream);
+/* DPX_LONG_SCORES: the band-direction fills with nothing stored but the results; f.mat is not read.  LDS and waves per workgroup as for the
+ * storing twin (with a table f.ldsPerWave includes DPX_SUBST_IMAGE_BYTES).
+ * dpx_bscore_kernels.hip (k_bscore_fill; BANW / BAXT): k_bdir_fill's / k_bdx_fill's cells and results in every mode, "no table, no scan"
+ * included (`tab` NULL: byte compare; `scan` both -1: off; BANW takes no scan).
+ * dpx_lscore_kernels.hip (k_lscore_fill; BSW / BASW, `affine`): k_bdl_fill's / k_bdlt_fill's cells and results; `scan` is not read. */
+hipError_t dpx_launch_bscore_fill(const dpx_bdx_args &a, int C, bool ext, hipStream_t stream);
+hipError_t dpx_launch_lscore_fill(const dpx_bdx_args &a, int C, bool affine, hipStream_t stream);
 hipError_t dpx_launch_unpack2(const uint32_t *packed, uint32_t alphabet, char *out, size_t numDwords, hipStream_t stream);
 hipError_t dpx_launch_prim_eval(const int32_t *op, const uint32_t *a, const uint32_t *b, const uint32_t *c, size_t count,
                                 uint32_t *res, uint32_t *pred, hipStream_t stream);

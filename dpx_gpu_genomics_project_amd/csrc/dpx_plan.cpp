@@ -333,11 +333,12 @@ int choose_kernel(const Knobs &kn, dpx_plan &p, int &R) {
     /* (no ANW / ASW fall-back: neither has a second piece; dpx_plan_batch has paired each two-piece flag with its storage flag) */
     p.twoPiece = (bandDirFlag && (p.flags & DPX_TWO_PIECE_GAPS) != 0) || (localFlag && (p.flags & DPX_LOCAL_TWO_PIECE_GAPS) != 0);
     p.gapOpen2 = prm.gapOpen; p.gapExtend2 = prm.gapExtend;
-    const bool bandDirCovering = bandDirFlag && !p.twoPiece && prm.algo == DPX_ALGO_BANW && (long long)prm.band >= longest + 1;
+    /* (DPX_LONG_SCORES: no fall-back either way -- no unbanded int32 score-only kernel exists; every band <= 512 runs the band kernel) */
+    const bool bandDirCovering = bandDirFlag && !p.twoPiece && !p.bandScores && prm.algo == DPX_ALGO_BANW && (long long)prm.band >= longest + 1;
     /* DPX_KEEP_LOCAL_BAND_DIRECTIONS (BSW / BASW; dpx_plan_batch has refused every other algorithm): a covering band takes the matrix batch's
      * fall-back to LSW / ASW, as a direction batch of that algorithm; every other band runs k_bdl_fill (two pieces: k_lb2_fill, covering
      * or not) */
-    const bool localCovering = localFlag && !p.twoPiece && (long long)prm.band >= longest;
+    const bool localCovering = localFlag && !p.twoPiece && !p.bandScores && (long long)prm.band >= longest;
     p.bandLocal = localFlag && !localCovering;
     p.dirs = (p.flags & DPX_KEEP_DIRECTIONS) != 0 || bandDirCovering || localCovering; p.bandDirs = (bandDirFlag && !bandDirCovering) || p.bandLocal; p.kernelAlgo = prm.algo;
     /* rows per lane: smallest tile that keeps short queries in one stripe, 8 (or DPX_R) otherwise */
@@ -355,7 +356,7 @@ int choose_kernel(const Knobs &kn, dpx_plan &p, int &R) {
     }
     /* (BANW: + 1, its band applies to the border cells too -- at B = max(m, n) the border cell (m, 0) or (0, n) is outside it) */
     /* (BAXT: no covering fall-back -- no unbanded extension kernel exists; a band <= 512 that covers the matrix runs k_baxt_fill) */
-    if (prm.algo != DPX_ALGO_BAXT && (long long)prm.band >= longest + (prm.algo == DPX_ALGO_BANW ? 1 : 0)) {
+    if (prm.algo != DPX_ALGO_BAXT && !p.bandScores && (long long)prm.band >= longest + (prm.algo == DPX_ALGO_BANW ? 1 : 0)) {
         p.kernelAlgo = prm.algo == DPX_ALGO_BSW ? DPX_ALGO_LSW : prm.algo == DPX_ALGO_BASW ? DPX_ALGO_ASW : DPX_ALGO_ANW; /* the band covers every cell: identical to the unbanded recurrence */
         return DPX_OK;
     }
@@ -528,6 +529,7 @@ void place_matrices(const Knobs &kn, bool banded, dpx_plan &p) {
         const uint64_t inband = (p.bandDirs || (banded && p.store && !p.dirs)) ? band_cells(pd.m, pd.n, p.prm.band) : 0;
         p.bandCells += inband;
         if (p.dirs) p.algBytes += ((uint64_t)(pd.m + 1) * (uint64_t)(pd.n + 1) + 1) / 2; /* half a byte per cell */
+        else if (p.bandScores) {}                                                        /* DPX_LONG_SCORES: nothing but the results */
         else if (p.bandDirs) p.algBytes += p.twoPiece ? inband : (inband + 1) / 2;        /* half a byte per in-band cell, two-piece: a byte */
         else if (p.store && banded) p.algBytes += 2ull * (uint64_t)bandPlanes * inband;   /* 2 B per in-band cell and plane */
         else if (p.store) p.algBytes += 2ull * (uint64_t)p.planes * (uint64_t)(pd.m + 1) * (uint64_t)(pd.n + 1);
@@ -660,8 +662,16 @@ int dpx_plan_batch(const dpx_params &params, const dpx_seq_pair *pairs, size_t f
         if (!(flags & DPX_KEEP_BAND_DIRECTIONS)) return DPX_ERR_INVALID;
         if (params.algo != DPX_ALGO_BANW && params.algo != DPX_ALGO_BAXT) return DPX_ERR_UNSUPPORTED;
     }
+    if (flags & DPX_LONG_SCORES) { /* legal only together with exactly one of the two band-direction storage flags, whose own checks came first */
+        const bool global = (flags & DPX_KEEP_BAND_DIRECTIONS) != 0, local = (flags & DPX_KEEP_LOCAL_BAND_DIRECTIONS) != 0;
+        if (global == local || (flags & DPX_SCORE_ONLY)) return DPX_ERR_INVALID;
+        if (flags & DPX_KEEP_DIRECTIONS) return DPX_ERR_UNSUPPORTED; /* 0x8 on a banded algorithm stays refused */
+        if (global ? (params.algo != DPX_ALGO_BANW && params.algo != DPX_ALGO_BAXT) : (params.algo != DPX_ALGO_BSW && params.algo != DPX_ALGO_BASW)) return DPX_ERR_UNSUPPORTED;
+        if (flags & (DPX_TWO_PIECE_GAPS | DPX_LOCAL_TWO_PIECE_GAPS)) return DPX_ERR_UNSUPPORTED; /* the two-piece steps are not built for the scoring pass */
+    }
     p.prm = params; p.flags = flags; p.numPairs = numPairs; p.packed2 = packed2Input;
-    p.store = !(flags & DPX_SCORE_ONLY); p.planes = is_affine(params.algo) ? 3 : 1;
+    p.bandScores = (flags & DPX_LONG_SCORES) != 0;
+    p.store = !(flags & DPX_SCORE_ONLY) && !p.bandScores; p.planes = is_affine(params.algo) ? 3 : 1;
     Shape sh; int baseR = 0;
     int rc = validate_pairs(numPairs ? pairs + firstPair : pairs, numBytes, p, sh, err);
     if (rc == DPX_OK) rc = choose_kernel(kn, p, baseR);
@@ -702,6 +712,8 @@ dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus,
     if (p.dirs) {
         r.dirs = true; r.kernel = dir[family];
         r.dirTable = substAlphabet != 0 && family != 0; /* (set only by dpx_batch_set_direction_table, on a DPX_KEEP_DIRECTIONS batch of the three) */
+    } else if (p.bandScores) { /* (DPX_LONG_SCORES: one kernel per unit in every mode the admitted setters bring; no walk, no export) */
+        r.main = p.bandLocal ? DPX_MAIN_LSCORE : DPX_MAIN_BSCORE; r.kernel = p.bandLocal ? DPX_K_LSCORE_FILL : DPX_K_BSCORE_FILL;
     } else if (p.bandLocal) { /* (a table comes through dpx_batch_set_local_direction_table only; every other setter refuses these batches) */
         if (p.twoPiece) { r.main = DPX_MAIN_LB2; r.kernel = DPX_K_LB2_FILL; } /* (DPX_LOCAL_TWO_PIECE_GAPS: one kernel with and without a table) */
         else { r.main = substAlphabet ? DPX_MAIN_BDLT : DPX_MAIN_BDL; r.kernel = substAlphabet ? DPX_K_BDLT_FILL : DPX_K_BDL_FILL; }
@@ -731,7 +743,7 @@ dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus,
                    : family ? (p.lanePacked ? lanes[family] : fill[family])
                    : p.packed ? DPX_K_LINEAR_FILL_PK : p.lanesPk ? DPX_K_LINEAR_LANES_PK : p.lanePacked ? DPX_K_LINEAR_LANES : p.split ? DPX_K_LINEAR_SPLIT : DPX_K_LINEAR_FILL;
     }
-    r.extRecords = r.main == DPX_MAIN_ZEXT || r.main == DPX_MAIN_ZSUB || ((r.main == DPX_MAIN_BDX || r.main == DPX_MAIN_BD2) && extension);
+    r.extRecords = r.main == DPX_MAIN_ZEXT || r.main == DPX_MAIN_ZSUB || ((r.main == DPX_MAIN_BDX || r.main == DPX_MAIN_BD2 || r.main == DPX_MAIN_BSCORE) && extension);
     r.walk = p.bandLocal ? (p.twoPiece ? DPX_WALK_LB2 : DPX_WALK_BDL) : p.twoPiece ? DPX_WALK_BD2 : p.bandDirs ? DPX_WALK_BDIR : (substAlphabet && !p.dirs && !r.scoreTable) ? DPX_WALK_SUBST : algo == DPX_ALGO_BASW ? DPX_WALK_BASW : is_banw_layout(algo) ? DPX_WALK_BANW
              : p.dirs ? DPX_WALK_DIR : DPX_WALK_PLAIN;
     r.walkMode = (r.walk == DPX_WALK_BDL || r.walk == DPX_WALK_LB2 || r.walk == DPX_WALK_BD2 || r.walk == DPX_WALK_BDIR || r.walk == DPX_WALK_DIR) ? 0 : walk_mode(p, tbWalk); /* (one walk: DPX_TB_WALK has no effect) */
@@ -778,6 +790,8 @@ const char *dpx_route_kernel_name(dpx_fill_kernel k) {
      * dpx_batch_set_local_direction_table brings is named here, its layout case is in tests/test_gpu_bdlt.py) */
     if (k == DPX_K_BDLT_FILL) return "k_bdlt_fill";
     if (k == DPX_K_LB2_FILL) return "k_lb2_fill"; /* (DPX_LOCAL_TWO_PIECE_GAPS; its layout cases are in tests/test_gpu_lb2.py) */
+    if (k == DPX_K_BSCORE_FILL) return "k_bscore_fill"; /* (DPX_LONG_SCORES; their layout cases are in tests/test_gpu_bscore.py) */
+    if (k == DPX_K_LSCORE_FILL) return "k_lscore_fill";
     static const char *const names[DPX_K_COUNT] = {
         "k_linear_fill", "k_linear_fill_pk", "k_linear_lanes", "k_linear_lanes_pk", "k_linear_split",
         "k_affine_fill", "k_asw_fill", "k_asg_fill", "k_affine_lanes", "k_asw_lanes", "k_asg_lanes",
@@ -815,12 +829,12 @@ int dpx_plan_describe(const dpx_plan &b, int tbWalk, int zdrop, int endBonus, in
                        name(b.prm.algo), name(b.kernelAlgo), dpx_route_kernel_name(r.kernel), (b.packed || b.lanesPk) ? "int16" : "int32", b.R, b.store ? 1 : 0, b.nCouples, b.nLanePairs,
                        b.nWaves, b.nSingles, (int)b.pkArgs.rowTags, b.packed2 ? "packed2" : "bytes",
                        b.dirs ? (r.dirTable ? dpx_plan_dirtab_waves(b) : b.dirArgs.wavesPerBlock) : (b.packed || b.lanePacked) ? b.pkArgs.wavesPerBlock : b.split ? (unsigned)b.splitWaves : b.bandDirs ? dpx_plan_bdx_waves(b, substAlphabet != 0) : r.scoreTable ? dpx_plan_scoretab_waves(b) : b.args.wavesPerBlock);
-    if ((is_banded_affine(b.kernelAlgo) || b.bandLocal) && len > 0 && (size_t)len < cap) /* which walk the batch's traceback takes */
+    if ((is_banded_affine(b.kernelAlgo) || b.bandLocal) && !b.bandScores && len > 0 && (size_t)len < cap) /* which walk the batch's traceback takes (DPX_LONG_SCORES: none) */
         len += snprintf(buf + len, cap - (size_t)len, " traceback=%s", dpx_route_walk_name(r.walk, r.walkMode));
     if (extension && len > 0 && (size_t)len < cap)
         len += snprintf(buf + len, cap - (size_t)len, " zdrop=%d end_bonus=%d", (int)zdrop, (int)endBonus);
     if (substAlphabet && len > 0 && (size_t)len < cap) len += snprintf(buf + len, cap - (size_t)len, " subst=%d", substAlphabet);
-    if (b.bandDirs && len > 0 && (size_t)len < cap) len += snprintf(buf + len, cap - (size_t)len, b.twoPiece ? " matrix=banddir8" : " matrix=banddir4");
+    if (b.bandDirs && !b.bandScores && len > 0 && (size_t)len < cap) len += snprintf(buf + len, cap - (size_t)len, b.twoPiece ? " matrix=banddir8" : " matrix=banddir4");
     if (b.twoPiece && len > 0 && (size_t)len < cap) len += snprintf(buf + len, cap - (size_t)len, " gap2=%d,%d", (int)b.gapOpen2, (int)b.gapExtend2);
     if (b.dirs && len > 0 && (size_t)len < cap) /* the code layout, and where the edge rows live */
         len += snprintf(buf + len, cap - (size_t)len, " matrix=dir4 dir_edges=%s dir_scratch_bytes=%zu", b.dirScratch ? "global" : "lds", b.dirScratch);

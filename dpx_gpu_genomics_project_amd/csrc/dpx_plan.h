@@ -53,6 +53,9 @@ struct dpx_plan {
                               (dpx_batch_set_local_direction_table) the fill is k_bdlt_fill, walk and export stay */
     bool twoPiece = false; /* ... with DPX_TWO_PIECE_GAPS: 8-bit codes in dpx_banddir2.h's layout, k_bd2_fill; every band <= 256 runs the band kernel.
                               On a bandLocal plan (DPX_LOCAL_TWO_PIECE_GAPS, BASW): the same codes and layout, k_lb2_fill / k_lb2_traceback / k_lb2_export */
+    bool bandScores = false; /* DPX_LONG_SCORES on a bandDirs (0x10) or bandLocal (0x40) plan: that plan's geometry -- C, parity, ldsPerWave, ldsRefOff, waves
+                              per workgroup, the range check against 2^28 -- with store = false: no pool, no line offsets, k_bscore_fill / k_lscore_fill.
+                              Every band <= 512 runs the band kernel, covering or not */
     int32_t gapOpen2 = 0, gapExtend2 = 0; /* twoPiece: the second gap piece (dpx_batch_set_second_gap; piece 1 until then) */
     bool packed = false;     /* LNW / LSW / BSW with matrices: couples of equal-shaped pairs, two per wave + leftover singles */
     bool split = false;      /* small batch: one workgroup per pair, one wave per stripe (k_linear_split) */
@@ -102,6 +105,12 @@ enum dpx_main_launch { DPX_MAIN_NONE, DPX_MAIN_FILL, DPX_MAIN_BASW, DPX_MAIN_BAN
  * dpx_route_kernel_name's table of create-time kernels.  Both values lie inside the enums' ranges (5 and 4 bits). */
 constexpr dpx_fill_kernel DPX_K_LB2_FILL = static_cast<dpx_fill_kernel>(DPX_K_COUNT + 1);
 constexpr dpx_main_launch DPX_MAIN_LB2 = static_cast<dpx_main_launch>(DPX_MAIN_BDLT + 1);
+/* DPX_LONG_SCORES (dpx_bscore_kernels.hip, dpx_lscore_kernels.hip): appended the same way, behind the values above (31 and 15: still
+ * inside the ranges) */
+constexpr dpx_fill_kernel DPX_K_BSCORE_FILL = static_cast<dpx_fill_kernel>(DPX_K_COUNT + 2);
+constexpr dpx_fill_kernel DPX_K_LSCORE_FILL = static_cast<dpx_fill_kernel>(DPX_K_COUNT + 3);
+constexpr dpx_main_launch DPX_MAIN_BSCORE = static_cast<dpx_main_launch>(DPX_MAIN_BDLT + 2);
+constexpr dpx_main_launch DPX_MAIN_LSCORE = static_cast<dpx_main_launch>(DPX_MAIN_BDLT + 3);
 enum dpx_second_launch { DPX_SECOND_NONE, DPX_SECOND_PACKED, DPX_SECOND_BANDED_PACKED, DPX_SECOND_LANES, DPX_SECOND_LANES_PK };
 enum dpx_walk_family { DPX_WALK_PLAIN, DPX_WALK_DIR, DPX_WALK_BASW, DPX_WALK_BANW, DPX_WALK_SUBST, DPX_WALK_BDIR, DPX_WALK_BD2, DPX_WALK_BDL, DPX_WALK_LB2 };
 enum dpx_export_kind { DPX_EXPORT_PLAIN, DPX_EXPORT_BASW, DPX_EXPORT_BANW };
@@ -128,7 +137,8 @@ struct dpx_route {
  * (dpx_batch_set_direction_table) sets dirTable and nothing else; on a score-only plan of the three (dpx_batch_set_score_table) it sets
  * scoreTable and nothing else.  A twoPiece plan runs k_bd2_fill and k_bd2_traceback in every mode (bandLocal as well: k_lb2_fill and
  * k_lb2_traceback, with or without the alphabet); its second piece is
- * the plan's own (the batch IS the plan), so the signatures here do not know it. */
+ * the plan's own (the batch IS the plan), so the signatures here do not know it.  A bandScores plan (DPX_LONG_SCORES) runs k_bscore_fill
+ * (0x10) or k_lscore_fill (0x40) in every mode its setters bring; it has no walk and no export. */
 dpx_route dpx_plan_route(const dpx_plan &p, int tbWalk, int zdrop, int endBonus, int substAlphabet);
 /* Waves per workgroup of a bandDirs plan's fill: the plan's own without a table; with one (DPX_SUBST_IMAGE_BYTES more per wave) the
  * plan's own when four waves' strings and images fit one workgroup's LDS, else 1, and 0 when not even one wave's fit (the setter

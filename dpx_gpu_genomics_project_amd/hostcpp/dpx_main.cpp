@@ -13,7 +13,7 @@
 // cs:Z:<text> under -cs, the strings built on the device (dpx_batch_diffs_begin / _end).
 //
 //   dpx_main -pairs <file> [-match 3] [-mismatch -1] [-open -2 | -gap -2] [-extend -1]
-//            [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band 128] [-batch N | -pool-gb 4] [-inflight K] [-tune 0|1] [-device 0] [-noprint] [-pack2] [-directions] [-cigar [M] [-md] [-cs]] [-zdrop Z] [-endbonus E] [-matrix FILE] [-localmatrix FILE] [-open2 O2 -extend2 E2] [-localopen2 O2 -localextend2 E2] [-reverse] [-producer P] [-rank r -world w]
+//            [-algo LSW|LNW|ANW|BSW|ASW|BASW|ASG|BANW|BAXT] [-band 128] [-batch N | -pool-gb 4] [-inflight K] [-tune 0|1] [-device 0] [-noprint] [-pack2] [-directions] [-cigar [M] [-md] [-cs]] [-zdrop Z] [-endbonus E] [-matrix FILE] [-localmatrix FILE] [-open2 O2 -extend2 E2] [-localopen2 O2 -localextend2 E2] [-reverse] [-longscores] [-producer P] [-rank r -world w]
 //
 // -matrix FILE (BANW / BAXT, not with -zdrop / -endbonus): score columns by a substitution matrix (dpx_batch_set_substitution) instead of
 // -match / -mismatch.  NCBI text format: '#' lines are comments; one header row of 1..32 single-character column letters; then one row
@@ -32,6 +32,11 @@
 // dpx_batch_set_score_table (k_scoretab_fill / k_scoretab_lanes) -- the scoring pass of a database search.  Not with -directions, -cigar,
 // -zdrop, -endbonus, -open2 / -extend2 or -reverse, and for the other algorithms not with -matrix.  Without -batch N a -scores run takes
 // batches of 20000 pairs, the cap of the budgeted batches (there is no matrix pool to size them by).
+// -longscores (only with -algo BANW|BAXT|BSW|BASW, which take -band B): the scoring pass of long banded pairs, DPX_LONG_SCORES on the band-direction
+// batch of the algorithm (k_bscore_fill / k_lscore_fill: int32 scores, no pool, no traceback), so pairs run that -scores refuses.  It prints
+// -scores' lines and takes -scores' batch sizing.  With -zdrop / -endbonus / -matrix FILE (BANW / BAXT, through
+// dpx_batch_set_direction_scoring), -localmatrix FILE (BSW / BASW), -reverse and -pack2.  Not with -scores, -directions, -cigar, -open2 /
+// -extend2 or -localopen2 / -localextend2.
 // -open2 O2 -extend2 E2 (both or neither; only with -directions and -algo BANW|BAXT): two-piece affine gaps, a gap of length k scores
 // max(open + k * extend, O2 + k * E2) (DPX_TWO_PIECE_GAPS and dpx_batch_set_second_gap, k_bd2_fill; bands up to 256).  They combine with
 // -zdrop / -endbonus / -matrix through dpx_batch_set_direction_scoring.
@@ -151,6 +156,7 @@ static void usage() {
                     "[-open2 <O2> -extend2 <E2>] (two-piece gaps: both together, only with -directions and -algo BANW|BAXT) "
                     "[-localopen2 <O2> -localextend2 <E2>] (two-piece gaps on local band-direction batches: both together, only with -directions and -algo BASW) "
                     "[-scores] (score-only batches: one line '<number> | <score> | <endRow> <endCol>' per pair; not with -directions / -cigar / -zdrop / -endbonus / -open2 / -extend2 / -reverse; -matrix <file> with it only for -algo ANW|ASW|ASG; batches of 20000 pairs unless -batch says otherwise) "
+                    "[-longscores] (the scoring pass of long banded pairs: -scores' lines from int32 band fills without a pool; only with -algo BANW|BAXT|BSW|BASW, with -zdrop / -endbonus / -matrix <file> (BANW / BAXT), -localmatrix <file> (BSW / BASW), -reverse, -pack2; not with -scores / -directions / -cigar / -open2 / -extend2 / -localopen2 / -localextend2) "
                     "[-reverse] (align every pair right to left on the device, output in the file's orientation; only with -algo BANW|BAXT)\n");
     exit(EXIT_FAILURE);
 }
@@ -173,6 +179,7 @@ int main(int argc, char *argv[]) {
     int gapOpen2 = 0, gapExtend2 = 0;
     bool haveLocalOpen2 = false, haveLocalExtend2 = false; // -localopen2 / -localextend2: the same on BASW's local band-direction batches (DPX_LOCAL_TWO_PIECE_GAPS)
     bool scoresOnly = false; // -scores: score-only batches (DPX_SCORE_ONLY), one "<number> | <score> | <endRow> <endCol>" line per pair from dpx_batch_results
+    bool longScores = false; // -longscores: DPX_LONG_SCORES on the algorithm's band-direction batch, -scores' lines from dpx_batch_results
     bool reverse = false;    // -reverse: every pair of every batch is reversed on the device (dpx_batch_set_reversed)
     const char *matrixFile = nullptr; // -matrix: a substitution table (dpx_batch_set_substitution) on every batch
     const char *localMatrixFile = nullptr; // -localmatrix: a substitution table (dpx_batch_set_local_direction_table) on every BSW / BASW band-direction batch
@@ -213,6 +220,7 @@ int main(int argc, char *argv[]) {
         else if (!strcmp(argv[i], "-localextend2")) { gapExtend2 = atoi(next("-localextend2")); haveLocalExtend2 = true; }
         else if (!strcmp(argv[i], "-reverse")) reverse = true;
         else if (!strcmp(argv[i], "-scores")) scoresOnly = true;
+        else if (!strcmp(argv[i], "-longscores")) longScores = true;
         else if (!strcmp(argv[i], "-producer")) producerFlag = atoi(next("-producer"));
         else if (!strcmp(argv[i], "-inflight")) inflight = atoi(next("-inflight"));
         else if (!strcmp(argv[i], "-tune")) tuneFlag = atoi(next("-tune"));
@@ -235,6 +243,9 @@ int main(int argc, char *argv[]) {
     if (reverse && algo != DPX_ALGO_BANW && algo != DPX_ALGO_BAXT) usage();
     if (diffKinds && !cigar) usage();
     if (scoresOnly && (directions || cigar || zdrop != -1 || endBonus != -1 || twoPiece || localTwoPiece || reverse)) usage();
+    const bool bandedAlgo = algo == DPX_ALGO_BSW || algo == DPX_ALGO_BASW || algo == DPX_ALGO_BANW || algo == DPX_ALGO_BAXT;
+    if (longScores && (scoresOnly || directions || cigar || twoPiece || localTwoPiece || !bandedAlgo)) usage();
+    const bool resultLines = scoresOnly || longScores; // one "<number> | <score> | <endRow> <endCol>" line per pair, no pool, no text
     std::vector<int8_t> substScores;
     int substAlphabet = 0;
     uint8_t substCode[256];
@@ -252,7 +263,7 @@ int main(int argc, char *argv[]) {
         }
     }
     if (localMatrixFile) {
-        if (matrixFile || !directions || (algo != DPX_ALGO_BSW && algo != DPX_ALGO_BASW)) usage();
+        if (matrixFile || !(directions || longScores) || (algo != DPX_ALGO_BSW && algo != DPX_ALGO_BASW)) usage();
         std::string why;
         if (!read_matrix(localMatrixFile, substScores, substAlphabet, substCode, why)) {
             fprintf(stderr, "-localmatrix %s: %s\n", localMatrixFile, why.c_str());
@@ -281,8 +292,8 @@ int main(int argc, char *argv[]) {
     const size_t poolBudget = (size_t)(poolGb * (double)(1ull << 30)) * (threePlanes && !directions ? 3 : 1);
     std::thread reserve;
     // (and pinned text buffers: one being printed, one per batch in flight, two spare)
-    const bool budgetedBatches = batchSize == 0 && !scoresOnly; // (-scores: the batches have no pool and no text)
-    if (batchSize == 0 && scoresOnly) batchSize = 20000; // no pool to budget against: the cap the budgeted batches have below (enough waves for the chip, small enough to pipeline)
+    const bool budgetedBatches = batchSize == 0 && !resultLines; // (-scores / -longscores: the batches have no pool and no text)
+    if (batchSize == 0 && resultLines) batchSize = 20000; // no pool to budget against: the cap the budgeted batches have below (enough waves for the chip, small enough to pipeline)
     if (budgetedBatches) reserve = std::thread([poolBudget, print, inflight]() { (void)dpx_pool_reserve(poolBudget, inflight); if (print) (void)dpx_text_reserve((size_t)16 << 20, inflight + 3); });
 
     printf("Parsing input file: %s\n", pairFileName);
@@ -359,7 +370,7 @@ int main(int argc, char *argv[]) {
         char *text = nullptr;
         size_t bytes = 0;
         std::string lines; // -cigar: the batch's lines, formatted here while the batch (which owns the records and ops) is alive
-        if (print && scoresOnly) { // no device text: the three result arrays, formatted here
+        if (print && resultLines) { // no device text: the three result arrays, formatted here
             std::vector<int32_t> scores(f.count), endRow(f.count), endCol(f.count);
             if ((rc = dpx_batch_results(f.b, scores.data(), endRow.data(), endCol.data())) != DPX_OK) die("RESULTS FAILED", rc);
             char line[96];
@@ -405,7 +416,7 @@ int main(int argc, char *argv[]) {
         double usec = 0;
         if ((rc = dpx_batch_last_fill_usec(f.b, &usec)) != DPX_OK) die("KERNEL TIMING FAILED", rc);
         kernel_time += (uint64_t)usec;
-        if (print && !scoresOnly && dpx_batch_last_output_usec(f.b, &usec) == DPX_OK) traceback_kernel_time += (uint64_t)usec;
+        if (print && !resultLines && dpx_batch_last_output_usec(f.b, &usec) == DPX_OK) traceback_kernel_time += (uint64_t)usec;
         backtracking_time += get_time() - t0;
         t0 = get_time();
         dpx_batch_destroy(f.b);
@@ -413,7 +424,7 @@ int main(int argc, char *argv[]) {
         memalloc_time += get_time() - t0;
         retire_printed();
         printingText = text;
-        if (print && (cigar || scoresOnly)) printer = std::thread([s = std::move(lines)]() { fwrite(s.data(), 1, s.size(), stdout); });
+        if (print && (cigar || resultLines)) printer = std::thread([s = std::move(lines)]() { fwrite(s.data(), 1, s.size(), stdout); });
         else if (print) printer = std::thread([text, bytes]() { fwrite(text, 1, bytes, stdout); });
     };
     size_t shardCells = 0;
@@ -436,9 +447,9 @@ int main(int argc, char *argv[]) {
         next.first = first;
         next.count = std::min(batchSize, shardHi - first);
         const uint64_t t0 = get_time();
-        const bool bandDirections = directions && (algo == DPX_ALGO_BANW || algo == DPX_ALGO_BAXT);
-        const bool localDirections = directions && (algo == DPX_ALGO_BSW || algo == DPX_ALGO_BASW);
-        const unsigned flags = (twoPiece ? DPX_TWO_PIECE_GAPS : localTwoPiece ? DPX_LOCAL_TWO_PIECE_GAPS : 0u) | (bandDirections ? DPX_KEEP_BAND_DIRECTIONS : localDirections ? DPX_KEEP_LOCAL_BAND_DIRECTIONS : directions ? DPX_KEEP_DIRECTIONS : scoresOnly ? DPX_SCORE_ONLY : DPX_KEEP_MATRICES) | DPX_TIME_FILLS | ((tunePools && !scoresOnly && tuned.fetch_add(1) < inflight) ? DPX_TUNE_PLACEMENT : 0u);
+        const bool bandDirections = (directions || longScores) && (algo == DPX_ALGO_BANW || algo == DPX_ALGO_BAXT);
+        const bool localDirections = (directions || longScores) && (algo == DPX_ALGO_BSW || algo == DPX_ALGO_BASW);
+        const unsigned flags = (longScores ? DPX_LONG_SCORES : 0u) | (twoPiece ? DPX_TWO_PIECE_GAPS : localTwoPiece ? DPX_LOCAL_TWO_PIECE_GAPS : 0u) | (bandDirections ? DPX_KEEP_BAND_DIRECTIONS : localDirections ? DPX_KEEP_LOCAL_BAND_DIRECTIONS : directions ? DPX_KEEP_DIRECTIONS : scoresOnly ? DPX_SCORE_ONLY : DPX_KEEP_MATRICES) | DPX_TIME_FILLS | ((tunePools && !resultLines && tuned.fetch_add(1) < inflight) ? DPX_TUNE_PLACEMENT : 0u);
         int prc = pack2 ? dpx_batch_create_packed2(-1, &prm, packed.data(), fileInfo.numBytes, alphabet, reinterpret_cast<const dpx_seq_pair *>(sequenceIdxs),
                                                    first, next.count, flags, &next.b)
                         : dpx_batch_create(&prm, sequences, fileInfo.numBytes, reinterpret_cast<const dpx_seq_pair *>(sequenceIdxs), first, next.count,
@@ -466,7 +477,7 @@ int main(int argc, char *argv[]) {
         create_time += get_time() - t0;
         if ((prc = dpx_batch_fill(next.b, nullptr)) != DPX_OK) die("KERNEL LAUNCH FAILED", prc);
         // global pair numbers: shardFirst + index inside the shard
-        if (print && scoresOnly) { /* (nothing to start: finish reads the results) */ }
+        if (print && resultLines) { /* (nothing to start: finish reads the results) */ }
         else if (print && cigar) { if ((prc = dpx_batch_cigars_begin(next.b, cigarFlags)) != DPX_OK) die("TRACEBACK LAUNCH FAILED", prc);
             if (diffKinds && (prc = dpx_batch_diffs_begin(next.b, diffKinds)) != DPX_OK) die("MD / CS LAUNCH FAILED", prc); }
         else if (print && (prc = dpx_batch_output_begin(next.b, shardFirst + first)) != DPX_OK) die("TRACEBACK LAUNCH FAILED", prc);

@@ -248,6 +248,36 @@ typedef struct dpx_params {
                                     bit and builds an int16 matrix batch -- dpx_batch_describe then shows kernel=k_banded_fill /
                                     k_banded_fill_pk / k_basw_fill (this library: kernel=k_bdl_fill, or k_linear_dir / k_asw_dir under a
                                     covering band) and dpx_batch_directions returns DPX_ERR_NO_MATRIX. */
+#define DPX_LONG_SCORES 0x100u /* BANW / BAXT / BSW / BASW: the scoring pass of long banded pairs.  Legal only together with exactly one of 0x10
+                                    (BANW / BAXT) or 0x40 (BSW / BASW), and means that direction batch with nothing stored but the results: its
+                                    definitions, int32 arithmetic, range check against 2^28, absence of any n or m + n limit and strings staged in
+                                    LDS (one-wave workgroups where four waves' strings do not fit, DPX_ERR_UNSUPPORTED where one wave's do not),
+                                    and no pool (k_bscore_fill on 0x10, k_lscore_fill on 0x40).  "Score everything here, realign the hits on a
+                                    direction batch": pairs the int16 DPX_SCORE_ONLY batch refuses with DPX_ERR_RANGE run.
+                                    Results.  dpx_batch_results and dpx_batch_device_results equal what the same pairs give on the 0x10 / 0x40
+                                    batch without this bit; under z-drop / end bonus dpx_batch_extensions is equal too, the chosen end, lastDiag
+                                    and flags included; wherever the int16 DPX_SCORE_ONLY batch admits the pairs, they equal that batch's.
+                                    No pool.  dpx_batch_info reports matrixBytes == 0; dpx_batch_matrix, dpx_batch_directions,
+                                    dpx_batch_traceback, dpx_batch_output_begin, dpx_batch_cigars_begin and dpx_batch_diffs_begin answer
+                                    DPX_ERR_NO_MATRIX, as on a DPX_SCORE_ONLY batch; DPX_TUNE_PLACEMENT is ignored (there is no pool to shop
+                                    for).  DPX_TIME_FILLS, dpx_batch_fill_timed, repeated fills, a caller's stream, dpx_batch_create_on and
+                                    packed2 input work as for the direction batch.  (dpx_align_batch takes no flags and stays the int16 one-shot.)
+                                    Setters.  On 0x10 | 0x100: dpx_batch_set_direction_scoring (a table on BANW; table, z-drop and end bonus on
+                                    BAXT) and dpx_batch_set_reversed, with their arguments, lifecycle and invalidation rules (the results stay
+                                    in the reversed frame; there are no lines to flip).  On 0x40 | 0x100: dpx_batch_set_local_direction_table.
+                                    Every other setter refuses as it does on the direction batch and leaves the batch as it was.
+                                    Flags.  Without 0x10 / 0x40, with both, or with DPX_SCORE_ONLY: DPX_ERR_INVALID.  With 0x8: the rules for 0x8
+                                    on a banded algorithm win (DPX_ERR_UNSUPPORTED).  With 0x20 or 0x80: DPX_ERR_UNSUPPORTED -- the two-piece
+                                    steps are not built for this pass, so dpx_batch_set_second_gap refuses too.  Wrong algorithm for the storage
+                                    bit: DPX_ERR_UNSUPPORTED, as without this bit.
+                                    Bands.  Band > 512: DPX_ERR_UNSUPPORTED always -- no unbanded int32 score-only kernel exists to fall back on.
+                                    A band up to 512 that covers the matrix runs the band kernel like any other band (BAXT's rule, here for all
+                                    four); BANW keeps its admission rule |m - n| < B.
+                                    dpx_batch_describe shows kernel=k_bscore_fill / k_lscore_fill and store=0, adds ` subst=<alphabet>` under a
+                                    table and ` zdrop=<z> end_bonus=<b>` in extension mode, and names no traceback= and no matrix=.
+                                    Added without an ABI bump or a new symbol.  Detecting it: a library that predates the flag ignores the bit
+                                    and builds the direction batch -- dpx_batch_describe then says kernel=k_bdir_fill / k_bdl_fill and
+                                    dpx_batch_directions succeeds. */
 
 /* matrix selectors for dpx_batch_matrix / dpx_batch_directions */
 #define DPX_MAT_H 0 /* scoring matrix   (reference: memo / scoringMemo)            */
